@@ -4,6 +4,17 @@ gx1 fp64, at 1/2/4/8 GPUs; % of the roofline).
 
   python bench.py --gpus N --steps K --warmup W        (N > 1: under torch.distributed.run, or bare -- it then re-executes
                                                         itself under torch.distributed.run, one rank per GPU, 127.0.0.1)
+  python bench.py ... --full                           everything listed below besides the headline
+  python bench.py ... --dump-outputs DIR               also write what the last timed step computed to DIR/<field>.npy
+
+A plain run (no --full) sets up, warms up, times the K steps and prints the line with the headline and the figures
+derived from that timed region alone (`config`, `roofline` from the committed PMC pass); `verified`, `median_ms_per_step`,
+the per-rank views, the kernel-alone timings, the extra workloads and `cpu_baseline` are --full's.
+
+--dump-outputs DIR: the 18 arrays cice_evp_hip_run hands back (12 stresses, strintxU, strintyU, taubxU, taubyU, uvel,
+vvel) as the state stands after the last timed step, gathered over the ranks to the global interior [ny][nx], fp64, one
+DIR/<name>.npy each.  Where the 18 would exceed 64 MB (3600x2400), every array is sampled at the same cells, a fixed set
+drawn with seed DUMP_SEED.  The inputs are synthetic and seeded: the same arguments give the same inputs in every run.
 
 A "step" is one evp() call's worth of the hot path: ndte subcycles
 (stress + stepu + velocity halo, ice_dyn_evp.F90:859-913) on a resident synthetic
@@ -77,6 +88,8 @@ EXTRAS = ("s01", "streaming", "tripole", "caps", "cgrid", "per_call", "configs2"
 EXTRAS_DEFAULT = {1: ("s01", "streaming", "tripole", "caps", "cgrid", "per_call"), 2: ("s01", "rccl_control")}
 CGRID_B_ALG_ONE = 408.0  # ... 51 in the one-launch kernel (cg_one: the default on one rank without a fold)
 CGRID_B_ALG_ONE_GEO = 289.0  # ... 36 + one mask byte where cg_one derives 15 of its 23 static arrays from the 8 dx / dy arrays
+DUMP_MAX_BYTES = 60 << 20    # --dump-outputs: all arrays together stay under 64 MB
+DUMP_SEED = 20261015         # ... the cells kept when they would not
 
 
 def parse():
@@ -89,12 +102,17 @@ def parse():
     ap.add_argument("--ndte", type=int, default=None)
     ap.add_argument("--fused", action="store_true",
                     help="allow FMA contraction (default: strict fp64, bit-identical to the reference built without FMA)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="besides the headline: checksum verification, the median of single calls, per-rank views, kernel-alone "
+                         "timings, the extra workloads (--extras) and the CPU baseline.  Off: only what the headline needs")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the arrays the last timed step computed to DIR/<name>.npy (fp64, at most 64 MB in all)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="(--full) skip the CPU baseline")
     ap.add_argument("--no-secondary", dest="secondary", action="store_false",
-                    help="skip the extra measurements reported under 'secondary', 'tripole', 'roofline.streaming', 'per_call_ms'")
-    ap.add_argument("--cpu-seconds", type=float, default=12.0, help="target CPU-baseline wall time per code path")
+                    help="(--full) skip the extra measurements reported under 'secondary', 'tripole', 'roofline.streaming', 'per_call_ms'")
+    ap.add_argument("--cpu-seconds", type=float, default=12.0, help="(--full) target CPU-baseline wall time per code path")
     ap.add_argument("--extras", default="auto",
-                    help="comma list of the extra measurements to run, or 'all'.  Default ('auto') at N = 1: s01, streaming, "
+                    help="(--full) comma list of the extra measurements to run, or 'all'.  Default ('auto') at N = 1: s01, streaming, "
                          "tripole, cgrid, per_call; at N > 1: s01 (3600x2400 at ndte = 480, library default) and rccl_control (the "
                          "headline workload forced onto RCCL point-to-point).  By name only, N > 1: configs2 (gx1 at ndte = 240, "
                          "default and forced RCCL), tripole (tx1 over the ranks), ring_variants (s01 again with the ring exchange "
@@ -113,6 +131,22 @@ def state_hash(glob: dict) -> str:
     for k in VERIFY_FIELDS:
         h.update(np.ascontiguousarray(glob[k], dtype="<f8").tobytes())
     return h.hexdigest()
+
+
+def write_dump(where, glob: dict) -> dict:
+    """--dump-outputs: each global array as fp64 <where>/<name>.npy; if all of them together would exceed DUMP_MAX_BYTES,
+    each is cut to the same cells (flat row-major indices drawn without replacement with DUMP_SEED, ascending)."""
+    d = Path(where)
+    d.mkdir(parents=True, exist_ok=True)
+    shape = next(iter(glob.values())).shape
+    n = int(np.prod(shape))
+    keep = DUMP_MAX_BYTES // (8 * len(glob))
+    idx = np.sort(np.random.default_rng(DUMP_SEED).choice(n, size=keep, replace=False)) if n > keep else None
+    for k, v in glob.items():
+        v = np.ascontiguousarray(v, dtype=np.float64)
+        np.save(d / f"{k}.npy", v.reshape(-1)[idx] if idx is not None else v)
+    return dict(dir=str(d), arrays=list(glob), shape=list(shape), dtype="float64",
+                sampled_cells=(int(keep) if idx is not None else None), sample_seed=(DUMP_SEED if idx is not None else None))
 
 
 def golden_key(workload, case, ndte, ns):
@@ -404,9 +438,12 @@ def main():
         dist.all_reduce(t, op=dist.ReduceOp.MIN)
         return bool(int(t.item()))
 
-    def measure(workload, case, ndte, steps, warmup, ns="closed", env=None, verify=True, proc_shape=None, again_env=None, median_calls=0):
+    def measure(workload, case, ndte, steps, warmup, ns="closed", env=None, verify=True, proc_shape=None, again_env=None, median_calls=0,
+                lean=False, keep_last=False):
         """One timed pass: `warmup` untimed + `steps` timed evp() subcycle loops of `workload`,
-        block-decomposed over the ranks; barrier + sync on both sides, MAX over ranks."""
+        block-decomposed over the ranks; barrier + sync on both sides, MAX over ranks.  lean (a plain run's headline): nothing
+        after the timed region but one download; keep_last: return that download (rank's own blocks) as `last`."""
+        verify = verify and not lean
         saved = {k: os.environ.get(k) for k in (env or {})}
         os.environ.update(env or {})
         try:
@@ -511,12 +548,14 @@ def main():
                     dt = float(tt.item())
                 # HIP events on the library's stream around the timed region (rank 0's share)
                 tm_ev = core.timings()
-                kt = core.time_kernels(200)
+                # the state as the last timed step left it (--dump-outputs; the only thing a lean pass does after the timing)
+                last = core.download() if (lean or keep_last) else None
+                kt = None if lean else core.time_kernels(200)
                 # N > 1: every rank's view of the timed region, so that a first run on real xGMI can be read -- its own wall
                 # time, the time its stream spent between the marks, its kernel alone (no exchange: HIP events around
                 # repeated launches on scratch state), which kernel / transport it ended up with, what it sends per exchange
                 per_rank = None
-                if world > 1:
+                if world > 1 and not lean:
                     mi = core.march_info()
                     mine = dict(rank=rank, wall_ms=1e3 * (t1 - t0), stream_ms=float(tm_ev["marks_ms"]),
                                 us_per_subcycle_stream=1e3 * float(tm_ev["marks_ms"]) / (steps * ndte),
@@ -549,13 +588,15 @@ def main():
                 key = golden_key(workload, case, ndte, ns)
                 target = next((n for n in CHECKPOINTS if n >= total and str(n) in golden.get(key, {})), None)
                 ver = dict(verified=None, why="no committed checksum for this configuration", key=key)
-                if not a.strict:
+                if lean:
+                    ver["why"] = "plain run: the state is checked against the committed checksum under --full"
+                elif not a.strict:
                     ver["why"] = "fused mode is not bit-comparable with the oracle (tolerance: DESIGN.md)"
                 elif verify and target is not None:
                     for _ in range(target - total):
                         core.subcycle(ndte)
                     core.sync()
-                out = core.download()
+                out = last if lean else core.download()
                 fallbacks = core.timings()["resident_fallbacks"]
                 # the same ranks, state and communicator once more under switches the library reads at every call
                 # (again_env): one untimed + `steps` timed loops continuing from where the verified run ended
@@ -601,6 +642,7 @@ def main():
                 core.finalize()
             return dict(nx=nx, ny=ny, ndte=ndte, dc=dc, tm=tm, n_active=n_active, dt=dt, tm_ev=tm_ev, kt=kt, per_rank=per_rank,
                         steps=steps, warmup=warmup, ver=ver, fallbacks=fallbacks, again=again, each_ms=each_ms,
+                        last=(last if keep_last else None),
                         finite=bool(np.isfinite(out["uvel"]).all() and np.isfinite(out["stressp_1"]).all()),
                         umax=float(np.abs(out["uvel"]).max()))
         finally:
@@ -920,13 +962,24 @@ def main():
         return res
 
     ndte = a.ndte or {"gx3": 120, "gx1": 120, "s01": 480}[a.workload]
-    M = measure_with_fallbacks(a.workload, a.case, ndte, a.steps, a.warmup, median_calls=(10 if (a.gpus == 1 and a.workload != "s01") else 0))
+    M = measure_with_fallbacks(a.workload, a.case, ndte, a.steps, a.warmup,
+                               median_calls=(10 if (a.full and a.gpus == 1 and a.workload != "s01") else 0),
+                               lean=not a.full, keep_last=bool(a.dump_outputs))
     nx, ny, dc, tm, n_active, dt, tm_ev, kt = (M[k] for k in ("nx", "ny", "dc", "tm", "n_active", "dt", "tm_ev", "kt"))
+    dumped = None
+    if a.dump_outputs:
+        parts = [M.pop("last")]
+        if world > 1:
+            mine, parts = parts[0], ([None] * world if rank == 0 else None)
+            dist.gather_object(mine, parts, dst=0)
+        if rank == 0:
+            dumped = write_dump(a.dump_outputs, {k: dc.gather({r: parts[r][k] for r in range(world)}) for k in evp.OUTPUTS})
+        del parts
     # extras must never cost the primary line: a failure is reported inside the JSON instead
     M2 = M3 = MS = None
     extra = {}
     extra_err = {}
-    want = (lambda k: a.secondary and k in a.extras)
+    want = (lambda k: a.full and a.secondary and k in a.extras)
 
     def rank_block(Mx, label):
         """One extra workload at N > 1 as the JSON line reports it (rank 0 only uses it)."""
@@ -1077,6 +1130,8 @@ def main():
             if traffic:
                 blk["measured_traffic_GBps"] = traffic / tk / 1e9
                 blk["pmc_source"] = f"{pmc_file}#{pmc_key}"
+            if not a.full:      # (the probe is a run of its own)
+                return blk
             try:      # what a plain streaming kernel of the same array shape (30 in, 16 out) reaches on this box, live
                 ceil = evp.stream_probe(my) / 1e9
                 blk["stream_ceiling"] = {"GBps": ceil, "frac_of_ceiling": alg / tk / 1e9 / ceil,
@@ -1254,10 +1309,12 @@ def main():
                 "resident_tiles_run": Mcaps["tm_ev"].get("resident_tiles_run"), "resident_tiles": Mcaps["tm_ev"].get("resident_tiles"),
                 "verified": Mcaps["ver"].get("verified"), "finite": Mcaps["finite"],
                 "note": "the on-chip resident kernel launches only the tiles that hold ice"}
-        if world == 1 and not a.no_cpu_baseline:
+        if world == 1 and a.full and not a.no_cpu_baseline:
             res["cpu_baseline"] = cpu_baseline(a.workload, a.case, ndte, a.cpu_seconds, a.strict)
         else:
             res["cpu_baseline"] = None
+        res["full"] = a.full
+        res["dump_outputs"] = dumped
         print(json.dumps(res), flush=True)
     if world > 1:
         dist.destroy_process_group()

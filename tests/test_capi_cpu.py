@@ -442,6 +442,31 @@ def test_tracked_pmc_summary_feeds_the_bench_line():
         assert k[key]["per_subcycle"]["hbm_bytes"], key
 
 
+def test_bench_dump_outputs_whole_or_one_seeded_sample(tmp_path, monkeypatch):
+    """bench.py --dump-outputs: every output array as fp64 .npy, whole while all of them fit the byte limit; past it, every
+    array cut to the same cells (ascending, the same set in every run) and the files together under the limit."""
+    import bench
+    shape = (24, 30)
+    glob = {k: np.arange(shape[0] * shape[1], dtype=np.float64).reshape(shape) + 1e6 * i for i, k in enumerate(evp.OUTPUTS)}
+    info = bench.write_dump(tmp_path / "whole", glob)
+    assert info["sampled_cells"] is None and info["arrays"] == evp.OUTPUTS
+    for k, v in glob.items():
+        got = np.load(tmp_path / "whole" / f"{k}.npy")
+        assert got.dtype == np.float64 and bits_equal(got, v)
+    limit = 8 * len(glob) * 100
+    monkeypatch.setattr(bench, "DUMP_MAX_BYTES", limit)
+    cut = [bench.write_dump(tmp_path / f"cut{r}", glob) for r in range(2)]
+    assert cut[0] == {**cut[1], "dir": cut[0]["dir"]} and cut[0]["sampled_cells"] == 100
+    cells = None
+    for i, k in enumerate(evp.OUTPUTS):
+        a, b = (np.load(tmp_path / f"cut{r}" / f"{k}.npy") for r in range(2))
+        assert a.dtype == np.float64 and bits_equal(a, b)
+        idx = a - 1e6 * i
+        cells = idx if cells is None else cells
+        assert bits_equal(idx, cells) and np.all(np.diff(idx) > 0)
+    assert sum(a.stat().st_size - 128 for a in (tmp_path / "cut0").glob("*.npy")) <= limit
+
+
 @pytest.mark.parametrize("nx,ny,bx,by,ew,ns", [
     (54, 26, 27, 26, "cyclic", "closed"), (40, 27, 40, 27, "cyclic", "closed"),      # the round-5 advisor's two: 8 and 7 one-way before
     (320, 384, 320, 384, "cyclic", "closed"), (100, 116, 50, 58, "cyclic", "closed"), (72, 40, 36, 20, "cyclic", "tripole"),

@@ -118,7 +118,7 @@ def test_bench_multi_rank_falls_back_together():
     root = Path(__file__).resolve().parents[1]
     cmd = [_sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node=2",
            "--master-addr", "127.0.0.1", "--master-port", str(_free_port()), str(root / "bench.py"),
-           "--gpus", "2", "--steps", "2", "--warmup", "1", "--workload", "gx3", "--no-secondary"]
+           "--gpus", "2", "--steps", "2", "--warmup", "1", "--workload", "gx3", "--full", "--no-secondary"]
     env = dict(os.environ, CICE_EVP_BENCH_REHEARSAL="1", CICE_EVP_HIP_HALO_TIMEOUT_MS="3000", CICE_EVP_HIP_RES_DEBUG="16")
     r = subprocess.run(cmd, capture_output=True, text=True, timeout=600, env=env)
     lines = [ln for ln in r.stdout.splitlines() if ln.startswith('{"metric"')]
@@ -130,7 +130,8 @@ def test_bench_multi_rank_falls_back_together():
 
 
 def test_bench_self_launches_when_started_bare():
-    """The literal command the driver may type, no launcher around it: `python bench.py --gpus 2 --steps 2 --warmup 1`.  bench.py
+    """The command the driver may type, no launcher around it: `python bench.py --gpus 2 --steps 2 --warmup 1` (with --full, whose
+    extras are asserted below).  bench.py
     re-executes itself under torch.distributed.run (one rank per GPU; here both ranks on the one GPU, CICE_EVP_BENCH_REHEARSAL=1)
     and rank 0 prints exactly one JSON line: the gx1 N-rank figure on top, the 3600x2400 grid under `secondary` with the ranks'
     own views, the forced-RCCL control named (it cannot run with two ranks on one device), no CPU-baseline leg."""
@@ -140,7 +141,7 @@ def test_bench_self_launches_when_started_bare():
     root = Path(__file__).resolve().parents[1]
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT")}
     env.update(CICE_EVP_BENCH_REHEARSAL="1", CICE_EVP_HIP_HALO_TIMEOUT_MS="20000")
-    r = subprocess.run([_sys.executable, "bench.py", "--gpus", "2", "--steps", "2", "--warmup", "1"], cwd=root,
+    r = subprocess.run([_sys.executable, "bench.py", "--gpus", "2", "--steps", "2", "--warmup", "1", "--full"], cwd=root,
                        capture_output=True, text=True, timeout=1500, env=env)
     lines = [ln for ln in r.stdout.splitlines() if ln.startswith('{"metric"')]
     assert r.returncode == 0 and len(lines) == 1, (r.stdout[-1500:], r.stderr[-3000:])
@@ -167,7 +168,7 @@ def test_bench_multi_rank_rehearsal():
     root = Path(__file__).resolve().parents[1]
     cmd = [_sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node=2",
            "--master-addr", "127.0.0.1", "--master-port", str(_free_port()), str(root / "bench.py"),
-           "--gpus", "2", "--steps", "3", "--warmup", "1", "--workload", "gx1", "--extras", "configs2,tripole,s01" + (",ring_variants" if FULL_SUITE else "")]
+           "--gpus", "2", "--steps", "3", "--warmup", "1", "--workload", "gx1", "--full", "--extras", "configs2,tripole,s01" + (",ring_variants" if FULL_SUITE else "")]
     env = dict(os.environ, CICE_EVP_BENCH_REHEARSAL="1", CICE_EVP_HIP_HALO_TIMEOUT_MS="20000")
     r = subprocess.run(cmd, capture_output=True, text=True, timeout=1500, env=env)
     lines = [ln for ln in r.stdout.splitlines() if ln.startswith('{"metric"')]
