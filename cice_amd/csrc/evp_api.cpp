@@ -112,6 +112,30 @@ int cice_evp_hip_cgrid_strip_plan(const cice_evp_hip_dims *dims, int32_t ex, int
     }
     return 0;
 }
+int cice_evp_hip_cgrid_strip_zones(const cice_evp_hip_dims *dims, int32_t ex, int32_t ey, int32_t *n_zones, int32_t *zones10, int32_t zones_cap)
+{
+    if (!dims || !n_zones) return fail(-1, "bad argument");
+    HaloPlan P;
+    if (!build_halo_plan(*dims, P)) return fail(-3, "halo plan: %s", P.error.c_str());
+    std::vector<int32_t> t4, tb;
+    build_window_table(*dims, P, ex, ey, 1 << 20, t4, tb);
+    std::vector<int> img((size_t)dims->nblocks * dims->nx_block * dims->ny_block, -1);
+    for (size_t k = 0; k < P.local_src.size(); ++k)
+        if (P.local_src[k] >= 0) img[(size_t)P.local_src[k]] = 0;
+    std::vector<StripZone> zones;
+    strip_zones(*dims, t4, ex, ey, img.data(), zones);
+    *n_zones = (int32_t)zones.size();
+    if (!zones10) return 0;
+    if ((size_t)zones_cap < zones.size()) return fail(-1, "room for %d rectangles, there are %d", zones_cap, *n_zones);
+    for (size_t k = 0; k < zones.size(); ++k) {
+        const StripZone &z = zones[k];
+        StripRange r;
+        const bool ok = strip_len_range(z, ex, ey, dims->nx_block, dims->ny_block, r);
+        const int32_t v[10] = {z.b, z.i0, z.i1, z.j0, z.j1, ok ? 1 : 0, r.i0, r.i1, r.j0, r.j1};
+        std::copy(v, v + 10, zones10 + 10 * k);
+    }
+    return 0;
+}
 #endif  // CICE_EVP_HIP_TESTING
 
 int cice_evp_hip_stream_probe(int64_t ncells, double *bytes_per_second)

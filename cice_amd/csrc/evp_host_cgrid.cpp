@@ -574,11 +574,11 @@ static int build_one_tables(const double *const *static23)
             const double *const *g = static23;
             const int nxb = d.nx_block, nyb = d.ny_block;
             auto holds = [&](const Zone &z) {
-                const int ia = std::max(2, z.i0 - 3), ib = std::min(nxb - 1, z.i1 + sx - 1 + 2);
-                const int ja = std::max(2, z.j0 - 2), jb = std::min(nyb - 1, z.j1 + sy - 1 + 2);
+                StripRange r;                              // (halo_plan.h: every cell the kernel forms a length for, or false)
+                if (!strip_len_range(z, EX, EY, nxb, nyb, r)) return false;
                 const double *N = g[CG_DXN], *E = g[CG_DYE];
-                for (int j = ja; j <= jb; ++j)
-                    for (int i = ia; i <= ib; ++i) {
+                for (int j = r.j0; j <= r.j1; ++j)
+                    for (int i = r.i0; i <= r.i1; ++i) {
                         const size_t p0 = (size_t)z.b * nxb * nyb + (size_t)(j - 1) * nxb + (i - 1);
                         if (!(same(g[CG_DXU][p0], 0.5 * (N[p0] + N[p0 + 1])) && same(g[CG_DXT][p0], 0.5 * (N[p0] + N[p0 - nxb])) &&
                               same(g[CG_DXE][p0], 0.25 * (N[p0] + N[p0 + 1] + N[p0 - nxb] + N[p0 - nxb + 1])) &&

@@ -726,6 +726,25 @@ void strip_zones(const cice_evp_hip_dims &d, const std::vector<int32_t> &tiles, 
             }
         if (!cnt || (i1 - i0) % sx || (j1 - j0) % sy) continue;
         if (cnt != ((i1 - i0) / sx + 1) * ((j1 - j0) / sy + 1)) continue;       // (not a rectangle: cg_one keeps the block)
+        // (the kernel's loads inside the array: a rectangle whose last owned row is jhi - 1 would prefetch row ny_block + 1)
+        while (j1 >= j0 && i1 + sx - i0 >= 62) {
+            StripRange r{1 << 30, -(1 << 30), 1 << 30, -(1 << 30)};
+            std::vector<int32_t> it;
+            const std::vector<StripZone> one{StripZone{b, i0, i1, j0, j1}};
+            for (int lo0 = 2; lo0 <= 3; ++lo0) {
+                strip_items(one, ex, ey, lo0, 1, 1, j1 - j0 + sy, it);
+                for (size_t k = 0; k < it.size(); k += 6) {
+                    const StripRange f = strip_footprint(&it[k], lo0 == 3);
+                    r = StripRange{std::min(r.i0, f.i0), std::max(r.i1, f.i1), std::min(r.j0, f.j0), std::max(r.j1, f.j1)};
+                }
+            }
+            if (r.j1 > d.ny_block) j1 -= sy;
+            else if (r.j0 < 1) j0 += sy;
+            else if (r.i1 > d.nx_block) i1 -= sx;
+            else if (r.i0 < 1) i0 += sx;
+            else break;
+        }
+        if (j1 < j0) continue;
         if (i1 + sx - i0 < 62) continue;                                          // (narrower than a strip)
         // (cells with ghost images -- the block's outermost interior cells -- never lie inside: the marched kernel has no pushes)
         bool images = false;
@@ -763,6 +782,15 @@ int strip_items(const std::vector<StripZone> &zones, int ex, int ey, int lo0, lo
         }
     }
     return seg;
+}
+
+bool strip_len_range(const StripZone &z, int ex, int ey, int nx_block, int ny_block, StripRange &r)
+{
+    // (strip_items with lo0 = 3: the first strip's lane 2 on column i0 - 1, the last strip's lane 61 on the last owned column)
+    const int sx = ex - 3, sy = ey - 3;
+    r = StripRange{z.i0 - 3, z.i1 + sx - 1 + 2, z.j0 - 2, z.j1 + sy - 1 + 2};
+    // (dxE reads HTN at i + 1 and j - 1, dyN HTE at i - 1 and j + 1, dxT HTN at j - 1, dyT HTE at i - 1 ...)
+    return r.i0 >= 2 && r.i1 <= nx_block - 1 && r.j0 >= 2 && r.j1 <= ny_block - 1;
 }
 
 void strip_windows(const std::vector<StripZone> &zones, const std::vector<int32_t> &tiles, std::vector<uint8_t> &in_zone)

@@ -167,9 +167,29 @@ inline bool cgres_in_reach(int ex, int ey, int last_ex, int last_ey, bool foldwi
 // A rectangle of a block that the regular windows of a window table cover (regular: every position an interior cell of the block,
 // its own source): first owned column / row of its first and last window column / row.
 struct StripZone { int b, i0, i1, j0, j1; };
+// A range of cells of one block's array, 1-based, both ends included.
+struct StripRange { int i0, i1, j0, j1; };
+// What cg_strip reads for the work item (b, c, ja, jb, lo, hi) -- every load of the kernel, counted from its loop: lanes 0 .. 63 hold
+// columns c - 2 .. c + 61 and load unconditionally (lane 63 only loads).  The iterations run j = j0 .. jb + 1, j0 = ja - 4 (LEN:
+// ja - 5, one earlier, so that dxE of row ja - 2 finds HTN of row ja - 3); each loads row j + 2 ahead (uE, dxE or HTN, dyE, the
+// land and ice masks -- the last iteration's too, which nothing uses), row j + 1 (vN, the other lengths, stresses, strength) and
+// row j - 1 (the momentum step's operands).  Rows ja - 5 .. jb + 3 (LEN: ja - 6 .. jb + 3).  The lane-shifted HTN / HTE of LEN are
+// register moves between these lanes, no further loads.
+inline StripRange strip_footprint(const int32_t *item, bool len)
+{
+    return StripRange{item[1] - 2, item[1] + 61, item[2] - (len ? 6 : 5), item[3] + 3};
+}
 // per block the rectangle of its regular windows, if they form one, it is at least a strip wide and none of its cells has a ghost
-// image (img_slot: per cell, < 0 = none; may be null)
+// image (img_slot: per cell, < 0 = none; may be null).  Window rows come off its top (then its bottom), window columns off its east
+// (then its west) side until the footprint of every item strip_items can make of it -- with the lengths formed or loaded -- lies
+// inside the block's array: the windows taken off stay with cg_one.
 void strip_zones(const cice_evp_hip_dims &d, const std::vector<int32_t> &tiles, int ex, int ey, const int *img_slot, std::vector<StripZone> &zones);
+// The cells on which the host checks, bit for bit, that the six lengths cg_strip<LEN> would form equal the loaded ones.  The kernel
+// forms dxT, dyT, dxU, dyU, dxE, dyN from HTN and HTE on columns c - 2 .. c + 61 (every lane) and rows ja - 2 .. jb + 2 of an item
+// (dxE of row jb + 2 enters the shear of row jb + 1, which the stresses of row jb + 1 and so the owned row jb use); r is the
+// rectangle all items of z (lo0 = 3) form lengths on.  False if that reaches a cell whose formula needs a neighbour outside the
+// block's array (the outermost row or column): such a rectangle cannot be verified, LEN is refused for it.
+bool strip_len_range(const StripZone &z, int ex, int ey, int nx_block, int ny_block, StripRange &r);
 // work items of the rectangles, x 6 ints each: block, column of lane 2, first and last owned row, first and last owned lane.  lo0: first lane
 // that may own a column (2; 3 where the kernel forms the lengths), the last is 61; strips of 62 - lo0 columns, the last one shifted west
 // so that lane 62 stays inside the rectangle + 1; segments of `seg` rows (0: the fewest rows >= seg_min with at most `slots` items).

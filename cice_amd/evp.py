@@ -53,7 +53,7 @@ EXPORTS = [
 # libcice_evp_hip_testing.so only (include/cice_evp_hip_testing.h): plan introspection of the CPU tests, read-outs of the tools,
 # the test transport
 TEST_EXPORTS = [
-    "cice_evp_hip_cgrid_fold_plan", "cice_evp_hip_cgrid_window_plan", "cice_evp_hip_cgrid_window_plan_ext", "cice_evp_hip_cgrid_window_deps", "cice_evp_hip_cgrid_strip_plan", "cice_evp_hip_set_test_transport", "cice_evp_hip_march_plan",
+    "cice_evp_hip_cgrid_fold_plan", "cice_evp_hip_cgrid_window_plan", "cice_evp_hip_cgrid_window_plan_ext", "cice_evp_hip_cgrid_window_deps", "cice_evp_hip_cgrid_strip_plan", "cice_evp_hip_cgrid_strip_zones", "cice_evp_hip_set_test_transport", "cice_evp_hip_march_plan",
     "cice_evp_hip_debug_cuload", "cice_evp_hip_debug_prof", "cice_evp_hip_debug_cgrid_prof", "cice_evp_hip_debug_cgres_prof", "cice_evp_hip_plan_build", "cice_evp_hip_halo_plan", "cice_evp_hip_seam_plan",
     "cice_evp_hip_peer_plan", "cice_evp_hip_peer_signs", "cice_evp_hip_center_plan", "cice_evp_hip_stress_plan",
     "cice_evp_hip_fold_split_plan", "cice_evp_hip_plan_flags", "cice_evp_hip_fold_images_plan",
@@ -259,6 +259,18 @@ def cgrid_strip_plan(dims: "Dims", ex=32, ey=8, lo0=3, slots=2048, seg_min=8, se
     _check(lib, lib.cice_evp_hip_cgrid_strip_plan(*a, C.byref(ni), _ip(items), C.c_int32(len(items)), C.byref(nw), _ip(tiles),
                                                   inz.ctypes.data_as(C.POINTER(C.c_uint8)), C.c_int32(len(tiles)), C.byref(sr)), "(cgrid_strip_plan)")
     return dict(items=items[:ni.value], tiles=tiles[:nw.value], in_zone=inz[:nw.value].astype(bool), segment_rows=sr.value)
+
+
+def cgrid_strip_zones(dims: "Dims", ex=32, ey=8) -> list:
+    """Host only: the rectangles the marched C-grid kernel's items are cut from, and the cells the host verifies the lengths on
+    before the kernel may form them (see the testing header)."""
+    lib = load_library(testing=True)
+    n = C.c_int32(0)
+    _check(lib, lib.cice_evp_hip_cgrid_strip_zones(C.byref(dims), C.c_int32(ex), C.c_int32(ey), C.byref(n), None, C.c_int32(0)), "(cgrid_strip_zones)")
+    z = np.zeros((max(n.value, 1), 10), dtype=np.int32)
+    _check(lib, lib.cice_evp_hip_cgrid_strip_zones(C.byref(dims), C.c_int32(ex), C.c_int32(ey), C.byref(n), _ip(z), C.c_int32(len(z))), "(cgrid_strip_zones)")
+    return [dict(block=int(v[0]), i0=int(v[1]), i1=int(v[2]), j0=int(v[3]), j1=int(v[4]), lengths_ok=bool(v[5]),
+                 verified=tuple(int(x) for x in v[6:10])) for v in z[:n.value]]
 
 
 def stream_probe(ncells: int) -> float:

@@ -53,6 +53,12 @@ int cice_evp_hip_cgrid_window_deps(const cice_evp_hip_dims *dims, int32_t *n_win
 int cice_evp_hip_cgrid_strip_plan(const cice_evp_hip_dims *dims, int32_t ex, int32_t ey, int32_t lo0, int32_t slots, int32_t seg_min, int32_t seg,
                                   int32_t *n_items, int32_t *items6, int32_t items_cap, int32_t *n_windows, int32_t *tiles4, uint8_t *in_zone, int32_t windows_cap,
                                   int32_t *seg_rows);
+/* Host only: the rectangles of cice_evp_hip_cgrid_strip_plan (same dims, ex, ey), 10 ints each in zones10: block, first owned column
+ * of its first and last window column, first owned row of its first and last window row (halo_plan.h: strip_zones -- window rows and
+ * columns already given back where an item would load outside the block's array), 1 if the lengths may be formed for it, and the
+ * rectangle of cells the host then checks them on (first and last column, first and last row; halo_plan.h: strip_len_range).  The
+ * library may still give a window row back where that check fails.  Pass NULL to learn the count.                                    */
+int cice_evp_hip_cgrid_strip_zones(const cice_evp_hip_dims *dims, int32_t ex, int32_t ey, int32_t *n_zones, int32_t *zones10, int32_t zones_cap);
 /* Test hook: route the exchanges and the rank agreements of the marching path through HOST buffers and the caller's
  * callbacks instead of RCCL (which refuses two ranks on one device), so that its several-rank form can be run as
  * processes sharing one GPU (tools/mailbox_2proc.py --march: torch.distributed gloo underneath).  xchg: per peer q

@@ -497,25 +497,41 @@ def test_cgrid_marched_kernel_plan_covers_every_cell_once(nx, ny, bx, by, ew, lo
     (halo_plan.h: strip_zones / strip_items / strip_windows): every interior cell of every block is owned exactly once -- by one lane
     of one work item, or by one window the windowed kernel keeps --, the items own exactly the cells of the windows they replace, every
     position an item computes is an interior cell of its block and every row / column it loads lies inside the block's array."""
-    from cice_amd import decomp
     dc = decomp.Decomp(nx, ny, bx, by, ew, "closed", 1)
+    pl, marched = check_strip_plan(dc, 32, 8, lo0, seg)
+    if (nx, ny) == (3600, 2400) and bx == 3600:
+        assert len(pl["items"]) == 2013 and pl["segment_rows"] == 73 and int(marched.sum()) == 8525130
+
+
+def strip_footprint(item, lo0):
+    """Rows and columns cg_strip loads for one work item (halo_plan.h: strip_footprint), restated: lanes 0 .. 63 hold columns
+    c - 2 .. c + 61; iterations j = ja - 4 (ja - 5 where the lengths are formed, lo0 = 3) .. jb + 1 load row j + 2 ahead (the
+    prefetch of the last iteration included) and row j - 1 for the momentum step."""
+    b, c, ja, jb, lo, hi = (int(v) for v in item)
+    return c - 2, c + 61, ja - (6 if lo0 == 3 else 5), jb + 3
+
+
+def check_strip_plan(dc, ex, ey, lo0, seg, slots=2048, seg_min=8):
     d, keep = evp.make_dims(dc, 0)
-    ex, ey = 32, 8
-    pl = evp.cgrid_strip_plan(d, ex=ex, ey=ey, lo0=lo0, slots=2048, seg_min=8, seg=seg)
+    pl = evp.cgrid_strip_plan(d, ex=ex, ey=ey, lo0=lo0, slots=slots, seg_min=seg_min, seg=seg)
     blks = dc.local_blocks(0)
     own = np.zeros((len(blks), dc.ny_block + 1, dc.nx_block + 1), dtype=np.int32)      # 1-based
-    for b, c, ja, jb, lo, hi in pl["items"]:
+    for it in pl["items"]:
+        b, c, ja, jb, lo, hi = (int(v) for v in it)
         B = blks[b]
         assert lo0 <= lo <= hi <= 61 and ja <= jb
         own[b, ja:jb + 1, c - 2 + lo:c - 2 + hi + 1] += 1
-        # computed positions: lanes 0 .. 62, rows ja - 2 .. jb + 1; loaded: lane 63 too, rows ja - 6 .. jb + 2
+        # computed positions: lanes 0 .. 62, rows ja - 2 .. jb + 1; loaded: lane 63 too, rows ja - 6 .. jb + 3 (ja - 5 without LEN)
         assert B.ilo <= c - 2 and c + 60 <= B.ihi and B.jlo <= ja - 2 and jb + 1 <= B.jhi, (b, c, ja, jb)
-        assert c + 61 <= dc.nx_block and ja - 6 >= 1 and jb + 2 <= dc.ny_block
+        i0, i1, j0, j1 = strip_footprint(it, lo0)
+        assert 1 <= i0 and i1 <= dc.nx_block and 1 <= j0 and j1 <= dc.ny_block, \
+            f"item {tuple(int(v) for v in it)} loads rows {j0} .. {j1}, columns {i0} .. {i1} of a {dc.nx_block} x {dc.ny_block} block array"
     marched = own.copy()
     win = np.zeros_like(own)
+    sx, sy = ex - 3, ey - 3
     for (b, i0, j0, reg), inz in zip(pl["tiles"], pl["in_zone"]):
         B = blks[b]
-        i1, j1 = min(i0 + ex - 4, B.ihi), min(j0 + ey - 4, B.jhi)
+        i1, j1 = min(i0 + sx - 1, B.ihi), min(j0 + sy - 1, B.jhi)
         (win if inz else own)[b, j0:j1 + 1, i0:i1 + 1] += 1
         assert reg or not inz
     for b, B in enumerate(blks):
@@ -526,9 +542,90 @@ def test_cgrid_marched_kernel_plan_covers_every_cell_once(nx, ny, bx, by, ew, lo
     assert (marched == win).all(), "the work items do not own exactly the cells of the windows they replace"
     if len(pl["items"]):
         rows = pl["items"][:, 3] - pl["items"][:, 2] + 1
-        assert rows.max() <= pl["segment_rows"] and (seg or len(pl["items"]) <= 2048 or pl["segment_rows"] == 8)
-    if (nx, ny) == (3600, 2400) and bx == 3600:
-        assert len(pl["items"]) == 2013 and pl["segment_rows"] == 73 and int(marched.sum()) == 8525130
+        assert rows.max() <= pl["segment_rows"] and (seg or len(pl["items"]) <= slots or pl["segment_rows"] == seg_min)
+    return pl, marched
+
+
+def strip_trimmed(pl, ey):
+    """Regular windows the plan gave back to the windowed kernel from the top of a rectangle: each sits right above the rectangle's
+    last window row, inside its columns, and is not marched."""
+    sy = ey - 3
+    out = 0
+    for b in set(int(v) for v in pl["items"][:, 0]):
+        inz = pl["tiles"][(pl["tiles"][:, 0] == b) & pl["in_zone"]]
+        top, ilo, ihi = inz[:, 2].max(), inz[:, 1].min(), inz[:, 1].max()
+        t = pl["tiles"]
+        out += int(((t[:, 0] == b) & (t[:, 3] == 1) & ~pl["in_zone"] & (t[:, 2] == top + sy) & (t[:, 1] >= ilo) & (t[:, 1] <= ihi)).sum())
+    return out
+
+
+# Heights at which the last owned row of the rectangle is jhi - 1, so that the last iteration's prefetch of row jb + 3 would fall one
+# row past the block's array: interior heights 1 mod 5 from 16 with windows of 8 rows, 1 mod 13 from 27 with windows of 16 rows.
+@pytest.mark.parametrize("nx,ny,bx,by,ew,ns,ex,ey,lo0", [
+    (200, 31, 200, 31, "cyclic", "closed", 32, 8, 3), (200, 31, 200, 31, "closed", "cyclic", 32, 8, 2),
+    (1000, 401, 1000, 401, "cyclic", "closed", 32, 8, 3),      # the default product path: 1000 x 401 in one block is marched automatically
+    (330, 36, 330, 36, "cyclic", "closed", 64, 8, 2), (200, 40, 200, 40, "cyclic", "closed", 64, 16, 3),
+    (400, 72, 200, 36, "cyclic", "closed", 32, 8, 3), (400, 31, 200, 31, "closed", "closed", 32, 8, 3)])
+def test_cgrid_marched_kernel_plan_stays_inside_the_block_array(nx, ny, bx, by, ew, ns, ex, ey, lo0):
+    """The marched kernel's loads stay inside the block's array where the rectangle of regular windows would end one row below the
+    top of the interior: the plan gives that window row back to the windowed kernel, the rest of the rectangle stays marched, and
+    the items still own exactly the cells of the windows they replace."""
+    dc = decomp.Decomp(nx, ny, bx, by, ew, ns, 1)
+    pl, marched = check_strip_plan(dc, ex, ey, lo0, 0)
+    assert len(pl["items"]) > 0 and strip_trimmed(pl, ey) > 0, pl["items"][:4]
+    assert int(pl["items"][:, 3].max()) + 3 == dc.ny_block + 1 - (ey - 3)      # (one window row given back)
+
+
+def test_cgrid_marched_kernel_plan_random_geometries():
+    """A seeded sweep over what shapes the marched kernel's plan -- domain, block cut (1 - 4 blocks, padded or not), both boundary
+    kinds in x, four in y, the edge window shape, lo0, automatic or forced segments --, heights drawn mostly from the two families
+    whose rectangle would end one row below the top: every plan covers every cell once, keeps every load of every item inside its
+    block's array, and (lo0 = 3) every cell the kernel forms a length for inside the rectangle the host verifies."""
+    rng = np.random.default_rng(2026)
+    shapes = [(32, 8), (64, 8), (64, 16)]
+    hit = marched = verified = 0
+    for draw in range(300):
+        ex, ey = shapes[int(rng.integers(0, 3))]
+        sy = ey - 3
+        r = rng.random()
+        if r < 0.7:        # a height of the overrun family of this window shape (+1: the outermost interior row)
+            by = sy * int(rng.integers(3 if sy == 5 else 2, 24 if sy == 5 else 9)) + 1
+        else:
+            by = int(rng.integers(14, 120))
+        bx = int(rng.integers(100, 340))
+        nbx, nby = [(1, 1), (2, 1), (1, 2), (2, 2)][int(rng.integers(0, 4))]
+        nx = nbx * bx - (int(rng.integers(0, 12)) if nbx > 1 else 0)
+        ny = nby * by - (int(rng.integers(0, 4)) if nby > 1 else 0)
+        ew = ("cyclic", "closed")[int(rng.integers(0, 2))]
+        ns = ("closed", "cyclic", "tripole", "tripoleT")[int(rng.integers(0, 4))]
+        if ns.startswith("tripole"):          # (an even number of columns, cyclic in x)
+            nx, ew = nx - nx % 2, "cyclic"
+        lo0 = int(rng.integers(2, 4))
+        seg = 0 if rng.integers(0, 2) else int(rng.integers(1, 40))
+        dc = decomp.Decomp(nx, ny, bx, by, ew, ns, 1)
+        geo = f"draw {draw}: {nx} x {ny} in blocks of {bx} x {by}, {ew} / {ns}, windows {ex} x {ey}, lo0 {lo0}, seg {seg}"
+        pl, _ = check_strip_plan(dc, ex, ey, lo0, seg)
+        if not len(pl["items"]):
+            continue
+        marched += 1
+        hit += strip_trimmed(pl, ey) > 0
+        if lo0 == 3:
+            d, keep = evp.make_dims(dc, 0)
+            zones = evp.cgrid_strip_zones(d, ex, ey)
+            for it in pl["items"]:
+                b, c, ja, jb = (int(v) for v in it[:4])
+                z = [z for z in zones if z["block"] == b]
+                assert len(z) == 1, (geo, b, zones)
+                ia, ib, rja, rjb = z[0]["verified"]
+                # (a rectangle whose last strip's lane 63 sits on the outermost column cannot be verified there: loaded lengths)
+                assert z[0]["lengths_ok"] == (ib <= dc.nx_block - 1), (geo, z[0])
+                if not z[0]["lengths_ok"]:
+                    continue
+                verified += 1
+                # formed: every lane's dxT, dyT, dxU, dyU, dxE, dyN of rows ja - 2 .. jb + 2 (dxE of jb + 2 feeds the shear of jb + 1)
+                assert ia <= c - 2 and c + 61 <= ib and rja <= ja - 2 and jb + 2 <= rjb, (geo, tuple(int(v) for v in it), z[0])
+                assert 2 <= ia and ib <= dc.nx_block - 1 and 2 <= rja and rjb <= dc.ny_block - 1, (geo, z[0])
+    assert marched >= 100 and hit >= 20 and verified >= 1000, (marched, hit, verified)
 
 
 def test_cgrid_resident_window_handoff_graph_against_a_python_restatement():

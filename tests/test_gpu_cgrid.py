@@ -667,16 +667,26 @@ def stir_momentum(inputs, masks, rng):
         inputs[f"rheofact{t}"] = inputs[f"rheofact{t}"] * (rng.random(shape) > 0.1)
 
 
-def marched_case(seed, nx, ny, bs, case, holes, land, general=False):
+def marched_case(seed, nx, ny, bs, case, holes, land, general=False, ew="cyclic", ns="closed"):
     """A synthetic workload in the default configuration (the reference's start-up identities hold for the geometry, waterx == uocn,
     Tb == 0, rheofact == 1 on ice: what the marched kernel is for) with the branches stirred up: random land cells inside the ocean
-    (coastal corners: the boundary-condition ratios), random, mutually independent holes in the four ice masks."""
+    (coastal corners: the boundary-condition ratios), random, mutually independent holes in the four ice masks.  ns = "cyclic": the
+    closed grid's lengths, with ocean (and ice) up to the top and bottom rows."""
     from cice_amd import decomp, synth
     rng = np.random.default_rng(seed)
-    g0 = synth.make_grid(nx, ny, 2.0e4, ns="closed")
+    g0 = synth.make_grid(nx, ny, 2.0e4, ns="closed" if ns == "cyclic" else ns)
+    if ns == "cyclic":
+        g0["kmt"][:2, :] = 1
+        g0["kmt"][-2:, :] = 1
     g0["kmt"] = g0["kmt"] * (rng.random((ny, nx)) >= land)
     g = synth.derive_geometry(g0)
+    if ns == "cyclic":            # (the land masks of the corners and N faces of the top row look across the boundary)
+        hm, hm_n = g["hm"], np.roll(g["hm"], -1, axis=0)
+        g["uvm"] = np.minimum(np.minimum(hm, np.roll(hm, -1, axis=1)), np.minimum(hm_n, np.roll(hm_n, -1, axis=1)))
+        g["umask"] = g["uvm"] > 0.5
     cg = synth.cgrid_geometry(g)
+    if ns == "cyclic":
+        cg["npm"] = np.minimum(g["hm"], np.roll(g["hm"], -1, axis=0))
     state, inputs, masks = synth.cgrid_state(g, cg, case=case, seed=seed, seabed=general)
     if general:
         stir_momentum(inputs, masks, rng)
@@ -685,7 +695,7 @@ def marched_case(seed, nx, ny, bs, case, holes, land, general=False):
     for k in ("stresspT", "stressmT", "stress12T"):
         state[k] = state[k] * masks["iceTmask"]
     state["stress12U"] = state["stress12U"] * masks["iceUmask"]
-    dc = decomp.Decomp(nx, ny, bs[0], bs[1], "cyclic", "closed", 1)
+    dc = decomp.Decomp(nx, ny, bs[0], bs[1], ew, ns, 1)
     return (dc, g) + synth.cgrid_scatter(dc, 0, cg, state, inputs, masks)
 
 
@@ -765,8 +775,8 @@ def test_cgrid_marched_interior_vs_oracle_bitwise(seed, nx, ny, bs, case, holes,
 
 @pytest.mark.parametrize("seed", [3101, 3102, 3103, 3104] + [int(s) for s in __import__("os").environ.get("CGRID_STRIP_SWEEP_SEEDS", "").split() if s])
 def test_cgrid_marched_interior_random_cuts_vs_oracle(seed, monkeypatch):
-    """A sweep over what shapes the marched kernel's plan: domain and block size (one to four blocks, padded or not, cyclic or closed
-    in x), segment length, the shape of the windows kept, lengths formed or loaded, the last subcycle marched or not, ice cover, islands,
+    """A sweep over what shapes the marched kernel's plan: domain and block size (one to four blocks, padded or not), cyclic or closed
+    in x, closed or cyclic in y, segment length, the shape of the windows kept, lengths formed or loaded, the last subcycle marched or not, ice cover, islands,
     classic / revised EVP -- all drawn from the seed; every array equal to the oracle's, bit for bit.  CGRID_STRIP_SWEEP_SEEDS adds seeds."""
     rng = np.random.default_rng(seed)
     nbx, nby = int(rng.integers(1, 3)), int(rng.integers(1, 3))
@@ -775,6 +785,7 @@ def test_cgrid_marched_interior_random_cuts_vs_oracle(seed, monkeypatch):
     nx, ny = nbx * bx - int(rng.integers(0, 20)) * (nbx > 1), nby * by - int(rng.integers(0, 6)) * (nby > 1)
     case, holes, land = ("full", "caps")[int(rng.integers(0, 2))], float(rng.choice([0.0, 0.2, 0.5])), float(rng.choice([0.0, 0.03, 0.1]))
     revised = bool(rng.integers(0, 2))
+    ew, ns = ("cyclic", "closed")[int(rng.integers(0, 2))], ("closed", "cyclic")[int(rng.integers(0, 2))]
     monkeypatch.setenv("CICE_EVP_HIP_CGRID_RESIDENT", "0")
     monkeypatch.setenv("CICE_EVP_HIP_CGRID_ONE_SHAPE", str(int(rng.integers(1, 3))))
     monkeypatch.setenv("CICE_EVP_HIP_CGRID_STRIP", "1")
@@ -798,7 +809,7 @@ def test_cgrid_marched_interior_random_cuts_vs_oracle(seed, monkeypatch):
     for k in ("stresspT", "stressmT", "stress12T"):
         state[k] = state[k] * masks["iceTmask"]
     state["stress12U"] = state["stress12U"] * masks["iceUmask"]
-    dc = decomp.Decomp(nx, ny, bx, by, "cyclic", "closed", 1)
+    dc = decomp.Decomp(nx, ny, bx, by, ew, ns, 1)
     static, state, inputs, masks = synth.cgrid_scatter(dc, 0, cg, state, inputs, masks)
     kw = dict(revised_evp=True, arlx=300.0, brlx=300.0) if revised else {}
     info = {}
@@ -807,8 +818,127 @@ def test_cgrid_marched_interior_random_cuts_vs_oracle(seed, monkeypatch):
     assert_bitwise(got, want, f"marched interior, random cut {seed}: {nx} x {ny} in blocks of {bx} x {by}")
     # (windows of 64 positions along the edges leave blocks under ~190 columns without a rectangle: cg_one runs those alone)
     assert info["marched_items"] > 0 or __import__("os").environ["CICE_EVP_HIP_CGRID_STRIP_EDGE"] != "0", info
-    print(f"STRIP_SWEEP seed {seed}: {nx} x {ny} / {bx} x {by}, items {info['marched_items']} x {info['marched_segment_rows']} rows, "
+    print(f"STRIP_SWEEP seed {seed}: {nx} x {ny} / {bx} x {by}, {ew} / {ns}, items {info['marched_items']} x {info['marched_segment_rows']} rows, "
           f"cells {info['marched_cells']}, lengths formed {info['marched_lengths_derived']}, general momentum step {general}, {visc}")
+
+
+def marched_against_both(dc, static, state, inputs, masks, monkeypatch, what, ndte=6, visc="avg_zeta"):
+    """One call with the marched kernel forced on (the environment as the caller set it), bit for bit against the oracle and against
+    the windowed kernel alone (CICE_EVP_HIP_CGRID_STRIP=0); returns the library's timings of the marched run."""
+    from cice_amd import synth
+    scal = synth.evp_scalars(120)
+    d, keep = evp.make_dims(dc, 0)
+
+    def run():
+        core = evp.EvpHip(d, evp.make_params(scal, strict=True), static["dyE"], static["dxN"], static["dxT"], static["dyT"],
+                          1.0 / static["uarea"], static["tarea"], keepalive=keep)
+        try:
+            core.cgrid_set_geometry(static)
+            return core.cgrid_run(ndte, state, inputs, masks, visc_method=visc), core.cgrid_timings()
+        finally:
+            core.finalize()
+    monkeypatch.setenv("CICE_EVP_HIP_CGRID_RESIDENT", "0")
+    monkeypatch.setenv("CICE_EVP_HIP_CGRID_STRIP", "1")
+    got, tt = run()
+    blks = dc.local_blocks(0)
+    dom = oracle.OracleDomain(dc.nx_block, dc.ny_block, len(blks), dc.nx_global, dc.ny_global, dc.ew, dc.ns,
+                              [b.ilo for b in blks], [b.ihi for b in blks], [b.jlo for b in blks],
+                              [b.jhi for b in blks], [b.gi0 for b in blks], [b.gj0 for b in blks])
+    prm = oracle.make_params(**{k: scal[k] for k in ("arlx1i", "denom1", "brlx", "revp", "e_factor", "epp2i", "capping",
+                                                      "Ktens", "deltaminEVP", "u0", "cosw", "sinw", "rhow")})
+    want = oracle.cgrid_subcycle(dom, prm, ndte, state, inputs, static, masks, visc_method=visc)
+    assert_bitwise(got, want, what)
+    assert np.abs(want["uvelE"] - state["uvelE"]).max() > 0
+    monkeypatch.setenv("CICE_EVP_HIP_CGRID_STRIP", "0")
+    windowed, tw = run()
+    monkeypatch.setenv("CICE_EVP_HIP_CGRID_STRIP", "1")
+    assert tw["marched_items"] == 0, tw
+    assert_bitwise(got, windowed, what + ", against the windowed kernel")
+    return tt
+
+
+# Interior heights whose rectangle of 32 x 8 windows (29 x 5 owned cells) would end on row jhi - 1: 31 and 36 (1 mod 5); of 64 x 16
+# windows: 40 (1 mod 13).  The marched kernel's last iteration would prefetch row ny_block + 1 there -- past the end of the arrays for
+# the last block; the plan gives that window row back to the windowed kernel (halo_plan.h: strip_zones).
+@pytest.mark.parametrize("nx,ny,bs,edge,length,last", [
+    (200, 31, (200, 31), "0", "1", "1"), (200, 31, (200, 31), "0", "0", "0"), (200, 36, (200, 36), "0", "1", "0"),
+    (200, 36, (200, 36), "0", "0", "1"), (400, 31, (200, 31), "0", "0", "1"), (400, 31, (200, 31), "0", "1", "0"),
+    (400, 36, (200, 36), "0", "1", "1"), (400, 36, (200, 36), "0", "0", "0"), (200, 40, (200, 40), "2", "1", "1")])
+def test_cgrid_marched_interior_at_the_top_of_the_block_array(nx, ny, bs, edge, length, last, monkeypatch):
+    """The marched kernel where its rectangle would reach the top of the block's interior: the plan the library runs is the trimmed
+    one (every item's loads inside the array), and the results equal the oracle's and the windowed kernel's bit for bit -- lengths
+    formed or loaded, the last subcycle marched or not."""
+    monkeypatch.setenv("CICE_EVP_HIP_CGRID_ONE_SHAPE", "2")
+    monkeypatch.setenv("CICE_EVP_HIP_CGRID_STRIP_EDGE", edge)
+    monkeypatch.setenv("CICE_EVP_HIP_CGRID_STRIP_LEN", length)
+    monkeypatch.setenv("CICE_EVP_HIP_CGRID_STRIP_LAST", last)
+    dc, _, static, state, inputs, masks = marched_case(40 + ny, nx, ny, bs, "full", 0.2, 0.02)
+    tt = marched_against_both(dc, static, state, inputs, masks, monkeypatch, f"marched interior {nx} x {ny} / {bs}")
+    assert tt["marched_items"] > 0 and tt["marched_lengths_derived"] == (length == "1"), tt
+    ex, ey = (64, 16) if edge == "2" else (32, 8)
+    d, keep = evp.make_dims(dc, 0)
+    pl = evp.cgrid_strip_plan(d, ex=ex, ey=ey, lo0=2 + int(length), slots=2048, seg_min=8, seg=0)
+    it = pl["items"]
+    assert int(it[:, 3].max()) + 3 <= dc.ny_block and int(it[:, 2].min()) - 6 >= 1 and int(it[:, 1].max()) + 61 <= dc.nx_block
+    if length == "0":             # (formed lengths: the host's check may give a further window row back)
+        assert tt["marched_items"] == len(it) and tt["marched_segment_rows"] == pl["segment_rows"], (tt, len(it))
+        assert tt["marched_cells"] == int(((it[:, 5] - it[:, 4] + 1) * (it[:, 3] - it[:, 2] + 1)).sum()), tt
+
+
+@pytest.mark.parametrize("kind,nx,ny,ew,ns", [("closed in x", 200, 48, "closed", "closed"), ("cyclic in y", 200, 48, "cyclic", "cyclic"),
+                                             ("u-fold tripole", 400, 120, "cyclic", "tripole"), ("T-fold tripole", 400, 120, "cyclic", "tripoleT")])
+def test_cgrid_marched_interior_boundary_kinds(kind, nx, ny, ew, ns, monkeypatch):
+    """The marched kernel on the boundary kinds besides cyclic x closed: closed in x, cyclic in y (ice up to row jhi), bit for bit
+    against the oracle and the windowed kernel.  On tripole grids (u-fold, T-fold) the one-launch schedule is not used at all: the
+    library must decline the marched kernel there, and the five-launch results still equal the oracle's."""
+    monkeypatch.setenv("CICE_EVP_HIP_CGRID_ONE_SHAPE", "2")
+    dc, _, static, state, inputs, masks = marched_case(77, nx, ny, (nx, ny), "full", 0.2, 0.02, ew=ew, ns=ns)
+    if ns == "cyclic":
+        jhi = dc.local_blocks(0)[0].jhi
+        assert masks["iceUmask"][0, jhi - 1].sum() > 0 and masks["iceEmask"][0, jhi - 1].sum() > 0
+    tt = marched_against_both(dc, static, state, inputs, masks, monkeypatch, f"marched interior, {kind}")
+    if ns.startswith("tripole"):
+        assert tt["marched_items"] == 0 and tt["one_launch_subcycles"] == 0, tt
+    else:
+        assert tt["marched_items"] > 0 and tt["one_launch_subcycles"] > 0, tt
+
+
+def perturb_length(static, name, b, i, j):
+    """dxE or dyN of one cell of the block arrays one ulp up, its area and reciprocal area along (the derived view's identities)."""
+    st = {k: v.copy() for k, v in static.items()}
+    st[name][b, j - 1, i - 1] = np.nextafter(st[name][b, j - 1, i - 1], np.inf)
+    face, other = ("E", "dyE") if name == "dxE" else ("N", "dxN")
+    a = st[name][b, j - 1, i - 1] * st[other][b, j - 1, i - 1]
+    st[f"{face.lower()}area"][b, j - 1, i - 1] = a
+    st[f"{face.lower()}arear"][b, j - 1, i - 1] = 1.0 / a
+    return st
+
+
+@pytest.mark.parametrize("name", ["dxE", "dyN"])
+@pytest.mark.parametrize("where", ["inside, east edge", "inside, west edge", "above", "right of it", "ghost row"])
+def test_cgrid_marched_lengths_check_covers_the_formed_cells(where, name, monkeypatch):
+    """The host lets the marched kernel form six lengths from HTN / HTE only after checking them bit for bit on the rectangle of
+    cells it forms them for (halo_plan.h: strip_len_range).  A grid cyclic in y, 31 rows (a rectangle that would end on row jhi - 1),
+    lengths the reference's means: one ulp off on a cell of that rectangle -- halfway up, where giving the top or bottom window row
+    back does not help -- refuses the formed lengths; one ulp off just outside it --
+    above it, right of it, on the ghost row ny_block -- leaves them formed.  Bit for bit against the oracle and the windowed kernel
+    either way: a formed value the check never saw would show here."""
+    monkeypatch.setenv("CICE_EVP_HIP_CGRID_ONE_SHAPE", "2")
+    monkeypatch.setenv("CICE_EVP_HIP_CGRID_STRIP_EDGE", "0")
+    monkeypatch.setenv("CICE_EVP_HIP_CGRID_STRIP_LEN", "1")
+    dc, _, static, state, inputs, masks = marched_case(91, 200, 31, (200, 31), "full", 0.1, 0.0, ew="cyclic", ns="cyclic")
+    d, keep = evp.make_dims(dc, 0)
+    (z,) = evp.cgrid_strip_zones(d, 32, 8)
+    assert z["lengths_ok"], z
+    ia, ib, ja, jb = z["verified"]
+    cell = {"inside, east edge": (ib, (ja + jb) // 2), "inside, west edge": (ia, (ja + jb) // 2), "above": ((ia + ib) // 2, jb + 1),
+            "right of it": (ib + 1, (ja + jb) // 2), "ghost row": ((ia + ib) // 2, dc.ny_block)}[where]
+    st = perturb_length(static, name, z["block"], *cell)
+    tt = marched_against_both(dc, st, state, inputs, masks, monkeypatch, f"{name} one ulp off at {cell} ({where})")
+    assert tt["marched_items"] > 0 and tt["geometry_derived"], tt
+    assert tt["marched_lengths_derived"] == (not where.startswith("inside")), tt
+    if tt["marched_lengths_derived"]:     # (and the whole rectangle kept)
+        assert tt["marched_items"] == len(evp.cgrid_strip_plan(d, ex=32, ey=8, lo0=3, slots=2048, seg_min=8, seg=0)["items"]), tt
 
 
 def test_cgrid_default_configuration_shortcuts_are_bit_neutral(monkeypatch):
