@@ -3,6 +3,7 @@
 // between dyn_prep1 and its subcycle loop at U, N and E points (dynamics/ice_dyn_evp.F90:430-453, 479-490, 563-691) --
 //   grid_average_X2Y 'S' T -> U / E / N    infrastructure/ice_grid.F90:4190-4209, 4290-4306, 4332-4348
 //   grid_average_X2Y 'F' T -> E / N        ice_grid.F90:4728-4744, 4766-4782
+//   ... or from U / E / N                  (cice_evp_hip_set_forcing_layout: cg_prep<true>, evp_forcing.h)
 //   dyn_prep2 (X = U, N, E; rheofactX)     dynamics/ice_dyn_shared.F90:697-838
 //   stresses zeroed off the ice            ice_dyn_evp.F90:676-691
 // -- in one launch, one thread per cell: every average a face / corner reads back is its own.  dyn_prep1, the T-grid halo
@@ -16,6 +17,8 @@
 #include "evp_device.h"
 
 #pragma clang fp contract(off)
+
+#include "evp_forcing.h"
 
 namespace {
 
@@ -38,6 +41,7 @@ __device__ __forceinline__ double avg_s2(const double *a, double mw0, double mw1
     return (m0 * a[c] * w0 + m1 * a[q] * w1) / wtmp;
 }
 
+template <bool LAYOUT>
 __global__ void cg_prep(EvpCgPrep P)
 {
     int i, j, bz; size_t c;
@@ -51,6 +55,22 @@ __global__ void cg_prep(EvpCgPrep P)
     double cdn[3] = {0, 0, 0}, ai[3] = {0, 0, 0}, uo[3] = {0, 0, 0}, vo[3] = {0, 0, 0};
     double water[3] = {0, 0, 0}, force[3] = {0, 0, 0}, massdti[3] = {0, 0, 0};
     bool ice[3] = {false, false, false};
+    double air_l[3] = {0, 0, 0}, ss_l[3] = {0, 0, 0};
+    if (LAYOUT) {
+        // ice_dyn_evp.F90:440-453 from grid_ocn_dynu / v, :479-489 from grid_atm_dynu / v (or T): the x component at E,
+        // the y component at N is what dyn_prep2 reads there.  Ghost cells too (a copy keeps them).
+        const EvpForcing &F = P.F;
+        for (int L = 1; L <= 2; ++L) {
+            const int X = L == 1 ? EVP_LOC_E : EVP_LOC_N, oc = F.ocn[L - 1];
+            uo[L] = x2y(false, F, F.ocn[0], X, P.t[5], c, P.nx, in);
+            vo[L] = x2y(false, F, F.ocn[1], X, P.t[6], c, P.nx, in);
+            ss_l[L] = x2y(false, F, oc, X, P.t[L == 1 ? 7 : 8], c, P.nx, in);
+            air_l[L] = x2y(true, F, F.calc_strair ? EVP_LOC_T : F.atm[L - 1], X, P.t[L == 1 ? 9 : 10], c, P.nx, in);
+        }
+        if (F.prod[0]) {
+            F.prod[0][c] = air_l[1]; F.prod[1][c] = air_l[2]; F.prod[2][c] = ss_l[1]; F.prod[3][c] = ss_l[2];
+        }
+    }
     if (in) {
         const size_t ce = c + 1, cn = c + P.nx, cne = c + P.nx + 1;
         const double m0 = P.hm[c], m1 = P.hm[ce], m2 = P.hm[cn], m3 = P.hm[cne];
@@ -72,8 +92,10 @@ __global__ void cg_prep(EvpCgPrep P)
                 mass = avg_s2(tm, mw0, mw1, m0, mq, w0, wq, c, q);
                 aiX = avg_s2(a_init, mw0, mw1, m0, mq, w0, wq, c, q);
                 cdn[L] = avg_s2(P.t[4], mw0, mw1, m0, mq, w0, wq, c, q);
-                uo[L] = avg_s2(P.t[5], mw0, mw1, m0, mq, w0, wq, c, q);
-                vo[L] = avg_s2(P.t[6], mw0, mw1, m0, mq, w0, wq, c, q);
+                if (!LAYOUT) {
+                    uo[L] = avg_s2(P.t[5], mw0, mw1, m0, mq, w0, wq, c, q);
+                    vo[L] = avg_s2(P.t[6], mw0, mw1, m0, mq, w0, wq, c, q);
+                }
                 ai[L] = aiX;
             }
             int32_t *mX = P.m4 + (size_t)(1 + L) * P.n;
@@ -102,10 +124,10 @@ __global__ void cg_prep(EvpCgPrep P)
             const double wy = vo[L] * P.cosw + uo[L] * P.sinw * sg;
             // the component this face carries: x at E, y at N
             const double *strair = P.t[L == 1 ? 9 : 10];
-            const double air = 0.5 * (strair[c] * w0 + strair[q] * wq) / (L == 1 ? P.earea[c] : P.narea[c]);
+            const double air = LAYOUT ? air_l[L] : 0.5 * (strair[c] * w0 + strair[q] * wq) / (L == 1 ? P.earea[c] : P.narea[c]);
             double tlt;
             if (P.ssh_coupled) {
-                const double ss = avg_s2(P.t[L == 1 ? 7 : 8], m0 * w0, mq * wq, m0, mq, w0, wq, c, q);
+                const double ss = LAYOUT ? ss_l[L] : avg_s2(P.t[L == 1 ? 7 : 8], m0 * w0, mq * wq, m0, mq, w0, wq, c, q);
                 tlt = -P.gravit * mass * ss;
             } else {
                 tlt = L == 1 ? -fm * vo[L] : fm * uo[L];
@@ -164,7 +186,10 @@ dim3 cell_grid(const EvpCgPrep &P, int nblocks) { return dim3((P.nx + 63) / 64, 
 
 void evp_launch_cgrid_prep(const EvpCgPrep &P, int nblocks, hipStream_t st)
 {
-    hipLaunchKernelGGL(cg_prep, cell_grid(P, nblocks), dim3(64), 0, st, P);
+    if (P.F.on)
+        hipLaunchKernelGGL(cg_prep<true>, cell_grid(P, nblocks), dim3(64), 0, st, P);
+    else
+        hipLaunchKernelGGL(cg_prep<false>, cell_grid(P, nblocks), dim3(64), 0, st, P);
 }
 void evp_launch_cgrid_seabed_lkd(const EvpCgPrep &P, int nblocks, const uint8_t *mask, const double *hwater, double k1, double k2,
                                  double alphab, double threshold_hw, hipStream_t st)

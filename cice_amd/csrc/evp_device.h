@@ -241,6 +241,18 @@ struct EvpDirect {
 };
 void evp_launch_halo_direct(const EvpDirect &D, double *u, double *v, hipStream_t st);
 
+// Forcing layout of the preparation phase (cice_evp_hip_set_forcing_layout; stencils: evp_forcing.h).  on = 0: the ocean
+// fields and the wind stress on the T grid (calc_strair = .true., grid_ocn = 'A'), the kernels' default instantiation.
+enum { EVP_LOC_T = 0, EVP_LOC_U = 1, EVP_LOC_E = 2, EVP_LOC_N = 3 };
+struct EvpForcing {
+    int on;
+    int calc_strair;              // 0: the wind stress is strax / stray at atm[] (tfields11 slots 9 / 10), not strairxT / yT
+    int ocn[2], atm[2];           // location (EVP_LOC_*) of the x / y component: grid_ocn_dynu / v, grid_atm_dynu / v
+    const double *area[4];        // tarea uarea earea narea (NULL where no stencil of the layout reads it)
+    const double *pm[4];          // hm uvm epm npm: the masks of the state-masked average
+    double *prod[4];              // C grid, optional: strairxE, strairyN, ss_tltxE, ss_tltyN as averaged (every cell)
+};
+
 // Preparation phase of evp() on the device (evp_prep.hip)
 struct EvpPrep {
     int nx, ny;
@@ -260,6 +272,7 @@ struct EvpPrep {
     unsigned *flagword;        // out: bit0 = waterx/watery differ from uocnU/vocnU somewhere
     double dt, rhoi, rhos, gravit, dyn_area_min, dyn_mass_min, cosw, sinw;
     int ssh_coupled;
+    EvpForcing F;              // (last: the default instantiation reads the members above at the same offsets)
 };
 struct EvpPrepHalo {
     double *a[10];
@@ -492,6 +505,7 @@ struct EvpCgPrep {
     double *in[CG_NIN];           // the loop's per-call inputs (CI_*; strength untouched)
     double dt, gravit, dyn_area_min, dyn_mass_min, cosw, sinw;
     int ssh_coupled;
+    EvpForcing F;                 // (last, as in EvpPrep)
 };
 void evp_launch_cgrid_prep(const EvpCgPrep &P, int nblocks, hipStream_t st);
 // seabed_stress_factor_LKD at E and N points (grid_location 'E' / 'N'): TbE, TbN from aice, vice, hwater and mask bits 2, 3

@@ -172,6 +172,14 @@ struct State {
         std::vector<uint8_t> h8;
         double t_ms = 0;
     } prep;
+    // where the forcing of the preparation lives, both grids (cice_evp_hip_set_forcing_layout); on = false: the T-grid layout
+    // (calc_strair = .true., grid_ocn = 'A') and the kernels' default instantiation
+    struct Forcing {
+        bool on = false;
+        int calc_strair = 1, ocn[2] = {0, 0}, atm[2] = {0, 0};          // EVP_LOC_*
+        double *earea = nullptr, *narea = nullptr, *uvm = nullptr, *epm = nullptr, *npm = nullptr;   // B grid: E / N sources
+        bool wind_t() const { return !on || calc_strair; }             // strairxT / yT in slots 9 / 10: halo-updated
+    } forcing;
     int32_t *h_send_src = nullptr, *h_recv_dst = nullptr;
     int8_t *h_recv_sign = nullptr;
     double *sendbuf = nullptr, *recvbuf = nullptr;
@@ -332,6 +340,10 @@ int upload_lists();
 int build_push_table();
 void fill_args(EvpArgs &A, int cur, int last);
 int cap_mode();
+// forcing layout of the preparation (evp_host_prep.cpp): the kernels' EvpForcing from S.forcing and this grid's areas / masks
+// (tarea uarea earea narea, hm uvm epm npm); the check of tfields11 against it
+int forcing_of(EvpForcing &F, const double *const area[4], const double *const pm[4]);
+int check_tfields(const double *const *tfields11);
 // evp_host_loop.cpp
 void fill_direct(EvpDirect &D);
 int halo_remote_pair(double *a, double *bb, bool masked = false, bool has_tail = false);

@@ -107,6 +107,7 @@ struct CGridState {
         double *hwater = nullptr, *tbt = nullptr, *aicen = nullptr, *vicen = nullptr;
         int ncat = 0;
         std::vector<int32_t> h4;               // the four mask words as they come back
+        double *prod[4] = {};                  // test build, forcing layout on: strairxE strairyN ss_tltxE ss_tltyN (EvpForcing::prod)
         cice_evp_hip_prep_params pp{};
         double t_ms = 0;
     } prep;
@@ -134,6 +135,7 @@ void cgrid_free()
         for (auto &p : Q.fcor) F(p);
         for (auto &p : Q.t) F(p);
         F(Q.tmass); F(Q.maskd); F(Q.c_dst); F(Q.c_src); F(Q.c_vsign); F(Q.hwater); F(Q.tbt); F(Q.aicen); F(Q.vicen);
+        for (auto &p : Q.prod) F(p);
     }
     F(CG.strengthU); F(CG.s12alt); F(CG.umaskd); F(CG.fac[0]); F(CG.fac[1]); F(CG.d_flags); F(CG.mask); F(CG.gmask); F(CG.mask4); F(CG.img_slot); F(CG.img_dst); F(CG.zero_cells); F(CG.fold_tmp);
     for (auto &f : CG.fold) { F(f.dst); F(f.a); F(f.b); F(f.flip); }
@@ -1367,8 +1369,20 @@ int cice_evp_hip_cgrid_prep(const cice_evp_hip_prep_params *pp, const double *co
     CGridState::Prep &Q = CG.prep;
     if (!Q.geo) return fail(-1, "cice_evp_hip_cgrid_set_prep_geometry was not called");
     if (!pp || !tfields11 || !iceTmask || !iceUmask || !iceEmask || !iceNmask) return fail(-1, "null argument");
-    for (int k = 0; k < 11; ++k)
-        if (!tfields11[k]) return fail(-1, "null T-grid field %d", k);
+    if (int rc = check_tfields(tfields11)) return rc;
+    EvpCgPrep P{};
+    {   // the forcing layout (cice_evp_hip_set_forcing_layout), checked before anything moves
+        const double *area[4] = {CG.g[CG_TAREA], CG.g[CG_UAREA], CG.g[CG_EAREA], CG.g[CG_NAREA]};
+        const double *pm[4] = {CG.g[CG_HM], CG.g[CG_UVM], CG.g[CG_EPM], CG.g[CG_NPM]};
+        if (int rc = forcing_of(P.F, area, pm)) return rc;
+#ifdef CICE_EVP_HIP_TESTING
+        if (P.F.on)
+            for (int k = 0; k < 4; ++k) {
+                if (!Q.prod[k] && alloc_d(&Q.prod[k], S.n)) return -1;
+                P.F.prod[k] = Q.prod[k];
+            }
+#endif
+    }
     // the loop's state: given, or NULL = what the previous call left on the device (evp() is its only writer)
     int nstate = 0;
     if (state12)
@@ -1399,7 +1413,9 @@ int cice_evp_hip_cgrid_prep(const cice_evp_hip_prep_params *pp, const double *co
         EvpPrepHalo H{};
         std::pair<double *, bool> arrs[10] = {{Q.maskd, false}, {Q.tmass, false}, {Q.t[3], false}, {Q.t[4], false}, {Q.t[5], true},
                                               {Q.t[6], true}, {Q.t[7], true}, {Q.t[8], true}, {Q.t[9], true}, {Q.t[10], true}};
-        for (const auto &a : arrs) { H.a[H.narr] = a.first; H.is_vec[H.narr] = a.second; ++H.narr; }
+        // calc_strair = .false.: strax / stray in slots 9 / 10 are averaged as the host holds them (ice_dyn_evp.F90:467-468)
+        const int nh = S.forcing.wind_t() ? 10 : 8;
+        for (int k = 0; k < nh; ++k) { H.a[H.narr] = arrs[k].first; H.is_vec[H.narr] = arrs[k].second; ++H.narr; }
         H.dst = Q.c_dst; H.src = Q.c_src; H.vsign = Q.c_vsign; H.n = Q.n_center;
         evp_launch_halo_center(H, S.stream);
         if (CG.tfold) {
@@ -1407,16 +1423,15 @@ int cice_evp_hip_cgrid_prep(const cice_evp_hip_prep_params *pp, const double *co
             // from row NY-1: the fold step of location 0, after the plain ghost copies (whose sources it does not write)
             fold({{arrs[0].first, 0, arrs[0].second}, {arrs[1].first, 0, arrs[1].second}, {arrs[2].first, 0, arrs[2].second}, {arrs[3].first, 0, arrs[3].second}});
             fold({{arrs[4].first, 0, arrs[4].second}, {arrs[5].first, 0, arrs[5].second}, {arrs[6].first, 0, arrs[6].second}, {arrs[7].first, 0, arrs[7].second}});
-            fold({{arrs[8].first, 0, arrs[8].second}, {arrs[9].first, 0, arrs[9].second}});
+            if (nh == 10) fold({{arrs[8].first, 0, arrs[8].second}, {arrs[9].first, 0, arrs[9].second}});
         }
         if (S.plan.center_remote) {
             double *pairs[5][2] = {{Q.maskd, Q.tmass}, {Q.t[3], Q.t[4]}, {Q.t[5], Q.t[6]}, {Q.t[7], Q.t[8]}, {Q.t[9], Q.t[10]}};
-            for (auto &pr : pairs)
-                if (int rc = halo_remote_pair(pr[0], pr[1])) return rc;
+            for (int q = 0; q < nh / 2; ++q)
+                if (int rc = halo_remote_pair(pairs[q][0], pairs[q][1])) return rc;
         }
     }
-    EvpCgPrep P{};
-    fill_prep(P);
+    fill_prep(P);                              // (P.F: set above)
     evp_launch_cgrid_prep(P, S.d.nblocks, S.stream);
     EvpCgrid A;
     fill(A);
@@ -1538,6 +1553,10 @@ int cice_evp_hip_cgrid_fetch(int32_t table, int32_t index, double *dst)
     const double *src = nullptr;
     if (table == 0 && index >= 0 && index < CG_NF) src = CG.f[index];
     if (table == 1 && index >= 0 && index < CG_NIN) src = CG.in[index];
+#ifdef CICE_EVP_HIP_TESTING
+    // the test build: what the last preparation with a forcing layout averaged -- strairxE strairyN ss_tltxE ss_tltyN
+    if (table == 2 && index >= 0 && index < 4) src = CG.prep.prod[index];
+#endif
     if (!src) return fail(-1, "cgrid_fetch: table %d index %d", (int)table, (int)index);
     if (d2h(dst, src)) return -1;
     HIPC(hipStreamSynchronize(S.stream));

@@ -85,6 +85,8 @@ void free_all()
         F(Q.strtltx); F(Q.strtlty); F(Q.flagword); F(Q.c_dst); F(Q.c_src); F(Q.c_vsign); F(Q.tf_dst); F(Q.tf_a); F(Q.tf_b); F(Q.tf_flip); F(Q.tf_tmp);
         S.prep = State::Prep();
     }
+    F(S.forcing.earea); F(S.forcing.narea); F(S.forcing.uvm); F(S.forcing.epm); F(S.forcing.npm);
+    S.forcing = State::Forcing();
     F(S.h_send_src);
     F(S.h_recv_dst);
     F(S.h_recv_sign);

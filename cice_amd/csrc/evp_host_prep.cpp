@@ -3,6 +3,42 @@
 
 using namespace evp_host;
 
+namespace evp_host {
+
+// the EvpForcing of a preparation kernel; area / pm: tarea uarea earea narea, hm uvm epm npm as this grid holds them.
+// Fails when a source of the layout needs an array that is not on the device.
+int forcing_of(EvpForcing &F, const double *const area[4], const double *const pm[4])
+{
+    const State::Forcing &G = S.forcing;
+    F = EvpForcing{};
+    F.on = G.on;
+    if (!G.on) return 0;
+    F.calc_strair = G.calc_strair;
+    for (int k = 0; k < 2; ++k) { F.ocn[k] = G.ocn[k]; F.atm[k] = G.atm[k]; }
+    for (int k = 0; k < 4; ++k) { F.area[k] = area[k]; F.pm[k] = pm[k]; }
+    const int used[4] = {G.ocn[0], G.ocn[1], G.calc_strair ? 0 : G.atm[0], G.calc_strair ? 0 : G.atm[1]};
+    static const char *const loc[4] = {"T", "U", "E", "N"};
+    for (int k = 0; k < 4; ++k)
+        if (used[k] >= EVP_LOC_E && (!area[used[k]] || !pm[used[k]]))
+            return fail(-1, "forcing layout: a source on %s points needs %sarea and %spm (cice_evp_hip_set_forcing_layout)",
+                        loc[used[k]], used[k] == EVP_LOC_E ? "e" : "n", used[k] == EVP_LOC_E ? "e" : "n");
+    return 0;
+}
+
+// tfields11 of a preparation (either grid): every slot given; with calc_strair = .false. slots 9 / 10 carry strax / stray
+int check_tfields(const double *const *t)
+{
+    for (int k = 0; k < 11; ++k)
+        if (!t[k]) {
+            if (k >= 9 && !S.forcing.wind_t())
+                return fail(-1, "calc_strair = .false.: %s (tfields11 slot %d) is NULL", k == 9 ? "strax" : "stray", k);
+            return fail(-1, "null T-grid field %d", k);
+        }
+    return 0;
+}
+
+}  // namespace evp_host
+
 extern "C" {
 
 // ---- next tier: the preparation phase of evp() on the device ----------------
@@ -63,6 +99,37 @@ int cice_evp_hip_set_prep_geometry(const int32_t *tmask, const int32_t *umask, c
     return 0;
 }
 
+// Where the forcing of the preparation lives (both grids): calc_strair and the locations of the x / y components of the
+// ocean fields (grid_ocn_dynu / v) and of the wind stress strax / stray (grid_atm_dynu / v), 0 T 1 U 2 E 3 N 4 NE.  NE (grid
+// 'CD') is refused, as the reference's grid_average_X2Y_1 does.  The geometry a B-grid preparation needs for E / N sources
+// (earea, narea, epm, npm; uvm is read only by U -> E / N averages, i.e. on the C grid, which holds its own) may be NULL
+// otherwise: a NULL pointer keeps what an earlier call uploaded.
+int cice_evp_hip_set_forcing_layout(int32_t calc_strair, int32_t ocn_u, int32_t ocn_v, int32_t atm_u, int32_t atm_v,
+                                    const double *earea, const double *narea, const double *uvm, const double *epm,
+                                    const double *npm)
+{
+    if (!S.ready) return fail(-1, "not initialised");
+    const int32_t code[4] = {ocn_u, ocn_v, atm_u, atm_v};
+    static const char *const name[4] = {"grid_ocn_dynu", "grid_ocn_dynv", "grid_atm_dynu", "grid_atm_dynv"};
+    for (int k = 0; k < 4; ++k) {
+        if (k >= 2 && calc_strair) break;                  // (the reference reads grid_atm only for strax / stray)
+        if (code[k] == 4)
+            return fail(-1, "forcing layout: %s = NE (grid 'CD'): the reference's grid_average_X2Y has no NE source", name[k]);
+        if (code[k] < 0 || code[k] > 3) return fail(-1, "forcing layout: %s = %d (0 T, 1 U, 2 E, 3 N)", name[k], (int)code[k]);
+    }
+    State::Forcing &G = S.forcing;
+    const double *src[5] = {earea, narea, uvm, epm, npm};
+    double **dst[5] = {&G.earea, &G.narea, &G.uvm, &G.epm, &G.npm};
+    for (int k = 0; k < 5; ++k)
+        if (src[k] && ((!*dst[k] && alloc_d(dst[k], S.n)) || h2d(*dst[k], src[k]))) return -1;
+    G.calc_strair = calc_strair != 0;
+    G.ocn[0] = ocn_u; G.ocn[1] = ocn_v;
+    G.atm[0] = G.calc_strair ? 0 : atm_u; G.atm[1] = G.calc_strair ? 0 : atm_v;
+    G.on = !(G.calc_strair && ocn_u == EVP_LOC_T && ocn_v == EVP_LOC_T);
+    HIPC(hipStreamSynchronize(S.stream));      // the caller may reuse its arrays
+    return 0;
+}
+
 int cice_evp_hip_prep(const cice_evp_hip_prep_params *pp, const double *const *tfields11,
                       const double *const *fields32, int32_t *iceTmask, int32_t *iceUmask,
                       double *strintxU, double *strintyU, double *strocnxU, double *strocnyU)
@@ -71,8 +138,13 @@ int cice_evp_hip_prep(const cice_evp_hip_prep_params *pp, const double *const *t
     State::Prep &Q = S.prep;
     if (!Q.geo) return fail(-1, "cice_evp_hip_set_prep_geometry was not called");
     if (!pp || !tfields11 || !fields32 || !iceTmask || !iceUmask) return fail(-1, "null argument");
-    for (int k = 0; k < 11; ++k)
-        if (!tfields11[k]) return fail(-1, "null T-grid field %d", k);
+    if (int rc = check_tfields(tfields11)) return rc;
+    EvpForcing F;                 // the forcing layout (cice_evp_hip_set_forcing_layout), checked before anything moves
+    {
+        const double *area[4] = {Q.tarea, Q.uarea, S.forcing.earea, S.forcing.narea};
+        const double *pm[4] = {Q.hm, S.forcing.uvm, S.forcing.epm, S.forcing.npm};
+        if (int rc = forcing_of(F, area, pm)) return rc;
+    }
     // stresses: all 12 given, or all 12 NULL = keep the copy the previous call left on the device
     // (nothing between two evp() calls touches them: ice_dyn_evp.F90 is their only writer)
     int nsig = 0;
@@ -127,27 +199,29 @@ int cice_evp_hip_prep(const cice_evp_hip_prep_params *pp, const double *const *t
     P.dt = pp->dt; P.rhoi = pp->rhoi; P.rhos = pp->rhos; P.gravit = pp->gravit;
     P.dyn_area_min = pp->dyn_area_min; P.dyn_mass_min = pp->dyn_mass_min;
     P.cosw = S.prm.cosw; P.sinw = S.prm.sinw; P.ssh_coupled = pp->ssh_stress_coupled;
+    P.F = F;
 
     evp_launch_prep1(P, S.d.nblocks, S.stream);
-    auto halo = [&](std::initializer_list<std::pair<double *, bool>> arrs) {
+    // ice_dyn_evp.F90:413-428: iceTmask; tmass, aice_init, cdn_ocn (scalars); uocn, vocn, ss_tltx/y (vectors, whatever grid
+    // they live on) and :466-469 (calc_strair branch): strairxT, strairyT -- one launch for all ten.  calc_strair = .false.:
+    // strax / stray in slots 9 / 10 are averaged as the host holds them, no exchange (:467-468): eight
+    const std::pair<double *, bool> arrs[10] = {{Q.maskd, false}, {Q.tmass, false}, {Q.t[3], false}, {Q.t[4], false}, {Q.t[5], true},
+                                                {Q.t[6], true}, {Q.t[7], true}, {Q.t[8], true}, {Q.t[9], true}, {Q.t[10], true}};
+    const int nh = S.forcing.wind_t() ? 10 : 8;
+    auto halo = [&]() {
         EvpPrepHalo H{};
-        for (const auto &a : arrs) { H.a[H.narr] = a.first; H.is_vec[H.narr] = a.second; ++H.narr; }
+        for (int k = 0; k < nh; ++k) { H.a[H.narr] = arrs[k].first; H.is_vec[H.narr] = arrs[k].second; ++H.narr; }
         H.dst = Q.c_dst; H.src = Q.c_src; H.vsign = (const signed char *)Q.c_vsign; H.n = Q.n_center;
         evp_launch_halo_center(H, S.stream);
     };
-    // ice_dyn_evp.F90:413-428: iceTmask; tmass, aice_init, cdn_ocn (scalars); uocn, vocn, ss_tltx/y (vectors)
-    // and :466-469 (calc_strair branch): strairxT, strairyT -- one launch for all ten
-    halo({{Q.maskd, false}, {Q.tmass, false}, {Q.t[3], false}, {Q.t[4], false},
-          {Q.t[5], true}, {Q.t[6], true}, {Q.t[7], true}, {Q.t[8], true}, {Q.t[9], true}, {Q.t[10], true}});
+    halo();
     if (S.plan.tfold && Q.n_tf) {
         // tripoleT: rows NY (on the fold: symmetrised, rewritten from its mirror) and NY+1 of the same ten fields, after the
         // plain ghost copies (whose sources are rows the fold step does not write); the two-pass fold launch of the C grid
         // (evp_cgrid.hip: cg_fold_reg / cg_fold_one), four fields at a time
-        const std::pair<double *, bool> arrs[10] = {{Q.maskd, false}, {Q.tmass, false}, {Q.t[3], false}, {Q.t[4], false}, {Q.t[5], true},
-                                                    {Q.t[6], true}, {Q.t[7], true}, {Q.t[8], true}, {Q.t[9], true}, {Q.t[10], true}};
-        for (int k0 = 0; k0 < 10; k0 += 4) {
+        for (int k0 = 0; k0 < nh; k0 += 4) {
             EvpCgFold F{};
-            for (int k = k0; k < std::min(k0 + 4, 10); ++k) {
+            for (int k = k0; k < std::min(k0 + 4, nh); ++k) {
                 F.x[F.nfields] = arrs[k].first;
                 F.loc[F.nfields] = 0;
                 F.isign[F.nfields] = arrs[k].second ? -1.0 : 1.0;
@@ -163,7 +237,8 @@ int cice_evp_hip_prep(const cice_evp_hip_prep_params *pp, const double *const *t
         // neighbours on other ranks (no tripole fold here: centre and corner fields mirror the same
         // cells, so the velocity exchange carries pairs of T-grid fields)
         double *pairs[5][2] = {{Q.maskd, Q.tmass}, {Q.t[3], Q.t[4]}, {Q.t[5], Q.t[6]}, {Q.t[7], Q.t[8]}, {Q.t[9], Q.t[10]}};
-        for (auto &pr : pairs) {
+        for (int q = 0; q < nh / 2; ++q) {
+            double *const *pr = pairs[q];
             if (int rc = halo_remote_pair(pr[0], pr[1], false, true)) return rc;
             if (S.plan.fold_split)       // east-west ghost cells of row NY owned elsewhere: the raw values in the staging slots
                 if (int rc = fold_seam_ghosts(pr[0], pr[1])) return rc;
@@ -172,12 +247,11 @@ int cice_evp_hip_prep(const cice_evp_hip_prep_params *pp, const double *const *t
             // the plain exchange follows the NE-corner rule: ghost cells across the fold whose CENTRE-rule source is on this
             // rank have just been overwritten with a corner-rule value from elsewhere -- the local list again (its sources
             // are interior cells)
-            halo({{Q.maskd, false}, {Q.tmass, false}, {Q.t[3], false}, {Q.t[4], false},
-                  {Q.t[5], true}, {Q.t[6], true}, {Q.t[7], true}, {Q.t[8], true}, {Q.t[9], true}, {Q.t[10], true}});
+            halo();
             // ... and where the fold row is split in x, the ghost cells whose centre-rule source lies across the fold on
             // another rank: the exchange of a shifted copy (halo_plan.h); scalars -1 (undo the exchange's sign), vectors +1
             const double fac[5][2] = {{-1, -1}, {-1, -1}, {1, 1}, {1, 1}, {1, 1}};
-            for (int q = 0; q < 5; ++q)
+            for (int q = 0; q < nh / 2; ++q)
                 if (int rc = fold_remote_pair(pairs[q][0], pairs[q][1], pairs[q][0], pairs[q][1], 0, fac[q][0], fac[q][1])) return rc;
         }
     }
@@ -351,11 +425,16 @@ int cice_evp_hip_prep_fetch(int32_t which, double *dst)
     if (!S.ready || !S.uploaded || !S.prep.geo) return fail(-1, "no prepared state");
     if (!dst) return fail(-1, "null argument");
     State::Prep &Q = S.prep;
-    const double *tab[21] = {S.in[F_AIX], S.in[F_CW], S.in[F_UOCN], S.in[F_VOCN], S.in[F_UMASSDTI], S.in[F_FM],
+#ifdef CICE_EVP_HIP_TESTING
+    constexpr int ntab = 23;            // the test build: + ss_tltxU, ss_tltyU (the forcing-layout equivalence runs)
+#else
+    constexpr int ntab = 21;
+#endif
+    const double *tab[23] = {S.in[F_AIX], S.in[F_CW], S.in[F_UOCN], S.in[F_VOCN], S.in[F_UMASSDTI], S.in[F_FM],
                              S.in[F_WATERX], S.in[F_WATERY], S.in[F_FORCEX], S.in[F_FORCEY], S.in[F_UVEL_INIT],
                              S.in[F_VVEL_INIT], Q.strtltx, Q.strtlty, Q.strairxU, Q.strairyU, Q.tmass, Q.umass,
-                             S.u[S.cur], S.v[S.cur], S.in[F_TBU]};
-    if (which < 0 || which >= 21) return fail(-1, "prep_fetch: which = %d", (int)which);
+                             S.u[S.cur], S.v[S.cur], S.in[F_TBU], Q.ss_tltxU, Q.ss_tltyU};
+    if (which < 0 || which >= ntab) return fail(-1, "prep_fetch: which = %d", (int)which);
     if (d2h(dst, tab[which])) return -1;
     HIPC(hipStreamSynchronize(S.stream));
     return 0;

@@ -6,6 +6,7 @@
 //   prep1a/prep1b   dyn_prep1                  ice_dyn_shared.F90:496-576
 //   halo_center     ice_HaloUpdate, centre      ice_dyn_evp.F90:413-428, 466-470
 //   prep_average    grid_average_X2Y T->U       ice_grid.F90:4183-4204 ('S'), 4650-4666 ('F')
+//                   ... or from U / E / N       (cice_evp_hip_set_forcing_layout: evp_forcing.h)
 //   prep2           dyn_prep2                   ice_dyn_shared.F90:586-839
 // Not a hot path (once per evp() call): one thread per cell, operation order of the
 // reference, no FMA contraction in either build mode so that it is bit-identical to it.
@@ -16,6 +17,8 @@
 #include "evp_device.h"
 
 #pragma clang fp contract(off)
+
+#include "evp_forcing.h"
 
 namespace {
 
@@ -94,7 +97,10 @@ __global__ void halo_center(EvpPrepHalo H)
     }
 }
 
-// T -> U averages on the physical cells, 0 elsewhere (work2(:,:,:) = c0 first)
+// T -> U averages on the physical cells, 0 elsewhere (work2(:,:,:) = c0 first).  LAYOUT: the ocean fields and the wind
+// stress from the locations of P.F (evp_forcing.h; a copy where they already live at U); the default instantiation is
+// today's T-grid layout
+template <bool LAYOUT>
 __device__ __forceinline__ void prep_average_cell(const EvpPrep &P, int i, int j, int bz, size_t c)
 {
     const int4 r = P.blk[bz];
@@ -108,15 +114,25 @@ __device__ __forceinline__ void prep_average_cell(const EvpPrep &P, int i, int j
         // state-masked: tmass, aice_init, cdn_ocn, uocn, vocn, ss_tltx, ss_tlty
         const double *src[7] = {P.tmass, P.t[3], P.t[4], P.t[5], P.t[6], P.t[7], P.t[8]};
         if (wtmp != 0.0)
-            for (int k = 0; k < 7; ++k) {
+            for (int k = 0; k < (LAYOUT ? 3 : 7); ++k) {
                 const double *a = src[k];
                 o[k] = (m0 * a[c] * w0 + m1 * a[c1] * w1 + m2 * a[c2] * w2 + m3 * a[c3] * w3) / wtmp;
             }
         // flux: wind stress
-        for (int k = 0; k < 2; ++k) {
-            const double *a = P.t[9 + k];
-            o[7 + k] = 0.25 * (a[c] * w0 + a[c1] * w1 + a[c2] * w2 + a[c3] * w3) / P.uarea[c];
-        }
+        if (!LAYOUT)
+            for (int k = 0; k < 2; ++k) {
+                const double *a = P.t[9 + k];
+                o[7 + k] = 0.25 * (a[c] * w0 + a[c1] * w1 + a[c2] * w2 + a[c3] * w3) / P.uarea[c];
+            }
+    }
+    if (LAYOUT) {       // ice_dyn_evp.F90:433-436 from grid_ocn_dynu / v, :467-476 from grid_atm_dynu / v or T
+        const EvpForcing &F = P.F;
+        o[3] = x2y(false, F, F.ocn[0], EVP_LOC_U, P.t[5], c, P.nx, in);
+        o[4] = x2y(false, F, F.ocn[1], EVP_LOC_U, P.t[6], c, P.nx, in);
+        o[5] = x2y(false, F, F.ocn[0], EVP_LOC_U, P.t[7], c, P.nx, in);
+        o[6] = x2y(false, F, F.ocn[1], EVP_LOC_U, P.t[8], c, P.nx, in);
+        o[7] = x2y(true, F, F.calc_strair ? EVP_LOC_T : F.atm[0], EVP_LOC_U, P.t[9], c, P.nx, in);
+        o[8] = x2y(true, F, F.calc_strair ? EVP_LOC_T : F.atm[1], EVP_LOC_U, P.t[10], c, P.nx, in);
     }
     P.umass[c] = o[0]; P.aiU[c] = o[1]; P.cdn_ocnU[c] = o[2]; P.uocnU[c] = o[3]; P.vocnU[c] = o[4];
     P.ss_tltxU[c] = o[5]; P.ss_tltyU[c] = o[6]; P.strairxU[c] = o[7]; P.strairyU[c] = o[8];
@@ -125,7 +141,7 @@ __global__ void prep_average(EvpPrep P)
 {
     int i, j, bz; size_t c;
     if (!cell_of(P, i, j, bz, c)) return;
-    prep_average_cell(P, i, j, bz, c);
+    prep_average_cell<false>(P, i, j, bz, c);
 }
 
 // dyn_prep2 (:697-838)
@@ -190,11 +206,12 @@ __global__ void prep2(EvpPrep P)
 }
 // the averages of a U-cell are read back by dyn_prep2 at that very cell only: one launch, one thread does both
 // (its own stores are visible to it)
+template <bool LAYOUT>
 __global__ void prep_average_prep2(EvpPrep P)
 {
     int i, j, bz; size_t c;
     if (!cell_of(P, i, j, bz, c)) return;
-    prep_average_cell(P, i, j, bz, c);
+    prep_average_cell<LAYOUT>(P, i, j, bz, c);
     prep2_cell(P, i, j, bz, c);
 }
 
@@ -338,7 +355,10 @@ void evp_launch_prep1(const EvpPrep &P, int nblocks, hipStream_t st)
 }
 void evp_launch_prep_average_prep2(const EvpPrep &P, int nblocks, hipStream_t st)
 {
-    hipLaunchKernelGGL(prep_average_prep2, cell_grid(P, nblocks), dim3(64), 0, st, P);
+    if (P.F.on)
+        hipLaunchKernelGGL(prep_average_prep2<true>, cell_grid(P, nblocks), dim3(64), 0, st, P);
+    else
+        hipLaunchKernelGGL(prep_average_prep2<false>, cell_grid(P, nblocks), dim3(64), 0, st, P);
 }
 void evp_launch_words_to_bytes(const int32_t *w, uint8_t *b, size_t n, hipStream_t st)
 {

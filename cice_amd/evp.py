@@ -46,6 +46,7 @@ EXPORTS = [
     "cice_evp_hip_pin_host", "cice_evp_hip_set_post_geometry", "cice_evp_hip_deformations", "cice_evp_hip_dyn_finish",
     "cice_evp_hip_halo_export", "cice_evp_hip_halo_import", "cice_evp_hip_stress_halo", "cice_evp_hip_stress_halo_available", 
     "cice_evp_hip_set_prep_geometry", "cice_evp_hip_prep", "cice_evp_hip_set_strength", "cice_evp_hip_set_tbu", "cice_evp_hip_seabed_lkd", "cice_evp_hip_seabed_prob", "cice_evp_hip_halo_mask", "cice_evp_hip_march_info", "cice_evp_hip_prep_fetch",
+    "cice_evp_hip_set_forcing_layout",
     "cice_evp_hip_addr", "cice_evp_hip_set_option", "cice_evp_hip_fetch_stresses", "cice_evp_hip_invalidate_stresses",
     "cice_evp_hip_cgrid_set_geometry", "cice_evp_hip_cgrid_run", "cice_evp_hip_cgrid_upload", "cice_evp_hip_cgrid_subcycle",
     "cice_evp_hip_cgrid_download", "cice_evp_hip_cgrid_sync", "cice_evp_hip_cgrid_deformations", "cice_evp_hip_cgrid_dyn_finish", "cice_evp_hip_cgrid_timings", "cice_evp_hip_stream_probe", 
@@ -93,6 +94,12 @@ PREP_FETCH = ["aiU", "cdn_ocnU", "uocnU", "vocnU", "umassdti", "fmU", "waterxU",
               "forceyU", "uvel_init", "vvel_init", "strtltxU", "strtltyU", "strairxU", "strairyU",
               "tmass", "umass", "uvel", "vvel"]
 PREP_FETCH_MORE = {"TbU": 20}      # further products cice_evp_hip_prep_fetch serves (not made by cice_evp_hip_prep itself)
+PREP_FETCH_TESTING = {"ss_tltxU": 21, "ss_tltyU": 22}     # ... and in the test build only
+# the test build's C-grid read-outs of a preparation under a forcing layout (cice_evp_hip_cgrid_fetch table 2)
+CGRID_FORCING_PRODUCTS = ["strairxE", "strairyN", "ss_tltxE", "ss_tltyN"]
+# forcing layout (cice_evp_hip_set_forcing_layout): location codes, and the (x, y) locations of grid_ocn / grid_atm
+LOC = {"T": 0, "U": 1, "E": 2, "N": 3, "NE": 4}
+GRID_LOC = {"A": ("T", "T"), "B": ("U", "U"), "C": ("E", "N"), "CD": ("NE", "NE")}
 
 
 class PrepParams(C.Structure):
@@ -289,6 +296,7 @@ class EvpHip:
         # the product library unless the caller asks for the test build or the environment holds one of its switches
         self.testing = testing_wanted() if testing is None else bool(testing)
         self.lib = load_library(testing=self.testing)
+        self.calc_strair = True          # the forcing layout's (set_forcing_layout): which wind-stress keys prep reads
         self._keep = keepalive
         self.shape = (dims.nblocks, dims.ny_block, dims.nx_block)
         arrs = [self._c(a) for a in (HTE, HTN, dxT, dyT, uarear, tarea)]
@@ -363,11 +371,32 @@ class EvpHip:
         _check(self.lib, self.lib.cice_evp_hip_set_prep_geometry(_ip(tm), _ip(um), *[_dp(x) for x in a]),
                "(dyn_evp_hip_set_prep_geometry)")
 
+    def set_forcing_layout(self, calc_strair: bool = True, ocn="A", atm="A", earea=None, narea=None, uvm=None, epm=None,
+                           npm=None):
+        """Where the preparation's forcing lives (both grids): ocn / atm = grid_ocn / grid_atm ('A', 'B', 'C', 'CD') or an
+        (x, y) pair of locations ('T', 'U', 'E', 'N', 'NE' or their codes); atm is read only with calc_strair False, when
+        prep / cgrid_prep take the wind stress from tfields' strax / stray.  earea, narea, epm, npm: the B grid's E / N
+        sources; uvm: U sources on the C grid (which holds all five already)."""
+        def codes(g):
+            pair = GRID_LOC[g] if isinstance(g, str) else g
+            return [LOC[v] if isinstance(v, str) else int(v) for v in pair]
+        geo = [self._c(a) if a is not None else None for a in (earea, narea, uvm, epm, npm)]
+        rc = self.lib.cice_evp_hip_set_forcing_layout(C.c_int32(1 if calc_strair else 0), *[C.c_int32(v) for v in codes(ocn) + codes(atm)],
+                                                      *[(_dp(a) if a is not None else None) for a in geo])
+        _check(self.lib, rc, "(dyn_evp_hip_set_forcing_layout)")
+        self.calc_strair = bool(calc_strair)
+
+    def _tfields11(self, tfields: dict):
+        """The tfields11 table: PREP_T, with strax / stray in the wind-stress slots under calc_strair = .false.
+        (set_forcing_layout); a field that is absent travels as NULL.  Returns (table, the arrays it points to)."""
+        keys = PREP_T[:9] + (["strairxT", "strairyT"] if self.calc_strair else ["strax", "stray"])
+        t = [self._c(tfields[k]) if tfields.get(k) is not None else None for k in keys]
+        return (_f64p * 11)(*[(_dp(a) if a is not None else None) for a in t]), t
+
     def prep(self, pp: "PrepParams", tfields: dict, state: dict):
         """state: the 12 stresses, uvel, vvel, iceUmask (previous call), optional TbU and
         strintxU/strintyU/strocnxU/strocnyU.  Returns (iceTmask, iceUmask, zeroed dict)."""
-        t = [self._c(tfields[k]) for k in PREP_T]
-        ttab = (_f64p * 11)(*[_dp(a) for a in t])
+        ttab, t = self._tfields11(tfields)
         f = [self._c(state[k]) if k in state and state[k] is not None and k in FIELDS[:12] + ["uvel", "vvel", "TbU"]
              else None for k in FIELDS]
         ftab = (_f64p * len(FIELDS))(*[(_dp(a) if a is not None else None) for a in f])
@@ -427,8 +456,7 @@ class EvpHip:
     def cgrid_prep(self, pp: "PrepParams", tfields: dict, state: dict | None, masks_prev: dict) -> dict:
         """state: the first 12 of CGRID_FIELDS as evp() is entered with them (None: keep what the device holds);
         masks_prev: iceUmask, iceEmask, iceNmask of the previous call.  Returns the four new masks."""
-        t = [self._c(tfields[k]) for k in PREP_T]
-        ttab = (_f64p * 11)(*[_dp(a) for a in t])
+        ttab, t = self._tfields11(tfields)
         stab = None
         if state is not None:
             st = [self._c(state[k]) for k in CGRID_FIELDS[:12]]
@@ -455,14 +483,23 @@ class EvpHip:
                                                                   C.c_double(gravit), C.c_double(pi), C.c_double(puny)),
                "(dyn_evp_hip_cgrid_seabed_prob)")
 
+    def cgrid_set_tb(self, TbE, TbN):
+        """Seabed stress factors computed by the host, between cgrid_prep and cgrid_prep_finish."""
+        e, n = self._c(TbE), self._c(TbN)
+        _check(self.lib, self.lib.cice_evp_hip_cgrid_set_tb(_dp(e), _dp(n)), "(dyn_evp_hip_cgrid_set_tb)")
+
     def cgrid_prep_finish(self, strength, visc_method: str = "avg_zeta"):
         a = self._c(strength)
         _check(self.lib, self.lib.cice_evp_hip_cgrid_prep_finish(_dp(a), C.c_int32(VISC_METHOD[visc_method])),
                "(dyn_evp_hip_cgrid_prep_finish)")
 
     def cgrid_fetch(self, name: str):
-        """One of CGRID_FIELDS / CGRID_INPUTS as it is on the device."""
-        table, index = (0, CGRID_FIELDS.index(name)) if name in CGRID_FIELDS else (1, CGRID_INPUTS.index(name))
+        """One of CGRID_FIELDS / CGRID_INPUTS as it is on the device (test build: CGRID_FORCING_PRODUCTS too)."""
+        if name in CGRID_FORCING_PRODUCTS:
+            self._need_testing(f"cgrid_fetch({name!r})")
+            table, index = 2, CGRID_FORCING_PRODUCTS.index(name)
+        else:
+            table, index = (0, CGRID_FIELDS.index(name)) if name in CGRID_FIELDS else (1, CGRID_INPUTS.index(name))
         out = np.zeros(self.shape)
         _check(self.lib, self.lib.cice_evp_hip_cgrid_fetch(C.c_int32(table), C.c_int32(index), _dp(out)), "(dyn_evp_hip_cgrid_fetch)")
         return out
@@ -526,7 +563,11 @@ class EvpHip:
 
     def prep_fetch(self, name: str):
         out = np.zeros(self.shape)
-        which = PREP_FETCH_MORE[name] if name in PREP_FETCH_MORE else PREP_FETCH.index(name)
+        if name in PREP_FETCH_TESTING:
+            self._need_testing(f"prep_fetch({name!r})")
+            which = PREP_FETCH_TESTING[name]
+        else:
+            which = PREP_FETCH_MORE[name] if name in PREP_FETCH_MORE else PREP_FETCH.index(name)
         _check(self.lib, self.lib.cice_evp_hip_prep_fetch(C.c_int32(which), _dp(out)),
                "(dyn_evp_hip_prep_fetch)")
         return out

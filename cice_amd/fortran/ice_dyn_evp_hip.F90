@@ -148,6 +148,13 @@ module ice_dyn_evp_hip
        real(c_double), dimension(*), intent(inout) :: strintxU, strintyU, strocnxU, strocnyU
      end function cice_evp_hip_prep
 
+     integer(c_int) function cice_evp_hip_set_forcing_layout(calc_strair, ocn_u, ocn_v, atm_u, atm_v, &
+          earea, narea, uvm, epm, npm) bind(C, name='cice_evp_hip_set_forcing_layout')
+       import :: c_int, c_int32_t, c_double
+       integer(c_int32_t), value :: calc_strair, ocn_u, ocn_v, atm_u, atm_v
+       real(c_double), dimension(*), intent(in) :: earea, narea, uvm, epm, npm
+     end function cice_evp_hip_set_forcing_layout
+
      type(c_ptr) function cice_evp_hip_addr(array) bind(C, name='cice_evp_hip_addr')
        import :: c_ptr
        type(*), dimension(*), intent(in) :: array      ! any contiguous array; no TARGET needed
@@ -306,6 +313,8 @@ module ice_dyn_evp_hip
   logical :: cgrid_geometry_set = .false.
   logical :: cgrid_pinned = .false.
   logical :: cgrid_prep_geometry_set = .false.
+  logical :: forcing_layout_set = .false.
+  logical :: wind_from_strax = .false.      ! calc_strair = .false.: the preparation averages strax / stray (ice_flux)
 
 contains
 
@@ -325,6 +334,47 @@ contains
     enddo
     call abort_ice(subname//' ERROR: '//trim(msg), file=file, line=line)
   end subroutine check
+
+!-----------------------------------------------------------------------
+! Where evp()'s forcing lives (ice_dyn_evp.F90:433-489): calc_strair, grid_ocn_dynu / v and grid_atm_dynu / v, handed to
+! the library once (cice_evp_hip_set_forcing_layout) for the preparation of either grid.  Afterwards wind_from_strax
+! tells the caller to pass strax / stray instead of strairxT / strairyT.  A 'CD' layout (NE points) aborts, as the
+! reference's grid_average_X2Y_1 does.
+  subroutine set_forcing_layout(subname)
+
+    use ice_grid, only: grid_ocn_dynu, grid_ocn_dynv, grid_atm_dynu, grid_atm_dynv, earea, narea, uvm, epm, npm
+    use icepack_intfc, only: icepack_query_parameters
+
+    character(len=*), intent(in) :: subname
+    logical :: calc_strair
+    integer(c_int32_t) :: code(4)
+
+    if (forcing_layout_set) return
+    call icepack_query_parameters(calc_strair_out=calc_strair)
+    code = [loc_code(grid_ocn_dynu), loc_code(grid_ocn_dynv), loc_code(grid_atm_dynu), loc_code(grid_atm_dynv)]
+    if (any(code(1:2) == 4) .or. (.not. calc_strair .and. any(code(3:4) == 4))) &
+       call abort_ice(subname//' ERROR: forcing on NE points (grid_ocn / grid_atm = ''CD''): '// &
+            'grid_average_X2Y has no NE source', file=__FILE__, line=__LINE__)
+    call check(cice_evp_hip_set_forcing_layout(merge(1_c_int32_t, 0_c_int32_t, calc_strair), code(1), code(2), &
+         code(3), code(4), earea, narea, uvm, epm, npm), subname, __FILE__, __LINE__)
+    wind_from_strax = .not. calc_strair
+    forcing_layout_set = .true.
+
+  contains
+
+    integer(c_int32_t) function loc_code(g)
+      character(len=*), intent(in) :: g
+      select case (trim(g))
+      case ('T');  loc_code = 0
+      case ('U');  loc_code = 1
+      case ('E');  loc_code = 2
+      case ('N');  loc_code = 3
+      case ('NE'); loc_code = 4
+      case default; loc_code = -1      ! (the library refuses it with a message)
+      end select
+    end function loc_code
+
+  end subroutine set_forcing_layout
 
 !-----------------------------------------------------------------------
 ! Replaces dyn_evp1d_init.  Everything it needs is public module data:
@@ -473,7 +523,7 @@ contains
     use ice_grid, only: tmask, umask, hm, tarea, uarea
     use ice_state, only: aice, vice, vsno, uvel, vvel, aice_init, strength, aicen, vicen
     use ice_arrays_column, only: Cdn_ocn
-    use ice_flux, only: uocn, vocn, ss_tltx, ss_tlty, strairxT, strairyT, &
+    use ice_flux, only: uocn, vocn, ss_tltx, ss_tlty, strairxT, strairyT, strax, stray, &
          stressp_1, stressp_2, stressp_3, stressp_4, stressm_1, stressm_2, stressm_3, stressm_4, &
          stress12_1, stress12_2, stress12_3, stress12_4, strintxU, strintyU, strocnxU, strocnyU, &
          taubxU, taubyU, TbU, hwater
@@ -519,12 +569,17 @@ contains
     pp%dyn_area_min = dyn_area_min
     pp%dyn_mass_min = dyn_mass_min
     pp%ssh_stress_coupled = merge(1_c_int32_t, 0_c_int32_t, trim(ssh_stress) == 'coupled')
+    call set_forcing_layout(subname)
 
     tf(1) = cice_evp_hip_addr(aice);      tf(2) = cice_evp_hip_addr(vice);     tf(3) = cice_evp_hip_addr(vsno)
     tf(4) = cice_evp_hip_addr(aice_init); tf(5) = cice_evp_hip_addr(Cdn_ocn)
-    tf(6) = cice_evp_hip_addr(uocn);      tf(7) = cice_evp_hip_addr(vocn)
+    tf(6) = cice_evp_hip_addr(uocn);      tf(7) = cice_evp_hip_addr(vocn)       ! (at the grid_ocn points)
     tf(8) = cice_evp_hip_addr(ss_tltx);   tf(9) = cice_evp_hip_addr(ss_tlty)
-    tf(10) = cice_evp_hip_addr(strairxT); tf(11) = cice_evp_hip_addr(strairyT)
+    if (wind_from_strax) then             ! calc_strair = .false. (ice_dyn_evp.F90:467-468): at the grid_atm points
+       tf(10) = cice_evp_hip_addr(strax); tf(11) = cice_evp_hip_addr(stray)
+    else
+       tf(10) = cice_evp_hip_addr(strairxT); tf(11) = cice_evp_hip_addr(strairyT)
+    endif
     f32 = c_null_ptr
     ! the 12 stresses travel in and out at every call (CICE's arrays current after every evp()) -- unless the host opted in to
     ! device-resident stresses (dyn_evp_hip_keep_stresses_resident) and the device copy is current: then they stay where
@@ -866,21 +921,21 @@ contains
 ! (seabed stress factors, by the reference's own routines on the host: libm exp()) and 938-1099 (the loop).  Public
 ! module data is taken from its modules; the arguments are the private arrays of ice_dyn_evp the loop hands back.
 ! compute_strength: fills ice_state's strength from the new iceTmask and halo-updates it (icepack_ice_strength,
-! :596-608, 727-728).  Conditions: calc_strair = .true., ocean forcing on the T grid (grid_ocn_dynu = grid_ocn_dynv =
-! 'T').  The host's own code after the loop that reads products of the preparation (dyn_finish at E / N points: aiX,
-! fmX, uocnX, vocnX, cdn_ocnX and dyn_prep2's index lists) gets them through dyn_evp_hip_cgrid_fetch_forcing and from
-! the masks.
+! :596-608, 727-728).  Every forcing layout the reference accepts: ocean on grid A / B / C, the wind stress from
+! strairxT / strairyT (calc_strair) or strax / stray on grid A / B / C (set_forcing_layout; 'CD' aborts).  The host's
+! own code after the loop that reads products of the preparation (dyn_finish at E / N points: aiX, fmX, uocnX, vocnX,
+! cdn_ocnX and dyn_prep2's index lists) gets them through dyn_evp_hip_cgrid_fetch_forcing and from the masks.
   subroutine dyn_evp_hip_cgrid_evp_body(dt, compute_strength, ratiodxN, ratiodxNr, ratiodyE, ratiodyEr, &
                                         zetax2T, etax2T, etax2U, shearU, deltaU)
 
     use ice_blocks, only: nx_block, ny_block, block, get_block
     use ice_domain_size, only: max_blocks
     use ice_domain, only: nblocks, blocks_ice
-    use ice_grid, only: tmask, umaskCD, emask, nmask, grid_ocn_dynu, grid_ocn_dynv
+    use ice_grid, only: tmask, umaskCD, emask, nmask
     use ice_state, only: aice, vice, vsno, aice_init, strength, aicen, vicen, uvel, vvel, uvelE, vvelE, uvelN, vvelN, &
                          divu, shear, vort
     use ice_arrays_column, only: Cdn_ocn
-    use ice_flux, only: uocn, vocn, ss_tltx, ss_tlty, strairxT, strairyT, stresspT, stressmT, stress12T, stress12U, &
+    use ice_flux, only: uocn, vocn, ss_tltx, ss_tlty, strairxT, strairyT, strax, stray, stresspT, stressmT, stress12T, stress12U, &
                         strintxE, strintyN, taubxE, taubyN, TbU, TbE, TbN, hwater, rdg_conv, rdg_shear
     use ice_dyn_shared, only: ndte, fcor_blk, fcorE_blk, fcorN_blk, iceTmask, iceUmask, iceEmask, iceNmask, &
                               dyn_area_min, dyn_mass_min, ssh_stress, seabed_stress, seabed_stress_method, &
@@ -902,7 +957,6 @@ contains
     integer(int_kind), allocatable :: ixT(:), jxT(:), ixE(:), jxE(:), ixN(:), jxN(:), ixU(:), jxU(:)
     integer :: nall, iblk, i, j, nT, nE, nN, nU
     type(block) :: tb
-    logical :: calc_strair
     character(len=*), parameter :: subname = '(dyn_evp_hip_cgrid_evp_body)'
 
     if (.not. initialised) call abort_ice(subname//' ERROR: dyn_evp_hip_init not called', &
@@ -911,10 +965,7 @@ contains
        call compute_strength()      ! (whatever the host does there among the tasks happens on this one too)
        return
     endif
-    call icepack_query_parameters(calc_strair_out=calc_strair)
-    if (.not. calc_strair .or. trim(grid_ocn_dynu) /= 'T' .or. trim(grid_ocn_dynv) /= 'T') &
-       call abort_ice(subname//' ERROR: needs calc_strair = .true. and ocean forcing on the T grid', &
-            file=__FILE__, line=__LINE__)
+    call set_forcing_layout(subname)
     nall = nx_block*ny_block*max_blocks
     call cgrid_ensure_geometry(ratiodxN, ratiodxNr, ratiodyE, ratiodyEr)
     if (.not. cgrid_prep_geometry_set) then
@@ -939,7 +990,11 @@ contains
     tf(4) = cice_evp_hip_addr(aice_init); tf(5) = cice_evp_hip_addr(Cdn_ocn)
     tf(6) = cice_evp_hip_addr(uocn);      tf(7) = cice_evp_hip_addr(vocn)
     tf(8) = cice_evp_hip_addr(ss_tltx);   tf(9) = cice_evp_hip_addr(ss_tlty)
-    tf(10) = cice_evp_hip_addr(strairxT); tf(11) = cice_evp_hip_addr(strairyT)
+    if (wind_from_strax) then
+       tf(10) = cice_evp_hip_addr(strax); tf(11) = cice_evp_hip_addr(stray)
+    else
+       tf(10) = cice_evp_hip_addr(strairxT); tf(11) = cice_evp_hip_addr(strairyT)
+    endif
     ! the state travels in at every call: the host's arrays stay the master copy (a host that never touches them
     ! between two evp() calls can pass null pointers to the C ABI instead and save the copies)
     s12 = [cice_evp_hip_addr(uvelE), cice_evp_hip_addr(vvelE), cice_evp_hip_addr(uvelN), cice_evp_hip_addr(vvelN), &
@@ -1134,6 +1189,9 @@ contains
     character(len=*), parameter :: subname = '(dyn_evp_hip_finalize)'
     if (initialised) call check(cice_evp_hip_finalize(), subname, __FILE__, __LINE__)
     initialised = .false.
+    ! the library's finalize drops the forcing layout too: a later dyn_evp_hip_init must hand it over again
+    forcing_layout_set = .false.
+    wind_from_strax = .false.
     empty_rank = .false.
     pinned = .false.
   end subroutine dyn_evp_hip_finalize

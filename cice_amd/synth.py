@@ -404,3 +404,13 @@ def cgrid_prep_inputs(g: dict, cg: dict, case: str = "full", seed: int = 5, coup
     prev = {k: ((rng.random((ny, nx)) < 0.8) & (static[m] != 0)).astype(np.int32)
             for k, m in (("iceUmask", "umaskCD"), ("iceEmask", "emask"), ("iceNmask", "nmask"))}
     return t, static, prev
+
+
+def located_forcing(shape, seed: int = 1) -> dict:
+    """Ocean currents, sea-surface tilt and wind stress for the forcing-layout tests (cice_evp_hip_set_forcing_layout), as
+    block arrays of `shape` with every cell set, ghost cells included: the preparation exchanges the ocean fields whatever
+    grid they are on, and averages strax / stray as the host holds them, so their ghost cells are part of the input.  The
+    values stand for any grid's points."""
+    rng = np.random.Generator(np.random.PCG64(seed))
+    f = lambda scale: scale * (2.0 * rng.random(shape) - 1.0)
+    return dict(uocn=f(0.2), vocn=f(0.2), ss_tltx=f(2e-6), ss_tlty=f(2e-6), strax=f(0.1), stray=f(0.1))

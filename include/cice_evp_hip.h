@@ -214,7 +214,12 @@ int cice_evp_hip_dyn_finish(double *strocnxU, double *strocnyU);
  * strintxU/strintyU/strocnxU/strocnyU (may be NULL): zeroed off the ice on the host arrays.
  * On a split domain the T-grid halos use the same transport as the velocities (collective call);
  * on a tripole domain too, whatever the rank layout (a fold row split over ranks in x: through the
- * exchange of a shifted copy, cice_amd/csrc/halo_plan.h).                                        */
+ * exchange of a shifted copy, cice_amd/csrc/halo_plan.h).
+ * Forcing layout (both grids; cice_evp_hip_set_forcing_layout, below): by default the ocean fields and the wind stress
+ * are on the T grid (calc_strair = .true., grid_ocn = 'A').  Otherwise slots 5-8 hold uocn, vocn, ss_tltx, ss_tlty at the
+ * grid_ocn points (halo-updated as cell-centre vectors, as the reference does whatever grid they live on), and with
+ * calc_strair = .false. slots 9 / 10 hold strax / stray (ice_flux) at the grid_atm points: averaged as given, ghost cells
+ * included, with no halo update (ice_dyn_evp.F90:467-468); NULL there is refused.                                     */
 typedef struct cice_evp_hip_prep_params {
     double dt;                 /* dynamics time step (dyn_prep2's Xmass/dt)                    */
     double rhoi, rhos, gravit; /* icepack_query_parameters                                      */
@@ -227,6 +232,19 @@ int cice_evp_hip_prep(const cice_evp_hip_prep_params *pp, const double *const *t
                       const double *const *fields32, int32_t *iceTmask, int32_t *iceUmask,
                       double *strintxU, double *strintyU, double *strocnxU, double *strocnyU);
 int cice_evp_hip_set_strength(const double *strength);
+/* Where the forcing of the preparation phase lives, for cice_evp_hip_prep and cice_evp_hip_cgrid_prep; call it after
+ * cice_evp_hip_init, before the preparation, once or whenever it changes.  Never called: today's layout (calc_strair = 1,
+ * everything on T).  calc_strair: icepack's calc_strair; ocn_u, ocn_v: grid_ocn_dynu / _dynv; atm_u, atm_v:
+ * grid_atm_dynu / _dynv (read only when calc_strair = 0) -- codes 0 T, 1 U, 2 E, 3 N, 4 NE.  grid_ocn / grid_atm 'A' ->
+ * (0, 0), 'B' -> (1, 1), 'C' -> (2, 3); 'CD' -> (4, 4) is refused (the reference's grid_average_X2Y_1 aborts on NE
+ * sources).  The averages follow grid_average_X2Y (ice_grid.F90:3817-4036): a field already at the target is copied
+ * whole, ghost cells included; otherwise 'S' (weights uarea / earea / narea, masks uvm / epm / npm) or 'F' (divided by
+ * the target's area) on the physical cells, 0 elsewhere.  earea, narea, epm, npm (ice_grid): the B grid's preparation
+ * needs them when a source is E or N; uvm: U sources on the C grid (which holds all of them already, NULL is fine
+ * there).  NULL keeps an earlier call's copy.  Returns non-zero, layout unchanged, on a bad code.                     */
+int cice_evp_hip_set_forcing_layout(int32_t calc_strair, int32_t ocn_u, int32_t ocn_v, int32_t atm_u, int32_t atm_v,
+                                    const double *earea, const double *narea, const double *uvm, const double *epm,
+                                    const double *npm);
 /* Seabed stress factor TbU for the coming subcycle loop, when the host computes it: evp() does so
  * AFTER dyn_prep2 (which zeroes it, ice_dyn_shared.F90:706) from the new iceUmask
  * (seabed_stress_factor_LKD / _prob, ice_dyn_evp.F90:770-826), so it cannot travel with
@@ -275,8 +293,9 @@ int cice_evp_hip_cgrid_set_geometry(const double *const *static23);
 int cice_evp_hip_cgrid_run(int32_t ndte, int32_t visc_method, double *const *fields19,
                            const double *const *inputs23, const int32_t *iceTmask, const int32_t *iceUmask,
                            const int32_t *iceEmask, const int32_t *iceNmask);
-/* The preparation phase of evp() for grid_ice = 'C' on the device (ice_dyn_evp.F90:383-735, calc_strair branch, forcing on the
- * T grid): dyn_prep1, the T-grid halo updates, the state-masked / flux averages T -> U, E, N (grid_average_X2Y 'S' / 'F'),
+/* The preparation phase of evp() for grid_ice = 'C' on the device (ice_dyn_evp.F90:383-735; forcing on the T grid, or where
+ * cice_evp_hip_set_forcing_layout puts it: ocean A / B / C, calc_strair true or false with the atmosphere on A / B / C):
+ * dyn_prep1, the T-grid halo updates, the state-masked / flux averages T (U, E, N) -> U, E, N (grid_average_X2Y 'S' / 'F'),
  * dyn_prep2 at U, N and E points, the stresses zeroed off the ice, the velocity exchanges and face -> face / face -> corner
  * averages -- everything the loop reads except the ice strength (Icepack's) is computed where the loop will read it:
  * 11 T-grid arrays travel in instead of 14 + 23.

@@ -135,6 +135,9 @@ int cice_evp_hip_fold_split_plan(int32_t which, int32_t *count, int32_t *cells);
  * hang on; [1] fold_rows (0 none here, 1 all here, 2 shared); [2] stress symmetrisation needs another rank;
  * [3] a cell-centre ghost needs another rank; [4] ... across the fold.  Returns the number written.           */
 int cice_evp_hip_plan_flags(int32_t *flags, int32_t n);
+/* Read-outs of the forcing-layout tests (no entry of their own): cice_evp_hip_prep_fetch serves which = 21, 22 = ss_tltxU,
+ * ss_tltyU; cice_evp_hip_cgrid_fetch serves table 2, index 0..3 = strairxE, strairyN, ss_tltxE, ss_tltyN as the last
+ * cice_evp_hip_cgrid_prep under a forcing layout other than the default averaged them (every cell).                    */
 
 
 #ifdef __cplusplus

@@ -17,6 +17,7 @@ import numpy as np
 
 ROOT = Path(__file__).resolve().parents[1]
 sys.path.insert(0, str(ROOT))
+sys.path.insert(0, str(ROOT / "tests"))      # (--forcing: the numpy restatement of the averages, tests/forcing_layout_ref.py)
 
 
 def main():
@@ -43,6 +44,13 @@ def main():
     ap.add_argument("--visc", default="avg_zeta")
     ap.add_argument("--expect-resident", action="store_true",
                     help="fail unless the on-chip resident kernel with remote neighbours ran")
+    ap.add_argument("--forcing", default="",
+                    help="with --prep: a forcing layout 'calc_strair,grid_ocn,grid_atm', e.g. 0,C,B "
+                         "(cice_evp_hip_set_forcing_layout): the ocean fields and strax / stray at those points")
+    ap.add_argument("--wind-ghosts", default="exchange", choices=["exchange", "own"],
+                    help="with --forcing and calc_strair 0: strax / stray ghost cells as an exchange would fill them, or "
+                         "(own) different on the split run -- the averages must read them as given: compared with the numpy "
+                         "restatement on this rank's inputs, and the wind-dependent arrays are not compared with the one-rank run")
     a = ap.parse_args()
     import torch
     import torch.distributed as dist
@@ -66,6 +74,57 @@ def main():
     st = synth.make_state(g, case="full", seed=7, warm=True)
     pr = synth.make_primary(g, "full", seed=9) if a.prep else None
     scal = synth.evp_scalars(120)
+    own_wind = bool(a.forcing) and a.wind_ghosts == "own"
+    if a.forcing:
+        calc_s, ocn_s, atm_s = a.forcing.split(",")
+        layout = (calc_s == "1", ocn_s, atm_s)
+        fglob = synth.located_forcing((ny, nx), seed=23)       # global [ny][nx]: values at whatever points the layout names
+        cgf = synth.cgrid_geometry(g)
+
+    def apply_forcing(core, dc, r, exchange, tf, area, pm):
+        """--forcing on this rank: the layout, the ocean fields and strax / stray at its points (tf updated in place); with
+        --wind-ghosts own on the split run, strax / stray ghost cells that no exchange would give.  Returns the mismatches
+        of the wind averages against the restatement on this rank's own inputs (checked after the preparation)."""
+        from forcing_layout_ref import GRID_LOC, x2y
+        calc, ocn, atm = layout
+        (ou, ov), (au, av) = GRID_LOC[ocn], GRID_LOC[atm]
+        where = {"T": "center", "U": "NEcorner", "E": "Eface", "N": "Nface"}
+        for k, loc in (("uocn", ou), ("vocn", ov), ("ss_tltx", ou), ("ss_tlty", ov)):
+            tf[k] = np.array(dc.scatter(fglob[k], r, fold=(where[loc], -1.0)), dtype=np.float64, order="C", copy=True)
+        plain = {}
+        for k, loc in (("strax", au), ("stray", av)):
+            v = np.array(dc.scatter(fglob[k], r, fold=(where[loc], -1.0)), dtype=np.float64, order="C", copy=True)
+            plain[k] = v.copy()
+            if exchange and own_wind:
+                for b in dc.local_blocks(r):
+                    ring = np.ones(v[b.local].shape, dtype=bool)
+                    ring[1:1 + b.gny, 1:1 + b.gnx] = False
+                    v[b.local][ring] = 1.5 * v[b.local][ring] + 0.125
+            tf[k] = v
+        geo = {k: dc.scatter(cgf[k], r, fill=(1.0 if k.endswith("area") else 0.0),
+                             fold=({"earea": "Eface", "epm": "Eface", "narea": "Nface", "npm": "Nface"}.get(k, "NEcorner"), 1.0))
+               for k in ("earea", "narea", "uvm", "epm", "npm")}
+        core.set_forcing_layout(calc, ocn, atm, **geo)
+        for k, loc in (("E", "earea"), ("N", "narea")):
+            area.setdefault(k, geo[loc])
+        for k, m in (("U", "uvm"), ("E", "epm"), ("N", "npm")):
+            pm.setdefault(k, geo[m])
+        if not (exchange and own_wind) or calc:
+            return lambda fetch, targets: []
+        blocks = [(b.ilo, b.ihi, b.jlo, b.jhi) for b in dc.local_blocks(r)]
+
+        def check(fetch, targets):
+            bad = []
+            for name, key, src, dst in ((targets[0], "strax", au, targets[0][-1]), (targets[1], "stray", av, targets[1][-1])):
+                want = x2y("F", tf[key], src, dst, area, pm, blocks)
+                asif = x2y("F", plain[key], src, dst, area, pm, blocks)
+                got = fetch(name)
+                if not np.array_equal(got.view(np.uint64), want.view(np.uint64)):
+                    bad.append((name + " vs restatement (own ghost cells)", int((got != want).sum())))
+                if np.array_equal(want, asif):
+                    bad.append((name + ": the changed ghost cells are not read", 0))
+            return bad
+        return check
 
     def run_cgrid(dc, r, exchange):
         cg = synth.cgrid_geometry(g)
@@ -77,7 +136,7 @@ def main():
         static, state, inputs, masks = synth.cgrid_scatter(dc, r, cg, state, inputs, masks)
         d, keep = evp.make_dims(dc, r)
         core = evp.EvpHip(d, evp.make_params(scal, strict=True), static["dyE"], static["dxN"], static["dxT"], static["dyT"],
-                          1.0 / static["uarea"], static["tarea"], keepalive=keep)
+                          1.0 / static["uarea"], static["tarea"], keepalive=keep, testing=(True if a.forcing else None))
         try:
             if exchange:
                 blobs = [None] * world
@@ -108,7 +167,13 @@ def main():
                 core.cgrid_set_prep_geometry(static)
                 pp = evp.PrepParams(dt=3600.0, rhoi=917.0, rhos=330.0, gravit=9.80616, dyn_area_min=1e-11, dyn_mass_min=1e-10,
                                     ssh_stress_coupled=0)
+                wind_check = None
+                if a.forcing:
+                    area = {"T": static["tarea"], "U": static["uarea"], "E": static["earea"], "N": static["narea"]}
+                    pm = {"T": static["hm"], "U": static["uvm"], "E": static["epm"], "N": static["npm"]}
+                    wind_check = apply_forcing(core, dc, r, exchange, tb, area, pm)
                 newm = core.cgrid_prep(pp, tb, state, prevb)
+                wind_bad = wind_check(core.cgrid_fetch, ("strairxE", "strairyN")) if wind_check else []
                 if exchange and a.maskhalo:
                     pass                  # (the mask above was built from the synthetic loop masks: not used together with --prep)
                 core.cgrid_prep_finish(inputs["strength"], a.visc)
@@ -129,8 +194,10 @@ def main():
             out = core.cgrid_download()
             out["_halomask"] = hm
             if a.prep:                    # what the preparation produced, too
-                for k in ("aiE", "forcexE", "emassdti", "aiN", "forceyN", "uocnN", "uvelE_init"):
+                for k in ("aiE", "forcexE", "emassdti", "aiN", "forceyN", "uocnN", "uvelE_init") + (
+                        ("uocnE", "vocnE", "vocnN", "strairxE", "strairyN") if a.forcing else ()):
                     out["prep_" + k] = core.cgrid_fetch(k)
+                out["_wind_bad"] = wind_bad
                 for k, v in newm.items():
                     out["prep_" + k] = v.astype(np.float64)
             return out, core.timings(), t
@@ -153,8 +220,12 @@ def main():
         assert tim["halo_transport"] == "mailbox", tim
         exchanged = ("uvelE", "vvelE", "uvelN", "vvelN", "uvel", "vvel", "stresspT", "stressmT", "stress12U", "zetax2T",
                      "etax2T", "shearU")
-        bad = []
+        bad = list(got.get("_wind_bad", []))
+        # (--wind-ghosts own: what depends on the wind stress is checked against the restatement above, not the one-rank run)
+        wind_dep = set(evp.CGRID_FIELDS) | {"prep_forcexE", "prep_forceyN", "prep_strairxE", "prep_strairyN"} if own_wind else set()
         for k in list(evp.CGRID_FIELDS) + [q for q in ref if q.startswith("prep_")]:
+            if k in wind_dep:
+                continue
             want = dcN.scatter(ref[k][0][1:-1, 1:-1], rank)
             for b in dcN.local_blocks(rank):
                 w = want[b.local][1:1 + b.gny, 1:1 + b.gnx]
@@ -191,7 +262,7 @@ def main():
         # (the test transport of --march exists in the test build only; everything else runs the product library unless the
         # environment holds one of the test build's switches)
         core = evp.EvpHip(d, evp.make_params(scal, strict=True), geo["HTE"], geo["HTN"], geo["dxT"],
-                          geo["dyT"], geo["uarear"], geo["tarea"], keepalive=keep, testing=(True if a.march else None))
+                          geo["dyT"], geo["uarear"], geo["tarea"], keepalive=keep, testing=(True if a.march or a.forcing else None))
         try:
             if exchange:
                 blobs = [None] * world
@@ -244,9 +315,16 @@ def main():
                         ring = np.ones(tf[k][b.local].shape, dtype=bool)
                         ring[1:1 + b.gny, 1:1 + b.gnx] = False
                         tf[k][b.local][ring] = 1.5 * tf[k][b.local][ring] + 0.125
+                wind_check = None
+                if a.forcing:
+                    area = {"T": static["tarea"], "U": static["uarea"]}
+                    pm = {"T": static["hm"]}
+                    wind_check = apply_forcing(core, dc, r, exchange, tf, area, pm)
                 tmk, umk, _ = core.prep(pp, tf, {k: sc(v) for k, v in pr["state"].items()})
                 core.set_strength(fields["strength"])
-                extra = {k: core.prep_fetch(k) for k in ("forcexU", "umassdti", "uvel_init", "aiU")}
+                extra = {k: core.prep_fetch(k) for k in ("forcexU", "umassdti", "uvel_init", "aiU") + (
+                    ("uocnU", "vocnU", "strairxU", "strairyU") if a.forcing else ())}
+                extra["_wind_bad"] = wind_check(core.prep_fetch, ("strairxU", "strairyU")) if wind_check else []
                 extra["iceTmask"] = tmk.astype(np.float64)
             else:
                 core.upload(fields, tm, um)
@@ -289,7 +367,7 @@ def main():
                             dcN.proc_shape)
     got, tim, t_us = run(dcN, rank, True)
     assert tim["halo_transport"] == "mailbox", tim
-    bad = []
+    bad = list(got.get("_wind_bad", []))
     if a.march:
         mi = got["_march"]
         if not (mi["mode"] == 1 and mi["last_call"] and mi["declined"] == 0 and mi["passes"] > 0):
@@ -297,9 +375,11 @@ def main():
         want_ring = "direct stores (HIP IPC)" if os.environ.get("CICE_EVP_HIP_MARCH_DIRECT") == "1" and os.environ.get("CICE_EVP_HIP_MARCH_OVERLAP", "0") != "1" else None
         if want_ring and mi["ring"] != want_ring:
             bad.append(("ring of the marching path not exchanged through the inboxes", mi))
+    wind_dep = {"uvel", "vvel", "stressp_1", "stressm_3", "stress12_4", "strintxU", "taubyU", "forcexU", "strairxU",
+                "strairyU"} if own_wind else set()      # (--wind-ghosts own: checked against the restatement instead)
     for k in ("uvel", "vvel", "stressp_1", "stressm_3", "stress12_4", "strintxU", "taubyU",
-              "forcexU", "umassdti", "uvel_init", "aiU", "iceTmask"):
-        if k not in got:
+              "forcexU", "umassdti", "uvel_init", "aiU", "iceTmask", "uocnU", "vocnU", "strairxU", "strairyU"):
+        if k not in got or k in wind_dep:
             continue
         want = dcN.scatter(ref[k][0][1:-1, 1:-1], rank)
         for b in dcN.local_blocks(rank):
