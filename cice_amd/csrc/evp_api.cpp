@@ -1072,6 +1072,11 @@ int cice_evp_hip_describe_path(char *buf, int32_t n)
                   (!S.plan.peers.empty() && !S.direct.on && !S.direct.why.empty()) ? (S.direct.why + ")").c_str() : "",
                   M.mode == 1 ? "on" : (M.mode == 0 ? "off" : "undecided"), (M.mode == 0 && !M.why.empty()) ? " -- " : "",
                   (M.mode == 0 && !M.why.empty()) ? M.why.c_str() : "", ring, (int)S.d.nblocks, (int)(S.msk.on ? S.msk.n_send : S.n_send));
+    const std::string cg = cgrid_schedule();
+    if (!cg.empty()) {
+        const size_t used = std::strlen(buf);
+        std::snprintf(buf + used, (size_t)n - used, "; %s", cg.c_str());
+    }
     return 0;
 }
 
@@ -1083,6 +1088,52 @@ int cice_evp_hip_plan_flags(int32_t *flags, int32_t n)
     int32_t k = 0;
     for (; flags && k < n && k < 5; ++k) flags[k] = v[k];
     return k;
+}
+
+// The C grid's fold step and exchange lists (halo_plan.h: cg_*), see the testing header
+int cice_evp_hip_cgrid_fold_xplan(int32_t loc, int32_t *info4, int32_t *count, int32_t *dst, int32_t *a, int32_t *b, int32_t *flip)
+{
+    if (loc < 0 || loc > 3) return fail(-1, "bad location %d", (int)loc);
+    const HaloPlan &P = S.plan;
+    if (info4) {
+        info4[0] = P.cg_split ? 1 : 0;
+        info4[1] = P.cg_tail;
+        info4[2] = (int32_t)P.cg_peers.size();
+        info4[3] = 0;
+        for (const HaloPeer &p : P.cg_peers) info4[3] += (int32_t)p.send_src.size();
+    }
+    const FoldList &L = P.cg_fold[loc];
+    if (count) *count = (int32_t)L.dst.size();
+    for (size_t k = 0; k < L.dst.size(); ++k) {
+        if (dst) dst[k] = L.dst[k];
+        if (a) a[k] = L.a[k];
+        if (b) b[k] = L.b[k];
+        if (flip) flip[k] = L.flip[k];
+    }
+    return 0;
+}
+
+int cice_evp_hip_cgrid_fold_xpeers(int32_t *peer5, int32_t *send_src, int32_t *send_dst, int32_t *recv_dst, int32_t *recv_gid)
+{
+    size_t q = 0, so = 0, ro = 0;
+    for (const HaloPeer &p : S.plan.cg_peers) {
+        if (peer5) {
+            peer5[5 * q] = p.rank; peer5[5 * q + 1] = (int32_t)p.send_src.size(); peer5[5 * q + 2] = (int32_t)p.recv_dst.size();
+            peer5[5 * q + 3] = p.n_ghost_send; peer5[5 * q + 4] = p.n_ghost_recv;
+        }
+        for (size_t k = 0; k < p.send_src.size(); ++k) {
+            if (send_src) send_src[so + k] = p.send_src[k];
+            if (send_dst) send_dst[so + k] = p.send_dst[k];
+        }
+        for (size_t k = 0; k < p.recv_dst.size(); ++k) {
+            if (recv_dst) recv_dst[ro + k] = p.recv_dst[k];
+            if (recv_gid) recv_gid[ro + k] = p.recv_gid[k];
+        }
+        so += p.send_src.size();
+        ro += p.recv_dst.size();
+        ++q;
+    }
+    return 0;
 }
 
 int cice_evp_hip_seam_plan(int32_t *counts3, int32_t *seam_a, int32_t *seam_b, int32_t *seam_pole,

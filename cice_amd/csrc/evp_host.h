@@ -184,6 +184,18 @@ struct State {
     int8_t *h_recv_sign = nullptr;
     double *sendbuf = nullptr, *recvbuf = nullptr;
     int n_send = 0, n_recv = 0;
+    // the C grid's exchange on a tripole grid whose fold rows have more than one owner (HaloPlan::cg_peers, cg_split): ghost
+    // cells + raw fold sources into the staging slots behind the C-grid arrays, the peers concatenated; mailbox tables as for
+    // the lists above, on a channel of the mailbox of their own (own flags, sequence, inbox: the peers are not the plan's)
+    struct CgX {
+        int n_send = 0, n_recv = 0;
+        int32_t *send_src = nullptr, *recv_dst = nullptr;
+        int8_t *recv_sign = nullptr;
+        double *sendbuf = nullptr, *recvbuf = nullptr;
+        double **send_addr = nullptr;
+        unsigned *send_pstride = nullptr;
+        unsigned **peer_flag = nullptr;
+    } cgx;
     // masked halo of the in-loop velocity exchange (ice_HaloMask, ice_boundary.F90:889-1062): the entries whose
     // halomask is set, compacted; the unmasked lists serve every other exchange
     struct Masked {
@@ -204,6 +216,7 @@ struct State {
         bool exported = false;
         void *mailbox = nullptr;     // [flags][seq][err][inbox x 2 parities]
         size_t bytes = 0, inbox_off = 0, rec_off = 0, raw_off = 0;
+        size_t cg_off = 0;           // the C grid's fold channel (0: none): CG_DIRECT_* below
         std::vector<void *> opened;  // hipIpcOpenMemHandle results
         EvpDirect *d_dx = nullptr;   // device copy of the argument block (exchange riding in the subcycle launch)
         EvpDirect *d_dx_m = nullptr; // the same with the masked lists (cice_evp_hip_halo_mask)
@@ -321,6 +334,11 @@ inline const char *env(const char *k) { return std::getenv(k); }
 constexpr size_t DIRECT_SEQ_OFF = (size_t)EVP_DIRECT_MAXPEER * EVP_DIRECT_FLAG_STRIDE * sizeof(unsigned);
 constexpr size_t DIRECT_ERR_OFF = DIRECT_SEQ_OFF + 64;
 constexpr size_t DIRECT_INBOX_OFF = DIRECT_ERR_OFF + 64;
+// ... and the C grid's fold channel, at Direct::cg_off: CG_DIRECT_MAXPEER flag lines, seq, err, inbox
+constexpr int CG_DIRECT_MAXPEER = 16;
+constexpr size_t CG_DIRECT_SEQ_OFF = (size_t)CG_DIRECT_MAXPEER * EVP_DIRECT_FLAG_STRIDE * sizeof(unsigned);
+constexpr size_t CG_DIRECT_ERR_OFF = CG_DIRECT_SEQ_OFF + 64;
+constexpr size_t CG_DIRECT_INBOX_OFF = CG_DIRECT_ERR_OFF + 64;
 
 uint64_t host_identity();   // evp_host_mailbox.cpp
 // evp_host_common.cpp
@@ -347,6 +365,9 @@ int check_tfields(const double *const *tfields11);
 // evp_host_loop.cpp
 void fill_direct(EvpDirect &D);
 int halo_remote_pair(double *a, double *bb, bool masked = false, bool has_tail = false);
+// the C grid's exchange of two arrays (with staging tail) through S.cgx: ghost cells and fold sources, one handshake
+int cgrid_fold_exchange(double *a, double *bb);
+void fill_direct_cg(EvpDirect &D);      // ... its mailbox form
 // centre-kind fields across a tripole fold whose row is split over ranks (halo_plan.h): dstA[d] <- fa * (the exchange of the
 // shifted copy of srcA)[d] for d in the list, likewise B.  kind 0: the centre-field ghost cells of the preparation phase,
 // 1: the ghost row of the stress symmetrisation
@@ -380,5 +401,6 @@ int march_direct_error();     // a ring neighbour never signalled (direct exchan
 int direct_check_error();
 // evp_host_cgrid.cpp
 void cgrid_free();
+std::string cgrid_schedule();     // "" unless the C grid runs with the fold exchange (tripole fold rows on several ranks)
 
 }  // namespace evp_host

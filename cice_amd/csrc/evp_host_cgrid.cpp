@@ -10,7 +10,9 @@
 // by the B-grid path's velocity exchange (halo_remote_pair: mailbox stores over xGMI, or RCCL point-to-point) run on
 // pairs of the loop's arrays after the launch that produces them -- the same points at which the reference calls
 // ice_HaloUpdate.  Tripole grids, u-fold and T-fold (tripoleT): a fold step per exchange point from host-built lists
-// (halo_plan.cpp: build_fold_list / build_fold_list_tfold), the blocks next to the fold on one rank.
+// (halo_plan.cpp: build_fold_list).  Where the blocks next to the fold have more than one owner, every exchange goes
+// through the C grid's own lists instead (HaloPlan::cg_peers): the ghost cells of the rows up to the fold and, behind them
+// in the same exchange, the raw values the fold step of another rank reads, into staging slots behind the C-grid arrays.
 // =====================================================================
 #include <cmath>
 #include <set>
@@ -182,15 +184,21 @@ static void fill(EvpCgrid &A)
     A.plane = S.plane;
 }
 
-static bool remote() { return !S.plan.peers.empty(); }
+static bool remote() { return !S.plan.peers.empty() || !S.plan.cg_peers.empty(); }
+// the blocks next to the tripole fold have more than one owner: the C grid's exchange (ghost cells + fold sources into
+// staging slots n + t of every exchanged array) replaces the velocity lists at every exchange point
+static bool fold_exchange() { return CG.tripole && S.plan.cg_split; }
 // ghost cells owned by other ranks, for two of the loop's arrays (no-op on one rank).  Every exchange inside the loop
 // goes through the masked halo when the host has handed one over (maskhalo_dyn: evp() builds it for the C grid as the
 // five-point dilation of iceTmask, ice_dyn_evp.F90:739-770, and passes halo_info_mask to every dyn_haloUpdate of the
 // loop, :965-1096); copies inside a rank -- the pushes of the kernels -- are never masked, as in ice_HaloMask.
 #define XCHG(a, b)                                             \
     do {                                                       \
-        if (remote())                                          \
+        if (fold_exchange()) {                                 \
+            if (int rc_ = cgrid_fold_exchange((a), (b))) return rc_; \
+        } else if (remote()) {                                 \
             if (int rc_ = halo_remote_pair((a), (b), true)) return rc_; \
+        }                                                      \
     } while (0)
 
 // tripole: the fold step of up to four fields after the launch that produced them (what their ice_HaloUpdate does
@@ -473,7 +481,8 @@ static int build_fold_lists()
     CG.fold_maxn = 0;
     for (int loc = 0; loc < 4; ++loc) {
         FoldList L;
-        build_fold_list(d, loc, L);
+        if (S.plan.cg_split) L = S.plan.cg_fold[loc];      // (operands >= S.n: staging slots the exchange fills)
+        else build_fold_list(d, loc, L);
         const std::vector<int32_t> &dst = L.dst, &a = L.a, &bb = L.b;
         const std::vector<uint8_t> &flip = L.flip;
         CGridState::Fold &Fd = CG.fold[loc];
@@ -955,6 +964,15 @@ static int res_subcycles(int ndte, bool first)
 
 int finish_upload(int32_t visc_method);
 
+std::string cgrid_schedule()
+{
+    if (!CG.geo || !fold_exchange()) return "";
+    char buf[160];
+    std::snprintf(buf, sizeof buf, "C grid: five phases + fold exchange, fold rows on %d ranks (%d staging slots here)", S.plan.cg_fold_ranks,
+                  S.plan.cg_tail);
+    return buf;
+}
+
 }  // namespace evp_host
 
 using namespace evp_host;
@@ -970,14 +988,13 @@ int cice_evp_hip_cgrid_set_geometry(const double *const *static23)
     // physical row there, halo_plan.cpp: build_fold_list_tfold)
     const bool tfold = S.d.ns_boundary_type == CICE_EVP_BND_TRIPOLET;
     const bool tripole = S.d.ns_boundary_type == CICE_EVP_BND_TRIPOLE || tfold;
-    if (tripole && P.fold_rows == 2)
-        return fail(-4, "C-grid EVP on a tripole grid: the blocks next to the fold (rows NY-1, NY; tripoleT: NY-2 .. NY) must all "
-                        "be on one rank (split the domain in y only); here they are shared with other ranks");
     cgrid_free();
     CG.tripole = tripole;
     CG.tfold = tfold;
+    // (the blocks next to the fold on several ranks: every exchanged array carries the staging slots of the fold exchange)
+    const size_t nf = S.n + (tripole && P.cg_split ? (size_t)P.cg_tail : 0);
     for (auto &p : CG.f)
-        if (alloc_d(&p, S.n)) return -1;
+        if (alloc_d(&p, nf)) return -1;
     if (alloc_d(&CG.inslab, (size_t)CG_NIN * S.n) || alloc_d(&CG.gslab, (size_t)CG_NG * S.n)) return -1;
     for (int k = 0; k < CG_NIN; ++k) CG.in[k] = CG.inslab + (size_t)k * S.n;
     for (int k = 0; k < CG_NG; ++k) {
@@ -987,7 +1004,7 @@ int cice_evp_hip_cgrid_set_geometry(const double *const *static23)
     }
     if (alloc_d(&CG.strengthU, S.n) || alloc_d(&CG.s12alt, S.n) || alloc_d(&CG.fac[0], S.n) || alloc_d(&CG.fac[1], S.n)) return -1;
     HIPC(hipMalloc((void **)&CG.d_flags, sizeof(unsigned)));
-    if (!S.plan.peers.empty() && alloc_d(&CG.umaskd, S.n)) return -1;
+    if (remote() && alloc_d(&CG.umaskd, nf)) return -1;
     HIPC(hipMalloc((void **)&CG.mask, S.n));
     HIPC(hipMalloc((void **)&CG.mask4, 4 * S.n * sizeof(int32_t)));
     // ghost images: for every interior cell the ghost cells of this rank that mirror it (what ice_HaloUpdate copies)
@@ -1020,7 +1037,7 @@ int cice_evp_hip_cgrid_set_geometry(const double *const *static23)
     HIPC(hipMalloc((void **)&CG.img_dst, dst.size() * sizeof(int)));
     HIPC(hipMemcpyAsync(CG.img_slot, CG.h_img_slot.data(), S.n * sizeof(int), hipMemcpyHostToDevice, S.stream));
     HIPC(hipMemcpyAsync(CG.img_dst, dst.data(), dst.size() * sizeof(int), hipMemcpyHostToDevice, S.stream));
-    if (tripole && P.fold_rows == 1)             // (ranks without the fold rows run the same schedule with empty lists)
+    if (tripole && (P.fold_rows == 1 || P.cg_split))   // (ranks without the fold rows run the same schedule with empty lists)
         if (int rc = build_fold_lists()) return rc;
     if (!tripole && S.plan.peers.empty() && S.d.nx_block >= 3 && S.d.ny_block >= 3) {
         if (int rc = build_one_tables(static23)) return rc;
@@ -1111,7 +1128,11 @@ int finish_upload(int32_t visc_method)
         EvpCgrid A;
         fill(A);
         evp_launch_cgrid_umask(A, CG.umaskd, 0, S.stream);
-        if (int rc = halo_remote_pair(CG.umaskd, CG.umaskd)) return rc;
+        if (fold_exchange()) {
+            if (int rc = cgrid_fold_exchange(CG.umaskd, CG.umaskd)) return rc;
+        } else if (int rc = halo_remote_pair(CG.umaskd, CG.umaskd)) {
+            return rc;
+        }
         evp_launch_cgrid_umask(A, CG.umaskd, 1, S.stream);
     }
     if (visc_method == 1) {
@@ -1201,6 +1222,10 @@ int cice_evp_hip_cgrid_download(double *const *fields19)
     if (CG.res.launched) {       // a resident launch whose waits gave up has written nothing back: the caller's arrays stay untouched
         HIPC(hipStreamSynchronize(S.stream));
         if (int rc = res_check_error()) return rc;
+    }
+    if (fold_exchange() && S.direct.on) {        // a fold exchange whose wait gave up: nothing goes back to the caller
+        HIPC(hipStreamSynchronize(S.stream));
+        if (int rc = direct_check_error()) return rc;
     }
     CopyBatch B;
     for (int k = 0; k < CG_NF; ++k)
@@ -1310,7 +1335,7 @@ int cice_evp_hip_cgrid_set_prep_geometry(const int32_t *tmask, const int32_t *um
 {
     if (!S.ready || !CG.geo) return fail(-1, "C-grid EVP: geometry not set");
     if (!tmask || !umaskCD || !emask || !nmask || !fcor_blk || !fcorE_blk || !fcorN_blk) return fail(-1, "null argument");
-    if (S.plan.center_fold_remote || (S.plan.tfold && S.plan.center_tf_remote))
+    if (S.plan.center_fold_remote || (S.plan.tfold && S.plan.center_tf_remote) || (CG.tripole && S.plan.cg_split))
         return fail(-9, "device preparation: T-grid ghost cells across the tripole fold live on other ranks here; keep "
                         "evp()'s host preparation (cice_evp_hip_cgrid_run) on this configuration");
     CGridState::Prep &Q = CG.prep;
@@ -1603,6 +1628,9 @@ int cice_evp_hip_cgrid_timings(double *out, int32_t n)
     if (n >= 13) out[12] = (double)CG.one.ntiles_e;   // ... and the windows cg_one keeps beside it
     if (n >= 14) out[13] = (double)CG.one.strip_seg;  // ... rows per segment
     if (n >= 15) out[14] = (double)CG.one.strip_len;  // ... 1: it forms six of the eight lengths from dxN, dyE
+    if (n >= 16) out[15] = fold_exchange() ? 1.0 : 0.0;            // tripole: the blocks next to the fold on several ranks (fold exchange)
+    if (n >= 17) out[16] = CG.tripole ? (double)S.plan.cg_fold_ranks : 0.0;   // ... on so many ranks
+    if (n >= 18) out[17] = fold_exchange() ? (double)S.plan.cg_tail : 0.0;    // ... staging slots of this rank
     return 0;
 }
 

@@ -94,6 +94,8 @@ void free_all()
     S.msk = State::Masked();
     F(S.sendbuf);
     F(S.recvbuf);
+    F(S.cgx.send_src); F(S.cgx.recv_dst); F(S.cgx.recv_sign); F(S.cgx.sendbuf); F(S.cgx.recvbuf); F(S.cgx.send_addr); F(S.cgx.send_pstride); F(S.cgx.peer_flag);
+    S.cgx = State::CgX();
     for (void *q : S.direct.opened) (void)hipIpcCloseMemHandle(q);
     F(S.direct.mailbox); F(S.direct.d_dx); F(S.direct.d_dx_m); F(S.direct.d_cnt); F(S.direct.send_addr); F(S.direct.send_pstride); F(S.direct.peer_flag);
     S.direct = State::Direct();
@@ -320,6 +322,25 @@ int upload_lists()
         HIPC(hipMemcpy(S.h_recv_dst, rd.data(), rd.size() * sizeof(int32_t), hipMemcpyHostToDevice));
         HIPC(hipMemcpy(S.h_recv_sign, rs.data(), rs.size(), hipMemcpyHostToDevice));
         HIPC(hipMalloc((void **)&S.recvbuf, 2 * rd.size() * sizeof(double)));
+    }
+    if (P.cg_split) {        // the C grid's exchange (HaloPlan::cg_peers)
+        std::vector<int32_t> cs, cr;
+        std::vector<int8_t> cg;
+        for (const HaloPeer &p : P.cg_peers) {
+            cs.insert(cs.end(), p.send_src.begin(), p.send_src.end());
+            cr.insert(cr.end(), p.recv_dst.begin(), p.recv_dst.end());
+            cg.insert(cg.end(), p.recv_sign.begin(), p.recv_sign.end());
+        }
+        State::CgX &X = S.cgx;
+        X.n_send = (int)cs.size();
+        X.n_recv = (int)cr.size();
+        if (up32(cs, X.send_src) || up32(cr, X.recv_dst)) return -1;
+        if (X.n_send) HIPC(hipMalloc((void **)&X.sendbuf, 2 * cs.size() * sizeof(double)));
+        if (X.n_recv) {
+            HIPC(hipMalloc((void **)&X.recv_sign, cg.size()));
+            HIPC(hipMemcpy(X.recv_sign, cg.data(), cg.size(), hipMemcpyHostToDevice));
+            HIPC(hipMalloc((void **)&X.recvbuf, 2 * cr.size() * sizeof(double)));
+        }
     }
     return 0;
 }

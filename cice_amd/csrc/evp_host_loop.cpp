@@ -71,6 +71,59 @@ int halo_remote_pair(double *a, double *bb, bool masked, bool has_tail)
     return 0;
 }
 
+// The C grid on a tripole grid whose fold rows have more than one owner: ghost cells of the rows up to the fold and the raw
+// fold sources (into the staging slots behind a and bb) in ONE exchange through the C grid's lists -- the fold sources ride
+// after the ghost cells of each peer, as the B grid's seam values do.  Never masked: the plan's any_fold_exchange holds on
+// such a layout, so cice_evp_hip_halo_mask leaves every rank's in-loop exchange unmasked too.
+// Mailbox form: the channel of its own at Direct::cg_off (flags, sequence, inbox), handshakes with the C grid's peers only.
+void fill_direct_cg(EvpDirect &D)
+{
+    const State::CgX &X = S.cgx;
+    fill_direct(D, false);
+    char *ch = (char *)S.direct.mailbox + S.direct.cg_off;
+    D.n_send = X.n_send;
+    D.n_recv = X.n_recv;
+    D.n_recv_slots = std::max(X.n_recv, 1);
+    D.npeers = (int)S.plan.cg_peers.size();
+    D.send_src = X.send_src;
+    D.send_addr = X.send_addr;
+    D.send_pstride = X.send_pstride;
+    D.recv_dst = X.recv_dst;
+    D.recv_sign = (const signed char *)X.recv_sign;
+    D.recv_slot = nullptr;
+    D.flags_in = (unsigned *)ch;
+    D.seq = (unsigned *)(ch + CG_DIRECT_SEQ_OFF);
+    D.err = (int *)(ch + CG_DIRECT_ERR_OFF);
+    D.inbox = (double *)(ch + CG_DIRECT_INBOX_OFF);
+    D.peer_flag = X.peer_flag;
+}
+
+int cgrid_fold_exchange(double *a, double *bb)
+{
+    const State::CgX &X = S.cgx;
+    if (S.plan.cg_peers.empty()) return 0;       // (its own channel: only the ranks that trade entries take part)
+    if (S.direct.on) {
+        EvpDirect D;
+        fill_direct_cg(D);
+        evp_launch_halo_direct(D, a, bb, S.stream);
+        return 0;
+    }
+    if (!S.have_comm) return fail(-2, "remote halo needed but neither cice_evp_hip_comm_init nor cice_evp_hip_halo_import was called");
+    evp_launch_halo_pack(a, bb, X.send_src, X.sendbuf, X.n_send, S.stream);
+    size_t so = 0, ro = 0;
+    NCCLC(ncclGroupStart());
+    for (const HaloPeer &p : S.plan.cg_peers) {
+        const size_t ns = p.send_src.size(), nr = p.recv_dst.size();
+        if (ns) NCCLC(ncclSend(X.sendbuf + 2 * so, 2 * ns, ncclDouble, p.rank, S.comm, S.stream));
+        if (nr) NCCLC(ncclRecv(X.recvbuf + 2 * ro, 2 * nr, ncclDouble, p.rank, S.comm, S.stream));
+        so += ns;
+        ro += nr;
+    }
+    NCCLC(ncclGroupEnd());
+    evp_launch_halo_unpack(a, bb, X.recv_dst, (const signed char *)X.recv_sign, X.recvbuf, X.n_recv, S.stream);
+    return 0;
+}
+
 static int foldx_setup();
 
 int fold_seam_ghosts(double *a, double *b)

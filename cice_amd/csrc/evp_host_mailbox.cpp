@@ -18,6 +18,11 @@ struct HaloBlob {
     int32_t can_res, pad_;         // this rank can run the resident kernel with remote neighbours
     hipIpcMemHandle_t handle;
     struct { int32_t rank, recv_off, count, flag_idx; } peer[EVP_DIRECT_MAXPEER];
+    // the C grid's fold exchange (HaloPlan::cg_peers): a channel of its own inside the mailbox -- flag lines, seq, err and
+    // inbox at cg_off (0: none) -- with its own peers, so that it needs nothing of the velocity halo's handshake
+    uint64_t cg_off, cg_slots;
+    int32_t cg_npeers, cg_pad_;
+    struct { int32_t rank, recv_off, count, flag_idx; } cg[CG_DIRECT_MAXPEER];
 };
 static_assert(sizeof(HaloBlob) <= CICE_EVP_HIP_HALO_BLOB, "HaloBlob must fit CICE_EVP_HIP_HALO_BLOB");
 constexpr uint32_t HALO_BLOB_MAGIC = 0x45565048u;   // "EVPH"
@@ -36,6 +41,8 @@ int direct_export(HaloBlob &B)
     State::Direct &X = S.direct;
     const int np = (int)S.plan.peers.size();
     if (np > EVP_DIRECT_MAXPEER) return fail(-8, "mailbox halo: %d peers > %d", np, EVP_DIRECT_MAXPEER);
+    const int ncg = (int)S.plan.cg_peers.size();
+    if (ncg > CG_DIRECT_MAXPEER) return fail(-8, "mailbox halo: the C grid's fold exchange has %d peers > %d", ncg, CG_DIRECT_MAXPEER);
     // resident kernel across GPUs: its record buffers must be writable by the neighbours, so they
     // live in the mailbox allocation (one IPC handle)
     bool want_res = resident_possible(true) && !S.plan.peers.empty() &&
@@ -48,6 +55,11 @@ int direct_export(HaloBlob &B)
         X.inbox_off = DIRECT_INBOX_OFF;
         X.bytes = X.inbox_off + 2 * 2 * (size_t)std::max(S.n_recv, 1) * sizeof(double);
         X.bytes = (X.bytes + 255) & ~(size_t)255;
+        if (S.plan.cg_split) {      // the C grid's channel
+            X.cg_off = X.bytes;
+            X.bytes += CG_DIRECT_INBOX_OFF + 2 * 2 * (size_t)std::max(S.cgx.n_recv, 1) * sizeof(double);
+            X.bytes = (X.bytes + 255) & ~(size_t)255;
+        }
         if (want_res) { rec_off = X.bytes; X.bytes += 2 * rec_stride; }
         X.rec_off = rec_off;
         if (want_res && S.plan.tail > 0) { X.raw_off = X.bytes; X.bytes += 2 * raw_stride; }
@@ -104,6 +116,17 @@ int direct_export(HaloBlob &B)
         B.peer[q].flag_idx = q;
         ro += (int)p.recv_dst.size();
     }
+    B.cg_off = X.cg_off;
+    B.cg_slots = (uint64_t)std::max(S.cgx.n_recv, 1);
+    B.cg_npeers = ncg;
+    for (int q = 0, co = 0; q < ncg; ++q) {
+        const HaloPeer &c = S.plan.cg_peers[q];
+        B.cg[q].rank = c.rank;
+        B.cg[q].recv_off = co;
+        B.cg[q].count = (int)c.recv_dst.size();
+        B.cg[q].flag_idx = q;
+        co += (int)c.recv_dst.size();
+    }
     X.exported = true;
     return 0;
 }
@@ -157,6 +180,45 @@ int direct_import(const HaloBlob *blobs, int nranks)
         return 0;
     };
     if (up(X.send_addr, send_addr) || up(X.send_pstride, send_pstride) || up(X.peer_flag, peer_flag)) return -1;
+    if (S.plan.cg_split) {      // the C grid's channel: where its entries land in the peers' inboxes, my flag line there
+        const int ncg = (int)S.plan.cg_peers.size();
+        std::vector<double *> ca((size_t)std::max(S.cgx.n_send, 1), nullptr);
+        std::vector<unsigned> cp((size_t)std::max(S.cgx.n_send, 1), 0u);
+        std::vector<unsigned *> cf((size_t)std::max(ncg, 1), nullptr);
+        size_t co = 0;
+        for (int q = 0; q < ncg; ++q) {
+            const HaloPeer &c = S.plan.cg_peers[q];
+            if (c.rank < 0 || c.rank >= nranks) return fail(-8, "mailbox halo: C-grid peer rank %d out of range", c.rank);
+            const HaloBlob &B = blobs[c.rank];
+            if (B.magic != HALO_BLOB_MAGIC || B.version != 1 || B.rank != c.rank || !B.cg_off)
+                return fail(-8, "mailbox halo: rank %d has no C-grid fold channel", c.rank);
+            if (B.host_id != host_identity()) return fail(-8, "mailbox halo: rank %d is on another host", c.rank);
+            int e = -1;
+            for (int k = 0; k < B.cg_npeers; ++k)
+                if (B.cg[k].rank == S.d.rank) e = k;
+            if (e < 0 || B.cg[e].count != (int)c.send_src.size())
+                return fail(-8, "mailbox halo: rank %d expects %d C-grid fold entries from this rank, plan sends %d", c.rank,
+                            e < 0 ? -1 : B.cg[e].count, (int)c.send_src.size());
+            char *base = nullptr;
+            if (B.pid == (int64_t)getpid()) base = (char *)(uintptr_t)B.base;
+            else if (mapped.count(c.rank)) base = mapped[c.rank];
+            else {
+                void *ptr = nullptr;
+                HIPC(hipIpcOpenMemHandle(&ptr, B.handle, hipIpcMemLazyEnablePeerAccess));
+                X.opened.push_back(ptr);
+                base = (char *)ptr;
+            }
+            mapped[c.rank] = base;
+            char *ch = base + B.cg_off;
+            cf[q] = (unsigned *)ch + (size_t)B.cg[e].flag_idx * EVP_DIRECT_FLAG_STRIDE;
+            for (size_t k = 0; k < c.send_src.size(); ++k) {
+                ca[co + k] = (double *)(ch + CG_DIRECT_INBOX_OFF) + 2 * ((size_t)B.cg[e].recv_off + k);
+                cp[co + k] = (unsigned)(2 * B.cg_slots);
+            }
+            co += c.send_src.size();
+        }
+        if (up(S.cgx.send_addr, ca) || up(S.cgx.send_pstride, cp) || up(S.cgx.peer_flag, cf)) return -1;
+    }
     S.msk.h_send_addr = send_addr;          // kept for cice_evp_hip_halo_mask (compacted copies of these tables)
     S.msk.h_send_pstride = send_pstride;
     // resident kernel with neighbours on other GPUs: only if EVERY rank can run it
@@ -254,6 +316,7 @@ int direct_probe()
                 hu[c] = gid + 1.0;
                 hv[c] = -2.0 * (gid + 1.0);
             }
+    const std::vector<double> hu0(hu), hv0(hv);
     HIPC(hipMemcpyAsync(S.u[0], hu.data(), S.nuv * sizeof(double), hipMemcpyHostToDevice, S.stream));
     HIPC(hipMemcpyAsync(S.v[0], hv.data(), S.nuv * sizeof(double), hipMemcpyHostToDevice, S.stream));
     EvpDirect D;
@@ -279,6 +342,38 @@ int direct_probe()
                 return fail(-8, "mailbox halo probe: ghost %d from rank %d holds %.17g, expected %.17g",
                             (int)p.recv_dst[k], p.rank, hu[p.recv_dst[k]], want);
         }
+    if (S.plan.cg_split) {
+        // the C grid's channel (every rank: cg_split is global): ghost cells AND the staging slots behind the arrays must
+        // receive the global number of the cell they stand for
+        const size_t nc = S.n + (size_t)S.plan.cg_tail;
+        std::vector<double> cu(nc, 0.0), cv(nc, 0.0);
+        std::copy(hu0.begin(), hu0.begin() + S.n, cu.begin());
+        std::copy(hv0.begin(), hv0.begin() + S.n, cv.begin());
+        double *du = nullptr, *dv = nullptr;
+        if (alloc_d(&du, nc) || alloc_d(&dv, nc)) return -1;
+        HIPC(hipMemcpyAsync(du, cu.data(), nc * sizeof(double), hipMemcpyHostToDevice, S.stream));
+        HIPC(hipMemcpyAsync(dv, cv.data(), nc * sizeof(double), hipMemcpyHostToDevice, S.stream));
+        EvpDirect C;
+        fill_direct_cg(C);
+        for (int rep = 0; rep < 3; ++rep) evp_launch_halo_direct(C, du, dv, S.stream);
+        HIPC(hipMemcpyAsync(cu.data(), du, nc * sizeof(double), hipMemcpyDeviceToHost, S.stream));
+        HIPC(hipMemcpyAsync(cv.data(), dv, nc * sizeof(double), hipMemcpyDeviceToHost, S.stream));
+        HIPC(hipMemcpyAsync(&err, C.err, sizeof(int), hipMemcpyDeviceToHost, S.stream));
+        HIPC(hipStreamSynchronize(S.stream));
+        (void)hipFree(du);
+        (void)hipFree(dv);
+        if (err) {
+            HIPC(hipMemset(C.err, 0, sizeof(int)));
+            return fail(-8, "mailbox halo probe (C-grid fold exchange): peer %d never signalled", S.plan.cg_peers[err - 1].rank);
+        }
+        for (const HaloPeer &p : S.plan.cg_peers)
+            for (size_t k = 0; k < p.recv_dst.size(); ++k) {
+                const double want = (double)p.recv_gid[k] + 1.0;
+                if (cu[p.recv_dst[k]] != want || cv[p.recv_dst[k]] != -2.0 * want)
+                    return fail(-8, "mailbox halo probe: C-grid %s %d from rank %d holds %.17g, expected %.17g",
+                                (size_t)p.recv_dst[k] >= S.n ? "staging slot" : "ghost", (int)p.recv_dst[k], p.rank, cu[p.recv_dst[k]], want);
+            }
+    }
     return 0;
 }
 
@@ -289,6 +384,11 @@ int direct_check_error()
     HIPC(hipMemcpy(&e, (char *)S.direct.mailbox + DIRECT_ERR_OFF, sizeof(int), hipMemcpyDeviceToHost));
     if (e) return fail(-8, "mailbox halo: rank %d never signalled within the time-out (CICE_EVP_HIP_HALO_TIMEOUT_MS)",
                        S.plan.peers[e - 1].rank);
+    if (S.direct.cg_off) {
+        HIPC(hipMemcpy(&e, (char *)S.direct.mailbox + S.direct.cg_off + CG_DIRECT_ERR_OFF, sizeof(int), hipMemcpyDeviceToHost));
+        if (e) return fail(-8, "mailbox halo (C-grid fold exchange): rank %d never signalled within the time-out (CICE_EVP_HIP_HALO_TIMEOUT_MS)",
+                           S.plan.cg_peers[e - 1].rank);
+    }
     return 0;
 }
 

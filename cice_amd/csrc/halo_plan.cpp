@@ -68,6 +68,173 @@ Src resolve(const cice_evp_hip_dims &d, int ig, int jg)
     return s;
 }
 
+// The fold step of the C grid for the blocks `blks` (their local index b, interior rectangle in array numbering, global origin):
+// one entry per cell of rows NY / NY+1, ghost columns included, in block, row, column order.  own(ig, jg), ig in 1..NX, jg in
+// NY-2 .. NY: the operand that stands for the raw value of interior cell (ig, jg) -- an offset, a staging slot, or -1 (no owner).
+// u-fold (ice_boundary.F90:1626-1722): row NY of NE-corner fields pairs i <-> NX-i (poles NX/2, NX), of N-face fields i <-> NX+1-i;
+// the ghost row NY+1 mirrors with offsets (0,0) centre, (1,1) NE corner, (1,0) E face, (0,1) N face.  A point ON the fold is
+// averaged with its partner even when the partner's block was eliminated (the buffer holds 0: b = -2).
+// T-fold (ice_boundary.F90:1563-1622 offsets and symmetrisation, :1686-1722 copy-out): rows NY and NY+1 take column
+// NX-ig+1-ioffset of the rows NY-joffset and NY-1-joffset, offsets (ioffset, joffset) = centre (-1, 0), NE corner (0, 1), E face
+// (0, 0), N face (-1, 1); centre and E-face fields lie ON the fold: their top row is made symmetric first (pairs i <-> NX-i+2,
+// i = 2..NX/2, resp. i <-> NX+1-i, i = 1..NX/2) -- an entry then holds the pair in the reference's order (a = the lower column)
+// and flip says which half the destination is.
+struct FoldBlk { int b, ilo, ihi, jlo, jhi, gi0, gj0; };
+template <class Own>
+void fold_entries(const cice_evp_hip_dims &d, const std::vector<FoldBlk> &blks, int loc, Own &&own, FoldList &L)
+{
+    const int NX = d.nx_global, NY = d.ny_global, nx = d.nx_block, ng = d.nghost;
+    const size_t plane = (size_t)nx * d.ny_block;
+    const bool tf = d.ns_boundary_type == CICE_EVP_BND_TRIPOLET;
+    auto wrap = [&](int ig) {
+        while (ig < 1) ig += NX;
+        while (ig > NX) ig -= NX;
+        return ig;
+    };
+    auto add = [&](int dd, int aa, int bb, int fl) { L.dst.push_back(dd); L.a.push_back(aa); L.b.push_back(bb); L.flip.push_back((uint8_t)fl); };
+    auto pair = [&](int dd, int ia, int ib, int fl) {
+        const int pa = own(wrap(ia), NY), pb = own(wrap(ib), NY);
+        add(dd, pa, pb >= 0 ? pb : -2, fl);
+    };
+    const int ioff = (loc == 0 || loc == 3) ? -1 : 0, joff = (loc == 1 || loc == 3) ? 1 : 0;   // (T-fold)
+    const bool on_fold = (loc == 0 || loc == 2);
+    for (const FoldBlk &B : blks)
+        for (int j = B.jlo - ng; j <= B.jhi + ng; ++j) {
+            const int jg = B.gj0 + (j - B.jlo);
+            if (jg != NY && jg != NY + 1) continue;
+            for (int i = B.ilo - ng; i <= B.ihi + ng; ++i) {
+                const int ig = wrap(B.gi0 + (i - B.ilo));
+                const int dd = (int)((size_t)B.b * plane + (size_t)(j - 1) * nx + (i - 1));
+                if (tf) {
+                    const int m = wrap(NX - ig + 1 - ioff);
+                    if (on_fold && jg == NY && m != ig) {      // a pair of the symmetrised row
+                        const int lo = std::min(ig, m), hi = std::max(ig, m);
+                        pair(dd, lo, hi, ig == lo ? 0 : 1);
+                    } else {
+                        add(dd, own(m, (jg == NY ? NY : NY - 1) - joff), -1, 1);
+                    }
+                    continue;
+                }
+                if (jg == NY) {
+                    if (loc == 1) {                           // NE corner: pairs i <-> NX-i, poles NX/2 and NX
+                        if (ig == NX / 2 || ig == NX) add(dd, own(ig, NY), -1, 1);
+                        else if (ig < NX / 2) pair(dd, ig, NX - ig, 0);
+                        else pair(dd, NX - ig, ig, 1);
+                    } else if (loc == 3) {                    // N face: pairs i <-> NX+1-i
+                        if (ig <= NX / 2) pair(dd, ig, NX + 1 - ig, 0);
+                        else pair(dd, NX + 1 - ig, ig, 1);
+                    }
+                    continue;                                 // centre / E face: the top row is an ordinary row
+                }
+                const int is = (loc == 0 || loc == 3) ? NX - ig + 1 : NX - ig;
+                add(dd, own(wrap(is), (loc == 0 || loc == 2) ? NY : NY - 1), -1, 1);
+            }
+        }
+}
+
+// The C grid's fold step and, when the blocks next to the fold have more than one owner, its exchange lists (halo_plan.h:
+// cg_*).  Every rank runs the same enumeration for every rank R, so that a value R needs appears at the same position of R's
+// recv list and of its owner's send list -- no set-up traffic, as for the lists above.
+void build_cg_fold(const cice_evp_hip_dims &d, const Table &T, HaloPlan &plan)
+{
+    const int NX = d.nx_global, NY = d.ny_global, ng = d.nghost, nx = d.nx_block, me = d.rank;
+    const size_t plane = (size_t)nx * d.ny_block;
+    const bool tfold = d.ns_boundary_type == CICE_EVP_BND_TRIPOLET;
+    const int jfold = tfold ? NY - 2 : NY - 1;           // first row the fold step reads
+    {
+        std::map<int, int> owners;
+        for (const HaloBlock &B : T.blk)
+            if (B.owner >= 0 && B.gj0 + B.gny - 1 >= jfold) owners[B.owner] = 1;
+        plan.cg_fold_ranks = (int)owners.size();
+        plan.cg_split = owners.size() > 1;
+    }
+    std::map<int, HaloPeer> peers;
+    if (plan.cg_split) {
+        // ghost cells of rows up to NY (T-fold NY-1) whose source another rank owns: plain copies.  The fold step writes
+        // everything above (and, u-fold, the east-west ghost cells of row NY of NE-corner / N-face fields, after this copy)
+        const int jmax = tfold ? NY - 1 : NY;
+        for (const auto &kv : T.by_rank) {
+            const int R = kv.first;
+            for (int kb : kv.second) {
+                const HaloBlock &B = T.blk[kb];
+                const int ilo = ng + 1, jlo = ng + 1, ihi = ng + B.gnx, jhi = ng + B.gny;
+                for (int j = jlo - ng; j <= jhi + ng; ++j) {
+                    const int jg = B.gj0 + (j - jlo);
+                    if (jg > jmax) continue;
+                    for (int i = ilo - ng; i <= ihi + ng; ++i) {
+                        if (i >= ilo && i <= ihi && j >= jlo && j <= jhi) continue;
+                        const Src src = resolve(d, B.gi0 + (i - ilo), jg);
+                        if (src.outside) continue;
+                        const int ks = T.find(src.ig, src.jg);
+                        if (ks < 0 || T.blk[ks].owner < 0 || T.blk[ks].owner == R) continue;   // (zero fill / local image)
+                        const HaloBlock &S = T.blk[ks];
+                        const int32_t dst = (int32_t)((size_t)B.local * plane + (size_t)(j - 1) * nx + (i - 1));
+                        const int32_t off = (int32_t)((size_t)S.local * plane + (size_t)(ng + (src.jg - S.gj0)) * nx + (ng + (src.ig - S.gi0)));
+                        if (R == me) {
+                            HaloPeer &p = peers[S.owner];
+                            p.rank = S.owner;
+                            p.recv_dst.push_back(dst);
+                            p.recv_sign.push_back(1);
+                            p.recv_gid.push_back((int32_t)((src.ig - 1) + (size_t)NX * (src.jg - 1)));
+                        } else if (S.owner == me) {
+                            HaloPeer &p = peers[R];
+                            p.rank = R;
+                            p.send_src.push_back(off);
+                            p.send_dst.push_back(dst);
+                            p.send_sign.push_back(1);
+                        }
+                    }
+                }
+            }
+        }
+        for (auto &kv : peers) { kv.second.n_ghost_send = (int)kv.second.send_src.size(); kv.second.n_ghost_recv = (int)kv.second.recv_dst.size(); }
+    }
+    for (const auto &kv : T.by_rank) {
+        const int R = kv.first;
+        if (R != me && !plan.cg_split) continue;
+        const int32_t nR = (int32_t)(plane * kv.second.size());
+        std::map<int64_t, int32_t> slot_of;                  // global cell of another rank -> staging slot of R
+        auto own = [&](int ig, int jg) -> int32_t {
+            const int k = T.find(ig, jg);
+            if (k < 0 || T.blk[k].owner < 0) return -1;
+            const HaloBlock &B = T.blk[k];
+            const int32_t off = (int32_t)((size_t)B.local * plane + (size_t)(ng + (jg - B.gj0)) * nx + (ng + (ig - B.gi0)));
+            if (B.owner == R) return off;
+            const int64_t key = (int64_t)jg * (NX + 1) + ig;
+            auto it = slot_of.find(key);
+            if (it != slot_of.end()) return it->second;
+            const int32_t slot = nR + (int32_t)slot_of.size();
+            slot_of[key] = slot;
+            if (R == me) {
+                HaloPeer &p = peers[B.owner];
+                p.rank = B.owner;
+                p.recv_dst.push_back(slot);
+                p.recv_sign.push_back(1);
+                p.recv_gid.push_back((int32_t)((ig - 1) + (size_t)NX * (jg - 1)));
+            } else if (B.owner == me) {
+                HaloPeer &p = peers[R];
+                p.rank = R;
+                p.send_src.push_back(off);
+                p.send_dst.push_back(slot);
+                p.send_sign.push_back(1);
+            }
+            return slot;
+        };
+        std::vector<FoldBlk> blks;
+        for (int kb : kv.second) {
+            const HaloBlock &B = T.blk[kb];
+            blks.push_back({B.local, ng + 1, ng + B.gnx, ng + 1, ng + B.gny, B.gi0, B.gj0});
+        }
+        for (int loc = 0; loc < 4; ++loc) {
+            FoldList L;
+            fold_entries(d, blks, loc, own, L);
+            if (R == me) plan.cg_fold[loc] = L;
+        }
+        if (R == me) plan.cg_tail = (int)slot_of.size();
+    }
+    for (auto &kv : peers) plan.cg_peers.push_back(kv.second);
+}
+
 }  // namespace
 
 bool build_halo_plan(const cice_evp_hip_dims &d, HaloPlan &plan)
@@ -525,21 +692,20 @@ bool build_halo_plan(const cice_evp_hip_dims &d, HaloPlan &plan)
             for (int32_t dd : plan.stress_dst) dup |= dd == plan.local_dst[k];
             if (!dup) { plan.stress_dst.push_back(plan.local_dst[k]); plan.stress_src.push_back(-1); }
         }
+    if (tripole || tfold) build_cg_fold(d, T, plan);
     return true;
 }
 
 
-// tripoleT (T-fold; ice_boundary.F90:1563-1622 offsets and symmetrisation, :1686-1722 copy-out): rows NY and NY+1 of every
-// block, ghost columns included, take column NX-ig+1-ioffset of the rows NY-joffset and NY-1-joffset, offsets (ioffset,
-// joffset) = centre (-1, 0), NE corner (0, 1), E face (0, 0), N face (-1, 1); centre and E-face fields lie ON the fold: their
-// top row is made symmetric first (pairs i <-> NX-i+2, i = 2..NX/2, resp. i <-> NX+1-i, i = 1..NX/2) -- an entry then holds
-// the pair in the reference's order (a = the lower column) and flip says which half the destination is
-static void build_fold_list_tfold(const cice_evp_hip_dims &d, int loc, FoldList &L)
+void build_fold_list(const cice_evp_hip_dims &d, int loc, FoldList &L)
 {
-    const int NX = d.nx_global, NY = d.ny_global, nx = d.nx_block, ng = d.nghost;
+    L = FoldList();
+    const int NX = d.nx_global, NY = d.ny_global, nx = d.nx_block;
     const size_t plane = (size_t)nx * d.ny_block;
-    std::vector<int> owner((size_t)NX * 3, -1);              // interior cell holding global (ig, NY-2 .. NY)
-    for (int b = 0; b < d.nblocks; ++b)
+    std::vector<int> owner((size_t)NX * 3, -1);              // interior cell of this rank holding global (ig, NY-2 .. NY)
+    std::vector<FoldBlk> blks;
+    for (int b = 0; b < d.nblocks; ++b) {
+        blks.push_back({b, d.ilo[b], d.ihi[b], d.jlo[b], d.jhi[b], d.iglob0[b], d.jglob0[b]});
         for (int j = d.jlo[b]; j <= d.jhi[b]; ++j) {
             const int jg = d.jglob0[b] + (j - d.jlo[b]);
             if (jg < NY - 2 || jg > NY) continue;
@@ -548,85 +714,8 @@ static void build_fold_list_tfold(const cice_evp_hip_dims &d, int loc, FoldList 
                 owner[(size_t)(jg - (NY - 2)) * NX + (ig - 1)] = (int)((size_t)b * plane + (size_t)(j - 1) * nx + (i - 1));
             }
         }
-    auto wrap = [&](int ig) {
-        while (ig < 1) ig += NX;
-        while (ig > NX) ig -= NX;
-        return ig;
-    };
-    auto own = [&](int ig, int jg) { return owner[(size_t)(jg - (NY - 2)) * NX + (wrap(ig) - 1)]; };
-    const int ioff = (loc == 0 || loc == 3) ? -1 : 0, joff = (loc == 1 || loc == 3) ? 1 : 0;
-    const bool on_fold = (loc == 0 || loc == 2);
-    for (int b = 0; b < d.nblocks; ++b)
-        for (int j = d.jlo[b] - ng; j <= d.jhi[b] + ng; ++j) {
-            const int jg = d.jglob0[b] + (j - d.jlo[b]);
-            if (jg != NY && jg != NY + 1) continue;
-            for (int i = d.ilo[b] - ng; i <= d.ihi[b] + ng; ++i) {
-                const int ig = wrap(d.iglob0[b] + (i - d.ilo[b]));
-                const int dd = (int)((size_t)b * plane + (size_t)(j - 1) * nx + (i - 1));
-                const int m = wrap(NX - ig + 1 - ioff);
-                const int jsrc = (jg == NY ? NY : NY - 1) - joff;
-                int a = own(m, jsrc), bb = -1, fl = 1;
-                if (on_fold && jg == NY && m != ig) {          // a pair of the symmetrised row
-                    const int lo = std::min(ig, m), hi = std::max(ig, m);
-                    a = own(lo, NY);
-                    bb = own(hi, NY);
-                    if (bb < 0) bb = -2;                         // partner's block eliminated: the buffer holds 0
-                    fl = ig == lo ? 0 : 1;
-                }
-                L.dst.push_back(dd); L.a.push_back(a); L.b.push_back(bb); L.flip.push_back((uint8_t)fl);
-            }
-        }
-}
-
-void build_fold_list(const cice_evp_hip_dims &d, int loc, FoldList &L)
-{
-    L = FoldList();
-    if (d.ns_boundary_type == CICE_EVP_BND_TRIPOLET) { build_fold_list_tfold(d, loc, L); return; }
-    const int NX = d.nx_global, NY = d.ny_global, nx = d.nx_block, ng = d.nghost;
-    const size_t plane = (size_t)nx * d.ny_block;
-    std::vector<int> owner((size_t)NX * 2, -1);              // interior cell holding global (ig, NY-1) / (ig, NY)
-    for (int b = 0; b < d.nblocks; ++b)
-        for (int j = d.jlo[b]; j <= d.jhi[b]; ++j) {
-            const int jg = d.jglob0[b] + (j - d.jlo[b]);
-            if (jg < NY - 1 || jg > NY) continue;
-            for (int i = d.ilo[b]; i <= d.ihi[b]; ++i) {
-                const int ig = d.iglob0[b] + (i - d.ilo[b]);
-                owner[(size_t)(jg - (NY - 1)) * NX + (ig - 1)] = (int)((size_t)b * plane + (size_t)(j - 1) * nx + (i - 1));
-            }
-        }
-    auto wrap = [&](int ig) {
-        while (ig < 1) ig += NX;
-        while (ig > NX) ig -= NX;
-        return ig;
-    };
-    auto own = [&](int ig, int row) { return owner[(size_t)row * NX + (wrap(ig) - 1)]; };   // row 0: NY-1, 1: NY
-    auto add = [&](int dd, int aa, int bb, int fl) { L.dst.push_back(dd); L.a.push_back(aa); L.b.push_back(bb); L.flip.push_back((uint8_t)fl); };
-    // a point ON the fold is averaged with its partner even when the partner's block was eliminated (the buffer holds 0)
-    auto pair = [&](int dd, int ia, int ib, int fl) { const int pb = own(ib, 1); add(dd, own(ia, 1), pb >= 0 ? pb : -2, fl); };
-    for (int b = 0; b < d.nblocks; ++b)
-        for (int j = d.jlo[b] - ng; j <= d.jhi[b] + ng; ++j) {
-            const int jg = d.jglob0[b] + (j - d.jlo[b]);
-            if (jg != NY && jg != NY + 1) continue;
-            for (int i = d.ilo[b] - ng; i <= d.ihi[b] + ng; ++i) {
-                const int ig = wrap(d.iglob0[b] + (i - d.ilo[b]));
-                const int dd = (int)((size_t)b * plane + (size_t)(j - 1) * nx + (i - 1));
-                if (jg == NY) {
-                    if (loc == 1) {                           // NE corner: pairs i <-> NX-i, poles NX/2 and NX
-                        if (ig == NX / 2 || ig == NX) add(dd, own(ig, 1), -1, 1);
-                        else if (ig < NX / 2) pair(dd, ig, NX - ig, 0);
-                        else pair(dd, NX - ig, ig, 1);
-                    } else if (loc == 3) {                    // N face: pairs i <-> NX+1-i
-                        if (ig <= NX / 2) pair(dd, ig, NX + 1 - ig, 0);
-                        else pair(dd, NX + 1 - ig, ig, 1);
-                    }
-                    continue;                                 // centre / E face: the top row is an ordinary row
-                }
-                // ghost row NY+1: mirror with offsets (0,0) centre, (1,1) NE corner, (1,0) E face, (0,1) N face
-                const int is = (loc == 0 || loc == 3) ? NX - ig + 1 : NX - ig;
-                const int row = (loc == 0 || loc == 2) ? 1 : 0;
-                add(dd, own(is, row), -1, 1);
-            }
-        }
+    }
+    fold_entries(d, blks, loc, [&](int ig, int jg) { return owner[(size_t)(jg - (NY - 2)) * NX + (ig - 1)]; }, L);
 }
 
 namespace {

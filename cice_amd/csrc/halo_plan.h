@@ -19,6 +19,11 @@
 
 #include "../../include/cice_evp_hip.h"
 
+struct FoldList {              // the C grid's fold step of one field location (build_fold_list below)
+    std::vector<int32_t> dst, a, b;
+    std::vector<uint8_t> flip;
+};
+
 struct HaloBlock {
     int gi0, gj0, gnx, gny;   // interior rectangle in global index space (1-based origin)
     int owner, local;         // owning rank (-1: eliminated land block), local block index
@@ -126,6 +131,20 @@ struct HaloPlan {
     std::vector<int32_t> center_seam_dst, center_seam_slot;
     bool fold_split = false;                      // the blocks holding row NY have more than one owner: the same on every rank
                                                   // (the exchanges above are collective)
+    // C grid on a tripole grid (u-fold and T-fold).  cg_fold: the fold step of each field location for this rank's blocks, the
+    // entries of build_fold_list in its order; an operand is a cell of this rank, a staging slot n_local + t (the RAW value of an
+    // interior cell of rows NY-2 .. NY that another rank owns, brought by the exchange of the same exchange point), or -1 / -2
+    // (no owner: eliminated block).  Without cg_split it is what build_fold_list gives, cg_tail = 0.
+    // cg_split: the blocks next to the fold (rows NY-1, NY; T-fold NY-2 .. NY) have more than one owner -- the same on every rank.
+    // Then the C-grid loop exchanges through cg_peers instead of peers: per peer (ascending rank) first the ghost cells of
+    // rows up to NY (T-fold NY-1) whose source another rank owns, plain copies (never across the fold: the fold step is the
+    // last writer of everything beyond, and reads only interior cells and staging slots), then the fold sources: the union over
+    // the four locations of this rank's cells that the peer's fold entries read, into the peer's staging slots (send_dst).
+    FoldList cg_fold[4];
+    std::vector<HaloPeer> cg_peers;
+    int cg_tail = 0;
+    bool cg_split = false;
+    int cg_fold_ranks = 0;                        // ranks that hold blocks next to the fold
     std::string error;
 };
 
@@ -217,8 +236,4 @@ int cgres_dependencies(const cice_evp_hip_dims &d, bool tripole, const std::vect
 //                           x[dst] = s * x[a]                      b == -1 (a == -1: source eliminated, 0)
 // s = flip ? isign : 1; isign = -1 for vector kinds.  Sources are interior cells of THIS rank (the blocks holding rows
 // NY-1 and NY must all be local).  Host only.
-struct FoldList {
-    std::vector<int32_t> dst, a, b;
-    std::vector<uint8_t> flip;
-};
 void build_fold_list(const cice_evp_hip_dims &d, int loc, FoldList &L);

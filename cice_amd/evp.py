@@ -57,7 +57,8 @@ TEST_EXPORTS = [
     "cice_evp_hip_cgrid_fold_plan", "cice_evp_hip_cgrid_window_plan", "cice_evp_hip_cgrid_window_plan_ext", "cice_evp_hip_cgrid_window_deps", "cice_evp_hip_cgrid_strip_plan", "cice_evp_hip_cgrid_strip_zones", "cice_evp_hip_set_test_transport", "cice_evp_hip_march_plan",
     "cice_evp_hip_debug_cuload", "cice_evp_hip_debug_prof", "cice_evp_hip_debug_cgrid_prof", "cice_evp_hip_debug_cgres_prof", "cice_evp_hip_plan_build", "cice_evp_hip_halo_plan", "cice_evp_hip_seam_plan",
     "cice_evp_hip_peer_plan", "cice_evp_hip_peer_signs", "cice_evp_hip_center_plan", "cice_evp_hip_stress_plan",
-    "cice_evp_hip_fold_split_plan", "cice_evp_hip_plan_flags", "cice_evp_hip_fold_images_plan",
+    "cice_evp_hip_fold_split_plan", "cice_evp_hip_plan_flags", "cice_evp_hip_fold_images_plan", "cice_evp_hip_cgrid_fold_xplan",
+    "cice_evp_hip_cgrid_fold_xpeers",
 ]
 # environment switches only the test build reads (cice_amd/csrc/evp_host.h: env_test): experiments, fault injection, routing
 # of on-device copies through the remote transports.  An EvpHip made while one of them is set uses the test build.
@@ -231,6 +232,33 @@ def cgrid_fold_plan(dims: "Dims", loc: str) -> dict:
     _check(lib, lib.cice_evp_hip_cgrid_fold_plan(C.byref(dims), C.c_int32(code), C.byref(n), *[_ip(out[k]) for k in ("dst", "a", "b", "flip")]),
            "(cgrid_fold_plan)")
     return out
+
+
+def cgrid_fold_xplan(dims: "Dims") -> dict:
+    """Host only: the C-grid fold step of every field location on a tripole grid for `dims.rank`, and -- when the blocks next to
+    the fold have more than one owner (split) -- the C-grid exchange that fills the staging slots its operands may name (see
+    the testing header).  Operands >= n_local are staging slots n_local + t."""
+    lib = load_library(testing=True)
+    _check(lib, lib.cice_evp_hip_plan_build(C.byref(dims)), "(plan_build)")
+    info = np.zeros(4, dtype=np.int32)
+    n = C.c_int32(0)
+    out = {}
+    for code, loc in enumerate(("center", "NEcorner", "Eface", "Nface")):
+        _check(lib, lib.cice_evp_hip_cgrid_fold_xplan(C.c_int32(code), _ip(info), C.byref(n), None, None, None, None), "(cgrid_fold_xplan)")
+        L = {k: np.zeros(max(n.value, 1), dtype=np.int32) for k in ("dst", "a", "b", "flip")}
+        _check(lib, lib.cice_evp_hip_cgrid_fold_xplan(C.c_int32(code), None, None, *[_ip(L[k]) for k in ("dst", "a", "b", "flip")]),
+               "(cgrid_fold_xplan)")
+        out[loc] = {k: v[:n.value] for k, v in L.items()}
+    npeer = int(info[2])
+    p5 = np.zeros((max(npeer, 1), 5), dtype=np.int32)
+    lib.cice_evp_hip_cgrid_fold_xpeers(_ip(p5), None, None, None, None)
+    ns, nr = int(p5[:npeer, 1].sum()), int(p5[:npeer, 2].sum())
+    ss, sd = [np.zeros(max(ns, 1), dtype=np.int32) for _ in range(2)]
+    rd, rg = [np.zeros(max(nr, 1), dtype=np.int32) for _ in range(2)]
+    lib.cice_evp_hip_cgrid_fold_xpeers(_ip(p5), _ip(ss), _ip(sd), _ip(rd), _ip(rg))
+    return dict(split=bool(info[0]), tail=int(info[1]), fold=out, peer_rank=p5[:npeer, 0].copy(), peer_nsend=p5[:npeer, 1].copy(),
+                peer_nrecv=p5[:npeer, 2].copy(), peer_nghost_send=p5[:npeer, 3].copy(), peer_nghost_recv=p5[:npeer, 4].copy(),
+                send_src=ss[:ns], send_dst=sd[:ns], recv_dst=rd[:nr], recv_gid=rg[:nr])
 
 
 def cgrid_window_plan(dims: "Dims", ox: int, oy: int, extra: int = 0) -> dict:
@@ -545,13 +573,14 @@ class EvpHip:
         _check(self.lib, self.lib.cice_evp_hip_cgrid_sync(), "(dyn_evp_hip_cgrid_sync)")
 
     def cgrid_timings(self):
-        out = np.zeros(15)
-        _check(self.lib, self.lib.cice_evp_hip_cgrid_timings(_dp(out), C.c_int32(15)), "(dyn_evp_hip_cgrid_timings)")
+        out = np.zeros(18)
+        _check(self.lib, self.lib.cice_evp_hip_cgrid_timings(_dp(out), C.c_int32(18)), "(dyn_evp_hip_cgrid_timings)")
         return dict(loop_ms=float(out[0]), nsub=int(out[1]), prep_ms=float(out[2]), one_launch_subcycles=int(out[3]),
                     geometry_derived=bool(out[4]), resident_subcycles=int(out[5]), resident_probe_ms=float(out[6]),
                     resident_fallbacks=int(out[7]), resident_windows_with_ice=int(out[8]), resident_windows=int(out[9]),
                     marched_items=int(out[10]), marched_cells=int(out[11]), marched_edge_windows=int(out[12]),
-                    marched_segment_rows=int(out[13]), marched_lengths_derived=bool(out[14]))
+                    marched_segment_rows=int(out[13]), marched_lengths_derived=bool(out[14]), fold_exchange=bool(out[15]),
+                    fold_ranks=int(out[16]), fold_staging_slots=int(out[17]))
 
     def debug_cgres_prof(self):
         self._need_testing("debug_cgres_prof")

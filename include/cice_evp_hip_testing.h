@@ -135,6 +135,16 @@ int cice_evp_hip_fold_split_plan(int32_t which, int32_t *count, int32_t *cells);
  * hang on; [1] fold_rows (0 none here, 1 all here, 2 shared); [2] stress symmetrisation needs another rank;
  * [3] a cell-centre ghost needs another rank; [4] ... across the fold.  Returns the number written.           */
 int cice_evp_hip_plan_flags(int32_t *flags, int32_t n);
+/* The C grid on a tripole grid, from the plan of cice_evp_hip_plan_build (cice_amd/csrc/halo_plan.h: cg_*).  For field location
+ * loc (0 centre, 1 NE corner, 2 E face, 3 N face) the fold step's entries as cice_evp_hip_cgrid_fold_plan gives them; an
+ * operand >= nx_block * ny_block * nblocks is a staging slot (the raw value of another rank's cell).  info4 = {1 if the blocks next
+ * to the fold have more than one owner (the same on every rank), staging slots, peers of the C-grid exchange, entries sent}. */
+int cice_evp_hip_cgrid_fold_xplan(int32_t loc, int32_t *info4, int32_t *count, int32_t *dst, int32_t *a, int32_t *b, int32_t *flip);
+/* ... and that exchange: per peer (ascending rank) peer5 = {rank, entries sent, received, of which ghost cells sent, received};
+ * the ghost cells come first in each peer's share, the fold sources (into the peer's staging slots) after them.  send_dst: the
+ * cell or staging slot each sent entry fills at the peer; recv_gid: the global cell number (ig-1) + NX*(jg-1) each received
+ * entry carries. */
+int cice_evp_hip_cgrid_fold_xpeers(int32_t *peer5, int32_t *send_src, int32_t *send_dst, int32_t *recv_dst, int32_t *recv_gid);
 /* Read-outs of the forcing-layout tests (no entry of their own): cice_evp_hip_prep_fetch serves which = 21, 22 = ss_tltxU,
  * ss_tltyU; cice_evp_hip_cgrid_fetch serves table 2, index 0..3 = strairxE, strairyN, ss_tltxE, ss_tltyN as the last
  * cice_evp_hip_cgrid_prep under a forcing layout other than the default averaged them (every cell).                    */

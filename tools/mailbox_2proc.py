@@ -42,6 +42,10 @@ def main():
                     help="the C-grid subcycle (cice_evp_hip_cgrid_*): ghost cells other ranks own filled through the "
                          "same transport after every producing launch")
     ap.add_argument("--visc", default="avg_zeta")
+    ap.add_argument("--fold-ghosts", action="store_true",
+                    help="with --cgrid on a tripole grid: also compare the ghost row beyond the fold and the east-west ghost cells "
+                         "of row NY with the one-rank run's own ghost cells (its single block has the whole ghost row), and "
+                         "report the C grid's schedule")
     ap.add_argument("--expect-resident", action="store_true",
                     help="fail unless the on-chip resident kernel with remote neighbours ran")
     ap.add_argument("--forcing", default="",
@@ -193,6 +197,9 @@ def main():
                 core.cgrid_subcycle(7)
             out = core.cgrid_download()
             out["_halomask"] = hm
+            if a.fold_ghosts:
+                cgt = core.cgrid_timings()
+                out["_schedule"] = (bool(cgt["fold_exchange"]), int(cgt["fold_ranks"]), core.describe_path().rpartition("; ")[2])
             if a.prep:                    # what the preparation produced, too
                 for k in ("aiE", "forcexE", "emassdti", "aiN", "forceyN", "uocnN", "uvelE_init") + (
                         ("uocnE", "vocnE", "vocnN", "strairxE", "strairyN") if a.forcing else ()):
@@ -242,8 +249,20 @@ def main():
                         w2, h2 = w2[keep], h2[keep]
                     if not np.array_equal(w2, h2):
                         bad.append((k + " ghosts", int((w2 != h2).sum()), float(np.abs(w2 - h2).max())))
+                if a.fold_ghosts and k in exchanged and b.gj0 + b.gny - 1 == ny and ns_bnd in ("tripole", "tripoleT"):
+                    # the one-rank run's own ghost cells: row NY+1 beyond the fold, and the east-west ghost cells of row NY
+                    cols = (np.arange(b.gi0 - 1, b.gi0 + b.gnx + 1) - 1) % nx + 1        # global columns of the local ones
+                    r1 = ref[k][0]
+                    for jl, jr, sel in ((b.gny + 1, ny + 1, slice(None)), (b.gny, ny, [0, b.gnx + 1])):
+                        w3 = r1[jr, cols][sel]
+                        h3 = got[k][b.local][jl, 0:b.gnx + 2][sel]
+                        if a.maskhalo:
+                            keep3 = got["_halomask"][b.local][jl, 0:b.gnx + 2][sel] != 0
+                            w3, h3 = w3[keep3], h3[keep3]
+                        if not np.array_equal(w3.view(np.int64), h3.view(np.int64)):
+                            bad.append((k + (" fold ghost row" if jr > ny else " row NY ghosts"), int((w3 != h3).sum())))
         res = [None] * world
-        dist.all_gather_object(res, (rank, bad, t_us, tim["halo_send_cells"]))
+        dist.all_gather_object(res, (rank, bad, t_us, tim["halo_send_cells"]) + ((got["_schedule"],) if a.fold_ghosts else ()))
         if rank == 0:
             ok = all(not r[1] for r in res)
             print("MAILBOX_2PROC", "OK" if ok else "FAIL", "cgrid", a.workload, f"world={world}", res, flush=True)
