@@ -364,6 +364,17 @@ int cice_evp_hip_seabed_lkd(const double *hwater, double k1, double k2, double a
     H.a[0] = Q.t[0]; H.a[1] = Q.t[1]; H.a[2] = Q.hwater; H.narr = 3;     // scalars at cell centres
     H.dst = Q.c_dst; H.src = Q.c_src; H.vsign = (const signed char *)Q.c_vsign; H.n = Q.n_center;
     evp_launch_halo_center(H, S.stream);
+    if (S.plan.tfold && Q.n_tf) {
+        // tripoleT: the fold step of the centre rule after the plain ghost copies (row NY symmetrised, NY+1 its mirror),
+        // as in the preparation -- without it the U points of row NY read unfolded values
+        EvpCgFold F{};
+        for (int k = 0; k < 3; ++k) { F.x[k] = H.a[k]; F.loc[k] = 0; F.isign[k] = 1.0; }
+        F.nfields = 3;
+        F.L[0] = {Q.tf_dst, Q.tf_a, Q.tf_b, Q.tf_flip, Q.n_tf};
+        F.tmp = Q.tf_tmp;
+        F.maxn = Q.n_tf;
+        evp_launch_cgrid_fold(F, S.stream);
+    }
     EvpPrep P{};
     P.nx = S.d.nx_block; P.ny = S.d.ny_block; P.plane = S.plane; P.blk = S.blk;
     P.t[0] = Q.t[0]; P.t[1] = Q.t[1]; P.mask = S.mask;

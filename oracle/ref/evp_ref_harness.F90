@@ -22,7 +22,7 @@
 module evp_cgrid_capture
   use ice_kinds_mod
   use ice_domain, only: nblocks
-  use ice_domain_size, only: max_blocks
+  use ice_domain_size, only: max_blocks, ncat
   use ice_blocks, only: nx_block, ny_block
   use ice_state, only: uvel, vvel, uvelE, vvelE, uvelN, vvelN, strength, divu, shear, vort, aice, vice, vsno, aice_init, &
                        aice0, aicen, vicen
@@ -78,6 +78,61 @@ contains
     vicen(:,:,1,1:nblocks) = vice(:,:,1:nblocks)
   end subroutine evolve_ice
 
+  ! h_ncat > 1: every cell's aice / vice split over the ncat categories by a rule of the cell's own values (ghost cells,
+  ! which hold copies, split the same way): uneven weights, one category empty in most cells, thicker ice in the higher
+  ! categories.  aice / vice then become the left-to-right sums of aicen / vicen, as CICE's aggregate forms them.
+  subroutine split_categories()
+    integer(int_kind) :: ib, i, j, n, k
+    real(dbl_kind) :: w(ncat), ws, h, a, s
+    do ib = 1, nblocks
+    do j = 1, ny_block
+    do i = 1, nx_block
+       a = aice(i,j,ib)
+       aicen(i,j,:,ib) = c0
+       vicen(i,j,:,ib) = c0
+       if (a > c0) then
+          h = vice(i,j,ib)/a
+          k = int(mod(a*1000._dbl_kind, 7._dbl_kind))
+          ws = c0
+          do n = 1, ncat
+             w(n) = real(mod(k + 3*n, 7), dbl_kind)
+             ws = ws + w(n)
+          enddo
+          do n = 1, ncat
+             aicen(i,j,n,ib) = a*w(n)/ws
+             vicen(i,j,n,ib) = aicen(i,j,n,ib)*h*(0.4_dbl_kind + 0.3_dbl_kind*real(n-1, dbl_kind))
+          enddo
+       endif
+       s = c0
+       do n = 1, ncat
+          s = s + aicen(i,j,n,ib)
+       enddo
+       aice(i,j,ib) = s
+       s = c0
+       do n = 1, ncat
+          s = s + vicen(i,j,n,ib)
+       enddo
+       vice(i,j,ib) = s
+       aice0(i,j,ib) = c1 - aice(i,j,ib)
+       aice_init(i,j,ib) = aice(i,j,ib)
+    enddo
+    enddo
+    enddo
+  end subroutine split_categories
+
+  ! ncat > 1: aicen / vicen of every category, as <tag>_aicen<n> / <tag>_vicen<n> (each (nx, ny, nblocks))
+  subroutine dump_categories(tag)
+    character(len=*), intent(in) :: tag
+    integer(int_kind) :: n
+    character(len=8) :: cn
+    if (ncat == 1) return
+    do n = 1, ncat
+       write(cn,'(i0)') n
+       call dump_r8_3d(trim(tag)//'_aicen'//trim(cn), aicen(:,:,n,:), nblocks)
+       call dump_r8_3d(trim(tag)//'_vicen'//trim(cn), vicen(:,:,n,:), nblocks)
+    enddo
+  end subroutine dump_categories
+
   ! icepack_ice_strength on the T-cells of the new iceTmask + its halo update (ice_dyn_evp.F90:596-608, 727-728):
   ! the callback of dyn_evp_hip_cgrid_evp_body
   subroutine cgrid_strength()
@@ -132,6 +187,7 @@ contains
     call dump_r8_3d(trim(tg)//'_strintxE', strintxE, nblocks);   call dump_r8_3d(trim(tg)//'_strintyN', strintyN, nblocks)
     call dump_l_3d (trim(tg)//'_iceUmask', iceUmask, nblocks)
     call dump_l_3d (trim(tg)//'_iceEmask', iceEmask, nblocks);   call dump_l_3d (trim(tg)//'_iceNmask', iceNmask, nblocks)
+    call dump_categories(trim(tg))
     if (.not. allocated(q_uE)) then
        allocate(q_uE(nx_block,ny_block,max_blocks), q_vN(nx_block,ny_block,max_blocks), q_uN(nx_block,ny_block,max_blocks), &
                 q_vE(nx_block,ny_block,max_blocks), q_spT(nx_block,ny_block,max_blocks), q_smT(nx_block,ny_block,max_blocks), &
@@ -297,7 +353,7 @@ program evp_ref_harness
       dyn_evp_hip_keep_stresses_resident
 #endif
   use evp_dumpio
-  use evp_cgrid_capture, only: cgrid_call, evolve_ice
+  use evp_cgrid_capture, only: cgrid_call, evolve_ice, split_categories, dump_categories
   use icepack_intfc, only: icepack_query_parameters
 #if defined (_OPENMP)
   use OMP_LIB
@@ -340,11 +396,14 @@ program evp_ref_harness
   logical            :: time_1d     = .false.     ! timing loop with evp_algorithm='shared_mem_1d' (HARNESS_REF1D build only)
   character(len=8)   :: h_grid_ice  = 'B'         ! 'B' | 'C': staggering of the dynamics (C: ice_dyn_evp.F90:936-1121)
   character(len=16)  :: h_visc_method = 'avg_zeta' ! C grid: 'avg_zeta' | 'avg_strength' (ice_dyn_evp.F90:992-996)
+  integer(int_kind)  :: h_ncat      = 1           ! thickness categories; > 1: aice / vice split over them (split_categories)
+  real(dbl_kind)     :: h_hw_span   = 40._dbl_kind ! with h_seabed: hwater = 8 + h_hw_span * y (> 42: deeper than 50 m in the north)
 
   namelist /harness_nml/ grid_kind, kmt_kind, icecase, dumpfile, h_grid_file, h_kmt_file, &
      h_dxrect, h_dyrect, h_dt, h_ndte, ncalls, nsub_list, h_revised, h_arlx, h_brlx, &
      h_capping, h_Ktens, h_e_yield, h_e_plast, h_elasticDamp, h_coriolis, h_seabed, h_seabed_method, &
-     dump_arrays, ntiming, hipmode, hipbody, hipresident, time_1d, h_grid_ice, h_visc_method, h_evolve, h_ssh
+     dump_arrays, ntiming, hipmode, hipbody, hipresident, time_1d, h_grid_ice, h_visc_method, h_evolve, h_ssh, &
+     h_ncat, h_hw_span
 
   ! ---- locals ----------------------------------------------------------
   integer(int_kind) :: i, j, iblk, icall, k, nsub, nl, ios, nthreads
@@ -375,7 +434,8 @@ program evp_ref_harness
   call init_fileunits
   nml_filename = 'ice_in'
 
-  ncat=1; nfsd=1; nilyr=1; nslyr=1; nblyr=1
+  if (h_ncat > 1 .and. h_evolve) stop 'h_ncat > 1 with h_evolve: evolve_ice fills category 1 only'
+  ncat=h_ncat; nfsd=1; nilyr=1; nslyr=1; nblyr=1
   n_iso=0; n_aero=0; n_zaero=0; n_algae=0; n_doc=0; n_dic=0; n_don=0; n_fed=0; n_fep=0
   nfreq=1
 
@@ -466,7 +526,7 @@ program evp_ref_harness
         endif
         strairxT(i,j,iblk) = aice(i,j,iblk)*0.1_dbl_kind*sin(twopi*x)*sin(p5*twopi*y)
         strairyT(i,j,iblk) = aice(i,j,iblk)*0.1_dbl_kind*sin(p5*twopi*x)*sin(twopi*y)
-        if (h_seabed) hwater(i,j,iblk) = 8._dbl_kind + 40._dbl_kind*y   ! shallow shelf in the south
+        if (h_seabed) hwater(i,j,iblk) = 8._dbl_kind + h_hw_span*y   ! shallow shelf in the south
      enddo
      enddo
   enddo
@@ -480,6 +540,7 @@ program evp_ref_harness
      aicen(:,:,1,iblk) = aice(:,:,iblk)
      vicen(:,:,1,iblk) = vice(:,:,iblk)
   enddo
+  if (ncat > 1) call split_categories()
 
   call icepack_query_parameters(rhow_out=rhow_l)
 
@@ -581,6 +642,7 @@ program evp_ref_harness
         call dump_r8_3d(trim(tag)//'_strairxT', strairxT, nblocks); call dump_r8_3d(trim(tag)//'_strairyT', strairyT, nblocks)
         call dump_r8_3d(trim(tag)//'_uvel', uvel, nblocks);       call dump_r8_3d(trim(tag)//'_vvel', vvel, nblocks)
         call dump_l_3d (trim(tag)//'_iceUmask', iceUmask, nblocks)
+        call dump_categories(trim(tag))
         call dump_r8_3d(trim(tag)//'_stressp_1', stressp_1, nblocks); call dump_r8_3d(trim(tag)//'_stressp_2', stressp_2, nblocks)
         call dump_r8_3d(trim(tag)//'_stressp_3', stressp_3, nblocks); call dump_r8_3d(trim(tag)//'_stressp_4', stressp_4, nblocks)
         call dump_r8_3d(trim(tag)//'_stressm_1', stressm_1, nblocks); call dump_r8_3d(trim(tag)//'_stressm_2', stressm_2, nblocks)

@@ -92,6 +92,21 @@ class GoldenCase:
             state[k] = z if icall == 1 else self.d[f"o{icall - 1:02d}n{self.nsub_list[-1]:04d}_{k}"]
         return t, state
 
+    def aicen(self, icall=1):
+        """aicen evp() was entered with on call `icall`, [nblocks][ncat][ny][nx]: the harness's categories where it ran with
+        h_ncat > 1 (pr / cp<icall>_aicen<n>), aice[:, None] where it ran with ncat = 1."""
+        return self._categories("aice", icall)
+
+    def vicen(self, icall=1):
+        return self._categories("vice", icall)
+
+    def _categories(self, k, icall):
+        pre = f"{'cp' if self.name.startswith(('cgrid_', 'cgtript_')) else 'pr'}{icall:02d}_"
+        if pre + k + "n1" not in self.d:
+            return self.d[pre + k][:, None]
+        ncat = sum(1 for q in self.d if q.startswith(pre + k + "n"))
+        return np.stack([self.d[f"{pre}{k}n{n}"] for n in range(1, ncat + 1)], axis=1)
+
     def prep_scal_dict(self):
         s = self.scal
         return dict(dt=s[28], rhoi=s[17], rhos=s[18], gravit=s[19], dyn_area_min=s[20], dyn_mass_min=s[21],

@@ -58,6 +58,11 @@ CASES = {
     "pop_cyc_2x2_seabedprob": (24, 20, 12, 10, "cyclic", "closed",
                                dict(grid_kind="popfile", icecase="patchy", nsub_list=[1, 120], ncalls=2,
                                     h_seabed=True, h_seabed_method="probabilistic")),
+    # ... with five thickness categories (aice / vice split unevenly, some categories empty: aicen / vicen dumped as
+    # pr01_aicen<n> / _vicen<n>) and water deeper than max_depth = 50 m in the north (hwater up to 68 m)
+    "pop_cyc_2x2_seabedprob_ncat5": (24, 20, 12, 10, "cyclic", "closed",
+                                     dict(grid_kind="popfile", icecase="patchy", nsub_list=[1, 120], ncalls=1,
+                                          h_seabed=True, h_seabed_method="probabilistic", h_ncat=5, h_hw_span=60.0)),
     # the ice cover changes between the two calls (cells gain and lose ice: dyn_prep2's new-ice / no-ice branches, :747-764)
     # and the sea surface slopes (ssh_stress = 'coupled'): the preparation phase's inputs pr02 differ from pr01
     "pop_cyc_2x2_evolve_coupled": (24, 20, 12, 10, "cyclic", "closed",
@@ -100,6 +105,10 @@ CGRID_CASES = {
     "cgrid_cyc_2x2_seabedprob": (24, 20, 12, 10, "cyclic", "closed",
                                  dict(icecase="patchy", nsub_list=[1, 120], ncalls=1, h_seabed=True,
                                       h_seabed_method="probabilistic")),
+    # ... five thickness categories, hwater up to 68 m (cp01_aicen<n> / _vicen<n>)
+    "cgrid_cyc_2x2_seabedprob_ncat5": (24, 20, 12, 10, "cyclic", "closed",
+                                       dict(icecase="patchy", nsub_list=[1, 120], ncalls=1, h_seabed=True,
+                                            h_seabed_method="probabilistic", h_ncat=5, h_hw_span=60.0)),
     "cgrid_cyccyc_2x2_cap0_ktens": (24, 20, 12, 10, "cyclic", "cyclic",
                                     dict(icecase="patchy", nsub_list=[1, 120], ncalls=1, h_capping=0.0, h_Ktens=0.2,
                                          h_e_yield=1.5, h_e_plast=2.5, h_ssh="coupled")),

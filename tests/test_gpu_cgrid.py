@@ -1086,8 +1086,8 @@ def device_prep(core, c, icall, state, visc=None):
     masks_prev = {k: st[k] for k in ("iceUmask", "iceEmask", "iceNmask")}
     masks = core.cgrid_prep(hip_prep_params(c), t, state if state is not None else None, masks_prev)
     s = c.scal
-    if s[23] != 0.0 and s[29] != 0.0:          # probabilistic (one thickness category in the harness)
-        core.cgrid_seabed_prob(c.d["hwater"], t["aice"][:, None], t["vice"][:, None], s[26], s[17], s[19], s[30], s[31])
+    if s[23] != 0.0 and s[29] != 0.0:          # probabilistic (the fixture's thickness categories)
+        core.cgrid_seabed_prob(c.d["hwater"], c.aicen(icall), c.vicen(icall), s[26], s[17], s[19], s[30], s[31])
     elif s[23] != 0.0:
         core.cgrid_seabed_lkd(c.d["hwater"], s[24], s[25], s[26], s[27])
     core.cgrid_prep_finish(c.d[f"in{icall:02d}_strength"], visc or str(c.d["visc_method"]))

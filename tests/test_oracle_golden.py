@@ -283,6 +283,43 @@ def test_seabed_prob_oracle_bitwise():
         assert bits_equal(tb, dyn["TbU"]), f"call {icall}"
 
 
+@pytest.mark.parametrize("name", ["pop_cyc_2x2_seabedprob_ncat5", "cgrid_cyc_2x2_seabedprob_ncat5"])
+def test_seabed_prob_oracle_bitwise_ncat5(name):
+    """seabed_stress_factor_prob with five thickness categories (the harness splits aice / vice unevenly, some categories
+    empty, and lets hwater run past max_depth = 50 m): the oracle's reading of the (nx, ny, ncat, nblocks) layout, of the
+    order of the sums over categories (atot, m_i) and of the v_i term gives the TbU / TbE / TbN the reference's evp() handed
+    to its loop, bit for bit."""
+    c = GoldenCase(name)
+    s = c.scal
+    assert s[23] == 1.0 and s[29] == 1.0
+    a, v = c.aicen(1), c.vicen(1)
+    assert a.shape[1] == 5 and (a == 0).any() and not bits_equal(a[:, 0], a[:, 1])
+    hw = c.d["hwater"]
+    assert (hw >= 50.0).any() and (hw < 50.0).any()
+    if name.startswith("cgrid_"):
+        t, _, _ = c.cgrid_prep_inputs(1)
+        _, want, masks = c.cgrid_inputs(1)
+        got = oracle.seabed_prob_c(c.oracle_domain(), s[26], s[17], s[12], s[19], s[30], s[31], a, v, hw,
+                                   masks["iceTmask"], masks["iceEmask"], masks["iceNmask"])
+        pairs = [(got[0], want["TbE"]), (got[1], want["TbN"])]
+    else:
+        t, _ = c.prep_inputs(1)
+        dyn, tm, um = c.inputs(1)
+        pairs = [(oracle.seabed_prob(c.oracle_domain(), s[26], s[17], s[12], s[19], s[30], s[31], a, v, hw, tm, um), dyn["TbU"])]
+    aice = np.zeros_like(t["aice"])
+    for n in range(a.shape[1]):
+        aice = aice + a[:, n]
+    assert bits_equal(aice, t["aice"])                      # aice is the left-to-right sum of the categories
+    for g, w in pairs:
+        assert np.abs(w).max() > 0 and bits_equal(g, w)
+    # the categories matter: the aggregate alone (ncat = 1) does not give the reference's factors
+    g1 = (oracle.seabed_prob_c(c.oracle_domain(), s[26], s[17], s[12], s[19], s[30], s[31], t["aice"][:, None], t["vice"][:, None],
+                               hw, masks["iceTmask"], masks["iceEmask"], masks["iceNmask"])[0] if name.startswith("cgrid_") else
+          oracle.seabed_prob(c.oracle_domain(), s[26], s[17], s[12], s[19], s[30], s[31], t["aice"][:, None], t["vice"][:, None],
+                             hw, tm, um))
+    assert not bits_equal(g1, pairs[0][1])
+
+
 @pytest.mark.parametrize("name", CGRID_CASES)
 def test_cgrid_deformations_t_oracle_bitwise(name):
     """deformationsC_T (ice_dyn_shared.F90:1968-2074) restated in oracle/evp_oracle.c: from the reference's final face
@@ -354,9 +391,9 @@ def test_cgrid_prep_oracle_bitwise(name):
         t, state, prev = c.cgrid_prep_inputs(icall)
         got = oracle.cgrid_prep(c.oracle_domain(), pp, c.cgrid_prep_static(), t, state, prev)
         want_state, want_in, want_masks = c.cgrid_inputs(icall)
-        if s[23] != 0.0 and s[29] != 0.0:      # seabed stress, probabilistic (ncat = 1 in the harness)
+        if s[23] != 0.0 and s[29] != 0.0:      # seabed stress, probabilistic (the fixture's thickness categories)
             got["TbE"], got["TbN"] = oracle.seabed_prob_c(c.oracle_domain(), s[26], s[17], s[12], s[19], s[30], s[31],
-                                                          t["aice"][:, None], t["vice"][:, None], c.d["hwater"],
+                                                          c.aicen(icall), c.vicen(icall), c.d["hwater"],
                                                           got["iceTmask"], got["iceEmask"], got["iceNmask"])
             assert np.abs(want_in["TbE"]).max() > 0 and np.abs(want_in["TbN"]).max() > 0
         elif s[23] != 0.0:                     # ... LKD
