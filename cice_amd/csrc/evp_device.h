@@ -114,8 +114,10 @@ struct EvpResident2 {
 };
 int evp_resident2_max_blocks_per_cu(bool strict, int cap, unsigned flags, int logw, bool remote, bool coop = false);
 bool evp_resident2_coop_built(bool strict, int cap, int logw, bool remote);   // the rim-cells-by-corners variant exists for this combination
+bool evp_resident2_lean_built(bool strict, int cap, int logw, bool remote);   // the lean variant (one rank, no fold, ...) exists
+// lean: the caller has checked what the lean variant fixes (evp_host_resident.cpp, resident2_lean)
 void evp_launch_resident2(const EvpArgs &A, const EvpResident2 &R, int max_ni, int max_nj, int logw,
-                          bool strict, int cap, hipStream_t st);
+                          bool strict, int cap, bool lean, hipStream_t st);
 
 // Several (2 .. 4) subcycles per pass over a device-private strip-major layout (evp_march.hip, evp_host_march.cpp)
 #ifndef EVP_MARCH_PAD          // (a build-time A/B: -DEVP_MARCH_PAD=3 makes three the most subcycles per pass, strips of 58)

@@ -466,7 +466,12 @@ int launch_resident2(int ndte, int cur0, bool dry)
         R.u[0] = S.u[0]; R.v[0] = S.v[0]; R.u[1] = S.u[1]; R.v[1] = S.v[1];
     }
     R.tab = S.res_tab + (dry ? 28 * (1 + cur0) : 0);
-    evp_launch_resident2(A, R, S.max_ni, S.max_nj, S.res2_logw, S.prm.strict != 0, cap_mode(), S.stream);
+    // the lean variant where nothing it leaves out can happen in this launch (CICE_EVP_HIP_RES_LEAN=0, test build: never)
+    const bool lean = evp_resident2_lean_built(S.prm.strict != 0, cap_mode(), S.res2_logw, R.rimg != nullptr) &&
+                      R.nblocks == 1 && !R.seam && !R.tfold && !R.img3 && !R.rimg && !R.rraw && !R.nlate &&
+                      A.p.revp == 0.0 && (A.flags & EVP_F_WATER_IS_OCN) && (A.flags & EVP_F_TBU_ZERO) &&
+                      !(env_test("CICE_EVP_HIP_RES_LEAN") && !std::atoi(env_test("CICE_EVP_HIP_RES_LEAN")));
+    evp_launch_resident2(A, R, S.max_ni, S.max_nj, S.res2_logw, S.prm.strict != 0, cap_mode(), lean, S.stream);
     HIPC(hipGetLastError());
     return 0;
 }

@@ -32,6 +32,7 @@
 // =====================================================================
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+#include <algorithm>
 
 // Debug hooks (lagging tiles, a workgroup that never shows up, A/B switches) and the per-phase cycle stamps exist in the
 // TEST build's object of this file only (-DCICE_EVP_HIP_TESTING, linked into libcice_evp_hip_testing.so): the product
@@ -65,6 +66,21 @@ __device__ __forceinline__ void ld_rec2(const void *p, v4u &a, v4u &b)
     asm volatile("global_load_dwordx4 %0, %2, off sc1\n\tglobal_load_dwordx4 %1, %2, off offset:16 sc1\n\ts_waitcnt vmcnt(0)"
                  : "=&v"(a), "=&v"(b)
                  : "v"(p)
+                 : "memory");
+}
+// the same as scalar base + 32-bit lane offset (the saddr form: no 64-bit address arithmetic per lane)
+__device__ __forceinline__ void st_rec2_s(const void *base, unsigned off, v4u a, v4u b)
+{
+    asm volatile("global_store_dwordx4 %0, %1, %3 sc1\n\tglobal_store_dwordx4 %0, %2, %3 offset:16 sc1"
+                 :
+                 : "v"(off), "v"(a), "v"(b), "s"(base)
+                 : "memory");
+}
+__device__ __forceinline__ void ld_rec2_s(const void *base, unsigned off, v4u &a, v4u &b)
+{
+    asm volatile("global_load_dwordx4 %0, %2, %3 sc1\n\tglobal_load_dwordx4 %1, %2, %3 offset:16 sc1\n\ts_waitcnt vmcnt(0)"
+                 : "=&v"(a), "=&v"(b)
+                 : "v"(off), "s"(base)
                  : "memory");
 }
 // the same at system scope: records another GPU writes into this one's buffer / this one into a peer's
@@ -117,10 +133,15 @@ constexpr int QP_X1 = 0xB1, QP_X2 = 0x4E, QP_X3 = 0x1B;      // quad_perm [1,0,3
 // operands and signs selected per lane, the operations and their order those of stress_cell: a - b*c == a + (-b)*c, x + y == y + x
 // bit for bit), fetches the other three corners' stresses with quad-permute moves, and forms the two stress-divergence partials
 // that carry its corner's coefficients.  The cell's stresses live three per lane in those quads for the whole call.
-template <bool STRICT, int CAP, int LOGW, bool REMOTE, bool COOP = false>
+// LEAN (one rank and block, no fold, TbU == 0, water == ocean current, revp == 0; evp_resident2_lean_built): none of the code for
+// the other cases is in the subcycle loop, which runs two subcycles per trip (one per record buffer), the record loads and stores
+// addressed as scalar buffer base + lane offset.  Same operations in the same order => same bits
+// (profiles/r07_resident_lean_*.txt, tools/resident_isa_mix.py).
+template <bool STRICT, int CAP, int LOGW, bool REMOTE, bool COOP = false, bool LEAN = false>
 __global__ __launch_bounds__(64 * RTY, REMOTE ? 2 : 3) void evp_resident2_tile(EvpArgs A, EvpResident2 R)
 {
     static_assert(!COOP || (STRICT && CAP == 3 && LOGW == 4), "COOP: 16 x 16 tiles, strict build, default scalars");
+    static_assert(!LEAN || (!REMOTE && !COOP && LOGW == 4), "LEAN: one rank, 16 x 16 tiles, one thread per rim cell");
     using MM = Math<STRICT>;
     constexpr int W = 1 << LOGW;
     constexpr int H = 256 / W;
@@ -253,8 +274,8 @@ __global__ __launch_bounds__(64 * RTY, REMOTE ? 2 : 3) void evp_resident2_tile(E
     const int c = cb + (j - 1) * nx + (i - 1);
     const int li = (trow + 1) * LW + (tcol + 1);   // this cell in the LDS velocity tile
     const unsigned flags = A.flags;
-    const bool water = !(flags & EVP_F_WATER_IS_OCN);
-    const bool tbu = !(flags & EVP_F_TBU_ZERO);
+    const bool water = !LEAN && !(flags & EVP_F_WATER_IS_OCN);     // (LEAN: launched only with both flags set)
+    const bool tbu = !LEAN && !(flags & EVP_F_TBU_ZERO);
     if (COOP) {
         s_rc = s_uc + (8 + (water ? 2 : 0) + (tbu ? 1 : 0)) * 256;
         s_r04 = s_rc + 10 * 64;
@@ -379,13 +400,13 @@ __global__ __launch_bounds__(64 * RTY, REMOTE ? 2 : 3) void evp_resident2_tile(E
     // after every momentum step, ice or not (ice_boundary.F90:1630-1649) -- role 1/2: low/high index
     // of a pair, 3: pole point; partner = the other cell of the pair
     int seam_role = 0, seam_partner = -1;
-    if (R.seam && ownU && j == r.w) {
+    if (!LEAN && R.seam && ownU && j == r.w) {
         const int sv = R.seam[bz * nx + i - 1];
         seam_role = sv & 3;
         seam_partner = sv >> 2;
     }
     const bool isSeam = seam_role != 0;
-    if (R.img3) {
+    if (!LEAN && R.img3) {
         // tripole: ghost images are not confined to the block edge (ghost row NY+1 mirrors row NY-1):
         // per-cell table, at most three images
         if (ownU) { img0 = R.img3[3 * c]; img1 = R.img3[3 * c + 1]; img2 = R.img3[3 * c + 2]; }
@@ -535,10 +556,14 @@ __global__ __launch_bounds__(64 * RTY, REMOTE ? 2 : 3) void evp_resident2_tile(E
     // asm block on fixed registers, compares included -- the compiler copies a poll's registers at a loop merge while the
     // load is in flight, in every form it was given): bit-identical, and SLOWER -- poll phase 4476 -> 5131 cycles, 4.69 ->
     // 4.90 us per subcycle (gpurun_out/r4i): twice the poll traffic costs more than the earlier sighting saves.
-    for (int k = 0; k < R.ndte; ++k) {
+    // LEAN: record addresses are a scalar base (the buffer of the subcycle's parity) plus a 32-bit lane offset fixed for the call
+    const unsigned ring_off = 32u * (unsigned)(ring_cp >= 0 ? ring_cp : 0);
+    const unsigned own_off = 32u * (unsigned)c;
+    const unsigned img_off0 = 32u * (unsigned)(img0 >> 1), img_off1 = 32u * (unsigned)(img1 >> 1), img_off2 = 32u * (unsigned)(img2 >> 1);
+    const double img_sg0 = (img0 & 1) ? -1.0 : 1.0, img_sg1 = (img1 & 1) ? -1.0 : 1.0, img_sg2 = (img2 & 1) ? -1.0 : 1.0;
+    // one subcycle: reads the records of buffer rd, writes those of buffer wr; false: a wait gave up, the workgroup leaves
+    auto subcycle = [&](const int k, const v4u *rd, v4u *wr) -> bool {
         const unsigned want = R.tag_base + (unsigned)k;       // tag of the velocities subcycle k reads
-        const v4u *rd = (const v4u *)R.rec[(k + par0) & 1];
-        v4u *wr = (v4u *)R.rec[((k + par0) & 1) ^ 1];
 
         if (((RES_DBG(R) & 8) && (tile & 3) == 1) || ((RES_DBG(R) & 256) && no_ucell)) {      // robustness test: every fourth tile lags by ~10 us per subcycle
             const unsigned long long t0 = wall_clock64();
@@ -556,7 +581,8 @@ __global__ __launch_bounds__(64 * RTY, REMOTE ? 2 : 3) void evp_resident2_tile(E
             unsigned spins = 0;
             if (REMOTE) t_wait0 = wall_clock64();
             for (;;) {
-                ld_rec2(rd + 2 * (size_t)ring_cp, ra, rb);
+                if (LEAN) ld_rec2_s(rd, ring_off, ra, rb);
+                else ld_rec2(rd + 2 * (size_t)ring_cp, ra, rb);
                 if ((ra.x == want && ra.w == want && rb.x == want && rb.w == want) || (RES_DBG(R) & 1)) break;
                 // a local neighbour may itself be waiting for another rank: with remote neighbours
                 // every wait is bounded by wall-clock time, not by a spin count
@@ -572,7 +598,7 @@ __global__ __launch_bounds__(64 * RTY, REMOTE ? 2 : 3) void evp_resident2_tile(E
         }
         if (!split) {
             __syncthreads();
-            if (s_bad) return;   // uniform: every thread of the workgroup leaves together
+            if (s_bad) return false;   // uniform: every thread of the workgroup leaves together
         } else {
             // ring cells are written and read by wave 0 only: LDS operations of one wave complete in order
             __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
@@ -605,7 +631,7 @@ __global__ __launch_bounds__(64 * RTY, REMOTE ? 2 : 3) void evp_resident2_tile(E
                 s_str[5 * SP + sp] = str[6];
             }
             __syncthreads();
-            if (split && s_bad) return;   // set by wave 0 before the barrier
+            if (split && s_bad) return false;   // set by wave 0 before the barrier
             if (COOP) {
                 EVP_STAMP(pacc2)      // (stamps: the wait at this barrier counts as "wait B1", the quads' work as "stress")
                 // the ring is in LDS for everybody now: the rim T-cells, one corner per lane, all four waves
@@ -658,8 +684,8 @@ __global__ __launch_bounds__(64 * RTY, REMOTE ? 2 : 3) void evp_resident2_tile(E
             if (water) { q.waterx = s_uc[row * 256 + t]; q.watery = s_uc[(row + 1) * 256 + t]; row += 2; }
             else { q.waterx = q.uocn; q.watery = q.vocn; }
             q.TbU = tbu ? s_uc[row * 256 + t] : 0.0;
-            q.uvel_init = A.p.revp != 0.0 ? A.uvel_init[c] : 0.0;
-            q.vvel_init = A.p.revp != 0.0 ? A.vvel_init[c] : 0.0;
+            q.uvel_init = !LEAN && A.p.revp != 0.0 ? A.uvel_init[c] : 0.0;
+            q.vvel_init = !LEAN && A.p.revp != 0.0 ? A.vvel_init[c] : 0.0;
             q.sx0 = str[0]; q.sx1 = sx1;
             q.sx2 = s_str[0 * SP + sp + SW]; q.sx3 = s_str[2 * SP + sp + SW + 1];
             q.sy0 = str[4]; q.sy1 = s_str[1 * SP + sp + SW];
@@ -675,7 +701,7 @@ __global__ __launch_bounds__(64 * RTY, REMOTE ? 2 : 3) void evp_resident2_tile(E
         // T-fold: a top-row cell waits for the record of the cell it is the image of -- which may sit in the SAME wave (next to the
         // pole columns) and publishes further down: every cell that is not such an image publishes first
         bool published = false;
-        if (R.tfold && !isSeam) {
+        if (!LEAN && R.tfold && !isSeam) {
             if (ownU) {
                 const unsigned tag = want + 1u;
                 if (pub) st_rec2(wr + 2 * (size_t)c, pack_rec(u_own, tag), pack_rec(v_own, tag));
@@ -755,7 +781,13 @@ __global__ __launch_bounds__(64 * RTY, REMOTE ? 2 : 3) void evp_resident2_tile(E
             }
         }
         if (isU || isSeam) { s_u[li] = u_own; s_v[li] = v_own; }   // read by the next stress phase (after the ring barrier)
-        if (ownU && !published) {
+        if (LEAN && ownU) {
+            const unsigned tag = want + 1u;
+            if (pub) st_rec2_s(wr, own_off, pack_rec(u_own, tag), pack_rec(v_own, tag));
+            if (img0 >= 0) st_rec2_s(wr, img_off0, pack_rec(img_sg0 * u_own, tag), pack_rec(img_sg0 * v_own, tag));
+            if (img1 >= 0) st_rec2_s(wr, img_off1, pack_rec(img_sg1 * u_own, tag), pack_rec(img_sg1 * v_own, tag));
+            if (img2 >= 0) st_rec2_s(wr, img_off2, pack_rec(img_sg2 * u_own, tag), pack_rec(img_sg2 * v_own, tag));
+        } else if (ownU && !published) {
             const unsigned tag = want + 1u;
             if (pub) st_rec2(wr + 2 * (size_t)c, pack_rec(u_own, tag), pack_rec(v_own, tag));
             if (img0 >= 0) { const double sg = (img0 & 1) ? -1.0 : 1.0; st_rec2(wr + 2 * (size_t)(img0 >> 1), pack_rec(sg * u_own, tag), pack_rec(sg * v_own, tag)); }
@@ -767,6 +799,20 @@ __global__ __launch_bounds__(64 * RTY, REMOTE ? 2 : 3) void evp_resident2_tile(E
         EVP_STAMP(pacc3)
         if (split) __syncthreads();   // the tile's own new velocities are in LDS before anybody's next stress update
         EVP_STAMP(pacc4)
+        return true;
+    };
+    if (LEAN) {
+        // two subcycles per trip, one per record buffer: the buffers' addresses are fixed in each
+        const v4u *const rec_a = (const v4u *)R.rec[par0 & 1];
+        v4u *const rec_b = (v4u *)R.rec[(par0 & 1) ^ 1];
+        for (int k = 0; k < R.ndte; k += 2) {
+            if (!subcycle(k, rec_a, rec_b)) return;
+            if (k + 1 == R.ndte) break;
+            if (!subcycle(k + 1, rec_b, (v4u *)rec_a)) return;
+        }
+    } else {
+        for (int k = 0; k < R.ndte; ++k)
+            if (!subcycle(k, (const v4u *)R.rec[(k + par0) & 1], (v4u *)R.rec[((k + par0) & 1) ^ 1])) return;
     }
 #undef EVP_STAMP
     if (prof && (t & 63) == 0) {
@@ -864,6 +910,11 @@ void evp_resident_geometry(int max_ni, int max_nj, int logw, int *gx, int *gy)
     *gy = (max_nj + H - 2) / (H - 1);
 }
 
+// LEAN (one rank, one block, no fold, TbU == 0, water == ocean current, revp == 0, default scalars, 16 x 16 tiles): what the
+// general kernel decides per launch is fixed at compile time -- the loop carries no seam, T-fold, remote or revp code, one
+// stepu -- and the record addresses are a scalar base per subcycle parity plus a lane offset fixed for the call
+bool evp_resident2_lean_built(bool, int cap, int logw, bool remote) { return cap == 3 && logw == 4 && !remote; }
+
 // (measured slower than one thread per rim cell wherever two or three tiles share a CU -- HISTORY.md, round 5 -- so the variant is
 // compiled into the test build only, as an A/B switch: CICE_EVP_HIP_RES_COOP=1, tools/coop_ab.py)
 #ifdef CICE_EVP_HIP_TESTING
@@ -884,12 +935,19 @@ int evp_resident2_max_blocks_per_cu(bool strict, int cap, unsigned flags, int lo
 #endif
     }
     const size_t lds = lds_bytes(flags, logw);
+    if (evp_resident2_lean_built(strict, cap, logw, remote)) {
+        // admitted against the smaller of the two: the launch picks the lean variant only while the data allow it
+        int nb = 0;
+        const hipError_t e = strict ? hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, evp_resident2_tile<true, 3, 4, false, false, true>, 64 * RTY, lds)
+                                    : hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, evp_resident2_tile<false, 3, 4, false, false, true>, 64 * RTY, lds);
+        return e == hipSuccess ? std::min(nb, occ<4, false>(strict, cap, lds)) : 0;
+    }
     if (remote) return logw == 4 ? occ<4, true>(strict, cap, lds) : logw == 5 ? occ<5, true>(strict, cap, lds) : occ<6, true>(strict, cap, lds);
     return logw == 4 ? occ<4, false>(strict, cap, lds) : logw == 5 ? occ<5, false>(strict, cap, lds) : occ<6, false>(strict, cap, lds);
 }
 
 void evp_launch_resident2(const EvpArgs &A0, const EvpResident2 &R, int max_ni, int max_nj, int logw,
-                          bool strict, int cap, hipStream_t st)
+                          bool strict, int cap, bool lean, hipStream_t st)
 {
     EvpArgs A = A0;
     evp_resident_geometry(max_ni, max_nj, logw, &A.gx, &A.gy);
@@ -902,6 +960,12 @@ void evp_launch_resident2(const EvpArgs &A0, const EvpResident2 &R, int max_ni, 
         return;
     }
 #endif
+    if (lean && evp_resident2_lean_built(strict, cap, logw, remote)) {
+        dim3 grid(R.nlaunch > 0 ? R.nlaunch : A.ntiles), block(64, RTY);
+        if (strict) hipLaunchKernelGGL((evp_resident2_tile<true, 3, 4, false, false, true>), grid, block, lds_bytes(A.flags, 4), st, A, R);
+        else hipLaunchKernelGGL((evp_resident2_tile<false, 3, 4, false, false, true>), grid, block, lds_bytes(A.flags, 4), st, A, R);
+        return;
+    }
     if (remote) {
         if (logw == 4) launch<4, true>(A, R, strict, cap, st);
         else if (logw == 5) launch<5, true>(A, R, strict, cap, st);
