@@ -136,6 +136,40 @@ int cice_evp_hip_cgrid_strip_zones(const cice_evp_hip_dims *dims, int32_t ex, in
     }
     return 0;
 }
+int cice_evp_hip_cgrid_frame_plan(const cice_evp_hip_dims *dims, int32_t ex, int32_t ey, int32_t lo0, int32_t slots, int32_t seg_min, int32_t seg,
+                                  int64_t *info6, uint8_t *cells, int32_t *wg, int32_t wg_cap, int32_t *items6, int32_t items_cap)
+{
+    if (!dims || !info6) return fail(-1, "bad argument");
+    HaloPlan P;
+    if (!build_halo_plan(*dims, P)) return fail(-3, "halo plan: %s", P.error.c_str());
+    std::vector<int32_t> t4, tb, it;
+    build_window_table(*dims, P, ex, ey, 1 << 20, t4, tb);
+    std::vector<int> img((size_t)dims->nblocks * dims->nx_block * dims->ny_block, -1);
+    for (size_t k = 0; k < P.local_src.size(); ++k)
+        if (P.local_src[k] >= 0) img[(size_t)P.local_src[k]] = 0;
+    std::vector<StripZone> zones;
+    strip_zones(*dims, t4, ex, ey, img.data(), zones);
+    if (!zones.empty()) strip_items(zones, ex, ey, lo0, slots, seg_min, seg, it);
+    CgFramePlan F;
+    std::string why;
+    const int rc = build_cg_frame(*dims, P, it, F, why);
+    if (rc < 0) return fail(-5, "%s", why.c_str());
+    for (int k = 0; k < 6; ++k) info6[k] = 0;
+    if (rc == 0) return 1;                                    // declined: one rank
+    info6[0] = F.zone_cells; info6[1] = F.frame_cells;
+    for (int k = 0; k < 3; ++k) info6[2 + k] = (int64_t)F.wg[k].size();
+    info6[5] = (int64_t)(it.size() / 6);
+    if (cells) std::copy(F.cells.begin(), F.cells.end(), cells);
+    if (wg) {
+        if ((size_t)wg_cap < F.wg[0].size() + F.wg[1].size() + F.wg[2].size()) return fail(-1, "room for %d workgroups", wg_cap);
+        for (int k = 0; k < 3; ++k) wg = std::copy(F.wg[k].begin(), F.wg[k].end(), wg);
+    }
+    if (items6) {
+        if ((size_t)items_cap * 6 < it.size()) return fail(-1, "room for %d items", items_cap);
+        std::copy(it.begin(), it.end(), items6);
+    }
+    return 0;
+}
 #endif  // CICE_EVP_HIP_TESTING
 
 int cice_evp_hip_stream_probe(int64_t ncells, double *bytes_per_second)

@@ -12,7 +12,7 @@
 // and no halo kernel runs inside the loop.  Fields the reference never exchanges (etax2U, deltaU, stress12T,
 // strintxE/yN, taubxE/yN) are not pushed: their ghost cells end up exactly as the reference leaves them.
 //
-// Three schedules.  "one" (cg_one, further down; the default on one rank without a fold -- from 300 000 cells per rank with the interior
+// Three schedules (and, across ranks, the third beside the marched kernel: below).  "one" (cg_one, further down; the default on one rank without a fold -- from 300 000 cells per rank with the interior
 // of every block marched by cg_strip, at the end of this file, and cg_one's windows along the block edges): ONE launch per subcycle, the three
 // dependent levels inside a workgroup, neighbouring positions recomputed.  "phases": the five phases as five launches (any
 // visc_method; tripole grids, with a fold step after each).  "fused" (visc_method = avg_zeta; several ranks):
@@ -23,6 +23,11 @@
 //   B  stressC_T as before;
 //   C  stressC_U recomputed at the three corners div_stress_Ex / _Ny read (own, south, west: stress12U ping-pongs
 //      between two buffers), then stepu_C / stepv_C.
+// Several ranks with rectangles for cg_strip on this rank ("zone marched + frame", evp_host_cgrid.cpp: enqueue_fused): cg_strip marches
+// them on a second stream while the FRAME variants of A, B, C (cg_frame_strain, cg_frame_stress_t, cg_frame_step: the same cell bodies)
+// advance every other interior cell on the loop's stream, with the fused schedule's exchanges.  They read all five ping-pong arrays
+// from the previous subcycle's buffers and write this subcycle's on frame cells only; zone cells a frame cell reads are recomputed
+// into scratch arrays (EvpCgFrame; halo_plan.cpp: build_cg_frame).
 // Arrays that nothing inside the loop reads (zetax2T, etax2U, deltaU, strintxE/yN, taubxE/yN) are stored in the last
 // subcycle of a call only.  81 instead of 99 doubles moved per cell and subcycle, 3 instead of 5 launches.
 //
@@ -173,6 +178,34 @@ __device__ __forceinline__ Cell cell(const EvpCgrid &A)
     return c;
 }
 
+// The cell of a thread of workgroup `id` of the plain 64 x 4 tiling, id = (block * gy + row) * gx + column: the frame kernels run the
+// workgroups of a host-built list (EvpCgFrame::wg)
+__device__ __forceinline__ Cell cell_of_wg(const EvpCgrid &A, int id)
+{
+    Cell c;
+    const int gx = (A.nx + TX - 1) / TX, gy = (A.ny + TY - 1) / TY;
+    const int bx = id % gx, r = id / gx;
+    c.b = r / gy;
+    c.i = bx * TX + threadIdx.x + 1;
+    c.j = (r - c.b * gy) * TY + threadIdx.y + 1;
+    c.in = c.i <= A.nx && c.j <= A.ny;
+    c.q = A.blk[c.b];
+    c.o = (size_t)c.b * A.plane + (size_t)(c.j - 1) * A.nx + (c.i - 1);
+    return c;
+}
+// An array as the frame kernels read it: on a zone cell (bit 8 of the plan's byte) the value lives in the frame's scratch copy d --
+// the array itself belongs to the marched kernel there, which runs at the same time.  FRAME = false: the array, nothing else.
+template <bool FRAME>
+struct ZArr {
+    const double *a, *d;
+    const uint8_t *cells;
+    __device__ __forceinline__ double operator[](size_t p) const
+    {
+        if (FRAME) return ((cells[p] & 8u) ? d : a)[p];
+        return a[p];
+    }
+};
+
 // ---- phase 0: strain_rates_U (strain rates * area at the corners); shearU is exchanged (:965-967) ----
 // strain_rates_U proper (ice_dyn_shared.F90:2341-2444) on values in registers
 struct StrainIn {
@@ -270,28 +303,35 @@ __device__ __forceinline__ double avg_2(const P &a, const W &w, size_t p, size_t
 // strain_rates_U reads it.  The east / north neighbour may be a ghost cell: its value in the reference is the copy
 // of the owner's average, which the same formula gives here from the (pushed) ghost velocities and the static
 // ghost weights. ----
-template <bool GEO>
-__global__ __launch_bounds__(TX *TY) void cg_avg_strain(EvpCgrid A, int last)
+// FRAME (here and in the two kernels below): the variant that runs beside the marched kernel on a rank with neighbours on other ranks
+// (EvpCgFrame).  The same arithmetic; the five ping-pong arrays are read from the previous subcycle's buffers and written to this
+// subcycle's on FRAME cells only (flag 1); a zone cell evaluated because a frame cell reads its shearU (flag 2 without 1) stores it to
+// the scratch array and nothing else.
+template <bool GEO, bool FRAME>
+__device__ __forceinline__ void avg_strain_cell(const EvpCgrid &A, const EvpCgFrame &F, const Cell &c, int last)
 {
-    const Cell c = cell(A);
-    if (!c.in || c.i < c.q.x || c.i > c.q.y || c.j < c.q.z || c.j > c.q.w) return;
     const size_t o = c.o, e = o + 1, n = o + A.nx;
     const unsigned m = A.mask[o];
+    const unsigned fl = FRAME ? F.cells[o] : 1u;
+    if (FRAME && !(fl & 2u)) return;
+    const bool mine = (fl & 1u) != 0;
     const auto G = AGeo<GEO>::make(A);
-    const double *uE = A.f[CF_UE], *vN = A.f[CF_VN];
+    const double *uE = FRAME ? F.uE_in : A.f[CF_UE], *vN = FRAME ? F.vN_in : A.f[CF_VN];
     const auto ea = G[CG_EAREA], na = G[CG_NAREA];
     const auto npm = G[CG_NPM], epm = G[CG_EPM];
     const double uNo = avg_nw(uE, ea, o, A.nx) * npm[o];
     const double vEo = avg_se(vN, na, o, A.nx) * epm[o];
-    A.f[CF_UN][o] = uNo;                         // stepv_C / stepu_C of this subcycle read them (own cell)
-    A.f[CF_VE][o] = vEo;
+    if (mine) {
+        A.f[CF_UN][o] = uNo;                     // stepv_C / stepu_C of this subcycle read them (own cell)
+        A.f[CF_VE][o] = vEo;
+    }
     // no early exit for cells without ice: every load below is in bounds, and issuing them all before the first
     // wait is what matters on grids this small (two waves per SIMD); only the stores are conditional
     const double uvm = G[CG_UVM][o];
     const double uU = avg_2(uE, ea, o, n) * uvm;
     const double vU = avg_2(vN, na, o, e) * uvm;
     double sh, delta = 0.0;
-    if (last) {                                  // deltaU is wanted (nothing inside the loop reads it): the whole of strain_rates_U
+    if (last && mine) {                          // deltaU is wanted (nothing inside the loop reads it): the whole of strain_rates_U
         StrainIn v;
         v.uNo = uNo; v.vEo = vEo; v.uU = uU; v.vU = vU;
         v.uNe = avg_nw(uE, ea, e, A.nx) * npm[e];
@@ -301,10 +341,26 @@ __global__ __launch_bounds__(TX *TY) void cg_avg_strain(EvpCgrid A, int last)
     } else {
         sh = shear_u(A, G, o, uE[o], uE[n], vN[o], vN[e], uU, vU);
     }
+    if (FRAME && !mine) {                        // (a cell without ice keeps what the array holds: nobody writes it during a call)
+        F.sh[o] = (m & 2u) ? sh : A.f[CF_SHEARU][o];
+        return;
+    }
     if (!(m & 2u)) return;
     A.f[CF_SHEARU][o] = sh;
     if (last) A.f[CF_DELTAU][o] = delta;
     if (m & 16u) push(A, o, m, CF_SHEARU, sh);
+}
+template <bool GEO>
+__global__ __launch_bounds__(TX *TY) void cg_avg_strain(EvpCgrid A, int last)
+{
+    const Cell c = cell(A);
+    if (!c.in || c.i < c.q.x || c.i > c.q.y || c.j < c.q.z || c.j > c.q.w) return;
+    avg_strain_cell<GEO, false>(A, EvpCgFrame{}, c, last);
+}
+__global__ __launch_bounds__(TX *TY) void cg_frame_strain(EvpCgrid A, EvpCgFrame F, int last)
+{
+    const Cell c = cell_of_wg(A, F.wg[0][blockIdx.x]);
+    if (c.in) avg_strain_cell<true, true>(A, F, c, last);
 }
 
 __global__ __launch_bounds__(TX *TY) void cg_strain_u(EvpCgrid A)
@@ -345,31 +401,43 @@ __global__ __launch_bounds__(TX *TY) void cg_strain_u(EvpCgrid A)
 // ---- phase 1: stressC_T on ilo..ihi+1 x jlo..jhi+1 (the reference's T list, ice_dyn_shared.F90:729-738).
 // zetax2T, etax2T, stresspT, stressmT are exchanged right after (:988-990): interior cells store and push them, the
 // extra row and column (ghost cells) only keep what is never exchanged, stress12T. ----
-template <bool ALWAYS, bool GEO>
-__global__ __launch_bounds__(TX *TY) void cg_stress_t(EvpCgrid A, int last)
+template <bool ALWAYS, bool GEO, bool FRAME>
+__device__ __forceinline__ void stress_t_cell(const EvpCgrid &A, const EvpCgFrame &F, const Cell &c, int last)
 {
     const auto G = AGeo<GEO>::make(A);
-    const Cell c = cell(A);
-    if (!c.in || c.i < c.q.x || c.i > c.q.y + 1 || c.j < c.q.z || c.j > c.q.w + 1) return;
     const size_t o = c.o, w = o - 1, s = o - A.nx, sw = s - 1;
     const unsigned m = A.mask[o];
+    const unsigned fl = FRAME ? F.cells[o] : 0u;
+    if (FRAME && !(fl & 4u)) return;
     const bool own = c.i <= c.q.y && c.j <= c.q.w;
-    const double *uE = A.f[CF_UE], *vN = A.f[CF_VN], *shU = A.f[CF_SHEARU];
+    const double *uE = FRAME ? F.uE_in : A.f[CF_UE], *vN = FRAME ? F.vN_in : A.f[CF_VN];
+    const double *sp_in = FRAME ? F.sp_in : A.f[CF_SP], *sm_in = FRAME ? F.sm_in : A.f[CF_SM];
+    const ZArr<FRAME> shU{A.f[CF_SHEARU], F.sh, F.cells};
     const auto dyE = G[CG_DYE], dxN = G[CG_DXN], uarea = G[CG_UAREA];
     const double dxT = G[CG_DXT][o], dyT = G[CG_DYT][o];
     const double divT = dyE[o] * uE[o] - dyE[w] * uE[w] + dxN[o] * vN[o] - dxN[s] * vN[s];
     const double tensionT = (dyT * dyT) * (uE[o] / dyE[o] - uE[w] / dyE[w]) - (dxT * dxT) * (vN[o] / dxN[o] - vN[s] / dxN[s]);
     const double uareaavgr = 1.0 / (uarea[o] + uarea[s] + uarea[sw] + uarea[w]);
-    const double shearTsqr = (shU[o] * shU[o] * uarea[o] + shU[s] * shU[s] * uarea[s] + shU[sw] * shU[sw] * uarea[sw] +
-                              shU[w] * shU[w] * uarea[w]) * uareaavgr;
-    const double shearT = (shU[o] * uarea[o] + shU[s] * uarea[s] + shU[sw] * uarea[sw] + shU[w] * uarea[w]) * uareaavgr;
+    const double shUo = shU[o], shUs = shU[s], shUsw = shU[sw], shUw = shU[w];
+    const double shearTsqr = (shUo * shUo * uarea[o] + shUs * shUs * uarea[s] + shUsw * shUsw * uarea[sw] +
+                              shUw * shUw * uarea[w]) * uareaavgr;
+    const double shearT = (shUo * uarea[o] + shUs * uarea[s] + shUsw * uarea[sw] + shUw * uarea[w]) * uareaavgr;
     const double DeltaT = sqrt(divT * divT + A.p.e_factor * (tensionT * tensionT + shearTsqr));
     double zetax2, etax2, rep_prs;
     visc_replpress(A.p, A.in[CI_STRENGTH][o], G[CG_DMINT][o], DeltaT, zetax2, etax2, rep_prs);
     const double relax = 1.0 - A.p.arlx1i * A.p.revp;
     const double s12 = (A.f[CF_S12T][o] * relax + A.p.arlx1i * 0.5 * etax2 * shearT) * A.p.denom1;
-    const double sp = (A.f[CF_SP][o] * relax + A.p.arlx1i * (zetax2 * divT - rep_prs)) * A.p.denom1;
-    const double sm = (A.f[CF_SM][o] * relax + A.p.arlx1i * etax2 * tensionT) * A.p.denom1;
+    const double sp = (sp_in[o] * relax + A.p.arlx1i * (zetax2 * divT - rep_prs)) * A.p.denom1;
+    const double sm = (sm_in[o] * relax + A.p.arlx1i * etax2 * tensionT) * A.p.denom1;
+    if (FRAME && (fl & 8u)) {
+        // a zone cell a frame cell reads etax2T, stresspT or stressmT of: to the scratch arrays only (a cell without ice keeps what the
+        // arrays hold -- nobody writes them there during a call); stress12T and the arrays themselves are the marched kernel's here
+        const bool ice = (m & 1u) != 0;
+        F.eta[o] = ice ? etax2 : A.f[CF_ETA][o];
+        F.sp[o] = ice ? sp : sp_in[o];
+        F.sm[o] = ice ? sm : sm_in[o];
+        return;
+    }
     if (!(m & 1u)) return;                       // loads above are unconditional (in bounds), stores are not
     A.f[CF_S12T][o] = s12;
     if (!own) return;
@@ -385,10 +453,22 @@ __global__ __launch_bounds__(TX *TY) void cg_stress_t(EvpCgrid A, int last)
         push(A, o, m, CF_SM, sm);
     }
 }
+template <bool ALWAYS, bool GEO>
+__global__ __launch_bounds__(TX *TY) void cg_stress_t(EvpCgrid A, int last)
+{
+    const Cell c = cell(A);
+    if (!c.in || c.i < c.q.x || c.i > c.q.y + 1 || c.j < c.q.z || c.j > c.q.w + 1) return;
+    stress_t_cell<ALWAYS, GEO, false>(A, EvpCgFrame{}, c, last);
+}
+__global__ __launch_bounds__(TX *TY) void cg_frame_stress_t(EvpCgrid A, EvpCgFrame F, int last)
+{
+    const Cell c = cell_of_wg(A, F.wg[1][blockIdx.x]);
+    if (c.in) stress_t_cell<false, true, true>(A, F, c, last);
+}
 
 // T -> U average, grid_average_X2YS('NE', work, tarea, hm): ice_grid.F90:4190-4209
-template <class GT>
-__device__ __forceinline__ double avg_t2u_g(const EvpCgrid &A, const GT &G, const double *w1, size_t o)
+template <class GT, class WT>
+__device__ __forceinline__ double avg_t2u_g(const EvpCgrid &A, const GT &G, const WT &w1, size_t o)
 {
     const auto hm = G[CG_HM], ta = G[CG_TAREA];
     const size_t e = o + 1, n = o + A.nx, ne = n + 1;
@@ -485,13 +565,13 @@ __global__ __launch_bounds__(TX *TY) void cg_step(EvpCgrid A)
 
 // stress12U after this subcycle at corner p (own cell or a neighbour, possibly a ghost cell): stressC_U with the
 // T -> U average of etax2T, from the previous subcycle's value in A.s12_in; unchanged where there is no ice
-template <class GT>
-__device__ __forceinline__ double s12u_new(const EvpCgrid &A, const GT &G, size_t p, bool ice, double relax, double *etaU)
+template <bool FRAME, class GT>
+__device__ __forceinline__ double s12u_new(const EvpCgrid &A, const EvpCgFrame &F, const GT &G, size_t p, bool ice, double relax, double *etaU)
 {
     const double old = A.s12_in[p];
-    const double e2 = avg_t2u_g(A, G, A.f[CF_ETA], p);
+    const double e2 = avg_t2u_g(A, G, ZArr<FRAME>{A.f[CF_ETA], F.eta, F.cells}, p);
     if (etaU) *etaU = e2;
-    const double upd = (old * relax + A.p.arlx1i * 0.5 * e2 * A.f[CF_SHEARU][p]) * A.p.denom1;
+    const double upd = (old * relax + A.p.arlx1i * 0.5 * e2 * ZArr<FRAME>{A.f[CF_SHEARU], F.sh, F.cells}[p]) * A.p.denom1;
     return ice ? upd : old;
 }
 
@@ -500,24 +580,25 @@ __device__ __forceinline__ double s12u_new(const EvpCgrid &A, const GT &G, size_
 // wateryN == vocnN bit for bit (cosw = 1, sinw = 0), TbE = TbN = +0 (no seabed stress), rheofactE = rheofactN = 1 --
 // established per call on every ice cell (cg_call_setup); aiX*rhow*Cw comes premultiplied (same operation order).
 // Bit-neutral: x*1.0, x + (+0.0) and 0.0/c are exact, taub = -u*(+0.0) is still formed.
-template <bool FAST, bool GEO>
-__global__ __launch_bounds__(TX *TY * 2) void cg_stress_u_step(EvpCgrid A, int last)
+template <bool FAST, bool GEO, bool FRAME>
+__device__ __forceinline__ void stress_u_step_cell(const EvpCgrid &A, const EvpCgFrame &F, const Cell &c, int last)
 {
     const auto G = AGeo<GEO>::make(A);
-    const Cell c = cell(A);
-    if (!c.in || c.i < c.q.x || c.i > c.q.y || c.j < c.q.z || c.j > c.q.w) return;
     const size_t o = c.o, e = o + 1, n = o + A.nx, s = o - A.nx, w = o - 1;
+    if (FRAME && !(F.cells[o] & 1u)) return;     // the frame cells only: nothing reads this level of a neighbour
     const unsigned m = A.mask[o];
     const double relax = 1.0 - A.p.arlx1i * A.p.revp;
     // blockDim.z == 2: the E face and the N face of a cell in different waves (half the dependent chain per wave, twice
     // the waves in flight: grids of gx1's size are latency-, not bandwidth-bound); blockDim.z == 1: one thread does both
     const bool doE = blockDim.z == 1 || threadIdx.z == 0, doN = blockDim.z == 1 || threadIdx.z == 1;
     double etaU;
-    const double s12c = s12u_new(A, G, o, (m & 2u) != 0, relax, &etaU);
-    const double s12s = doE ? s12u_new(A, G, s, (A.mask[s] & 32u) != 0, relax, nullptr) : 0.0;
-    const double s12w = doN ? s12u_new(A, G, w, (A.mask[w] & 32u) != 0, relax, nullptr) : 0.0;
-    const double *sp = A.f[CF_SP], *sm = A.f[CF_SM];
-    const double spc = sp[o], smc = sm[o];
+    const double s12c = s12u_new<FRAME>(A, F, G, o, (m & 2u) != 0, relax, &etaU);
+    const double s12s = doE ? s12u_new<FRAME>(A, F, G, s, (A.mask[s] & 32u) != 0, relax, nullptr) : 0.0;
+    const double s12w = doN ? s12u_new<FRAME>(A, F, G, w, (A.mask[w] & 32u) != 0, relax, nullptr) : 0.0;
+    // (this subcycle's stresses: of a zone neighbour from the frame's scratch copy, of any other cell from the arrays)
+    const ZArr<FRAME> sp{A.f[CF_SP], F.sp, F.cells}, sm{A.f[CF_SM], F.sm, F.cells};
+    const double *uE_old = FRAME ? F.uE_in : A.f[CF_UE], *vN_old = FRAME ? F.vN_in : A.f[CF_VN];
+    const double spc = A.f[CF_SP][o], smc = A.f[CF_SM][o];
     const EvpScalars &p = A.p;
     // both faces computed for every interior cell (all loads in bounds and issued together); stores by mask
     double unew = 0.0, vnew = 0.0, strintx = 0.0, strinty = 0.0, taubx = 0.0, tauby = 0.0;
@@ -527,7 +608,7 @@ __global__ __launch_bounds__(TX *TY * 2) void cg_stress_u_step(EvpCgrid A, int l
         strintx = (FAST ? G[CG_EAREAR][o] : A.in[CI_RHEOE][o] * G[CG_EAREAR][o]) *
                   (0.5 * dyE * (sp[e] - spc) + (0.5 / dyE) * ((dyT[e] * dyT[e]) * sm[e] - (dyT[o] * dyT[o]) * smc) +
                    (1.0 / dxE) * ((dxU[o] * dxU[o]) * s12c - (dxU[s] * dxU[s]) * s12s));
-        const double uold = A.f[CF_UE][o], vold = A.f[CF_VE][o];
+        const double uold = uE_old[o], vold = A.f[CF_VE][o];
         const double uocn = A.in[CI_UOCNE][o];
         const double du = uocn - uold, dv = A.in[CI_VOCNE][o] - vold;
         const double vrel = (FAST ? A.facE[o] : A.in[CI_AIE][o] * p.rhow * A.in[CI_CWE][o]) * sqrt(du * du + dv * dv);
@@ -550,7 +631,7 @@ __global__ __launch_bounds__(TX *TY * 2) void cg_stress_u_step(EvpCgrid A, int l
         strinty = (FAST ? G[CG_NAREAR][o] : A.in[CI_RHEON][o] * G[CG_NAREAR][o]) *
                   (0.5 * dxN * (sp[n] - spc) - (0.5 / dxN) * ((dxT[n] * dxT[n]) * sm[n] - (dxT[o] * dxT[o]) * smc) +
                    (1.0 / dyN) * ((dyU[o] * dyU[o]) * s12c - (dyU[w] * dyU[w]) * s12w));
-        const double uold = A.f[CF_UN][o], vold = A.f[CF_VN][o];
+        const double uold = A.f[CF_UN][o], vold = vN_old[o];
         const double vocn = A.in[CI_VOCNN][o];
         const double du = A.in[CI_UOCNN][o] - uold, dv = vocn - vold;
         const double vrel = (FAST ? A.facN[o] : A.in[CI_AIN][o] * p.rhow * A.in[CI_CWN][o]) * sqrt(du * du + dv * dv);
@@ -590,6 +671,19 @@ __global__ __launch_bounds__(TX *TY * 2) void cg_stress_u_step(EvpCgrid A, int l
         }
         if (m & 16u) push(A, o, m, CF_VN, vnew);
     }
+}
+template <bool FAST, bool GEO>
+__global__ __launch_bounds__(TX *TY * 2) void cg_stress_u_step(EvpCgrid A, int last)
+{
+    const Cell c = cell(A);
+    if (!c.in || c.i < c.q.x || c.i > c.q.y || c.j < c.q.z || c.j > c.q.w) return;
+    stress_u_step_cell<FAST, GEO, false>(A, EvpCgFrame{}, c, last);
+}
+template <bool FAST>
+__global__ __launch_bounds__(TX *TY * 2) void cg_frame_step(EvpCgrid A, EvpCgFrame F, int last)
+{
+    const Cell c = cell_of_wg(A, F.wg[2][blockIdx.x]);
+    if (c.in) stress_u_step_cell<FAST, true, true>(A, F, c, last);
 }
 
 // ---- once per call: the leading factor of vrel, and whether the default-configuration shortcuts of cg_stress_u_step
@@ -1720,6 +1814,16 @@ void evp_launch_cgrid_phase(const EvpCgrid &A, int phase, int last, hipStream_t 
     case 5: hipLaunchKernelGGL(cg_strength_u, grid, block, 0, st, A, const_cast<double *>(A.strengthU)); break;
     default: hipLaunchKernelGGL(cg_zero_outside, grid, block, 0, st, A); break;
     }
+}
+
+void evp_launch_cgrid_frame(const EvpCgrid &A, const EvpCgFrame &F, int level, int fast, int last, hipStream_t st)
+{
+    if (level < 0 || level > 2 || F.nwg[level] <= 0) return;
+    const dim3 grid((unsigned)F.nwg[level]);
+    if (level == 0) hipLaunchKernelGGL(cg_frame_strain, grid, dim3(TX, TY), 0, st, A, F, last);
+    else if (level == 1) hipLaunchKernelGGL(cg_frame_stress_t, grid, dim3(TX, TY), 0, st, A, F, last);
+    else if (fast) hipLaunchKernelGGL(cg_frame_step<true>, grid, dim3(TX, TY, A.split_faces ? 2 : 1), 0, st, A, F, last);
+    else hipLaunchKernelGGL(cg_frame_step<false>, grid, dim3(TX, TY, A.split_faces ? 2 : 1), 0, st, A, F, last);
 }
 
 void evp_launch_cgrid_deformations(const EvpCgrid &A, const double *tarear, double *divu, double *shear, double *vort,

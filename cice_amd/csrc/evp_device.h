@@ -421,6 +421,18 @@ struct EvpCgStrip {
     int lengths;                  // 1: dxT, dyT, dxU, dyU, dxE, dyN formed in the kernel from dxN, dyE (verified by the host); the items own lanes >= 3
 };
 void evp_launch_cgrid_strip(const EvpCgrid &A, const EvpCgOne &T, const EvpCgStrip &Z, const EvpCgOne *E, int fast, int last, hipStream_t st);
+// The three fused kernels on the FRAME of a rank whose zone cg_strip marches at the same time (several ranks; evp_cgrid.hip:
+// cg_frame_*; halo_plan.h: build_cg_frame).  They read the five ping-pong arrays of the previous subcycle (uE_in .. sm_in, A.s12_in) and
+// write this subcycle's (A.f[...]) on frame cells only; intermediates of the zone cells a frame cell reads go to the scratch arrays.
+struct EvpCgFrame {
+    const uint8_t *cells;         // per cell: 1 frame cell, 2 level S runs here, 4 level T, 8 zone cell (halo_plan.h: CGF_*)
+    const int *wg[3];             // workgroups of 64 x 4 cells of level S, T, C: (block * gy + row) * gx + column
+    int nwg[3];
+    const double *uE_in, *vN_in, *sp_in, *sm_in;
+    double *sh, *eta, *sp, *sm;   // shearU, etax2T and this subcycle's stresspT, stressmT on the zone cells the frame reads
+};
+// level: 0 averages + strain_rates_U (phase 7), 1 stressC_T (phase 10), 2 stressC_U + momentum step (phase 8; fast: phase 11)
+void evp_launch_cgrid_frame(const EvpCgrid &A, const EvpCgFrame &F, int level, int fast, int last, hipStream_t st);
 // All subcycles of a call in one launch, state on the chip (evp_cgrid_res.hip: cg_res).  Windows of 16 x 16 positions, the inner
 // 13 x 13 owned; tab: per window the source cell of its 17 x 17 positions (one row / column more than cg_one's: what level S reads
 // of its north / east neighbour), as in EvpCgOne.  The velocities another window's rim mirrors travel as tagged 32-byte records.

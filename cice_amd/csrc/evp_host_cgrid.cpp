@@ -48,6 +48,17 @@ struct CGridState {
         int strip_len = 0;       // 1: the marched kernel forms six of the eight lengths from dxN, dyE
         long strip_cells = 0;    // cells the marched kernel owns
     } one;
+    // several ranks: the marched kernel on the rectangles above beside the fused chain on every other interior cell (enqueue_fused:
+    // "zone marched + frame"; halo_plan.cpp: build_cg_frame)
+    struct Frame {
+        uint8_t *cells = nullptr;            // per cell: frame cell | level S | level T | zone cell
+        int *wg[3] = {};                     // workgroup lists of the three levels
+        int nwg[3] = {};
+        double *scr[4] = {};                 // shearU, etax2T, stresspT, stressmT of the zone cells the frame reads
+        long ncells = 0;                     // frame cells
+        hipStream_t st2 = nullptr;           // the marched kernel's stream, forked from and joined to S.stream in every subcycle
+        hipEvent_t fork = nullptr, join = nullptr;
+    } fr;
     // all subcycles of a call in one launch, state on the chip (evp_cgrid_res.hip: cg_res)
     struct Res {
         int *tab = nullptr;
@@ -97,6 +108,7 @@ struct CGridState {
     double t_loop_ms = 0;
     int t_nsub = 0;
     int t_one = 0;               // subcycles of the last call that ran as one launch each (cg_one)
+    int t_march = 0;             // ... as the marched kernel beside the fused chain on the frame (several ranks)
     double *tarear = nullptr, *post[5] = {};   // deformationsC_T: 1/tarea (static), divu shear vort rdg_conv rdg_shear
     // preparation phase on the device (cice_evp_hip_cgrid_prep)
     struct Prep {
@@ -129,6 +141,11 @@ void cgrid_free()
     F(CG.tarear); for (auto &p : CG.post) F(p);
     F(CG.one.tab); F(CG.one.tiles); F(CG.one.items); F(CG.one.tiles_e); F(CG.one.tab_e); for (auto &p : CG.one.alt) F(p);
     CG.one = CGridState::One{};
+    F(CG.fr.cells); for (auto &p : CG.fr.wg) F(p); for (auto &p : CG.fr.scr) F(p);
+    if (CG.fr.st2) (void)hipStreamDestroy(CG.fr.st2);
+    if (CG.fr.fork) (void)hipEventDestroy(CG.fr.fork);
+    if (CG.fr.join) (void)hipEventDestroy(CG.fr.join);
+    CG.fr = CGridState::Frame{};
     F(CG.res.tab); F(CG.res.tiles); F(CG.res.tiles2); F(CG.res.pubmap); F(CG.res.gmask); F(CG.res.rec); F(CG.res.err); F(CG.res.pairs); F(CG.res.prof); F(CG.res.d_order); F(CG.res.live_win); F(CG.res.live_cell);
     CG.res = CGridState::Res{};
     {
@@ -351,6 +368,20 @@ static bool one_launch()
     return true;
 }
 static int one_subcycles(int ndte, bool first) { return one_launch() ? ndte - (first ? 1 : 0) : 0; }
+// Several ranks, no fold, visc_method = avg_zeta, the derived view of the static table, and rectangles for the marched kernel on THIS
+// rank: cg_strip marches them on a second stream while the three fused kernels' frame variants advance every other interior cell on
+// S.stream, with today's exchanges at today's points -- so a rank without rectangles simply runs today's schedule and the ranks
+// need not agree on anything.  CICE_EVP_HIP_CGRID_ONE=0 forces today's schedule (CICE_EVP_HIP_CGRID_MARCH_RANKS=0, test build: this
+// schedule alone off, for A/B).  Faster than the fused schedule on both cuts measured: the default.
+static bool march_ranks()
+{
+    if (!CG.fr.cells || CG.one.nitems <= 0 || !remote() || CG.tripole || CG.avg_strength || !geo_derived()) return false;
+    if (const char *e = env("CICE_EVP_HIP_CGRID_ONE"))
+        if (!std::atoi(e)) return false;
+    if (const char *e = env_test("CICE_EVP_HIP_CGRID_MARCH_RANKS")) return std::atoi(e) != 0;
+    return true;
+}
+static int march_subcycles(int ndte, bool first) { return march_ranks() ? ndte - (first ? 1 : 0) : 0; }
 static int res_launch(const EvpCgrid &A, int nsub, bool dry, double *const cur5[5], double *const alt5[5]);
 static int build_res_tables(const double *const *static23);
 
@@ -361,7 +392,7 @@ static int build_res_tables(const double *const *static23);
 static int enqueue_fused(EvpCgrid A, int ndte, bool first, int nres = 0)
 {
     double *cur = CG.f[CF_S12U], *other = CG.s12alt;
-    const bool one = one_launch();
+    const bool one = one_launch(), march = march_ranks();
     double *c4[4], *o4[4];
     for (int q = 0; q < 4; ++q) {
         c4[q] = CG.f[ONE_FIELDS[q]];
@@ -408,6 +439,36 @@ static int enqueue_fused(EvpCgrid A, int ndte, bool first, int nres = 0)
             for (int q = 0; q < 4; ++q) std::swap(c4[q], o4[q]);
             continue;
         }
+        if (march && !(first && k == 0)) {
+            // the rectangles marched on the second stream, every other interior cell by the frame variants of the three fused kernels
+            // here, with the exchanges of the fused schedule at their points: both read the previous subcycle's buffers, own disjoint
+            // cells of this subcycle's, and meet again before the buffers swap
+            const int fast = CG.fast ? 1 : 0;
+            EvpCgOne T{nullptr, nullptr, 0, 0, CG.one.ex, CG.one.ey, 0, c4[0], c4[1], c4[2], c4[3], CG.gslab, CG.inslab, S.n, nullptr, CG.gmask};
+            EvpCgStrip Z{CG.one.items, CG.one.nitems, ((CG.one.nitems + 3) / 4 + 7) / 8, CG.one.strip_len};
+            const CGridState::Frame &Q = CG.fr;
+            EvpCgFrame Fr{Q.cells, {Q.wg[0], Q.wg[1], Q.wg[2]}, {Q.nwg[0], Q.nwg[1], Q.nwg[2]}, c4[0], c4[1], c4[2], c4[3], Q.scr[0], Q.scr[1], Q.scr[2], Q.scr[3]};
+            for (int q = 0; q < 4; ++q) A.f[ONE_FIELDS[q]] = o4[q];
+            A.s12_in = cur;
+            A.f[CF_S12U] = other;
+            // (the frame's first launch goes ahead of the marched kernel, which fills the chip: DESIGN.md section 7)
+            HIPC(hipEventRecord(Q.fork, S.stream));
+            evp_launch_cgrid_frame(A, Fr, 0, fast, last, S.stream);
+            HIPC(hipStreamWaitEvent(Q.st2, Q.fork, 0));
+            evp_launch_cgrid_strip(A, T, Z, nullptr, fast, last, Q.st2);
+            HIPC(hipEventRecord(Q.join, Q.st2));
+            XCHG(A.f[CF_SHEARU], A.f[CF_SHEARU]);
+            evp_launch_cgrid_frame(A, Fr, 1, fast, last, S.stream);
+            XCHG(A.f[CF_ETA], A.f[CF_ZETA]);
+            XCHG(A.f[CF_SP], A.f[CF_SM]);
+            evp_launch_cgrid_frame(A, Fr, 2, fast, last, S.stream);
+            XCHG(other, other);
+            XCHG(A.f[CF_UE], A.f[CF_VN]);
+            HIPC(hipStreamWaitEvent(S.stream, Q.join, 0));
+            std::swap(cur, other);
+            for (int q = 0; q < 4; ++q) std::swap(c4[q], o4[q]);
+            continue;
+        }
         if (first && k == 0 && CG.avg_strength) {
             // (only with cg_one for the rest: fused_schedule) the first subcycle as the five launches, stress12U in place
             evp_launch_cgrid_phase(A, 0, 1, S.stream);
@@ -439,7 +500,7 @@ static int enqueue_fused(EvpCgrid A, int ndte, bool first, int nres = 0)
         XCHG(other, other);
         XCHG(A.f[CF_UE], A.f[CF_VN]);
         std::swap(cur, other);
-        if (one && first && k == 0)          // cells no subcycle writes (no ice, ghost cells nothing is copied into): the same in both buffers
+        if ((one || march) && first && k == 0)          // cells no subcycle writes (no ice, ghost cells nothing is copied into): the same in both buffers
             for (int q = 0; q < 4; ++q)
                 HIPC(hipMemcpyAsync(o4[q], c4[q], S.n * sizeof(double), hipMemcpyDeviceToDevice, S.stream));
     }
@@ -528,17 +589,20 @@ static int build_one_tables(const double *const *static23)
     std::vector<int32_t> tab, tiles;
     build_window_table(d, P, OX, OY, strip, tiles, tab);       // halo_plan.cpp (host only: CPU known-answer test)
     CGridState::One &O = CG.one;
-    O.ntiles = (int)(tiles.size() / 4);
-    O.ox = OX;
-    O.oy = OY;
-    O.per_xcd = (O.ntiles + 7) / 8;
-    HIPC(hipMalloc((void **)&O.tab, tab.size() * sizeof(int)));
-    HIPC(hipMalloc((void **)&O.tiles, tiles.size() * sizeof(int32_t)));
-    HIPC(hipMemcpyAsync(O.tab, tab.data(), tab.size() * sizeof(int), hipMemcpyHostToDevice, S.stream));
-    HIPC(hipMemcpyAsync(O.tiles, tiles.data(), tiles.size() * sizeof(int32_t), hipMemcpyHostToDevice, S.stream));
-    for (auto &p : O.alt)
-        if (alloc_d(&p, S.n)) return -1;
-    if (env_test("CICE_EVP_HIP_CGRID_PROF") && std::atoi(env_test("CICE_EVP_HIP_CGRID_PROF"))) {
+    const bool ranks = remote();                 // no window kernel here: the table only tells which cells are regular
+    if (!ranks) {
+        O.ntiles = (int)(tiles.size() / 4);
+        O.ox = OX;
+        O.oy = OY;
+        O.per_xcd = (O.ntiles + 7) / 8;
+        HIPC(hipMalloc((void **)&O.tab, tab.size() * sizeof(int)));
+        HIPC(hipMalloc((void **)&O.tiles, tiles.size() * sizeof(int32_t)));
+        HIPC(hipMemcpyAsync(O.tab, tab.data(), tab.size() * sizeof(int), hipMemcpyHostToDevice, S.stream));
+        HIPC(hipMemcpyAsync(O.tiles, tiles.data(), tiles.size() * sizeof(int32_t), hipMemcpyHostToDevice, S.stream));
+        for (auto &p : O.alt)
+            if (alloc_d(&p, S.n)) return -1;
+    }
+    if (!ranks && env_test("CICE_EVP_HIP_CGRID_PROF") && std::atoi(env_test("CICE_EVP_HIP_CGRID_PROF"))) {
         HIPC(hipMalloc((void **)&O.prof, (size_t)O.ntiles * 8 * sizeof(unsigned long long)));
         HIPC(hipMemsetAsync(O.prof, 0, (size_t)O.ntiles * 8 * sizeof(unsigned long long), S.stream));
     }
@@ -629,6 +693,9 @@ static int build_one_tables(const double *const *static23)
             // 32 us, 408 of 16 49)
             long slots = 2048;
             if (const char *e = env_test("CICE_EVP_HIP_CGRID_STRIP_ITEMS")) slots = std::max(1, std::atoi(e));
+            // (several ranks, A/B: so many of the resident slots left to the frame's workgroups, which run beside the marched kernel)
+            if (ranks)
+                if (const char *e = env_test("CICE_EVP_HIP_CGRID_MARCH_RESERVE")) slots = std::max<long>(64, slots - std::max(0, std::atoi(e)));
             int seg_forced = 0;
             if (const char *e = env_test("CICE_EVP_HIP_CGRID_STRIP_SEG")) seg_forced = std::max(1, std::atoi(e));
             std::vector<int32_t> items;
@@ -641,6 +708,30 @@ static int build_one_tables(const double *const *static23)
                     tiles_e.insert(tiles_e.end(), tiles.begin() + 4 * w, tiles.begin() + 4 * w + 4);
                     tab_e.insert(tab_e.end(), tab.begin() + (size_t)w * per, tab.begin() + (size_t)(w + 1) * per);
                 }
+            if (ranks) {
+                // the frame: every interior cell the items do not own, and where each level of the fused chain has to run for it
+                CgFramePlan FP;
+                std::string why;
+                if (build_cg_frame(d, P, items, FP, why) != 1) return fail(-4, "C-grid EVP: %s", why.c_str());
+                tiles_e.clear();
+                tab_e.clear();
+                CGridState::Frame &Q = CG.fr;
+                Q.ncells = FP.frame_cells;
+                HIPC(hipMalloc((void **)&Q.cells, FP.cells.size()));
+                HIPC(hipMemcpy(Q.cells, FP.cells.data(), FP.cells.size(), hipMemcpyHostToDevice));
+                for (int k = 0; k < 3; ++k) {
+                    Q.nwg[k] = (int)FP.wg[k].size();
+                    HIPC(hipMalloc((void **)&Q.wg[k], std::max<size_t>(1, FP.wg[k].size()) * sizeof(int32_t)));
+                    HIPC(hipMemcpy(Q.wg[k], FP.wg[k].data(), FP.wg[k].size() * sizeof(int32_t), hipMemcpyHostToDevice));
+                }
+                for (auto &p : Q.scr)
+                    if (alloc_d(&p, S.n)) return -1;
+                for (auto &p : O.alt)
+                    if (alloc_d(&p, S.n)) return -1;
+                HIPC(hipStreamCreateWithFlags(&Q.st2, hipStreamNonBlocking));
+                HIPC(hipEventCreateWithFlags(&Q.fork, hipEventDisableTiming));
+                HIPC(hipEventCreateWithFlags(&Q.join, hipEventDisableTiming));
+            }
             O.nitems = (int)(items.size() / 6);
             O.ntiles_e = (int)(tiles_e.size() / 4);
             O.ex = EX; O.ey = EY;
@@ -966,8 +1057,13 @@ int finish_upload(int32_t visc_method);
 
 std::string cgrid_schedule()
 {
+    char buf[200];
+    if (CG.geo && CG.uploaded && march_ranks()) {
+        std::snprintf(buf, sizeof buf, "C grid: zone marched + frame (%ld cells in %d items beside %ld frame cells, fused chain and its exchanges)",
+                      CG.one.strip_cells, CG.one.nitems, CG.fr.ncells);
+        return buf;
+    }
     if (!CG.geo || !fold_exchange()) return "";
-    char buf[160];
     std::snprintf(buf, sizeof buf, "C grid: five phases + fold exchange, fold rows on %d ranks (%d staging slots here)", S.plan.cg_fold_ranks,
                   S.plan.cg_tail);
     return buf;
@@ -1039,9 +1135,11 @@ int cice_evp_hip_cgrid_set_geometry(const double *const *static23)
     HIPC(hipMemcpyAsync(CG.img_dst, dst.data(), dst.size() * sizeof(int), hipMemcpyHostToDevice, S.stream));
     if (tripole && (P.fold_rows == 1 || P.cg_split))   // (ranks without the fold rows run the same schedule with empty lists)
         if (int rc = build_fold_lists()) return rc;
-    if (!tripole && S.plan.peers.empty() && S.d.nx_block >= 3 && S.d.ny_block >= 3) {
+    if (!tripole && S.d.nx_block >= 3 && S.d.ny_block >= 3) {
+        // (several ranks: the marched kernel's rectangles and the frame around them only -- no window runs there)
         if (int rc = build_one_tables(static23)) return rc;
-        if (int rc = build_res_tables(static23)) return rc;
+        if (S.plan.peers.empty())
+            if (int rc = build_res_tables(static23)) return rc;
     }
     if (tripole && !tfold && S.plan.peers.empty() && P.fold_rows == 1 && S.d.ew_boundary_type == CICE_EVP_BND_CYCLIC)
         if (int rc = build_res_tables(static23)) return rc;
@@ -1179,7 +1277,7 @@ int cice_evp_hip_cgrid_subcycle(int32_t ndte)
     HIPC(hipEventRecord(S.ev0, S.stream));
     // (the resident launch carries a fresh epoch in its arguments: enqueued eagerly, with the few launches around it)
     if (nres == 0 && S.use_graph && (!remote() || S.direct.on)) {     // RCCL point-to-point is enqueued eagerly (as the B-grid loop does)
-        const std::pair<int, int> key(ndte, (geo_derived() ? 128 : 0) | (fused && one_launch() ? 64 : 0) | (CG.one.flip << 5) | (CG.fast ? 16 : 0) | (CG.flip << 3) |
+        const std::pair<int, int> key(ndte, (geo_derived() ? 128 : 0) | (fused && one_launch() ? 64 : 0) | (fused && march_ranks() ? 256 : 0) | (CG.one.flip << 5) | (CG.fast ? 16 : 0) | (CG.flip << 3) |
                                                 (fused ? 4 : 0) | (CG.first ? 2 : 0) | CG.avg_strength);
         auto it = CG.graphs.find(key);
         if (it == CG.graphs.end()) {
@@ -1202,13 +1300,14 @@ int cice_evp_hip_cgrid_subcycle(int32_t ndte)
         std::swap(CG.f[CF_S12U], CG.s12alt);
         CG.flip ^= 1;
     }
-    if (fused && ((one_subcycles(ndte, CG.first) - nres) & 1)) {      // and so are uvelE, vvelN, stresspT, stressmT
+    if (fused && ((one_subcycles(ndte, CG.first) + march_subcycles(ndte, CG.first) - nres) & 1)) {      // and so are uvelE, vvelN, stresspT, stressmT
         for (int q = 0; q < 4; ++q) std::swap(CG.f[ONE_FIELDS[q]], CG.one.alt[q]);
         CG.one.flip ^= 1;
     }
     HIPC(hipEventRecord(S.ev1, S.stream));
     HIPC(hipGetLastError());
     CG.t_one = fused ? one_subcycles(ndte, CG.first) - nres : 0;
+    CG.t_march = fused ? march_subcycles(ndte, CG.first) : 0;
     CG.res.last_nsub = nres;
     CG.first = false;
     CG.t_nsub = ndte;
@@ -1631,6 +1730,10 @@ int cice_evp_hip_cgrid_timings(double *out, int32_t n)
     if (n >= 16) out[15] = fold_exchange() ? 1.0 : 0.0;            // tripole: the blocks next to the fold on several ranks (fold exchange)
     if (n >= 17) out[16] = CG.tripole ? (double)S.plan.cg_fold_ranks : 0.0;   // ... on so many ranks
     if (n >= 18) out[17] = fold_exchange() ? (double)S.plan.cg_tail : 0.0;    // ... staging slots of this rank
+    if (n >= 20) {
+        out[18] = (double)CG.t_march;                 // subcycles of the last call that ran as "zone marched + frame" (several ranks)
+        out[19] = (double)CG.fr.ncells;               // ... and the frame cells of this rank (0: no such plan here)
+    }
     return 0;
 }
 

@@ -893,6 +893,138 @@ void strip_windows(const std::vector<StripZone> &zones, const std::vector<int32_
                 in_zone[(size_t)w] = 1;
 }
 
+int build_cg_frame(const cice_evp_hip_dims &d, const HaloPlan &P, const std::vector<int32_t> &items, CgFramePlan &F, std::string &why)
+{
+    F = CgFramePlan();
+    why.clear();
+    if (P.peers.empty() && P.cg_peers.empty()) {
+        why = "no neighbour on another rank";
+        return 0;
+    }
+    const int nxb = d.nx_block, nyb = d.ny_block;
+    const long plane = (long)nxb * nyb;
+    F.cells.assign((size_t)plane * d.nblocks, 0);
+    auto off = [&](int b, int i, int j) { return (size_t)b * plane + (size_t)(j - 1) * nxb + (size_t)(i - 1); };
+    auto inside = [&](int i, int j) { return i >= 1 && i <= nxb && j >= 1 && j <= nyb; };
+    auto interior = [&](int b, int i, int j) { return i >= d.ilo[b] && i <= d.ihi[b] && j >= d.jlo[b] && j <= d.jhi[b]; };
+    auto bad = [&](const char *what, int b, int i, int j) {
+        char buf[200];
+        std::snprintf(buf, sizeof buf, "frame plan: %s at block %d cell (%d, %d)", what, b, i, j);
+        why = buf;
+        return -1;
+    };
+    // the stencils, as offsets from the evaluating cell: T cells level C reads (etax2T around its three corners; the new stresspT,
+    // stressmT of the east and north neighbour are among them), corners level C and level T read shearU at
+    static const int c_reads_t[8][2] = {{0, 0}, {1, 0}, {0, 1}, {1, 1}, {0, -1}, {1, -1}, {-1, 0}, {-1, 1}};
+    static const int c_reads_s[3][2] = {{0, 0}, {0, -1}, {-1, 0}};
+    static const int t_reads_s[4][2] = {{0, 0}, {0, -1}, {-1, -1}, {-1, 0}};
+    // ---- ownership: the items' cells, then everything else of the interior ----
+    for (size_t k = 0; k + 5 < items.size(); k += 6) {
+        const int b = items[k], c = items[k + 1], ja = items[k + 2], jb = items[k + 3], lo = items[k + 4], hi = items[k + 5];
+        if (b < 0 || b >= d.nblocks) return bad("an item of a block that is not here", b, c, ja);
+        for (int j = ja; j <= jb; ++j)
+            for (int i = c - 2 + lo; i <= c - 2 + hi; ++i) {
+                if (!interior(b, i, j)) return bad("a marched cell outside the interior", b, i, j);
+                uint8_t &f = F.cells[off(b, i, j)];
+                if (f & CGF_ZONE) return bad("a cell two items own", b, i, j);
+                f |= CGF_ZONE;
+                ++F.zone_cells;
+            }
+    }
+    long n_interior = 0;
+    for (int b = 0; b < d.nblocks; ++b)
+        for (int j = d.jlo[b]; j <= d.jhi[b]; ++j)
+            for (int i = d.ilo[b]; i <= d.ihi[b]; ++i) {
+                ++n_interior;
+                uint8_t &f = F.cells[off(b, i, j)];
+                if (!(f & CGF_ZONE)) {
+                    f |= CGF_FRAME;
+                    ++F.frame_cells;
+                }
+            }
+    // ---- the levels, each dilated by what the next one reads of it ----
+    for (int b = 0; b < d.nblocks; ++b) {
+        for (int j = d.jlo[b]; j <= d.jhi[b] + 1; ++j)
+            for (int i = d.ilo[b]; i <= d.ihi[b] + 1; ++i) {
+                if (!inside(i, j)) return bad("the extra T row / column outside the array", b, i, j);
+                const bool in = interior(b, i, j);
+                if (!in) {
+                    F.cells[off(b, i, j)] |= CGF_T;          // (the reference's T list: stress12T of the ghost row / column)
+                    continue;
+                }
+                if (!(F.cells[off(b, i, j)] & CGF_FRAME)) continue;
+                for (const auto &r : c_reads_t)
+                    if (interior(b, i + r[0], j + r[1])) F.cells[off(b, i + r[0], j + r[1])] |= CGF_T;
+                for (const auto &r : c_reads_s)
+                    if (interior(b, i + r[0], j + r[1])) F.cells[off(b, i + r[0], j + r[1])] |= CGF_S;
+            }
+        for (int j = d.jlo[b]; j <= d.jhi[b] + 1; ++j)
+            for (int i = d.ilo[b]; i <= d.ihi[b] + 1; ++i)
+                if (F.cells[off(b, i, j)] & CGF_T)
+                    for (const auto &r : t_reads_s)
+                        if (interior(b, i + r[0], j + r[1])) F.cells[off(b, i + r[0], j + r[1])] |= CGF_S;
+    }
+    // ---- the invariants ----
+    if (F.zone_cells + F.frame_cells != n_interior) return bad("zone and frame do not add up to the interior", 0, 0, 0);
+    auto cell_of = [&](size_t c, int &b, int &i, int &j) {
+        b = (int)(c / (size_t)plane);
+        j = (int)((c % (size_t)plane) / nxb) + 1;
+        i = (int)((c % (size_t)plane) % nxb) + 1;
+    };
+    auto must_be_frame = [&](int32_t c, const char *what) {
+        if (c < 0 || (size_t)c >= F.cells.size()) return 0;          // (a staging slot behind the array: no cell)
+        if (F.cells[(size_t)c] & CGF_FRAME) return 0;
+        int b, i, j;
+        cell_of((size_t)c, b, i, j);
+        return bad(what, b, i, j);
+    };
+    for (const std::vector<HaloPeer> *pp : {&P.peers, &P.cg_peers})
+        for (const HaloPeer &p : *pp)
+            for (int32_t c : p.send_src)
+                if (must_be_frame(c, "a cell another rank receives is not a frame cell")) return -1;
+    for (size_t k = 0; k < P.local_src.size(); ++k)
+        if (P.local_src[k] >= 0 && must_be_frame(P.local_src[k], "a cell with a ghost image is not a frame cell")) return -1;
+    for (int b = 0; b < d.nblocks; ++b)
+        for (int j = 1; j <= nyb; ++j)
+            for (int i = 1; i <= nxb; ++i) {
+                const uint8_t f = F.cells[off(b, i, j)];
+                const bool in = interior(b, i, j);
+                if ((f & CGF_ZONE) && (f & CGF_FRAME)) return bad("a cell in both sets", b, i, j);
+                if (in != ((f & (CGF_ZONE | CGF_FRAME)) != 0)) return bad("a cell of neither set, or a ghost cell of one", b, i, j);
+                if ((f & (CGF_S | CGF_FRAME)) && !in) return bad("level S or C on a ghost cell", b, i, j);
+                if (f & CGF_FRAME) {
+                    if (!(f & CGF_T) || !(f & CGF_S)) return bad("a frame cell without its own levels", b, i, j);
+                    for (const auto &r : c_reads_t)
+                        if (interior(b, i + r[0], j + r[1]) && !(F.cells[off(b, i + r[0], j + r[1])] & CGF_T))
+                            return bad("etax2T read where level T does not run", b, i + r[0], j + r[1]);
+                    for (const auto &r : c_reads_s)
+                        if (interior(b, i + r[0], j + r[1]) && !(F.cells[off(b, i + r[0], j + r[1])] & CGF_S))
+                            return bad("shearU read where level S does not run", b, i + r[0], j + r[1]);
+                }
+                if (f & CGF_T)
+                    for (const auto &r : t_reads_s) {
+                        if (!inside(i + r[0], j + r[1])) return bad("level T loads outside the array", b, i, j);
+                        if (interior(b, i + r[0], j + r[1]) && !(F.cells[off(b, i + r[0], j + r[1])] & CGF_S))
+                            return bad("shearU read where level S does not run", b, i + r[0], j + r[1]);
+                    }
+                // (levels S and C: the velocities, lengths and masks one cell around the cell)
+                if ((f & (CGF_S | CGF_FRAME)) && !(inside(i - 1, j - 1) && inside(i + 1, j + 1))) return bad("a stencil outside the array", b, i, j);
+            }
+    // ---- the workgroups of each level ----
+    const int gx = (nxb + 63) / 64, gy = (nyb + 3) / 4;
+    const int bit[3] = {CGF_S, CGF_T, CGF_FRAME};
+    for (int k = 0; k < 3; ++k) {
+        std::vector<uint8_t> on((size_t)gx * gy * d.nblocks, 0);
+        for (int b = 0; b < d.nblocks; ++b)
+            for (int j = 1; j <= nyb; ++j)
+                for (int i = 1; i <= nxb; ++i)
+                    if (F.cells[off(b, i, j)] & bit[k]) on[((size_t)b * gy + (size_t)(j - 1) / 4) * gx + (size_t)(i - 1) / 64] = 1;
+        for (size_t w = 0; w < on.size(); ++w)
+            if (on[w]) F.wg[k].push_back((int32_t)w);
+    }
+    return 1;
+}
+
 int cgres_dependencies(const cice_evp_hip_dims &d, bool tripole, const std::vector<int32_t> &tiles, const std::vector<int32_t> &tab,
                        std::vector<uint8_t> *pub, int *n_edges, int *n_oneway)
 {

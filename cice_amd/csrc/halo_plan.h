@@ -217,6 +217,30 @@ int strip_items(const std::vector<StripZone> &zones, int ex, int ey, int lo0, lo
 // 1 for every window of `tiles` that lies inside one of the rectangles (the marched kernel owns its cells), 0: cg_one keeps it
 void strip_windows(const std::vector<StripZone> &zones, const std::vector<int32_t> &tiles, std::vector<uint8_t> &in_zone);
 
+// ---- the marched kernel beside the fused chain on a rank with neighbours on other ranks (evp_host_cgrid.cpp: "zone marched + frame") ----
+// A rank's interior cells split in two: the ZONE -- the cells the marched kernel's items own -- and the FRAME, every other interior
+// cell, which the frame variants of the three fused kernels advance (evp_cgrid.hip: cg_frame_*).  A frame cell reads intermediates of
+// its neighbours, so each phase also runs on the zone cells the next one reads ("dilation": stored to scratch arrays only):
+//   level C (momentum step) on the frame cells; it reads etax2T around its three corners and the new stresspT / stressmT of its east and
+//           north neighbour (T cells within one of it), and shearU at its own, south and west corner;
+//   level T (stressC_T) on those T cells and on the reference's extra T row and column (ghost cells i = ihi + 1, j = jhi + 1, which keep
+//           stress12T only); it reads shearU at its four corners (own, west, south, south-west);
+//   level S (strain_rates_U's shear) on every interior cell one of the two reads shearU of.
+// cells: per array cell the CGF_* bits; wg[k]: the workgroups of 64 x 4 cells ((b * gy + by) * gx + bx, gx = ceil(nx_block / 64), gy =
+// ceil(ny_block / 4)) that hold a cell of level S / T / C, ascending.
+enum { CGF_FRAME = 1, CGF_S = 2, CGF_T = 4, CGF_ZONE = 8 };
+struct CgFramePlan {
+    std::vector<uint8_t> cells;
+    std::vector<int32_t> wg[3];
+    long zone_cells = 0, frame_cells = 0;
+};
+// items: x 6 as strip_items makes them (may be empty: every interior cell is a frame cell).  Returns 1 and the plan; 0 with `why` when
+// the rank has no neighbour on another rank (nothing to plan: the one-launch schedule serves it); -1 with `why` when one of the plan's
+// invariants does not hold -- the two sets are disjoint and cover the interior; every cell a peer receives and every cell with a ghost
+// image on this rank is a frame cell; every shearU / etax2T / stresspT a level reads at an interior cell is produced by the level
+// before it; every cell a workgroup evaluates has its whole stencil (one cell around it) inside the block's array.
+int build_cg_frame(const cice_evp_hip_dims &d, const HaloPlan &P, const std::vector<int32_t> &items, CgFramePlan &F, std::string &why);
+
 // The hand-off graph of the resident windows (tiles / tab as build_window_table(..., 16, 16, ., extra = 1) or
 // build_fold_window_table made them): window w READS window p when it polls a cell p owns.  A window cannot start subcycle j + 1
 // before every window it reads has finished subcycle j, so a window p is never more than len subcycles ahead of w, len = the

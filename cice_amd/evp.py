@@ -54,7 +54,7 @@ EXPORTS = [
 # libcice_evp_hip_testing.so only (include/cice_evp_hip_testing.h): plan introspection of the CPU tests, read-outs of the tools,
 # the test transport
 TEST_EXPORTS = [
-    "cice_evp_hip_cgrid_fold_plan", "cice_evp_hip_cgrid_window_plan", "cice_evp_hip_cgrid_window_plan_ext", "cice_evp_hip_cgrid_window_deps", "cice_evp_hip_cgrid_strip_plan", "cice_evp_hip_cgrid_strip_zones", "cice_evp_hip_set_test_transport", "cice_evp_hip_march_plan",
+    "cice_evp_hip_cgrid_fold_plan", "cice_evp_hip_cgrid_window_plan", "cice_evp_hip_cgrid_window_plan_ext", "cice_evp_hip_cgrid_window_deps", "cice_evp_hip_cgrid_strip_plan", "cice_evp_hip_cgrid_strip_zones", "cice_evp_hip_cgrid_frame_plan", "cice_evp_hip_set_test_transport", "cice_evp_hip_march_plan",
     "cice_evp_hip_debug_cuload", "cice_evp_hip_debug_prof", "cice_evp_hip_debug_cgrid_prof", "cice_evp_hip_debug_cgres_prof", "cice_evp_hip_plan_build", "cice_evp_hip_halo_plan", "cice_evp_hip_seam_plan",
     "cice_evp_hip_peer_plan", "cice_evp_hip_peer_signs", "cice_evp_hip_center_plan", "cice_evp_hip_stress_plan",
     "cice_evp_hip_fold_split_plan", "cice_evp_hip_plan_flags", "cice_evp_hip_fold_images_plan", "cice_evp_hip_cgrid_fold_xplan",
@@ -74,6 +74,7 @@ TEST_ENV = [
     "CICE_EVP_HIP_MARCH_EXT", "CICE_EVP_HIP_MARCH_DIRECT", "CICE_EVP_HIP_CGRID_FUSED", "CICE_EVP_HIP_CGRID_GEO",
     "CICE_EVP_HIP_CGRID_RES_SLEEP", "CICE_EVP_HIP_CGRID_RES_CULL", "CICE_EVP_HIP_CGRID_RES_DEBUG",
     "CICE_EVP_HIP_CGRID_STRIP", "CICE_EVP_HIP_CGRID_STRIP_SEG", "CICE_EVP_HIP_CGRID_STRIP_EDGE", "CICE_EVP_HIP_CGRID_STRIP_RIDE", "CICE_EVP_HIP_CGRID_STRIP_LEN", "CICE_EVP_HIP_CGRID_STRIP_ITEMS", "CICE_EVP_HIP_CGRID_STRIP_LAST",
+    "CICE_EVP_HIP_CGRID_MARCH_RESERVE", "CICE_EVP_HIP_CGRID_MARCH_RANKS",
 ]
 # C-grid subcycle (cice_evp_hip_cgrid_*): order of the pointer tables, see include/cice_evp_hip.h
 CGRID_FIELDS = ["uvelE", "vvelE", "uvelN", "vvelN", "uvel", "vvel", "stresspT", "stressmT", "stress12T", "stress12U",
@@ -306,6 +307,27 @@ def cgrid_strip_zones(dims: "Dims", ex=32, ey=8) -> list:
     _check(lib, lib.cice_evp_hip_cgrid_strip_zones(C.byref(dims), C.c_int32(ex), C.c_int32(ey), C.byref(n), _ip(z), C.c_int32(len(z))), "(cgrid_strip_zones)")
     return [dict(block=int(v[0]), i0=int(v[1]), i1=int(v[2]), j0=int(v[3]), j1=int(v[4]), lengths_ok=bool(v[5]),
                  verified=tuple(int(x) for x in v[6:10])) for v in z[:n.value]]
+
+
+def cgrid_frame_plan(dims: "Dims", ex=32, ey=8, lo0=3, slots=2048, seg_min=8, seg=0):
+    """Host only: how a rank with neighbours on other ranks shares its interior between the marched C-grid kernel (zone) and the
+    frame variants of the fused kernels (see the testing header).  None when the plan declines (no neighbour on another rank)."""
+    lib = load_library(testing=True)
+    info = np.zeros(6, dtype=np.int64)
+    ip = info.ctypes.data_as(C.POINTER(C.c_int64))
+    a = (C.byref(dims), C.c_int32(ex), C.c_int32(ey), C.c_int32(lo0), C.c_int32(slots), C.c_int32(seg_min), C.c_int32(seg), ip)
+    rc = lib.cice_evp_hip_cgrid_frame_plan(*a, None, None, C.c_int32(0), None, C.c_int32(0))
+    if rc == 1:
+        return None
+    _check(lib, rc, "(cgrid_frame_plan)")
+    cells = np.zeros((dims.nblocks, dims.ny_block, dims.nx_block), dtype=np.uint8)
+    wg = np.zeros(max(int(info[2:5].sum()), 1), dtype=np.int32)
+    items = np.zeros((max(int(info[5]), 1), 6), dtype=np.int32)
+    _check(lib, lib.cice_evp_hip_cgrid_frame_plan(*a, cells.ctypes.data_as(C.POINTER(C.c_uint8)), _ip(wg), C.c_int32(len(wg)), _ip(items),
+                                                  C.c_int32(len(items))), "(cgrid_frame_plan)")
+    n = [int(v) for v in info[2:5]]
+    return dict(zone_cells=int(info[0]), frame_cells=int(info[1]), cells=cells, items=items[:int(info[5])],
+                wg=[wg[:n[0]], wg[n[0]:n[0] + n[1]], wg[n[0] + n[1]:n[0] + n[1] + n[2]]])
 
 
 def stream_probe(ncells: int) -> float:
@@ -573,14 +595,15 @@ class EvpHip:
         _check(self.lib, self.lib.cice_evp_hip_cgrid_sync(), "(dyn_evp_hip_cgrid_sync)")
 
     def cgrid_timings(self):
-        out = np.zeros(18)
-        _check(self.lib, self.lib.cice_evp_hip_cgrid_timings(_dp(out), C.c_int32(18)), "(dyn_evp_hip_cgrid_timings)")
+        out = np.zeros(20)
+        _check(self.lib, self.lib.cice_evp_hip_cgrid_timings(_dp(out), C.c_int32(20)), "(dyn_evp_hip_cgrid_timings)")
         return dict(loop_ms=float(out[0]), nsub=int(out[1]), prep_ms=float(out[2]), one_launch_subcycles=int(out[3]),
                     geometry_derived=bool(out[4]), resident_subcycles=int(out[5]), resident_probe_ms=float(out[6]),
                     resident_fallbacks=int(out[7]), resident_windows_with_ice=int(out[8]), resident_windows=int(out[9]),
                     marched_items=int(out[10]), marched_cells=int(out[11]), marched_edge_windows=int(out[12]),
                     marched_segment_rows=int(out[13]), marched_lengths_derived=bool(out[14]), fold_exchange=bool(out[15]),
-                    fold_ranks=int(out[16]), fold_staging_slots=int(out[17]))
+                    fold_ranks=int(out[16]), fold_staging_slots=int(out[17]),
+                    marched_ranks_subcycles=int(out[18]), frame_cells=int(out[19]))
 
     def debug_cgres_prof(self):
         self._need_testing("debug_cgres_prof")

@@ -353,7 +353,13 @@ int cice_evp_hip_cgrid_dyn_finish(double *strocnxN, double *strocnyN, double *st
  * all its windows, [10] .. [14] (n >= 15) the one-launch schedule's marched kernel (evp_cgrid.hip: cg_strip -- the interior of
  * large blocks, one wave per strip of 61 columns and segment of rows): work items (0: not in use), cells it owns, windows the
  * windowed kernel keeps beside it (the block edges), rows per segment, 1 if it forms dxT, dyT, dxU, dyU, dxE, dyN from dxN and dyE
- * (the reference's start-up means, verified bit for bit on the caller's arrays)  */
+ * (the reference's start-up means, verified bit for bit on the caller's arrays),
+ * [15] .. [17] (n >= 18) tripole grids: 1 if the blocks next to the fold have more than one owner (fold exchange), on how many ranks,
+ * staging slots of this rank,
+ * [18], [19] (n >= 20) several ranks, no fold, visc_method = avg_zeta: subcycles of the last call that ran as "zone marched + frame" --
+ * cg_strip on the interior of the blocks (the items of [10]) on a second stream beside the three fused kernels' frame variants and
+ * their five exchanges on every other interior cell --, and those frame cells on this rank (0: no such plan here; a rank without
+ * rectangles for the marched kernel runs the fused schedule, and so does every rank under CICE_EVP_HIP_CGRID_ONE=0)  */
 int cice_evp_hip_cgrid_timings(double *out, int32_t n);
 
 /* ---- multi-GPU: RCCL point-to-point halo over xGMI ---------------------------- */

@@ -59,6 +59,15 @@ int cice_evp_hip_cgrid_strip_plan(const cice_evp_hip_dims *dims, int32_t ex, int
  * rectangle of cells the host then checks them on (first and last column, first and last row; halo_plan.h: strip_len_range).  The
  * library may still give a window row back where that check fails.  Pass NULL to learn the count.                                    */
 int cice_evp_hip_cgrid_strip_zones(const cice_evp_hip_dims *dims, int32_t ex, int32_t ey, int32_t *n_zones, int32_t *zones10, int32_t zones_cap);
+/* Host only: how a rank with neighbours on other ranks shares its interior cells between the marched kernel (the zone: the items of
+ * cice_evp_hip_cgrid_strip_plan with the same ex, ey, lo0, slots, seg_min, seg) and the frame variants of the three fused kernels
+ * (cice_amd/csrc/halo_plan.h: build_cg_frame, which checks the plan's invariants itself and fails with -5 where one does not hold).
+ * cells: one byte per array cell -- 1 frame cell, 2 level S (strain_rates_U) runs here, 4 level T (stressC_T), 8 zone cell.  wg: the
+ * workgroups of 64 x 4 cells, id = (block * ceil(ny_block / 4) + row) * ceil(nx_block / 64) + column, of level S, then T, then C (the
+ * momentum step: frame cells only).  info6 = {zone cells, frame cells, workgroups of S, T, C, items}.  Arrays may be NULL.  Returns
+ * 0, or 1 when the rank has no neighbour on another rank (the plan declines: nothing is written but zeros to info6).             */
+int cice_evp_hip_cgrid_frame_plan(const cice_evp_hip_dims *dims, int32_t ex, int32_t ey, int32_t lo0, int32_t slots, int32_t seg_min, int32_t seg,
+                                  int64_t *info6, uint8_t *cells, int32_t *wg, int32_t wg_cap, int32_t *items6, int32_t items_cap);
 /* Test hook: route the exchanges and the rank agreements of the marching path through HOST buffers and the caller's
  * callbacks instead of RCCL (which refuses two ranks on one device), so that its several-rank form can be run as
  * processes sharing one GPU (tools/mailbox_2proc.py --march: torch.distributed gloo underneath).  xchg: per peer q

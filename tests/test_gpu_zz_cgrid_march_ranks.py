@@ -1,0 +1,83 @@
+"""GPU (-m gpu), run last: the C-grid subcycle on several ranks with the marched kernel (cg_strip) on the interior of every block
+and the frame variants of the three fused kernels on the block edges ("zone marched + frame": cice_amd/csrc/evp_host_cgrid.cpp,
+enqueue_fused; plan: halo_plan.cpp, build_cg_frame).  Several ranks = several processes on the one GPU of the test box
+(tools/mailbox_2proc.py --cgrid --expect-marched): every rank's arrays, ghost cells included, must equal the one-rank, one-block run
+of the same state bit for bit, and every rank with rectangles for the marched kernel must have run every subcycle of its last call
+-- but the first after an upload -- on the new schedule.
+
+Each subprocess gets ONE attempt under a timeout; a failed run leaves its whole output in a file under
+test_failures/ (git-ignored) and fails."""
+import os
+import subprocess
+import sys
+from pathlib import Path
+
+import pytest
+
+pytestmark = pytest.mark.gpu
+
+ROOT = Path(__file__).resolve().parents[1]
+# the marched kernel wherever a regular window exists (test build), for grids far below its 300 000-cell default
+FORCED = {"CICE_EVP_HIP_CGRID_STRIP": "1"}
+
+
+def _free_port():
+    import socket
+    with socket.socket() as sk:
+        sk.bind(("127.0.0.1", 0))
+        return sk.getsockname()[1]
+
+
+def _run(name, world, workload, shape, extra, env_extra, ndte=24, timeout=900):
+    cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", f"--nproc-per-node={world}",
+           "--master-addr", "127.0.0.1", "--master-port", str(_free_port()),
+           str(ROOT / "tools" / "mailbox_2proc.py"), "--cgrid", "--workload", workload, "--ndte", str(ndte), "--shape", shape] + extra
+    env = dict(os.environ, CICE_EVP_HIP_HALO_TIMEOUT_MS="20000", **env_extra)
+    r = subprocess.run(cmd, capture_output=True, text=True, timeout=timeout, env=env)
+    ok = r.returncode == 0 and "MAILBOX_2PROC OK" in r.stdout
+    if not ok:
+        try:
+            (ROOT / "test_failures").mkdir(exist_ok=True)
+            (ROOT / "test_failures" / f"cgrid_march_ranks_fail_{name}.log").write_text(" ".join(cmd) + "\n" + r.stdout + "\n---\n" + r.stderr)
+        except OSError:
+            pass
+    print([ln for ln in r.stdout.splitlines() if ln.startswith("MAILBOX_2PROC")])
+    assert ok, (r.stdout[-2000:], r.stderr[-3000:])
+
+
+# blocks of 200 x 216 cells (216 = 5 * 42 + 6 interior rows) unless noted
+MARCHED = {
+    "world2_cut2x1": (2, "400x216", "2x1", []),
+    "world2_cut1x2": (2, "400x432", "1x2", []),
+    "world4_cut2x2": (4, "400x432", "2x2", []),                                       # corner neighbours on other ranks
+    "world4_cut2x2_blocks2x2": (4, "800x864", "2x2", ["--blocks-per-rank", "2x2"]),   # local and remote neighbours on one rank
+    "world3_cut3x1": (3, "600x216", "3x1", []),
+    "maskhalo_caps": (2, "400x216", "2x1", ["--maskhalo", "--case", "caps"]),         # every in-loop exchange through the masked halo
+    "prep": (2, "400x432", "1x2", ["--prep"]),                                        # the preparation phase on the device first
+    "timing_odd_counts": (2, "400x216", "2x1", ["--timing"]),                         # 3 x 40 + 7 more subcycles without an upload
+}
+
+
+@pytest.mark.parametrize("name", sorted(MARCHED))
+def test_cgrid_marched_beside_the_frame_across_processes(name):
+    world, workload, shape, extra = MARCHED[name]
+    _run(name, world, workload, shape, extra + ["--expect-marched"], FORCED)
+
+
+def test_cgrid_marched_beside_the_frame_unforced_above_the_threshold():
+    """nothing forced, the product library: 1440 x 1080 over 2 ranks is 777 600 cells per rank, above cg_strip's 300 000-cell default"""
+    _run("unforced_1440x1080", 2, "1440x1080", "1x2", ["--expect-marched"], {}, ndte=12)
+
+
+def test_cgrid_switch_forces_the_fused_schedule():
+    """CICE_EVP_HIP_CGRID_ONE=0: today's three-launch schedule on every rank, same bits (the harness's --expect-marched is not given;
+    its counter must read 0, which tools/mailbox_2proc.py cannot see from here -- the bits are what this case pins)"""
+    _run("switch_off", 2, "400x216", "2x1", [], dict(FORCED, CICE_EVP_HIP_CGRID_ONE="0"))
+
+
+@pytest.mark.parametrize("name,world,workload,shape,extra", [
+    ("avg_strength", 2, "400x216", "2x1", ["--visc", "avg_strength"]),     # five phases across ranks: out of scope, unchanged
+    ("tx1_tripole", 2, "tx1", "1x2", []),                                  # five phases + fold steps: out of scope, unchanged
+])
+def test_schedules_out_of_scope_still_run_and_match(name, world, workload, shape, extra):
+    _run(name, world, workload, shape, extra, FORCED)

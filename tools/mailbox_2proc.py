@@ -48,6 +48,10 @@ def main():
                          "report the C grid's schedule")
     ap.add_argument("--expect-resident", action="store_true",
                     help="fail unless the on-chip resident kernel with remote neighbours ran")
+    ap.add_argument("--expect-marched", action="store_true",
+                    help="with --cgrid: every rank on which the marched kernel has rectangles must have run every subcycle of its last "
+                         "call but the first after an upload as 'zone marched + frame' (cgrid_timings: marched_ranks_subcycles), "
+                         "and some rank must have rectangles")
     ap.add_argument("--forcing", default="",
                     help="with --prep: a forcing layout 'calc_strair,grid_ocn,grid_atm', e.g. 0,C,B "
                          "(cice_evp_hip_set_forcing_layout): the ocean fields and strax / stray at those points")
@@ -184,8 +188,10 @@ def main():
             else:
                 core.cgrid_upload(state, inputs, masks, visc_method=a.visc)
             core.cgrid_subcycle(a.ndte)
+            want_marched = a.ndte - 1            # (the first subcycle after an upload still reads the caller's averages)
             t = None
             if a.timing:
+                want_marched = 7
                 core.cgrid_sync()
                 if exchange:
                     dist.barrier()
@@ -197,6 +203,8 @@ def main():
                 core.cgrid_subcycle(7)
             out = core.cgrid_download()
             out["_halomask"] = hm
+            if a.expect_marched and exchange:
+                out["_marched"] = (core.cgrid_timings(), want_marched, core.describe_path().rpartition("; ")[2])
             if a.fold_ghosts:
                 cgt = core.cgrid_timings()
                 out["_schedule"] = (bool(cgt["fold_exchange"]), int(cgt["fold_ranks"]), core.describe_path().rpartition("; ")[2])
@@ -261,10 +269,19 @@ def main():
                             w3, h3 = w3[keep3], h3[keep3]
                         if not np.array_equal(w3.view(np.int64), h3.view(np.int64)):
                             bad.append((k + (" fold ghost row" if jr > ny else " row NY ghosts"), int((w3 != h3).sum())))
+        zoned = 0
+        if a.expect_marched:
+            cgt, want_marched, sched = got["_marched"]
+            zoned = 1 if cgt["marched_items"] > 0 else 0
+            if zoned and not (cgt["marched_ranks_subcycles"] == want_marched and cgt["frame_cells"] > 0 and "zone marched + frame" in sched):
+                bad.append(("the marched kernel did not run beside the frame", cgt["marched_ranks_subcycles"], want_marched, cgt["marched_items"], sched))
         res = [None] * world
-        dist.all_gather_object(res, (rank, bad, t_us, tim["halo_send_cells"]) + ((got["_schedule"],) if a.fold_ghosts else ()))
+        dist.all_gather_object(res, (rank, bad, t_us, tim["halo_send_cells"]) + ((got["_schedule"],) if a.fold_ghosts else ()) +
+                               (((zoned, got["_marched"][0]["marched_cells"], got["_marched"][0]["frame_cells"]),) if a.expect_marched else ()))
         if rank == 0:
             ok = all(not r[1] for r in res)
+            if a.expect_marched:
+                ok = ok and any(r[-1][0] for r in res)
             print("MAILBOX_2PROC", "OK" if ok else "FAIL", "cgrid", a.workload, f"world={world}", res, flush=True)
             if not ok:
                 sys.exit(1)
