@@ -1079,9 +1079,10 @@ int cice_evp_hip_seam_fin_plan(int32_t *counts2, int32_t *dst, int32_t *a, int32
 int cice_evp_hip_march_info(int32_t *out, int32_t n)
 {
     const State::March &M = S.march;
-    const int32_t v[10] = {M.mode, (int32_t)std::min<long>(M.passes, 0x7fffffffL), M.declined, M.nstrips, M.nseg, M.seglen,
-                           M.last_call ? 1 : 0, M.direct, M.kpass, (int32_t)std::min<long>(M.subcycles, 0x7fffffffL)};
-    for (int k = 0; out && k < n && k < 10; ++k) out[k] = v[k];
+    const int32_t v[12] = {M.mode, (int32_t)std::min<long>(M.passes, 0x7fffffffL), M.declined, M.nstrips, M.nseg, M.seglen,
+                           M.last_call ? 1 : 0, M.direct, M.kpass, (int32_t)std::min<long>(M.subcycles, 0x7fffffffL),
+                           M.mode == 1 ? M.fold_h : 0, M.last_call ? M.call_band_subcycles : 0};
+    for (int k = 0; out && k < n && k < 12; ++k) out[k] = v[k];
     return 0;
 }
 
@@ -1100,12 +1101,15 @@ int cice_evp_hip_describe_path(char *buf, int32_t n)
                            ? (M.direct == 1 ? " (ring between ranks: stores into HIP-IPC-mapped inboxes)"
                                             : (M.direct == 2 ? " (ring between ranks: RCCL send/recv, direct stores on trial)" : " (ring between ranks: RCCL send/recv)"))
                            : "";
-    std::snprintf(buf, (size_t)n, "rank %d of %d: kernel = %s; halo transport = %s%s%s; marching path: %s%s%s%s; blocks %d, cells per exchange %d",
+    char band[96] = "";
+    if (M.mode == 1 && M.fold_h > 0)
+        std::snprintf(band, sizeof band, " (tripole: rows 1 .. %d marched, fold band of %d rows one subcycle per launch)", M.fold_zone, M.fold_h);
+    std::snprintf(buf, (size_t)n, "rank %d of %d: kernel = %s; halo transport = %s%s%s; marching path: %s%s%s%s%s; blocks %d, cells per exchange %d",
                   (int)S.d.rank, (int)std::max(1, (int)S.d.nranks), kernel, transport,
                   (!S.plan.peers.empty() && !S.direct.on && !S.direct.why.empty()) ? " (mailbox off: " : "",
                   (!S.plan.peers.empty() && !S.direct.on && !S.direct.why.empty()) ? (S.direct.why + ")").c_str() : "",
                   M.mode == 1 ? "on" : (M.mode == 0 ? "off" : "undecided"), (M.mode == 0 && !M.why.empty()) ? " -- " : "",
-                  (M.mode == 0 && !M.why.empty()) ? M.why.c_str() : "", ring, (int)S.d.nblocks, (int)(S.msk.on ? S.msk.n_send : S.n_send));
+                  (M.mode == 0 && !M.why.empty()) ? M.why.c_str() : "", ring, band, (int)S.d.nblocks, (int)(S.msk.on ? S.msk.n_send : S.n_send));
     const std::string cg = cgrid_schedule();
     if (!cg.empty()) {
         const size_t used = std::strlen(buf);

@@ -165,6 +165,8 @@ struct EvpMarchGeo {
     int wrapx;
     int gx0, gy0, nxg, nyg, ew_cyclic;   // the rectangle in the global index space (0-based), the global domain
     int ext_w, ext_s, nxo, nyo;          // several ranks: the rank's OWN cells are [ext_w, ext_w+nxo) x [ext_s, ext_s+nyo) of the rectangle
+    int nyblk;                           // rows above ext_s that this rank's blocks hold: nyo, or -- the zone under a fold band, whose
+                                         // blocks go on above it -- every row up to the fold
     const int *blkid;          // [nby][nbx] local block index
     const int2 *blk_org;       // [nblocks] rectangle coordinates of the first interior cell
     const int4 *blk;           // [nblocks] ilo ihi jlo jhi
@@ -179,12 +181,18 @@ struct EvpMarchTab {
     int n;
 };
 void evp_launch_march(const EvpMarch &A, bool strict, int mode, hipStream_t st);
+// Row windows [y0, y1) in rows of the rectangle (y = 0: its first row; halo rows are negative / beyond nyr).  gather fills the
+// rows of the window in the rectangle; scatter and check touch the block cells (ghost and fringe images included) whose row of
+// the rectangle lies in it -- j0, nj: the rows of the block arrays (1-based, the same for every block) the launch is cut down to,
+// a superset of what the window needs.  EvpMarchAllRows: every row there is.
+struct EvpMarchRows { int y0, y1, j0, nj; };
+constexpr EvpMarchRows EvpMarchAllRows{-(1 << 28), 1 << 28, 1, 1 << 28};
 void evp_launch_march_gather(const EvpMarchGeo &G, const EvpMarchTab &T, const uint8_t *mask_blk, uint8_t *mask_rect,
-                             hipStream_t st);
+                             EvpMarchRows W, hipStream_t st);
 void evp_launch_march_check(const EvpMarchGeo &G, const EvpMarchTab &T, const uint8_t *mask_blk, const uint8_t *mask_rect,
-                            int nuv, int nfringe, unsigned *bad, hipStream_t st);
+                            int nuv, int nfringe, unsigned *bad, EvpMarchRows W, hipStream_t st);
 void evp_launch_march_scatter(const EvpMarchGeo &G, const EvpMarchTab &T, const uint8_t *mask_blk, int nuv, int nsig,
-                              hipStream_t st);
+                              EvpMarchRows W, hipStream_t st);
 // Wire format of the ring: the peers' blocks one after the other, inside a block field by field ([f][entry]: consecutive
 // lanes take consecutive entries of ONE field -- the ring cells of a row sit next to each other in a 64-lane block of the
 // packed layout, so a wave gathers runs of 48 bytes and more instead of 64 single doubles 512 bytes apart).

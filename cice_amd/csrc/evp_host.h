@@ -310,6 +310,10 @@ struct State {
         int direct = -1;               // the ring between ranks as stores into HIP-IPC-mapped inboxes: -1 not tried, 0 off, 1 on, 2 being verified
         std::string direct_why;        // ... and why it is off
         int direct_asked = -1;         // value of CICE_EVP_HIP_MARCH_DIRECT the decision was taken on (a change re-opens it)
+        // tripole grid on one rank (march_plan.h: MarchFold): the top fold_h rows and the ghost row beyond the fold stay in the block
+        // layout, advanced one subcycle at a time beside the passes; 0 = no band
+        int fold_h = 0, fold_zone = 0, fold_row0 = 0;
+        int call_band_subcycles = 0;   // subcycles the band advanced in the last call
     } march;
     unsigned upload_seq = 0;                       // bumped whenever the caller hands new state / inputs to the device
     int fault_calls = 0;                           // test hook counter (fault_hook, evp_api.cpp)

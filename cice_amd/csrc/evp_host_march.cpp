@@ -15,10 +15,21 @@
 //   [ndte = 4q + 1: one subcycle with the one-subcycle kernel]  gather -> consistency check (first call after an upload)
 //   -> q passes of four subcycles and one of the remaining two or three (ping-pong between two sets of u, v, 12
 //   stresses) -> scatter.
-// Not eligible (the one-subcycle kernels keep running): tripole / cyclic north-south boundary, blocks that do not tile a
-// rectangle per rank (eliminated land blocks), metric terms handed over as arrays (tripole), a rank too thin next to a
-// closed boundary for its redundant rim (march_plan.cpp), a caller whose ghost values are not images of one global
-// state.  Several ranks: the ring of ext + P cells travels over RCCL send / recv once per ext + P subcycles (section 6).
+// Not eligible (the one-subcycle kernels keep running): cyclic north-south boundary, a tripole grid on several ranks, blocks
+// that do not tile a rectangle per rank (eliminated land blocks), metric terms (dxhy, dyhx) handed over as arrays that are not
+// what the kernel derives from HTE / HTN on the rows it evaluates, a rank too thin next to a closed boundary for its redundant
+// rim (march_plan.cpp), a caller whose ghost values are not images of one global state.  Several ranks: the ring of ext + P
+// cells travels over RCCL send / recv once per ext + P subcycles (section 6).
+//
+// Tripole / tripoleT grid on one rank (march_plan.h: MarchFold): the fold does not go into the marching kernel.  The rectangle is
+// the ZONE, global rows 1 .. NY - H, closed in the south and with a "neighbour" in the north that is this process's own fold BAND:
+// the top H rows and the ghost row beyond the fold stay in the caller's block layout and advance one subcycle at a time with what
+// runs tripole grids anyway -- the tile kernel over a tile list that covers the band and ext + P rows below it, then halo_uv (seam
+// averaging, mirrored ghost row, images between blocks, the cyclic wrap).  Serial on one stream: a pass of K subcycles, then K band
+// subcycles.  Every ext + P subcycles the ring between the two travels on the device (march_scatter / march_gather over row
+// windows): the zone's rows under the band into the block layout, the band's rows above the zone into the rectangle; in between
+// each side loses one row of validity per subcycle and never reads a lost row for a cell it owns.  The call ends with the
+// scatter of the zone's rows into the ping-pong buffer the band's last subcycle wrote.
 // =====================================================================
 #include "evp_host.h"
 #include "march_plan.h"
@@ -43,6 +54,7 @@ struct MarchBuf {
     double *sendbuf = nullptr, *recvbuf = nullptr;
     // the early launch of an exchange pass: work items that cover every cell other ranks receive from this one
     int4 *band_items = nullptr, *rest_items = nullptr;      // ... and every other (strip, row) of the rectangle
+    std::map<int, std::pair<int *, int>> fold_tiles;        // fold band: tile list of the one-subcycle kernel, by tile variant
     int nband = 0, nrest = 0;
     hipEvent_t ev_in = nullptr, ev_main = nullptr, ev_done = nullptr;
     // the same ring as stores into the peers' HIP-IPC-mapped inboxes (march_direct_setup)
@@ -53,6 +65,7 @@ struct MarchBuf {
     EvpRingCuts cut_send{}, cut_recv{};      // where each neighbour's block begins in the send / receive list
 };
 MarchPlan PL;
+MarchFold FD;                    // the fold band of a tripole grid (H == 0: none)
 // slots of the constants block (evp_march.hip: C_*), of the optional block (O_*)
 enum { C_DXT = 0, C_DYT, C_STRENGTH, C_HTE, C_HTN, C_VRELFAC, C_UOCN, C_VOCN, C_FORCEX, C_FORCEY, C_UMASSDTI, C_FM, C_UAREAR };
 enum { O_WATERX = 0, O_WATERY, O_TBU, O_UINIT, O_VINIT };
@@ -73,6 +86,9 @@ void march_free()
     F(B.send_pos); F(B.recv_pos1); F(B.recv_pos2); F(B.send_midx); F(B.recv_midx); F(B.sendbuf); F(B.recvbuf);
     F(B.band_items); F(B.rest_items);
     B.nband = B.nrest = 0;
+    for (auto &kv : B.fold_tiles) F(kv.second.first);
+    B.fold_tiles.clear();
+    FD = MarchFold();
     for (void *m : B.dx_mapped) (void)hipIpcCloseMemHandle(m);
     B.dx_mapped.clear();
     F(B.dx_area);
@@ -83,11 +99,65 @@ void march_free()
     S.march = State::March{};
 }
 
+// Are the metric terms the one-subcycle kernels read from arrays (cxp, cyp, cxm, cym, dxhy, dyhx, deltaminEVP * tarea) what the
+// marching kernel derives from HTE, HTN, dxT, dyT (evp_cell.inc: metrics) on every T-cell of the global rows below `nrows`?  On a
+// tripole grid dxhy / dyhx carry mirrored values on the ghost row beyond the fold (evp_host_common.cpp: derive_metrics,
+// cice_evp_hip_set_metrics), and on a tripoleT grid tarea is not dxT * dyT on the top physical row -- rows the zone never
+// evaluates.  Once, on the host; the flags EVP_F_METRICS / EVP_F_DXHY_ARRAY speak for the whole domain and are not asked.
+static bool metrics_hold(int nrows)
+{
+    const size_t bytes = S.n * sizeof(double);
+    auto down = [&](const double *dev, std::vector<double> &h) -> bool {
+        h.resize(S.n);
+        if (hipMemcpy(h.data(), dev, bytes, hipMemcpyDeviceToHost) == hipSuccess) return true;
+        (void)hipGetLastError();
+        return false;
+    };
+    std::vector<double> hte, htn, dxT, dyT, arr;
+    if (!down(S.hte, hte) || !down(S.htn, htn) || !down(S.stat[0], dxT) || !down(S.stat[1], dyT)) return false;
+    const int nx = S.d.nx_block;
+    const double p5 = 0.5, c1p5 = 1.5, dmin = S.prm.deltaminEVP;
+    for (int k = 2; k <= 8; ++k) {           // stat slots: dxhy dyhx cxp cyp cxm cym DminTarea
+        if (!down(S.stat[k], arr)) return false;
+        for (int b = 0; b < S.d.nblocks; ++b)
+            for (int j = S.jlo[b]; j <= S.jhi[b] + 1; ++j) {
+                if (S.jglob0[b] - 1 + (j - S.jlo[b]) >= nrows) break;
+                for (int i = S.ilo[b]; i <= S.ihi[b] + 1; ++i) {
+                    const size_t c = (size_t)b * S.plane + (size_t)(j - 1) * nx + (i - 1);
+                    double e;
+                    switch (k) {
+                    case 2: e = p5 * (hte[c] - hte[c - 1]); break;
+                    case 3: e = p5 * (htn[c] - htn[c - nx]); break;
+                    case 4: e = (c1p5 * htn[c] - p5 * htn[c - nx]); break;
+                    case 5: e = (c1p5 * hte[c] - p5 * hte[c - 1]); break;
+                    case 6: e = -(c1p5 * htn[c - nx] - p5 * htn[c]); break;
+                    case 7: e = -(c1p5 * hte[c - 1] - p5 * hte[c]); break;
+                    default: { const double tarea = dxT[c] * dyT[c]; e = dmin * tarea; }
+                    }
+                    if (std::memcmp(&e, &arr[c], 8) != 0) return false;
+                }
+            }
+    }
+    return true;
+}
+
 // Can this rank's sub-domain be held as one rectangle?  Fills S.march.G (host fields) when it can.
 static bool march_geometry(std::string &why)
 {
     State::March &M = S.march;
     const cice_evp_hip_dims &d = S.d;
+    // tripole grid: the rectangle is the zone under the fold band, whose height follows from the rim
+    const bool tripole = d.ns_boundary_type == CICE_EVP_BND_TRIPOLE || d.ns_boundary_type == CICE_EVP_BND_TRIPOLET;
+    auto plan = [&](int e, int own_max, bool wrap_inside) -> bool {
+        FD = MarchFold();
+        if (tripole && !build_march_fold(d, e, S.tyb % 100, FD)) {
+            PL = MarchPlan();
+            PL.error = FD.error;
+            FD = MarchFold();
+            return false;
+        }
+        return build_march_plan(d, own_max, wrap_inside, e, PL, FD.H);
+    };
     // the rectangles of all ranks, this rank's strips and the exchange lists: the same verdict on every rank
     const int own_max = env_test("CICE_EVP_HIP_MARCH_OWN") ? std::atoi(env_test("CICE_EVP_HIP_MARCH_OWN")) : EVP_MARCH_OWN;
     const bool wrap_inside = !(env_test("CICE_EVP_HIP_MARCH_SELFX") && std::atoi(env_test("CICE_EVP_HIP_MARCH_SELFX")));
@@ -97,7 +167,7 @@ static bool march_geometry(std::string &why)
     // against 47.0 without any exchange.)
     int ext = env_test("CICE_EVP_HIP_MARCH_EXT") ? std::max(0, std::atoi(env_test("CICE_EVP_HIP_MARCH_EXT")) & ~1) : -1;
     if (ext >= 0) {
-        if (!build_march_plan(d, own_max, wrap_inside, ext, PL)) { why = PL.error; return false; }
+        if (!plan(ext, own_max, wrap_inside)) { why = PL.error; return false; }
     } else {
         // Default (round 6): the widest rim of 12 / 8 / 4 cells that costs no rank a strip more than a rim of 4 does and at most 2 %
         // more rows -- the exchange then comes every 16th / 12th / 8th subcycle for the same bytes per subcycle.  (The 8 x 1 pieces of
@@ -107,7 +177,7 @@ static bool march_geometry(std::string &why)
         bool ok = false;
         std::string first_error;
         for (int e : {12, 8, 4, 0}) {
-            if (!build_march_plan(d, own_max, wrap_inside, e, PL)) {
+            if (!plan(e, own_max, wrap_inside)) {
                 if (first_error.empty()) first_error = PL.error;
                 continue;
             }
@@ -150,7 +220,13 @@ static bool march_geometry(std::string &why)
     if (env_test("CICE_EVP_HIP_MARCH_K")) M.kpass = std::min(EVP_MARCH_KMAX, std::max(2, std::atoi(env_test("CICE_EVP_HIP_MARCH_K"))));
     if (PL.peers.size() > (size_t)EVP_MARCH_DIRECT_MAXPEER) { why = "more ring neighbours than the exchange lists hold"; return false; }
     if (!PL.peers.empty() && !S.have_comm && !S.test_xchg) { why = "cells of other ranks needed but no RCCL communicator (cice_evp_hip_comm_init)"; return false; }
-    if (!(S.flags & EVP_F_METRICS) || (S.flags & EVP_F_DXHY_ARRAY)) { why = "metric terms come from arrays"; return false; }
+    // The kernel derives every metric term from HTE, HTN, dxT, dyT.  A closed grid: tarea == dxT * dyT was verified on every cell
+    // at init (EVP_F_METRICS) and nothing else stands in the arrays.  A tripole grid: the arrays differ from that on the ghost row
+    // beyond the fold (and, tripoleT, on the top physical row), so the test is the thing itself -- the terms hold on every row
+    // the zone evaluates: its own, the redundant rim and the ring.
+    if (tripole) {
+        if (!metrics_hold(FD.to_rect[1])) { why = "the metric arrays are not what HTE, HTN, dxT, dyT give on the rows the marching kernel evaluates"; return false; }
+    } else if (!(S.flags & EVP_F_METRICS) || (S.flags & EVP_F_DXHY_ARRAY)) { why = "metric terms come from arrays"; return false; }
     if (d.nblocks < 1) { why = "no blocks"; return false; }
     // blocks must tile [gx0, gx0+nxr) x [gy0, gy0+nyr) with full blocks of bsx x bsy (the last column / row may be smaller)
     int gx0 = 1 << 30, gy0 = 1 << 30, gx1 = 0, gy1 = 0;
@@ -179,12 +255,14 @@ static bool march_geometry(std::string &why)
         M.blkid_h[(size_t)bj * nbx + bi] = b;
         M.org_h[b] = int2{ox, oy};
     }
-    if (nxr != PL.owned.nxr || nyr != PL.owned.nyr || gx0 - 1 != PL.owned.gx0 || gy0 - 1 != PL.owned.gy0) { why = "local blocks disagree with the global block table"; return false; }
+    if (nxr != PL.owned.nxr || nyr - FD.H != PL.owned.nyr || gx0 - 1 != PL.owned.gx0 || gy0 - 1 != PL.owned.gy0) { why = "local blocks disagree with the global block table"; return false; }
     for (auto &o : M.org_h) { o.x += PL.ext_w; o.y += PL.ext_s; }        // block origins in the rectangle the rank HOLDS
     const bool wrapx = PL.wrapx;
     EvpMarchGeo &G = M.G;
     G.nxr = PL.me.nxr; G.nyr = PL.me.nyr;                                  // held: own cells + the redundant rim
-    G.ext_w = PL.ext_w; G.ext_s = PL.ext_s; G.nxo = nxr; G.nyo = nyr;
+    G.ext_w = PL.ext_w; G.ext_s = PL.ext_s; G.nxo = nxr; G.nyo = nyr - FD.H;
+    G.nyblk = nyr;                   // (a fold band: the blocks go on above the zone, and the ring above it is read from them)
+    M.fold_h = FD.H; M.fold_zone = FD.zone; M.fold_row0 = FD.list_row0;
     G.nxb = d.nx_block; G.nyb = d.ny_block; G.plane = (int)S.plane; G.nblocks = d.nblocks;
     G.bsx = bsx; G.bsy = bsy; G.nbx = nbx; G.nby = nby;
     G.ilo = d.nghost + 1;
@@ -631,6 +709,70 @@ struct TabBuilder {
 };
 }  // namespace
 
+// Rows [y0, y1) of the rectangle as a window of the gather / scatter / check kernels: with the rows of the block arrays that hold
+// an image of one of them (a cell of row j of block b lies on row blk_org[b].y + j - ilo).
+static EvpMarchRows rows_window(int y0, int y1)
+{
+    const State::March &M = S.march;
+    int j0 = 1 << 28, j1 = -(1 << 28);
+    for (const int2 &o : M.org_h) {
+        j0 = std::min(j0, std::max(y0, -(1 << 20)) - o.y + M.G.ilo);
+        j1 = std::max(j1, std::min(y1, 1 << 20) - o.y + M.G.ilo);
+    }
+    j0 = std::max(j0, 1);
+    return EvpMarchRows{y0, y1, j0, std::max(j1 - j0, 0)};
+}
+// the rows the consistency checks look at: all of them, or -- under a fold band -- those the rectangle holds
+static EvpMarchRows check_window()
+{
+    const State::March &M = S.march;
+    return M.fold_h > 0 ? rows_window(-(1 << 28), M.G.nyr + EVP_MARCH_PAD) : EvpMarchAllRows;
+}
+
+// The tile list of the fold band for the tile variant in use: every tile of every block that reaches row FD.list_row0 or above.
+static int fold_tile_list(int variant, int *&list, int &count)
+{
+    auto it = B.fold_tiles.find(variant);
+    if (it == B.fold_tiles.end()) {
+        int tyb, gx, gy;
+        evp_tile_geometry(S.max_ni, S.max_nj, variant, &tyb, &gx, &gy);
+        MarchFold Fv = FD;
+        Fv.trow = tyb - 1;
+        std::vector<int> t;
+        for (int b = 0; b < S.d.nblocks; ++b) {
+            int by0, by1;
+            march_fold_tile_rows(Fv, S.jglob0[b] - 1, S.jhi[b] - S.jlo[b] + 1, by0, by1);
+            const int nbx = std::min(gx, (S.ihi[b] - S.ilo[b] + 1 + 62) / 63);
+            for (int by = by0; by < std::min(by1, gy); ++by)
+                for (int bx = 0; bx < nbx; ++bx) t.push_back((b * gy + by) * gx + bx);      // row-major tile id
+        }
+        int *dl = nullptr;
+        HIPC(hipMalloc((void **)&dl, std::max<size_t>(t.size(), 1) * sizeof(int)));
+        if (!t.empty()) HIPC(hipMemcpy(dl, t.data(), t.size() * sizeof(int), hipMemcpyHostToDevice));
+        it = B.fold_tiles.emplace(variant, std::make_pair(dl, (int)t.size())).first;
+    }
+    list = it->second.first;
+    count = it->second.second;
+    return 0;
+}
+
+// n subcycles of the fold band in the block layout, as enqueue_loop runs them on a tripole grid but over the band's tiles only
+static int fold_band_subcycles(int n, int &bcur, bool ends_call)
+{
+    const int variant = S.tyb % 100;         // (the list holds row-major tile ids)
+    int *list = nullptr, count = 0;
+    if (int rc = fold_tile_list(variant, list, count)) return rc;
+    for (int k = 0; k < n; ++k) {
+        EvpArgs A;
+        fill_args(A, bcur, ends_call && k == n - 1);       // strintx/y, taubx/y of the band: from its own last subcycle
+        A.tile_list = list; A.tile_count = count;
+        evp_launch_subcycle(A, S.max_ni, S.max_nj, S.d.nblocks, variant, S.prm.strict != 0, cap_mode(), S.stream);
+        if (int rc = halo_uv(bcur ^ 1, true)) return rc;
+        bcur ^= 1;
+    }
+    return 0;
+}
+
 // static fields into the constants block, once; are their ghost values images of one global field?
 static int march_statics()
 {
@@ -639,12 +781,12 @@ static int march_statics()
     double *src[5] = {S.stat[0], S.stat[1], S.hte, S.htn, S.stat[9]};
     const int slot[5] = {C_DXT, C_DYT, C_HTE, C_HTN, C_UAREAR};
     for (int k = 0; k < 5; ++k) G.add(src[k], B.cst, nullptr, EVP_MARCH_C_NF, slot[k]);
-    evp_launch_march_gather(M.G, G.T, nullptr, nullptr, S.stream);
+    evp_launch_march_gather(M.G, G.T, nullptr, nullptr, EvpMarchAllRows, S.stream);
     if (march_exchange(B.cst, nullptr, EVP_MARCH_C_NF)) return -1;      // (the per-call slots travel too: overwritten at every call)
     TabBuilder C;              // dxT dyT (fringe) | HTE HTN (fringe + column ilo-1 / row jlo-1)
     for (int k = 0; k < 4; ++k) C.add(src[k], B.cst, nullptr, EVP_MARCH_C_NF, slot[k]);
     HIPC(hipMemsetAsync(B.bad, 0, sizeof(unsigned), S.stream));
-    evp_launch_march_check(M.G, C.T, nullptr, nullptr, 0, 2, B.bad, S.stream);
+    evp_launch_march_check(M.G, C.T, nullptr, nullptr, 0, 2, B.bad, check_window(), S.stream);
     unsigned bad = 0;
     if (agree_max(bad)) return -1;
     M.stat_ok = bad == 0;
@@ -762,8 +904,18 @@ int march_run(int ndte)
         sizes.assign((size_t)q, kp);
         if (rem) sizes.push_back(rem);
     }
-    M.call_passes = 0; M.call_subcycles = 0;
+    M.call_passes = 0; M.call_subcycles = 0; M.call_band_subcycles = 0;
     if (left == 0) { S.cur = cur; return 0; }
+    // Fold band (tripole grid): its subcycles flip the block layout's ping-pong buffers, one flip each; bcur names the buffer
+    // that holds the band's current state.  The zone's rows reach it at the ring exchanges and in the final scatter.
+    const bool fold = M.fold_h > 0;
+    int bcur = cur;
+    auto state_tab = [&](double *pk) {
+        TabBuilder T;
+        T.add(S.u[bcur], pk, nullptr, EVP_MARCH_S_NF, 0); T.add(S.v[bcur], pk, nullptr, EVP_MARCH_S_NF, 1);
+        for (int k = 0; k < 12; ++k) T.add(S.sig[bcur][k], pk, nullptr, EVP_MARCH_S_NF, 2 + k);
+        return T;
+    };
     const unsigned fl = S.flags & S.flags_allowed;
     // ---- gather the state and the per-call inputs ----
     {
@@ -783,7 +935,7 @@ int march_run(int ndte)
         if (S.prm.revp != 0.0) {
             G.add(S.in[F_UVEL_INIT], B.opt, nullptr, EVP_MARCH_O_NF, O_UINIT); G.add(S.in[F_VVEL_INIT], B.opt, nullptr, EVP_MARCH_O_NF, O_VINIT);
         }
-        evp_launch_march_gather(M.G, G.T, S.mask, B.mask, S.stream);
+        evp_launch_march_gather(M.G, G.T, S.mask, B.mask, EvpMarchAllRows, S.stream);
         // the two-cell ring of everything: other ranks' cells (once per call for the constants and the mask)
         if (march_exchange(B.cst, nullptr, EVP_MARCH_C_NF)) return -1;
         const bool need_opt = !(fl & EVP_F_WATER_IS_OCN) || !(fl & EVP_F_TBU_ZERO) || S.prm.revp != 0.0;
@@ -799,7 +951,7 @@ int march_run(int ndte)
         for (int k = 0; k < 12; ++k) C.add(S.sig[cur][k], B.st[0], nullptr, EVP_MARCH_S_NF, 2 + k);
         C.add(S.in[F_STRENGTH], B.cst, nullptr, EVP_MARCH_C_NF, C_STRENGTH);
         HIPC(hipMemsetAsync(B.bad, 0, sizeof(unsigned), S.stream));
-        evp_launch_march_check(M.G, C.T, S.mask, B.mask, 2, 13, B.bad, S.stream);
+        evp_launch_march_check(M.G, C.T, S.mask, B.mask, 2, 13, B.bad, check_window(), S.stream);
         unsigned bad = 0;
         if (agree_max(bad)) return -1;
         if (bad) return fallback("ghost cells of the uploaded state are not images of one global state (here or on another rank)");
@@ -833,7 +985,9 @@ int march_run(int ndte)
         // the ring afterwards is a state older)
         valid = std::min(valid - sizes[(size_t)k], M.ring_valid - EVP_MARCH_PAD);
         const bool exch = !PL.peers.empty() && (k == npass - 1 || valid < sizes[(size_t)k + 1]);
-        if (exch) valid = M.ring_valid;
+        // (the fold band's ring: at the same points, but not after the last pass -- the final scatter moves the zone's rows then)
+        const bool fexch = fold && k < npass - 1 && valid < sizes[(size_t)k + 1];
+        if (exch || fexch) valid = M.ring_valid;
         EvpMarch A;
         march_args(A, rc, k == npass - 1);
         A.kpass = sizes[(size_t)k];
@@ -859,6 +1013,18 @@ int march_run(int ndte)
         } else if (exch) {
             if (march_exchange(B.st[rc], nullptr, EVP_MARCH_S_NF)) return -1;
         }
+        if (fold) {
+            // the band catches up with the pass; then, when either side has used up its ring, the two trade rows: the zone's
+            // ext + P rows under the band into the block layout (every image of a cell), the band's ext + P rows above the zone
+            // into the rectangle (every lane that holds the column)
+            if (int e = fold_band_subcycles(sizes[(size_t)k], bcur, k == npass - 1)) return e;
+            M.call_band_subcycles += sizes[(size_t)k];
+            if (fexch) {
+                const TabBuilder T = state_tab(B.st[rc]);
+                evp_launch_march_scatter(M.G, T.T, S.mask, 2, 12, rows_window(FD.to_block[0], FD.to_block[1]), S.stream);
+                evp_launch_march_gather(M.G, T.T, nullptr, nullptr, rows_window(FD.to_rect[0], FD.to_rect[1]), S.stream);
+            }
+        }
     }
     HIPC(hipGetLastError());
     M.passes += npass;
@@ -866,15 +1032,15 @@ int march_run(int ndte)
     M.call_passes = npass; M.call_subcycles = left;
     // ---- back to the block layout ----
     {
-        TabBuilder T;
-        T.add(S.u[cur], B.st[rc], nullptr, EVP_MARCH_S_NF, 0); T.add(S.v[cur], B.st[rc], nullptr, EVP_MARCH_S_NF, 1);
-        for (int k = 0; k < 12; ++k) T.add(S.sig[cur][k], B.st[rc], nullptr, EVP_MARCH_S_NF, 2 + k);
+        // (a fold band: into the buffer its last subcycle wrote, the zone's rows only -- the band's own are current there)
+        TabBuilder T = state_tab(B.st[rc]);
         T.add(S.in[F_STRINTX], B.diag, nullptr, EVP_MARCH_D_NF, 0); T.add(S.in[F_STRINTY], B.diag, nullptr, EVP_MARCH_D_NF, 1);
         T.add(S.in[F_TAUBX], B.diag, nullptr, EVP_MARCH_D_NF, 2); T.add(S.in[F_TAUBY], B.diag, nullptr, EVP_MARCH_D_NF, 3);
-        evp_launch_march_scatter(M.G, T.T, S.mask, 2, 12, S.stream);
+        evp_launch_march_scatter(M.G, T.T, S.mask, 2, 12, fold ? rows_window(-(1 << 28), FD.zone) : EvpMarchAllRows, S.stream);
     }
     HIPC(hipGetLastError());
-    S.cur = cur;            // the passes leave the block layout's ping-pong buffer where it was: the scatter wrote the new state there
+    S.cur = bcur;           // without a band the passes leave the block layout's ping-pong buffer where it was: the scatter wrote the
+                            // new state there; the band's subcycles flipped it once each
     return 0;
 }
 
@@ -916,6 +1082,27 @@ extern "C" int cice_evp_hip_march_plan(const cice_evp_hip_dims *dims, int32_t ow
             if (recv_pos2) recv_pos2[ro + k] = p.recv_pos2[k];
         }
         so += p.send_pos.size(); ro += p.recv_pos1.size();
+    }
+    return 0;
+}
+
+// Host-only: how a tripole grid on one rank is shared between the marched zone and the fold band (march_plan.h: MarchFold).
+extern "C" int cice_evp_hip_march_fold_plan(const cice_evp_hip_dims *dims, int32_t ext, int32_t tyb, int32_t *out10, int32_t *tile_rows)
+{
+    using namespace evp_host;
+    if (!dims) return fail(-1, "null dims");
+    MarchFold F;
+    if (!build_march_fold(*dims, ext, tyb, F)) return fail(-3, "march fold plan: %s", F.error.c_str());
+    MarchPlan P;
+    if (!build_march_plan(*dims, EVP_MARCH_OWN, true, ext, P, F.H)) return fail(-3, "march fold plan: %s", P.error.c_str());
+    if (out10) {
+        const int32_t v[10] = {F.zone, F.H, F.ext, F.trow, F.list_row0, F.to_block[0], F.to_block[1], F.to_rect[0], F.to_rect[1], P.me.nyr};
+        for (int k = 0; k < 10; ++k) out10[k] = v[k];
+    }
+    for (int b = 0; tile_rows && b < dims->nblocks; ++b) {
+        int by0, by1;
+        march_fold_tile_rows(F, dims->jglob0[b] - 1, dims->jhi[b] - dims->jlo[b] + 1, by0, by1);
+        tile_rows[2 * b] = by0; tile_rows[2 * b + 1] = by1;
     }
     return 0;
 }

@@ -380,6 +380,7 @@ struct CellMap {
     int em;               // element of the row-major byte mask
     bool ok;              // the position exists
     bool live;            // it is a real cell of the rank's rectangle (interior, or the cell a wrap ghost images)
+    int ys;               // its row of the rectangle
 };
 
 // block cell (b; i, j 1-based) -> packed position
@@ -389,6 +390,7 @@ __device__ __forceinline__ CellMap block_to_packed(const EvpMarchGeo &G, int b, 
     int xs = o.x + (i - G.ilo);
     const int ys = o.y + (j - G.ilo);
     CellMap c{};
+    c.ys = ys;
     if (xs < -EVP_MARCH_PAD || xs >= G.nxr + EVP_MARCH_PAD || ys < -EVP_MARCH_PAD || ys >= G.nyr + EVP_MARCH_PAD) return c;
     if (G.wrapx) {                               // a ghost cell across the cyclic seam takes the cell it images
         if (xs < 0) xs += G.nxr;
@@ -412,8 +414,8 @@ __device__ __forceinline__ int rect_to_block(const EvpMarchGeo &G, int x, int y,
 {
     int xs = x - G.ext_w, ys = y - G.ext_s;          // relative to the rank's own cells
     if (G.wrapx) { if (xs < 0) xs += G.nxo; else if (xs >= G.nxo) xs -= G.nxo; }
-    is_cell = xs >= 0 && xs < G.nxo && ys >= 0 && ys < G.nyo;
-    if (xs < -1 || xs > G.nxo || ys < -1 || ys > G.nyo) return -1;
+    is_cell = xs >= 0 && xs < G.nxo && ys >= 0 && ys < G.nyblk;
+    if (xs < -1 || xs > G.nxo || ys < -1 || ys > G.nyblk) return -1;
     const int bi = min(max(xs, 0) / G.bsx, G.nbx - 1), bj = min(max(ys, 0) / G.bsy, G.nby - 1);
     const int b = G.blkid[bj * G.nbx + bi];
     if (b < 0) return -1;
@@ -422,11 +424,12 @@ __device__ __forceinline__ int rect_to_block(const EvpMarchGeo &G, int x, int y,
     return b * G.plane + (j - 1) * G.nxb + (i - 1);
 }
 
-// every lane of every block of every row (all duplicates included) <- the block-layout arrays
+// every lane of every block of the rows from row0 (all duplicates included) <- the block-layout arrays.  The whole rectangle at
+// the start of a call; the ring exchange of a folded grid (evp_host_march.cpp) refills the rows above the zone's own this way.
 __global__ __launch_bounds__(256) void march_gather(EvpMarchGeo G, EvpMarchTab T, const uint8_t *__restrict__ mask_blk,
-                                                    uint8_t *__restrict__ mask_rect)
+                                                    uint8_t *__restrict__ mask_rect, int row0)
 {
-    const int lane = threadIdx.x & 63, s = blockIdx.x * 4 + (threadIdx.x >> 6), row = blockIdx.y;
+    const int lane = threadIdx.x & 63, s = blockIdx.x * 4 + (threadIdx.x >> 6), row = row0 + (int)blockIdx.y;
     if (s >= G.nstrips) return;
     const int x = s * G.own - PADW + lane, y = row - EVP_MARCH_PAD;
     bool is_cell;
@@ -455,11 +458,11 @@ __global__ __launch_bounds__(256) void march_gather(EvpMarchGeo G, EvpMarchTab T
 // one-subcycle kernels, which keep per-block ghost storage.
 __global__ __launch_bounds__(256) void march_check(EvpMarchGeo G, EvpMarchTab T, const uint8_t *__restrict__ mask_blk,
                                                    const uint8_t *__restrict__ mask_rect, int nuv, int nfringe,
-                                                   unsigned *__restrict__ bad)
+                                                   unsigned *__restrict__ bad, EvpMarchRows W)
 {
     // T: [0, nuv) compared on the whole ghost ring, [nuv, nuv + nfringe) on the fringe T-cells, the rest (HTE, HTN) on
     // the fringe and on column ilo-1 / row jlo-1
-    const int i = blockIdx.x * 256 + threadIdx.x + 1, j = blockIdx.y + 1, b = blockIdx.z;
+    const int i = blockIdx.x * 256 + threadIdx.x + 1, j = blockIdx.y + W.j0, b = blockIdx.z;
     const int4 r = G.blk[b];
     if (i < r.x - 1 || i > r.y + 1 || j < r.z - 1 || j > r.w + 1) return;
     const bool ghost = i < r.x || i > r.y || j < r.z || j > r.w;
@@ -467,6 +470,7 @@ __global__ __launch_bounds__(256) void march_check(EvpMarchGeo G, EvpMarchTab T,
     const bool fringe = (i == r.y + 1 || j == r.w + 1) && i >= r.x && j >= r.z;
     const int s = b * G.plane + (j - 1) * G.nxb + (i - 1);
     const CellMap c = block_to_packed(G, b, i, j);
+    if (c.ys < W.y0 || c.ys >= W.y1) return;
     unsigned nbad = 0;
     auto differs = [](double p, double q) { return __double_as_longlong(p) != __double_as_longlong(q); };
     auto pk = [&](int f) { return T.pk[f][((size_t)c.blk * T.nf[f] + T.slot[f]) * 64 + c.lane]; };
@@ -489,15 +493,17 @@ __global__ __launch_bounds__(256) void march_check(EvpMarchGeo G, EvpMarchTab T,
 
 // packed -> block layout after the loop.  Velocities: every cell with a live source (interior, ghost images of cells
 // of this rank: what the reference's halo update leaves, ice_dyn_evp.F90:908-910); stresses: the T-cells the reference
-// updates (ilo..ihi+1 x jlo..jhi+1 where iceTmask); strintx/y, taubx/y: interior ice U-cells.
+// updates (ilo..ihi+1 x jlo..jhi+1 where iceTmask); strintx/y, taubx/y: interior ice U-cells.  Every image of a cell whose row
+// lies in the window W: the whole rectangle after the loop; on a folded grid the zone's rows then, and at a ring exchange the
+// rows under the band.
 __global__ __launch_bounds__(256) void march_scatter(EvpMarchGeo G, EvpMarchTab T, const uint8_t *__restrict__ mask_blk,
-                                                     int nuv, int nsig)
+                                                     int nuv, int nsig, EvpMarchRows W)
 {
-    const int i = blockIdx.x * 256 + threadIdx.x + 1, j = blockIdx.y + 1, b = blockIdx.z;
+    const int i = blockIdx.x * 256 + threadIdx.x + 1, j = blockIdx.y + W.j0, b = blockIdx.z;
     const int4 r = G.blk[b];
     if (i < r.x - 1 || i > r.y + 1 || j < r.z - 1 || j > r.w + 1) return;
     const CellMap c = block_to_packed(G, b, i, j);
-    if (!c.live) return;
+    if (!c.live || c.ys < W.y0 || c.ys >= W.y1) return;
     const int s = b * G.plane + (j - 1) * G.nxb + (i - 1);
     const unsigned m = mask_blk[s];
     auto pk = [&](int f) { return T.pk[f][((size_t)c.blk * T.nf[f] + T.slot[f]) * 64 + c.lane]; };
@@ -674,24 +680,37 @@ void evp_launch_march(const EvpMarch &A, bool strict, int mode, hipStream_t st)
 }
 
 void evp_launch_march_gather(const EvpMarchGeo &G, const EvpMarchTab &T, const uint8_t *mask_blk, uint8_t *mask_rect,
-                             hipStream_t st)
+                             EvpMarchRows W, hipStream_t st)
 {
-    hipLaunchKernelGGL(march_gather, dim3((unsigned)((G.nstrips + 3) / 4), (unsigned)G.rows), dim3(256), 0, st, G, T,
-                       mask_blk, mask_rect);
+    // storage rows: row = y + P, clipped to the rows the buffers hold
+    const int r0 = std::max(W.y0 + EVP_MARCH_PAD, 0), r1 = std::min(W.y1 + EVP_MARCH_PAD, G.rows);
+    if (r1 <= r0) return;
+    hipLaunchKernelGGL(march_gather, dim3((unsigned)((G.nstrips + 3) / 4), (unsigned)(r1 - r0)), dim3(256), 0, st, G, T,
+                       mask_blk, mask_rect, r0);
+}
+
+// the rows of the block arrays a window is cut down to, clipped to the arrays
+static bool block_rows(const EvpMarchGeo &G, EvpMarchRows &W)
+{
+    const int j0 = std::max(W.j0, 1), j1 = std::min(W.j0 + std::min(W.nj, 1 << 28), G.nyb + 1);
+    W.j0 = j0; W.nj = j1 - j0;
+    return W.nj > 0;
 }
 
 void evp_launch_march_check(const EvpMarchGeo &G, const EvpMarchTab &T, const uint8_t *mask_blk, const uint8_t *mask_rect,
-                            int nuv, int nfringe, unsigned *bad, hipStream_t st)
+                            int nuv, int nfringe, unsigned *bad, EvpMarchRows W, hipStream_t st)
 {
-    hipLaunchKernelGGL(march_check, dim3((unsigned)((G.nxb + 255) / 256), (unsigned)G.nyb, (unsigned)G.nblocks), dim3(256),
-                       0, st, G, T, mask_blk, mask_rect, nuv, nfringe, bad);
+    if (!block_rows(G, W)) return;
+    hipLaunchKernelGGL(march_check, dim3((unsigned)((G.nxb + 255) / 256), (unsigned)W.nj, (unsigned)G.nblocks), dim3(256),
+                       0, st, G, T, mask_blk, mask_rect, nuv, nfringe, bad, W);
 }
 
 void evp_launch_march_scatter(const EvpMarchGeo &G, const EvpMarchTab &T, const uint8_t *mask_blk, int nuv, int nsig,
-                              hipStream_t st)
+                              EvpMarchRows W, hipStream_t st)
 {
-    hipLaunchKernelGGL(march_scatter, dim3((unsigned)((G.nxb + 255) / 256), (unsigned)G.nyb, (unsigned)G.nblocks),
-                       dim3(256), 0, st, G, T, mask_blk, nuv, nsig);
+    if (!block_rows(G, W)) return;
+    hipLaunchKernelGGL(march_scatter, dim3((unsigned)((G.nxb + 255) / 256), (unsigned)W.nj, (unsigned)G.nblocks),
+                       dim3(256), 0, st, G, T, mask_blk, nuv, nsig, W);
 }
 
 void evp_launch_march_pack(const double *buf, int nf, const int *pos, int n, const EvpRingCuts &C, double *out, hipStream_t st)

@@ -42,17 +42,63 @@ bool dup_table(int nxr, int own, bool wrapx, std::vector<int32_t> &dup)
 
 }  // namespace
 
-bool build_march_plan(const cice_evp_hip_dims &d, int own_max, bool wrap_inside, int ext, MarchPlan &P)
+bool build_march_fold(const cice_evp_hip_dims &d, int ext, int tyb, MarchFold &F)
+{
+    F = MarchFold();
+    const int NY = d.ny_global;
+    if (d.ns_boundary_type != CICE_EVP_BND_TRIPOLE && d.ns_boundary_type != CICE_EVP_BND_TRIPOLET) { F.error = "no tripole fold"; return false; }
+    if (d.nranks > 1) { F.error = "tripole grid on several ranks: the fold band of the marching path is built for one rank"; return false; }
+    if (ext < 0 || (ext & 1)) { F.error = "ext must be even and >= 0"; return false; }
+    if (tyb < 2 || tyb > 9) tyb = 5;
+    F.ext = ext;
+    F.trow = tyb - 1;
+    const int ring = ext + PW;
+    // tripoleT: the top physical row holds images (its T-cell areas are not dxT * dyT in CICE's arrays, which the marching kernel
+    // would use): the zone's ring stays below it, the band is one row taller
+    const int top = d.ns_boundary_type == CICE_EVP_BND_TRIPOLET ? 1 : 0;
+    int row0 = NY - top - 2 * ring;                 // first row of the list with the smallest band, H = ext + P (+ 1)
+    if (row0 < 0) { F.error = "grid too short for a marched zone under the fold band"; return false; }
+    // down to a tile row of the block that holds it (the highest such row if blocks with different origins hold it)
+    int snapped = -1;
+    for (int b = 0; b < d.nblocks; ++b) {
+        const int gj0 = d.jglob0[b] - 1, gny = d.jhi[b] - d.jlo[b] + 1;
+        if (row0 < gj0 || row0 >= gj0 + gny) continue;
+        snapped = std::max(snapped, gj0 + ((row0 - gj0) / F.trow) * F.trow);
+    }
+    if (snapped >= 0) row0 = snapped;
+    F.list_row0 = row0;
+    F.zone = row0 + ring;
+    F.H = NY - F.zone;
+    F.to_block[0] = F.zone - ring; F.to_block[1] = F.zone;
+    F.to_rect[0] = F.zone; F.to_rect[1] = F.zone + ring;
+    if (F.zone < 1 || F.H < ring) { F.error = "grid too short for a marched zone under the fold band"; return false; }
+    return true;
+}
+
+void march_fold_tile_rows(const MarchFold &F, int gj0, int gny, int &by0, int &by1)
+{
+    by0 = by1 = 0;
+    if (gny <= 0 || gj0 + gny <= F.list_row0) return;            // the block lies below the list
+    by0 = F.list_row0 > gj0 ? (F.list_row0 - gj0) / F.trow : 0;
+    by1 = (gny - 1) / F.trow + 1;                                 // (its last tile row also owns the T-row jhi + 1)
+}
+
+bool build_march_plan(const cice_evp_hip_dims &d, int own_max, bool wrap_inside, int ext, MarchPlan &P, int fold_h)
 {
     P = MarchPlan();
     const int me = d.rank;
     const int NX = d.nx_global, NY = d.ny_global;
     if (d.nghost != 1) { P.error = "nghost != 1"; return false; }
-    if (d.ns_boundary_type == CICE_EVP_BND_TRIPOLE || d.ns_boundary_type == CICE_EVP_BND_TRIPOLET ||
-        d.ns_boundary_type == CICE_EVP_BND_CYCLIC) {
+    const bool tripole = d.ns_boundary_type == CICE_EVP_BND_TRIPOLE || d.ns_boundary_type == CICE_EVP_BND_TRIPOLET;
+    if (tripole && d.nranks > 1) {
+        P.error = "tripole grid on several ranks: the fold band of the marching path is built for one rank";
+        return false;
+    }
+    if (d.ns_boundary_type == CICE_EVP_BND_CYCLIC || (tripole && fold_h <= 0) || (!tripole && fold_h > 0)) {
         P.error = "north-south boundary is not closed";
         return false;
     }
+    if (fold_h >= NY) { P.error = "fold band as tall as the grid"; return false; }
     const bool ew_cyclic = d.ew_boundary_type == CICE_EVP_BND_CYCLIC;
     std::vector<Blk> blk;
     if (d.gi0 != nullptr && d.nblocks_tot > 0) {
@@ -61,6 +107,16 @@ bool build_march_plan(const cice_evp_hip_dims &d, int own_max, bool wrap_inside,
         if (d.nranks != 1) { P.error = "global block table required when nranks > 1"; return false; }
         for (int b = 0; b < d.nblocks; ++b)
             blk.push_back({d.iglob0[b] - 1, d.jglob0[b] - 1, d.ihi[b] - d.ilo[b] + 1, d.jhi[b] - d.jlo[b] + 1, me});
+    }
+    if (fold_h > 0) {
+        // the zone of a folded grid: the blocks cut off at row NY - fold_h (what lies above belongs to the band)
+        std::vector<Blk> cut;
+        for (Blk b : blk) {
+            if (b.gj0 >= NY - fold_h) continue;
+            b.gny = std::min(b.gny, NY - fold_h - b.gj0);
+            cut.push_back(b);
+        }
+        blk.swap(cut);
     }
     // every rank's rectangle
     const int nranks = std::max(1, (int)d.nranks);

@@ -60,4 +60,30 @@ struct MarchPlan {
 // ext (even, >= 0): every rank also holds -- and advances redundantly -- `ext` cells beyond its own on every side that
 // has a neighbour.  One exchange then brings the ring of ext + P cells around the rank's own cells up to date, and
 // passes advancing ext + P subcycles in all can follow before the next one: every subcycle costs one cell of validity.
-bool build_march_plan(const cice_evp_hip_dims &d, int own_max, bool wrap_inside, int ext, MarchPlan &P);
+// fold_h > 0 (one rank, tripole / tripoleT): the plan is built for the ZONE of a folded grid -- global rows 0 .. NY - fold_h - 1, a
+// rectangle closed in the south with a neighbour in the north.  That neighbour is no rank: it is this process's own fold band
+// (MarchFold), so no peer list names it; the rows above the zone's own are filled by the ring exchange of evp_host_march.cpp.
+bool build_march_plan(const cice_evp_hip_dims &d, int own_max, bool wrap_inside, int ext, MarchPlan &P, int fold_h = 0);
+
+// A tripole grid on one rank: two sets of cells with a ring between them.
+//   zone  global rows 0 .. zone-1, advanced several subcycles per pass in the strip-major rectangle (which also holds `ext`
+//         redundant rows above them and reads a ring of P rows above those);
+//   band  global rows zone .. NY-1 and the ghost row beyond the fold, advanced one subcycle at a time in the caller's block
+//         layout by the tile kernel over a tile list that also covers ext + P rows below the band's own (list_row0 .. zone-1).
+// Every ext + P subcycles the ring is exchanged: rows to_block (zone rows under the band) travel rectangle -> block layout,
+// rows to_rect (band rows above the zone) block layout -> rectangle.  In between either side loses one row of validity per
+// subcycle, from the bottom of the band's list and from the top of the rectangle.
+struct MarchFold {
+    int H = 0, zone = 0, ext = 0;
+    int trow = 0;                  // U-rows per tile row (tile height - 1)
+    int list_row0 = 0;             // the band's tile list covers every row from here up (<= zone - (ext + P))
+    int to_block[2] = {0, 0};      // [lo, hi) global rows
+    int to_rect[2] = {0, 0};
+    std::string error;
+};
+// tyb: tile height of the one-subcycle kernel (2 .. 9).  H is the smallest ext + P (tripoleT: one more, the zone's ring stays
+// below the top physical row), rounded up so that the band's list starts on a tile row of the block that holds it (the same
+// tiles run either way; the zone loses the rows).
+bool build_march_fold(const cice_evp_hip_dims &d, int ext, int tyb, MarchFold &F);
+// tile rows [by0, by1) of a block with `gny` rows whose first row is global row gj0 (0-based) that belong to the band's list
+void march_fold_tile_rows(const MarchFold &F, int gj0, int gny, int &by0, int &by1);

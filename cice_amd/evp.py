@@ -54,7 +54,7 @@ EXPORTS = [
 # libcice_evp_hip_testing.so only (include/cice_evp_hip_testing.h): plan introspection of the CPU tests, read-outs of the tools,
 # the test transport
 TEST_EXPORTS = [
-    "cice_evp_hip_cgrid_fold_plan", "cice_evp_hip_cgrid_window_plan", "cice_evp_hip_cgrid_window_plan_ext", "cice_evp_hip_cgrid_window_deps", "cice_evp_hip_cgrid_strip_plan", "cice_evp_hip_cgrid_strip_zones", "cice_evp_hip_cgrid_frame_plan", "cice_evp_hip_set_test_transport", "cice_evp_hip_march_plan",
+    "cice_evp_hip_cgrid_fold_plan", "cice_evp_hip_cgrid_window_plan", "cice_evp_hip_cgrid_window_plan_ext", "cice_evp_hip_cgrid_window_deps", "cice_evp_hip_cgrid_strip_plan", "cice_evp_hip_cgrid_strip_zones", "cice_evp_hip_cgrid_frame_plan", "cice_evp_hip_set_test_transport", "cice_evp_hip_march_plan", "cice_evp_hip_march_fold_plan",
     "cice_evp_hip_debug_cuload", "cice_evp_hip_debug_prof", "cice_evp_hip_debug_cgrid_prof", "cice_evp_hip_debug_cgres_prof", "cice_evp_hip_plan_build", "cice_evp_hip_halo_plan", "cice_evp_hip_seam_plan",
     "cice_evp_hip_peer_plan", "cice_evp_hip_peer_signs", "cice_evp_hip_center_plan", "cice_evp_hip_stress_plan",
     "cice_evp_hip_fold_split_plan", "cice_evp_hip_plan_flags", "cice_evp_hip_fold_images_plan", "cice_evp_hip_cgrid_fold_xplan",
@@ -706,11 +706,12 @@ class EvpHip:
 
     def march_info(self) -> dict:
         """The marching path (evp_march.hip): did it run, how is the domain cut."""
-        v = np.zeros(10, dtype=np.int32)
+        v = np.zeros(12, dtype=np.int32)
         v[7] = -1
-        self.lib.cice_evp_hip_march_info(_ip(v), 10)
+        self.lib.cice_evp_hip_march_info(_ip(v), 12)
         return dict(mode=int(v[0]), passes=int(v[1]), declined=int(v[2]), strips=int(v[3]), segments=int(v[4]),
                     seglen=int(v[5]), last_call=bool(v[6]), kpass=int(v[8]), subcycles=int(v[9]),
+                    band_rows=int(v[10]), band_subcycles=int(v[11]),      # tripole grid: the fold band beside the marched zone
                     ring={-1: "not set up", 0: "rccl", 1: "direct stores (HIP IPC)", 2: "direct, on trial"}.get(int(v[7]), "?"))
 
     def halo_mask(self, halomask):
@@ -817,6 +818,17 @@ def march_plan(dims: Dims, own_max: int = 0, wrap_inside: bool = True, ext: int 
     return dict(gx0=int(geo[0]), gy0=int(geo[1]), nxr=int(geo[2]), nyr=int(geo[3]), own=int(geo[4]), nstrips=int(geo[5]),
                 wrapx=bool(geo[9]), ext=tuple(int(v) for v in geo[10:14]), peer_rank=pr[:npeer], peer_nsend=pns[:npeer],
                 peer_nrecv=pnr[:npeer], send_pos=sp[:ns], recv_pos1=r1[:nr], recv_pos2=r2[:nr])
+
+
+def march_fold_plan(dims: Dims, ext: int = 0, tyb: int = 5) -> dict:
+    """Host-only: a tripole grid on one rank as the marching path cuts it into the marched zone and the fold band (CPU tests;
+    rows global and 0-based, windows half open -- see the testing header)."""
+    lib = load_library(testing=True)
+    v = np.zeros(10, dtype=np.int32)
+    tr = np.zeros((max(int(dims.nblocks), 1), 2), dtype=np.int32)
+    _check(lib, lib.cice_evp_hip_march_fold_plan(C.byref(dims), ext, tyb, _ip(v), _ip(tr)), "(march_fold_plan)")
+    return dict(zone=int(v[0]), band_rows=int(v[1]), ext=int(v[2]), tile_rows_height=int(v[3]), list_row0=int(v[4]),
+                to_block=(int(v[5]), int(v[6])), to_rect=(int(v[7]), int(v[8])), rect_rows=int(v[9]), tile_rows=tr[:int(dims.nblocks)])
 
 
 def halo_plan(dims: Dims) -> dict:

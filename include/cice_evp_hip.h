@@ -107,7 +107,9 @@ int cice_evp_hip_init(const cice_evp_hip_dims *dims, const cice_evp_hip_params *
  * (ice_dyn_shared module arrays cxp,cyp,cxm,cym,dxhy,dyhx,DminTarea); NULL = keep.
  * On tripole grids pass at least dxhy,dyhx: their north ghost row is a mirrored
  * interior value (halo update with sign, ice_dyn_shared.F90:412-417) which the library
- * can only reproduce by local differencing when the grid is symmetric about the seam. */
+ * can only reproduce by local differencing when the grid is symmetric about the seam.
+ * (The marching path derives the terms in its kernel: on a tripole grid it verifies once, on
+ * the host, that the arrays are those terms on every row below the fold band it marches.) */
 int cice_evp_hip_set_metrics(const double *cxp, const double *cyp, const double *cxm,
                              const double *cym, const double *dxhy, const double *dyhx,
                              const double *DminTarea);
@@ -423,7 +425,12 @@ int cice_evp_hip_time_kernels(int32_t nrep, double *out3);
  * cice_evp_hip_subcycle ran through it, [7] (n >= 8) how its ring travels between ranks: -1 not set up, 0 RCCL send / recv,
  * 1 stores into the neighbours' HIP-IPC-mapped inboxes (opt-in: CICE_EVP_HIP_MARCH_DIRECT=1 on every rank, inside one
  * node; in use once a trial exchange has delivered the same bits as RCCL on every rank), 2 on trial; [8] (n >= 10) subcycles
- * a full pass advances the state by (4), [9] subcycles advanced by passes since init.
+ * a full pass advances the state by (4), [9] subcycles advanced by passes since init; (n >= 12) [10] rows of the fold band
+ * (0 = no band), [11] subcycles the band advanced in the last call.  Tripole / tripoleT grid on one rank: rows 1 .. NY - [10] are
+ * marched, the top [10] rows and the ghost row beyond the fold advance one subcycle per launch beside the passes (tile kernel +
+ * seam step), and the two trade a ring of rows on the device every few passes.  Not eligible: cyclic north-south boundary, a
+ * tripole grid on several ranks, blocks that do not tile a rectangle per rank, metric arrays that are not what HTE, HTN, dxT, dyT
+ * give on the rows the marching kernel evaluates.
  * CICE_EVP_HIP_MARCH=0/1 forces the path off / on (default: from 450k cells per rank).  Several ranks:
  * CICE_EVP_HIP_MARCH_OVERLAP=1 (every rank alike) advances the cells other ranks wait for first, on a second stream, and
  * overlaps their RCCL send / recv with the rest of the pass (default: pack, send / recv, unpack after the pass).        */

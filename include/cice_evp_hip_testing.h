@@ -87,6 +87,13 @@ int cice_evp_hip_set_test_transport(cice_evp_hip_test_xchg_fn xchg, cice_evp_hip
 int cice_evp_hip_march_plan(const cice_evp_hip_dims *dims, int32_t own_max, int32_t wrap_inside, int32_t ext, int32_t *geo14,
                             int32_t *peer_rank, int32_t *peer_nsend, int32_t *peer_nrecv, int32_t *send_pos,
                             int32_t *recv_pos1, int32_t *recv_pos2);
+/* Host-only (CPU tests): how the marching path shares a tripole / tripoleT grid on one rank between the marched zone and the fold
+ * band (cice_amd/csrc/march_plan.h: MarchFold).  ext as above; tyb = tile height of the one-subcycle kernel (2 .. 9).  Rows are
+ * global, 0-based, windows half open.  out10 = {zone rows (the zone is rows 0 .. zone-1), band rows H, ext, U-rows per tile row,
+ * lowest row the band's tile list covers, ring exchange rectangle -> block layout [lo, hi), block layout -> rectangle [lo, hi),
+ * rows the zone's rectangle holds (zone + ext)}; tile_rows (may be NULL) = per local block the tile rows [by0, by1) of the band's
+ * list.  Fails (-3) where there is no fold, on several ranks, and on a grid too short for a zone under the band.           */
+int cice_evp_hip_march_fold_plan(const cice_evp_hip_dims *dims, int32_t ext, int32_t tyb, int32_t *out10, int32_t *tile_rows);
 /* Per-CU record of the last on-chip resident launch with 16 x 16 tiles (tools): n <= 2048*8 ints, per CU
  * (index = XCC<<8 | HW_ID[15:8]) {lock, launch stamp, ice-holding waves on SIMD 0..3, 0, 0}.        */
 int cice_evp_hip_debug_cuload(int32_t *out, int32_t n);
