@@ -271,8 +271,7 @@ int cice_evp_hip_init(const cice_evp_hip_dims *dims, const cice_evp_hip_params *
     S.jhi.assign(dims->jhi, dims->jhi + nb);
     S.iglob0.assign(dims->iglob0, dims->iglob0 + nb);
     S.jglob0.assign(dims->jglob0, dims->jglob0 + nb);
-    S.d.ilo = S.ilo.data(); S.d.ihi = S.ihi.data(); S.d.jlo = S.jlo.data(); S.d.jhi = S.jhi.data();
-    S.d.iglob0 = S.iglob0.data(); S.d.jglob0 = S.jglob0.data();
+    S.d = host_dims();
 
     if (!build_halo_plan(*dims, S.plan)) return fail(-3, "halo plan: %s", S.plan.error.c_str());
     if (env_test("CICE_EVP_HIP_SELF_EXCHANGE") && std::atoi(env_test("CICE_EVP_HIP_SELF_EXCHANGE")) && dims->nranks == 1) {

@@ -20,6 +20,7 @@
 #include <hip/hip_runtime.h>
 #include <rccl/rccl.h>
 
+#include <climits>
 #include <cstdarg>
 #include <cstdio>
 #include <cstdlib>
@@ -333,6 +334,10 @@ inline const char *env(const char *k) { return std::getenv(k); }
 #else
 #define env_test(k) (static_cast<const char *>(nullptr))
 #endif
+// a switch's value as env() / env_test() hand it over (null: not set -> dflt): on unless 0 / as a number
+inline bool env_on(const char *value, bool dflt) { return value ? std::atoi(value) != 0 : dflt; }
+inline int env_int(const char *value, int dflt) { return value ? std::atoi(value) : dflt; }
+constexpr int ENV_UNSET = INT_MIN;      // env_int's dflt where "not set" is a third answer
 
 // mailbox layout: EVP_DIRECT_MAXPEER flag lines, then seq, err, then the inbox
 constexpr size_t DIRECT_SEQ_OFF = (size_t)EVP_DIRECT_MAXPEER * EVP_DIRECT_FLAG_STRIDE * sizeof(unsigned);
@@ -348,6 +353,46 @@ uint64_t host_identity();   // evp_host_mailbox.cpp
 // evp_host_common.cpp
 int alloc_d(double **p, size_t n);
 void free_all();
+cice_evp_hip_dims host_dims();      // S.d with its six per-block tables pointing at the copies init kept
+// a host vector on the device: room for max(1, n) elements, n of them copied; the copy blocks, so the vector may go at once
+template <class T, class V> int upload(T *&p, const std::vector<V> &v)
+{
+    HIPC(hipMalloc((void **)&p, std::max<size_t>(1, v.size()) * sizeof(V)));
+    if (!v.empty()) HIPC(hipMemcpy(p, v.data(), v.size() * sizeof(V), hipMemcpyHostToDevice));
+    return 0;
+}
+// Owner of a set of device allocations by registration: whatever alloc / upload hand out is released by free_all (or, for a buffer
+// that is replaced on its own, free_one).  No destructor: a global's would call HIP after the runtime has shut down.
+struct DevicePool {
+    std::vector<void *> owned;
+    template <class T> int alloc(T *&p, size_t n, bool zero = false)      // zero: cleared on S.stream
+    {
+        HIPC(hipMalloc((void **)&p, n * sizeof(T)));
+        owned.push_back(p);
+        if (zero) HIPC(hipMemsetAsync(p, 0, n * sizeof(T), S.stream));
+        return 0;
+    }
+    template <class T, class V> int upload(T *&p, const std::vector<V> &v)
+    {
+        if (int rc = evp_host::upload(p, v)) return rc;
+        owned.push_back(p);
+        return 0;
+    }
+    template <class T> void free_one(T *&p)
+    {
+        const auto it = std::find(owned.begin(), owned.end(), static_cast<void *>(p));
+        if (it != owned.end()) {
+            (void)hipFree(p);
+            owned.erase(it);
+        }
+        p = nullptr;
+    }
+    void free_all()
+    {
+        for (void *p : owned) (void)hipFree(p);
+        owned.clear();
+    }
+};
 int h2d(double *dst, const double *src);
 int d2h(double *dst, const double *src);
 // batched variants: arrays the caller page-locked travel in ONE gather / scatter launch, the rest as copies

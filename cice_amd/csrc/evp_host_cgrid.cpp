@@ -21,7 +21,38 @@
 
 namespace evp_host {
 
+// the five arrays a subcycle reads in one allocation and writes in the other (every schedule but the five phases), in this order
+static const int PP_FIELDS[5] = {CF_UE, CF_VN, CF_SP, CF_SM, CF_S12U};
+constexpr unsigned PP_FOUR = 15u, PP_S12 = 16u, PP_ALL = PP_FOUR | PP_S12;     // bit q: PP_FIELDS[q]
+
+// What a schedule did with a call's subcycles: the enqueue_* functions fill it in as they enqueue, the graph cache keeps it beside
+// the captured graph (a replay did what the capture did), cice_evp_hip_cgrid_subcycle applies it
+struct Ran {
+    unsigned swapped = 0;        // bit q: PP_FIELDS[q] ended in the allocation that was the other one when the call began
+    int one = 0;                 // subcycles run as one launch each (cg_one)
+    int march = 0;               // ... as the marched kernel beside the fused chain on the frame (several ranks)
+    int mfold = 0;               // ... as the marched kernel beside the five phases on the fold band (tripole grids, one rank)
+};
+// Everything a captured graph bakes in that can change between calls: pointers (in_alt) and kernel / template choices
+struct GraphKey {
+    int ndte, avg_strength;
+    unsigned in_alt;
+    bool first, fused, fast, one, geo, march, mfold, mfold_serial, mfold_sync;
+    auto tie() const { return std::tie(ndte, avg_strength, in_alt, first, fused, fast, one, geo, march, mfold, mfold_serial, mfold_sync); }
+    bool operator<(const GraphKey &o) const { return tie() < o.tie(); }
+};
+// The cells the marched kernel does not own, as the kernels beside it want them: per-cell bits, per level the workgroups to launch,
+// scratch arrays for the intermediates of the zone cells those kernels read
+struct CellLists {
+    uint8_t *cells = nullptr;
+    int *wg[5] = {};
+    int nwg[5] = {};
+    double *scr[5] = {};
+    long ncells = 0;
+};
+
 struct CGridState {
+    DevicePool mem;              // owns every device allocation below
     bool geo = false, uploaded = false;
     double *f[CG_NF] = {}, *in[CG_NIN] = {}, *g[CG_NG] = {};
     double *gslab = nullptr, *inslab = nullptr;   // g[k] = gslab + k * n, in[k] = inslab + k * n: one allocation per table (cg_one addresses them as base + k * stride)
@@ -30,16 +61,16 @@ struct CGridState {
     double *fac[2] = {nullptr, nullptr};   // leading factor of vrel at E / N (once per call)
     unsigned *d_flags = nullptr;
     bool fast = false;           // the shortcuts of cg_stress_u_step<true> hold on every ice cell of this call
-    double *s12alt = nullptr;    // second stress12U buffer of the fused schedule (f[CF_S12U] always holds the current one)
-    int flip = 0;                // which of the two allocations f[CF_S12U] is (part of the graph key)
-    // one launch per subcycle (evp_cgrid.hip: cg_one): window table, second buffers of uvelE, vvelN, stresspT, stressmT
+    // second allocations of PP_FIELDS (f[PP_FIELDS[q]] always holds the current one); [4] always, [0..3] where a schedule that
+    // ping-pongs them can run (need_alt)
+    double *alt[5] = {};
+    unsigned in_alt = 0;         // bit q: f[PP_FIELDS[q]] is the second allocation
+    // one launch per subcycle (evp_cgrid.hip: cg_one): window table
     struct One {
         int *tab = nullptr;
         int4 *tiles = nullptr;
         int ntiles = 0, per_xcd = 0, ox = 0, oy = 0;
-        double *alt[4] = {};
         unsigned long long *prof = nullptr;   // test build: phase stamps (CICE_EVP_HIP_CGRID_PROF=1)
-        int flip = 0;            // which allocation f[CF_UE], f[CF_VN], f[CF_SP], f[CF_SM] are (part of the graph key)
         // the interior of large blocks marched (evp_cgrid.hip: cg_strip): its items, and the windows cg_one keeps (the block edges)
         int *items = nullptr;
         int4 *tiles_e = nullptr;
@@ -49,34 +80,27 @@ struct CGridState {
         long strip_cells = 0;    // cells the marched kernel owns
     } one;
     // several ranks: the marched kernel on the rectangles above beside the fused chain on every other interior cell (enqueue_fused:
-    // "zone marched + frame"; halo_plan.cpp: build_cg_frame)
-    struct Frame {
-        uint8_t *cells = nullptr;            // per cell: frame cell | level S | level T | zone cell
-        int *wg[3] = {};                     // workgroup lists of the three levels
-        int nwg[3] = {};
-        double *scr[4] = {};                 // shearU, etax2T, stresspT, stressmT of the zone cells the frame reads
-        long ncells = 0;                     // frame cells
-        hipStream_t st2 = nullptr;           // the marched kernel's stream, forked from and joined to S.stream in every subcycle
-        hipEvent_t fork = nullptr, join = nullptr;
-    } fr;
+    // "zone marched + frame"; halo_plan.cpp: build_cg_frame).  cells: frame cell | level S | level T | zone cell; three levels; scr:
+    // shearU, etax2T, stresspT, stressmT of the zone cells the frame reads; ncells: frame cells
+    CellLists fr;
     // tripole / tripoleT on one rank: the marched kernel on the rectangles under the fold band beside list-driven variants of the five
     // phase kernels on every other interior cell (enqueue_march_fold: "marched zone + fold band"; halo_plan.cpp: build_cg_march_fold).
-    // The items live in `one` (items, nitems, strip_*), as do the second buffers (one.alt, s12alt)
+    // The items live in `one` (items, nitems, strip_*)
     struct MarchFold {
-        uint8_t *cells = nullptr;            // per cell: the CGM_* bits
-        int *wg[5] = {};                     // workgroup lists of the five phases
-        int nwg[5] = {};
-        double *scr[5] = {};                 // shearU, etax2T, stresspT, stressmT, stress12U of the zone cells the rest reads
+        CellLists rest;                      // cells: the CGM_* bits; five phases; scr: shearU, etax2T, stresspT, stressmT, stress12U; ncells: REST cells
         uint8_t *gmask = nullptr;            // the land masks as bits on the rows the marched kernel derives its geometry on
-        long ncells = 0;                     // REST cells
         int band_rows = 0;
         bool by_size = false;                // cg_strip's size rule holds for the zone
         bool synced = false;                 // the second allocations of the five ping-pong arrays agree with the current ones on every cell no
                                              // subcycle writes (false after an upload and after any call another schedule ran)
         std::string why;                     // why there is no plan on this rank
-        hipStream_t st2 = nullptr;
-        hipEvent_t fork = nullptr, join = nullptr;
     } mf;
+    // the marched kernel's stream beside S.stream, forked from and joined to it in every subcycle.  One per geometry: zone + frame
+    // needs several ranks and no fold, zone + fold band a fold and one rank
+    struct Side {
+        hipStream_t st = nullptr;
+        hipEvent_t fork = nullptr, join = nullptr;
+    } side;
     // all subcycles of a call in one launch, state on the chip (evp_cgrid_res.hip: cg_res)
     struct Res {
         int *tab = nullptr;
@@ -84,7 +108,7 @@ struct CGridState {
         int ntiles = 0;
         uint8_t *pubmap = nullptr;
         uint8_t *gmask = nullptr;    // tripole grids: the land masks as bits (elsewhere CG.gmask, which the one-launch kernels share)
-        void *rec = nullptr;         // EVP_CGRES_SLOTS x S.n records of 32 bytes
+        char *rec = nullptr;         // EVP_CGRES_SLOTS x S.n records of 32 bytes
         int *err = nullptr;
         int *d_order = nullptr;      // the windows that hold ice in this call (cg_res_live at every upload), n_live of them
         int *live_win = nullptr;     // [ntiles] 0 / 1
@@ -122,7 +146,8 @@ struct CGridState {
     int32_t *mask4 = nullptr;    // the caller's four logical masks as uploaded (4 x n words)
     int avg_strength = 0;
     bool first = true;           // no subcycle has run since the upload
-    std::map<std::pair<int, int>, hipGraphExec_t> graphs;   // (ndte, flip << 3 | fused << 2 | first << 1 | avg_strength)
+    struct Captured { hipGraphExec_t exec; Ran ran; };
+    std::map<GraphKey, Captured> graphs;     // the loop of a call as a graph, with what it did
     double t_loop_ms = 0;
     int t_nsub = 0;
     int t_one = 0;               // subcycles of the last call that ran as one launch each (cg_one)
@@ -149,42 +174,47 @@ static CGridState CG;
 
 void cgrid_free()
 {
-    auto F = [](auto *&p) {
-        if (p) (void)hipFree((void *)p);
-        p = nullptr;
-    };
-    for (auto &p : CG.f) F(p);
-    F(CG.gslab); F(CG.inslab); F(CG.one.prof);
-    for (auto &p : CG.in) p = nullptr;
-    for (auto &p : CG.g) p = nullptr;
-    F(CG.tarear); for (auto &p : CG.post) F(p);
-    F(CG.one.tab); F(CG.one.tiles); F(CG.one.items); F(CG.one.tiles_e); F(CG.one.tab_e); for (auto &p : CG.one.alt) F(p);
-    CG.one = CGridState::One{};
-    F(CG.fr.cells); for (auto &p : CG.fr.wg) F(p); for (auto &p : CG.fr.scr) F(p);
-    if (CG.fr.st2) (void)hipStreamDestroy(CG.fr.st2);
-    if (CG.fr.fork) (void)hipEventDestroy(CG.fr.fork);
-    if (CG.fr.join) (void)hipEventDestroy(CG.fr.join);
-    CG.fr = CGridState::Frame{};
-    F(CG.mf.cells); F(CG.mf.gmask); for (auto &p : CG.mf.wg) F(p); for (auto &p : CG.mf.scr) F(p);
-    if (CG.mf.st2) (void)hipStreamDestroy(CG.mf.st2);
-    if (CG.mf.fork) (void)hipEventDestroy(CG.mf.fork);
-    if (CG.mf.join) (void)hipEventDestroy(CG.mf.join);
-    CG.mf = CGridState::MarchFold{};
-    F(CG.res.tab); F(CG.res.tiles); F(CG.res.tiles2); F(CG.res.pubmap); F(CG.res.gmask); F(CG.res.rec); F(CG.res.err); F(CG.res.pairs); F(CG.res.prof); F(CG.res.d_order); F(CG.res.live_win); F(CG.res.live_cell);
-    CG.res = CGridState::Res{};
-    {
-        CGridState::Prep &Q = CG.prep;
-        F(Q.tmask); for (auto &p : Q.xmask) F(p);
-        for (auto &p : Q.fcor) F(p);
-        for (auto &p : Q.t) F(p);
-        F(Q.tmass); F(Q.maskd); F(Q.c_dst); F(Q.c_src); F(Q.c_vsign); F(Q.hwater); F(Q.tbt); F(Q.aicen); F(Q.vicen);
-        for (auto &p : Q.prod) F(p);
-    }
-    F(CG.strengthU); F(CG.s12alt); F(CG.umaskd); F(CG.fac[0]); F(CG.fac[1]); F(CG.d_flags); F(CG.mask); F(CG.gmask); F(CG.mask4); F(CG.img_slot); F(CG.img_dst); F(CG.zero_cells); F(CG.fold_tmp);
-    for (auto &f : CG.fold) { F(f.dst); F(f.a); F(f.b); F(f.flip); }
-    for (auto &kv : CG.graphs) (void)hipGraphExecDestroy(kv.second);
-    CG.graphs.clear();
+    CG.mem.free_all();
+    for (auto &kv : CG.graphs) (void)hipGraphExecDestroy(kv.second.exec);
+    if (CG.side.st) (void)hipStreamDestroy(CG.side.st);
+    if (CG.side.fork) (void)hipEventDestroy(CG.side.fork);
+    if (CG.side.join) (void)hipEventDestroy(CG.side.join);
     CG = CGridState();
+}
+
+// ---- switches: each is read here and nowhere else.  env_test(): the test build only (evp_host.h) ----
+static bool one_switch() { return env_on(env("CICE_EVP_HIP_CGRID_ONE"), true); }     // =0: neither cg_one nor the marched kernel
+static bool split_faces_on() { return env_on(env_test("CICE_EVP_HIP_CGRID_SPLIT"), S.n <= 600000); }
+static int xcd_switch() { return env_int(env_test("CICE_EVP_HIP_CGRID_XCD"), 1); }    // 0: plain 2-D launch, > 1: so many rows per band
+static bool fused_switch() { return env_on(env_test("CICE_EVP_HIP_CGRID_FUSED"), true); }
+static bool geo_switch() { return env_on(env_test("CICE_EVP_HIP_CGRID_GEO"), true); }
+static bool march_ranks_switch() { return env_on(env_test("CICE_EVP_HIP_CGRID_MARCH_RANKS"), true); }
+static int march_fold_switch() { return env_int(env_test("CICE_EVP_HIP_CGRID_MARCH_FOLD"), ENV_UNSET); }
+static bool march_fold_serial() { return env_on(env_test("CICE_EVP_HIP_CGRID_MARCH_FOLD_SERIAL"), false); }
+static bool strip_last_on() { return env_on(env_test("CICE_EVP_HIP_CGRID_STRIP_LAST"), true); }
+static bool strip_ride_on() { return env_on(env_test("CICE_EVP_HIP_CGRID_STRIP_RIDE"), true); }
+static bool one_xcd_on() { return env_on(env_test("CICE_EVP_HIP_CGRID_ONE_XCD"), true); }
+static int one_shape_switch(int dflt) { return std::min(2, std::max(0, env_int(env_test("CICE_EVP_HIP_CGRID_ONE_SHAPE"), dflt))); }
+static int one_strip_switch() { return std::max(1, env_int(env_test("CICE_EVP_HIP_CGRID_ONE_STRIP"), 1 << 20)); }
+static bool prof_on() { return env_on(env_test("CICE_EVP_HIP_CGRID_PROF"), false); }
+static int strip_switch() { return env_int(env_test("CICE_EVP_HIP_CGRID_STRIP"), ENV_UNSET); }
+static int strip_edge_switch() { return std::min(2, std::max(0, env_int(env_test("CICE_EVP_HIP_CGRID_STRIP_EDGE"), 0))); }
+static bool res_cull() { return env_on(env_test("CICE_EVP_HIP_CGRID_RES_CULL"), true); }
+static bool res_sleep_on() { return env_on(env_test("CICE_EVP_HIP_CGRID_RES_SLEEP"), false); }
+static int res_debug() { return env_int(env_test("CICE_EVP_HIP_CGRID_RES_DEBUG"), 0); }
+static bool fast_switch() { return env_on(env_test("CICE_EVP_HIP_CGRID_FAST"), true); }
+static int resident_switch() { return env_int(env("CICE_EVP_HIP_CGRID_RESIDENT"), -1); }     // 0 / 1 forces the verdict
+static bool verbose() { return env("CICE_EVP_HIP_VERBOSE") != nullptr; }
+// The marched kernel's knobs (cg_strip; test build): work items that fill the chip once, a forced segment length in rows (0: the
+// planner's), whether the kernel may form six of the eight lengths itself, and -- several ranks -- slots left to the frame's workgroups
+constexpr long STRIP_SLOTS = 2048;           // about two waves per SIMD resident at once (256 CUs x 8)
+constexpr long STRIP_MIN_CELLS = 300000;     // the size rule: where the work items fill enough of the chip (measured: build_one_tables)
+struct StripKnobs { long slots; int seg_forced; bool want_len; int reserve; };
+static StripKnobs strip_knobs()
+{
+    const int seg = env_int(env_test("CICE_EVP_HIP_CGRID_STRIP_SEG"), ENV_UNSET);
+    return {std::max(1, env_int(env_test("CICE_EVP_HIP_CGRID_STRIP_ITEMS"), (int)STRIP_SLOTS)), seg == ENV_UNSET ? 0 : std::max(1, seg),
+            env_on(env_test("CICE_EVP_HIP_CGRID_STRIP_LEN"), true), env_int(env_test("CICE_EVP_HIP_CGRID_MARCH_RESERVE"), ENV_UNSET)};
 }
 
 static bool geo_derived();
@@ -211,16 +241,12 @@ static void fill(EvpCgrid &A)
     A.nblocks = S.d.nblocks;
     A.avg_strength = CG.avg_strength;
     A.tripole = CG.tripole ? 1 : 0;
-    {   // two waves per cell in the fused step kernel while the grid is small enough to be latency-bound
-        const char *e = env_test("CICE_EVP_HIP_CGRID_SPLIT");
-        A.split_faces = e ? (std::atoi(e) != 0) : (S.n <= 600000);
-    }
-    {   // XCD-banded workgroup numbering (evp_cgrid.hip: cell()); CICE_EVP_HIP_CGRID_XCD=0: plain 2-D launch
-        const bool on = !(env_test("CICE_EVP_HIP_CGRID_XCD") && !std::atoi(env_test("CICE_EVP_HIP_CGRID_XCD")));
+    A.split_faces = split_faces_on();      // two waves per cell in the fused step kernel while the grid is small enough to be latency-bound
+    {   // XCD-banded workgroup numbering (evp_cgrid.hip: cell())
+        const int xcd = xcd_switch();
         const int gy = (S.d.ny_block + 3) / 4;      // TY = 4 rows per workgroup
         const int gx = (S.d.nx_block + 63) / 64;    // TX = 64
-        const int rows = env_test("CICE_EVP_HIP_CGRID_XCD") && std::atoi(env_test("CICE_EVP_HIP_CGRID_XCD")) > 1 ? std::atoi(env_test("CICE_EVP_HIP_CGRID_XCD")) : std::max(1, 256 / gx);
-        A.xcd_rows = on ? std::min((gy + 7) / 8, rows) : 0;
+        A.xcd_rows = xcd ? std::min((gy + 7) / 8, xcd > 1 ? xcd : std::max(1, 256 / gx)) : 0;
     }
     A.plane = S.plane;
 }
@@ -267,7 +293,7 @@ static bool fused_schedule()
 {
     if (CG.avg_strength && !one_launch()) return false;   // the three-launch kernels need deltaU at the neighbours: five phases
     if (CG.tripole) return false;                // recomputing a neighbour across the fold would sum in mirrored order
-    return !(env_test("CICE_EVP_HIP_CGRID_FUSED") && !std::atoi(env_test("CICE_EVP_HIP_CGRID_FUSED")));
+    return fused_switch();
 }
 
 // The kernels push a cell into its ghost images only where there is ice; the reference's ice_HaloUpdate copies every
@@ -313,11 +339,50 @@ static int enqueue_phases(const EvpCgrid &A, int ndte, bool first)
     return 0;
 }
 
-static int res_launch(const EvpCgrid &A, int nsub, bool dry, double *const cur5[5], double *const alt5[5]);
+// The current and the other allocation of PP_FIELDS as a schedule sees them while it enqueues: swap() per subcycle, `swapped` for Ran
+struct PingPong {
+    double *cur[5], *alt[5];
+    unsigned swapped = 0;
+    PingPong()
+    {
+        for (int q = 0; q < 5; ++q) {
+            cur[q] = CG.f[PP_FIELDS[q]];
+            alt[q] = CG.alt[q];
+        }
+    }
+    void swap(unsigned which)
+    {
+        for (int q = 0; q < 5; ++q)
+            if (which >> q & 1u) std::swap(cur[q], alt[q]);
+        swapped ^= which;
+    }
+    // a launch that works in place, and what the call leaves: the current allocations
+    void at_current(EvpCgrid &A) const
+    {
+        for (int q = 0; q < 5; ++q) A.f[PP_FIELDS[q]] = cur[q];
+    }
+    // this subcycle writes the other allocations and reads the current ones
+    void aim(EvpCgrid &A, unsigned which) const
+    {
+        for (int q = 0; q < 5; ++q)
+            if (which >> q & 1u) A.f[PP_FIELDS[q]] = alt[q];
+        if (which & PP_S12) A.s12_in = cur[4];
+    }
+    // bring the second allocations into line: both then agree on the cells no later subcycle writes (no ice; ghost cells nothing
+    // is copied into)
+    int sync(unsigned which) const
+    {
+        for (int q = 0; q < 5; ++q)
+            if (which >> q & 1u) HIPC(hipMemcpyAsync(alt[q], cur[q], S.n * sizeof(double), hipMemcpyDeviceToDevice, S.stream));
+        return 0;
+    }
+};
+// (the resident launch reads P.cur and leaves the final state in BOTH allocations: it swaps nothing)
+static int res_launch(const EvpCgrid &A, int nsub, bool dry, const PingPong &P);
 // tripole (u-fold) on one rank: the first subcycles as five launches + fold steps, the last nres inside ONE launch of the on-chip
 // resident kernel's FOLD variant, then the fold step of everything that launch leaves (ghost row beyond the fold; the points ON the fold
 // come out averaged already, and the step leaves an averaged pair as it is) and the velocity averages after the loop
-static int enqueue_phases_resident(const EvpCgrid &A, int ndte, bool first, int nres);
+static int enqueue_phases_resident(const EvpCgrid &A, int ndte, bool first, int nres, Ran &ran);
 
 // one launch per subcycle (cg_one) for every subcycle but the first after an upload (which still reads the caller's
 // uvelN, vvelE, uvel, vvel): one rank, no fold.  Measured, us per subcycle, three launches -> one:
@@ -330,8 +395,7 @@ static int enqueue_phases_resident(const EvpCgrid &A, int ndte, bool first, int 
 static bool geo_derived()
 {
     if (!CG.gmask) return false;
-    if (const char *e = env_test("CICE_EVP_HIP_CGRID_GEO")) return std::atoi(e) != 0;
-    return true;
+    return geo_switch();
 }
 // Checks, on every cell the kernels can read (the blocks' cells with their ghost ring; the ratios and nothing else need
 // a neighbour: interior cells), that the caller's derived arrays are what the reference's start-up computes from dx / dy
@@ -408,14 +472,7 @@ static bool strip_lengths_hold(const StripZone &z, int EX, int EY, const double 
     return true;
 }
 
-static const int ONE_FIELDS[4] = {CF_UE, CF_VN, CF_SP, CF_SM};
-static bool one_launch()
-{
-    if (!CG.one.tab || remote()) return false;
-    if (const char *e = env("CICE_EVP_HIP_CGRID_ONE")) return std::atoi(e) != 0;
-    return true;
-}
-static int one_subcycles(int ndte, bool first) { return one_launch() ? ndte - (first ? 1 : 0) : 0; }
+static bool one_launch() { return CG.one.tab && !remote() && one_switch(); }
 // Several ranks, no fold, visc_method = avg_zeta, the derived view of the static table, and rectangles for the marched kernel on THIS
 // rank: cg_strip marches them on a second stream while the three fused kernels' frame variants advance every other interior cell on
 // S.stream, with today's exchanges at today's points -- so a rank without rectangles simply runs today's schedule and the ranks
@@ -424,14 +481,8 @@ static int one_subcycles(int ndte, bool first) { return one_launch() ? ndte - (f
 static bool march_ranks()
 {
     if (!CG.fr.cells || CG.one.nitems <= 0 || !remote() || CG.tripole || CG.avg_strength || !geo_derived()) return false;
-    if (const char *e = env("CICE_EVP_HIP_CGRID_ONE"))
-        if (!std::atoi(e)) return false;
-    if (const char *e = env_test("CICE_EVP_HIP_CGRID_MARCH_RANKS")) return std::atoi(e) != 0;
-    return true;
+    return one_switch() && march_ranks_switch();
 }
-static int march_subcycles(int ndte, bool first) { return march_ranks() ? ndte - (first ? 1 : 0) : 0; }
-static int res_launch(const EvpCgrid &A, int nsub, bool dry, double *const cur5[5], double *const alt5[5]);
-static int build_res_tables(const double *const *static23);
 
 // Tripole / tripoleT on one rank, visc_method = avg_zeta, with rectangles for cg_strip under the fold band (set_geometry built the plan):
 // every subcycle but the first after an upload runs as "marched zone + fold band" (enqueue_march_fold).  The on-chip resident kernel
@@ -441,72 +492,67 @@ static int build_res_tables(const double *const *static23);
 static constexpr bool MARCH_FOLD_DEFAULT = true;       // measured: profiles/r09_cgrid_march_tripole.txt
 static int march_fold_wanted()         // 0 off, 1 forced on, 2 by the size rule
 {
-    if (const char *e = env("CICE_EVP_HIP_CGRID_ONE"))
-        if (!std::atoi(e)) return 0;
-    if (const char *e = env_test("CICE_EVP_HIP_CGRID_MARCH_FOLD")) return std::atoi(e) ? 1 : 0;
+    if (!one_switch()) return 0;
+    const int forced = march_fold_switch();
+    if (forced != ENV_UNSET) return forced ? 1 : 0;
     return MARCH_FOLD_DEFAULT ? 2 : 0;
 }
-static bool march_fold_serial() { return env_test("CICE_EVP_HIP_CGRID_MARCH_FOLD_SERIAL") && std::atoi(env_test("CICE_EVP_HIP_CGRID_MARCH_FOLD_SERIAL")); }
-static bool strip_last_on() { return !(env_test("CICE_EVP_HIP_CGRID_STRIP_LAST") && !std::atoi(env_test("CICE_EVP_HIP_CGRID_STRIP_LAST"))); }
-// subcycles of a call of ndte that run in the schedule (the first after an upload, and under CICE_EVP_HIP_CGRID_STRIP_LAST=0 the last,
-// run as the five full phases)
-static int march_fold_count(int ndte, bool first) { return std::max(0, ndte - (first ? 1 : 0) - (strip_last_on() ? 0 : 1)); }
 static bool march_fold()
 {
-    if (!CG.mf.cells || CG.one.nitems <= 0 || !CG.tripole || remote() || CG.avg_strength) return false;
+    if (!CG.mf.rest.cells || CG.one.nitems <= 0 || !CG.tripole || remote() || CG.avg_strength) return false;
     const int want = march_fold_wanted();
     return want == 1 || (want == 2 && CG.mf.by_size);
 }
 static int enqueue_phases(const EvpCgrid &A, int ndte, bool first);
-static const int MF_FIELDS[5] = {CF_UE, CF_VN, CF_SP, CF_SM, CF_S12U};
-// The two allocations of the five ping-pong arrays change places march_fold_count() times (the caller renames them when that is odd)
+// The marched kernel's arguments from CG.one: its items, and the buffers and tables as cg_one takes them (no window list)
+struct StripArgs { EvpCgOne T; EvpCgStrip Z; };
+static StripArgs strip_args(const PingPong &P, const uint8_t *gmask)
+{
+    const CGridState::One &O = CG.one;
+    return {EvpCgOne{nullptr, nullptr, 0, 0, O.ex, O.ey, 0, P.cur[0], P.cur[1], P.cur[2], P.cur[3], CG.gslab, CG.inslab, S.n, nullptr, gmask},
+            EvpCgStrip{O.items, O.nitems, ((O.nitems + 3) / 4 + 7) / 8, O.strip_len}};
+}
 // sync: the second allocations have not been brought into line since the upload (another schedule ran the calls before this one)
-static int enqueue_march_fold(EvpCgrid A, int ndte, bool first, bool sync)
+static int enqueue_march_fold(EvpCgrid A, int ndte, bool first, bool sync, Ran &ran)
 {
     const CGridState::MarchFold &Q = CG.mf;
-    double *c5[5], *o5[5];
-    for (int q = 0; q < 5; ++q) {
-        c5[q] = CG.f[MF_FIELDS[q]];
-        o5[q] = q < 4 ? CG.one.alt[q] : CG.s12alt;
-    }
+    const CellLists &R = Q.rest;
+    PingPong P;
     // zone first, then the rest, on one stream (test build, A/B)
     const bool serial = march_fold_serial(), strip_last = strip_last_on();
     const int fast = CG.fast ? 1 : 0;
     int k = 0;
     if (first) {
         // the first subcycle after an upload still reads the caller's uvelN, vvelE, uvel, vvel and repairs the ghost cells: the five
-        // full phases, in place.  Then both allocations agree on the cells no later subcycle writes (no ice; ghost cells nothing is
-        // copied into)
+        // full phases, in place
         if (int rc = enqueue_phases(A, 1, true)) return rc;
-        for (int q = 0; q < 5; ++q) HIPC(hipMemcpyAsync(o5[q], c5[q], S.n * sizeof(double), hipMemcpyDeviceToDevice, S.stream));
         k = 1;
-    } else if (sync) {
-        for (int q = 0; q < 5; ++q) HIPC(hipMemcpyAsync(o5[q], c5[q], S.n * sizeof(double), hipMemcpyDeviceToDevice, S.stream));
     }
+    if (first || sync)
+        if (int rc = P.sync(PP_ALL)) return rc;
     for (; k < ndte; ++k) {
         const int last = (k == ndte - 1);
         if (last && !strip_last) {
             // (A/B: the call's last subcycle without the marched kernel's LAST instantiation -- the five full phases, in place)
-            for (int q = 0; q < 5; ++q) A.f[MF_FIELDS[q]] = c5[q];
-            return enqueue_phases(A, 1, false);
+            P.at_current(A);
+            if (int rc = enqueue_phases(A, 1, false)) return rc;
+            break;
         }
         // both sets read the previous subcycle's buffers and own disjoint cells of this subcycle's
-        for (int q = 0; q < 5; ++q) A.f[MF_FIELDS[q]] = o5[q];
-        A.s12_in = c5[4];
-        EvpCgOne T{nullptr, nullptr, 0, 0, CG.one.ex, CG.one.ey, 0, c5[0], c5[1], c5[2], c5[3], CG.gslab, CG.inslab, S.n, nullptr, Q.gmask};
-        EvpCgStrip Z{CG.one.items, CG.one.nitems, ((CG.one.nitems + 3) / 4 + 7) / 8, CG.one.strip_len};
-        EvpCgBand B{Q.cells, {Q.wg[0], Q.wg[1], Q.wg[2], Q.wg[3], Q.wg[4]}, {Q.nwg[0], Q.nwg[1], Q.nwg[2], Q.nwg[3], Q.nwg[4]},
-                    c5[0], c5[1], c5[2], c5[3], c5[4], Q.scr[0], Q.scr[1], Q.scr[2], Q.scr[3], Q.scr[4]};
+        P.aim(A, PP_ALL);
+        const StripArgs Z = strip_args(P, Q.gmask);
+        EvpCgBand B{R.cells, {R.wg[0], R.wg[1], R.wg[2], R.wg[3], R.wg[4]}, {R.nwg[0], R.nwg[1], R.nwg[2], R.nwg[3], R.nwg[4]},
+                    P.cur[0], P.cur[1], P.cur[2], P.cur[3], P.cur[4], R.scr[0], R.scr[1], R.scr[2], R.scr[3], R.scr[4]};
         if (serial) {
-            evp_launch_cgrid_strip(A, T, Z, nullptr, fast, last, S.stream);
+            evp_launch_cgrid_strip(A, Z.T, Z.Z, nullptr, fast, last, S.stream);
             evp_launch_cgrid_band(A, B, 0, S.stream);
         } else {
             // (the rest's first launch goes ahead of the marched kernel, which fills the chip)
-            HIPC(hipEventRecord(Q.fork, S.stream));
+            HIPC(hipEventRecord(CG.side.fork, S.stream));
             evp_launch_cgrid_band(A, B, 0, S.stream);
-            HIPC(hipStreamWaitEvent(Q.st2, Q.fork, 0));
-            evp_launch_cgrid_strip(A, T, Z, nullptr, fast, last, Q.st2);
-            HIPC(hipEventRecord(Q.join, Q.st2));
+            HIPC(hipStreamWaitEvent(CG.side.st, CG.side.fork, 0));
+            evp_launch_cgrid_strip(A, Z.T, Z.Z, nullptr, fast, last, CG.side.st);
+            HIPC(hipEventRecord(CG.side.join, CG.side.st));
         }
         fold({{A.f[CF_SHEARU], 1, false}});
         evp_launch_cgrid_band(A, B, 1, S.stream);
@@ -517,53 +563,46 @@ static int enqueue_march_fold(EvpCgrid A, int ndte, bool first, bool sync)
         fold({{A.f[CF_UE], 2, true}, {A.f[CF_VN], 3, true}});
         // the averages read the new velocities of both sets: the two meet again before them.  In the call's last subcycle over the
         // whole domain: the caller gets uvelN, vvelE, uvel, vvel of every cell
-        if (!serial) HIPC(hipStreamWaitEvent(S.stream, Q.join, 0));
+        if (!serial) HIPC(hipStreamWaitEvent(S.stream, CG.side.join, 0));
         // (and before a last subcycle that runs as the five full phases, which read them on every cell)
         if (last || (k == ndte - 2 && !strip_last)) evp_launch_cgrid_phase(A, 4, 1, S.stream);
         else evp_launch_cgrid_band(A, B, 4, S.stream);
         fold({{A.f[CF_UN], 3, true}, {A.f[CF_VE], 2, true}, {A.f[CF_UU], 1, true}, {A.f[CF_VU], 1, true}});
-        for (int q = 0; q < 5; ++q) std::swap(c5[q], o5[q]);
+        P.swap(PP_ALL);
+        ++ran.mfold;
     }
+    ran.swapped = P.swapped;
     return 0;
 }
 
-// three launches per subcycle + one after the loop (evp_cgrid.hip); stress12U ping-pongs, returns with the
-// current values in `cur` (the caller swaps the pointers when ndte is odd)
-// nres > 0: the last nres subcycles of the call run inside ONE launch of the on-chip resident kernel (evp_cgrid_res.hip), which
-// reads the current allocation of each ping-pong array and leaves the final state in both
-static int enqueue_fused(EvpCgrid A, int ndte, bool first, int nres = 0)
+// three launches per subcycle + one after the loop (evp_cgrid.hip); stress12U ping-pongs, and with it -- one launch per subcycle, zone
+// marched + frame -- uvelE, vvelN, stresspT, stressmT
+// nres > 0: the last nres subcycles of the call run inside ONE launch of the on-chip resident kernel (evp_cgrid_res.hip)
+static int enqueue_fused(EvpCgrid A, int ndte, bool first, int nres, Ran &ran)
 {
-    double *cur = CG.f[CF_S12U], *other = CG.s12alt;
     const bool one = one_launch(), march = march_ranks();
-    double *c4[4], *o4[4];
-    for (int q = 0; q < 4; ++q) {
-        c4[q] = CG.f[ONE_FIELDS[q]];
-        o4[q] = CG.one.alt[q];
-    }
+    const int fast = CG.fast ? 1 : 0;
+    PingPong P;
     if (first) {
         // the caller's ghost cells of stress12U are whatever dyn_prep left there (zero: iceUmask is never set on
         // ghost cells, ice_dyn_evp.F90:683-690); the reference repairs them with the first halo update, the fused
         // kernel recomputes neighbours from their previous value: make the previous values ghost-consistent first
         evp_launch_cgrid_phase(A, 9, CF_S12U, S.stream);
-        XCHG(cur, cur);
+        XCHG(P.cur[4], P.cur[4]);
         // (ghost cells of eliminated land blocks: zero in both buffers; no ice cell reads them before the first exchange)
         evp_launch_cgrid_zero_cells(A, CG.zero_cells, CG.n_zero, S.stream);
-        HIPC(hipMemcpyAsync(other, cur, S.n * sizeof(double), hipMemcpyDeviceToDevice, S.stream));
+        if (int rc = P.sync(PP_S12)) return rc;
     }
     for (int k = 0; k < ndte - nres; ++k) {
         const int last = (k == ndte - 1);
-        A.f[CF_S12U] = cur;
+        P.at_current(A);
         if (one && !(first && k == 0)) {
-            EvpCgOne T{CG.one.tab, CG.one.tiles, CG.one.ntiles, CG.one.per_xcd, CG.one.ox, CG.one.oy,
-                       (env_test("CICE_EVP_HIP_CGRID_ONE_XCD") && !std::atoi(env_test("CICE_EVP_HIP_CGRID_ONE_XCD"))) ? 1 : 0, c4[0], c4[1], c4[2], c4[3], CG.gslab, CG.inslab, S.n,
-                       CG.one.prof, geo_derived() ? CG.gmask : nullptr};
-            for (int q = 0; q < 4; ++q) A.f[ONE_FIELDS[q]] = o4[q];
-            A.s12_in = cur;
-            A.f[CF_S12U] = other;
-            if (CG.one.nitems > 0 && T.gmask && !(last && env_test("CICE_EVP_HIP_CGRID_STRIP_LAST") && !std::atoi(env_test("CICE_EVP_HIP_CGRID_STRIP_LAST")))) {
+            EvpCgOne T{CG.one.tab, CG.one.tiles, CG.one.ntiles, CG.one.per_xcd, CG.one.ox, CG.one.oy, one_xcd_on() ? 0 : 1,
+                       P.cur[0], P.cur[1], P.cur[2], P.cur[3], CG.gslab, CG.inslab, S.n, CG.one.prof, geo_derived() ? CG.gmask : nullptr};
+            P.aim(A, PP_ALL);
+            if (CG.one.nitems > 0 && T.gmask && !(last && !strip_last_on())) {
                 // the interior of the blocks marched, the windows along their edges as before: both read the previous
                 // subcycle's buffers only and own disjoint cells
-                EvpCgStrip Z{CG.one.items, CG.one.nitems, ((CG.one.nitems + 3) / 4 + 7) / 8, CG.one.strip_len};
                 EvpCgOne E = T;
                 E.tab = CG.one.tab_e; E.tiles = CG.one.tiles_e; E.ntiles = CG.one.ntiles_e; E.per_xcd = (CG.one.ntiles_e + 7) / 8;
                 E.ox = CG.one.ex; E.oy = CG.one.ey;
@@ -571,44 +610,41 @@ static int enqueue_fused(EvpCgrid A, int ndte, bool first, int nres = 0)
                 // (the edge windows on the second stream beside the marched kernel: measured no gain, 565 us against 552 -- a
                 // 1024-thread workgroup does not fit beside the marched kernel's waves on a CU anyway)
                 // windows of 32 x 8 ride in the marched kernel's launch; other shapes (A/B) get a launch of their own behind it
-                const bool ride = E.ox == 32 && E.oy == 8 && !(env_test("CICE_EVP_HIP_CGRID_STRIP_RIDE") && !std::atoi(env_test("CICE_EVP_HIP_CGRID_STRIP_RIDE")));
-                evp_launch_cgrid_strip(A, T, Z, ride ? &E : nullptr, CG.fast ? 1 : 0, last, S.stream);
-                if (!ride && E.ntiles > 0) evp_launch_cgrid_one(A, E, CG.fast ? 1 : 0, last, S.stream);
+                const bool ride = E.ox == 32 && E.oy == 8 && strip_ride_on();
+                evp_launch_cgrid_strip(A, T, strip_args(P, T.gmask).Z, ride ? &E : nullptr, fast, last, S.stream);
+                if (!ride && E.ntiles > 0) evp_launch_cgrid_one(A, E, fast, last, S.stream);
             } else if (T.ntiles > 0) {
-                evp_launch_cgrid_one(A, T, CG.fast ? 1 : 0, last, S.stream);
+                evp_launch_cgrid_one(A, T, fast, last, S.stream);
             }
-            std::swap(cur, other);
-            for (int q = 0; q < 4; ++q) std::swap(c4[q], o4[q]);
+            P.swap(PP_ALL);
+            ++ran.one;
             continue;
         }
         if (march && !(first && k == 0)) {
             // the rectangles marched on the second stream, every other interior cell by the frame variants of the three fused kernels
             // here, with the exchanges of the fused schedule at their points: both read the previous subcycle's buffers, own disjoint
             // cells of this subcycle's, and meet again before the buffers swap
-            const int fast = CG.fast ? 1 : 0;
-            EvpCgOne T{nullptr, nullptr, 0, 0, CG.one.ex, CG.one.ey, 0, c4[0], c4[1], c4[2], c4[3], CG.gslab, CG.inslab, S.n, nullptr, CG.gmask};
-            EvpCgStrip Z{CG.one.items, CG.one.nitems, ((CG.one.nitems + 3) / 4 + 7) / 8, CG.one.strip_len};
-            const CGridState::Frame &Q = CG.fr;
-            EvpCgFrame Fr{Q.cells, {Q.wg[0], Q.wg[1], Q.wg[2]}, {Q.nwg[0], Q.nwg[1], Q.nwg[2]}, c4[0], c4[1], c4[2], c4[3], Q.scr[0], Q.scr[1], Q.scr[2], Q.scr[3]};
-            for (int q = 0; q < 4; ++q) A.f[ONE_FIELDS[q]] = o4[q];
-            A.s12_in = cur;
-            A.f[CF_S12U] = other;
+            const StripArgs Z = strip_args(P, CG.gmask);
+            const CellLists &Q = CG.fr;
+            EvpCgFrame Fr{Q.cells, {Q.wg[0], Q.wg[1], Q.wg[2]}, {Q.nwg[0], Q.nwg[1], Q.nwg[2]}, P.cur[0], P.cur[1], P.cur[2], P.cur[3],
+                          Q.scr[0], Q.scr[1], Q.scr[2], Q.scr[3]};
+            P.aim(A, PP_ALL);
             // (the frame's first launch goes ahead of the marched kernel, which fills the chip: DESIGN.md section 7)
-            HIPC(hipEventRecord(Q.fork, S.stream));
+            HIPC(hipEventRecord(CG.side.fork, S.stream));
             evp_launch_cgrid_frame(A, Fr, 0, fast, last, S.stream);
-            HIPC(hipStreamWaitEvent(Q.st2, Q.fork, 0));
-            evp_launch_cgrid_strip(A, T, Z, nullptr, fast, last, Q.st2);
-            HIPC(hipEventRecord(Q.join, Q.st2));
+            HIPC(hipStreamWaitEvent(CG.side.st, CG.side.fork, 0));
+            evp_launch_cgrid_strip(A, Z.T, Z.Z, nullptr, fast, last, CG.side.st);
+            HIPC(hipEventRecord(CG.side.join, CG.side.st));
             XCHG(A.f[CF_SHEARU], A.f[CF_SHEARU]);
             evp_launch_cgrid_frame(A, Fr, 1, fast, last, S.stream);
             XCHG(A.f[CF_ETA], A.f[CF_ZETA]);
             XCHG(A.f[CF_SP], A.f[CF_SM]);
             evp_launch_cgrid_frame(A, Fr, 2, fast, last, S.stream);
-            XCHG(other, other);
+            XCHG(A.f[CF_S12U], A.f[CF_S12U]);
             XCHG(A.f[CF_UE], A.f[CF_VN]);
-            HIPC(hipStreamWaitEvent(S.stream, Q.join, 0));
-            std::swap(cur, other);
-            for (int q = 0; q < 4; ++q) std::swap(c4[q], o4[q]);
+            HIPC(hipStreamWaitEvent(S.stream, CG.side.join, 0));
+            P.swap(PP_ALL);
+            ++ran.march;
             continue;
         }
         if (first && k == 0 && CG.avg_strength) {
@@ -620,9 +656,7 @@ static int enqueue_fused(EvpCgrid A, int ndte, bool first, int nres = 0)
             evp_launch_cgrid_phase(A, 2, 1, S.stream);
             first_exchange_copies_everything(A, {CF_S12U});
             evp_launch_cgrid_phase(A, 3, 1, S.stream);
-            for (int q = 0; q < 4; ++q)
-                HIPC(hipMemcpyAsync(o4[q], c4[q], S.n * sizeof(double), hipMemcpyDeviceToDevice, S.stream));
-            HIPC(hipMemcpyAsync(other, cur, S.n * sizeof(double), hipMemcpyDeviceToDevice, S.stream));
+            if (int rc = P.sync(PP_ALL)) return rc;
             continue;
         }
         if (first && k == 0) {
@@ -636,36 +670,30 @@ static int enqueue_fused(EvpCgrid A, int ndte, bool first, int nres = 0)
         if (first && k == 0) first_exchange_copies_everything(A, {CF_SP, CF_SM});   // (stress12U: above, before the loop)
         XCHG(A.f[CF_ETA], A.f[CF_ZETA]);         // (zetax2T is stored in the last subcycle only; harmless before)
         XCHG(A.f[CF_SP], A.f[CF_SM]);
-        A.s12_in = cur;
-        A.f[CF_S12U] = other;
+        P.aim(A, PP_S12);
         evp_launch_cgrid_phase(A, CG.fast ? 11 : 8, last, S.stream);
-        XCHG(other, other);
+        XCHG(A.f[CF_S12U], A.f[CF_S12U]);
         XCHG(A.f[CF_UE], A.f[CF_VN]);
-        std::swap(cur, other);
-        if ((one || march) && first && k == 0)          // cells no subcycle writes (no ice, ghost cells nothing is copied into): the same in both buffers
-            for (int q = 0; q < 4; ++q)
-                HIPC(hipMemcpyAsync(o4[q], c4[q], S.n * sizeof(double), hipMemcpyDeviceToDevice, S.stream));
+        P.swap(PP_S12);
+        if ((one || march) && first && k == 0)          // the four others ping-pong from the next subcycle on
+            if (int rc = P.sync(PP_FOUR)) return rc;
     }
-    A.f[CF_S12U] = cur;
-    for (int q = 0; q < 4; ++q) A.f[ONE_FIELDS[q]] = c4[q];
-    if (nres > 0) {
-        double *cur5[5] = {c4[0], c4[1], c4[2], c4[3], cur};
-        double *alt5[5] = {o4[0], o4[1], o4[2], o4[3], other};
-        if (int rc = res_launch(A, nres, false, cur5, alt5)) return rc;
-    }
+    P.at_current(A);
+    ran.swapped = P.swapped;
+    if (nres > 0)
+        if (int rc = res_launch(A, nres, false, P)) return rc;
     evp_launch_cgrid_phase(A, 4, 1, S.stream);
     XCHG(A.f[CF_UN], A.f[CF_VE]);
     XCHG(A.f[CF_UU], A.f[CF_VU]);
     return 0;
 }
 
-static int enqueue_phases_resident(const EvpCgrid &A, int ndte, bool first, int nres)
+static int enqueue_phases_resident(const EvpCgrid &A, int ndte, bool first, int nres, Ran &ran)
 {
     if (ndte > nres)
         if (int rc = enqueue_phases(A, ndte - nres, first)) return rc;
-    double *cur5[5] = {CG.f[CF_UE], CG.f[CF_VN], CG.f[CF_SP], CG.f[CF_SM], CG.f[CF_S12U]};
-    double *alt5[5] = {CG.one.alt[0], CG.one.alt[1], CG.one.alt[2], CG.one.alt[3], CG.s12alt};
-    if (int rc = res_launch(A, nres, false, cur5, alt5)) return rc;
+    ran = Ran{};       // (the five phases run in place, the resident launch leaves its result in both allocations)
+    if (int rc = res_launch(A, nres, false, PingPong())) return rc;
     fold({{A.f[CF_SHEARU], 1, false}, {A.f[CF_S12U], 1, false}});
     fold({{A.f[CF_ZETA], 0, false}, {A.f[CF_ETA], 0, false}, {A.f[CF_SP], 0, false}, {A.f[CF_SM], 0, false}});
     fold({{A.f[CF_UE], 2, true}, {A.f[CF_VN], 3, true}});
@@ -678,30 +706,64 @@ static int enqueue_phases_resident(const EvpCgrid &A, int ndte, bool first, int 
 static int build_fold_lists()
 {
     if (S.d.nx_global % 2) return fail(-4, "tripole: nx_global must be even");
-    cice_evp_hip_dims d = S.d;
-    d.ilo = S.ilo.data(); d.ihi = S.ihi.data(); d.jlo = S.jlo.data(); d.jhi = S.jhi.data();
-    d.iglob0 = S.iglob0.data(); d.jglob0 = S.jglob0.data();
+    const cice_evp_hip_dims d = host_dims();
     CG.fold_maxn = 0;
     for (int loc = 0; loc < 4; ++loc) {
         FoldList L;
         if (S.plan.cg_split) L = S.plan.cg_fold[loc];      // (operands >= S.n: staging slots the exchange fills)
         else build_fold_list(d, loc, L);
-        const std::vector<int32_t> &dst = L.dst, &a = L.a, &bb = L.b;
-        const std::vector<uint8_t> &flip = L.flip;
         CGridState::Fold &Fd = CG.fold[loc];
-        Fd.n = (int)dst.size();
+        Fd.n = (int)L.dst.size();
         CG.fold_maxn = std::max(CG.fold_maxn, Fd.n);
         if (!Fd.n) continue;
-        HIPC(hipMalloc((void **)&Fd.dst, dst.size() * sizeof(int)));
-        HIPC(hipMalloc((void **)&Fd.a, dst.size() * sizeof(int)));
-        HIPC(hipMalloc((void **)&Fd.b, dst.size() * sizeof(int)));
-        HIPC(hipMalloc((void **)&Fd.flip, dst.size()));
-        HIPC(hipMemcpy(Fd.dst, dst.data(), dst.size() * sizeof(int), hipMemcpyHostToDevice));
-        HIPC(hipMemcpy(Fd.a, a.data(), dst.size() * sizeof(int), hipMemcpyHostToDevice));
-        HIPC(hipMemcpy(Fd.b, bb.data(), dst.size() * sizeof(int), hipMemcpyHostToDevice));
-        HIPC(hipMemcpy(Fd.flip, flip.data(), dst.size(), hipMemcpyHostToDevice));
+        if (CG.mem.upload(Fd.dst, L.dst) || CG.mem.upload(Fd.a, L.a) || CG.mem.upload(Fd.b, L.b) || CG.mem.upload(Fd.flip, L.flip)) return -1;
     }
-    if (CG.fold_maxn) HIPC(hipMalloc((void **)&CG.fold_tmp, (size_t)4 * CG.fold_maxn * sizeof(double)));
+    if (CG.fold_maxn && CG.mem.alloc(CG.fold_tmp, (size_t)4 * CG.fold_maxn)) return -1;
+    return 0;
+}
+
+// ---- what the marched kernel (cg_strip) and the kernels beside it need, whichever schedule runs them ----
+static long interior_cells(const cice_evp_hip_dims &d)
+{
+    long n = 0;
+    for (int b = 0; b < d.nblocks; ++b) n += (long)(d.ihi[b] - d.ilo[b] + 1) * (d.jhi[b] - d.jlo[b] + 1);
+    return n;
+}
+// the kernel's 32-bit byte offsets span the static and the per-call table
+static bool strip_offsets_fit() { return (double)S.n * 8.0 * std::max((int)CG_NG, (int)CG_NIN) < 4294967296.0; }
+static int zeros(double *&p, size_t n) { return CG.mem.alloc(p, n, true); }      // a cleared array of doubles
+// the second allocations of uvelE, vvelN, stresspT, stressmT (stress12U's always exists)
+static int need_alt()
+{
+    for (int q = 0; q < 4; ++q)
+        if (!CG.alt[q] && zeros(CG.alt[q], S.n)) return -1;
+    return 0;
+}
+static int upload_items(const std::vector<int32_t> &items, int ex, int ey, int lengths, int seg, long cells)
+{
+    CGridState::One &O = CG.one;
+    O.nitems = (int)(items.size() / 6);
+    O.ex = ex; O.ey = ey;
+    O.strip_len = lengths;
+    O.strip_seg = seg;
+    O.strip_cells = cells;
+    return CG.mem.upload(O.items, items);
+}
+// the plan's per-cell bits and workgroup lists of nlev levels, nscr scratch arrays, the second buffers, the side stream
+static int upload_cell_lists(CellLists &Q, const std::vector<uint8_t> &cells, const std::vector<int32_t> *wg, int nlev, int nscr, long ncells)
+{
+    Q.ncells = ncells;
+    if (CG.mem.upload(Q.cells, cells)) return -1;
+    for (int k = 0; k < nlev; ++k) {
+        Q.nwg[k] = (int)wg[k].size();
+        if (CG.mem.upload(Q.wg[k], wg[k])) return -1;
+    }
+    for (int k = 0; k < nscr; ++k)
+        if (zeros(Q.scr[k], S.n)) return -1;
+    if (need_alt()) return -1;
+    HIPC(hipStreamCreateWithFlags(&CG.side.st, hipStreamNonBlocking));
+    HIPC(hipEventCreateWithFlags(&CG.side.fork, hipEventDisableTiming));
+    HIPC(hipEventCreateWithFlags(&CG.side.join, hipEventDisableTiming));
     return 0;
 }
 
@@ -716,18 +778,14 @@ static int build_one_tables(const double *const *static23)
     // workgroups (gx1: 462), 64x16 from there on -- the fewest recomputed positions and re-read rows per owned cell, which is
     // what counts once there are several windows per CU (720x270: 24.6 / 21.9 us with 32x8 / 64x16; 3600x2400: 1083 / 1032 /
     // 925 with 32x8 / 64x8 / 64x16).  CICE_EVP_HIP_CGRID_ONE_SHAPE=0 / 1 / 2 picks one
-    int shape = S.n > 160000 ? 2 : (S.n > 40000 ? 1 : 0);
-    if (const char *e = env_test("CICE_EVP_HIP_CGRID_ONE_SHAPE")) shape = std::min(2, std::max(0, std::atoi(e)));
+    const int shape = one_shape_switch(S.n > 160000 ? 2 : (S.n > 40000 ? 1 : 0));
     const int OX = shape ? 64 : 32, OY = shape == 2 ? 16 : 8;
     // Order of the windows = order of the workgroups on an XCD (each XCD takes a contiguous run of the list): row by row.
     // (Strips of a few windows in x, top to bottom, so that vertical neighbours run together and share their 2-3 common rows
     // in L2, were measured: 3600 x 2400 1083 us row by row, 1171 / 1139 / 1106 / 1082 in strips of 4 / 8 / 16 / 32 windows --
     // narrow strips cost more in DRAM locality than the shared rows save.  CICE_EVP_HIP_CGRID_ONE_STRIP=<n> for A/B.)
-    int strip = 1 << 20;
-    if (const char *e = env_test("CICE_EVP_HIP_CGRID_ONE_STRIP")) strip = std::max(1, std::atoi(e));
-    cice_evp_hip_dims d = S.d;
-    d.ilo = S.ilo.data(); d.ihi = S.ihi.data(); d.jlo = S.jlo.data(); d.jhi = S.jhi.data();
-    d.iglob0 = S.iglob0.data(); d.jglob0 = S.jglob0.data();
+    const int strip = one_strip_switch();
+    const cice_evp_hip_dims d = host_dims();
     std::vector<int32_t> tab, tiles;
     build_window_table(d, P, OX, OY, strip, tiles, tab);       // halo_plan.cpp (host only: CPU known-answer test)
     CGridState::One &O = CG.one;
@@ -737,31 +795,21 @@ static int build_one_tables(const double *const *static23)
         O.ox = OX;
         O.oy = OY;
         O.per_xcd = (O.ntiles + 7) / 8;
-        HIPC(hipMalloc((void **)&O.tab, tab.size() * sizeof(int)));
-        HIPC(hipMalloc((void **)&O.tiles, tiles.size() * sizeof(int32_t)));
-        HIPC(hipMemcpyAsync(O.tab, tab.data(), tab.size() * sizeof(int), hipMemcpyHostToDevice, S.stream));
-        HIPC(hipMemcpyAsync(O.tiles, tiles.data(), tiles.size() * sizeof(int32_t), hipMemcpyHostToDevice, S.stream));
-        for (auto &p : O.alt)
-            if (alloc_d(&p, S.n)) return -1;
-    }
-    if (!ranks && env_test("CICE_EVP_HIP_CGRID_PROF") && std::atoi(env_test("CICE_EVP_HIP_CGRID_PROF"))) {
-        HIPC(hipMalloc((void **)&O.prof, (size_t)O.ntiles * 8 * sizeof(unsigned long long)));
-        HIPC(hipMemsetAsync(O.prof, 0, (size_t)O.ntiles * 8 * sizeof(unsigned long long), S.stream));
+        if (CG.mem.upload(O.tab, tab) || CG.mem.upload(O.tiles, tiles) || need_alt()) return -1;
+        if (prof_on() && CG.mem.alloc(O.prof, (size_t)O.ntiles * 8, true)) return -1;
     }
     // ---- the marched kernel's share (cg_strip): per block the rectangle its regular windows cover, if they form one ----
     // default: large domains (the rectangle at least 300 000 cells and half of the rank's); CICE_EVP_HIP_CGRID_STRIP=0 / 1 (test
     // build) switches it off / on wherever a regular window exists, CICE_EVP_HIP_CGRID_STRIP_SEG=<rows> sets the segment length
     {
-        int want = shape == 2 ? 2 : 0;              // 2: auto
-        if (const char *e = env_test("CICE_EVP_HIP_CGRID_STRIP")) want = std::atoi(e) ? 1 : 0;
-        long interior = 0;
-        for (int b = 0; b < d.nblocks; ++b) interior += (long)(d.ihi[b] - d.ilo[b] + 1) * (d.jhi[b] - d.jlo[b] + 1);
-        if (want == 2 && interior < 300000) want = 0;
+        const int forced = strip_switch();
+        int want = forced != ENV_UNSET ? (forced ? 1 : 0) : shape == 2 ? 2 : 0;              // 2: auto
+        const long interior = interior_cells(d);
+        if (want == 2 && interior < STRIP_MIN_CELLS) want = 0;
         // the windows cg_one keeps beside the marched kernel -- a frame one window deep along the block's edges -- are cut
         // smaller than the ones it covers a whole domain with: 32 x 8 positions (29 x 5 owned), 256 threads, four workgroups per CU
         // in one round instead of two rounds of 1024-thread ones (3600 x 2400: the frame 51 us -> see DESIGN.md section 7)
-        int eshape = 0;
-        if (const char *e = env_test("CICE_EVP_HIP_CGRID_STRIP_EDGE")) eshape = std::min(2, std::max(0, std::atoi(e)));
+        const int eshape = strip_edge_switch();
         const int EX = eshape ? 64 : 32, EY = eshape == 2 ? 16 : 8;
         std::vector<int32_t> etiles, etab;
         if (want && (EX != OX || EY != OY)) {
@@ -774,18 +822,18 @@ static int build_one_tables(const double *const *static23)
         std::vector<Zone> zones;
         long zcells = 0;
         std::vector<uint8_t> in_zone((size_t)nt, 0);
-        if ((double)S.n * 8.0 * std::max((int)CG_NG, (int)CG_NIN) >= 4294967296.0) want = 0;     // (the kernel's 32-bit offsets into the tables)
+        if (!strip_offsets_fit()) want = 0;
         if (want) strip_zones(d, tiles, EX, EY, CG.h_img_slot.empty() ? nullptr : CG.h_img_slot.data(), zones);
         for (const Zone &z : zones) zcells += (long)(z.i1 - z.i0 + sx) * (z.j1 - z.j0 + sy);
         // (default: where the work items fill enough of the chip -- measured against cg_one alone: 720 x 270 23-48 us (segments of 4-16 rows)
         // against 22, 720 x 540 32 (8 rows) against 40, 1440 x 1080 95 against 154, 3600 x 2400 455-489 against 794)
-        if (want == 2 && (2 * zcells < interior || zcells < 300000)) zones.clear();
+        if (want == 2 && (2 * zcells < interior || zcells < STRIP_MIN_CELLS)) zones.clear();
         // The six lengths the reference's start-up forms from HTN (= dxN) and HTE (= dyE) -- dxU, dyU, dxT, dyT two-point means, dxE, dyN
         // four-point means (ice_grid.F90:3063-3280) -- checked BIT FOR BIT on every cell the marched kernel would form them for (each
         // rectangle with three columns and rows around it); where all hold the kernel forms them itself instead of loading them.  A
         // grid whose lengths were made otherwise (or a rectangle that reaches a row the reference extrapolates) keeps all eight loaded.
-        bool lengths = !zones.empty() && static23 != nullptr;
-        if (const char *e = env_test("CICE_EVP_HIP_CGRID_STRIP_LEN")) lengths = lengths && std::atoi(e) != 0;
+        const StripKnobs knobs = strip_knobs();
+        bool lengths = !zones.empty() && static23 != nullptr && knobs.want_len;
         if (lengths) {
             auto holds = [&](const Zone &z) { return strip_lengths_hold(z, EX, EY, static23); };
             // (a rectangle whose outermost window row reaches a row the reference extrapolates -- j = 1, j = ny_global -- gives that
@@ -816,15 +864,11 @@ static int build_one_tables(const double *const *static23)
             // 2950 x 48 597, 4720 x 30 603, 11741 x 12 624: one round of work, as long as possible.  Shortest segment: 16 rows from a
             // million cells -- 1440 x 1080: 1608 items of 16 rows 95 us, 1992 of 13 104 --, 8 below -- 720 x 540: 804 items of 8 rows
             // 32 us, 408 of 16 49)
-            long slots = 2048;
-            if (const char *e = env_test("CICE_EVP_HIP_CGRID_STRIP_ITEMS")) slots = std::max(1, std::atoi(e));
+            long slots = knobs.slots;
             // (several ranks, A/B: so many of the resident slots left to the frame's workgroups, which run beside the marched kernel)
-            if (ranks)
-                if (const char *e = env_test("CICE_EVP_HIP_CGRID_MARCH_RESERVE")) slots = std::max<long>(64, slots - std::max(0, std::atoi(e)));
-            int seg_forced = 0;
-            if (const char *e = env_test("CICE_EVP_HIP_CGRID_STRIP_SEG")) seg_forced = std::max(1, std::atoi(e));
+            if (ranks && knobs.reserve != ENV_UNSET) slots = std::max<long>(64, slots - std::max(0, knobs.reserve));
             std::vector<int32_t> items;
-            const int seg = strip_items(zones, EX, EY, lengths ? 3 : 2, slots, zcells >= 1000000 ? 16 : 8, seg_forced, items);
+            const int seg = strip_items(zones, EX, EY, lengths ? 3 : 2, slots, zcells >= 1000000 ? 16 : 8, knobs.seg_forced, items);
             strip_windows(zones, tiles, in_zone);
             std::vector<int32_t> tiles_e, tab_e;
             const size_t per = (size_t)EX * EY;
@@ -840,40 +884,13 @@ static int build_one_tables(const double *const *static23)
                 if (build_cg_frame(d, P, items, FP, why) != 1) return fail(-4, "C-grid EVP: %s", why.c_str());
                 tiles_e.clear();
                 tab_e.clear();
-                CGridState::Frame &Q = CG.fr;
-                Q.ncells = FP.frame_cells;
-                HIPC(hipMalloc((void **)&Q.cells, FP.cells.size()));
-                HIPC(hipMemcpy(Q.cells, FP.cells.data(), FP.cells.size(), hipMemcpyHostToDevice));
-                for (int k = 0; k < 3; ++k) {
-                    Q.nwg[k] = (int)FP.wg[k].size();
-                    HIPC(hipMalloc((void **)&Q.wg[k], std::max<size_t>(1, FP.wg[k].size()) * sizeof(int32_t)));
-                    HIPC(hipMemcpy(Q.wg[k], FP.wg[k].data(), FP.wg[k].size() * sizeof(int32_t), hipMemcpyHostToDevice));
-                }
-                for (auto &p : Q.scr)
-                    if (alloc_d(&p, S.n)) return -1;
-                for (auto &p : O.alt)
-                    if (alloc_d(&p, S.n)) return -1;
-                HIPC(hipStreamCreateWithFlags(&Q.st2, hipStreamNonBlocking));
-                HIPC(hipEventCreateWithFlags(&Q.fork, hipEventDisableTiming));
-                HIPC(hipEventCreateWithFlags(&Q.join, hipEventDisableTiming));
+                if (upload_cell_lists(CG.fr, FP.cells, FP.wg, 3, 4, FP.frame_cells)) return -1;
             }
-            O.nitems = (int)(items.size() / 6);
+            if (upload_items(items, EX, EY, lengths ? 1 : 0, seg, zcells)) return -1;
             O.ntiles_e = (int)(tiles_e.size() / 4);
-            O.ex = EX; O.ey = EY;
-            O.strip_len = lengths ? 1 : 0;
-            O.strip_seg = seg;
-            O.strip_cells = zcells;
-            HIPC(hipMalloc((void **)&O.items, items.size() * sizeof(int32_t)));
-            HIPC(hipMemcpy(O.items, items.data(), items.size() * sizeof(int32_t), hipMemcpyHostToDevice));
-            if (O.ntiles_e) {
-                HIPC(hipMalloc((void **)&O.tiles_e, tiles_e.size() * sizeof(int32_t)));
-                HIPC(hipMalloc((void **)&O.tab_e, tab_e.size() * sizeof(int32_t)));
-                HIPC(hipMemcpy(O.tiles_e, tiles_e.data(), tiles_e.size() * sizeof(int32_t), hipMemcpyHostToDevice));
-                HIPC(hipMemcpy(O.tab_e, tab_e.data(), tab_e.size() * sizeof(int32_t), hipMemcpyHostToDevice));
-            }
+            if (O.ntiles_e && (CG.mem.upload(O.tiles_e, tiles_e) || CG.mem.upload(O.tab_e, tab_e))) return -1;
         }
     }
-    HIPC(hipStreamSynchronize(S.stream));       // (the host vectors go out of scope)
     return 0;
 }
 
@@ -891,16 +908,13 @@ static int build_march_fold_tables(const double *const *static23)
         Q.why = "several ranks, or the fold rows not on this rank";
         return 0;
     }
-    if ((double)S.n * 8.0 * std::max((int)CG_NG, (int)CG_NIN) >= 4294967296.0) {
+    if (!strip_offsets_fit()) {
         Q.why = "the marched kernel's 32-bit offsets do not span the tables";
         return 0;
     }
-    cice_evp_hip_dims d = S.d;
-    d.ilo = S.ilo.data(); d.ihi = S.ihi.data(); d.jlo = S.jlo.data(); d.jhi = S.jhi.data();
-    d.iglob0 = S.iglob0.data(); d.jglob0 = S.jglob0.data();
-    long interior = 0;
-    for (int b = 0; b < d.nblocks; ++b) interior += (long)(d.ihi[b] - d.ilo[b] + 1) * (d.jhi[b] - d.jlo[b] + 1);
-    if (want == 2 && interior < 300000) {
+    const cice_evp_hip_dims d = host_dims();
+    const long interior = interior_cells(d);
+    if (want == 2 && interior < STRIP_MIN_CELLS) {
         Q.why = "fewer cells than the marched kernel's size rule asks for";
         return 0;
     }
@@ -920,16 +934,12 @@ static int build_march_fold_tables(const double *const *static23)
         }
     } geo;
     geo.g = static23;
-    long slots = 2048;
-    if (const char *e = env_test("CICE_EVP_HIP_CGRID_STRIP_ITEMS")) slots = std::max(1, std::atoi(e));
-    int seg_forced = 0, want_len = 1;
-    if (const char *e = env_test("CICE_EVP_HIP_CGRID_STRIP_SEG")) seg_forced = std::max(1, std::atoi(e));
-    if (const char *e = env_test("CICE_EVP_HIP_CGRID_STRIP_LEN")) want_len = std::atoi(e) != 0;
+    const StripKnobs knobs = strip_knobs();
     CgMarchFoldPlan FP;
-    const int rc = build_cg_march_fold(d, P, EX, EY, slots, 0, seg_forced, want_len, &geo, FP, Q.why);
+    const int rc = build_cg_march_fold(d, P, EX, EY, knobs.slots, 0, knobs.seg_forced, knobs.want_len ? 1 : 0, &geo, FP, Q.why);
     if (rc < 0) return fail(-4, "C-grid EVP: %s", Q.why.c_str());
     if (rc == 0) return 0;
-    Q.by_size = 2 * FP.zone_cells >= interior && FP.zone_cells >= 300000;
+    Q.by_size = 2 * FP.zone_cells >= interior && FP.zone_cells >= STRIP_MIN_CELLS;
     if (want == 2 && !Q.by_size) {
         Q.why = "the rectangles under the fold band are smaller than the marched kernel's size rule asks for";
         return 0;
@@ -940,31 +950,8 @@ static int build_march_fold_tables(const double *const *static23)
     std::string w;
     const std::vector<uint8_t> gm = derive_geometry_check(static23, w, true, &jmax);
     if (gm.empty()) return fail(-4, "C-grid EVP: fold-band plan: %s", w.c_str());
-    HIPC(hipMalloc((void **)&Q.gmask, S.n));
-    HIPC(hipMemcpy(Q.gmask, gm.data(), S.n, hipMemcpyHostToDevice));
-    HIPC(hipMalloc((void **)&Q.cells, FP.cells.size()));
-    HIPC(hipMemcpy(Q.cells, FP.cells.data(), FP.cells.size(), hipMemcpyHostToDevice));
-    for (int k = 0; k < 5; ++k) {
-        Q.nwg[k] = (int)FP.wg[k].size();
-        HIPC(hipMalloc((void **)&Q.wg[k], std::max<size_t>(1, FP.wg[k].size()) * sizeof(int32_t)));
-        HIPC(hipMemcpy(Q.wg[k], FP.wg[k].data(), FP.wg[k].size() * sizeof(int32_t), hipMemcpyHostToDevice));
-    }
-    for (auto &p : Q.scr)
-        if (alloc_d(&p, S.n)) return -1;
-    for (auto &p : CG.one.alt)
-        if (!p && alloc_d(&p, S.n)) return -1;
-    HIPC(hipStreamCreateWithFlags(&Q.st2, hipStreamNonBlocking));
-    HIPC(hipEventCreateWithFlags(&Q.fork, hipEventDisableTiming));
-    HIPC(hipEventCreateWithFlags(&Q.join, hipEventDisableTiming));
-    CGridState::One &O = CG.one;
-    O.nitems = (int)(FP.items.size() / 6);
-    O.ex = EX; O.ey = EY;
-    O.strip_len = FP.lengths;
-    O.strip_seg = FP.seg;
-    O.strip_cells = FP.zone_cells;
-    HIPC(hipMalloc((void **)&O.items, FP.items.size() * sizeof(int32_t)));
-    HIPC(hipMemcpy(O.items, FP.items.data(), FP.items.size() * sizeof(int32_t), hipMemcpyHostToDevice));
-    Q.ncells = FP.rest_cells;
+    if (CG.mem.upload(Q.gmask, gm) || upload_cell_lists(Q.rest, FP.cells, FP.wg, 5, 5, FP.rest_cells)) return -1;
+    if (upload_items(FP.items, EX, EY, FP.lengths, FP.seg, FP.zone_cells)) return -1;
     Q.band_rows = FP.band_rows;
     return 0;
 }
@@ -1000,9 +987,7 @@ static int build_res_tables(const double *const *static23)
             }
     }
     if (!Q.images_ok) return 0;
-    cice_evp_hip_dims d = S.d;
-    d.ilo = S.ilo.data(); d.ihi = S.ihi.data(); d.jlo = S.jlo.data(); d.jhi = S.jhi.data();
-    d.iglob0 = S.iglob0.data(); d.jglob0 = S.jglob0.data();
+    const cice_evp_hip_dims d = host_dims();
     if (tripole) {
         // The kernel's FOLD variant takes the operands of a cell beyond the fold from the cell it mirrors: every ghost cell of the row
         // NY+1 must hold, array by array, what the cell its field location maps it to holds (true of a grid whose static fields went
@@ -1042,10 +1027,7 @@ static int build_res_tables(const double *const *static23)
         // the land masks as bits, the boundary ratios' identities (the five-phase kernels of these grids load all 23 arrays: no gmask yet)
         const std::vector<uint8_t> gm = derive_geometry_check(static23, Q.why, false);
         if (gm.empty()) return 0;
-        HIPC(hipMalloc((void **)&Q.gmask, S.n));
-        HIPC(hipMemcpy(Q.gmask, gm.data(), S.n, hipMemcpyHostToDevice));
-        for (auto &p : CG.one.alt)
-            if (!p && alloc_d(&p, S.n)) return -1;
+        if (CG.mem.upload(Q.gmask, gm) || need_alt()) return -1;
     } else {
         build_window_table(d, P, RX, RY, 1 << 20, tiles, tab, 1);
     }
@@ -1101,32 +1083,15 @@ static int build_res_tables(const double *const *static23)
         }
         if (!Q.images_ok) return 0;
         Q.npairs = (int)pairs.size();
-        if (Q.npairs) {
-            HIPC(hipMalloc((void **)&Q.pairs, pairs.size() * sizeof(int2)));
-            HIPC(hipMemcpy(Q.pairs, pairs.data(), pairs.size() * sizeof(int2), hipMemcpyHostToDevice));
-        }
+        if (Q.npairs && CG.mem.upload(Q.pairs, pairs)) return -1;
     }
-    HIPC(hipMalloc((void **)&Q.tab, tab.size() * sizeof(int)));
-    HIPC(hipMalloc((void **)&Q.tiles, tiles.size() * sizeof(int32_t)));
-    HIPC(hipMalloc((void **)&Q.pubmap, S.n));
-    HIPC(hipMalloc((void **)&Q.rec, (size_t)EVP_CGRES_SLOTS * S.n * 32));
-    HIPC(hipMalloc((void **)&Q.err, 8 * sizeof(int)));
-    HIPC(hipMemcpy(Q.tab, tab.data(), tab.size() * sizeof(int), hipMemcpyHostToDevice));
-    HIPC(hipMemcpy(Q.tiles, tiles.data(), tiles.size() * sizeof(int32_t), hipMemcpyHostToDevice));
-    if (tripole) {
-        HIPC(hipMalloc((void **)&Q.tiles2, tiles2.size() * sizeof(int32_t)));
-        HIPC(hipMemcpy(Q.tiles2, tiles2.data(), tiles2.size() * sizeof(int32_t), hipMemcpyHostToDevice));
-    }
-    HIPC(hipMemcpy(Q.pubmap, pub.data(), S.n, hipMemcpyHostToDevice));
-    HIPC(hipMemset(Q.rec, 0, (size_t)EVP_CGRES_SLOTS * S.n * 32));
-    HIPC(hipMemset(Q.err, 0, 8 * sizeof(int)));
+    if (CG.mem.upload(Q.tab, tab) || CG.mem.upload(Q.tiles, tiles) || CG.mem.upload(Q.pubmap, pub)) return -1;
+    if (tripole && CG.mem.upload(Q.tiles2, tiles2)) return -1;
+    if (CG.mem.alloc(Q.rec, (size_t)EVP_CGRES_SLOTS * S.n * 32, true) || CG.mem.alloc(Q.err, 8, true)) return -1;
     {   // until the first upload says otherwise: every window runs
         std::vector<int> ident(Q.ntiles);
         for (int w = 0; w < Q.ntiles; ++w) ident[w] = w;
-        HIPC(hipMalloc((void **)&Q.d_order, ident.size() * sizeof(int)));
-        HIPC(hipMalloc((void **)&Q.live_win, ident.size() * sizeof(int)));
-        HIPC(hipMalloc((void **)&Q.live_cell, S.n));
-        HIPC(hipMemcpy(Q.d_order, ident.data(), ident.size() * sizeof(int), hipMemcpyHostToDevice));
+        if (CG.mem.upload(Q.d_order, ident) || CG.mem.alloc(Q.live_win, ident.size()) || CG.mem.alloc(Q.live_cell, S.n)) return -1;
         HIPC(hipMemset(Q.live_cell, 1, S.n));
         Q.n_live = Q.ntiles;
     }
@@ -1138,7 +1103,6 @@ static int build_res_tables(const double *const *static23)
 
 // eligible in this call: one rank, no fold (either visc_method, classic or revised EVP), the default-configuration shortcuts hold on every ice cell, the static
 // identities hold (the kernel takes -1 for a boundary ratio away from a coast), every window co-resident
-static bool res_cull() { return !(env_test("CICE_EVP_HIP_CGRID_RES_CULL") && !std::atoi(env_test("CICE_EVP_HIP_CGRID_RES_CULL"))); }
 // per_call (may be NULL): set when what stands in the way holds for THIS call only (the call's masks, operands, state)
 static bool res_eligible(std::string *why = nullptr, bool *per_call = nullptr)
 {
@@ -1161,15 +1125,15 @@ static bool res_eligible(std::string *why = nullptr, bool *per_call = nullptr)
     return true;
 }
 
-static int res_launch(const EvpCgrid &A, int nsub, bool dry, double *const cur5[5], double *const alt5[5])
+static int res_launch(const EvpCgrid &A, int nsub, bool dry, const PingPong &P)
 {
     CGridState::Res &Q = CG.res;
     EvpCgRes R{};
     R.tab = Q.tab; R.tiles = Q.tiles; R.order = nullptr; R.ntiles = Q.ntiles;
     R.tiles2 = Q.tiles2; R.fold = CG.tripole ? 1 : 0;
     R.slow = CG.fast ? 0 : 1;
-    R.long_sleep = env_test("CICE_EVP_HIP_CGRID_RES_SLEEP") && std::atoi(env_test("CICE_EVP_HIP_CGRID_RES_SLEEP")) ? 1 : 0;
-    R.dbg = env_test("CICE_EVP_HIP_CGRID_RES_DEBUG") ? std::atoi(env_test("CICE_EVP_HIP_CGRID_RES_DEBUG")) : 0;
+    R.long_sleep = res_sleep_on() ? 1 : 0;
+    R.dbg = res_debug();
     // the windows that hold ice in this call (finish_upload: cg_res_live); CICE_EVP_HIP_CGRID_RES_CULL=0 (test build) runs them all
     if (res_cull()) {
         R.order = Q.d_order; R.ntiles = Q.n_live; R.live = Q.live_cell;
@@ -1184,14 +1148,13 @@ static int res_launch(const EvpCgrid &A, int nsub, bool dry, double *const cur5[
     R.err = Q.err;
     R.pubmap = Q.pubmap;
     for (int k = 0; k < EVP_CGRES_SLOTS; ++k) R.rec[k] = (char *)Q.rec + (size_t)k * S.n * 32;
-    R.uE_in = cur5[0]; R.vN_in = cur5[1]; R.sp_in = cur5[2]; R.sm_in = cur5[3]; R.s12_in = cur5[4];
-    R.uE_out[0] = cur5[0]; R.uE_out[1] = alt5[0]; R.vN_out[0] = cur5[1]; R.vN_out[1] = alt5[1];
-    R.sp_out[0] = cur5[2]; R.sp_out[1] = alt5[2]; R.sm_out[0] = cur5[3]; R.sm_out[1] = alt5[3];
-    R.s12_out[0] = cur5[4]; R.s12_out[1] = alt5[4];
+    R.uE_in = P.cur[0]; R.vN_in = P.cur[1]; R.sp_in = P.cur[2]; R.sm_in = P.cur[3]; R.s12_in = P.cur[4];
+    R.uE_out[0] = P.cur[0]; R.uE_out[1] = P.alt[0]; R.vN_out[0] = P.cur[1]; R.vN_out[1] = P.alt[1];
+    R.sp_out[0] = P.cur[2]; R.sp_out[1] = P.alt[2]; R.sm_out[0] = P.cur[3]; R.sm_out[1] = P.alt[3];
+    R.s12_out[0] = P.cur[4]; R.s12_out[1] = P.alt[4];
     R.gbase = CG.gslab; R.inbase = CG.inslab; R.stride = S.n;
     R.gmask = CG.tripole ? Q.gmask : CG.gmask;
-    if (!dry && !Q.prof && env_test("CICE_EVP_HIP_CGRID_PROF") && std::atoi(env_test("CICE_EVP_HIP_CGRID_PROF")))
-        HIPC(hipMalloc((void **)&Q.prof, (size_t)Q.ntiles * 32 * sizeof(unsigned long long)));
+    if (!dry && !Q.prof && prof_on() && CG.mem.alloc(Q.prof, (size_t)Q.ntiles * 32)) return -1;
     R.prof = dry ? nullptr : Q.prof;
     evp_launch_cgrid_res(A, R, S.stream);
     HIPC(hipGetLastError());
@@ -1221,15 +1184,14 @@ static int res_decide(const EvpCgrid &A)
 {
     CGridState::Res &Q = CG.res;
     if (Q.mode >= 0) return 0;
-    int want = -1;
-    if (const char *e = env("CICE_EVP_HIP_CGRID_RESIDENT")) want = std::atoi(e);
+    const int want = resident_switch();
     std::string why;
     bool per_call = false;
     if (want == 0 || !res_eligible(&why, &per_call)) {
         // forced on: only what can never change (tables, geometry, rank layout) is an error; a condition of this call's masks,
         // operands or state is a fall-back for this call, as it is once the kernel has run (res_subcycles)
         if (want == 1 && !per_call) return fail(-6, "resident C-grid kernel requested but not applicable: %s", why.c_str());
-        if (env("CICE_EVP_HIP_VERBOSE") && want != 0) std::fprintf(stderr, "[cice_evp_hip] C grid: on-chip resident kernel not used: %s\n", why.c_str());
+        if (verbose() && want != 0) std::fprintf(stderr, "[cice_evp_hip] C grid: on-chip resident kernel not used: %s\n", why.c_str());
         // (per-call conditions -- visc_method, the shortcuts -- may hold in a later call: stay undecided unless switched off)
         if (want == 0) Q.mode = 0;
         return 0;
@@ -1238,21 +1200,20 @@ static int res_decide(const EvpCgrid &A)
         Q.mode = 1;
         return 0;
     }
-    double *cur5[5] = {CG.f[CF_UE], CG.f[CF_VN], CG.f[CF_SP], CG.f[CF_SM], CG.f[CF_S12U]};
-    double *alt5[5] = {CG.one.alt[0], CG.one.alt[1], CG.one.alt[2], CG.one.alt[3], CG.s12alt};
+    const PingPong P;
     const int nshort = 8, nlong = 40;
     float tl[2] = {0, 0}, ms = 0;
     for (int rep = 0; rep < 3; ++rep) {
         const int np = rep == 2 ? nlong : nshort;
         HIPC(hipEventRecord(S.ev2, S.stream));
-        if (int rc = res_launch(A, np, true, cur5, alt5)) return rc;
+        if (int rc = res_launch(A, np, true, P)) return rc;
         HIPC(hipEventRecord(S.ev3, S.stream));
         HIPC(hipStreamSynchronize(S.stream));
         if (res_check_error()) {
             if (want == 1) return -7;
             g_err.clear();
             Q.mode = 0;
-            if (env("CICE_EVP_HIP_VERBOSE")) std::fprintf(stderr, "[cice_evp_hip] C grid: on-chip resident kernel failed its probe, not used\n");
+            if (verbose()) std::fprintf(stderr, "[cice_evp_hip] C grid: on-chip resident kernel failed its probe, not used\n");
             return 0;
         }
         HIPC(hipEventElapsedTime(&ms, S.ev2, S.ev3));
@@ -1282,12 +1243,12 @@ std::string cgrid_schedule()
     }
     if (CG.geo && CG.uploaded && march_fold()) {
         std::snprintf(buf, sizeof buf, "C grid: marched zone + fold band, %d rows (%ld cells in %d items beside %ld cells of the band and the block edges, "
-                      "five phases and their fold steps)", CG.mf.band_rows, CG.one.strip_cells, CG.one.nitems, CG.mf.ncells);
+                      "five phases and their fold steps)", CG.mf.band_rows, CG.one.strip_cells, CG.one.nitems, CG.mf.rest.ncells);
         return buf;
     }
     if (CG.geo && CG.tripole && march_fold_wanted() == 1) {
         // asked for and not in use: say why
-        const char *w = remote() ? "several ranks" : !CG.mf.cells ? CG.mf.why.c_str() : (CG.uploaded && CG.avg_strength) ? "visc_method = avg_strength" : "";
+        const char *w = remote() ? "several ranks" : !CG.mf.rest.cells ? CG.mf.why.c_str() : (CG.uploaded && CG.avg_strength) ? "visc_method = avg_strength" : "";
         if (*w) {
             std::snprintf(buf, sizeof buf, "C grid: five phases + fold steps (marched zone + fold band not in use: %s)", w);
             return buf;
@@ -1320,19 +1281,17 @@ int cice_evp_hip_cgrid_set_geometry(const double *const *static23)
     // (the blocks next to the fold on several ranks: every exchanged array carries the staging slots of the fold exchange)
     const size_t nf = S.n + (tripole && P.cg_split ? (size_t)P.cg_tail : 0);
     for (auto &p : CG.f)
-        if (alloc_d(&p, nf)) return -1;
-    if (alloc_d(&CG.inslab, (size_t)CG_NIN * S.n) || alloc_d(&CG.gslab, (size_t)CG_NG * S.n)) return -1;
+        if (zeros(p, nf)) return -1;
+    if (zeros(CG.inslab, (size_t)CG_NIN * S.n) || zeros(CG.gslab, (size_t)CG_NG * S.n)) return -1;
     for (int k = 0; k < CG_NIN; ++k) CG.in[k] = CG.inslab + (size_t)k * S.n;
     for (int k = 0; k < CG_NG; ++k) {
         if (!static23[k]) return fail(-1, "null static array %d", k);
         CG.g[k] = CG.gslab + (size_t)k * S.n;
         if (h2d(CG.g[k], static23[k])) return -1;
     }
-    if (alloc_d(&CG.strengthU, S.n) || alloc_d(&CG.s12alt, S.n) || alloc_d(&CG.fac[0], S.n) || alloc_d(&CG.fac[1], S.n)) return -1;
-    HIPC(hipMalloc((void **)&CG.d_flags, sizeof(unsigned)));
-    if (remote() && alloc_d(&CG.umaskd, nf)) return -1;
-    HIPC(hipMalloc((void **)&CG.mask, S.n));
-    HIPC(hipMalloc((void **)&CG.mask4, 4 * S.n * sizeof(int32_t)));
+    if (zeros(CG.strengthU, S.n) || zeros(CG.alt[4], S.n) || zeros(CG.fac[0], S.n) || zeros(CG.fac[1], S.n)) return -1;
+    if (remote() && zeros(CG.umaskd, nf)) return -1;
+    if (CG.mem.alloc(CG.d_flags, 1) || CG.mem.alloc(CG.mask, S.n) || CG.mem.alloc(CG.mask4, 4 * S.n)) return -1;
     // ghost images: for every interior cell the ghost cells of this rank that mirror it (what ice_HaloUpdate copies)
     CG.h_img_slot.assign(S.n, -1);
     std::vector<int> dst, zero;
@@ -1359,10 +1318,7 @@ int cice_evp_hip_cgrid_set_geometry(const double *const *static23)
     }
     if (dst.empty()) dst.assign(3, -1);
     CG.h_img_dst = dst;
-    HIPC(hipMalloc((void **)&CG.img_slot, S.n * sizeof(int)));
-    HIPC(hipMalloc((void **)&CG.img_dst, dst.size() * sizeof(int)));
-    HIPC(hipMemcpyAsync(CG.img_slot, CG.h_img_slot.data(), S.n * sizeof(int), hipMemcpyHostToDevice, S.stream));
-    HIPC(hipMemcpyAsync(CG.img_dst, dst.data(), dst.size() * sizeof(int), hipMemcpyHostToDevice, S.stream));
+    if (CG.mem.upload(CG.img_slot, CG.h_img_slot) || CG.mem.upload(CG.img_dst, dst)) return -1;
     if (tripole && (P.fold_rows == 1 || P.cg_split))   // (ranks without the fold rows run the same schedule with empty lists)
         if (int rc = build_fold_lists()) return rc;
     if (!tripole && S.d.nx_block >= 3 && S.d.ny_block >= 3) {
@@ -1378,18 +1334,14 @@ int cice_evp_hip_cgrid_set_geometry(const double *const *static23)
     if (!tripole) {      // (the five-phase kernels of tripole grids always load all 23)
         const std::vector<uint8_t> gm = derive_geometry_check(static23, CG.geo_why);
         if (!gm.empty()) {
-            HIPC(hipMalloc((void **)&CG.gmask, S.n));
-            HIPC(hipMemcpy(CG.gmask, gm.data(), S.n, hipMemcpyHostToDevice));
-        } else if (env("CICE_EVP_HIP_VERBOSE")) {
+            if (CG.mem.upload(CG.gmask, gm)) return -1;
+        } else if (verbose()) {
             std::fprintf(stderr, "[cice_evp_hip] C grid: all 23 static arrays stay in use: %s\n", CG.geo_why.c_str());
         }
     }
     CG.n_zero = (int)zero.size();
-    if (CG.n_zero) {
-        HIPC(hipMalloc((void **)&CG.zero_cells, zero.size() * sizeof(int)));
-        HIPC(hipMemcpyAsync(CG.zero_cells, zero.data(), zero.size() * sizeof(int), hipMemcpyHostToDevice, S.stream));
-    }
-    HIPC(hipStreamSynchronize(S.stream));
+    if (CG.n_zero && CG.mem.upload(CG.zero_cells, zero)) return -1;
+    HIPC(hipStreamSynchronize(S.stream));       // (the static arrays are on their way from the caller's)
     CG.geo = true;
     return 0;
 }
@@ -1442,8 +1394,8 @@ int finish_upload(int32_t visc_method)
         HIPC(hipMemsetAsync(CG.d_flags, 0, sizeof(unsigned), S.stream));
         evp_launch_cgrid_call_setup(A, CG.fac[0], CG.fac[1], CG.d_flags, S.stream);
         if (CG.res.npairs) {
-            const double *five[5] = {CG.f[CF_UE], CG.f[CF_VN], CG.f[CF_SP], CG.f[CF_SM], CG.f[CF_S12U]};
-            evp_launch_cgrid_res_pair_check(five, CG.res.pairs, CG.res.npairs, CG.d_flags, S.stream);
+            const PingPong P;
+            evp_launch_cgrid_res_pair_check(P.cur, CG.res.pairs, CG.res.npairs, CG.d_flags, S.stream);
         }
         HIPC(hipMemcpyAsync(&h_flags, CG.d_flags, sizeof(unsigned), hipMemcpyDeviceToHost, S.stream));
         if (CG.res.tab) {        // which windows of the resident kernel hold ice in this call
@@ -1472,7 +1424,7 @@ int finish_upload(int32_t visc_method)
     }
     HIPC(hipGetLastError());
     HIPC(hipStreamSynchronize(S.stream));       // the caller may change its arrays after this returns
-    CG.fast = (h_flags & 255u) == 0 && !(env_test("CICE_EVP_HIP_CGRID_FAST") && !std::atoi(env_test("CICE_EVP_HIP_CGRID_FAST")));
+    CG.fast = (h_flags & 255u) == 0 && fast_switch();
     CG.res.pairs_state_ok = (h_flags & 256u) == 0;
     if (CG.res.tab) {
         CGridState::Res &Q = CG.res;
@@ -1504,17 +1456,21 @@ int cice_evp_hip_cgrid_subcycle(int32_t ndte)
     const int nres = (fused || CG.tripole) ? res_subcycles(ndte, CG.first) : 0;
     const bool mfold = nres == 0 && march_fold();
     const bool mf_sync = mfold && !CG.first && !CG.mf.synced;
+    Ran ran;
     auto enqueue = [&]() -> int {
-        if (fused) return enqueue_fused(A, ndte, CG.first, nres);
-        if (nres > 0) return enqueue_phases_resident(A, ndte, CG.first, nres);
-        if (mfold) return enqueue_march_fold(A, ndte, CG.first, mf_sync);
-        return enqueue_phases(A, ndte, CG.first);
+        if (fused) return enqueue_fused(A, ndte, CG.first, nres, ran);
+        if (nres > 0) return enqueue_phases_resident(A, ndte, CG.first, nres, ran);
+        if (mfold) return enqueue_march_fold(A, ndte, CG.first, mf_sync, ran);
+        return enqueue_phases(A, ndte, CG.first);      // (in place)
     };
     HIPC(hipEventRecord(S.ev0, S.stream));
     // (the resident launch carries a fresh epoch in its arguments: enqueued eagerly, with the few launches around it)
     if (nres == 0 && S.use_graph && (!remote() || S.direct.on)) {     // RCCL point-to-point is enqueued eagerly (as the B-grid loop does)
-        const std::pair<int, int> key(ndte, (mfold ? (march_fold_serial() ? 1536 : 512) | (mf_sync ? 2048 : 0) : 0) | (geo_derived() ? 128 : 0) | (fused && one_launch() ? 64 : 0) | (fused && march_ranks() ? 256 : 0) | (CG.one.flip << 5) | (CG.fast ? 16 : 0) | (CG.flip << 3) |
-                                                (fused ? 4 : 0) | (CG.first ? 2 : 0) | CG.avg_strength);
+        GraphKey key;
+        key.ndte = ndte; key.avg_strength = CG.avg_strength; key.in_alt = CG.in_alt;
+        key.first = CG.first; key.fused = fused; key.fast = CG.fast;
+        key.one = fused && one_launch(); key.geo = geo_derived(); key.march = fused && march_ranks();
+        key.mfold = mfold; key.mfold_serial = mfold && march_fold_serial(); key.mfold_sync = mf_sync;
         auto it = CG.graphs.find(key);
         if (it == CG.graphs.end()) {
             hipGraph_t gr = nullptr;
@@ -1525,33 +1481,23 @@ int cice_evp_hip_cgrid_subcycle(int32_t ndte)
             if (rc) return rc;
             HIPC(hipGraphInstantiate(&ex, gr, nullptr, nullptr, 0));
             (void)hipGraphDestroy(gr);
-            it = CG.graphs.emplace(key, ex).first;
+            it = CG.graphs.emplace(key, CGridState::Captured{ex, ran}).first;
         }
-        HIPC(hipGraphLaunch(it->second, S.stream));
+        HIPC(hipGraphLaunch(it->second.exec, S.stream));
+        ran = it->second.ran;
     } else if (enqueue()) {
         return -1;
     }
     CG.mf.synced = mfold;
-    if (mfold && (march_fold_count(ndte, CG.first) & 1)) {               // the current uvelE, vvelN, stresspT, stressmT, stress12U are in the other allocations now
-        for (int q = 0; q < 4; ++q) std::swap(CG.f[ONE_FIELDS[q]], CG.one.alt[q]);
-        std::swap(CG.f[CF_S12U], CG.s12alt);
-        CG.one.flip ^= 1;
-        CG.flip ^= 1;
-    }
-    if (fused && ((ndte - nres - ((CG.first && CG.avg_strength) ? 1 : 0)) & 1)) {   // the current stress12U is in the other allocation now
-        // (every subcycle swaps the two, except a first one run as five launches: visc_method = avg_strength)
-        std::swap(CG.f[CF_S12U], CG.s12alt);
-        CG.flip ^= 1;
-    }
-    if (fused && ((one_subcycles(ndte, CG.first) + march_subcycles(ndte, CG.first) - nres) & 1)) {      // and so are uvelE, vvelN, stresspT, stressmT
-        for (int q = 0; q < 4; ++q) std::swap(CG.f[ONE_FIELDS[q]], CG.one.alt[q]);
-        CG.one.flip ^= 1;
-    }
+    // the current arrays are where the schedule left them
+    for (int q = 0; q < 5; ++q)
+        if (ran.swapped >> q & 1u) std::swap(CG.f[PP_FIELDS[q]], CG.alt[q]);
+    CG.in_alt ^= ran.swapped;
     HIPC(hipEventRecord(S.ev1, S.stream));
     HIPC(hipGetLastError());
-    CG.t_one = fused ? one_subcycles(ndte, CG.first) - nres : 0;
-    CG.t_march = fused ? march_subcycles(ndte, CG.first) : 0;
-    CG.t_mfold = mfold ? march_fold_count(ndte, CG.first) : 0;
+    CG.t_one = ran.one;
+    CG.t_march = ran.march;
+    CG.t_mfold = ran.mfold;
     CG.res.last_nsub = nres;
     CG.first = false;
     CG.t_nsub = ndte;
@@ -1593,12 +1539,12 @@ int cice_evp_hip_cgrid_deformations(const double *tarear, double *divu, double *
         if (!p) return fail(-1, "null argument");
     if (!CG.tarear) {
         if (!tarear) return fail(-1, "tarear needed on the first call");
-        if (alloc_d(&CG.tarear, S.n)) return -1;
+        if (zeros(CG.tarear, S.n)) return -1;
     }
     if (tarear && h2d(CG.tarear, tarear)) return -1;
     CopyBatch U;
     for (int k = 0; k < 5; ++k) {
-        if (!CG.post[k] && alloc_d(&CG.post[k], S.n)) return -1;
+        if (!CG.post[k] && zeros(CG.post[k], S.n)) return -1;
         U.items.push_back({CG.post[k], host[k]});
     }
     if (h2d_batch(U)) return -1;
@@ -1625,7 +1571,7 @@ int cice_evp_hip_cgrid_dyn_finish(double *strocnxN, double *strocnyN, double *st
         if (!p) return fail(-1, "null argument");
     CopyBatch U;
     for (int k = 0; k < 4; ++k) {
-        if (!CG.post[k] && alloc_d(&CG.post[k], S.n)) return -1;
+        if (!CG.post[k] && zeros(CG.post[k], S.n)) return -1;
         U.items.push_back({CG.post[k], host[k]});
     }
     if (h2d_batch(U)) return -1;
@@ -1661,7 +1607,7 @@ int cice_evp_hip_cgrid_run(int32_t ndte, int32_t visc_method, double *const *fie
         // bounded, a launch that gives up writes nothing back and the download has not touched the caller's arrays: the call
         // is repeated from them with the per-subcycle kernels, which later calls use too (the verdict is kept).
         ++CG.res.fallbacks;
-        if (env("CICE_EVP_HIP_VERBOSE")) std::fprintf(stderr, "[cice_evp_hip] C grid: %s -- repeating the call without the resident kernel\n", g_err.c_str());
+        if (verbose()) std::fprintf(stderr, "[cice_evp_hip] C grid: %s -- repeating the call without the resident kernel\n", g_err.c_str());
         g_err.clear();
         if (cice_evp_hip_cgrid_upload(fields19, inputs23, iceTmask, iceUmask, iceEmask, iceNmask, visc_method)) return -1;
         if (cice_evp_hip_cgrid_subcycle(ndte)) return -1;
@@ -1684,7 +1630,7 @@ int cice_evp_hip_cgrid_set_prep_geometry(const int32_t *tmask, const int32_t *um
     CGridState::Prep &Q = CG.prep;
     std::vector<uint8_t> h8(S.n);
     auto B = [&](uint8_t *&p, const int32_t *src) -> int {
-        if (!p) HIPC(hipMalloc((void **)&p, S.n));
+        if (!p && CG.mem.alloc(p, S.n)) return -1;
         for (size_t k = 0; k < S.n; ++k) h8[k] = src[k] != 0;
         HIPC(hipMemcpy(p, h8.data(), S.n, hipMemcpyHostToDevice));
         return 0;
@@ -1692,19 +1638,14 @@ int cice_evp_hip_cgrid_set_prep_geometry(const int32_t *tmask, const int32_t *um
     if (B(Q.tmask, tmask) || B(Q.xmask[0], umaskCD) || B(Q.xmask[1], emask) || B(Q.xmask[2], nmask)) return -1;
     const double *fc[3] = {fcor_blk, fcorE_blk, fcorN_blk};
     for (int k = 0; k < 3; ++k)
-        if ((!Q.fcor[k] && alloc_d(&Q.fcor[k], S.n)) || h2d(Q.fcor[k], fc[k])) return -1;
+        if ((!Q.fcor[k] && zeros(Q.fcor[k], S.n)) || h2d(Q.fcor[k], fc[k])) return -1;
     for (auto &p : Q.t)
-        if (!p && alloc_d(&p, S.n)) return -1;
-    if ((!Q.tmass && alloc_d(&Q.tmass, S.n)) || (!Q.maskd && alloc_d(&Q.maskd, S.n))) return -1;
+        if (!p && zeros(p, S.n)) return -1;
+    if ((!Q.tmass && zeros(Q.tmass, S.n)) || (!Q.maskd && zeros(Q.maskd, S.n))) return -1;
     const HaloPlan &P = S.plan;
     Q.n_center = (int)P.center_dst.size();
     if (Q.n_center && !Q.c_dst) {
-        HIPC(hipMalloc((void **)&Q.c_dst, Q.n_center * sizeof(int32_t)));
-        HIPC(hipMalloc((void **)&Q.c_src, Q.n_center * sizeof(int32_t)));
-        HIPC(hipMalloc((void **)&Q.c_vsign, Q.n_center));
-        HIPC(hipMemcpy(Q.c_dst, P.center_dst.data(), Q.n_center * sizeof(int32_t), hipMemcpyHostToDevice));
-        HIPC(hipMemcpy(Q.c_src, P.center_src.data(), Q.n_center * sizeof(int32_t), hipMemcpyHostToDevice));
-        HIPC(hipMemcpy(Q.c_vsign, P.center_vsign.data(), Q.n_center, hipMemcpyHostToDevice));
+        if (CG.mem.upload(Q.c_dst, P.center_dst) || CG.mem.upload(Q.c_src, P.center_src) || CG.mem.upload(Q.c_vsign, P.center_vsign)) return -1;
     }
     // the loop's inputs persist between calls as the reference's module arrays do (a cell off the ice keeps e.g. its fmE)
     for (auto &p : CG.in) HIPC(hipMemsetAsync(p, 0, S.n * sizeof(double), S.stream));
@@ -1746,7 +1687,7 @@ int cice_evp_hip_cgrid_prep(const cice_evp_hip_prep_params *pp, const double *co
 #ifdef CICE_EVP_HIP_TESTING
         if (P.F.on)
             for (int k = 0; k < 4; ++k) {
-                if (!Q.prod[k] && alloc_d(&Q.prod[k], S.n)) return -1;
+                if (!Q.prod[k] && zeros(Q.prod[k], S.n)) return -1;
                 P.F.prod[k] = Q.prod[k];
             }
 #endif
@@ -1841,7 +1782,7 @@ int cice_evp_hip_cgrid_seabed_lkd(const double *hwater, double k1, double k2, do
     if (!Q.pending) return fail(-1, "no prepared C-grid state (cice_evp_hip_cgrid_prep first)");
     if (!Q.hwater) {
         if (!hwater) return fail(-1, "hwater needed on the first call");
-        if (alloc_d(&Q.hwater, S.n)) return -1;
+        if (zeros(Q.hwater, S.n)) return -1;
     }
     if (hwater && h2d(Q.hwater, hwater)) return -1;
     // aice, vice, hwater are read at (i+1, j) / (i, j+1) as the caller handed them over, ghost cells included -- the
@@ -1864,16 +1805,16 @@ int cice_evp_hip_cgrid_seabed_prob(const double *hwater, const double *aicen, co
     if (!aicen || !vicen || ncat < 1) return fail(-1, "bad argument");
     if (!Q.hwater) {
         if (!hwater) return fail(-1, "hwater needed on the first call");
-        if (alloc_d(&Q.hwater, S.n)) return -1;
+        if (zeros(Q.hwater, S.n)) return -1;
     }
     if (hwater && h2d(Q.hwater, hwater)) return -1;
     if (Q.ncat != ncat) {
-        if (Q.aicen) { (void)hipFree(Q.aicen); Q.aicen = nullptr; }
-        if (Q.vicen) { (void)hipFree(Q.vicen); Q.vicen = nullptr; }
-        if (alloc_d(&Q.aicen, S.n * (size_t)ncat) || alloc_d(&Q.vicen, S.n * (size_t)ncat)) return -1;
+        CG.mem.free_one(Q.aicen);
+        CG.mem.free_one(Q.vicen);
+        if (zeros(Q.aicen, S.n * (size_t)ncat) || zeros(Q.vicen, S.n * (size_t)ncat)) return -1;
         Q.ncat = ncat;
     }
-    if (!Q.tbt && alloc_d(&Q.tbt, S.n)) return -1;
+    if (!Q.tbt && zeros(Q.tbt, S.n)) return -1;
     HIPC(hipMemcpyAsync(Q.aicen, aicen, S.n * (size_t)ncat * sizeof(double), hipMemcpyHostToDevice, S.stream));
     HIPC(hipMemcpyAsync(Q.vicen, vicen, S.n * (size_t)ncat * sizeof(double), hipMemcpyHostToDevice, S.stream));
     EvpPrep PB{};
@@ -1981,7 +1922,7 @@ int cice_evp_hip_cgrid_timings(double *out, int32_t n)
     if (n >= 23) {
         out[20] = (double)CG.t_mfold;                 // subcycles of the last call that ran as "marched zone + fold band" (tripole grids, one rank)
         out[21] = (double)CG.mf.band_rows;            // ... rows from the zone's top row to the fold (0: no such plan here)
-        out[22] = (double)CG.mf.ncells;               // ... and the cells the five list-driven phase kernels advance
+        out[22] = (double)CG.mf.rest.ncells;               // ... and the cells the five list-driven phase kernels advance
     }
     return 0;
 }

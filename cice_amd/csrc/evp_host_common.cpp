@@ -36,6 +36,14 @@ int alloc_d(double **p, size_t n)
     return 0;
 }
 
+cice_evp_hip_dims host_dims()
+{
+    cice_evp_hip_dims d = S.d;
+    d.ilo = S.ilo.data(); d.ihi = S.ihi.data(); d.jlo = S.jlo.data(); d.jhi = S.jhi.data();
+    d.iglob0 = S.iglob0.data(); d.jglob0 = S.jglob0.data();
+    return d;
+}
+
 void free_all()
 {
     auto F = [](auto *&p) {

@@ -99,6 +99,9 @@ void march_free()
     S.march = State::March{};
 }
 
+// (test build) the ring between ranks as stores into HIP-IPC-mapped inboxes
+static bool march_direct_asked() { return env_on(env_test("CICE_EVP_HIP_MARCH_DIRECT"), false); }
+
 // Are the metric terms the one-subcycle kernels read from arrays (cxp, cyp, cxm, cym, dxhy, dyhx, deltaminEVP * tarea) what the
 // marching kernel derives from HTE, HTN, dxT, dyT (evp_cell.inc: metrics) on every T-cell of the global rows below `nrows`?  On a
 // tripole grid dxhy / dyhx carry mirrored values on the ghost row beyond the fold (evp_host_common.cpp: derive_metrics,
@@ -159,13 +162,14 @@ static bool march_geometry(std::string &why)
         return build_march_plan(d, own_max, wrap_inside, e, PL, FD.H);
     };
     // the rectangles of all ranks, this rank's strips and the exchange lists: the same verdict on every rank
-    const int own_max = env_test("CICE_EVP_HIP_MARCH_OWN") ? std::atoi(env_test("CICE_EVP_HIP_MARCH_OWN")) : EVP_MARCH_OWN;
-    const bool wrap_inside = !(env_test("CICE_EVP_HIP_MARCH_SELFX") && std::atoi(env_test("CICE_EVP_HIP_MARCH_SELFX")));
+    const int own_max = env_int(env_test("CICE_EVP_HIP_MARCH_OWN"), EVP_MARCH_OWN);
+    const bool wrap_inside = !env_on(env_test("CICE_EVP_HIP_MARCH_SELFX"), false);
     // cells a rank holds beyond its own on every side with a neighbour: the ring of ext + P cells is then exchanged every
     // (ext + P)-th subcycle only (march_plan.h); 4 = after every second pass of four.  (Rounds 4-5, two subcycles per pass and a
     // two-cell ring, 3600 x 2400 as 4x2 pieces, one-GPU rehearsal: 54.3 / 52.3 / 52.0 / 51.2 us per subcycle with ext 0 / 2 / 4 / 6
     // against 47.0 without any exchange.)
-    int ext = env_test("CICE_EVP_HIP_MARCH_EXT") ? std::max(0, std::atoi(env_test("CICE_EVP_HIP_MARCH_EXT")) & ~1) : -1;
+    const int ext_asked = env_int(env_test("CICE_EVP_HIP_MARCH_EXT"), ENV_UNSET);
+    int ext = ext_asked == ENV_UNSET ? -1 : std::max(0, ext_asked & ~1);
     if (ext >= 0) {
         if (!plan(ext, own_max, wrap_inside)) { why = PL.error; return false; }
     } else {
@@ -217,7 +221,8 @@ static bool march_geometry(std::string &why)
         }
         M.kpass = std::min(EVP_MARCH_KMAX, slmin >= 12 ? 4 : slmin >= 8 ? 3 : 2);
     }
-    if (env_test("CICE_EVP_HIP_MARCH_K")) M.kpass = std::min(EVP_MARCH_KMAX, std::max(2, std::atoi(env_test("CICE_EVP_HIP_MARCH_K"))));
+    const int k_asked = env_int(env_test("CICE_EVP_HIP_MARCH_K"), ENV_UNSET);
+    if (k_asked != ENV_UNSET) M.kpass = std::min(EVP_MARCH_KMAX, std::max(2, k_asked));
     if (PL.peers.size() > (size_t)EVP_MARCH_DIRECT_MAXPEER) { why = "more ring neighbours than the exchange lists hold"; return false; }
     if (!PL.peers.empty() && !S.have_comm && !S.test_xchg) { why = "cells of other ranks needed but no RCCL communicator (cice_evp_hip_comm_init)"; return false; }
     // The kernel derives every metric term from HTE, HTN, dxT, dyT.  A closed grid: tarea == dxT * dyT was verified on every cell
@@ -280,7 +285,7 @@ static bool march_geometry(std::string &why)
     if (M.nblk * EVP_MARCH_S_NF * 512 >= (1ull << 32)) { why = "state buffer beyond 32-bit byte offsets"; return false; }
     // segments: one wave per SIMD (1024 of them), all resident at once -- measured at 3600 x 2400: 16 segments (960
     // waves) 318 us per subcycle, 24 (1440: some SIMDs get two) 400, 34 (2040: two each) 378, 12 (720) 372
-    int seglen = env_test("CICE_EVP_HIP_MARCH_SEG") ? std::atoi(env_test("CICE_EVP_HIP_MARCH_SEG")) : 0;
+    int seglen = env_int(env_test("CICE_EVP_HIP_MARCH_SEG"), 0);
     if (seglen <= 0) {
         // (medium domains, 0.45M .. 1M cells: shorter segments keep the count near 1000 -- 1080 x 720: 14-row segments 39 us
         // per subcycle against 53 for the one-subcycle kernel; each segment recomputes ~3.5 rows of warm-up)
@@ -313,12 +318,7 @@ static int march_alloc()
     }
     if (!B.bad) HIPC(hipMalloc((void **)&B.bad, sizeof(unsigned)));
     if (!B.blkid) {
-        HIPC(hipMalloc((void **)&B.blkid, M.blkid_h.size() * sizeof(int)));
-        HIPC(hipMemcpy(B.blkid, M.blkid_h.data(), M.blkid_h.size() * sizeof(int), hipMemcpyHostToDevice));
-        HIPC(hipMalloc((void **)&B.org, M.org_h.size() * sizeof(int2)));
-        HIPC(hipMemcpy(B.org, M.org_h.data(), M.org_h.size() * sizeof(int2), hipMemcpyHostToDevice));
-        HIPC(hipMalloc((void **)&B.dup, M.dup_h.size() * sizeof(unsigned)));
-        HIPC(hipMemcpy(B.dup, M.dup_h.data(), M.dup_h.size() * sizeof(unsigned), hipMemcpyHostToDevice));
+        if (upload(B.blkid, M.blkid_h) || upload(B.org, M.org_h) || upload(B.dup, M.dup_h)) return -1;
     }
     if (PL.n_send + PL.n_recv > 0 && !B.sendbuf) {
         std::vector<int> sp, r1, r2, sm, rm;
@@ -331,12 +331,7 @@ static int march_alloc()
             for (size_t k = 0; k < p.recv_pos1.size(); ++k)
                 rm.push_back((int)((size_t)p.recv_row[k] * M.G.ldx + EVP_MARCH_PAD + p.recv_col[k]));
         }
-        auto up = [&](int *&dp, const std::vector<int> &v) -> int {
-            HIPC(hipMalloc((void **)&dp, std::max<size_t>(v.size(), 1) * sizeof(int)));
-            if (!v.empty()) HIPC(hipMemcpy(dp, v.data(), v.size() * sizeof(int), hipMemcpyHostToDevice));
-            return 0;
-        };
-        if (up(B.send_pos, sp) || up(B.recv_pos1, r1) || up(B.recv_pos2, r2) || up(B.send_midx, sm) || up(B.recv_midx, rm)) return -1;
+        if (upload(B.send_pos, sp) || upload(B.recv_pos1, r1) || upload(B.recv_pos2, r2) || upload(B.send_midx, sm) || upload(B.recv_midx, rm)) return -1;
         B.cut_send.n = B.cut_recv.n = (int)PL.peers.size();
         int cs = 0, cr = 0;
         for (size_t q = 0; q < PL.peers.size(); ++q) {
@@ -358,7 +353,7 @@ static int march_alloc()
             const int blk = pos >> 6, strip = blk % nstr, y = blk / nstr - EVP_MARCH_PAD;
             if (y >= 0 && y < M.G.nyr) rows[(size_t)strip][(size_t)y] = 1;
         }
-        int bseg = env_test("CICE_EVP_HIP_MARCH_BANDSEG") ? std::atoi(env_test("CICE_EVP_HIP_MARCH_BANDSEG")) : 0;
+        int bseg = env_int(env_test("CICE_EVP_HIP_MARCH_BANDSEG"), 0);
         if (bseg <= 0) bseg = std::max(6, M.seglen / 3);
         std::vector<int4> items;
         for (int st = 0; st < nstr; ++st)
@@ -370,10 +365,7 @@ static int march_alloc()
                 y = y1;
             }
         B.nband = (int)items.size();
-        if (B.nband > 0) {
-            HIPC(hipMalloc((void **)&B.band_items, items.size() * sizeof(int4)));
-            HIPC(hipMemcpy(B.band_items, items.data(), items.size() * sizeof(int4), hipMemcpyHostToDevice));
-        }
+        if (B.nband > 0 && upload(B.band_items, items)) return -1;
         std::vector<int4> rest;
         for (int st = 0; st < nstr; ++st)
             for (int y = 0; y < M.G.nyr;) {
@@ -384,10 +376,7 @@ static int march_alloc()
                 y = y1;
             }
         B.nrest = (int)rest.size();
-        if (B.nrest > 0) {
-            HIPC(hipMalloc((void **)&B.rest_items, rest.size() * sizeof(int4)));
-            HIPC(hipMemcpy(B.rest_items, rest.data(), rest.size() * sizeof(int4), hipMemcpyHostToDevice));
-        }
+        if (B.nrest > 0 && upload(B.rest_items, rest)) return -1;
         for (hipEvent_t *e : {&B.ev_in, &B.ev_main, &B.ev_done})
             if (!*e) HIPC(hipEventCreateWithFlags(e, hipEventDisableTiming));
     }
@@ -468,7 +457,7 @@ static int march_direct_setup()
     // pack kernel's uncached 8-byte stores take as long (13.4 us) as RCCL's pack + copy kernel (6.4 + 8.3) -- and what it does over
     // xGMI has never been measured; bench.py --gpus N times the 3600 x 2400 block this way too.
     {
-        const bool want = env_test("CICE_EVP_HIP_MARCH_DIRECT") && std::atoi(env_test("CICE_EVP_HIP_MARCH_DIRECT")) &&
+        const bool want = march_direct_asked() &&
                           !(env("CICE_EVP_HIP_HALO") && !std::strcmp(env("CICE_EVP_HIP_HALO"), "rccl"));
         unsigned no = want ? 0u : 1u;
         HIPC(hipMemcpyAsync(B.bad, &no, sizeof no, hipMemcpyHostToDevice, S.stream));
@@ -616,7 +605,7 @@ static int march_exchange(double *buf, double *buf2, int nf)
     // tests and bench.py's ring_variants set it in all processes alike.  Mutually exclusive with CICE_EVP_HIP_MARCH_OVERLAP
     // (the overlapped path ignores it).
     if (nf == EVP_MARCH_S_NF) {
-        const int asked = (env_test("CICE_EVP_HIP_MARCH_DIRECT") && std::atoi(env_test("CICE_EVP_HIP_MARCH_DIRECT"))) ? 1 : 0;
+        const int asked = march_direct_asked() ? 1 : 0;
         if (M.direct >= 0 && asked != M.direct_asked) {       // (bench.py times one state both ways: the switch changed between two calls)
             HIPC(hipStreamSynchronize(S.stream));
             for (void *m : B.dx_mapped) (void)hipIpcCloseMemHandle(m);
@@ -747,8 +736,7 @@ static int fold_tile_list(int variant, int *&list, int &count)
                 for (int bx = 0; bx < nbx; ++bx) t.push_back((b * gy + by) * gx + bx);      // row-major tile id
         }
         int *dl = nullptr;
-        HIPC(hipMalloc((void **)&dl, std::max<size_t>(t.size(), 1) * sizeof(int)));
-        if (!t.empty()) HIPC(hipMemcpy(dl, t.data(), t.size() * sizeof(int), hipMemcpyHostToDevice));
+        if (upload(dl, t)) return -1;
         it = B.fold_tiles.emplace(variant, std::make_pair(dl, (int)t.size())).first;
     }
     list = it->second.first;
@@ -858,7 +846,7 @@ static void march_args(EvpMarch &A, int cur, int last)
     A.wrapx = M.G.wrapx;
     A.last = last;
     A.kpass = M.kpass;
-    A.order = env_test("CICE_EVP_HIP_MARCH_ORDER") ? std::atoi(env_test("CICE_EVP_HIP_MARCH_ORDER")) : 1;
+    A.order = env_int(env_test("CICE_EVP_HIP_MARCH_ORDER"), 1);
     A.flags = S.flags & S.flags_allowed;
     A.mask = B.mask;
     A.st_in = B.st[cur]; A.st_out = B.st[cur ^ 1];
@@ -977,7 +965,7 @@ int march_run(int ndte)
     // can say whether hiding that is worth 6 us per subcycle.  bench.py --gpus N --extras ring_variants times both.
     const bool overlap = !PL.peers.empty() && B.nband > 0 && M.direct != 1 &&
                          env("CICE_EVP_HIP_MARCH_OVERLAP") && std::atoi(env("CICE_EVP_HIP_MARCH_OVERLAP")) &&
-                         !(env_test("CICE_EVP_HIP_MARCH_DIRECT") && std::atoi(env_test("CICE_EVP_HIP_MARCH_DIRECT")));
+                         !march_direct_asked();
     for (int k = 0; k < npass; ++k) {
         // the ring of the new state travels after this pass when the next one needs more valid cells than are left, and after the
         // last one (the way back to the block layout reads the ghost cells from it)

@@ -327,6 +327,72 @@ def test_cgrid_split_calls_equal_one_call():
         core.finalize()
 
 
+# schedule -> (environment, visc_method, subcycles per call, then per call: one_launch_subcycles, resident_subcycles).  The counters
+# are those the library gave before the schedules reported their own swaps (the commit before that change), run on the GPU.
+SPLIT_SCHEDULES = {
+    "five phases": ({"CICE_EVP_HIP_CGRID_FUSED": "0"}, "avg_zeta", (1, 2, 3, 1, 5), (0, 0, 0, 0, 0), (0, 0, 0, 0, 0)),
+    "three launches": ({"CICE_EVP_HIP_CGRID_ONE": "0"}, "avg_zeta", (1, 2, 3, 1, 5), (0, 0, 0, 0, 0), (0, 0, 0, 0, 0)),
+    "one launch": ({}, "avg_zeta", (1, 2, 3, 1, 5), (0, 2, 3, 1, 5), (0, 0, 0, 0, 0)),
+    "one launch, avg_strength": ({}, "avg_strength", (1, 2, 3, 1, 5), (0, 2, 3, 1, 5), (0, 0, 0, 0, 0)),
+    "marched": ({"CICE_EVP_HIP_CGRID_STRIP": "1"}, "avg_zeta", (1, 2, 3, 1, 5), (0, 2, 3, 1, 5), (0, 0, 0, 0, 0)),
+    "marched, last subcycle windowed": ({"CICE_EVP_HIP_CGRID_STRIP": "1", "CICE_EVP_HIP_CGRID_STRIP_LAST": "0"}, "avg_zeta",
+                                        (1, 2, 3, 1, 5), (0, 2, 3, 1, 5), (0, 0, 0, 0, 0)),
+    "resident": ({"CICE_EVP_HIP_CGRID_RESIDENT": "1"}, "avg_zeta", (4, 1, 2, 5), (0, 1, 2, 0), (3, 0, 0, 5)),
+}
+SPLIT_MARCHED_ITEMS = 15          # work items of the marched kernel on the 200 x 48 block (the other cases: none)
+
+
+@pytest.mark.parametrize("schedule", list(SPLIT_SCHEDULES))
+def test_cgrid_split_calls_per_schedule(schedule, monkeypatch):
+    """One upload, subcycle calls of 1, 2, 3, 1 and 5 -- odd and even counts after each state of the ping-pong buffers --, one
+    download: bit for bit what one call of 12 gives and what the oracle gives, on every one-rank schedule without a fold; and each
+    call reports the subcycles it ran per kind.  With the resident kernel (calls of 4, 1, 2, 5) resident and per-subcycle calls
+    alternate."""
+    env, visc, calls, want_one, want_res = SPLIT_SCHEDULES[schedule]
+    monkeypatch.setenv("CICE_EVP_HIP_CGRID_RESIDENT", "0")
+    marched = schedule.startswith("marched")
+    if marched:
+        monkeypatch.setenv("CICE_EVP_HIP_CGRID_ONE_SHAPE", "2")
+    for k, v in env.items():
+        monkeypatch.setenv(k, v)
+    if marched:       # the smallest shape at which a zone forms: one block of 200 x 48, cyclic
+        from cice_amd import synth
+        dc, _, static, state, inputs, masks = marched_case(77, 200, 48, (200, 48), "full", 0.2, 0.02, ew="cyclic", ns="cyclic")
+        scal = synth.evp_scalars(120)
+        blks = dc.local_blocks(0)
+        dom = oracle.OracleDomain(dc.nx_block, dc.ny_block, len(blks), dc.nx_global, dc.ny_global, dc.ew, dc.ns,
+                                  [b.ilo for b in blks], [b.ihi for b in blks], [b.jlo for b in blks],
+                                  [b.jhi for b in blks], [b.gi0 for b in blks], [b.gj0 for b in blks])
+        prm = oracle.make_params(**{k: scal[k] for k in ("arlx1i", "denom1", "brlx", "revp", "e_factor", "epp2i", "capping",
+                                                          "Ktens", "deltaminEVP", "u0", "cosw", "sinw", "rhow")})
+        d, keep = evp.make_dims(dc, 0)
+        core = evp.EvpHip(d, evp.make_params(scal, strict=True), static["dyE"], static["dxN"], static["dxT"], static["dyT"],
+                          1.0 / static["uarea"], static["tarea"], keepalive=keep)
+        core.cgrid_set_geometry(static)
+    else:
+        c = GoldenCase("cgrid_cyc_2x2_patchy")
+        dom, prm, static = c.oracle_domain(), c.oracle_params(), c.cgrid_static()
+        state, inputs, masks = c.cgrid_inputs(1)
+        core = cgrid_core(c)
+    try:
+        core.cgrid_upload(state, inputs, masks, visc_method=visc)
+        seen = []
+        for n in calls:
+            core.cgrid_subcycle(n)
+            t = core.cgrid_timings()
+            seen.append((t["nsub"], t["one_launch_subcycles"], t["marched_items"], t["resident_subcycles"], t["marched_fold_subcycles"]))
+        out = core.cgrid_download()
+        print(f"split calls, {schedule}: (nsub, one launch, marched items, resident, marched fold) per call {seen}")
+        one_call = core.cgrid_run(sum(calls), state, inputs, masks, visc_method=visc)
+    finally:
+        core.finalize()
+    assert_bitwise(out, one_call, f"split calls against one call, {schedule}")
+    assert_bitwise(out, oracle.cgrid_subcycle(dom, prm, sum(calls), state, inputs, static, masks, visc_method=visc),
+                   f"split calls against the oracle, {schedule}")
+    items = SPLIT_MARCHED_ITEMS if marched else 0
+    assert seen == [(n, o, items, r, 0) for n, o, r in zip(calls, want_one, want_res)], seen
+
+
 def test_cgrid_fails_loudly_without_geometry():
     c = GoldenCase("trip_cyc_1blk_patchy")
     d, keep = c.hip_dims()
