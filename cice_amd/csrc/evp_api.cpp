@@ -87,14 +87,9 @@ int cice_evp_hip_cgrid_strip_plan(const cice_evp_hip_dims *dims, int32_t ex, int
     if (!dims || !n_items || !n_windows) return fail(-1, "bad argument");
     HaloPlan P;
     if (!build_halo_plan(*dims, P)) return fail(-3, "halo plan: %s", P.error.c_str());
-    std::vector<int32_t> t4, tb, it;
-    build_window_table(*dims, P, ex, ey, 1 << 20, t4, tb);
-    // (ghost images: the sources of the rank's own ghost copies)
-    std::vector<int> img((size_t)dims->nblocks * dims->nx_block * dims->ny_block, -1);
-    for (size_t k = 0; k < P.local_src.size(); ++k)
-        if (P.local_src[k] >= 0) img[(size_t)P.local_src[k]] = 0;        // (-1: a ghost cell filled with 0, no source)
+    std::vector<int32_t> t4, it;
     std::vector<StripZone> zones;
-    strip_zones(*dims, t4, ex, ey, img.data(), zones);
+    plan_strip_zones(*dims, P, ex, ey, 62, STRIP_EVERY_IMAGE, t4, zones);
     const int s = strip_items(zones, ex, ey, lo0, slots, seg_min, seg, it);
     std::vector<uint8_t> in;
     strip_windows(zones, t4, in);
@@ -117,13 +112,9 @@ int cice_evp_hip_cgrid_strip_zones(const cice_evp_hip_dims *dims, int32_t ex, in
     if (!dims || !n_zones) return fail(-1, "bad argument");
     HaloPlan P;
     if (!build_halo_plan(*dims, P)) return fail(-3, "halo plan: %s", P.error.c_str());
-    std::vector<int32_t> t4, tb;
-    build_window_table(*dims, P, ex, ey, 1 << 20, t4, tb);
-    std::vector<int> img((size_t)dims->nblocks * dims->nx_block * dims->ny_block, -1);
-    for (size_t k = 0; k < P.local_src.size(); ++k)
-        if (P.local_src[k] >= 0) img[(size_t)P.local_src[k]] = 0;
+    std::vector<int32_t> t4;
     std::vector<StripZone> zones;
-    strip_zones(*dims, t4, ex, ey, img.data(), zones);
+    plan_strip_zones(*dims, P, ex, ey, 62, STRIP_EVERY_IMAGE, t4, zones);
     *n_zones = (int32_t)zones.size();
     if (!zones10) return 0;
     if ((size_t)zones_cap < zones.size()) return fail(-1, "room for %d rectangles, there are %d", zones_cap, *n_zones);
@@ -142,13 +133,9 @@ int cice_evp_hip_cgrid_frame_plan(const cice_evp_hip_dims *dims, int32_t ex, int
     if (!dims || !info6) return fail(-1, "bad argument");
     HaloPlan P;
     if (!build_halo_plan(*dims, P)) return fail(-3, "halo plan: %s", P.error.c_str());
-    std::vector<int32_t> t4, tb, it;
-    build_window_table(*dims, P, ex, ey, 1 << 20, t4, tb);
-    std::vector<int> img((size_t)dims->nblocks * dims->nx_block * dims->ny_block, -1);
-    for (size_t k = 0; k < P.local_src.size(); ++k)
-        if (P.local_src[k] >= 0) img[(size_t)P.local_src[k]] = 0;
+    std::vector<int32_t> t4, it;
     std::vector<StripZone> zones;
-    strip_zones(*dims, t4, ex, ey, img.data(), zones);
+    plan_strip_zones(*dims, P, ex, ey, 62, STRIP_EVERY_IMAGE, t4, zones);
     if (!zones.empty()) strip_items(zones, ex, ey, lo0, slots, seg_min, seg, it);
     CgFramePlan F;
     std::string why;
@@ -156,7 +143,7 @@ int cice_evp_hip_cgrid_frame_plan(const cice_evp_hip_dims *dims, int32_t ex, int
     if (rc < 0) return fail(-5, "%s", why.c_str());
     for (int k = 0; k < 6; ++k) info6[k] = 0;
     if (rc == 0) return 1;                                    // declined: one rank
-    info6[0] = F.zone_cells; info6[1] = F.frame_cells;
+    info6[0] = F.zone_cells; info6[1] = F.rest_cells;
     for (int k = 0; k < 3; ++k) info6[2 + k] = (int64_t)F.wg[k].size();
     info6[5] = (int64_t)(it.size() / 6);
     if (cells) std::copy(F.cells.begin(), F.cells.end(), cells);

@@ -193,7 +193,7 @@ __device__ __forceinline__ Cell cell_of_wg(const EvpCgrid &A, int id)
     c.o = (size_t)c.b * A.plane + (size_t)(c.j - 1) * A.nx + (c.i - 1);
     return c;
 }
-// An array as the frame kernels read it: on a zone cell (bit 8 of the plan's byte) the value lives in the frame's scratch copy d --
+// An array as the frame kernels read it: on a zone cell (EVP_CGS_ZONE in the plan's byte) the value lives in the frame's scratch copy d --
 // the array itself belongs to the marched kernel there, which runs at the same time.  FRAME = false: the array, nothing else.
 template <bool FRAME>
 struct ZArr {
@@ -201,7 +201,7 @@ struct ZArr {
     const uint8_t *cells;
     __device__ __forceinline__ double operator[](size_t p) const
     {
-        if (FRAME) return ((cells[p] & 8u) ? d : a)[p];
+        if (FRAME) return ((cells[p] & EVP_CGS_ZONE) ? d : a)[p];
         return a[p];
     }
 };
@@ -277,22 +277,22 @@ __device__ __forceinline__ double shear_u(const EvpCgrid &A, const GT &G, size_t
 }
 
 // grid_average_X2YA at cell p (ice_grid.F90:4388-4606): 'NW' (E -> N), 'SE' (N -> E), 'N' (E -> U), 'E' (N -> U)
-template <class P, class W>
-__device__ __forceinline__ double avg_nw(const P &a, const W &w, size_t p, int nx)
+template <class W>
+__device__ __forceinline__ double avg_nw(const double *a, const W &w, size_t p, int nx)
 {
     const double wtmp = (w[p - 1] + w[p] + w[p + nx - 1] + w[p + nx]);
     if (wtmp == 0.0) return 0.0;
     return (a[p - 1] * w[p - 1] + a[p] * w[p] + a[p + nx - 1] * w[p + nx - 1] + a[p + nx] * w[p + nx]) / wtmp;
 }
-template <class P, class W>
-__device__ __forceinline__ double avg_se(const P &a, const W &w, size_t p, int nx)
+template <class W>
+__device__ __forceinline__ double avg_se(const double *a, const W &w, size_t p, int nx)
 {
     const double wtmp = (w[p - nx] + w[p - nx + 1] + w[p] + w[p + 1]);
     if (wtmp == 0.0) return 0.0;
     return (a[p - nx] * w[p - nx] + a[p - nx + 1] * w[p - nx + 1] + a[p] * w[p] + a[p + 1] * w[p + 1]) / wtmp;
 }
-template <class P, class W>
-__device__ __forceinline__ double avg_2(const P &a, const W &w, size_t p, size_t q)
+template <class W>
+__device__ __forceinline__ double avg_2(const double *a, const W &w, size_t p, size_t q)
 {
     const double wtmp = (w[p] + w[q]);
     if (wtmp == 0.0) return 0.0;
@@ -305,16 +305,16 @@ __device__ __forceinline__ double avg_2(const P &a, const W &w, size_t p, size_t
 // ghost weights. ----
 // FRAME (here and in the two kernels below): the variant that runs beside the marched kernel on a rank with neighbours on other ranks
 // (EvpCgFrame).  The same arithmetic; the five ping-pong arrays are read from the previous subcycle's buffers and written to this
-// subcycle's on FRAME cells only (flag 1); a zone cell evaluated because a frame cell reads its shearU (flag 2 without 1) stores it to
+// subcycle's on FRAME cells only (EVP_CGS_REST); a zone cell evaluated because a frame cell reads its shearU (EVP_CGS_S without it) stores it to
 // the scratch array and nothing else.
 template <bool GEO, bool FRAME>
 __device__ __forceinline__ void avg_strain_cell(const EvpCgrid &A, const EvpCgFrame &F, const Cell &c, int last)
 {
     const size_t o = c.o, e = o + 1, n = o + A.nx;
     const unsigned m = A.mask[o];
-    const unsigned fl = FRAME ? F.cells[o] : 1u;
-    if (FRAME && !(fl & 2u)) return;
-    const bool mine = (fl & 1u) != 0;
+    const unsigned fl = FRAME ? F.cells[o] : EVP_CGS_REST;
+    if (FRAME && !(fl & EVP_CGS_S)) return;
+    const bool mine = (fl & EVP_CGS_REST) != 0;
     const auto G = AGeo<GEO>::make(A);
     const double *uE = FRAME ? F.uE_in : A.f[CF_UE], *vN = FRAME ? F.vN_in : A.f[CF_VN];
     const auto ea = G[CG_EAREA], na = G[CG_NAREA];
@@ -365,23 +365,23 @@ __global__ __launch_bounds__(TX *TY) void cg_frame_strain(EvpCgrid A, EvpCgFrame
 
 // BAND (here and in the four phase kernels below): the list-driven variant that runs on the REST of a tripole grid beside the marched
 // kernel (EvpCgBand; halo_plan.h: build_cg_march_fold).  The same arithmetic; the five ping-pong arrays are read from the previous
-// subcycle's buffers and written to this subcycle's on REST cells only (flag 1; without ice: the previous value taken along); a zone
+// subcycle's buffers and written to this subcycle's on REST cells only (EVP_CGS_REST; without ice: the previous value taken along); a zone
 // cell evaluated because a REST cell reads its shearU / etax2T / stresspT / stressmT / stress12U stores it to the scratch array only.
 template <bool BAND>
 __device__ __forceinline__ void strain_u_cell(const EvpCgrid &A, const EvpCgBand &B, const Cell &c)
 {
     const size_t o = c.o, e = o + 1, n = o + A.nx;
     const unsigned m = A.mask[o];
-    const unsigned fl = BAND ? B.cells[o] : 1u;
-    if (BAND && !(fl & 2u)) return;
-    const bool mine = (fl & 1u) != 0;
+    const unsigned fl = BAND ? B.cells[o] : EVP_CGS_REST;
+    if (BAND && !(fl & EVP_CGS_S)) return;
+    const bool mine = (fl & EVP_CGS_REST) != 0;
     if (!(m & 2u)) {
         // strain_rates_U zero-fills shearU before computing the ice cells; on a tripole grid the fold step of the
         // previous subcycle may have stored an average into a fold-row cell without ice
         // (BAND: only there -- below row NY a cell without ice holds the zero of the first subcycle, and the marched kernel reads it)
         if (BAND) {
             if (!mine) B.sh[o] = A.f[CF_SHEARU][o];
-            else if (fl & 64u) A.f[CF_SHEARU][o] = 0.0;
+            else if (fl & EVP_CGS_FOLDROW) A.f[CF_SHEARU][o] = 0.0;
         } else if (A.tripole) {
             A.f[CF_SHEARU][o] = 0.0;
         }
@@ -435,7 +435,7 @@ __device__ __forceinline__ void stress_t_cell(const EvpCgrid &A, const FT &F, co
     const size_t o = c.o, w = o - 1, s = o - A.nx, sw = s - 1;
     const unsigned m = A.mask[o];
     const unsigned fl = FRAME ? F.cells[o] : 0u;
-    if (FRAME && !(fl & 4u)) return;
+    if (FRAME && !(fl & EVP_CGS_T)) return;
     const bool own = c.i <= c.q.y && c.j <= c.q.w;
     const double *uE = FRAME ? F.uE_in : A.f[CF_UE], *vN = FRAME ? F.vN_in : A.f[CF_VN];
     const double *sp_in = FRAME ? F.sp_in : A.f[CF_SP], *sm_in = FRAME ? F.sm_in : A.f[CF_SM];
@@ -456,7 +456,7 @@ __device__ __forceinline__ void stress_t_cell(const EvpCgrid &A, const FT &F, co
     const double s12 = (A.f[CF_S12T][o] * relax + A.p.arlx1i * 0.5 * etax2 * shearT) * A.p.denom1;
     const double sp = (sp_in[o] * relax + A.p.arlx1i * (zetax2 * divT - rep_prs)) * A.p.denom1;
     const double sm = (sm_in[o] * relax + A.p.arlx1i * etax2 * tensionT) * A.p.denom1;
-    if (FRAME && (fl & 8u)) {
+    if (FRAME && (fl & EVP_CGS_ZONE)) {
         // a zone cell a frame cell reads etax2T, stresspT or stressmT of: to the scratch arrays only (a cell without ice keeps what the
         // arrays hold -- nobody writes them there during a call); stress12T and the arrays themselves are the marched kernel's here
         const bool ice = (m & 1u) != 0;
@@ -466,7 +466,7 @@ __device__ __forceinline__ void stress_t_cell(const EvpCgrid &A, const FT &F, co
         return;
     }
     if (!(m & 1u)) {                             // loads above are unconditional (in bounds), stores are not
-        if (BAND && own && (fl & 1u)) {          // (this subcycle's buffers: the previous values taken along)
+        if (BAND && own && (fl & EVP_CGS_REST)) {          // (this subcycle's buffers: the previous values taken along)
             A.f[CF_SP][o] = sp_in[o];
             A.f[CF_SM][o] = sm_in[o];
         }
@@ -522,9 +522,9 @@ __device__ __forceinline__ void stress_u_cell(const EvpCgrid &A, const EvpCgBand
 {
     const size_t o = c.o;
     const unsigned m = A.mask[o];
-    const unsigned fl = BAND ? B.cells[o] : 1u;
-    if (BAND && !(fl & 16u)) return;
-    const bool mine = (fl & 1u) != 0;
+    const unsigned fl = BAND ? B.cells[o] : EVP_CGS_REST;
+    if (BAND && !(fl & EVP_CGS_U)) return;
+    const bool mine = (fl & EVP_CGS_REST) != 0;
     const double *s12_in = BAND ? B.s12_in : A.f[CF_S12U];
     double etax2U;
     if (!BAND && A.avg_strength) {               // (BAND: visc_method = avg_zeta only)
@@ -566,7 +566,7 @@ __device__ __forceinline__ void step_cell(const EvpCgrid &A, const EvpCgBand &B,
 {
     constexpr bool FAST = false;      // (the shortcuts live in the fused schedule's cg_stress_u_step<true>)
     const size_t o = c.o, e = o + 1, n = o + A.nx, s = o - A.nx, w = o - 1;
-    if (BAND && !(B.cells[o] & 1u)) return;      // the REST cells only: nothing reads this phase of a neighbour within a subcycle
+    if (BAND && !(B.cells[o] & EVP_CGS_REST)) return;      // the REST cells only: nothing reads this phase of a neighbour within a subcycle
     const unsigned m = A.mask[o];
     const double *uE_old = BAND ? B.uE_in : A.f[CF_UE], *vN_old = BAND ? B.vN_in : A.f[CF_VN];
     if (BAND) {                                  // (this subcycle's buffers: the previous values taken along)
@@ -661,7 +661,7 @@ __device__ __forceinline__ void stress_u_step_cell(const EvpCgrid &A, const EvpC
 {
     const auto G = AGeo<GEO>::make(A);
     const size_t o = c.o, e = o + 1, n = o + A.nx, s = o - A.nx, w = o - 1;
-    if (FRAME && !(F.cells[o] & 1u)) return;     // the frame cells only: nothing reads this level of a neighbour
+    if (FRAME && !(F.cells[o] & EVP_CGS_REST)) return;     // the frame cells only: nothing reads this level of a neighbour
     const unsigned m = A.mask[o];
     const double relax = 1.0 - A.p.arlx1i * A.p.revp;
     // blockDim.z == 2: the E face and the N face of a cell in different waves (half the dependent chain per wave, twice
@@ -805,7 +805,7 @@ template <bool BAND>
 __device__ __forceinline__ void average_cell(const EvpCgrid &A, const EvpCgBand &B, const Cell &c)
 {
     const size_t o = c.o, e = o + 1, n = o + A.nx, s = o - A.nx, w = o - 1;
-    if (BAND && !(B.cells[o] & 32u)) return;
+    if (BAND && !(B.cells[o] & EVP_CGS_AVG)) return;
     const unsigned m = A.mask[o];
     const double *uE = A.f[CF_UE], *vN = A.f[CF_VN], *ea = A.g[CG_EAREA], *na = A.g[CG_NAREA];
     const double eo = ea[o], no = na[o], uo = uE[o], vo = vN[o];
@@ -1094,74 +1094,6 @@ __global__ void cg_zero_cells(EvpCgrid A, const int *cells, int n)
 // no exchange overwrites) is kept up by the workgroup that owns the neighbouring interior cell, with the ghost cell's own
 // metrics and history.
 // =====================================================================
-// The marched kernel's views (cg_strip): an array = a wave-uniform base + a 32-bit byte offset per lane, so that ONE register per
-// lane (the cell's offset) addresses every array -- in a loop over rows the compiler otherwise keeps a 64-bit per-lane address for
-// each of the ~50 arrays (250 registers, two waves per SIMD).  The tables (23 x n, 23 x n doubles) must end below 4 GB: the host checks.
-struct P32 {
-    const char *base;
-    __device__ __forceinline__ double operator[](size_t i) const { return *(const double *)(base + (size_t)((unsigned)i * 8u)); }
-};
-struct P32W {
-    char *base;
-    __device__ __forceinline__ double &operator[](size_t i) const { return *(double *)(base + (size_t)((unsigned)i * 8u)); }
-};
-struct P32K {      // array k of a table: base + (k * stride + i) * 8, the sum in 32 bits
-    const char *base;
-    unsigned koff;
-    __device__ __forceinline__ double operator[](size_t i) const { return *(const double *)(base + (size_t)((unsigned)i * 8u + koff)); }
-};
-struct Slab32 {
-    static constexpr bool derived = false;
-    const char *base;
-    unsigned stride8;
-    __device__ __forceinline__ P32K operator[](int k) const { return P32K{base, (unsigned)k * stride8}; }
-};
-struct DSlab32 {   // DSlab with 32-bit offsets
-    static constexpr bool derived = true;
-    const char *base;
-    unsigned stride8;
-    const uint8_t *gm;
-    int nx;
-    double dmin;
-    struct Acc {
-        const DSlab32 &S;
-        int k;
-        __device__ __forceinline__ double raw(int a, size_t p) const { return *(const double *)(S.base + (size_t)((unsigned)p * 8u + (unsigned)a * S.stride8)); }
-        __device__ __forceinline__ unsigned bits(size_t p) const { return S.gm[(size_t)(unsigned)p]; }
-        __device__ __forceinline__ double operator[](size_t p) const
-        {
-            switch (k) {
-            case CG_TAREA: return raw(CG_DXT, p) * raw(CG_DYT, p);
-            case CG_UAREA: return raw(CG_DXU, p) * raw(CG_DYU, p);
-            case CG_NAREA: return raw(CG_DXN, p) * raw(CG_DYN, p);
-            case CG_EAREA: return raw(CG_DXE, p) * raw(CG_DYE, p);
-            case CG_EAREAR: { const double a = raw(CG_DXE, p) * raw(CG_DYE, p); return a > 0.0 ? 1.0 / a : 0.0; }
-            case CG_NAREAR: { const double a = raw(CG_DXN, p) * raw(CG_DYN, p); return a > 0.0 ? 1.0 / a : 0.0; }
-            case CG_DMINT: return S.dmin * (raw(CG_DXT, p) * raw(CG_DYT, p));
-            case CG_RXN: return -(raw(CG_DXN, p + 1) / raw(CG_DXN, p));
-            case CG_RXNR: return 1.0 / -(raw(CG_DXN, p + 1) / raw(CG_DXN, p));
-            case CG_RYE: return -(raw(CG_DYE, p + S.nx) / raw(CG_DYE, p));
-            case CG_RYER: return 1.0 / -(raw(CG_DYE, p + S.nx) / raw(CG_DYE, p));
-            case CG_EPM: return (bits(p) & 1u) ? 1.0 : 0.0;
-            case CG_NPM: return (bits(p) & 2u) ? 1.0 : 0.0;
-            case CG_UVM: return (bits(p) & 4u) ? 1.0 : 0.0;
-            case CG_HM: return (bits(p) & 8u) ? 1.0 : 0.0;
-            default: return raw(k, p);
-            }
-        }
-    };
-    __device__ __forceinline__ Acc operator[](int k) const { return Acc{*this, k}; }
-};
-template <bool GEO> struct GeoView32;
-template <> struct GeoView32<false> {
-    static __device__ __forceinline__ Slab32 make(const EvpCgrid &, const EvpCgOne &T) { return Slab32{(const char *)T.gbase, (unsigned)T.stride * 8u}; }
-};
-template <> struct GeoView32<true> {
-    static __device__ __forceinline__ DSlab32 make(const EvpCgrid &A, const EvpCgOne &T)
-    {
-        return DSlab32{(const char *)T.gbase, (unsigned)T.stride * 8u, T.gmask, A.nx, A.deltaminEVP};
-    }
-};
 template <bool GEO> struct GeoView;
 template <> struct GeoView<false> {
     static __device__ __forceinline__ Slab make(const EvpCgrid &, const EvpCgOne &T) { return Slab{T.gbase, T.stride}; }
@@ -1174,8 +1106,8 @@ template <> struct GeoView<true> {
 };
 struct TStress { double zetax2, etax2, sp, sm, shearT; };
 // stressC_T at cell o (ice_dyn_evp.F90:1758-1860) with the four corner values of shearU handed in; spo, smo: previous
-template <class GT, class IT, class P>
-__device__ __forceinline__ TStress t_stress(const EvpCgrid &A, const GT &G, const IT &IN, const P &uE, const P &vN, size_t o,
+template <class GT>
+__device__ __forceinline__ TStress t_stress(const EvpCgrid &A, const GT &G, const Slab &IN, const double *uE, const double *vN, size_t o,
                                             double shO, double shS, double shSW, double shW, double spo, double smo)
 {
     const size_t w = o - 1, s = o - A.nx, sw = s - 1;
@@ -1496,7 +1428,8 @@ __device__ __forceinline__ unsigned cg_lane_dn_u(unsigned v)
 {
     return (unsigned)__builtin_amdgcn_update_dpp(0, (int)v, 0x130, 0xf, 0xf, false);
 }
-// an array as a wave-uniform base + a 32-bit byte offset per lane: one register per lane addresses every array
+// an array as a wave-uniform base + a 32-bit byte offset per lane: one register per lane addresses every array (in a loop over rows
+// the compiler otherwise keeps a 64-bit per-lane address for each of the ~50 arrays).  The tables must end below 4 GB: the host checks.
 __device__ __forceinline__ double cg_ld(const void *base, unsigned off) { return *(const double *)((const char *)base + (size_t)off); }
 __device__ __forceinline__ unsigned cg_ldb(const uint8_t *base, unsigned cell) { return base[(size_t)cell]; }
 __device__ __forceinline__ void cg_st(void *base, unsigned off, double v) { *(double *)((char *)base + (size_t)off) = v; }

@@ -430,11 +430,18 @@ struct EvpCgStrip {
     int lengths;                  // 1: dxT, dyT, dxU, dyU, dxE, dyN formed in the kernel from dxN, dyE (verified by the host); the items own lanes >= 3
 };
 void evp_launch_cgrid_strip(const EvpCgrid &A, const EvpCgOne &T, const EvpCgStrip &Z, const EvpCgOne *E, int fast, int last, hipStream_t st);
+// What a plan that splits a rank's interior cells between cg_strip (the ZONE) and list-driven kernels (the REST) says of an array cell:
+// the bits of EvpCgFrame::cells and EvpCgBand::cells, written by halo_plan.cpp (build_cg_frame, build_cg_march_fold) and tested by the
+// kernels of evp_cgrid.hip.  REST: an interior cell that is no zone cell -- the "frame" of the schedule for several ranks as well; the
+// momentum step runs on these.  S, T, U, AVG: strain_rates_U's shear, stressC_T, etax2U + stressC_U and the velocity averages run on the
+// cell (REST cells, and the zone cells a later level reads: to scratch arrays only).  The frame plan sets REST, S, T and ZONE only.
+enum { EVP_CGS_REST = 1, EVP_CGS_S = 2, EVP_CGS_T = 4, EVP_CGS_ZONE = 8, EVP_CGS_U = 16, EVP_CGS_AVG = 32,
+       EVP_CGS_FOLDROW = 64 };   // FOLDROW: an interior cell of global row NY (tripole grids)
 // The three fused kernels on the FRAME of a rank whose zone cg_strip marches at the same time (several ranks; evp_cgrid.hip:
 // cg_frame_*; halo_plan.h: build_cg_frame).  They read the five ping-pong arrays of the previous subcycle (uE_in .. sm_in, A.s12_in) and
 // write this subcycle's (A.f[...]) on frame cells only; intermediates of the zone cells a frame cell reads go to the scratch arrays.
 struct EvpCgFrame {
-    const uint8_t *cells;         // per cell: 1 frame cell, 2 level S runs here, 4 level T, 8 zone cell (halo_plan.h: CGF_*)
+    const uint8_t *cells;         // per cell: EVP_CGS_* (REST = frame cell; levels S, T)
     const int *wg[3];             // workgroups of 64 x 4 cells of level S, T, C: (block * gy + row) * gx + column
     int nwg[3];
     const double *uE_in, *vN_in, *sp_in, *sm_in;
@@ -448,7 +455,7 @@ void evp_launch_cgrid_frame(const EvpCgrid &A, const EvpCgFrame &F, int level, i
 // cells are what the arrays of the five-phase schedule hold; intermediates of the zone cells a REST cell reads go to the scratch arrays.
 // All 23 static arrays are loaded: the start-up identities do not hold next to the fold.
 struct EvpCgBand {
-    const uint8_t *cells;         // per cell: 1 REST cell (phase 3), 2 phase 0, 4 phase 1, 8 zone cell, 16 phase 2, 32 phase 4, 64 row NY (halo_plan.h: CGM_*)
+    const uint8_t *cells;         // per cell: EVP_CGS_* (phase 0 = S, 1 = T, 2 = U, 3 = REST, 4 = AVG)
     const int *wg[5];             // workgroups of 64 x 4 cells of phases 0 .. 4: (block * gy + row) * gx + column
     int nwg[5];
     const double *uE_in, *vN_in, *sp_in, *sm_in, *s12_in;

@@ -80,14 +80,14 @@ struct CGridState {
         long strip_cells = 0;    // cells the marched kernel owns
     } one;
     // several ranks: the marched kernel on the rectangles above beside the fused chain on every other interior cell (enqueue_fused:
-    // "zone marched + frame"; halo_plan.cpp: build_cg_frame).  cells: frame cell | level S | level T | zone cell; three levels; scr:
+    // "zone marched + frame"; halo_plan.cpp: build_cg_frame).  cells: the EVP_CGS_* bits (REST = frame cell); three levels; scr:
     // shearU, etax2T, stresspT, stressmT of the zone cells the frame reads; ncells: frame cells
     CellLists fr;
     // tripole / tripoleT on one rank: the marched kernel on the rectangles under the fold band beside list-driven variants of the five
     // phase kernels on every other interior cell (enqueue_march_fold: "marched zone + fold band"; halo_plan.cpp: build_cg_march_fold).
     // The items live in `one` (items, nitems, strip_*)
     struct MarchFold {
-        CellLists rest;                      // cells: the CGM_* bits; five phases; scr: shearU, etax2T, stresspT, stressmT, stress12U; ncells: REST cells
+        CellLists rest;                      // cells: the EVP_CGS_* bits; five phases; scr: shearU, etax2T, stresspT, stressmT, stress12U; ncells: REST cells
         uint8_t *gmask = nullptr;            // the land masks as bits on the rows the marched kernel derives its geometry on
         int band_rows = 0;
         bool by_size = false;                // cg_strip's size rule holds for the zone
@@ -884,7 +884,7 @@ static int build_one_tables(const double *const *static23)
                 if (build_cg_frame(d, P, items, FP, why) != 1) return fail(-4, "C-grid EVP: %s", why.c_str());
                 tiles_e.clear();
                 tab_e.clear();
-                if (upload_cell_lists(CG.fr, FP.cells, FP.wg, 3, 4, FP.frame_cells)) return -1;
+                if (upload_cell_lists(CG.fr, FP.cells, FP.wg, 3, 4, FP.rest_cells)) return -1;
             }
             if (upload_items(items, EX, EY, lengths ? 1 : 0, seg, zcells)) return -1;
             O.ntiles_e = (int)(tiles_e.size() / 4);

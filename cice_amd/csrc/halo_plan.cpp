@@ -1,4 +1,5 @@
 #include "halo_plan.h"
+#include "evp_device.h"          // EVP_CGS_*: the bits of a zone / rest plan's cells
 
 #include <algorithm>
 #include <map>
@@ -894,6 +895,168 @@ void strip_windows(const std::vector<StripZone> &zones, const std::vector<int32_
                 in_zone[(size_t)w] = 1;
 }
 
+void plan_strip_zones(const cice_evp_hip_dims &d, const HaloPlan &P, int ex, int ey, int min_cols, int last_image_row, std::vector<int32_t> &tiles,
+                      std::vector<StripZone> &zones)
+{
+    std::vector<int32_t> tab;
+    build_window_table(d, P, ex, ey, 1 << 20, tiles, tab);
+    // ghost images: the sources of the rank's own ghost copies (-1: a ghost cell filled with 0, no source)
+    const long plane = (long)d.nx_block * d.ny_block;
+    std::vector<int> img((size_t)plane * d.nblocks, -1);
+    for (size_t k = 0; k < P.local_src.size(); ++k) {
+        if (P.local_src[k] < 0) continue;
+        if (last_image_row != STRIP_EVERY_IMAGE) {
+            const int db = (int)(P.local_dst[k] / plane), dj = (int)((P.local_dst[k] % plane) / d.nx_block) + 1;
+            if (d.jglob0[db] + (dj - d.jlo[db]) > last_image_row) continue;
+        }
+        img[(size_t)P.local_src[k]] = 0;
+    }
+    strip_zones(d, tiles, ex, ey, img.data(), zones, min_cols);
+}
+
+namespace {
+// ---- a rank's interior cells split between cg_strip (the zone) and list-driven kernels (the rest): what build_cg_frame and
+// build_cg_march_fold share (halo_plan.h) ----
+// One read of the list-driven chain: a cell on which level `reader` runs reads `what` -- the text of the check that fails -- at these
+// offsets from itself, and level `producer` makes it.  A plan lists its reads from the last level of a subcycle back to the first, every
+// level complete before the reads OF it come; marking (dilate) and checking (check_cell) walk the same table.
+struct CgRead {
+    int reader, producer, n;
+    int at[8][2];
+    const char *what;
+};
+// the words in which the two plans' error texts differ
+struct CgSplitWords {
+    const char *plan, *sum, *ghost, *own, *t_loads;
+    bool near;          // a read nobody produces is reported at the reading cell ("..., near"), not at the cell read
+};
+struct CgSplit {
+    const cice_evp_hip_dims &d;
+    CgSplitPlan &F;
+    std::string &why;
+    const CgSplitWords &words;
+    const std::vector<CgRead> &reads;
+    const int nxb, nyb;
+    const long plane;
+    int own_levels = 0, not_t = 0;       // the levels a rest cell runs itself; everything that may not run on a ghost cell
+    long n_interior = 0;
+    CgSplit(const cice_evp_hip_dims &d_, CgSplitPlan &F_, std::string &why_, const CgSplitWords &w, const std::vector<CgRead> &r)
+        : d(d_), F(F_), why(why_), words(w), reads(r), nxb(d_.nx_block), nyb(d_.ny_block), plane((long)d_.nx_block * d_.ny_block)
+    {
+        for (const CgRead &q : reads) own_levels |= q.reader | q.producer;
+        not_t = own_levels & ~EVP_CGS_T;
+        own_levels &= ~EVP_CGS_REST;
+    }
+    size_t off(int b, int i, int j) const { return (size_t)b * plane + (size_t)(j - 1) * nxb + (size_t)(i - 1); }
+    bool inside(int i, int j) const { return i >= 1 && i <= nxb && j >= 1 && j <= nyb; }
+    bool interior(int b, int i, int j) const { return i >= d.ilo[b] && i <= d.ihi[b] && j >= d.jlo[b] && j <= d.jhi[b]; }
+    void cell_of(size_t c, int &b, int &i, int &j) const
+    {
+        b = (int)(c / (size_t)plane);
+        j = (int)((c % (size_t)plane) / nxb) + 1;
+        i = (int)((c % (size_t)plane) % nxb) + 1;
+    }
+    int bad(const char *what, int b, int i, int j) const
+    {
+        char buf[200];
+        std::snprintf(buf, sizeof buf, "%s: %s at block %d cell (%d, %d)", words.plan, what, b, i, j);
+        why = buf;
+        return -1;
+    }
+    // ownership: the items' cells are the zone, everything else of the interior the rest
+    int own(const std::vector<int32_t> &items)
+    {
+        F.cells.assign((size_t)plane * d.nblocks, 0);
+        for (size_t k = 0; k + 5 < items.size(); k += 6) {
+            const int b = items[k], c = items[k + 1], ja = items[k + 2], jb = items[k + 3], lo = items[k + 4], hi = items[k + 5];
+            if (b < 0 || b >= d.nblocks) return bad("an item of a block that is not here", b, c, ja);
+            for (int j = ja; j <= jb; ++j)
+                for (int i = c - 2 + lo; i <= c - 2 + hi; ++i) {
+                    if (!interior(b, i, j)) return bad("a marched cell outside the interior", b, i, j);
+                    uint8_t &f = F.cells[off(b, i, j)];
+                    if (f & EVP_CGS_ZONE) return bad("a cell two items own", b, i, j);
+                    f |= EVP_CGS_ZONE;
+                    ++F.zone_cells;
+                }
+        }
+        n_interior = 0;
+        for (int b = 0; b < d.nblocks; ++b)
+            for (int j = d.jlo[b]; j <= d.jhi[b]; ++j)
+                for (int i = d.ilo[b]; i <= d.ihi[b]; ++i) {
+                    ++n_interior;
+                    uint8_t &f = F.cells[off(b, i, j)];
+                    if (!(f & EVP_CGS_ZONE)) {
+                        f |= EVP_CGS_REST;
+                        ++F.rest_cells;
+                    }
+                }
+        return 0;
+    }
+    // the levels, each dilated by what the next one reads of it
+    int dilate()
+    {
+        // the reference's T list: stress12T of the ghost row and column i = ihi + 1, j = jhi + 1 -- level T there, and nothing else
+        for (int b = 0; b < d.nblocks; ++b)
+            for (int j = d.jlo[b]; j <= d.jhi[b] + 1; ++j)
+                for (int i = d.ilo[b]; i <= d.ihi[b] + 1; ++i) {
+                    if (!inside(i, j)) return bad("the extra T row / column outside the array", b, i, j);
+                    if (!interior(b, i, j)) F.cells[off(b, i, j)] |= EVP_CGS_T;
+                }
+        for (const CgRead &r : reads)
+            for (int b = 0; b < d.nblocks; ++b)
+                for (int j = d.jlo[b]; j <= d.jhi[b] + 1; ++j) {
+                    const uint8_t *row = &F.cells[off(b, 1, j)] - 1;
+                    for (int i = d.ilo[b]; i <= d.ihi[b] + 1; ++i)
+                        if (row[i] & r.reader)
+                            for (int q = 0; q < r.n; ++q)
+                                if (interior(b, i + r.at[q][0], j + r.at[q][1])) F.cells[off(b, i + r.at[q][0], j + r.at[q][1])] |= (uint8_t)r.producer;
+                }
+        return 0;
+    }
+    int check_sum() const { return F.zone_cells + F.rest_cells == n_interior ? 0 : bad(words.sum, 0, 0, 0); }
+    // the invariants of one array cell
+    int check_cell(int b, int i, int j) const
+    {
+        const uint8_t f = F.cells[off(b, i, j)];
+        const bool in = interior(b, i, j);
+        if ((f & EVP_CGS_ZONE) && (f & EVP_CGS_REST)) return bad("a cell in both sets", b, i, j);
+        if (in != ((f & (EVP_CGS_ZONE | EVP_CGS_REST)) != 0)) return bad("a cell of neither set, or a ghost cell of one", b, i, j);
+        if (!(f & (not_t | EVP_CGS_T))) return 0;          // (no level runs here)
+        if ((f & not_t) && !in) return bad(words.ghost, b, i, j);
+        if ((f & EVP_CGS_REST) && (f & own_levels) != own_levels) return bad(words.own, b, i, j);
+        for (const CgRead &r : reads) {
+            if (!(f & r.reader)) continue;
+            if (r.reader == EVP_CGS_T)           // (the one level that runs on ghost cells)
+                for (int q = 0; q < r.n; ++q)
+                    if (!inside(i + r.at[q][0], j + r.at[q][1])) return bad(words.t_loads, b, i, j);
+            for (int q = 0; q < r.n; ++q) {
+                const int ri = i + r.at[q][0], rj = j + r.at[q][1];
+                if (interior(b, ri, rj) && !(F.cells[off(b, ri, rj)] & r.producer)) return words.near ? bad(r.what, b, i, j) : bad(r.what, b, ri, rj);
+            }
+        }
+        // (every level but T: the velocities, lengths and masks one cell around the cell)
+        if ((f & not_t) && !(inside(i - 1, j - 1) && inside(i + 1, j + 1))) return bad("a stencil outside the array", b, i, j);
+        return 0;
+    }
+    // wg[k]: the workgroups of 64 x 4 cells that hold a cell of level bits[k]
+    void workgroups(std::initializer_list<int> bits)
+    {
+        const int gx = (nxb + 63) / 64, gy = (nyb + 3) / 4;
+        int k = 0;
+        for (int bit : bits) {
+            std::vector<uint8_t> on((size_t)gx * gy * d.nblocks, 0);
+            for (int b = 0; b < d.nblocks; ++b)
+                for (int j = 1; j <= nyb; ++j)
+                    for (int i = 1; i <= nxb; ++i)
+                        if (F.cells[off(b, i, j)] & bit) on[((size_t)b * gy + (size_t)(j - 1) / 4) * gx + (size_t)(i - 1) / 64] = 1;
+            for (size_t w = 0; w < on.size(); ++w)
+                if (on[w]) F.wg[k].push_back((int32_t)w);
+            ++k;
+        }
+    }
+};
+}   // namespace
+
 int build_cg_frame(const cice_evp_hip_dims &d, const HaloPlan &P, const std::vector<int32_t> &items, CgFramePlan &F, std::string &why)
 {
     F = CgFramePlan();
@@ -902,82 +1065,24 @@ int build_cg_frame(const cice_evp_hip_dims &d, const HaloPlan &P, const std::vec
         why = "no neighbour on another rank";
         return 0;
     }
-    const int nxb = d.nx_block, nyb = d.ny_block;
-    const long plane = (long)nxb * nyb;
-    F.cells.assign((size_t)plane * d.nblocks, 0);
-    auto off = [&](int b, int i, int j) { return (size_t)b * plane + (size_t)(j - 1) * nxb + (size_t)(i - 1); };
-    auto inside = [&](int i, int j) { return i >= 1 && i <= nxb && j >= 1 && j <= nyb; };
-    auto interior = [&](int b, int i, int j) { return i >= d.ilo[b] && i <= d.ihi[b] && j >= d.jlo[b] && j <= d.jhi[b]; };
-    auto bad = [&](const char *what, int b, int i, int j) {
-        char buf[200];
-        std::snprintf(buf, sizeof buf, "frame plan: %s at block %d cell (%d, %d)", what, b, i, j);
-        why = buf;
-        return -1;
+    // level C reads etax2T around its three corners (the new stresspT, stressmT of the east and north neighbour are among those T cells) and
+    // shearU at its own, south and west corner; level T reads shearU at its four corners
+    static const std::vector<CgRead> reads = {
+        {EVP_CGS_REST, EVP_CGS_T, 8, {{0, 0}, {1, 0}, {0, 1}, {1, 1}, {0, -1}, {1, -1}, {-1, 0}, {-1, 1}}, "etax2T read where level T does not run"},
+        {EVP_CGS_REST, EVP_CGS_S, 3, {{0, 0}, {0, -1}, {-1, 0}}, "shearU read where level S does not run"},
+        {EVP_CGS_T, EVP_CGS_S, 4, {{0, 0}, {0, -1}, {-1, -1}, {-1, 0}}, "shearU read where level S does not run"},
     };
-    // the stencils, as offsets from the evaluating cell: T cells level C reads (etax2T around its three corners; the new stresspT,
-    // stressmT of the east and north neighbour are among them), corners level C and level T read shearU at
-    static const int c_reads_t[8][2] = {{0, 0}, {1, 0}, {0, 1}, {1, 1}, {0, -1}, {1, -1}, {-1, 0}, {-1, 1}};
-    static const int c_reads_s[3][2] = {{0, 0}, {0, -1}, {-1, 0}};
-    static const int t_reads_s[4][2] = {{0, 0}, {0, -1}, {-1, -1}, {-1, 0}};
-    // ---- ownership: the items' cells, then everything else of the interior ----
-    for (size_t k = 0; k + 5 < items.size(); k += 6) {
-        const int b = items[k], c = items[k + 1], ja = items[k + 2], jb = items[k + 3], lo = items[k + 4], hi = items[k + 5];
-        if (b < 0 || b >= d.nblocks) return bad("an item of a block that is not here", b, c, ja);
-        for (int j = ja; j <= jb; ++j)
-            for (int i = c - 2 + lo; i <= c - 2 + hi; ++i) {
-                if (!interior(b, i, j)) return bad("a marched cell outside the interior", b, i, j);
-                uint8_t &f = F.cells[off(b, i, j)];
-                if (f & CGF_ZONE) return bad("a cell two items own", b, i, j);
-                f |= CGF_ZONE;
-                ++F.zone_cells;
-            }
-    }
-    long n_interior = 0;
-    for (int b = 0; b < d.nblocks; ++b)
-        for (int j = d.jlo[b]; j <= d.jhi[b]; ++j)
-            for (int i = d.ilo[b]; i <= d.ihi[b]; ++i) {
-                ++n_interior;
-                uint8_t &f = F.cells[off(b, i, j)];
-                if (!(f & CGF_ZONE)) {
-                    f |= CGF_FRAME;
-                    ++F.frame_cells;
-                }
-            }
-    // ---- the levels, each dilated by what the next one reads of it ----
-    for (int b = 0; b < d.nblocks; ++b) {
-        for (int j = d.jlo[b]; j <= d.jhi[b] + 1; ++j)
-            for (int i = d.ilo[b]; i <= d.ihi[b] + 1; ++i) {
-                if (!inside(i, j)) return bad("the extra T row / column outside the array", b, i, j);
-                const bool in = interior(b, i, j);
-                if (!in) {
-                    F.cells[off(b, i, j)] |= CGF_T;          // (the reference's T list: stress12T of the ghost row / column)
-                    continue;
-                }
-                if (!(F.cells[off(b, i, j)] & CGF_FRAME)) continue;
-                for (const auto &r : c_reads_t)
-                    if (interior(b, i + r[0], j + r[1])) F.cells[off(b, i + r[0], j + r[1])] |= CGF_T;
-                for (const auto &r : c_reads_s)
-                    if (interior(b, i + r[0], j + r[1])) F.cells[off(b, i + r[0], j + r[1])] |= CGF_S;
-            }
-        for (int j = d.jlo[b]; j <= d.jhi[b] + 1; ++j)
-            for (int i = d.ilo[b]; i <= d.ihi[b] + 1; ++i)
-                if (F.cells[off(b, i, j)] & CGF_T)
-                    for (const auto &r : t_reads_s)
-                        if (interior(b, i + r[0], j + r[1])) F.cells[off(b, i + r[0], j + r[1])] |= CGF_S;
-    }
-    // ---- the invariants ----
-    if (F.zone_cells + F.frame_cells != n_interior) return bad("zone and frame do not add up to the interior", 0, 0, 0);
-    auto cell_of = [&](size_t c, int &b, int &i, int &j) {
-        b = (int)(c / (size_t)plane);
-        j = (int)((c % (size_t)plane) / nxb) + 1;
-        i = (int)((c % (size_t)plane) % nxb) + 1;
-    };
+    static const CgSplitWords words = {"frame plan", "zone and frame do not add up to the interior", "level S or C on a ghost cell",
+                                       "a frame cell without its own levels", "level T loads outside the array", false};
+    CgSplit X(d, F, why, words, reads);
+    if (X.own(items) || X.dilate() || X.check_sum()) return -1;
+    // what leaves the rank, or has an image on it, is the frame's: the marched kernel has no pushes and runs beside the exchange
     auto must_be_frame = [&](int32_t c, const char *what) {
         if (c < 0 || (size_t)c >= F.cells.size()) return 0;          // (a staging slot behind the array: no cell)
-        if (F.cells[(size_t)c] & CGF_FRAME) return 0;
+        if (F.cells[(size_t)c] & EVP_CGS_REST) return 0;
         int b, i, j;
-        cell_of((size_t)c, b, i, j);
-        return bad(what, b, i, j);
+        X.cell_of((size_t)c, b, i, j);
+        return X.bad(what, b, i, j);
     };
     for (const std::vector<HaloPeer> *pp : {&P.peers, &P.cg_peers})
         for (const HaloPeer &p : *pp)
@@ -986,43 +1091,10 @@ int build_cg_frame(const cice_evp_hip_dims &d, const HaloPlan &P, const std::vec
     for (size_t k = 0; k < P.local_src.size(); ++k)
         if (P.local_src[k] >= 0 && must_be_frame(P.local_src[k], "a cell with a ghost image is not a frame cell")) return -1;
     for (int b = 0; b < d.nblocks; ++b)
-        for (int j = 1; j <= nyb; ++j)
-            for (int i = 1; i <= nxb; ++i) {
-                const uint8_t f = F.cells[off(b, i, j)];
-                const bool in = interior(b, i, j);
-                if ((f & CGF_ZONE) && (f & CGF_FRAME)) return bad("a cell in both sets", b, i, j);
-                if (in != ((f & (CGF_ZONE | CGF_FRAME)) != 0)) return bad("a cell of neither set, or a ghost cell of one", b, i, j);
-                if ((f & (CGF_S | CGF_FRAME)) && !in) return bad("level S or C on a ghost cell", b, i, j);
-                if (f & CGF_FRAME) {
-                    if (!(f & CGF_T) || !(f & CGF_S)) return bad("a frame cell without its own levels", b, i, j);
-                    for (const auto &r : c_reads_t)
-                        if (interior(b, i + r[0], j + r[1]) && !(F.cells[off(b, i + r[0], j + r[1])] & CGF_T))
-                            return bad("etax2T read where level T does not run", b, i + r[0], j + r[1]);
-                    for (const auto &r : c_reads_s)
-                        if (interior(b, i + r[0], j + r[1]) && !(F.cells[off(b, i + r[0], j + r[1])] & CGF_S))
-                            return bad("shearU read where level S does not run", b, i + r[0], j + r[1]);
-                }
-                if (f & CGF_T)
-                    for (const auto &r : t_reads_s) {
-                        if (!inside(i + r[0], j + r[1])) return bad("level T loads outside the array", b, i, j);
-                        if (interior(b, i + r[0], j + r[1]) && !(F.cells[off(b, i + r[0], j + r[1])] & CGF_S))
-                            return bad("shearU read where level S does not run", b, i + r[0], j + r[1]);
-                    }
-                // (levels S and C: the velocities, lengths and masks one cell around the cell)
-                if ((f & (CGF_S | CGF_FRAME)) && !(inside(i - 1, j - 1) && inside(i + 1, j + 1))) return bad("a stencil outside the array", b, i, j);
-            }
-    // ---- the workgroups of each level ----
-    const int gx = (nxb + 63) / 64, gy = (nyb + 3) / 4;
-    const int bit[3] = {CGF_S, CGF_T, CGF_FRAME};
-    for (int k = 0; k < 3; ++k) {
-        std::vector<uint8_t> on((size_t)gx * gy * d.nblocks, 0);
-        for (int b = 0; b < d.nblocks; ++b)
-            for (int j = 1; j <= nyb; ++j)
-                for (int i = 1; i <= nxb; ++i)
-                    if (F.cells[off(b, i, j)] & bit[k]) on[((size_t)b * gy + (size_t)(j - 1) / 4) * gx + (size_t)(i - 1) / 64] = 1;
-        for (size_t w = 0; w < on.size(); ++w)
-            if (on[w]) F.wg[k].push_back((int32_t)w);
-    }
+        for (int j = 1; j <= d.ny_block; ++j)
+            for (int i = 1; i <= d.nx_block; ++i)
+                if (X.check_cell(b, i, j)) return -1;
+    X.workgroups({EVP_CGS_S, EVP_CGS_T, EVP_CGS_REST});
     return 1;
 }
 
@@ -1044,19 +1116,24 @@ int build_cg_march_fold(const cice_evp_hip_dims &d, const HaloPlan &P, int ex, i
         why = "a block too small";
         return 0;
     }
-    const int nxb = d.nx_block, nyb = d.ny_block, NY = d.ny_global, sy = ey - 3;
-    const long plane = (long)nxb * nyb;
-    const size_t ncell = (size_t)plane * d.nblocks;
-    auto off = [&](int b, int i, int j) { return (size_t)b * plane + (size_t)(j - 1) * nxb + (size_t)(i - 1); };
-    auto inside = [&](int i, int j) { return i >= 1 && i <= nxb && j >= 1 && j <= nyb; };
-    auto interior = [&](int b, int i, int j) { return i >= d.ilo[b] && i <= d.ihi[b] && j >= d.jlo[b] && j <= d.jhi[b]; };
-    auto grow = [&](int b, int j) { return d.jglob0[b] + (j - d.jlo[b]); };          // global row of local row j
-    auto bad = [&](const char *what, int b, int i, int j) {
-        char buf[200];
-        std::snprintf(buf, sizeof buf, "fold-band plan: %s at block %d cell (%d, %d)", what, b, i, j);
-        why = buf;
-        return -1;
+    // the five phases, from the momentum step back (offsets from the evaluating cell); phase 4, the averages, runs AFTER the two sets have
+    // met again: on the rest cells and on what phase 0 of the next subcycle reads
+    static const std::vector<CgRead> reads = {
+        {EVP_CGS_REST, EVP_CGS_U, 3, {{0, 0}, {0, -1}, {-1, 0}}, "stress12U read where phase 2 does not run, near"},
+        {EVP_CGS_REST, EVP_CGS_T, 3, {{0, 0}, {1, 0}, {0, 1}}, "stresspT read where phase 1 does not run, near"},          // and stressmT
+        {EVP_CGS_U, EVP_CGS_T, 4, {{0, 0}, {1, 0}, {0, 1}, {1, 1}}, "etax2T / shearU read where it is not produced, near"},
+        {EVP_CGS_U, EVP_CGS_S, 1, {{0, 0}}, "etax2T / shearU read where it is not produced, near"},
+        {EVP_CGS_T, EVP_CGS_S, 4, {{0, 0}, {0, -1}, {-1, -1}, {-1, 0}}, "shearU read where phase 0 does not run, near"},
+        {EVP_CGS_REST, EVP_CGS_AVG, 1, {{0, 0}}, "a REST cell without its own levels"},
+        // uvelN (own, east), vvelE (own, north), uvelU, vvelU (own)
+        {EVP_CGS_S, EVP_CGS_AVG, 3, {{0, 0}, {1, 0}, {0, 1}}, "an average read where phase 4 does not run, near"},
     };
+    static const CgSplitWords words = {"fold-band plan", "zone and rest do not add up to the interior", "a phase other than stressC_T on a ghost cell",
+                                       "a REST cell without its own levels", "phase 1 loads outside the array", true};
+    CgSplit X(d, F, why, words, reads);
+    const int nxb = d.nx_block, nyb = d.ny_block, NY = d.ny_global, sy = ey - 3;
+    const size_t ncell = (size_t)nxb * nyb * d.nblocks;
+    auto grow = [&](int b, int j) { return d.jglob0[b] + (j - d.jlo[b]); };          // global row of local row j
     // on the fold or beyond it, by field location (0 centre, 1 NE corner, 2 E face, 3 N face) and global row
     auto at_fold = [&](int loc, int jg) { return jg > NY || (jg == NY && (tf || loc == 1 || loc == 3)); };
     // ---- the fold step's cells: destinations and sources of every location ----
@@ -1069,21 +1146,13 @@ int build_cg_march_fold(const cice_evp_hip_dims &d, const HaloPlan &P, int ex, i
                 if (c >= 0 && (size_t)c < ncell) foldcell[(size_t)c] = 1;
     }
     // ---- the rectangles, cut from the top until the fold rule holds ----
-    std::vector<int32_t> tiles, tab;
-    build_window_table(d, P, ex, ey, 1 << 20, tiles, tab);
-    std::vector<int> img(ncell, -1);
-    for (size_t k = 0; k < P.local_src.size(); ++k) {
-        if (P.local_src[k] < 0) continue;
-        // (ghost cells the fold step fills -- the row beyond the fold, on a T-fold the top physical row too -- are no images: their
-        // sources are fold cells, which come off the rectangle's top below instead of costing a block its rectangle)
-        const int db = (int)(P.local_dst[k] / plane), dj = (int)((P.local_dst[k] % plane) / nxb) + 1;
-        if (grow(db, dj) > NY - (tf ? 1 : 0)) continue;
-        img[(size_t)P.local_src[k]] = 0;
-    }
+    // (ghost cells the fold step fills -- the row beyond the fold, on a T-fold the top physical row too -- are no images: their sources
+    // are fold cells, which come off the rectangle's top below instead of costing a block its rectangle.  A rectangle narrower than a
+    // strip is one item per segment with fewer owned lanes: tx3's 100 columns hold two regular window columns, 58 cells; the footprint
+    // check below keeps its lanes inside the array)
+    std::vector<int32_t> tiles;
     std::vector<StripZone> zones0, zones;
-    // (a rectangle narrower than a strip is one item per segment with fewer owned lanes: tx3's 100 columns hold two regular window
-    // columns, 58 cells; the footprint check below keeps its lanes inside the array)
-    strip_zones(d, tiles, ex, ey, img.data(), zones0, ex - 3);
+    plan_strip_zones(d, P, ex, ey, ex - 3, NY - (tf ? 1 : 0), tiles, zones0);
     bool len_all = want_len != 0;
     for (StripZone z : zones0) {
         auto rule_holds = [&]() {
@@ -1102,7 +1171,7 @@ int build_cg_march_fold(const cice_evp_hip_dims &d, const HaloPlan &P, int ex, i
             }
             for (int j = z.j0; j <= jb; ++j)
                 for (int i = z.i0; i <= z.i1 + ex - 3 - 1; ++i)
-                    if (foldcell[off(z.b, i, j)]) return false;
+                    if (foldcell[X.off(z.b, i, j)]) return false;
             return true;
         };
         int g = 0;
@@ -1130,125 +1199,35 @@ int build_cg_march_fold(const cice_evp_hip_dims &d, const HaloPlan &P, int ex, i
             if (z.b == b) top = std::max(top, z.j1 + sy - 1);
         F.band_rows = std::max(F.band_rows, NY - grow(b, top));          // (a block at the fold without a rectangle: all its rows)
     }
-    // ---- ownership ----
-    F.cells.assign(ncell, 0);
-    for (size_t k = 0; k + 5 < F.items.size(); k += 6) {
-        const int b = F.items[k], c = F.items[k + 1], ja = F.items[k + 2], jb = F.items[k + 3], lo = F.items[k + 4], hi = F.items[k + 5];
-        for (int j = ja; j <= jb; ++j)
-            for (int i = c - 2 + lo; i <= c - 2 + hi; ++i) {
-                if (!interior(b, i, j)) return bad("a marched cell outside the interior", b, i, j);
-                uint8_t &f = F.cells[off(b, i, j)];
-                if (f & CGM_ZONE) return bad("a cell two items own", b, i, j);
-                f |= CGM_ZONE;
-                ++F.zone_cells;
-            }
-    }
-    long n_interior = 0;
+    // ---- the two sets, the fold row, the phases ----
+    if (X.own(F.items)) return -1;
     for (int b = 0; b < d.nblocks; ++b)
-        for (int j = d.jlo[b]; j <= d.jhi[b]; ++j)
-            for (int i = d.ilo[b]; i <= d.ihi[b]; ++i) {
-                ++n_interior;
-                uint8_t &f = F.cells[off(b, i, j)];
-                if (!(f & CGM_ZONE)) {
-                    f |= CGM_REST;
-                    ++F.rest_cells;
-                }
-                if (grow(b, j) == NY) f |= CGM_FOLDROW;
-            }
-    // ---- the phases, each dilated by what the next one reads of it (offsets from the evaluating cell) ----
-    static const int p3_reads_u[3][2] = {{0, 0}, {0, -1}, {-1, 0}};                 // stress12U
-    static const int p3_reads_t[3][2] = {{0, 0}, {1, 0}, {0, 1}};                   // stresspT, stressmT
-    static const int p2_reads_t[4][2] = {{0, 0}, {1, 0}, {0, 1}, {1, 1}};           // etax2T
-    static const int p1_reads_s[4][2] = {{0, 0}, {0, -1}, {-1, -1}, {-1, 0}};       // shearU
-    static const int p0_reads_a[3][2] = {{0, 0}, {1, 0}, {0, 1}};                   // uvelN (o, e), vvelE (o, n), uvelU, vvelU (o)
-    auto mark = [&](int b, int i, int j, int bit) {
-        if (interior(b, i, j)) F.cells[off(b, i, j)] |= (uint8_t)bit;
-    };
-    for (int b = 0; b < d.nblocks; ++b) {
-        const int i0 = d.ilo[b], i1 = d.ihi[b], j0 = d.jlo[b], j1 = d.jhi[b];
-        for (int j = j0; j <= j1; ++j)
-            for (int i = i0; i <= i1; ++i)
-                if (F.cells[off(b, i, j)] & CGM_REST) {
-                    for (const auto &r : p3_reads_u) mark(b, i + r[0], j + r[1], CGM_U);
-                    for (const auto &r : p3_reads_t) mark(b, i + r[0], j + r[1], CGM_T);
-                }
-        for (int j = j0; j <= j1; ++j)
-            for (int i = i0; i <= i1; ++i)
-                if (F.cells[off(b, i, j)] & CGM_U) {
-                    for (const auto &r : p2_reads_t) mark(b, i + r[0], j + r[1], CGM_T);
-                    mark(b, i, j, CGM_S);
-                }
-        for (int j = j0; j <= j1 + 1; ++j)
-            for (int i = i0; i <= i1 + 1; ++i) {
-                if (!inside(i, j)) return bad("the extra T row / column outside the array", b, i, j);
-                if (!interior(b, i, j)) F.cells[off(b, i, j)] |= CGM_T;              // (the reference's T list: stress12T there)
-                if (F.cells[off(b, i, j)] & CGM_T)
-                    for (const auto &r : p1_reads_s) mark(b, i + r[0], j + r[1], CGM_S);
-            }
-        for (int j = j0; j <= j1; ++j)
-            for (int i = i0; i <= i1; ++i) {
-                const uint8_t f = F.cells[off(b, i, j)];
-                if (f & CGM_REST) F.cells[off(b, i, j)] |= CGM_AVG;
-                if (f & CGM_S)
-                    for (const auto &r : p0_reads_a) mark(b, i + r[0], j + r[1], CGM_AVG);
-            }
-    }
+        if (grow(b, d.jhi[b]) == NY)
+            for (int i = d.ilo[b]; i <= d.ihi[b]; ++i) F.cells[X.off(b, i, d.jhi[b])] |= EVP_CGS_FOLDROW;
+    if (X.dilate() || X.check_sum()) return -1;
     // ---- the invariants ----
-    if (F.zone_cells + F.rest_cells != n_interior) return bad("zone and rest do not add up to the interior", 0, 0, 0);
-    static const int level_of_loc[4] = {CGM_T, CGM_U, CGM_REST, CGM_REST};         // who produces a field of this location (phase 4's
-    for (int loc = 0; loc < 4; ++loc)                                               // fields: CGM_AVG, checked with it)
+    static const int level_of_loc[4] = {EVP_CGS_T, EVP_CGS_U, EVP_CGS_REST, EVP_CGS_REST};   // who produces a field of this location (phase 4's
+    for (int loc = 0; loc < 4; ++loc)                                                         // fields: EVP_CGS_AVG, checked with it)
         for (size_t k = 0; k < L[loc].dst.size(); ++k)
             for (int32_t c : {L[loc].dst[k], L[loc].a[k], L[loc].b[k]}) {
                 if (c < 0 || (size_t)c >= ncell) continue;
-                const int b = (int)((size_t)c / (size_t)plane), j = (int)(((size_t)c % (size_t)plane) / nxb) + 1, i = (int)(((size_t)c % (size_t)plane) % nxb) + 1;
-                if (!interior(b, i, j)) continue;
+                int b, i, j;
+                X.cell_of((size_t)c, b, i, j);
+                if (!X.interior(b, i, j)) continue;
                 const uint8_t f = F.cells[(size_t)c];
-                if (!(f & CGM_REST)) return bad("a cell of the fold step is not a REST cell", b, i, j);
-                if (!(f & level_of_loc[loc]) || !(f & CGM_AVG) || !(f & CGM_S)) return bad("a cell of the fold step is not evaluated at its level", b, i, j);
+                if (!(f & EVP_CGS_REST)) return X.bad("a cell of the fold step is not a REST cell", b, i, j);
+                if (!(f & level_of_loc[loc]) || !(f & EVP_CGS_AVG) || !(f & EVP_CGS_S)) return X.bad("a cell of the fold step is not evaluated at its level", b, i, j);
             }
     for (int b = 0; b < d.nblocks; ++b)
         for (int j = 1; j <= nyb; ++j)
             for (int i = 1; i <= nxb; ++i) {
-                const uint8_t f = F.cells[off(b, i, j)];
-                const bool in = interior(b, i, j);
-                if ((f & CGM_ZONE) && (f & CGM_REST)) return bad("a cell in both sets", b, i, j);
-                if (in != ((f & (CGM_ZONE | CGM_REST)) != 0)) return bad("a cell of neither set, or a ghost cell of one", b, i, j);
-                if ((f & (CGM_S | CGM_U | CGM_AVG | CGM_REST)) && !in) return bad("a phase other than stressC_T on a ghost cell", b, i, j);
-                auto need = [&](const int (*r)[2], int n, int bit) {
-                    for (int q = 0; q < n; ++q)
-                        if (interior(b, i + r[q][0], j + r[q][1]) && !(F.cells[off(b, i + r[q][0], j + r[q][1])] & bit)) return false;
-                    return true;
-                };
-                if (f & CGM_REST) {
-                    if (!(f & CGM_U) || !(f & CGM_T) || !(f & CGM_S) || !(f & CGM_AVG)) return bad("a REST cell without its own levels", b, i, j);
-                    if (!need(p3_reads_u, 3, CGM_U)) return bad("stress12U read where phase 2 does not run, near", b, i, j);
-                    if (!need(p3_reads_t, 3, CGM_T)) return bad("stresspT read where phase 1 does not run, near", b, i, j);
-                }
-                if ((f & CGM_U) && (!need(p2_reads_t, 4, CGM_T) || !(f & CGM_S))) return bad("etax2T / shearU read where it is not produced, near", b, i, j);
-                if (f & CGM_T) {
-                    for (const auto &r : p1_reads_s)
-                        if (!inside(i + r[0], j + r[1])) return bad("phase 1 loads outside the array", b, i, j);
-                    if (!need(p1_reads_s, 4, CGM_S)) return bad("shearU read where phase 0 does not run, near", b, i, j);
-                }
-                if ((f & CGM_S) && !need(p0_reads_a, 3, CGM_AVG)) return bad("an average read where phase 4 does not run, near", b, i, j);
-                if ((f & (CGM_S | CGM_U | CGM_AVG | CGM_REST)) && !(inside(i - 1, j - 1) && inside(i + 1, j + 1))) return bad("a stencil outside the array", b, i, j);
+                if (X.check_cell(b, i, j)) return -1;
                 // (no item forms anything on the fold or beyond it)
-                if ((f & CGM_ZONE))
+                if (F.cells[X.off(b, i, j)] & EVP_CGS_ZONE)
                     for (int loc = 0; loc < 4; ++loc)
-                        if (at_fold(loc, grow(b, j + strip_form_top(loc)))) return bad("the marched kernel forms a value on the fold above", b, i, j);
+                        if (at_fold(loc, grow(b, j + strip_form_top(loc)))) return X.bad("the marched kernel forms a value on the fold above", b, i, j);
             }
-    // ---- the workgroups of each phase ----
-    const int gx = (nxb + 63) / 64, gy = (nyb + 3) / 4;
-    const int bit[5] = {CGM_S, CGM_T, CGM_U, CGM_REST, CGM_AVG};
-    for (int k = 0; k < 5; ++k) {
-        std::vector<uint8_t> on((size_t)gx * gy * d.nblocks, 0);
-        for (int b = 0; b < d.nblocks; ++b)
-            for (int j = 1; j <= nyb; ++j)
-                for (int i = 1; i <= nxb; ++i)
-                    if (F.cells[off(b, i, j)] & bit[k]) on[((size_t)b * gy + (size_t)(j - 1) / 4) * gx + (size_t)(i - 1) / 64] = 1;
-        for (size_t w = 0; w < on.size(); ++w)
-            if (on[w]) F.wg[k].push_back((int32_t)w);
-    }
+    X.workgroups({EVP_CGS_S, EVP_CGS_T, EVP_CGS_U, EVP_CGS_REST, EVP_CGS_AVG});
     return 1;
 }
 

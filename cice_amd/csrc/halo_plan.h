@@ -220,35 +220,49 @@ int strip_items(const std::vector<StripZone> &zones, int ex, int ey, int lo0, lo
 // 1 for every window of `tiles` that lies inside one of the rectangles (the marched kernel owns its cells), 0: cg_one keeps it
 void strip_windows(const std::vector<StripZone> &zones, const std::vector<int32_t> &tiles, std::vector<uint8_t> &in_zone);
 
-// ---- the marched kernel beside the fused chain on a rank with neighbours on other ranks (evp_host_cgrid.cpp: "zone marched + frame") ----
-// A rank's interior cells split in two: the ZONE -- the cells the marched kernel's items own -- and the FRAME, every other interior
-// cell, which the frame variants of the three fused kernels advance (evp_cgrid.hip: cg_frame_*).  A frame cell reads intermediates of
-// its neighbours, so each phase also runs on the zone cells the next one reads ("dilation": stored to scratch arrays only):
-//   level C (momentum step) on the frame cells; it reads etax2T around its three corners and the new stresspT / stressmT of its east and
-//           north neighbour (T cells within one of it), and shearU at its own, south and west corner;
-//   level T (stressC_T) on those T cells and on the reference's extra T row and column (ghost cells i = ihi + 1, j = jhi + 1, which keep
-//           stress12T only); it reads shearU at its four corners (own, west, south, south-west);
-//   level S (strain_rates_U's shear) on every interior cell one of the two reads shearU of.
-// cells: per array cell the CGF_* bits; wg[k]: the workgroups of 64 x 4 cells ((b * gy + by) * gx + bx, gx = ceil(nx_block / 64), gy =
-// ceil(ny_block / 4)) that hold a cell of level S / T / C, ascending.
-enum { CGF_FRAME = 1, CGF_S = 2, CGF_T = 4, CGF_ZONE = 8 };
-struct CgFramePlan {
+// The rectangles of a rank from its halo plan: the table of ex x ey windows (tiles, x 4 as above), the map of the cells that have a
+// ghost image among the rank's own copies, and strip_zones with both.  last_image_row: a ghost cell in a global row above it is no
+// image (build_cg_march_fold: the rows the fold step fills); STRIP_EVERY_IMAGE: every ghost cell with a source is one.
+constexpr int STRIP_EVERY_IMAGE = 1 << 30;
+void plan_strip_zones(const cice_evp_hip_dims &d, const HaloPlan &P, int ex, int ey, int min_cols, int last_image_row, std::vector<int32_t> &tiles,
+                      std::vector<StripZone> &zones);
+
+// ---- the marched kernel beside list-driven kernels: a rank's interior cells split in two ----
+// The ZONE -- the cells cg_strip's items own -- and the REST, every other interior cell, which list-driven variants of the un-fused or
+// fused kernels advance (evp_cgrid.hip).  Two schedules split a rank this way: several ranks (build_cg_frame; the rest is the FRAME
+// around each block's rectangle) and a tripole / tripoleT grid on one rank (build_cg_march_fold; the rest is the band under the fold and
+// the block edges).  A rest cell reads intermediates of its neighbours, so each level also runs on the zone cells the next level reads
+// ("dilation"; a zone cell evaluated for a rest cell's sake stores to scratch arrays only).  Each plan is a table of reads -- level, the
+// level that produces what it reads, offsets, in halo_plan.cpp -- which one helper walks to mark the cells of every level and walks
+// again to check them.  Level T (stressC_T) also runs on the reference's extra T row and column (ghost cells i = ihi + 1, j = jhi + 1,
+// which keep stress12T only); no other level runs on a ghost cell.
+// cells: per array cell the EVP_CGS_* bits (evp_device.h); wg[k]: the workgroups of 64 x 4 cells ((b * gy + by) * gx + bx, gx =
+// ceil(nx_block / 64), gy = ceil(ny_block / 4)) that hold a cell of the plan's k-th level, ascending.
+// Both planners return 1 and the plan; 0 with `why` where the schedule does not apply; -1 with `why` when an invariant of the plan does
+// not hold: the two sets are disjoint and cover the interior; a rest cell runs every level itself; every value a level reads at an
+// interior cell is produced by the level before it (or is the previous subcycle's); level T's loads, and the stencil of every other
+// evaluated cell (one cell around it), lie inside the block's array.
+struct CgSplitPlan {
     std::vector<uint8_t> cells;
-    std::vector<int32_t> wg[3];
-    long zone_cells = 0, frame_cells = 0;
+    std::vector<int32_t> wg[5];
+    long zone_cells = 0, rest_cells = 0;
 };
-// items: x 6 as strip_items makes them (may be empty: every interior cell is a frame cell).  Returns 1 and the plan; 0 with `why` when
-// the rank has no neighbour on another rank (nothing to plan: the one-launch schedule serves it); -1 with `why` when one of the plan's
-// invariants does not hold -- the two sets are disjoint and cover the interior; every cell a peer receives and every cell with a ghost
-// image on this rank is a frame cell; every shearU / etax2T / stresspT a level reads at an interior cell is produced by the level
-// before it; every cell a workgroup evaluates has its whole stencil (one cell around it) inside the block's array.
+
+// ---- several ranks (evp_host_cgrid.cpp: "zone marched + frame"): the frame variants of the three fused kernels, cg_frame_* ----
+//   level C (momentum step; EVP_CGS_REST) on the frame cells; it reads etax2T around its three corners and the new stresspT / stressmT of
+//           its east and north neighbour (T cells within one of it), and shearU at its own, south and west corner;
+//   level T (stressC_T) on those T cells; it reads shearU at its four corners (own, west, south, south-west);
+//   level S (strain_rates_U's shear) on every interior cell one of the two reads shearU of.
+// wg[0 .. 2]: levels S, T, C.  items: x 6 as strip_items makes them (may be empty: every interior cell is a frame cell).  Declines (0)
+// when the rank has no neighbour on another rank: the one-launch schedule serves it.  Its own invariant: every cell a peer receives and
+// every cell with a ghost image on this rank is a frame cell.
+using CgFramePlan = CgSplitPlan;
 int build_cg_frame(const cice_evp_hip_dims &d, const HaloPlan &P, const std::vector<int32_t> &items, CgFramePlan &F, std::string &why);
 
-// ---- the marched kernel on a tripole / tripoleT grid on one rank (evp_host_cgrid.cpp: "marched zone + fold band") ----
-// The rank's interior cells split in two again: the ZONE, the cells cg_strip's items own -- strip_zones' rectangles, cut from the top in
-// the blocks at the fold until the fold rule holds for every item -- and the REST: the band under the fold and the block edges, which
-// list-driven variants of the five un-fused phase kernels advance (evp_cgrid.hip: cg_band_*), with the fold steps of the five-phase
-// schedule.  The fold rule (what cg_strip forms, by field location and row, counted from its loop; jb = an item's last owned row):
+// ---- a tripole / tripoleT grid on one rank (evp_host_cgrid.cpp: "marched zone + fold band"): the five un-fused phase kernels, cg_band_*,
+// with the fold steps of the five-phase schedule ----
+// The zone: strip_zones' rectangles, cut from the top in the blocks at the fold until the fold rule holds for every item.  The fold rule
+// (what cg_strip forms, by field location and row, counted from its loop; jb = an item's last owned row):
 //   * nothing is FORMED at a point on the fold or beyond it.  The kernel forms, up to row jb + 1, the face -> corner and face <-> face
 //     averages of the previous subcycle's velocities (corner, N face, E face), the shear at the corner and stressC_T at the centre; up
 //     to row jb deltaU, etax2U and stress12U (corner) and the momentum step (E and N face): strip_form_top.  On the fold lie row NY of
@@ -257,18 +271,16 @@ int build_cg_frame(const cice_evp_hip_dims &d, const HaloPlan &P, const std::vec
 //     fold step of the previous subcycle left there: no fold-list source or destination may be a zone cell, so the fold step of a
 //     subcycle finds every operand written by the REST's kernels on its own stream.
 //   * the static arrays the kernel derives must be the caller's on every cell an item derives them for: `geo` (below).
-// Per level of the five-phase chain the cells it has to be evaluated on, each dilated by what the next one reads of it:
-//   phase 3 (div_stress + stepu_C / stepv_C) on the REST cells; it reads stress12U at its own, south and west corner, the new stresspT /
-//           stressmT at its own cell and the east / north neighbour;
-//   phase 2 (etax2U, stressC_U) on those corners; it reads etax2T at the four T cells around the corner and the corner's shearU;
-//   phase 1 (stressC_T) on those T cells and the reference's extra row and column (ghost cells i = ihi + 1, j = jhi + 1: stress12T only);
-//           it reads shearU at its four corners;
-//   phase 0 (strain_rates_U) on those corners; it reads uvelN / vvelE at the cell, its east / north neighbour, uvelU / vvelU at the cell;
-//   phase 4 (the averages, AFTER the two sets have met again) on the REST cells and on every cell phase 0 of the next subcycle reads.
-// A zone cell evaluated for a REST cell's sake stores to scratch arrays only (phase 4: uvelN, vvelE, uvelU, vvelU are not the marched
-// kernel's, the arrays themselves).  cells: the CGM_* bits; wg[k]: the workgroups of 64 x 4 cells of phase k, ascending, numbered as
-// in CgFramePlan.
-enum { CGM_REST = 1, CGM_S = 2, CGM_T = 4, CGM_ZONE = 8, CGM_U = 16, CGM_AVG = 32, CGM_FOLDROW = 64 };
+// The levels:
+//   phase 3 (div_stress + stepu_C / stepv_C; EVP_CGS_REST) on the REST cells; it reads stress12U at its own, south and west corner, the new
+//           stresspT / stressmT at its own cell and the east / north neighbour;
+//   phase 2 (etax2U, stressC_U; EVP_CGS_U) on those corners; it reads etax2T at the four T cells around the corner and the corner's shearU;
+//   phase 1 (stressC_T; EVP_CGS_T) on those T cells; it reads shearU at its four corners;
+//   phase 0 (strain_rates_U; EVP_CGS_S) on those corners; it reads uvelN / vvelE at the cell, its east / north neighbour, uvelU / vvelU at
+//           the cell;
+//   phase 4 (the averages, AFTER the two sets have met again; EVP_CGS_AVG) on the REST cells and on every cell phase 0 of the next subcycle
+//           reads (uvelN, vvelE, uvelU, vvelU are not the marched kernel's: phase 4 stores to the arrays themselves on zone cells too).
+// wg[0 .. 4]: phases 0 .. 4.  EVP_CGS_FOLDROW marks the interior cells of global row NY.
 // last row, relative to an item's last owned row, at which cg_strip forms a value of field location loc (0 centre, 1 NE corner, 2 E
 // face, 3 N face) -- from the kernel's loop: it runs to j = jb + 1 and evaluates levels S and T and both face averages (the N-face one
 // in the last subcycle of a call) on row j, levels U and C on row j - 1
@@ -292,22 +304,18 @@ inline int strip_form_top(int loc)
         if (l.loc == loc) top = top > l.last ? top : l.last;
     return top;
 }
-struct CgMarchFoldPlan {
-    std::vector<uint8_t> cells;
-    std::vector<int32_t> wg[5];
+struct CgMarchFoldPlan : CgSplitPlan {
     std::vector<int32_t> items;            // x 6, as strip_items makes them
     std::vector<StripZone> zones;
-    long zone_cells = 0, rest_cells = 0;
     int band_rows = 0;                     // rows from the zone's top row (exclusive) to NY, on the blocks at the fold (the most)
     int seg = 0, lengths = 0;              // rows per segment; 1: the items own lanes >= 3 (the kernel forms six of the eight lengths)
 };
 // geo (may be null: everything holds): what the caller's static arrays allow for the rectangle z -- 0 an identity fails on a cell the
 // kernel would derive it for (a window row comes off the top and the question is asked again), 1 the 15 derived arrays hold, 3 the six
 // formed lengths hold as well.  The items own lanes >= 3 (lengths = 1) when every rectangle answers 3 and want_len != 0.
-// Returns 1 and the plan; 0 with `why` where the schedule does not apply (no fold, several ranks or split fold rows, no rectangle
-// left under the band); -1 with `why` when an invariant of the plan does not hold: the sets are disjoint and cover the interior; every
-// fold-list source and destination that is an interior cell is a REST cell (evaluated at its level); every value a phase reads at an
-// interior cell is produced by the phase before it (or is the previous subcycle's); every evaluated cell has its stencil in the array.
+// Declines (0) without a fold, on several ranks or with split fold rows, and when no rectangle is left under the band.  Its own
+// invariants: every fold-list source and destination that is an interior cell is a REST cell, evaluated at its level; no item forms a
+// value on the fold.
 struct CgGeoCheck {
     virtual int operator()(const StripZone &z) const = 0;
     virtual ~CgGeoCheck() {}
