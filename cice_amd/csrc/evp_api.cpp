@@ -342,25 +342,22 @@ int cice_evp_hip_init(const cice_evp_hip_dims *dims, const cice_evp_hip_params *
     S.use_graph = !(env_test("CICE_EVP_HIP_NOGRAPH") && std::atoi(env_test("CICE_EVP_HIP_NOGRAPH")));
 
     for (auto &p : S.stat)
-        if (alloc_d(&p, S.n)) return -1;
+        if (S.mem.alloc(p, S.n, true)) return -1;
     for (int f = F_STRENGTH; f < F_COUNT; ++f) {
         if (f == F_UVEL || f == F_VVEL) continue;
-        if (alloc_d(&S.in[f], S.n)) return -1;
+        if (S.mem.alloc(S.in[f], S.n, true)) return -1;
     }
     S.nuv = S.n + (size_t)S.plan.tail;          // + staging slots for raw seam values of other ranks (tripole, any layout)
     for (int k = 0; k < 2; ++k) {
-        if (alloc_d(&S.u[k], S.nuv) || alloc_d(&S.v[k], S.nuv)) return -1;
+        if (S.mem.alloc(S.u[k], S.nuv, true) || S.mem.alloc(S.v[k], S.nuv, true)) return -1;
         for (auto &p : S.sig[k])
-            if (alloc_d(&p, S.n)) return -1;
+            if (S.mem.alloc(p, S.n, true)) return -1;
     }
-    if (alloc_d(&S.hte, S.n) || alloc_d(&S.htn, S.n) || alloc_d(&S.vrelfac, S.n)) return -1;
+    if (S.mem.alloc(S.hte, S.n, true) || S.mem.alloc(S.htn, S.n, true) || S.mem.alloc(S.vrelfac, S.n, true)) return -1;
     S.flags = EVP_F_VRELFAC;
     S.flags_allowed = ~0u;
     if (env_test("CICE_EVP_HIP_FLAGS")) S.flags_allowed = (unsigned)std::strtoul(env_test("CICE_EVP_HIP_FLAGS"), nullptr, 0);
-    HIPC(hipMalloc((void **)&S.mask, S.n));
-    HIPC(hipMemsetAsync(S.mask, 0, S.n, S.stream));
-    HIPC(hipMalloc((void **)&S.blk, nb * sizeof(int4)));
-    HIPC(hipMemcpy(S.blk, hb.data(), nb * sizeof(int4), hipMemcpyHostToDevice));
+    if (S.mem.alloc(S.mask, S.n, true) || S.mem.upload(S.blk, hb)) return -1;
     if (upload_lists()) return -1;
     if (build_push_table()) return -1;
     if (S.push_ok) S.flags |= EVP_F_PUSH;
@@ -609,11 +606,11 @@ int cice_evp_hip_set_post_geometry(const double *dxU, const double *dyU, const d
     if (!dxU || !dyU || !tarear) return fail(-1, "null argument");
     const double *src[3] = {dxU, dyU, tarear};
     for (int k = 0; k < 3; ++k) {
-        if (!S.post_geo[k] && alloc_d(&S.post_geo[k], S.n)) return -1;
+        if (!S.post_geo[k] && S.mem.alloc(S.post_geo[k], S.n, true)) return -1;
         if (h2d(S.post_geo[k], src[k])) return -1;
     }
     for (auto &p : S.post_out)
-        if (!p && alloc_d(&p, S.n)) return -1;
+        if (!p && S.mem.alloc(p, S.n, true)) return -1;
     HIPC(hipStreamSynchronize(S.stream));
     S.have_post_geo = true;
     return 0;
@@ -639,7 +636,7 @@ int cice_evp_hip_dyn_finish(double *strocnxU, double *strocnyU)
     if (!S.ready || !S.uploaded) return fail(-1, "state not uploaded");
     if (!strocnxU || !strocnyU) return fail(-1, "null argument");
     for (int k = 5; k < 7; ++k)
-        if (!S.post_out[k] && alloc_d(&S.post_out[k], S.n)) return -1;
+        if (!S.post_out[k] && S.mem.alloc(S.post_out[k], S.n, true)) return -1;
     // inout: cells outside the ice keep the caller's values (dyn_prep2 zeroes them, :776-784)
     if (h2d(S.post_out[5], strocnxU) || h2d(S.post_out[6], strocnyU)) return -1;
     EvpArgs A;
@@ -804,7 +801,8 @@ int cice_evp_hip_run(double *stressp_1, double *stressp_2, double *stressp_3, do
         T.len = S.n;
         T.vec2 = 1;
         for (int k = 0; k < 12; ++k) {
-            if (!S.sig_snap[k]) HIPC(hipMalloc((void **)&S.sig_snap[k], S.n * sizeof(double)));
+            if (!S.sig_snap[k])
+                if (int rc = S.mem.alloc(S.sig_snap[k], S.n)) return rc;
             T.src[T.n] = S.sig[cur0][k]; T.dst[T.n] = S.sig_snap[k]; ++T.n;
             if ((((uintptr_t)T.src[k]) | ((uintptr_t)T.dst[k])) & 15u) T.vec2 = 0;
         }
@@ -835,7 +833,7 @@ int cice_evp_hip_run(double *stressp_1, double *stressp_2, double *stressp_3, do
             if (int rc = cice_evp_hip_subcycle(ndte)) return rc;
             // the resident kernel is off from here on (res_mode = 0): the snapshot has no further use
             HIPC(hipStreamSynchronize(S.stream));
-            for (auto &q : S.sig_snap) { if (q) (void)hipFree(q); q = nullptr; }
+            for (auto &q : S.sig_snap) S.mem.free_one(q);
         }
     }
     // only the documented outputs travel back
@@ -918,6 +916,13 @@ int cice_evp_hip_time_kernels(int32_t nrep, double *out3)
 }
 
 #ifdef CICE_EVP_HIP_TESTING
+int cice_evp_hip_debug_device_allocs(int64_t *count)
+{
+    if (!count) return fail(-1, "null argument");
+    *count = (int64_t)(S.mem.owned.size() + march_allocs() + cgrid_allocs());
+    return 0;
+}
+
 // Per-CU record of the last resident launch (16 x 16 tiles): 2048 CUs x {lock, stamp, ice-holding waves
 // on SIMD 0..3, 0, 0}; for tools that check how evenly the workgroups spread their waves.
 int cice_evp_hip_debug_cuload(int32_t *out, int32_t n)

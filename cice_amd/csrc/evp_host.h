@@ -30,6 +30,7 @@
 #include <map>
 #include <string>
 #include <tuple>
+#include <type_traits>
 #include <vector>
 
 #include "../../include/cice_evp_hip.h"
@@ -68,6 +69,35 @@ enum Field {
 
 #define EVP_RES2_COOP_DEFAULT 0      // rim T-cells by corners in the resident B-grid kernel: the product's choice where it is possible
 
+// Owner of a set of device allocations by registration: whatever alloc / alloc_fine / upload hand out is released by free_all (or,
+// for a buffer that is replaced on its own, free_one).  A pointer INTO somebody else's allocation is never registered: free_one
+// only nulls it.  No destructor: a global's would call HIP after the runtime has shut down.
+struct DevicePool {
+    std::vector<void *> owned;
+    template <class T> int alloc(T *&p, size_t n, bool zero = false);      // zero: cleared on S.stream
+    int alloc_fine(void *&p, size_t bytes);                                // fine-grained (peers store into it): cleared, blocking
+    // a host vector on the device: room for max(1, n) elements, n of them copied; the copy blocks, so the vector may go at once
+    template <class T, class V> int upload(T *&p, const std::vector<V> &v);
+    template <class T> void free_one(T *&p)
+    {
+        const auto it = std::find(owned.begin(), owned.end(), static_cast<void *>(p));
+        if (it != owned.end()) {
+            (void)hipFree(p);
+            owned.erase(it);
+        }
+        p = nullptr;
+    }
+    void free_all()
+    {
+        for (void *p : owned) (void)hipFree(p);
+        owned.clear();
+    }
+};
+// ... for scratch memory of one function: released on every return path.  Locals only.
+struct ScratchPool : DevicePool {
+    ~ScratchPool() { free_all(); }
+};
+
 struct State {
     bool ready = false;
     // A rank that holds NO blocks (the reference allows it: a cartesian distribution whose processor grid does not divide
@@ -81,6 +111,7 @@ struct State {
     std::vector<int32_t> ilo, ihi, jlo, jhi, iglob0, jglob0;
     std::vector<int32_t> gtab[6];   // the global block table (gi0 gj0 gnx gny gowner glocal): plans built after init need it
     int device = 0;
+    DevicePool mem;              // every device allocation behind a pointer of this struct and of its nested ones
     size_t plane = 0, n = 0;     // nx*ny, nx*ny*nblocks
     int max_ni = 0, max_nj = 0;
     int tyb = 4;
@@ -351,48 +382,30 @@ constexpr size_t CG_DIRECT_INBOX_OFF = CG_DIRECT_ERR_OFF + 64;
 
 uint64_t host_identity();   // evp_host_mailbox.cpp
 // evp_host_common.cpp
-int alloc_d(double **p, size_t n);
 void free_all();
 cice_evp_hip_dims host_dims();      // S.d with its six per-block tables pointing at the copies init kept
-// a host vector on the device: room for max(1, n) elements, n of them copied; the copy blocks, so the vector may go at once
-template <class T, class V> int upload(T *&p, const std::vector<V> &v)
+template <class T> int DevicePool::alloc(T *&p, size_t n, bool zero)
+{
+    const size_t bytes = n * sizeof(std::conditional_t<std::is_void<T>::value, char, T>);      // (a void *: n bytes)
+    HIPC(hipMalloc((void **)&p, bytes));
+    owned.push_back(p);
+    if (zero) HIPC(hipMemsetAsync(p, 0, bytes, S.stream));
+    return 0;
+}
+inline int DevicePool::alloc_fine(void *&p, size_t bytes)
+{
+    HIPC(hipExtMallocWithFlags(&p, bytes, hipDeviceMallocFinegrained));
+    owned.push_back(p);
+    HIPC(hipMemset(p, 0, bytes));
+    return 0;
+}
+template <class T, class V> int DevicePool::upload(T *&p, const std::vector<V> &v)
 {
     HIPC(hipMalloc((void **)&p, std::max<size_t>(1, v.size()) * sizeof(V)));
+    owned.push_back(p);
     if (!v.empty()) HIPC(hipMemcpy(p, v.data(), v.size() * sizeof(V), hipMemcpyHostToDevice));
     return 0;
 }
-// Owner of a set of device allocations by registration: whatever alloc / upload hand out is released by free_all (or, for a buffer
-// that is replaced on its own, free_one).  No destructor: a global's would call HIP after the runtime has shut down.
-struct DevicePool {
-    std::vector<void *> owned;
-    template <class T> int alloc(T *&p, size_t n, bool zero = false)      // zero: cleared on S.stream
-    {
-        HIPC(hipMalloc((void **)&p, n * sizeof(T)));
-        owned.push_back(p);
-        if (zero) HIPC(hipMemsetAsync(p, 0, n * sizeof(T), S.stream));
-        return 0;
-    }
-    template <class T, class V> int upload(T *&p, const std::vector<V> &v)
-    {
-        if (int rc = evp_host::upload(p, v)) return rc;
-        owned.push_back(p);
-        return 0;
-    }
-    template <class T> void free_one(T *&p)
-    {
-        const auto it = std::find(owned.begin(), owned.end(), static_cast<void *>(p));
-        if (it != owned.end()) {
-            (void)hipFree(p);
-            owned.erase(it);
-        }
-        p = nullptr;
-    }
-    void free_all()
-    {
-        for (void *p : owned) (void)hipFree(p);
-        owned.clear();
-    }
-};
 int h2d(double *dst, const double *src);
 int d2h(double *dst, const double *src);
 // batched variants: arrays the caller page-locked travel in ONE gather / scatter launch, the rest as copies
@@ -445,11 +458,13 @@ int tune_after_upload();
 bool march_wanted();
 int march_run(int ndte);
 void march_free();
+size_t march_allocs();         // device allocations its pool has registered (test read-out)
 int march_direct_error();     // a ring neighbour never signalled (direct exchange of the marching path)
 // evp_host_mailbox.cpp
 int direct_check_error();
 // evp_host_cgrid.cpp
 void cgrid_free();
+size_t cgrid_allocs();
 std::string cgrid_schedule();     // "" unless the C grid runs with the fold exchange (tripole fold rows on several ranks)
 
 }  // namespace evp_host

@@ -172,6 +172,8 @@ struct CGridState {
 };
 static CGridState CG;
 
+size_t cgrid_allocs() { return CG.mem.owned.size(); }
+
 void cgrid_free()
 {
     CG.mem.free_all();

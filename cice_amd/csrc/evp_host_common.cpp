@@ -29,13 +29,6 @@ int fail(int code, const char *fmt, ...)
 
 State S;
 
-int alloc_d(double **p, size_t n)
-{
-    HIPC(hipMalloc((void **)p, n * sizeof(double)));
-    HIPC(hipMemsetAsync(*p, 0, n * sizeof(double), S.stream));
-    return 0;
-}
-
 cice_evp_hip_dims host_dims()
 {
     cice_evp_hip_dims d = S.d;
@@ -44,105 +37,18 @@ cice_evp_hip_dims host_dims()
     return d;
 }
 
+// The device memory (S.mem), then what is not memory.  The caller resets the state itself (S = State()).
 void free_all()
 {
-    auto F = [](auto *&p) {
-        if (p) (void)hipFree((void *)p);
-        p = nullptr;
-    };
-    for (auto &p : S.stat) F(p);
-    for (auto &p : S.in) F(p);
-    for (int k = 0; k < 2; ++k) {
-        F(S.u[k]);
-        F(S.v[k]);
-        for (auto &p : S.sig[k]) F(p);
-    }
-    for (auto &p : S.sig_snap) F(p);
-    F(S.hte);
-    F(S.htn);
-    F(S.vrelfac);
-    F(S.res_err); F(S.res_tab);
-    F(S.res2_ring); F(S.res2_cnt); F(S.res2_pub); F(S.res2_perm); F(S.res2_late); F(S.res2_nact); F(S.res2_nlate); F(S.res2_live); F(S.res2_celltile); F(S.res2_cuload); F(S.res2_prof);
-    if (S.res2_rec_owned) { F(S.res2_rec[0]); F(S.res2_rec[1]); }
-    S.res2_rec[0] = S.res2_rec[1] = nullptr;
-    S.res2_rec_owned = true;
-    S.res_remote = false;
-    S.res2_par = 0; S.res2_epoch = 0;
-    F(S.res2_rimg); F(S.res2_peer_rec); F(S.res2_peer_rstride);
-    F(S.res2_order); F(S.res2_seam); F(S.res2_img3);
-    if (S.res2_raw_owned) { F(S.res2_rec_raw[0]); F(S.res2_rec_raw[1]); }
-    S.res2_rec_raw[0] = S.res2_rec_raw[1] = nullptr;
-    S.res2_raw_owned = true;
-    F(S.res2_rraw); F(S.res2_peer_raw); F(S.res2_peer_raw_stride);
-    for (auto &p : S.post_geo) F(p);
-    for (auto &p : S.post_out) F(p);
-    F(S.push);
-    F(S.mask);
-    F(S.blk);
-    F(S.h_local_dst);
-    F(S.h_local_src);
-    F(S.h_local_sign);
-    F(S.h_seam_a); F(S.h_seam_b); F(S.h_seam_pole); F(S.h_late_dst); F(S.h_late_src); F(S.h_late_sign);
-    F(S.h_fin_dst); F(S.h_fin_a); F(S.h_fin_b); F(S.h_fin_coef);
-    F(S.h_stress_dst); F(S.h_stress_src); F(S.h_stress_own_dst); F(S.h_stress_own_src); F(S.h_stress_corner_dst); F(S.h_stress_corner_src);
-    {
-        State::Prep &Q = S.prep;
-        F(Q.tmask); F(Q.umask); F(Q.umask_old); F(Q.umask_old32); F(Q.tmphm); F(Q.hm); F(Q.tarea); F(Q.uarea); F(Q.fcor); F(Q.hwater); F(Q.aicen); F(Q.vicen); F(Q.tbt); Q.ncat = 0;
-        for (auto &q : Q.t) F(q);
-        F(Q.tmass); F(Q.umass); F(Q.maskd); F(Q.ss_tltxU); F(Q.ss_tltyU); F(Q.strairxU); F(Q.strairyU);
-        F(Q.strtltx); F(Q.strtlty); F(Q.flagword); F(Q.c_dst); F(Q.c_src); F(Q.c_vsign); F(Q.tf_dst); F(Q.tf_a); F(Q.tf_b); F(Q.tf_flip); F(Q.tf_tmp);
-        S.prep = State::Prep();
-    }
-    F(S.forcing.earea); F(S.forcing.narea); F(S.forcing.uvm); F(S.forcing.epm); F(S.forcing.npm);
-    S.forcing = State::Forcing();
-    F(S.h_send_src);
-    F(S.h_recv_dst);
-    F(S.h_recv_sign);
-    F(S.msk.send_src); F(S.msk.recv_dst); F(S.msk.recv_slot); F(S.msk.recv_sign); F(S.msk.send_addr); F(S.msk.send_pstride);
-    S.msk = State::Masked();
-    F(S.sendbuf);
-    F(S.recvbuf);
-    F(S.cgx.send_src); F(S.cgx.recv_dst); F(S.cgx.recv_sign); F(S.cgx.sendbuf); F(S.cgx.recvbuf); F(S.cgx.send_addr); F(S.cgx.send_pstride); F(S.cgx.peer_flag);
-    S.cgx = State::CgX();
+    S.mem.free_all();
     for (void *q : S.direct.opened) (void)hipIpcCloseMemHandle(q);
-    F(S.direct.mailbox); F(S.direct.d_dx); F(S.direct.d_dx_m); F(S.direct.d_cnt); F(S.direct.send_addr); F(S.direct.send_pstride); F(S.direct.peer_flag);
-    S.direct = State::Direct();
     for (auto &kv : S.graphs) (void)hipGraphExecDestroy(kv.second);
-    S.graphs.clear();
-    if (S.ev0) (void)hipEventDestroy(S.ev0);
-    if (S.ev1) (void)hipEventDestroy(S.ev1);
-    if (S.ev2) (void)hipEventDestroy(S.ev2);
-    if (S.ev3) (void)hipEventDestroy(S.ev3);
-    for (auto &e : S.evm) { if (e) (void)hipEventDestroy(e); e = nullptr; }
-    S.ev0 = S.ev1 = S.ev2 = S.ev3 = nullptr;
+    for (hipEvent_t e : {S.ev0, S.ev1, S.ev2, S.ev3, S.evm[0], S.evm[1], S.ev_pack, S.ev_halo})
+        if (e) (void)hipEventDestroy(e);
     if (S.have_comm) (void)ncclCommDestroy(S.comm);
-    S.have_comm = false;
-    {
-        State::FoldX &F = S.foldx;
-        if (F.cells) (void)hipFree(F.cells);
-        if (F.seam_dst) (void)hipFree(F.seam_dst);
-        if (F.seam_slot) (void)hipFree(F.seam_slot);
-        if (F.seam_one) (void)hipFree(F.seam_one);
-        for (auto &p : F.dst) if (p) (void)hipFree(p);
-        for (auto &p : F.scr) if (p) (void)hipFree(p);
-        F = State::FoldX();
-    }
     for (auto &kv : S.pinned) (void)hipHostUnregister(const_cast<void *>(kv.first));
-    S.sig_valid = false;
-    S.pinned.clear();
-    for (auto &kv : S.splits) {
-        if (kv.second.d_boundary) (void)hipFree(kv.second.d_boundary);
-        if (kv.second.d_interior) (void)hipFree(kv.second.d_interior);
-        if (kv.second.d_all) (void)hipFree(kv.second.d_all);
-    }
-    S.splits.clear();
-    if (S.ev_pack) (void)hipEventDestroy(S.ev_pack);
-    if (S.ev_halo) (void)hipEventDestroy(S.ev_halo);
-    S.ev_pack = S.ev_halo = nullptr;
     if (S.stream_comm) (void)hipStreamDestroy(S.stream_comm);
-    S.stream_comm = nullptr;
     if (S.stream) (void)hipStreamDestroy(S.stream);
-    S.stream = nullptr;
 }
 
 // Copies blocks 1..nblocks of a host (nx,ny,max_blocks) array: contiguous prefix.
@@ -271,45 +177,28 @@ int derive_metrics(const double *HTE, const double *HTN, const double *dxT, cons
 int upload_lists()
 {
     const HaloPlan &P = S.plan;
+    // a list on the device; an empty one stays a null pointer
+    auto up = [&](const auto &v, auto *&dptr) -> int { return v.empty() ? 0 : S.mem.upload(dptr, v); };
     S.n_local = (int)P.local_dst.size();
-    if (S.n_local) {
-        HIPC(hipMalloc((void **)&S.h_local_dst, S.n_local * sizeof(int32_t)));
-        HIPC(hipMalloc((void **)&S.h_local_src, S.n_local * sizeof(int32_t)));
-        HIPC(hipMalloc((void **)&S.h_local_sign, S.n_local));
-        HIPC(hipMemcpy(S.h_local_dst, P.local_dst.data(), S.n_local * sizeof(int32_t), hipMemcpyHostToDevice));
-        HIPC(hipMemcpy(S.h_local_src, P.local_src.data(), S.n_local * sizeof(int32_t), hipMemcpyHostToDevice));
-        HIPC(hipMemcpy(S.h_local_sign, P.local_sign.data(), S.n_local, hipMemcpyHostToDevice));
-    }
-    auto up32 = [&](const std::vector<int32_t> &v, int32_t *&dptr) -> int {
-        if (v.empty()) return 0;
-        HIPC(hipMalloc((void **)&dptr, v.size() * sizeof(int32_t)));
-        HIPC(hipMemcpy(dptr, v.data(), v.size() * sizeof(int32_t), hipMemcpyHostToDevice));
-        return 0;
-    };
+    if (up(P.local_dst, S.h_local_dst) || up(P.local_src, S.h_local_src) || up(P.local_sign, S.h_local_sign)) return -1;
     S.n_seam = (int)P.seam_a.size();
     S.n_pole = (int)P.seam_pole.size();
     S.n_late = (int)P.late_dst.size();
-    if (up32(P.seam_a, S.h_seam_a) || up32(P.seam_b, S.h_seam_b) || up32(P.seam_pole, S.h_seam_pole) ||
-        up32(P.late_dst, S.h_late_dst) || up32(P.late_src, S.h_late_src)) return -1;
+    if (up(P.seam_a, S.h_seam_a) || up(P.seam_b, S.h_seam_b) || up(P.seam_pole, S.h_seam_pole) ||
+        up(P.late_dst, S.h_late_dst) || up(P.late_src, S.h_late_src)) return -1;
     S.n_stress = (int)P.stress_dst.size();
-    if (up32(P.stress_dst, S.h_stress_dst) || up32(P.stress_src, S.h_stress_src)) return -1;
+    if (up(P.stress_dst, S.h_stress_dst) || up(P.stress_src, S.h_stress_src)) return -1;
     S.n_stress_own = (int)P.stress_own_dst.size();
-    if (up32(P.stress_own_dst, S.h_stress_own_dst) || up32(P.stress_own_src, S.h_stress_own_src)) return -1;
+    if (up(P.stress_own_dst, S.h_stress_own_dst) || up(P.stress_own_src, S.h_stress_own_src)) return -1;
     S.n_stress_corner = (int)P.stress_corner_dst.size();
-    if (up32(P.stress_corner_dst, S.h_stress_corner_dst) || up32(P.stress_corner_src, S.h_stress_corner_src)) return -1;
-    if (S.n_late) {
-        HIPC(hipMalloc((void **)&S.h_late_sign, S.n_late));
-        HIPC(hipMemcpy(S.h_late_sign, P.late_sign.data(), S.n_late, hipMemcpyHostToDevice));
-    }
+    if (up(P.stress_corner_dst, S.h_stress_corner_dst) || up(P.stress_corner_src, S.h_stress_corner_src)) return -1;
+    if (up(P.late_sign, S.h_late_sign)) return -1;
     S.n_fin = (int)P.fin_dst.size();
     // the list is only run on layouts that split the seam row (halo_uv: general form) or when forced for tests
     const bool fin_used = P.tail > 0 || (env_test("CICE_EVP_HIP_SEAM_FIN") && std::atoi(env_test("CICE_EVP_HIP_SEAM_FIN")));
     if (fin_used && S.n_fin > evp_halo_seam_fin_capacity()) return fail(-3, "tripole seam: %d cells to finalise on one rank (limit %d)", S.n_fin, evp_halo_seam_fin_capacity());
-    if (up32(P.fin_dst, S.h_fin_dst) || up32(P.fin_a, S.h_fin_a) || up32(P.fin_b, S.h_fin_b)) return -1;
-    if (S.n_fin) {
-        HIPC(hipMalloc((void **)&S.h_fin_coef, S.n_fin));
-        HIPC(hipMemcpy(S.h_fin_coef, P.fin_coef.data(), S.n_fin, hipMemcpyHostToDevice));
-    }
+    if (up(P.fin_dst, S.h_fin_dst) || up(P.fin_a, S.h_fin_a) || up(P.fin_b, S.h_fin_b)) return -1;
+    if (up(P.fin_coef, S.h_fin_coef)) return -1;
     std::vector<int32_t> ss, rd;
     std::vector<int8_t> rs;
     for (const HaloPeer &p : P.peers) {
@@ -319,18 +208,9 @@ int upload_lists()
     }
     S.n_send = (int)ss.size();
     S.n_recv = (int)rd.size();
-    if (S.n_send) {
-        HIPC(hipMalloc((void **)&S.h_send_src, ss.size() * sizeof(int32_t)));
-        HIPC(hipMemcpy(S.h_send_src, ss.data(), ss.size() * sizeof(int32_t), hipMemcpyHostToDevice));
-        HIPC(hipMalloc((void **)&S.sendbuf, 2 * ss.size() * sizeof(double)));
-    }
-    if (S.n_recv) {
-        HIPC(hipMalloc((void **)&S.h_recv_dst, rd.size() * sizeof(int32_t)));
-        HIPC(hipMalloc((void **)&S.h_recv_sign, rs.size()));
-        HIPC(hipMemcpy(S.h_recv_dst, rd.data(), rd.size() * sizeof(int32_t), hipMemcpyHostToDevice));
-        HIPC(hipMemcpy(S.h_recv_sign, rs.data(), rs.size(), hipMemcpyHostToDevice));
-        HIPC(hipMalloc((void **)&S.recvbuf, 2 * rd.size() * sizeof(double)));
-    }
+    if (up(ss, S.h_send_src) || up(rd, S.h_recv_dst) || up(rs, S.h_recv_sign)) return -1;
+    if (S.n_send && S.mem.alloc(S.sendbuf, 2 * ss.size())) return -1;
+    if (S.n_recv && S.mem.alloc(S.recvbuf, 2 * rd.size())) return -1;
     if (P.cg_split) {        // the C grid's exchange (HaloPlan::cg_peers)
         std::vector<int32_t> cs, cr;
         std::vector<int8_t> cg;
@@ -342,13 +222,9 @@ int upload_lists()
         State::CgX &X = S.cgx;
         X.n_send = (int)cs.size();
         X.n_recv = (int)cr.size();
-        if (up32(cs, X.send_src) || up32(cr, X.recv_dst)) return -1;
-        if (X.n_send) HIPC(hipMalloc((void **)&X.sendbuf, 2 * cs.size() * sizeof(double)));
-        if (X.n_recv) {
-            HIPC(hipMalloc((void **)&X.recv_sign, cg.size()));
-            HIPC(hipMemcpy(X.recv_sign, cg.data(), cg.size(), hipMemcpyHostToDevice));
-            HIPC(hipMalloc((void **)&X.recvbuf, 2 * cr.size() * sizeof(double)));
-        }
+        if (up(cs, X.send_src) || up(cr, X.recv_dst) || up(cg, X.recv_sign)) return -1;
+        if (X.n_send && S.mem.alloc(X.sendbuf, 2 * cs.size())) return -1;
+        if (X.n_recv && S.mem.alloc(X.recvbuf, 2 * cr.size())) return -1;
     }
     return 0;
 }
@@ -390,8 +266,7 @@ int build_push_table()
         if (!placed) ok = false;
     }
     if (!ok || P.local_dst.empty()) return 0;
-    HIPC(hipMalloc((void **)&S.push, tab.size() * sizeof(int)));
-    HIPC(hipMemcpy(S.push, tab.data(), tab.size() * sizeof(int), hipMemcpyHostToDevice));
+    if (S.mem.upload(S.push, tab)) return -1;
     S.push_ok = true;
     return 0;
 }

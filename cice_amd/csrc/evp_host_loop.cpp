@@ -156,11 +156,7 @@ static int foldx_setup()
         const HaloPlan &P = S.plan;
         auto up = [&](int32_t *&dp, int &n, const std::vector<int32_t> &v) -> int {
             n = (int)v.size();
-            if (n) {
-                HIPC(hipMalloc((void **)&dp, v.size() * sizeof(int32_t)));
-                HIPC(hipMemcpy(dp, v.data(), v.size() * sizeof(int32_t), hipMemcpyHostToDevice));
-            }
-            return 0;
+            return n ? S.mem.upload(dp, v) : 0;
         };
         int n2 = 0;
         if (up(F.cells, F.n_cells, P.fold_shift_cells) || up(F.dst[0], F.n_dst[0], P.center_foldr_dst) ||
@@ -168,13 +164,10 @@ static int foldx_setup()
             up(F.seam_slot, n2, P.center_seam_slot)) return -1;
         if (F.n_seam) {
             std::vector<int8_t> one(F.n_seam, 1);
-            HIPC(hipMalloc((void **)&F.seam_one, one.size()));
-            HIPC(hipMemcpy(F.seam_one, one.data(), one.size(), hipMemcpyHostToDevice));
+            if (S.mem.upload(F.seam_one, one)) return -1;
         }
-        for (auto &p : F.scr) {
-            if (alloc_d(&p, S.nuv)) return -1;
-            HIPC(hipMemsetAsync(p, 0, S.nuv * sizeof(double), S.stream));
-        }
+        for (auto &p : F.scr)
+            if (S.mem.alloc(p, S.nuv, true)) return -1;
         F.ready = true;
     }
     return 0;
@@ -256,14 +249,7 @@ int get_tile_split(int variant, State::TileSplit **out)
     State::TileSplit ts;
     ts.nb = (int)lb.size();
     ts.ni = (int)li.size();
-    if (ts.nb) {
-        HIPC(hipMalloc((void **)&ts.d_boundary, lb.size() * sizeof(int)));
-        HIPC(hipMemcpy(ts.d_boundary, lb.data(), lb.size() * sizeof(int), hipMemcpyHostToDevice));
-    }
-    if (ts.ni) {
-        HIPC(hipMalloc((void **)&ts.d_interior, li.size() * sizeof(int)));
-        HIPC(hipMemcpy(ts.d_interior, li.data(), li.size() * sizeof(int), hipMemcpyHostToDevice));
-    }
+    if ((ts.nb && S.mem.upload(ts.d_boundary, lb)) || (ts.ni && S.mem.upload(ts.d_interior, li))) return -1;
     {   // boundary tiles first, then the rest: order of the launch that carries the exchange workgroup
         // interior tiles in XCD-chunked order: workgroup w runs on XCD w % 8, so give each XCD one
         // contiguous run of the (row-major) interior sequence -- neighbouring tiles share an L2
@@ -277,8 +263,7 @@ int get_tile_split(int variant, State::TileSplit **out)
         }
         if (chunked.size() != n) chunked = li;
         all.insert(all.end(), chunked.begin(), chunked.end());
-        HIPC(hipMalloc((void **)&ts.d_all, all.size() * sizeof(int)));
-        HIPC(hipMemcpy(ts.d_all, all.data(), all.size() * sizeof(int), hipMemcpyHostToDevice));
+        if (S.mem.upload(ts.d_all, all)) return -1;
     }
     *out = &S.splits.emplace(variant, ts).first->second;
     return 0;

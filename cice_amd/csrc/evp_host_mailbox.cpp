@@ -66,19 +66,16 @@ int direct_export(HaloBlob &B)
         // fine-grained: stores of another GPU become visible to loads here without a kernel boundary
         // (no coarse-grained fallback: without this property a peer's stores are only guaranteed
         // to be seen at kernel boundaries, and the transport would be wrong on a real node)
-        HIPC(hipExtMallocWithFlags(&X.mailbox, X.bytes, hipDeviceMallocFinegrained));
-        HIPC(hipMemset(X.mailbox, 0, X.bytes));
+        if (int rc = S.mem.alloc_fine(X.mailbox, X.bytes)) return rc;
     }
     int can_res = 0;
     if (want_res && X.rec_off) {
-        if (S.res2_rec_owned)
-            for (auto &q : S.res2_rec) { if (q) (void)hipFree(q); q = nullptr; }
+        for (auto &q : S.res2_rec) S.mem.free_one(q);         // (an earlier export's pointers into the mailbox: only reset)
         S.res2_rec_owned = false;
         S.res2_rec[0] = (char *)X.mailbox + X.rec_off;
         S.res2_rec[1] = (char *)X.mailbox + X.rec_off + rec_stride;
         if (X.raw_off) {
-            if (S.res2_raw_owned)
-                for (auto &q : S.res2_rec_raw) { if (q) (void)hipFree(q); q = nullptr; }
+            for (auto &q : S.res2_rec_raw) S.mem.free_one(q);
             S.res2_raw_owned = false;
             S.res2_rec_raw[0] = (char *)X.mailbox + X.raw_off;
             S.res2_rec_raw[1] = (char *)X.mailbox + X.raw_off + raw_stride;
@@ -175,7 +172,7 @@ int direct_import(const HaloBlob *blobs, int nranks)
     }
     auto up = [&](auto *&dptr, const auto &v) -> int {
         using T = typename std::remove_reference<decltype(v[0])>::type;
-        if (!dptr) HIPC(hipMalloc((void **)&dptr, v.size() * sizeof(T)));
+        if (!dptr && S.mem.alloc(dptr, v.size())) return -1;
         HIPC(hipMemcpy((void *)dptr, v.data(), v.size() * sizeof(T), hipMemcpyHostToDevice));
         return 0;
     };
@@ -247,8 +244,8 @@ int direct_import(const HaloBlob *blobs, int nranks)
             if (B.raw_off) { praw[q] = mapped[p.rank] + B.raw_off; prawstr[q] = (size_t)B.raw_stride; }
             if (env_test("CICE_EVP_HIP_RES_REMOTE_BREAK")) {      // test hook: records go nowhere -> the probe must fail
                 void *dummy = nullptr;
-                HIPC(hipMalloc(&dummy, 2 * (size_t)B.rec_stride));
-                prec[q] = dummy;                             // (leaked on purpose: test processes only)
+                if (S.mem.alloc(dummy, 2 * (size_t)B.rec_stride)) return -1;
+                prec[q] = dummy;
             }
             // ghost cells of the peer: the FINAL velocity (negative across the tripole fold)
             for (int k = 0; k < p.n_ghost_send && ok; ++k)
@@ -293,9 +290,9 @@ int direct_import(const HaloBlob *blobs, int nranks)
     }
     EvpDirect D;
     fill_direct(D);
-    if (!X.d_dx) HIPC(hipMalloc((void **)&X.d_dx, sizeof(EvpDirect)));
+    if (!X.d_dx && S.mem.alloc(X.d_dx, 1)) return -1;
     HIPC(hipMemcpy(X.d_dx, &D, sizeof(EvpDirect), hipMemcpyHostToDevice));
-    if (!X.d_cnt) HIPC(hipMalloc((void **)&X.d_cnt, 32 * sizeof(unsigned)));
+    if (!X.d_cnt && S.mem.alloc(X.d_cnt, 32)) return -1;
     HIPC(hipMemset(X.d_cnt, 0, 32 * sizeof(unsigned)));
     return 0;
 }
@@ -350,7 +347,8 @@ int direct_probe()
         std::copy(hu0.begin(), hu0.begin() + S.n, cu.begin());
         std::copy(hv0.begin(), hv0.begin() + S.n, cv.begin());
         double *du = nullptr, *dv = nullptr;
-        if (alloc_d(&du, nc) || alloc_d(&dv, nc)) return -1;
+        ScratchPool tmp;
+        if (tmp.alloc(du, nc, true) || tmp.alloc(dv, nc, true)) return -1;
         HIPC(hipMemcpyAsync(du, cu.data(), nc * sizeof(double), hipMemcpyHostToDevice, S.stream));
         HIPC(hipMemcpyAsync(dv, cv.data(), nc * sizeof(double), hipMemcpyHostToDevice, S.stream));
         EvpDirect C;
@@ -360,8 +358,6 @@ int direct_probe()
         HIPC(hipMemcpyAsync(cv.data(), dv, nc * sizeof(double), hipMemcpyDeviceToHost, S.stream));
         HIPC(hipMemcpyAsync(&err, C.err, sizeof(int), hipMemcpyDeviceToHost, S.stream));
         HIPC(hipStreamSynchronize(S.stream));
-        (void)hipFree(du);
-        (void)hipFree(dv);
         if (err) {
             HIPC(hipMemset(C.err, 0, sizeof(int)));
             return fail(-8, "mailbox halo probe (C-grid fold exchange): peer %d never signalled", S.plan.cg_peers[err - 1].rank);
@@ -529,8 +525,9 @@ int cice_evp_hip_comm_init(const void *id128)
     const int nr = S.d.nranks;
     char *d_blobs = nullptr;
     int *d_ok = nullptr;
-    HIPC(hipMalloc((void **)&d_blobs, (size_t)nr * CICE_EVP_HIP_HALO_BLOB));
-    HIPC(hipMalloc((void **)&d_ok, sizeof(int)));
+    ScratchPool tmp;
+    if (int rc = tmp.alloc(d_blobs, (size_t)nr * CICE_EVP_HIP_HALO_BLOB)) return rc;
+    if (int rc = tmp.alloc(d_ok, 1)) return rc;
     auto agree = [&](int mine, int &all) -> int {
         HIPC(hipMemcpy(d_ok, &mine, sizeof(int), hipMemcpyHostToDevice));
         NCCLC(ncclAllReduce(d_ok, d_ok, 1, ncclInt, ncclMin, S.comm, S.stream));
@@ -571,8 +568,6 @@ int cice_evp_hip_comm_init(const void *id128)
                              why_res.empty() ? "another rank's probe failed" : why_res.c_str());
         }
     }
-    (void)hipFree(d_blobs);
-    (void)hipFree(d_ok);
     S.direct.on = all_ok != 0;
     S.direct.why = S.direct.on ? "" : (why.empty() ? "another rank could not set it up" : why);
     if (!S.direct.on && halo_choice() == 2)
@@ -629,7 +624,7 @@ int cice_evp_hip_halo_mask(const int32_t *halomask)
     }
     auto up = [&](auto *&dptr, const auto &v, size_t cap) -> int {
         using T = typename std::remove_reference<decltype(v[0])>::type;
-        if (!dptr) HIPC(hipMalloc((void **)&dptr, std::max<size_t>(cap, 1) * sizeof(T)));
+        if (!dptr && S.mem.alloc(dptr, std::max<size_t>(cap, 1))) return -1;
         if (!v.empty()) HIPC(hipMemcpyAsync((void *)dptr, v.data(), v.size() * sizeof(T), hipMemcpyHostToDevice, S.stream));
         return 0;
     };
@@ -642,7 +637,7 @@ int cice_evp_hip_halo_mask(const int32_t *halomask)
     if (S.direct.on) {
         EvpDirect D;
         fill_direct(D, true);
-        if (!S.direct.d_dx_m) HIPC(hipMalloc((void **)&S.direct.d_dx_m, sizeof(EvpDirect)));
+        if (!S.direct.d_dx_m && S.mem.alloc(S.direct.d_dx_m, 1)) return -1;
         HIPC(hipMemcpyAsync(S.direct.d_dx_m, &D, sizeof(EvpDirect), hipMemcpyHostToDevice, S.stream));
     }
     HIPC(hipStreamSynchronize(S.stream));

@@ -41,6 +41,7 @@ namespace evp_host {
 namespace {
 
 struct MarchBuf {
+    DevicePool mem;              // every device allocation behind a pointer of this struct
     double *st[2] = {};          // state blocks: u v sig x 12
     double *cst = nullptr;       // dxT dyT strength HTE HTN vrelfac uocn vocn forcex forcey umassdti fm uarear
     double *opt = nullptr;       // waterx watery TbU uvel_init vvel_init
@@ -71,34 +72,48 @@ enum { C_DXT = 0, C_DYT, C_STRENGTH, C_HTE, C_HTN, C_VRELFAC, C_UOCN, C_VOCN, C_
 enum { O_WATERX = 0, O_WATERY, O_TBU, O_UINIT, O_VINIT };
 MarchBuf B;
 
-template <class T> void F(T *&p)
+// the direct ring's mappings and inbox (a change of the switch re-opens the set-up)
+void direct_close()
 {
-    if (p) (void)hipFree((void *)p);
-    p = nullptr;
+    for (void *m : B.dx_mapped) (void)hipIpcCloseMemHandle(m);
+    B.dx_mapped.clear();
+    B.mem.free_one(B.dx_area);
+    B.dx = EvpMarchDirect{};
+    B.dx_seq = 0;
 }
 
 }  // namespace
 
 void march_free()
 {
-    F(B.st[0]); F(B.st[1]); F(B.cst); F(B.opt); F(B.diag);
-    F(B.mask); F(B.bad); F(B.dup); F(B.blkid); F(B.org);
-    F(B.send_pos); F(B.recv_pos1); F(B.recv_pos2); F(B.send_midx); F(B.recv_midx); F(B.sendbuf); F(B.recvbuf);
-    F(B.band_items); F(B.rest_items);
-    B.nband = B.nrest = 0;
-    for (auto &kv : B.fold_tiles) F(kv.second.first);
-    B.fold_tiles.clear();
-    FD = MarchFold();
-    for (void *m : B.dx_mapped) (void)hipIpcCloseMemHandle(m);
-    B.dx_mapped.clear();
-    F(B.dx_area);
-    B.dx = EvpMarchDirect{};
-    B.dx_seq = 0;
-    for (hipEvent_t *e : {&B.ev_in, &B.ev_main, &B.ev_done}) { if (*e) (void)hipEventDestroy(*e); *e = nullptr; }
+    direct_close();
+    B.mem.free_all();
+    for (hipEvent_t e : {B.ev_in, B.ev_main, B.ev_done})
+        if (e) (void)hipEventDestroy(e);
+    B = MarchBuf();
     PL = MarchPlan();
+    FD = MarchFold();
     S.march = State::March{};
 }
 
+size_t march_allocs() { return B.mem.owned.size(); }
+
+// ---- switches --------------------------------------------------------------------------------------------------------
+// CICE_EVP_HIP_MARCH: 0 never, 1 whenever the layout allows, not set (-1): where it pays (march_wanted)
+static int march_asked() { return env_int(env("CICE_EVP_HIP_MARCH"), -1); }
+// the early launch of an exchange pass (march_run); read on each rank for itself: every rank must be given the same value
+static bool march_overlap_asked() { return env_on(env("CICE_EVP_HIP_MARCH_OVERLAP"), false); }
+// CICE_EVP_HIP_VERBOSE (set at all): one line on stderr
+static void verbose(const char *fmt, ...)
+{
+    if (!env("CICE_EVP_HIP_VERBOSE")) return;
+    char buf[1024];
+    va_list ap;
+    va_start(ap, fmt);
+    vsnprintf(buf, sizeof buf, fmt, ap);
+    va_end(ap);
+    std::fprintf(stderr, "[cice_evp_hip] %s\n", buf);
+}
 // (test build) the ring between ranks as stores into HIP-IPC-mapped inboxes
 static bool march_direct_asked() { return env_on(env_test("CICE_EVP_HIP_MARCH_DIRECT"), false); }
 
@@ -305,21 +320,13 @@ static int march_alloc()
     State::March &M = S.march;
     auto A = [&](double *&p, int nf) -> int {
         if (p) return 0;
-        const size_t bytes = M.nblk * (size_t)nf * 512;
-        HIPC(hipMalloc((void **)&p, bytes));
-        HIPC(hipMemsetAsync(p, 0, bytes, S.stream));
-        return 0;
+        return B.mem.alloc(p, M.nblk * (size_t)nf * 64, true);
     };
     if (A(B.st[0], EVP_MARCH_S_NF) || A(B.st[1], EVP_MARCH_S_NF) || A(B.cst, EVP_MARCH_C_NF) || A(B.opt, EVP_MARCH_O_NF) ||
         A(B.diag, EVP_MARCH_D_NF)) return -1;
-    if (!B.mask) {
-        HIPC(hipMalloc((void **)&B.mask, (size_t)M.G.rows * M.G.ldx));
-        HIPC(hipMemsetAsync(B.mask, 0, (size_t)M.G.rows * M.G.ldx, S.stream));
-    }
-    if (!B.bad) HIPC(hipMalloc((void **)&B.bad, sizeof(unsigned)));
-    if (!B.blkid) {
-        if (upload(B.blkid, M.blkid_h) || upload(B.org, M.org_h) || upload(B.dup, M.dup_h)) return -1;
-    }
+    if (!B.mask && B.mem.alloc(B.mask, (size_t)M.G.rows * M.G.ldx, true)) return -1;
+    if (!B.bad && B.mem.alloc(B.bad, 1)) return -1;
+    if (!B.blkid && (B.mem.upload(B.blkid, M.blkid_h) || B.mem.upload(B.org, M.org_h) || B.mem.upload(B.dup, M.dup_h))) return -1;
     if (PL.n_send + PL.n_recv > 0 && !B.sendbuf) {
         std::vector<int> sp, r1, r2, sm, rm;
         for (const MarchPeer &p : PL.peers) {
@@ -331,7 +338,8 @@ static int march_alloc()
             for (size_t k = 0; k < p.recv_pos1.size(); ++k)
                 rm.push_back((int)((size_t)p.recv_row[k] * M.G.ldx + EVP_MARCH_PAD + p.recv_col[k]));
         }
-        if (upload(B.send_pos, sp) || upload(B.recv_pos1, r1) || upload(B.recv_pos2, r2) || upload(B.send_midx, sm) || upload(B.recv_midx, rm)) return -1;
+        if (B.mem.upload(B.send_pos, sp) || B.mem.upload(B.recv_pos1, r1) || B.mem.upload(B.recv_pos2, r2) || B.mem.upload(B.send_midx, sm) ||
+            B.mem.upload(B.recv_midx, rm)) return -1;
         B.cut_send.n = B.cut_recv.n = (int)PL.peers.size();
         int cs = 0, cr = 0;
         for (size_t q = 0; q < PL.peers.size(); ++q) {
@@ -339,8 +347,8 @@ static int march_alloc()
             cs += (int)PL.peers[q].send_pos.size(); cr += (int)PL.peers[q].recv_pos1.size();
         }
         B.cut_send.start[PL.peers.size()] = cs; B.cut_recv.start[PL.peers.size()] = cr;
-        HIPC(hipMalloc((void **)&B.sendbuf, std::max<size_t>(PL.n_send, 1) * EVP_MARCH_S_NF * sizeof(double)));
-        HIPC(hipMalloc((void **)&B.recvbuf, std::max<size_t>(PL.n_recv, 1) * EVP_MARCH_S_NF * sizeof(double)));
+        if (B.mem.alloc(B.sendbuf, std::max<size_t>(PL.n_send, 1) * EVP_MARCH_S_NF) ||
+            B.mem.alloc(B.recvbuf, std::max<size_t>(PL.n_recv, 1) * EVP_MARCH_S_NF)) return -1;
         // Work items of the EARLY launch of an exchange pass (march_run): per strip the rows that hold cells some other rank
         // receives, cut into short segments -- from the send lists themselves, so every sent cell is covered whatever the
         // layout.  Short segments (a third of the regular length, at least 6 rows) so that the launch, the pack and the
@@ -365,7 +373,7 @@ static int march_alloc()
                 y = y1;
             }
         B.nband = (int)items.size();
-        if (B.nband > 0 && upload(B.band_items, items)) return -1;
+        if (B.nband > 0 && B.mem.upload(B.band_items, items)) return -1;
         std::vector<int4> rest;
         for (int st = 0; st < nstr; ++st)
             for (int y = 0; y < M.G.nyr;) {
@@ -376,7 +384,7 @@ static int march_alloc()
                 y = y1;
             }
         B.nrest = (int)rest.size();
-        if (B.nrest > 0 && upload(B.rest_items, rest)) return -1;
+        if (B.nrest > 0 && B.mem.upload(B.rest_items, rest)) return -1;
         for (hipEvent_t *e : {&B.ev_in, &B.ev_main, &B.ev_done})
             if (!*e) HIPC(hipEventCreateWithFlags(e, hipEventDisableTiming));
     }
@@ -386,48 +394,69 @@ static int march_alloc()
     return 0;
 }
 
-// The two-cell ring of one strip-major buffer (all nf fields of every halo cell) from the ranks that own the cells:
-// pack -> ncclGroupStart{ncclSend, ncclRecv per neighbour}ncclGroupEnd -> unpack (incl. the duplicates), on the
-// library's stream.  Once per PASS of two subcycles for the state, once per call for the constants and the mask.
-// (test hook) the same exchange through host buffers and the caller's callback
-static int hook_exchange(int nf, hipStream_t st)
+// One transfer between the ranks of PL.peers on stream `st`: to / from each, in the plan's order, nf doubles per cell of its send /
+// receive list (per_cell) or nf doubles flat, out of `send` into `recv` (device buffers, the peers' shares one after the other).
+// ncclGroupStart{ncclSend, ncclRecv per neighbour}ncclGroupEnd, or (test hook) host buffers and the caller's callback.
+static int ring_transfer(const double *send, double *recv, int nf, hipStream_t st, bool per_cell = true)
 {
-    std::vector<int32_t> ranks;
-    std::vector<int64_t> ns, nr;
-    for (const MarchPeer &p : PL.peers) {
-        ranks.push_back(p.rank);
-        ns.push_back((int64_t)p.send_pos.size() * nf);
-        nr.push_back((int64_t)p.recv_pos1.size() * nf);
+    auto count = [&](size_t cells) { return (per_cell ? cells : (size_t)1) * nf; };
+    if (S.test_xchg) {
+        std::vector<int32_t> ranks;
+        std::vector<int64_t> ns, nr;
+        size_t ts = 0, tr = 0;
+        for (const MarchPeer &p : PL.peers) {
+            ranks.push_back(p.rank);
+            ns.push_back((int64_t)count(p.send_pos.size()));
+            nr.push_back((int64_t)count(p.recv_pos1.size()));
+            ts += (size_t)ns.back(); tr += (size_t)nr.back();
+        }
+        S.test_send.resize(ts + 1);
+        S.test_recv.resize(tr + 1);
+        HIPC(hipMemcpyAsync(S.test_send.data(), send, ts * sizeof(double), hipMemcpyDeviceToHost, st));
+        HIPC(hipStreamSynchronize(st));
+        if (S.test_xchg(S.test_user, (int32_t)ranks.size(), ranks.data(), ns.data(), nr.data(), S.test_send.data(), S.test_recv.data()))
+            return fail(-2, "test transport: the exchange callback failed");
+        HIPC(hipMemcpyAsync(recv, S.test_recv.data(), tr * sizeof(double), hipMemcpyHostToDevice, st));
+        HIPC(hipStreamSynchronize(st));
+        return 0;
     }
-    S.test_send.resize((size_t)PL.n_send * nf + 1);
-    S.test_recv.resize((size_t)PL.n_recv * nf + 1);
-    HIPC(hipMemcpyAsync(S.test_send.data(), B.sendbuf, (size_t)PL.n_send * nf * sizeof(double), hipMemcpyDeviceToHost, st));
-    HIPC(hipStreamSynchronize(st));
-    if (S.test_xchg(S.test_user, (int32_t)ranks.size(), ranks.data(), ns.data(), nr.data(), S.test_send.data(), S.test_recv.data()))
-        return fail(-2, "test transport: the exchange callback failed");
-    HIPC(hipMemcpyAsync(B.recvbuf, S.test_recv.data(), (size_t)PL.n_recv * nf * sizeof(double), hipMemcpyHostToDevice, st));
-    HIPC(hipStreamSynchronize(st));
-    return 0;
-}
-
-// pack + transfer of the ring of `buf` on stream `st` (what is left is the unpack)
-static int march_send_recv(double *buf, int nf, hipStream_t st)
-{
-    evp_launch_march_pack(buf, nf, B.send_pos, PL.n_send, B.cut_send, B.sendbuf, st);
-    if (S.test_xchg) return hook_exchange(nf, st);
     size_t so = 0, ro = 0;
     NCCLC(ncclGroupStart());
     for (const MarchPeer &p : PL.peers) {
-        const size_t ns = p.send_pos.size(), nr = p.recv_pos1.size();
-        if (ns) NCCLC(ncclSend(B.sendbuf + so * nf, ns * nf, ncclDouble, p.rank, S.comm, st));
-        if (nr) NCCLC(ncclRecv(B.recvbuf + ro * nf, nr * nf, ncclDouble, p.rank, S.comm, st));
+        const size_t ns = count(p.send_pos.size()), nr = count(p.recv_pos1.size());
+        if (ns) NCCLC(ncclSend(send + so, ns, ncclDouble, p.rank, S.comm, st));
+        if (nr) NCCLC(ncclRecv(recv + ro, nr, ncclDouble, p.rank, S.comm, st));
         so += ns; ro += nr;
     }
     NCCLC(ncclGroupEnd());
     return 0;
 }
 
-static int agree_max(unsigned &v);
+// The ring of one strip-major buffer (all nf fields of every halo cell) from the ranks that own the cells: pack + transfer on stream
+// `st` (what is left is the unpack, incl. the duplicates).  Once per exchange pass for the state, once per call for the constants.
+static int march_send_recv(double *buf, int nf, hipStream_t st)
+{
+    evp_launch_march_pack(buf, nf, B.send_pos, PL.n_send, B.cut_send, B.sendbuf, st);
+    return ring_transfer(B.sendbuf, B.recvbuf, nf, st);
+}
+
+// One word that the ranks agree on (they must take the same path): the minimum (a vote: int32) or the maximum (a counter: uint32) over
+// the ranks of the word at B.bad, into v; not `collective`: this rank's own word.  store: v goes to B.bad first -- otherwise a kernel
+// has left the word there.  Over RCCL, or the test hook's reduce callback.
+static int agree(unsigned &v, ncclRedOp_t op, bool store, bool collective)
+{
+    if (!B.bad && B.mem.alloc(B.bad, 1)) return -1;
+    if (store) HIPC(hipMemcpyAsync(B.bad, &v, sizeof v, hipMemcpyHostToDevice, S.stream));
+    if (collective && !S.test_reduce)
+        NCCLC(ncclAllReduce(B.bad, B.bad, 1, op == ncclMax ? ncclUint32 : ncclInt32, op, S.comm, S.stream));
+    HIPC(hipMemcpyAsync(&v, B.bad, sizeof v, hipMemcpyDeviceToHost, S.stream));
+    HIPC(hipStreamSynchronize(S.stream));
+    if (collective && S.test_reduce && S.test_reduce(S.test_user, op == ncclMax ? 1 : 0, &v))
+        return fail(-2, "test transport: the reduce callback failed");
+    return 0;
+}
+// ... the maximum over the ranks that have ring neighbours
+static int agree_max(unsigned &v, bool store = false) { return agree(v, ncclMax, store, !PL.peers.empty() && S.d.nranks > 1); }
 
 // ---- the ring without a communication library ------------------------------------------------------------------------
 // What a rank tells each of its ring neighbours: how to map its inbox and where that neighbour's entries land in it.
@@ -460,8 +489,7 @@ static int march_direct_setup()
         const bool want = march_direct_asked() &&
                           !(env("CICE_EVP_HIP_HALO") && !std::strcmp(env("CICE_EVP_HIP_HALO"), "rccl"));
         unsigned no = want ? 0u : 1u;
-        HIPC(hipMemcpyAsync(B.bad, &no, sizeof no, hipMemcpyHostToDevice, S.stream));
-        if (agree_max(no)) return -1;
+        if (agree_max(no, true)) return -1;
         if (no) {
             M.direct_why = want ? "not asked for on every rank" : "not asked for (CICE_EVP_HIP_MARCH_DIRECT=1)";
             return 0;
@@ -475,8 +503,9 @@ static int march_direct_setup()
     std::vector<double> out((size_t)np * MARCH_BLOB_DOUBLES, 0.0), in((size_t)np * MARCH_BLOB_DOUBLES, 0.0);
     if (ok) {
         const size_t bytes = inbox_off + 2 * par_doubles * sizeof(double);
-        if (hipExtMallocWithFlags(&B.dx_area, bytes, hipDeviceMallocFinegrained) != hipSuccess || hipMemset(B.dx_area, 0, bytes) != hipSuccess) {
+        if (B.mem.alloc_fine(B.dx_area, bytes)) {
             (void)hipGetLastError();
+            g_err.clear();
             ok = false;
             M.direct_why = "no fine-grained device memory for the inbox";
         }
@@ -503,27 +532,13 @@ static int march_direct_setup()
         ro += PL.peers[q].recv_pos1.size();
     }
     // the blobs travel like a ring of 32 doubles per neighbour
-    if (S.test_xchg) {
-        std::vector<int32_t> ranks;
-        std::vector<int64_t> cnt((size_t)np, MARCH_BLOB_DOUBLES);
-        for (const MarchPeer &p : PL.peers) ranks.push_back(p.rank);
-        if (S.test_xchg(S.test_user, np, ranks.data(), cnt.data(), cnt.data(), out.data(), in.data()))
-            return fail(-2, "test transport: the exchange callback failed");
-    } else {
+    {
+        ScratchPool tmp;
         double *d_out = nullptr, *d_in = nullptr;
-        const size_t nb = (size_t)np * MARCH_BLOB_DOUBLES * sizeof(double);
-        HIPC(hipMalloc((void **)&d_out, nb));
-        HIPC(hipMalloc((void **)&d_in, nb));
-        HIPC(hipMemcpyAsync(d_out, out.data(), nb, hipMemcpyHostToDevice, S.stream));
-        NCCLC(ncclGroupStart());
-        for (int q = 0; q < np; ++q) {
-            NCCLC(ncclSend(d_out + (size_t)q * MARCH_BLOB_DOUBLES, MARCH_BLOB_DOUBLES, ncclDouble, PL.peers[q].rank, S.comm, S.stream));
-            NCCLC(ncclRecv(d_in + (size_t)q * MARCH_BLOB_DOUBLES, MARCH_BLOB_DOUBLES, ncclDouble, PL.peers[q].rank, S.comm, S.stream));
-        }
-        NCCLC(ncclGroupEnd());
-        HIPC(hipMemcpyAsync(in.data(), d_in, nb, hipMemcpyDeviceToHost, S.stream));
+        if (tmp.upload(d_out, out) || tmp.alloc(d_in, in.size() + 1)) return -1;
+        if (int rc = ring_transfer(d_out, d_in, MARCH_BLOB_DOUBLES, S.stream, false)) return rc;
+        HIPC(hipMemcpyAsync(in.data(), d_in, in.size() * sizeof(double), hipMemcpyDeviceToHost, S.stream));
         HIPC(hipStreamSynchronize(S.stream));
-        (void)hipFree(d_out); (void)hipFree(d_in);
     }
     EvpMarchDirect D{};
     D.npeers = np;
@@ -568,14 +583,11 @@ static int march_direct_setup()
     }
     // everybody or nobody
     unsigned vote = ok ? 0u : 1u;
-    HIPC(hipMemcpyAsync(B.bad, &vote, sizeof vote, hipMemcpyHostToDevice, S.stream));
-    if (agree_max(vote)) return -1;
+    if (agree_max(vote, true)) return -1;
     if (vote && ok) M.direct_why = "another rank cannot take part";
     M.direct = vote ? 0 : 2;         // 2: the first exchange runs both ways and compares
-    if (env("CICE_EVP_HIP_VERBOSE"))
-        std::fprintf(stderr, "[cice_evp_hip] rank %d: ring of the marching path %s%s\n", (int)S.d.rank,
-                     M.direct ? "as stores into the neighbours' HIP-IPC-mapped inboxes" : "through RCCL send / recv: ",
-                     M.direct ? "" : M.direct_why.c_str());
+    verbose("rank %d: ring of the marching path %s%s", (int)S.d.rank,
+            M.direct ? "as stores into the neighbours' HIP-IPC-mapped inboxes" : "through RCCL send / recv: ", M.direct ? "" : M.direct_why.c_str());
     return 0;
 }
 
@@ -608,11 +620,7 @@ static int march_exchange(double *buf, double *buf2, int nf)
         const int asked = march_direct_asked() ? 1 : 0;
         if (M.direct >= 0 && asked != M.direct_asked) {       // (bench.py times one state both ways: the switch changed between two calls)
             HIPC(hipStreamSynchronize(S.stream));
-            for (void *m : B.dx_mapped) (void)hipIpcCloseMemHandle(m);
-            B.dx_mapped.clear();
-            F(B.dx_area);
-            B.dx = EvpMarchDirect{};
-            B.dx_seq = 0;
+            direct_close();
             M.direct = -1;
         }
         M.direct_asked = asked;
@@ -639,14 +647,11 @@ static int march_exchange(double *buf, double *buf2, int nf)
         int e = 0;
         HIPC(hipMemcpy(&e, B.dx.err, sizeof e, hipMemcpyDeviceToHost));
         unsigned tmo = e ? 1u : 0u;
-        HIPC(hipMemcpyAsync(B.bad, &tmo, sizeof tmo, hipMemcpyHostToDevice, S.stream));
-        if (agree_max(tmo)) return -1;
+        if (agree_max(tmo, true)) return -1;
         if (e) HIPC(hipMemset(B.dx.err, 0, sizeof(int)));
         M.direct = (bad || tmo) ? 0 : 1;
         if (!M.direct) M.direct_why = tmo ? "a neighbour never signalled in the trial exchange" : "the trial exchange delivered other bits than the library";
-        if (env("CICE_EVP_HIP_VERBOSE"))
-            std::fprintf(stderr, "[cice_evp_hip] rank %d: trial of the direct ring exchange: %s\n", (int)S.d.rank,
-                         M.direct ? "identical to RCCL, in use from now on" : M.direct_why.c_str());
+        verbose("rank %d: trial of the direct ring exchange: %s", (int)S.d.rank, M.direct ? "identical to RCCL, in use from now on" : M.direct_why.c_str());
     }
     return 0;
 }
@@ -655,36 +660,8 @@ static int march_exchange_mask()
 {
     if (PL.peers.empty()) return 0;
     evp_launch_march_pack_mask(B.mask, B.send_midx, PL.n_send, B.sendbuf, S.stream);
-    if (S.test_xchg) {
-        if (int rc = hook_exchange(1, S.stream)) return rc;
-        evp_launch_march_unpack_mask(B.mask, B.recv_midx, PL.n_recv, B.recvbuf, S.stream);
-        return 0;
-    }
-    size_t so = 0, ro = 0;
-    NCCLC(ncclGroupStart());
-    for (const MarchPeer &p : PL.peers) {
-        const size_t ns = p.send_pos.size(), nr = p.recv_pos1.size();
-        if (ns) NCCLC(ncclSend(B.sendbuf + so, ns, ncclDouble, p.rank, S.comm, S.stream));
-        if (nr) NCCLC(ncclRecv(B.recvbuf + ro, nr, ncclDouble, p.rank, S.comm, S.stream));
-        so += ns; ro += nr;
-    }
-    NCCLC(ncclGroupEnd());
+    if (int rc = ring_transfer(B.sendbuf, B.recvbuf, 1, S.stream)) return rc;
     evp_launch_march_unpack_mask(B.mask, B.recv_midx, PL.n_recv, B.recvbuf, S.stream);
-    return 0;
-}
-
-// max over ranks of a device counter (the ranks must take the same path)
-static int agree_max(unsigned &v)
-{
-    if (S.test_reduce && !PL.peers.empty() && S.d.nranks > 1) {
-        HIPC(hipMemcpyAsync(&v, B.bad, sizeof v, hipMemcpyDeviceToHost, S.stream));
-        HIPC(hipStreamSynchronize(S.stream));
-        if (S.test_reduce(S.test_user, 1, &v)) return fail(-2, "test transport: the reduce callback failed");
-        return 0;
-    }
-    if (!PL.peers.empty() && S.d.nranks > 1) NCCLC(ncclAllReduce(B.bad, B.bad, 1, ncclUint32, ncclMax, S.comm, S.stream));
-    HIPC(hipMemcpyAsync(&v, B.bad, sizeof v, hipMemcpyDeviceToHost, S.stream));
-    HIPC(hipStreamSynchronize(S.stream));
     return 0;
 }
 
@@ -694,6 +671,13 @@ struct TabBuilder {
     void add(double *blk, double *pk, double *pk2, int nf, int slot)
     {
         T.blk[T.n] = blk; T.pk[T.n] = pk; T.pk2[T.n] = pk2; T.nf[T.n] = nf; T.slot[T.n] = slot; ++T.n;
+    }
+    // u, v and the 12 stresses of ping-pong copy `cur` of the block layout <-> slots 0 .. 13 of the state block(s)
+    void add_state(int cur, double *pk, double *pk2 = nullptr)
+    {
+        add(S.u[cur], pk, pk2, EVP_MARCH_S_NF, 0);
+        add(S.v[cur], pk, pk2, EVP_MARCH_S_NF, 1);
+        for (int k = 0; k < 12; ++k) add(S.sig[cur][k], pk, pk2, EVP_MARCH_S_NF, 2 + k);
     }
 };
 }  // namespace
@@ -736,7 +720,7 @@ static int fold_tile_list(int variant, int *&list, int &count)
                 for (int bx = 0; bx < nbx; ++bx) t.push_back((b * gy + by) * gx + bx);      // row-major tile id
         }
         int *dl = nullptr;
-        if (upload(dl, t)) return -1;
+        if (B.mem.upload(dl, t)) return -1;
         it = B.fold_tiles.emplace(variant, std::make_pair(dl, (int)t.size())).first;
     }
     list = it->second.first;
@@ -797,27 +781,18 @@ bool march_wanted()
         for (char h : has)
             if (!h) { M.why = "a rank holds no blocks"; return false; }
     }
-    const int want = env("CICE_EVP_HIP_MARCH") ? std::atoi(env("CICE_EVP_HIP_MARCH")) : -1;
+    const int want = march_asked();
     // (a rank that was told CICE_EVP_HIP_MARCH=0 still takes part in the agreement below, voting no: an environment that
     // differs between the ranks then switches the path off everywhere instead of leaving the others in a collective)
     std::string why;
     bool ok = want != 0 && march_geometry(why);
     if (want == 0) why = "CICE_EVP_HIP_MARCH=0";
-    if (S.d.nranks > 1 && S.test_reduce) {
-        int32_t h = ok ? 1 : 0;
-        if (S.test_reduce(S.test_user, 0, &h)) return false;
-        if (ok && !h) { ok = false; why = "another rank cannot use it"; }
-    } else if (S.d.nranks > 1 && S.have_comm) {
+    if (S.d.nranks > 1 && (S.test_reduce || S.have_comm)) {
         // the choice must be the same on every rank (what decides it is partly local: e.g. whether the metric terms can be
-        // recomputed from the edge lengths is verified on each rank's own cells)
-        int *dflag = nullptr;
-        int h = ok ? 1 : 0;
-        if (hipMalloc((void **)&dflag, sizeof(int)) != hipSuccess) return false;
-        bool fine = hipMemcpyAsync(dflag, &h, sizeof h, hipMemcpyHostToDevice, S.stream) == hipSuccess &&
-                    ncclAllReduce(dflag, dflag, 1, ncclInt32, ncclMin, S.comm, S.stream) == ncclSuccess &&
-                    hipMemcpyAsync(&h, dflag, sizeof h, hipMemcpyDeviceToHost, S.stream) == hipSuccess &&
-                    hipStreamSynchronize(S.stream) == hipSuccess;
-        (void)hipFree(dflag);
+        // recomputed from the edge lengths is verified on each rank's own cells); an agreement that fails switches the path off
+        unsigned h = ok ? 1u : 0u;
+        const bool fine = agree(h, ncclMin, true, true) == 0;
+        g_err.clear();
         if (ok && (!fine || !h)) { ok = false; why = "another rank cannot use it"; }
     } else if (S.d.nranks > 1) {
         ok = false;
@@ -825,7 +800,7 @@ bool march_wanted()
     }
     if (!ok) {
         M.why = why;
-        if (env("CICE_EVP_HIP_VERBOSE")) std::fprintf(stderr, "[cice_evp_hip] marching kernel off: %s\n", why.c_str());
+        verbose("marching kernel off: %s", why.c_str());
         return false;
     }
     // worth it when the domain is far beyond what stays on the chip (the on-chip resident kernel is chosen before this
@@ -834,6 +809,9 @@ bool march_wanted()
     M.mode = 1;
     return true;
 }
+
+// does the kernel read the optional block (waterx watery TbU uvel_init vvel_init) under the flags in effect?
+static bool need_opt(unsigned fl) { return !(fl & EVP_F_WATER_IS_OCN) || !(fl & EVP_F_TBU_ZERO) || S.prm.revp != 0.0; }
 
 static void march_args(EvpMarch &A, int cur, int last)
 {
@@ -851,8 +829,7 @@ static void march_args(EvpMarch &A, int cur, int last)
     A.mask = B.mask;
     A.st_in = B.st[cur]; A.st_out = B.st[cur ^ 1];
     A.cst = B.cst;
-    const bool need_opt = !(A.flags & EVP_F_WATER_IS_OCN) || !(A.flags & EVP_F_TBU_ZERO) || q.revp != 0.0;
-    A.opt = need_opt ? B.opt : nullptr;
+    A.opt = need_opt(A.flags) ? B.opt : nullptr;
     A.diag = B.diag;
     A.dup = B.dup;
     A.items = nullptr;
@@ -869,7 +846,7 @@ int march_run(int ndte)
     auto fallback = [&](const char *why) -> int {
         ++M.declined;
         M.why = why;
-        if (env("CICE_EVP_HIP_VERBOSE")) std::fprintf(stderr, "[cice_evp_hip] marching kernel declined this call: %s\n", why);
+        verbose("marching kernel declined this call: %s", why);
         if (left > 0)
             if (int rc = enqueue_loop(left, cur)) return rc;
         S.cur = cur ^ (left & 1);
@@ -898,19 +875,11 @@ int march_run(int ndte)
     // that holds the band's current state.  The zone's rows reach it at the ring exchanges and in the final scatter.
     const bool fold = M.fold_h > 0;
     int bcur = cur;
-    auto state_tab = [&](double *pk) {
-        TabBuilder T;
-        T.add(S.u[bcur], pk, nullptr, EVP_MARCH_S_NF, 0); T.add(S.v[bcur], pk, nullptr, EVP_MARCH_S_NF, 1);
-        for (int k = 0; k < 12; ++k) T.add(S.sig[bcur][k], pk, nullptr, EVP_MARCH_S_NF, 2 + k);
-        return T;
-    };
     const unsigned fl = S.flags & S.flags_allowed;
     // ---- gather the state and the per-call inputs ----
     {
         TabBuilder G;
-        G.add(S.u[cur], B.st[0], B.st[1], EVP_MARCH_S_NF, 0);
-        G.add(S.v[cur], B.st[0], B.st[1], EVP_MARCH_S_NF, 1);
-        for (int k = 0; k < 12; ++k) G.add(S.sig[cur][k], B.st[0], B.st[1], EVP_MARCH_S_NF, 2 + k);
+        G.add_state(cur, B.st[0], B.st[1]);
         G.add(S.in[F_STRENGTH], B.cst, nullptr, EVP_MARCH_C_NF, C_STRENGTH);
         G.add(S.vrelfac, B.cst, nullptr, EVP_MARCH_C_NF, C_VRELFAC);
         G.add(S.in[F_UOCN], B.cst, nullptr, EVP_MARCH_C_NF, C_UOCN); G.add(S.in[F_VOCN], B.cst, nullptr, EVP_MARCH_C_NF, C_VOCN);
@@ -926,17 +895,14 @@ int march_run(int ndte)
         evp_launch_march_gather(M.G, G.T, S.mask, B.mask, EvpMarchAllRows, S.stream);
         // the two-cell ring of everything: other ranks' cells (once per call for the constants and the mask)
         if (march_exchange(B.cst, nullptr, EVP_MARCH_C_NF)) return -1;
-        const bool need_opt = !(fl & EVP_F_WATER_IS_OCN) || !(fl & EVP_F_TBU_ZERO) || S.prm.revp != 0.0;
-        if (need_opt && march_exchange(B.opt, nullptr, EVP_MARCH_O_NF)) return -1;
+        if (need_opt(fl) && march_exchange(B.opt, nullptr, EVP_MARCH_O_NF)) return -1;
         if (march_exchange_mask()) return -1;
         if (march_exchange(B.st[0], B.st[1], EVP_MARCH_S_NF)) return -1;
     }
     if (M.checked_seq != S.upload_seq || !PL.peers.empty()) {
         // first call on this uploaded state: are the caller's ghost values images of one global state?
         TabBuilder C;
-        C.add(S.u[cur], B.st[0], nullptr, EVP_MARCH_S_NF, 0);
-        C.add(S.v[cur], B.st[0], nullptr, EVP_MARCH_S_NF, 1);
-        for (int k = 0; k < 12; ++k) C.add(S.sig[cur][k], B.st[0], nullptr, EVP_MARCH_S_NF, 2 + k);
+        C.add_state(cur, B.st[0]);
         C.add(S.in[F_STRENGTH], B.cst, nullptr, EVP_MARCH_C_NF, C_STRENGTH);
         HIPC(hipMemsetAsync(B.bad, 0, sizeof(unsigned), S.stream));
         evp_launch_march_check(M.G, C.T, S.mask, B.mask, 2, 13, B.bad, check_window(), S.stream);
@@ -963,9 +929,7 @@ int march_run(int ndte)
     // no idle resource to hide a transfer under, and "early" means SHORT segments for the band -- 2K - 1 rows of warm-up on 7 stored.
     // On one GPU the transfer is a 7-us device copy; over xGMI it is 1.6 MB per neighbour every eighth subcycle, and only a node
     // can say whether hiding that is worth 6 us per subcycle.  bench.py --gpus N --extras ring_variants times both.
-    const bool overlap = !PL.peers.empty() && B.nband > 0 && M.direct != 1 &&
-                         env("CICE_EVP_HIP_MARCH_OVERLAP") && std::atoi(env("CICE_EVP_HIP_MARCH_OVERLAP")) &&
-                         !march_direct_asked();
+    const bool overlap = !PL.peers.empty() && B.nband > 0 && M.direct != 1 && march_overlap_asked() && !march_direct_asked();
     for (int k = 0; k < npass; ++k) {
         // the ring of the new state travels after this pass when the next one needs more valid cells than are left, and after the
         // last one (the way back to the block layout reads the ghost cells from it)
@@ -1008,7 +972,8 @@ int march_run(int ndte)
             if (int e = fold_band_subcycles(sizes[(size_t)k], bcur, k == npass - 1)) return e;
             M.call_band_subcycles += sizes[(size_t)k];
             if (fexch) {
-                const TabBuilder T = state_tab(B.st[rc]);
+                TabBuilder T;
+                T.add_state(bcur, B.st[rc]);
                 evp_launch_march_scatter(M.G, T.T, S.mask, 2, 12, rows_window(FD.to_block[0], FD.to_block[1]), S.stream);
                 evp_launch_march_gather(M.G, T.T, nullptr, nullptr, rows_window(FD.to_rect[0], FD.to_rect[1]), S.stream);
             }
@@ -1021,7 +986,8 @@ int march_run(int ndte)
     // ---- back to the block layout ----
     {
         // (a fold band: into the buffer its last subcycle wrote, the zone's rows only -- the band's own are current there)
-        TabBuilder T = state_tab(B.st[rc]);
+        TabBuilder T;
+        T.add_state(bcur, B.st[rc]);
         T.add(S.in[F_STRINTX], B.diag, nullptr, EVP_MARCH_D_NF, 0); T.add(S.in[F_STRINTY], B.diag, nullptr, EVP_MARCH_D_NF, 1);
         T.add(S.in[F_TAUBX], B.diag, nullptr, EVP_MARCH_D_NF, 2); T.add(S.in[F_TAUBY], B.diag, nullptr, EVP_MARCH_D_NF, 3);
         evp_launch_march_scatter(M.G, T.T, S.mask, 2, 12, fold ? rows_window(-(1 << 28), FD.zone) : EvpMarchAllRows, S.stream);

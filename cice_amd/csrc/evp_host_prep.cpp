@@ -55,16 +55,16 @@ int cice_evp_hip_set_prep_geometry(const int32_t *tmask, const int32_t *umask, c
     if (S.plan.tfold && S.plan.center_tf_remote)
         return fail(-9, "device preparation on a tripoleT grid: the top row's mirror cells live on other ranks (or in an eliminated "
                         "block) here; keep evp()'s host preparation (cice_evp_hip_run)");
-    auto B = [&](uint8_t *&p) -> int { if (!p) HIPC(hipMalloc((void **)&p, S.n)); return 0; };
+    auto B = [&](uint8_t *&p) -> int { return p ? 0 : S.mem.alloc(p, S.n); };
     if (B(Q.tmask) || B(Q.umask) || B(Q.umask_old) || B(Q.tmphm)) return -1;
-    HIPC(hipMalloc((void **)&Q.umask_old32, S.n * sizeof(int32_t)));
+    if (!Q.umask_old32 && S.mem.alloc(Q.umask_old32, S.n)) return -1;
     // (with the staging tail of a split tripole seam row: these arrays go through the velocity exchange too)
-    auto D = [&](double *&p) -> int { return p ? 0 : alloc_d(&p, S.nuv); };
+    auto D = [&](double *&p) -> int { return p ? 0 : S.mem.alloc(p, S.nuv, true); };
     if (D(Q.hm) || D(Q.tarea) || D(Q.uarea) || D(Q.fcor) || D(Q.tmass) || D(Q.umass) || D(Q.maskd) ||
         D(Q.ss_tltxU) || D(Q.ss_tltyU) || D(Q.strairxU) || D(Q.strairyU) || D(Q.strtltx) || D(Q.strtlty)) return -1;
     for (auto &q : Q.t)
         if (D(q)) return -1;
-    if (!Q.flagword) HIPC(hipMalloc((void **)&Q.flagword, sizeof(unsigned)));
+    if (!Q.flagword && S.mem.alloc(Q.flagword, 1)) return -1;
     Q.h8.resize(S.n);
     for (size_t k = 0; k < S.n; ++k) Q.h8[k] = tmask[k] != 0;
     HIPC(hipMemcpy(Q.tmask, Q.h8.data(), S.n, hipMemcpyHostToDevice));
@@ -73,27 +73,12 @@ int cice_evp_hip_set_prep_geometry(const int32_t *tmask, const int32_t *umask, c
     if (h2d(Q.hm, hm) || h2d(Q.tarea, tarea) || h2d(Q.uarea, uarea) || h2d(Q.fcor, fcor_blk)) return -1;
     const HaloPlan &P = S.plan;
     Q.n_center = (int)P.center_dst.size();
-    if (Q.n_center && !Q.c_dst) {
-        HIPC(hipMalloc((void **)&Q.c_dst, Q.n_center * sizeof(int32_t)));
-        HIPC(hipMalloc((void **)&Q.c_src, Q.n_center * sizeof(int32_t)));
-        HIPC(hipMalloc((void **)&Q.c_vsign, Q.n_center));
-        HIPC(hipMemcpy(Q.c_dst, P.center_dst.data(), Q.n_center * sizeof(int32_t), hipMemcpyHostToDevice));
-        HIPC(hipMemcpy(Q.c_src, P.center_src.data(), Q.n_center * sizeof(int32_t), hipMemcpyHostToDevice));
-        HIPC(hipMemcpy(Q.c_vsign, P.center_vsign.data(), Q.n_center, hipMemcpyHostToDevice));
-    }
+    if (Q.n_center && !Q.c_dst &&
+        (S.mem.upload(Q.c_dst, P.center_dst) || S.mem.upload(Q.c_src, P.center_src) || S.mem.upload(Q.c_vsign, P.center_vsign))) return -1;
     Q.n_tf = (int)P.center_tf_dst.size();
-    if (Q.n_tf && !Q.tf_dst) {
-        const size_t nb = (size_t)Q.n_tf * sizeof(int32_t);
-        HIPC(hipMalloc((void **)&Q.tf_dst, nb));
-        HIPC(hipMalloc((void **)&Q.tf_a, nb));
-        HIPC(hipMalloc((void **)&Q.tf_b, nb));
-        HIPC(hipMalloc((void **)&Q.tf_flip, (size_t)Q.n_tf));
-        HIPC(hipMalloc((void **)&Q.tf_tmp, (size_t)4 * Q.n_tf * sizeof(double)));
-        HIPC(hipMemcpy(Q.tf_dst, P.center_tf_dst.data(), nb, hipMemcpyHostToDevice));
-        HIPC(hipMemcpy(Q.tf_a, P.center_tf_a.data(), nb, hipMemcpyHostToDevice));
-        HIPC(hipMemcpy(Q.tf_b, P.center_tf_b.data(), nb, hipMemcpyHostToDevice));
-        HIPC(hipMemcpy(Q.tf_flip, P.center_tf_flip.data(), (size_t)Q.n_tf, hipMemcpyHostToDevice));
-    }
+    if (Q.n_tf && !Q.tf_dst &&
+        (S.mem.upload(Q.tf_dst, P.center_tf_dst) || S.mem.upload(Q.tf_a, P.center_tf_a) || S.mem.upload(Q.tf_b, P.center_tf_b) ||
+         S.mem.upload(Q.tf_flip, P.center_tf_flip) || S.mem.alloc(Q.tf_tmp, (size_t)4 * Q.n_tf))) return -1;
     HIPC(hipStreamSynchronize(S.stream));
     Q.geo = true;
     return 0;
@@ -121,7 +106,7 @@ int cice_evp_hip_set_forcing_layout(int32_t calc_strair, int32_t ocn_u, int32_t 
     const double *src[5] = {earea, narea, uvm, epm, npm};
     double **dst[5] = {&G.earea, &G.narea, &G.uvm, &G.epm, &G.npm};
     for (int k = 0; k < 5; ++k)
-        if (src[k] && ((!*dst[k] && alloc_d(dst[k], S.n)) || h2d(*dst[k], src[k]))) return -1;
+        if (src[k] && ((!*dst[k] && S.mem.alloc(*dst[k], S.n, true)) || h2d(*dst[k], src[k]))) return -1;
     G.calc_strair = calc_strair != 0;
     G.ocn[0] = ocn_u; G.ocn[1] = ocn_v;
     G.atm[0] = G.calc_strair ? 0 : atm_u; G.atm[1] = G.calc_strair ? 0 : atm_v;
@@ -357,7 +342,7 @@ int cice_evp_hip_seabed_lkd(const double *hwater, double k1, double k2, double a
                                               "compute TbU on the host (cice_evp_hip_set_tbu)");
     if (!Q.hwater) {
         if (!hwater) return fail(-1, "hwater needed on the first call");
-        if (alloc_d(&Q.hwater, S.n)) return -1;
+        if (S.mem.alloc(Q.hwater, S.n, true)) return -1;
     }
     if (hwater && h2d(Q.hwater, hwater)) return -1;
     EvpPrepHalo H{};
@@ -401,16 +386,16 @@ int cice_evp_hip_seabed_prob(const double *hwater, const double *aicen, const do
     State::Prep &Q = S.prep;
     if (!Q.hwater) {
         if (!hwater) return fail(-1, "hwater needed on the first call");
-        if (alloc_d(&Q.hwater, S.n)) return -1;
+        if (S.mem.alloc(Q.hwater, S.n, true)) return -1;
     }
     if (hwater && h2d(Q.hwater, hwater)) return -1;
     if (Q.ncat != ncat) {
-        if (Q.aicen) { (void)hipFree(Q.aicen); Q.aicen = nullptr; }
-        if (Q.vicen) { (void)hipFree(Q.vicen); Q.vicen = nullptr; }
-        if (alloc_d(&Q.aicen, S.n * (size_t)ncat) || alloc_d(&Q.vicen, S.n * (size_t)ncat)) return -1;
+        S.mem.free_one(Q.aicen);
+        S.mem.free_one(Q.vicen);
+        if (S.mem.alloc(Q.aicen, S.n * (size_t)ncat, true) || S.mem.alloc(Q.vicen, S.n * (size_t)ncat, true)) return -1;
         Q.ncat = ncat;
     }
-    if (!Q.tbt && alloc_d(&Q.tbt, S.n)) return -1;
+    if (!Q.tbt && S.mem.alloc(Q.tbt, S.n, true)) return -1;
     // the caller's arrays are (nx, ny, ncat, max_blocks): blocks 1..nblocks are contiguous
     HIPC(hipMemcpyAsync(Q.aicen, aicen, S.n * (size_t)ncat * sizeof(double), hipMemcpyHostToDevice, S.stream));
     HIPC(hipMemcpyAsync(Q.vicen, vicen, S.n * (size_t)ncat * sizeof(double), hipMemcpyHostToDevice, S.stream));

@@ -60,9 +60,9 @@ bool resident_possible(bool with_peers)
 int resident2_setup(int logw)
 {
     if (S.res2_ring && S.res2_logw == logw) return 0;
-    auto F = [](auto *&p) { if (p) (void)hipFree((void *)p); p = nullptr; };
-    F(S.res2_ring); F(S.res2_cnt); F(S.res2_pub); F(S.res2_perm); F(S.res2_late); F(S.res2_nact); F(S.res2_nlate);
-    F(S.res2_live); F(S.res2_celltile);
+    DevicePool &M = S.mem;       // the tables of the previous tile shape
+    M.free_one(S.res2_ring); M.free_one(S.res2_cnt); M.free_one(S.res2_pub); M.free_one(S.res2_perm); M.free_one(S.res2_late);
+    M.free_one(S.res2_nact); M.free_one(S.res2_nlate); M.free_one(S.res2_live); M.free_one(S.res2_celltile);
     S.res2_nlive = 0;
     S.res2_cls_h.clear();
     S.res2_order_stale = true;
@@ -161,9 +161,7 @@ int resident2_setup(int logw)
     for (int c : tfold_src) pub[(size_t)c] = 1;
     S.res2_ntiles = ntiles;
     S.res2_always_h = always;
-    HIPC(hipMalloc((void **)&S.res2_celltile, celltile.size() * sizeof(int)));
-    HIPC(hipMemcpy(S.res2_celltile, celltile.data(), celltile.size() * sizeof(int), hipMemcpyHostToDevice));
-    HIPC(hipMalloc((void **)&S.res2_live, (size_t)ntiles));
+    if (S.mem.upload(S.res2_celltile, celltile) || S.mem.alloc(S.res2_live, (size_t)ntiles)) return -1;
     HIPC(hipMemset(S.res2_live, 1, (size_t)ntiles));
     // ghost images from a per-cell table whenever they are not confined to the edge of ONE block:
     // tripole grids (ghost row NY+1 mirrors row NY-1) and several blocks per rank
@@ -178,8 +176,7 @@ int resident2_setup(int logw)
             if (e == 3) return fail(-6, "resident2: more than three ghost images of one cell");
             img3[(size_t)src * 3 + e] = enc;
         }
-        HIPC(hipMalloc((void **)&S.res2_img3, img3.size() * sizeof(int)));
-        HIPC(hipMemcpy(S.res2_img3, img3.data(), img3.size() * sizeof(int), hipMemcpyHostToDevice));
+        if (S.mem.upload(S.res2_img3, img3)) return -1;
     }
     if ((tripole_seam() || S.plan.tfold) && !S.res2_seam) {
         std::vector<int> seam((size_t)nx * nb, 0);       // per block and column of the fold row
@@ -200,28 +197,20 @@ int resident2_setup(int logw)
             if ((size_t)a < ncell && (size_t)b < ncell) continue;            // both local: set above
             seam[slot(dst)] = (dst == a) ? b * 4 + 1 : a * 4 + 2;
         }
-        HIPC(hipMalloc((void **)&S.res2_seam, seam.size() * sizeof(int)));
-        HIPC(hipMemcpy(S.res2_seam, seam.data(), seam.size() * sizeof(int), hipMemcpyHostToDevice));
+        if (S.mem.upload(S.res2_seam, seam)) return -1;
         for (auto &q : S.res2_rec_raw)
             if (!q) {
                 if (!S.res2_raw_owned) return fail(-6, "resident2: raw seam records missing from the mailbox");
-                HIPC(hipMalloc(&q, (ncell + (size_t)S.plan.tail) * 32));
+                if (S.mem.alloc(q, (ncell + (size_t)S.plan.tail) * 32)) return -1;
                 HIPC(hipMemset(q, 0, (ncell + (size_t)S.plan.tail) * 32));
             }
     }
-    HIPC(hipMalloc((void **)&S.res2_ring, ring.size() * sizeof(int4)));
-    HIPC(hipMemcpy(S.res2_ring, ring.data(), ring.size() * sizeof(int4), hipMemcpyHostToDevice));
-    HIPC(hipMalloc((void **)&S.res2_cnt, cnt.size() * sizeof(int)));
-    HIPC(hipMemcpy(S.res2_cnt, cnt.data(), cnt.size() * sizeof(int), hipMemcpyHostToDevice));
-    HIPC(hipMalloc((void **)&S.res2_pub, pub.size()));
-    HIPC(hipMemcpy(S.res2_pub, pub.data(), pub.size(), hipMemcpyHostToDevice));
+    if (S.mem.upload(S.res2_ring, ring) || S.mem.upload(S.res2_cnt, cnt) || S.mem.upload(S.res2_pub, pub)) return -1;
     if (permuted) {
-        HIPC(hipMalloc((void **)&S.res2_perm, (size_t)ntiles * 256));
-        HIPC(hipMalloc((void **)&S.res2_late, (size_t)ntiles));
-        HIPC(hipMalloc((void **)&S.res2_nact, (size_t)ntiles));
-        HIPC(hipMalloc((void **)&S.res2_nlate, (size_t)ntiles));
+        if (S.mem.alloc(S.res2_perm, (size_t)ntiles * 256) || S.mem.alloc(S.res2_late, (size_t)ntiles) ||
+            S.mem.alloc(S.res2_nact, (size_t)ntiles) || S.mem.alloc(S.res2_nlate, (size_t)ntiles)) return -1;
         if (!S.res2_cuload) {
-            HIPC(hipMalloc((void **)&S.res2_cuload, 2048 * 8 * sizeof(int)));
+            if (S.mem.alloc(S.res2_cuload, 2048 * 8)) return -1;
             HIPC(hipMemset(S.res2_cuload, 0, 2048 * 8 * sizeof(int)));
         }
         S.res2_cls_h = cls;
@@ -230,11 +219,11 @@ int resident2_setup(int logw)
     for (auto &p : S.res2_rec)
         if (!p) {
             if (!S.res2_rec_owned) return fail(-6, "resident2: record buffers missing from the mailbox");
-            HIPC(hipMalloc(&p, ncell * 32));
+            if (S.mem.alloc(p, ncell * 32)) return -1;
             HIPC(hipMemset(p, 0, ncell * 32));
         }
     if (!S.res_err) {
-        HIPC(hipMalloc((void **)&S.res_err, 8 * sizeof(int)));
+        if (S.mem.alloc(S.res_err, 8)) return -1;
         HIPC(hipMemset(S.res_err, 0, 8 * sizeof(int)));
     }
     return 0;
@@ -381,8 +370,8 @@ int resident2_order()
         for (int c = 0; c < ncu; ++c)
             for (size_t k = 0; k < mine[c].size(); ++k) order[c + (int)k * ncu] = mine[c][k];
     }
-    if (S.res2_order && S.res2_order_for != S.res2_logw) { (void)hipFree(S.res2_order); S.res2_order = nullptr; }
-    if (!S.res2_order) HIPC(hipMalloc((void **)&S.res2_order, order.size() * sizeof(int)));
+    if (S.res2_order_for != S.res2_logw) S.mem.free_one(S.res2_order);
+    if (!S.res2_order && S.mem.alloc(S.res2_order, order.size())) return -1;
     HIPC(hipMemcpyAsync(S.res2_order, order.data(), order.size() * sizeof(int), hipMemcpyHostToDevice, S.stream));
     HIPC(hipMemcpyAsync(S.res2_live, live.data(), live.size(), hipMemcpyHostToDevice, S.stream));
     HIPC(hipStreamSynchronize(S.stream));
@@ -434,7 +423,7 @@ int launch_resident2(int ndte, int cur0, bool dry)
     R.cuload = S.res2_cuload;
     R.prof = nullptr;
     if (S.res2_logw == 4 && env_test("CICE_EVP_HIP_RES_PROF") && std::atoi(env_test("CICE_EVP_HIP_RES_PROF"))) {
-        if (!S.res2_prof) HIPC(hipMalloc((void **)&S.res2_prof, (size_t)S.res2_ntiles * 32 * sizeof(unsigned long long)));
+        if (!S.res2_prof && S.mem.alloc(S.res2_prof, (size_t)S.res2_ntiles * 32)) return -1;
         HIPC(hipMemsetAsync(S.res2_prof, 0, (size_t)S.res2_ntiles * 32 * sizeof(unsigned long long), S.stream));
         R.prof = S.res2_prof;
     }
@@ -489,7 +478,7 @@ int resident_tables()
             tab[v][24] = S.in[F_STRINTX]; tab[v][25] = S.in[F_STRINTY];
             tab[v][26] = S.in[F_TAUBX]; tab[v][27] = S.in[F_TAUBY];
         }
-        HIPC(hipMalloc((void **)&S.res_tab, sizeof tab));
+        if (S.mem.alloc(S.res_tab, sizeof tab / sizeof(double *))) return -1;
         HIPC(hipMemcpy(S.res_tab, tab, sizeof tab, hipMemcpyHostToDevice));
     }
     return 0;

@@ -55,7 +55,7 @@ EXPORTS = [
 # the test transport
 TEST_EXPORTS = [
     "cice_evp_hip_cgrid_fold_plan", "cice_evp_hip_cgrid_window_plan", "cice_evp_hip_cgrid_window_plan_ext", "cice_evp_hip_cgrid_window_deps", "cice_evp_hip_cgrid_strip_plan", "cice_evp_hip_cgrid_strip_zones", "cice_evp_hip_cgrid_frame_plan", "cice_evp_hip_cgrid_march_fold_plan", "cice_evp_hip_set_test_transport", "cice_evp_hip_march_plan", "cice_evp_hip_march_fold_plan",
-    "cice_evp_hip_debug_cuload", "cice_evp_hip_debug_prof", "cice_evp_hip_debug_cgrid_prof", "cice_evp_hip_debug_cgres_prof", "cice_evp_hip_plan_build", "cice_evp_hip_halo_plan", "cice_evp_hip_seam_plan",
+    "cice_evp_hip_debug_device_allocs", "cice_evp_hip_debug_cuload", "cice_evp_hip_debug_prof", "cice_evp_hip_debug_cgrid_prof", "cice_evp_hip_debug_cgres_prof", "cice_evp_hip_plan_build", "cice_evp_hip_halo_plan", "cice_evp_hip_seam_plan",
     "cice_evp_hip_peer_plan", "cice_evp_hip_peer_signs", "cice_evp_hip_center_plan", "cice_evp_hip_stress_plan",
     "cice_evp_hip_fold_split_plan", "cice_evp_hip_plan_flags", "cice_evp_hip_fold_images_plan", "cice_evp_hip_cgrid_fold_xplan",
     "cice_evp_hip_cgrid_fold_xpeers",
@@ -828,6 +828,15 @@ class EvpHip:
             self.finalize()
         except Exception:
             pass
+
+
+def device_allocs() -> int:
+    """Device allocations the TEST build's library holds right now (B-grid state, marching path, C-grid state): 0 before init and
+    after finalize.  Counts what an EvpHip(..., testing=True) allocated; the product library is another state."""
+    lib = load_library(testing=True)
+    n = C.c_int64(-1)
+    _check(lib, lib.cice_evp_hip_debug_device_allocs(C.byref(n)), "(debug_device_allocs)")
+    return int(n.value)
 
 
 def march_plan(dims: Dims, own_max: int = 0, wrap_inside: bool = True, ext: int = 0) -> dict:

@@ -119,6 +119,9 @@ int cice_evp_hip_debug_cgrid_prof(uint64_t *out, int32_t ntiles_max);
 /* The same for the on-chip resident C-grid kernel (cg_res): 32 values per window = 4 waves x 8 phases, shader cycles summed over the
  * last launch: poll | barrier | S | barrier | T | barrier | U + barrier | C.  Returns the number of windows.                       */
 int cice_evp_hip_debug_cgres_prof(uint64_t *out, int32_t ntiles_max);
+/* How many device allocations the library holds right now, over the B-grid state, the marching path and the C-grid state (what
+ * their pools have registered and cice_evp_hip_finalize releases): 0 before cice_evp_hip_init and after cice_evp_hip_finalize. */
+int cice_evp_hip_debug_device_allocs(int64_t *count);
 /* Host-only: build the plan for `dims` without touching a device (CPU tests). */
 int cice_evp_hip_plan_build(const cice_evp_hip_dims *dims);
 int cice_evp_hip_halo_plan(int32_t *counts4, int32_t *local_dst, int32_t *local_src,
