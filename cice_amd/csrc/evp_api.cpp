@@ -7,6 +7,64 @@
 
 using namespace evp_host;
 
+// Read-outs of the plan's lists: v into a caller's int32 list, entry k at out[k * stride]; out may be NULL.  Returns the count.
+namespace {
+int32_t *at(int32_t *out, size_t k) { return out ? out + k : nullptr; }
+template <class T> size_t copy_out(int32_t *out, const std::vector<T> &v, int stride = 1)
+{
+    for (size_t k = 0; out && k < v.size(); ++k) out[k * stride] = (int32_t)v[k];
+    return v.size();
+}
+// ... one member of every peer, peer after peer
+template <class T> size_t copy_out(int32_t *out, const std::vector<HaloPeer> &peers, std::vector<T> HaloPeer::*member, int stride = 1)
+{
+    size_t n = 0;
+    for (const HaloPeer &p : peers) n += copy_out(at(out, n * stride), p.*member, stride);
+    return n;
+}
+}  // namespace
+
+// Every member of the plan built last, in declaration order (halo_plan.h), as int32: a vector as its length and its entries, a
+// peer list as its length and every peer member by member, the error text as its length and its characters.  Reads only the struct.
+#ifdef CICE_EVP_HIP_TESTING
+namespace {
+struct PlanDump {
+    int32_t *out;
+    int32_t n = 0;
+    void put(long v) { if (out) out[n] = (int32_t)v; ++n; }
+    template <class T> void put(const std::vector<T> &v) { put((long)v.size()); for (const T &x : v) put((long)x); }
+    void put(const FoldList &L) { put(L.dst); put(L.a); put(L.b); put(L.flip); }
+    void put(const std::vector<HaloPeer> &peers)
+    {
+        put((long)peers.size());
+        for (const HaloPeer &p : peers) {
+            put(p.rank); put(p.send_src); put(p.send_dst); put(p.recv_dst); put(p.recv_sign); put(p.recv_gid); put(p.send_sign);
+            put(p.n_ghost_send); put(p.n_ghost_recv);
+            put(p.fimg_src); put(p.fimg_dst); put(p.fimg_sign); put(p.fimg_recv_dst); put(p.fimg_recv_col); put(p.fimg_recv_sign);
+        }
+    }
+    void put(const HaloPlan &P)
+    {
+        put(P.nx_block); put(P.ny_block); put(P.nblocks);
+        put(P.local_dst); put(P.local_src); put(P.local_sign); put(P.peers);
+        put(P.seam_a); put(P.seam_b); put(P.seam_pole); put(P.late_dst); put(P.late_src); put(P.late_sign);
+        put(P.fin_dst); put(P.fin_a); put(P.fin_b); put(P.fin_coef); put(P.tail);
+        put(P.any_fold_exchange); put(P.stress_remote); put(P.fold_rows);
+        put(P.stress_dst); put(P.stress_src); put(P.stress_own_dst); put(P.stress_own_src);
+        put(P.stress_corner_dst); put(P.stress_corner_src);
+        put(P.center_dst); put(P.center_src); put(P.center_vsign); put(P.tfold);
+        put(P.center_tf_dst); put(P.center_tf_a); put(P.center_tf_b); put(P.center_tf_flip);
+        put(P.center_tf_remote); put(P.center_remote); put(P.center_fold_remote);
+        put(P.center_foldr_dst); put(P.stress_foldr_dst); put(P.fold_shift_cells); put(P.center_seam_dst); put(P.center_seam_slot);
+        put(P.fold_split);
+        for (const FoldList &L : P.cg_fold) put(L);
+        put(P.cg_peers); put(P.cg_tail); put(P.cg_split); put(P.cg_fold_ranks);
+        put(std::vector<char>(P.error.begin(), P.error.end()));
+    }
+};
+}  // namespace
+#endif
+
 extern "C" {
 
 int cice_evp_hip_abi_version(void) { return CICE_EVP_HIP_ABI_VERSION; }
@@ -953,37 +1011,37 @@ int cice_evp_hip_plan_build(const cice_evp_hip_dims *dims)
     return 0;
 }
 
+// the whole plan built last (PlanDump above; tests/test_halo_plan_digest_cpu.py)
+int cice_evp_hip_plan_dump(int32_t *out, int32_t n)
+{
+    PlanDump count{nullptr};
+    count.put(S.plan);
+    if (!out) return count.n;
+    if (n < count.n) return fail(-1, "plan_dump: room for %d values, %d needed", (int)n, (int)count.n);
+    PlanDump dump{out};
+    dump.put(S.plan);
+    return dump.n;
+}
+
 int cice_evp_hip_halo_plan(int32_t *counts4, int32_t *local_dst, int32_t *local_src,
                            int32_t *local_sign, int32_t *peer_rank, int32_t *peer_nsend,
                            int32_t *peer_nrecv, int32_t *send_src, int32_t *recv_dst)
 {
     const HaloPlan &P = S.plan;
-    size_t ns = 0, nr = 0;
-    for (const HaloPeer &p : P.peers) {
-        ns += p.send_src.size();
-        nr += p.recv_dst.size();
+    copy_out(local_dst, P.local_dst);
+    copy_out(local_src, P.local_src);
+    copy_out(local_sign, P.local_sign);
+    const size_t ns = copy_out(send_src, P.peers, &HaloPeer::send_src), nr = copy_out(recv_dst, P.peers, &HaloPeer::recv_dst);
+    for (size_t q = 0; q < P.peers.size(); ++q) {
+        if (peer_rank) peer_rank[q] = P.peers[q].rank;
+        if (peer_nsend) peer_nsend[q] = (int32_t)P.peers[q].send_src.size();
+        if (peer_nrecv) peer_nrecv[q] = (int32_t)P.peers[q].recv_dst.size();
     }
     if (counts4) {
         counts4[0] = (int32_t)P.local_dst.size();
         counts4[1] = (int32_t)P.peers.size();
         counts4[2] = (int32_t)ns;
         counts4[3] = (int32_t)nr;
-    }
-    for (size_t k = 0; k < P.local_dst.size(); ++k) {
-        if (local_dst) local_dst[k] = P.local_dst[k];
-        if (local_src) local_src[k] = P.local_src[k];
-        if (local_sign) local_sign[k] = P.local_sign[k];
-    }
-    size_t so = 0, ro = 0;
-    for (size_t q = 0; q < P.peers.size(); ++q) {
-        const HaloPeer &p = P.peers[q];
-        if (peer_rank) peer_rank[q] = p.rank;
-        if (peer_nsend) peer_nsend[q] = (int32_t)p.send_src.size();
-        if (peer_nrecv) peer_nrecv[q] = (int32_t)p.recv_dst.size();
-        if (send_src) std::copy(p.send_src.begin(), p.send_src.end(), send_src + so);
-        if (recv_dst) std::copy(p.recv_dst.begin(), p.recv_dst.end(), recv_dst + ro);
-        so += p.send_src.size();
-        ro += p.recv_dst.size();
     }
     return 0;
 }
@@ -992,16 +1050,8 @@ int cice_evp_hip_halo_plan(int32_t *counts4, int32_t *local_dst, int32_t *local_
 // {pairs, poles, late copies}; lists may be NULL.
 int cice_evp_hip_peer_plan(int32_t *send_dst, int32_t *recv_gid)
 {
-    const HaloPlan &P = S.plan;
-    size_t so = 0, ro = 0;
-    for (const HaloPeer &p : P.peers) {
-        for (size_t k = 0; k < p.send_dst.size(); ++k)
-            if (send_dst) send_dst[so + k] = p.send_dst[k];
-        for (size_t k = 0; k < p.recv_gid.size(); ++k)
-            if (recv_gid) recv_gid[ro + k] = p.recv_gid[k];
-        so += p.send_dst.size();
-        ro += p.recv_gid.size();
-    }
+    copy_out(send_dst, S.plan.peers, &HaloPeer::send_dst);
+    copy_out(recv_gid, S.plan.peers, &HaloPeer::recv_gid);
     return 0;
 }
 
@@ -1010,46 +1060,36 @@ int cice_evp_hip_peer_plan(int32_t *send_dst, int32_t *recv_gid)
 // send_sign in send-list order; the seam images out as (src, dst at the peer, sign), in as (dst, global column, sign).
 int cice_evp_hip_fold_images_plan(int32_t *counts4, int32_t *send_sign, int32_t *out3, int32_t *in3)
 {
-    const HaloPlan &P = S.plan;
-    size_t q = 0, so = 0, oo = 0, io = 0;
-    for (const HaloPeer &p : P.peers) {
-        if (counts4) {
-            counts4[4 * q] = p.n_ghost_send; counts4[4 * q + 1] = p.n_ghost_recv;
-            counts4[4 * q + 2] = (int32_t)p.fimg_src.size(); counts4[4 * q + 3] = (int32_t)p.fimg_recv_dst.size();
-        }
-        for (size_t k = 0; k < p.send_sign.size(); ++k)
-            if (send_sign) send_sign[so + k] = p.send_sign[k];
-        for (size_t k = 0; k < p.fimg_src.size(); ++k)
-            if (out3) { out3[3 * (oo + k)] = p.fimg_src[k]; out3[3 * (oo + k) + 1] = p.fimg_dst[k]; out3[3 * (oo + k) + 2] = p.fimg_sign[k]; }
-        for (size_t k = 0; k < p.fimg_recv_dst.size(); ++k)
-            if (in3) { in3[3 * (io + k)] = p.fimg_recv_dst[k]; in3[3 * (io + k) + 1] = p.fimg_recv_col[k]; in3[3 * (io + k) + 2] = p.fimg_recv_sign[k]; }
-        so += p.send_sign.size(); oo += p.fimg_src.size(); io += p.fimg_recv_dst.size();
-        ++q;
+    const std::vector<HaloPeer> &peers = S.plan.peers;
+    for (size_t q = 0; counts4 && q < peers.size(); ++q) {
+        const HaloPeer &p = peers[q];
+        counts4[4 * q] = p.n_ghost_send; counts4[4 * q + 1] = p.n_ghost_recv;
+        counts4[4 * q + 2] = (int32_t)p.fimg_src.size(); counts4[4 * q + 3] = (int32_t)p.fimg_recv_dst.size();
     }
+    copy_out(send_sign, peers, &HaloPeer::send_sign);
+    copy_out(out3, peers, &HaloPeer::fimg_src, 3);
+    copy_out(at(out3, 1), peers, &HaloPeer::fimg_dst, 3);
+    copy_out(at(out3, 2), peers, &HaloPeer::fimg_sign, 3);
+    copy_out(in3, peers, &HaloPeer::fimg_recv_dst, 3);
+    copy_out(at(in3, 1), peers, &HaloPeer::fimg_recv_col, 3);
+    copy_out(at(in3, 2), peers, &HaloPeer::fimg_recv_sign, 3);
     return 0;
 }
 
 // recv_sign of cice_evp_hip_halo_plan's recv list (-1: the ghost lies across the tripole fold), same order
 int cice_evp_hip_peer_signs(int32_t *recv_sign)
 {
-    size_t ro = 0;
-    for (const HaloPeer &p : S.plan.peers) {
-        for (size_t k = 0; k < p.recv_sign.size(); ++k)
-            if (recv_sign) recv_sign[ro + k] = p.recv_sign[k];
-        ro += p.recv_sign.size();
-    }
+    copy_out(recv_sign, S.plan.peers, &HaloPeer::recv_sign);
     return 0;
 }
 
 int cice_evp_hip_center_plan(int32_t *count, int32_t *dst, int32_t *src, int32_t *vsign)
 {
     const HaloPlan &P = S.plan;
-    if (count) *count = (int32_t)P.center_dst.size();
-    for (size_t k = 0; k < P.center_dst.size(); ++k) {
-        if (dst) dst[k] = P.center_dst[k];
-        if (src) src[k] = P.center_src[k];
-        if (vsign) vsign[k] = P.center_vsign[k];
-    }
+    const size_t n = copy_out(dst, P.center_dst);
+    copy_out(src, P.center_src);
+    copy_out(vsign, P.center_vsign);
+    if (count) *count = (int32_t)n;
     return P.center_remote ? 1 : 0;
 }
 
@@ -1061,25 +1101,19 @@ int cice_evp_hip_fold_split_plan(int32_t which, int32_t *count, int32_t *cells)
 {
     const HaloPlan &P = S.plan;
     // (5 / 6: tripoleT -- east-west ghost cells of the top row that the stress symmetrisation leaves as images of their own array,
-    // and the cells they mirror)
-    const std::vector<int32_t> &v = which == 0 ? P.fold_shift_cells : (which == 1 ? P.center_foldr_dst :
-                                    (which == 2 ? P.stress_foldr_dst : (which == 3 ? P.center_seam_dst :
-                                    (which == 4 ? P.center_seam_slot : (which == 5 ? P.stress_own_dst : (which == 6 ? P.stress_own_src :
-                                    (which == 7 ? P.stress_corner_dst : P.stress_corner_src)))))));
-    if (count) *count = (int32_t)v.size();
-    if (cells)
-        for (size_t k = 0; k < v.size(); ++k) cells[k] = v[k];
+    // and the cells they mirror; 7 / 8: the north-west corner ghost cells and theirs)
+    const std::vector<int32_t> *lists[9] = {&P.fold_shift_cells, &P.center_foldr_dst, &P.stress_foldr_dst, &P.center_seam_dst, &P.center_seam_slot,
+                                            &P.stress_own_dst, &P.stress_own_src, &P.stress_corner_dst, &P.stress_corner_src};
+    const size_t n = copy_out(cells, *lists[which >= 0 && which < 8 ? which : 8]);
+    if (count) *count = (int32_t)n;
     return P.fold_split ? 1 : 0;
 }
 
 int cice_evp_hip_stress_plan(int32_t *count, int32_t *dst, int32_t *src)
 {
-    const HaloPlan &P = S.plan;
-    if (count) *count = (int32_t)P.stress_dst.size();
-    for (size_t k = 0; k < P.stress_dst.size(); ++k) {
-        if (dst) dst[k] = P.stress_dst[k];
-        if (src) src[k] = P.stress_src[k];
-    }
+    const size_t n = copy_out(dst, S.plan.stress_dst);
+    copy_out(src, S.plan.stress_src);
+    if (count) *count = (int32_t)n;
     return 0;
 }
 #endif  // CICE_EVP_HIP_TESTING
@@ -1089,12 +1123,10 @@ int cice_evp_hip_seam_fin_plan(int32_t *counts2, int32_t *dst, int32_t *a, int32
 {
     const HaloPlan &P = S.plan;
     if (counts2) { counts2[0] = (int32_t)P.fin_dst.size(); counts2[1] = (int32_t)P.tail; }
-    for (size_t k = 0; k < P.fin_dst.size(); ++k) {
-        if (dst) dst[k] = P.fin_dst[k];
-        if (a) a[k] = P.fin_a[k];
-        if (b) b[k] = P.fin_b[k];
-        if (coef) coef[k] = P.fin_coef[k];
-    }
+    copy_out(dst, P.fin_dst);
+    copy_out(a, P.fin_a);
+    copy_out(b, P.fin_b);
+    copy_out(coef, P.fin_coef);
     return P.stress_remote ? 1 : 0;
 }
 
@@ -1164,35 +1196,25 @@ int cice_evp_hip_cgrid_fold_xplan(int32_t loc, int32_t *info4, int32_t *count, i
     }
     const FoldList &L = P.cg_fold[loc];
     if (count) *count = (int32_t)L.dst.size();
-    for (size_t k = 0; k < L.dst.size(); ++k) {
-        if (dst) dst[k] = L.dst[k];
-        if (a) a[k] = L.a[k];
-        if (b) b[k] = L.b[k];
-        if (flip) flip[k] = L.flip[k];
-    }
+    copy_out(dst, L.dst);
+    copy_out(a, L.a);
+    copy_out(b, L.b);
+    copy_out(flip, L.flip);
     return 0;
 }
 
 int cice_evp_hip_cgrid_fold_xpeers(int32_t *peer5, int32_t *send_src, int32_t *send_dst, int32_t *recv_dst, int32_t *recv_gid)
 {
-    size_t q = 0, so = 0, ro = 0;
-    for (const HaloPeer &p : S.plan.cg_peers) {
-        if (peer5) {
-            peer5[5 * q] = p.rank; peer5[5 * q + 1] = (int32_t)p.send_src.size(); peer5[5 * q + 2] = (int32_t)p.recv_dst.size();
-            peer5[5 * q + 3] = p.n_ghost_send; peer5[5 * q + 4] = p.n_ghost_recv;
-        }
-        for (size_t k = 0; k < p.send_src.size(); ++k) {
-            if (send_src) send_src[so + k] = p.send_src[k];
-            if (send_dst) send_dst[so + k] = p.send_dst[k];
-        }
-        for (size_t k = 0; k < p.recv_dst.size(); ++k) {
-            if (recv_dst) recv_dst[ro + k] = p.recv_dst[k];
-            if (recv_gid) recv_gid[ro + k] = p.recv_gid[k];
-        }
-        so += p.send_src.size();
-        ro += p.recv_dst.size();
-        ++q;
+    const std::vector<HaloPeer> &peers = S.plan.cg_peers;
+    for (size_t q = 0; peer5 && q < peers.size(); ++q) {
+        const HaloPeer &p = peers[q];
+        peer5[5 * q] = p.rank; peer5[5 * q + 1] = (int32_t)p.send_src.size(); peer5[5 * q + 2] = (int32_t)p.recv_dst.size();
+        peer5[5 * q + 3] = p.n_ghost_send; peer5[5 * q + 4] = p.n_ghost_recv;
     }
+    copy_out(send_src, peers, &HaloPeer::send_src);
+    copy_out(send_dst, peers, &HaloPeer::send_dst);
+    copy_out(recv_dst, peers, &HaloPeer::recv_dst);
+    copy_out(recv_gid, peers, &HaloPeer::recv_gid);
     return 0;
 }
 
@@ -1205,17 +1227,12 @@ int cice_evp_hip_seam_plan(int32_t *counts3, int32_t *seam_a, int32_t *seam_b, i
         counts3[1] = (int32_t)P.seam_pole.size();
         counts3[2] = (int32_t)P.late_dst.size();
     }
-    for (size_t k = 0; k < P.seam_a.size(); ++k) {
-        if (seam_a) seam_a[k] = P.seam_a[k];
-        if (seam_b) seam_b[k] = P.seam_b[k];
-    }
-    for (size_t k = 0; k < P.seam_pole.size(); ++k)
-        if (seam_pole) seam_pole[k] = P.seam_pole[k];
-    for (size_t k = 0; k < P.late_dst.size(); ++k) {
-        if (late_dst) late_dst[k] = P.late_dst[k];
-        if (late_src) late_src[k] = P.late_src[k];
-        if (late_sign) late_sign[k] = P.late_sign[k];
-    }
+    copy_out(seam_a, P.seam_a);
+    copy_out(seam_b, P.seam_b);
+    copy_out(seam_pole, P.seam_pole);
+    copy_out(late_dst, P.late_dst);
+    copy_out(late_src, P.late_src);
+    copy_out(late_sign, P.late_sign);
     return 0;
 }
 #endif  // CICE_EVP_HIP_TESTING

@@ -27,7 +27,7 @@
 // them on a second stream while the FRAME variants of A, B, C (cg_frame_strain, cg_frame_stress_t, cg_frame_step: the same cell bodies)
 // advance every other interior cell on the loop's stream, with the fused schedule's exchanges.  They read all five ping-pong arrays
 // from the previous subcycle's buffers and write this subcycle's on frame cells only; zone cells a frame cell reads are recomputed
-// into scratch arrays (EvpCgFrame; halo_plan.cpp: build_cg_frame).
+// into scratch arrays (EvpCgFrame; cgrid_plan.cpp: build_cg_frame).
 // Arrays that nothing inside the loop reads (zetax2T, etax2U, deltaU, strintxE/yN, taubxE/yN) are stored in the last
 // subcycle of a call only.  81 instead of 99 doubles moved per cell and subcycle, 3 instead of 5 launches.
 //
@@ -364,7 +364,7 @@ __global__ __launch_bounds__(TX *TY) void cg_frame_strain(EvpCgrid A, EvpCgFrame
 }
 
 // BAND (here and in the four phase kernels below): the list-driven variant that runs on the REST of a tripole grid beside the marched
-// kernel (EvpCgBand; halo_plan.h: build_cg_march_fold).  The same arithmetic; the five ping-pong arrays are read from the previous
+// kernel (EvpCgBand; cgrid_plan.h: build_cg_march_fold).  The same arithmetic; the five ping-pong arrays are read from the previous
 // subcycle's buffers and written to this subcycle's on REST cells only (EVP_CGS_REST; without ice: the previous value taken along); a zone
 // cell evaluated because a REST cell reads its shearU / etax2T / stresspT / stressmT / stress12U stores it to the scratch array only.
 template <bool BAND>
@@ -1406,7 +1406,7 @@ __global__ __launch_bounds__(ONE_X *ONE_Y) void cg_one(EvpCgrid A, EvpCgOne T, i
 // not show in its bits.  The derived view of the static table only (else cg_one); template variants for the lengths formed in the
 // kernel (LEN), the last subcycle of a call (LAST), the general momentum step (FAST = false) and visc_method = avg_strength (AVGS),
 // described above the kernel.  Only "regular" positions (interior cells of the block, each its own source): the host hands this
-// kernel the rectangle of the block that the regular windows of 32 x 8 cover (halo_plan.cpp: strip_zones / strip_items) and keeps
+// kernel the rectangle of the block that the regular windows of 32 x 8 cover (cgrid_plan.cpp: strip_zones / strip_items) and keeps
 // the windows along the block's edges for cg_one -- which run as further workgroups of the same launch.
 // Lanes: S on 0..62 (lane 63 only loads: the east neighbour's operands), T on 1..62, U on 1..61, C -- the owned cells -- on 2..61.
 // =====================================================================

@@ -12,7 +12,7 @@
 // written with write-through stores and polled (L1-bypassing) by the reader until both tags carry the subcycle it waits for.
 //
 // Window = 16 x 16 positions, one thread each, the inner 13 x 13 owned (cg_one's window, same table of source cells:
-// halo_plan.cpp build_window_table with one extra row / column).  Levels as in cg_one, separated by workgroup barriers:
+// cgrid_plan.cpp build_window_table with one extra row / column).  Levels as in cg_one, separated by workgroup barriers:
 //   S  strain_rates_U (shearU alone except for deltaU in the last subcycle) at every position
 //   T  stressC_T at tx, ty >= 1          U  corner viscosity + stressC_U at tx, ty <= 14
 //   C  div_stress + stepu_C / stepv_C on the owned cells; publish.
@@ -153,7 +153,7 @@ __device__ __forceinline__ void push1(const EvpCgrid &A, size_t c, double *f, do
 //
 // FOLD: a tripole (u-fold) grid, ice_boundary.F90:1626-1722.  The windows at the fold (tl.w bit 0) own the rows up to the fold row NY at
 // tile row tf and hold, in the three tile rows above it, a MIRRORED mini-tile in SOURCE orientation (global rows NY-2, NY-1, NY; the table:
-// halo_plan.cpp build_fold_window_table): recomputing a ghost cell in ITS orientation would sum in another order, recomputing the cell it
+// cgrid_plan.cpp build_fold_window_table): recomputing a ghost cell in ITS orientation would sum in another order, recomputing the cell it
 // mirrors in that cell's own orientation does not.  The two rows that face each other across the fold (tile rows tf and tf+3, "cls" 1 / 3)
 // read "north" through a remap: E-face / corner type fields at column 15 - tx of the other row, centre / N-face type at 16 - tx (N faces
 // and corners one row further), vectors with the sign changed.  Everything ON the fold (N faces and NE corners of row NY: vvelN, uvelN,
@@ -422,7 +422,7 @@ __global__ __launch_bounds__(X *Y, 3) void cg_res(EvpCgrid A, EvpCgRes R)
     // Entry e of the (Y+1) x (X+1) tile is polled if it lies outside the owned range and has a producer (not static);
     // (X, Y), the one entry no level reads, is left out
     // ... and lies within reach of the owned cells (EVP_CGRES_REACH positions beyond the last owned column / row; the rule of
-    // halo_plan.h: cgres_in_reach, which also makes the publishers' map): a narrow window at a block's edge would otherwise poll far
+    // cgrid_plan.h: cgres_in_reach, which also makes the publishers' map): a narrow window at a block's edge would otherwise poll far
     // into windows that do not poll it back, and the two-slot record protocol needs every dependency to be mutual
     const int last_ex = min(X - 2, 2 + q.y - tl.y), last_ey = min(Y - 2, 2 + jmax - tl.z);
     auto ring_src = [&](int e) -> int {
@@ -517,7 +517,7 @@ __global__ __launch_bounds__(X *Y, 3) void cg_res(EvpCgrid A, EvpCgRes R)
         constexpr bool LAST = decltype(LASTC)::value;
         const unsigned want = R.tag_base + (unsigned)k;
         // (four slots: a window that is read without reading back may be up to three subcycles ahead of its reader -- the host has
-        // checked that it cannot be more, halo_plan.cpp: cgres_dependencies -- and still not overwrite what that reader waits for)
+        // checked that it cannot be more, cgrid_plan.cpp: cgres_dependencies -- and still not overwrite what that reader waits for)
         const v4u *rd = (const v4u *)R.rec[(k + R.par0) & (EVP_CGRES_SLOTS - 1)];
         v4u *wr = (v4u *)R.rec[(k + 1 + R.par0) & (EVP_CGRES_SLOTS - 1)];
         // (the operand planes never change inside the loop: without an index the compiler cannot see through it hoists every one

@@ -423,7 +423,7 @@ void evp_launch_cgrid_one(const EvpCgrid &A, const EvpCgOne &T, int fast, int la
 // The interior of a large block, marched (evp_cgrid.hip: cg_strip): one wave per item = strip of 64 positions (up to 60 owned
 // columns) x segment of rows; T carries the buffers and tables as for cg_one (its window list is not used).  The derived view of
 // the static table (T.gmask) only; fast, last, A.avg_strength: as for cg_one.
-#define EVP_CGSTRIP_AHEAD 1     // == STRIP_AHEAD (halo_plan.h): rows levels S and T and the face averages run ahead of the momentum step
+#define EVP_CGSTRIP_AHEAD 1     // == STRIP_AHEAD (cgrid_plan.h): rows levels S and T and the face averages run ahead of the momentum step
 struct EvpCgStrip {
     const int *items;             // x 6: block, column of lane 2, first and last owned row (1-based), first and last owned lane
     int nitems, per_xcd;          // items; workgroups (of four items) per XCD (launch = 8 * per_xcd workgroups)
@@ -431,14 +431,14 @@ struct EvpCgStrip {
 };
 void evp_launch_cgrid_strip(const EvpCgrid &A, const EvpCgOne &T, const EvpCgStrip &Z, const EvpCgOne *E, int fast, int last, hipStream_t st);
 // What a plan that splits a rank's interior cells between cg_strip (the ZONE) and list-driven kernels (the REST) says of an array cell:
-// the bits of EvpCgFrame::cells and EvpCgBand::cells, written by halo_plan.cpp (build_cg_frame, build_cg_march_fold) and tested by the
+// the bits of EvpCgFrame::cells and EvpCgBand::cells, written by cgrid_plan.cpp (build_cg_frame, build_cg_march_fold) and tested by the
 // kernels of evp_cgrid.hip.  REST: an interior cell that is no zone cell -- the "frame" of the schedule for several ranks as well; the
 // momentum step runs on these.  S, T, U, AVG: strain_rates_U's shear, stressC_T, etax2U + stressC_U and the velocity averages run on the
 // cell (REST cells, and the zone cells a later level reads: to scratch arrays only).  The frame plan sets REST, S, T and ZONE only.
 enum { EVP_CGS_REST = 1, EVP_CGS_S = 2, EVP_CGS_T = 4, EVP_CGS_ZONE = 8, EVP_CGS_U = 16, EVP_CGS_AVG = 32,
        EVP_CGS_FOLDROW = 64 };   // FOLDROW: an interior cell of global row NY (tripole grids)
 // The three fused kernels on the FRAME of a rank whose zone cg_strip marches at the same time (several ranks; evp_cgrid.hip:
-// cg_frame_*; halo_plan.h: build_cg_frame).  They read the five ping-pong arrays of the previous subcycle (uE_in .. sm_in, A.s12_in) and
+// cg_frame_*; cgrid_plan.h: build_cg_frame).  They read the five ping-pong arrays of the previous subcycle (uE_in .. sm_in, A.s12_in) and
 // write this subcycle's (A.f[...]) on frame cells only; intermediates of the zone cells a frame cell reads go to the scratch arrays.
 struct EvpCgFrame {
     const uint8_t *cells;         // per cell: EVP_CGS_* (REST = frame cell; levels S, T)
@@ -450,7 +450,7 @@ struct EvpCgFrame {
 // level: 0 averages + strain_rates_U (phase 7), 1 stressC_T (phase 10), 2 stressC_U + momentum step (phase 8; fast: phase 11)
 void evp_launch_cgrid_frame(const EvpCgrid &A, const EvpCgFrame &F, int level, int fast, int last, hipStream_t st);
 // The five un-fused phase kernels on the REST of a tripole grid whose zone cg_strip marches at the same time (one rank; evp_cgrid.hip:
-// cg_band_*; halo_plan.h: build_cg_march_fold).  They read the five ping-pong arrays of the previous subcycle (uE_in .. s12_in) and
+// cg_band_*; cgrid_plan.h: build_cg_march_fold).  They read the five ping-pong arrays of the previous subcycle (uE_in .. s12_in) and
 // write this subcycle's (A.f[...]) on REST cells only -- a REST cell without ice takes the previous value along, so that a buffer's REST
 // cells are what the arrays of the five-phase schedule hold; intermediates of the zone cells a REST cell reads go to the scratch arrays.
 // All 23 static arrays are loaded: the start-up identities do not hold next to the fold.
@@ -466,13 +466,13 @@ void evp_launch_cgrid_band(const EvpCgrid &A, const EvpCgBand &B, int phase, hip
 // All subcycles of a call in one launch, state on the chip (evp_cgrid_res.hip: cg_res).  Windows of 16 x 16 positions, the inner
 // 13 x 13 owned; tab: per window the source cell of its 17 x 17 positions (one row / column more than cg_one's: what level S reads
 // of its north / east neighbour), as in EvpCgOne.  The velocities another window's rim mirrors travel as tagged 32-byte records.
-#define EVP_CGRES_REACH 3      // == CGRES_REACH (halo_plan.h): positions beyond the last owned column / row a resident window polls
+#define EVP_CGRES_REACH 3      // == CGRES_REACH (cgrid_plan.h): positions beyond the last owned column / row a resident window polls
 #define EVP_CGRES_SLOTS 4      // == CGRES_SLOTS: record slots per cell; the record of subcycle j sits in slot (j + par0) mod 4, so a window
-                               // may be up to three subcycles ahead of one that reads it (halo_plan.h: cgres_dependencies proves it is not more)
+                               // may be up to three subcycles ahead of one that reads it (cgrid_plan.h: cgres_dependencies proves it is not more)
 struct EvpCgRes {
     const int *tab;               // [ntiles][17 * 17]
     const int4 *tiles;            // block, first owned i, first owned j (1-based), fold: fold window | tf << 8 | last owned row << 16
-    const int4 *tiles2;           // fold (tripole grids): global column of tile column 0, NX, -, -   (halo_plan.cpp: build_fold_window_table)
+    const int4 *tiles2;           // fold (tripole grids): global column of tile column 0, NX, -, -   (cgrid_plan.cpp: build_fold_window_table)
     int fold;                     // 1: tripole (u-fold) grid, the kernel's FOLD variant
     int slow;                     // 1: the SLOW variant (seabed stress, waterx != uocn, rheofact != 1 on some ice cell: general momentum step)
     const int *order;             // [ntiles] window run by workgroup w (NULL: identity): the windows that hold ice in this call

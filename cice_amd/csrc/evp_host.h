@@ -37,6 +37,7 @@
 #include "../../include/cice_evp_hip_testing.h"   // (declarations; the definitions exist under CICE_EVP_HIP_TESTING only)
 #include "evp_device.h"
 #include "halo_plan.h"
+#include "cgrid_plan.h"
 
 namespace evp_host {
 

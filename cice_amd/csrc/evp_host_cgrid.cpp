@@ -80,11 +80,11 @@ struct CGridState {
         long strip_cells = 0;    // cells the marched kernel owns
     } one;
     // several ranks: the marched kernel on the rectangles above beside the fused chain on every other interior cell (enqueue_fused:
-    // "zone marched + frame"; halo_plan.cpp: build_cg_frame).  cells: the EVP_CGS_* bits (REST = frame cell); three levels; scr:
+    // "zone marched + frame"; cgrid_plan.cpp: build_cg_frame).  cells: the EVP_CGS_* bits (REST = frame cell); three levels; scr:
     // shearU, etax2T, stresspT, stressmT of the zone cells the frame reads; ncells: frame cells
     CellLists fr;
     // tripole / tripoleT on one rank: the marched kernel on the rectangles under the fold band beside list-driven variants of the five
-    // phase kernels on every other interior cell (enqueue_march_fold: "marched zone + fold band"; halo_plan.cpp: build_cg_march_fold).
+    // phase kernels on every other interior cell (enqueue_march_fold: "marched zone + fold band"; cgrid_plan.cpp: build_cg_march_fold).
     // The items live in `one` (items, nitems, strip_*)
     struct MarchFold {
         CellLists rest;                      // cells: the EVP_CGS_* bits; five phases; scr: shearU, etax2T, stresspT, stressmT, stress12U; ncells: REST cells
@@ -104,7 +104,7 @@ struct CGridState {
     // all subcycles of a call in one launch, state on the chip (evp_cgrid_res.hip: cg_res)
     struct Res {
         int *tab = nullptr;
-        int4 *tiles = nullptr, *tiles2 = nullptr;     // (tiles2: tripole grids, halo_plan.cpp build_fold_window_table)
+        int4 *tiles = nullptr, *tiles2 = nullptr;     // (tiles2: tripole grids, cgrid_plan.cpp build_fold_window_table)
         int ntiles = 0;
         uint8_t *pubmap = nullptr;
         uint8_t *gmask = nullptr;    // tripole grids: the land masks as bits (elsewhere CG.gmask, which the one-launch kernels share)
@@ -454,7 +454,7 @@ static std::vector<uint8_t> derive_geometry_check(const double *const *g, std::s
 }
 
 // The six lengths the reference's start-up forms from HTN (= dxN) and HTE (= dyE), BIT FOR BIT on every cell the marched kernel would
-// form them for in the rectangle z (halo_plan.h: strip_len_range; false too where that cannot be verified)
+// form them for in the rectangle z (cgrid_plan.h: strip_len_range; false too where that cannot be verified)
 static bool strip_lengths_hold(const StripZone &z, int EX, int EY, const double *const *g)
 {
     auto same = [](double a, double b) { return std::memcmp(&a, &b, 8) == 0; };
@@ -789,7 +789,7 @@ static int build_one_tables(const double *const *static23)
     const int strip = one_strip_switch();
     const cice_evp_hip_dims d = host_dims();
     std::vector<int32_t> tab, tiles;
-    build_window_table(d, P, OX, OY, strip, tiles, tab);       // halo_plan.cpp (host only: CPU known-answer test)
+    build_window_table(d, P, OX, OY, strip, tiles, tab);       // cgrid_plan.cpp (host only: CPU known-answer test)
     CGridState::One &O = CG.one;
     const bool ranks = remote();                 // no window kernel here: the table only tells which cells are regular
     if (!ranks) {
@@ -820,7 +820,7 @@ static int build_one_tables(const double *const *static23)
             tab.swap(etab);
         }
         const int nt = (int)(tiles.size() / 4), sx = EX - 3, sy = EY - 3;
-        using Zone = StripZone;                        // (halo_plan.h: the planning is host-only code with a CPU test)
+        using Zone = StripZone;                        // (cgrid_plan.h: the planning is host-only code with a CPU test)
         std::vector<Zone> zones;
         long zcells = 0;
         std::vector<uint8_t> in_zone((size_t)nt, 0);
@@ -897,9 +897,9 @@ static int build_one_tables(const double *const *static23)
 }
 
 // ---- tripole / tripoleT on one rank: what the marched kernel needs under the fold band, and the lists of the five phase kernels
-// that advance every other interior cell (halo_plan.cpp: build_cg_march_fold plans and checks; enqueue_march_fold runs it).  Built
+// that advance every other interior cell (cgrid_plan.cpp: build_cg_march_fold plans and checks; enqueue_march_fold runs it).  Built
 // only where the schedule can be used; a rank where no rectangle survives keeps today's schedule, with the reason in CG.mf.why.
-static_assert(STRIP_AHEAD == EVP_CGSTRIP_AHEAD, "halo_plan.h and evp_device.h must agree on how far the marched kernel's loop runs ahead");
+static_assert(STRIP_AHEAD == EVP_CGSTRIP_AHEAD, "cgrid_plan.h and evp_device.h must agree on how far the marched kernel's loop runs ahead");
 static int build_march_fold_tables(const double *const *static23)
 {
     const HaloPlan &P = S.plan;
@@ -1036,8 +1036,8 @@ static int build_res_tables(const double *const *static23)
     Q.ntiles = (int)(tiles.size() / 4);
     // the last owned row of a window, the last row of positions that matter to its owned cells (fold windows: the fold row)
     auto jmax_of = [&](int w) { return tripole ? tiles[4 * w + 3] >> 16 : S.jhi[tiles[4 * w]]; };
-    // who publishes what, and is every hand-off mutual?  (halo_plan.cpp: cgres_dependencies -- the rule the kernel's ring applies)
-    static_assert(CGRES_REACH == EVP_CGRES_REACH && CGRES_SLOTS == EVP_CGRES_SLOTS, "halo_plan.h and evp_device.h must agree on the windows' ring");
+    // who publishes what, and is every hand-off mutual?  (cgrid_plan.cpp: cgres_dependencies -- the rule the kernel's ring applies)
+    static_assert(CGRES_REACH == EVP_CGRES_REACH && CGRES_SLOTS == EVP_CGRES_SLOTS, "cgrid_plan.h and evp_device.h must agree on the windows' ring");
     std::vector<uint8_t> pub;
     {
         int n_edges = 0, n_oneway = 0;

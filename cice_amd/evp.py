@@ -58,7 +58,7 @@ TEST_EXPORTS = [
     "cice_evp_hip_debug_device_allocs", "cice_evp_hip_debug_cuload", "cice_evp_hip_debug_prof", "cice_evp_hip_debug_cgrid_prof", "cice_evp_hip_debug_cgres_prof", "cice_evp_hip_plan_build", "cice_evp_hip_halo_plan", "cice_evp_hip_seam_plan",
     "cice_evp_hip_peer_plan", "cice_evp_hip_peer_signs", "cice_evp_hip_center_plan", "cice_evp_hip_stress_plan",
     "cice_evp_hip_fold_split_plan", "cice_evp_hip_plan_flags", "cice_evp_hip_fold_images_plan", "cice_evp_hip_cgrid_fold_xplan",
-    "cice_evp_hip_cgrid_fold_xpeers",
+    "cice_evp_hip_cgrid_fold_xpeers", "cice_evp_hip_plan_dump",
 ]
 # environment switches only the test build reads (cice_amd/csrc/evp_host.h: env_test): experiments, fault injection, routing
 # of on-device copies through the remote transports.  An EvpHip made while one of them is set uses the test build.
@@ -921,3 +921,15 @@ def halo_plan(dims: Dims) -> dict:
                 peer_nsend=pns[:npeer], peer_nrecv=pnr[:npeer], send_src=ss[:ns], recv_dst=rd[:nr],
                 seam_a=sa[:npair], seam_b=sb[:npair], seam_pole=sp[:npole],
                 late_dst=td[:nlate], late_src=ts[:nlate], late_sign=tg[:nlate])
+
+
+def halo_plan_dump(dims: Dims) -> np.ndarray:
+    """Host-only: every member of the halo plan of `dims.rank` as one int32 array (see the testing header).  Raises EvpHipError
+    with the library's text where the plan refuses `dims`."""
+    lib = load_library(testing=True)
+    _check(lib, lib.cice_evp_hip_plan_build(C.byref(dims)), "(plan_build)")
+    out = np.zeros(lib.cice_evp_hip_plan_dump(None, 0), dtype=np.int32)
+    n = lib.cice_evp_hip_plan_dump(_ip(out), len(out))
+    if n != len(out):
+        _check(lib, n if n < 0 else -1, "(plan_dump)")
+    return out

@@ -33,19 +33,19 @@ int cice_evp_hip_cgrid_window_plan(const cice_evp_hip_dims *dims, int32_t ox, in
 /* The same with (ox + extra) x (oy + extra) positions per window, extra = 0 or 1 (same owned range and window stride): the table of the
  * on-chip resident C-grid kernel, whose level S reads one position beyond the window to the east and north (evp_cgrid_res.hip).
  * extra = 2: that kernel's table on a tripole (u-fold) grid, 17 x 17 positions (ox, oy unused): the windows at the fold own up to
- * 11 rows and carry a mirrored mini-tile above the fold row, tiles4[3] = fold flag | tf << 8 | last owned row << 16 (halo_plan.cpp:
+ * 11 rows and carry a mirrored mini-tile above the fold row, tiles4[3] = fold flag | tf << 8 | last owned row << 16 (cgrid_plan.cpp:
  * build_fold_window_table); -5 when a mirrored cell is not on this rank.                                                          */
 int cice_evp_hip_cgrid_window_plan_ext(const cice_evp_hip_dims *dims, int32_t ox, int32_t oy, int32_t extra, int32_t *ntiles,
                                        int32_t *tiles4, int32_t *tab);
 /* Host only: the hand-off graph of the on-chip resident C-grid kernel's windows (closed / cyclic grids: the table of extra = 1;
  * tripole: of extra = 2).  A window depends on another when it polls a cell that one owns -- every non-owned position with a
- * producer within 3 positions of its last owned column / row (halo_plan.h: cgres_in_reach; fold windows: every position).  n_edges:
+ * producer within 3 positions of its last owned column / row (cgrid_plan.h: cgres_in_reach; fold windows: every position).  n_edges:
  * dependencies, n_oneway: those that are not mutual, n_unsafe: those of them with no chain of at most 3 dependencies back (the
  * window read could then be four subcycles ahead of its reader and overwrite one of the kernel's four record slots per cell that
  * the reader still waits for): the library does not use the kernel unless n_unsafe == 0.                                          */
 int cice_evp_hip_cgrid_window_deps(const cice_evp_hip_dims *dims, int32_t *n_windows, int32_t *n_edges, int32_t *n_oneway, int32_t *n_unsafe);
 /* Host only: how the one-launch C-grid schedule of large domains shares a rank's cells between the marched kernel (cg_strip) and the
- * windowed kernel (halo_plan.h: strip_zones, strip_items, strip_windows, on the window table of ex x ey positions).  items6: per work
+ * windowed kernel (cgrid_plan.h: strip_zones, strip_items, strip_windows, on the window table of ex x ey positions).  items6: per work
  * item block, column of lane 2, first and last owned row (1-based), first and last owned lane (lane l holds column items6[1] - 2 + l);
  * tiles4 / in_zone: the windows (block, first owned i, first owned j, regular) and 1 where the marched kernel owns the window's cells.
  * lo0: first lane that may own a column (2, or 3 where the kernel forms the lengths); slots, seg_min, seg as in strip_items.  Pass NULL
@@ -54,14 +54,14 @@ int cice_evp_hip_cgrid_strip_plan(const cice_evp_hip_dims *dims, int32_t ex, int
                                   int32_t *n_items, int32_t *items6, int32_t items_cap, int32_t *n_windows, int32_t *tiles4, uint8_t *in_zone, int32_t windows_cap,
                                   int32_t *seg_rows);
 /* Host only: the rectangles of cice_evp_hip_cgrid_strip_plan (same dims, ex, ey), 10 ints each in zones10: block, first owned column
- * of its first and last window column, first owned row of its first and last window row (halo_plan.h: strip_zones -- window rows and
+ * of its first and last window column, first owned row of its first and last window row (cgrid_plan.h: strip_zones -- window rows and
  * columns already given back where an item would load outside the block's array), 1 if the lengths may be formed for it, and the
- * rectangle of cells the host then checks them on (first and last column, first and last row; halo_plan.h: strip_len_range).  The
+ * rectangle of cells the host then checks them on (first and last column, first and last row; cgrid_plan.h: strip_len_range).  The
  * library may still give a window row back where that check fails.  Pass NULL to learn the count.                                    */
 int cice_evp_hip_cgrid_strip_zones(const cice_evp_hip_dims *dims, int32_t ex, int32_t ey, int32_t *n_zones, int32_t *zones10, int32_t zones_cap);
 /* Host only: how a rank with neighbours on other ranks shares its interior cells between the marched kernel (the zone: the items of
  * cice_evp_hip_cgrid_strip_plan with the same ex, ey, lo0, slots, seg_min, seg) and the frame variants of the three fused kernels
- * (cice_amd/csrc/halo_plan.h: build_cg_frame, which checks the plan's invariants itself and fails with -5 where one does not hold).
+ * (cice_amd/csrc/cgrid_plan.h: build_cg_frame, which checks the plan's invariants itself and fails with -5 where one does not hold).
  * cells: one byte per array cell -- 1 frame cell, 2 level S (strain_rates_U) runs here, 4 level T (stressC_T), 8 zone cell.  wg: the
  * workgroups of 64 x 4 cells, id = (block * ceil(ny_block / 4) + row) * ceil(nx_block / 64) + column, of level S, then T, then C (the
  * momentum step: frame cells only).  info6 = {zone cells, frame cells, workgroups of S, T, C, items}.  Arrays may be NULL.  Returns
@@ -70,7 +70,7 @@ int cice_evp_hip_cgrid_frame_plan(const cice_evp_hip_dims *dims, int32_t ex, int
                                   int64_t *info6, uint8_t *cells, int32_t *wg, int32_t wg_cap, int32_t *items6, int32_t items_cap);
 /* Host only: how ONE rank shares the interior of a tripole / tripoleT grid between the marched kernel (the zone: strip_zones' rectangles
  * cut from the top until the fold rule holds) and the list-driven variants of the five phase kernels (the rest: the band under the fold
- * and the block edges) -- cice_amd/csrc/halo_plan.h: build_cg_march_fold, which checks the plan's invariants itself (-5 where one fails).
+ * and the block edges) -- cice_amd/csrc/cgrid_plan.h: build_cg_march_fold, which checks the plan's invariants itself (-5 where one fails).
  * len: 1 the items own lanes >= 3 (the kernel forms six lengths), 0 lanes >= 2; slots, seg_min (0: by size), seg as in strip_items.
  * cells: one byte per array cell -- 1 rest cell (phase 3 runs here), 2 phase 0, 4 phase 1, 8 zone cell, 16 phase 2, 32 phase 4, 64 an
  * interior cell of global row NY.  wg: the workgroups of 64 x 4 cells of phases 0 .. 4, numbered as for cice_evp_hip_cgrid_frame_plan.
@@ -124,6 +124,10 @@ int cice_evp_hip_debug_cgres_prof(uint64_t *out, int32_t ntiles_max);
 int cice_evp_hip_debug_device_allocs(int64_t *count);
 /* Host-only: build the plan for `dims` without touching a device (CPU tests). */
 int cice_evp_hip_plan_build(const cice_evp_hip_dims *dims);
+/* The whole plan built last as int32 values: every member of HaloPlan in declaration order (cice_amd/csrc/halo_plan.h) -- a list as
+ * its length, then its entries; the peer lists (peers, cg_peers) as their length, then every peer member by member; cg_fold[0 .. 3];
+ * the error text as its length, then its characters.  Returns the number of values; out = NULL: only counts; -1 when n is too small. */
+int cice_evp_hip_plan_dump(int32_t *out, int32_t n);
 int cice_evp_hip_halo_plan(int32_t *counts4, int32_t *local_dst, int32_t *local_src,
                            int32_t *local_sign, int32_t *peer_rank, int32_t *peer_nsend,
                            int32_t *peer_nrecv, int32_t *send_src, int32_t *recv_dst);
