@@ -4,6 +4,7 @@
 // state and the helpers live in evp_host*.cpp (overview in evp_host.h).
 // =====================================================================
 #include "evp_host.h"
+#include "rim_plan.h"
 
 using namespace evp_host;
 
@@ -1003,6 +1004,32 @@ int cice_evp_hip_debug_prof(uint64_t *out, int32_t ntiles_max)
     return S.res2_ntiles > 0 ? 0 : -1;
 }
 
+// Host-only: the lane tables of the resident kernel's rim-wave schedule (rim_plan.h) for ONE block of ni x nj cells with one
+// ghost cell all round, closed or cyclic; mask: (ni + 2) x (nj + 2) bytes, bit 0 ice T-cell, bit 1 ice U-cell.  Returns the number
+// of tiles (out pointers may be NULL to ask for it), or < 0.  Per tile: perm[256], uperm[256] (255: none), info8 = {|L_T|, |L_U|,
+// active chunks, active chunks of the ice-first packing, ok, tiles per row, tiles per column, 0}; cls[256] as resident2_setup's.
+int cice_evp_hip_rim_plan(int32_t ni, int32_t nj, int32_t cyclic_ew, int32_t cyclic_ns, const uint8_t *mask, int32_t ntiles_max,
+                          uint8_t *perm, uint8_t *uperm, int32_t *info8, uint8_t *cls)
+{
+    if (ni < 1 || nj < 1 || !mask) return fail(-1, "rim_plan: bad argument");
+    rim_plan::Block B;
+    rim_plan::block(ni, nj, cyclic_ew != 0, cyclic_ns != 0, mask, B);
+    const int nt = B.gx * B.gy;
+    if (!perm && !uperm && !info8 && !cls) return nt;
+    if (ntiles_max < nt) return fail(-1, "rim_plan: room for %d tiles, %d needed", (int)ntiles_max, nt);
+    for (int t = 0; t < nt; ++t) {
+        const rim_plan::Tile &tl = B.tiles[(size_t)t];
+        if (perm) std::copy(tl.perm, tl.perm + 256, perm + (size_t)t * 256);
+        if (uperm) std::copy(tl.uperm, tl.uperm + 256, uperm + (size_t)t * 256);
+        if (cls) std::copy(&B.cls[(size_t)t * 256], &B.cls[(size_t)t * 256] + 256, cls + (size_t)t * 256);
+        if (info8) {
+            const int32_t v[8] = {tl.n_lt, tl.n_lu, tl.nact, tl.nact_packed, tl.ok ? 1 : 0, B.gx, B.gy, 0};
+            std::copy(v, v + 8, info8 + (size_t)t * 8);
+        }
+    }
+    return nt;
+}
+
 // Host-only: build the halo plan for `dims` without touching a device (tests).
 int cice_evp_hip_plan_build(const cice_evp_hip_dims *dims)
 {
@@ -1147,7 +1174,8 @@ int cice_evp_hip_describe_path(char *buf, int32_t n)
     if (!buf || n < 2) return fail(-1, "describe_path: no buffer");
     const State::March &M = S.march;
     const char *kernel = S.res_mode == 1 ? (S.res_remote ? "on-chip resident (tagged records, neighbours on other ranks)"
-                                                       : "on-chip resident (tagged records)")
+                                                       : S.res2_rimu ? "on-chip resident (tagged records; edge U-cells in the rim wave)"
+                                                                     : "on-chip resident (tagged records)")
                          : (M.last_call ? (M.kpass == 4 ? "four subcycles per pass (marching)" : M.kpass == 3 ? "three subcycles per pass (marching)" : "two subcycles per pass (marching)")
                                       : "one subcycle per launch (streaming)");
     const char *transport = S.plan.peers.empty() ? "none (one rank)" : (S.direct.on ? "mailbox over HIP IPC" : (S.have_comm ? "RCCL send/recv" : "not set up"));

@@ -296,19 +296,31 @@ struct StepuOut {
     double u, v, strintx, strinty, taubx, tauby;
 };
 
+// What the momentum step of a U-cell knows before any stress partial of the subcycle exists: it depends on the cell's previous
+// velocity and on per-call operands only (stepu_pre_cell), and what needs the eight partials (stepu_post_cell).  Every expression
+// is the reference's, whole and in its order, so both builds round / contract as the one-piece form did; stepu_cell is the two in
+// turn.  (evp_resident2.hip, RIMU: the rim wave works out the first part for the next subcycle while it is off the hand-off chain.)
+struct StepuPre {
+    double taux, tauy, Cb, cca, ccb, ab2;
+    double bu, bv;               // brlx*uold + revp*uvel_init, brlx*vold + revp*vvel_init (WITH_B)
+};
+
 // TBU: false when the host has verified TbU == 0 on every ice U-cell (seabed stress off): Cb = 0/(...) == 0
-template <bool SIMPLE = false, bool TBU = true>
-__device__ __forceinline__ void stepu_cell(const EvpScalars &p, const StepuIn &a, StepuOut &o)
+// WITH_B: the first part also forms bu, bv; without, the second part forms them inside cc1 / cc2, where the one-piece form had
+// them -- stepu_cell takes that order, so that the kernels that call it compile to the code they compiled to before the split
+template <bool SIMPLE = false, bool TBU = true, bool WITH_B = true>
+__device__ __forceinline__ void stepu_pre_cell(const EvpScalars &p, const StepuIn &a, StepuPre &w)
 {
     const double uold = a.uold, vold = a.vold;
     // (magnitude of relative ocean current)*rhow*drag*aice
     const double du = a.uocn - uold, dv = a.vocn - vold;
     const double vrel = a.vrelfac * sqrt(du * du + dv * dv);
     // ice/ocean stress
-    const double taux = vrel * a.waterx;
-    const double tauy = vrel * a.watery;
+    w.taux = vrel * a.waterx;
+    w.tauy = vrel * a.watery;
     double Cb = 0.0;
     if (TBU) Cb = a.TbU / (sqrt(uold * uold + vold * vold) + p.u0);   // for seabed stress
+    w.Cb = Cb;
     // revp = 0 for classic evp, 1 for revised evp
     double cca, ccb;
     if (SIMPLE) {      // revp == 0, cosw == 1, sinw == 0: ccb = fm + (+-0) == fm for either sign of fm
@@ -318,24 +330,50 @@ __device__ __forceinline__ void stepu_cell(const EvpScalars &p, const StepuIn &a
         cca = (p.brlx + p.revp) * a.Umassdti + vrel * p.cosw + Cb;
         ccb = a.fm + copysign(1.0, a.fm) * vrel * p.sinw;
     }
-    const double ab2 = cca * cca + ccb * ccb;
+    w.cca = cca; w.ccb = ccb;
+    w.ab2 = cca * cca + ccb * ccb;
+    if (!WITH_B) return;
+    if (SIMPLE) {      // revp*uvel_init == +0.0 (the kernels pass uvel_init = 0 when revp == 0); the add stays: -0 + 0 = +0
+        w.bu = p.brlx * uold + 0.0;
+        w.bv = p.brlx * vold + 0.0;
+    } else {
+        w.bu = p.brlx * uold + p.revp * a.uvel_init;
+        w.bv = p.brlx * vold + p.revp * a.vvel_init;
+    }
+}
+
+// the part that reads the stress partials (a.sx0 .. a.sy3; a.uarear, a.forcex / forcey, a.Umassdti besides)
+template <bool SIMPLE = false, bool WITH_B = true>
+__device__ __forceinline__ void stepu_post_cell(const EvpScalars &p, const StepuIn &a, const StepuPre &w, StepuOut &o)
+{
     // divergence of the internal stress tensor
     o.strintx = a.uarear * (a.sx0 + a.sx1 + a.sx2 + a.sx3);
     o.strinty = a.uarear * (a.sy0 + a.sy1 + a.sy2 + a.sy3);
     // finally, the velocity components
     double cc1, cc2;
-    if (SIMPLE) {      // revp*uvel_init == +0.0 (the kernels pass uvel_init = 0 when revp == 0); the add stays: -0 + 0 = +0
-        cc1 = o.strintx + a.forcex + taux + a.Umassdti * (p.brlx * uold + 0.0);
-        cc2 = o.strinty + a.forcey + tauy + a.Umassdti * (p.brlx * vold + 0.0);
+    if (WITH_B) {
+        cc1 = o.strintx + a.forcex + w.taux + a.Umassdti * w.bu;
+        cc2 = o.strinty + a.forcey + w.tauy + a.Umassdti * w.bv;
+    } else if (SIMPLE) {      // revp*uvel_init == +0.0 (the kernels pass uvel_init = 0 when revp == 0); the add stays: -0 + 0 = +0
+        cc1 = o.strintx + a.forcex + w.taux + a.Umassdti * (p.brlx * a.uold + 0.0);
+        cc2 = o.strinty + a.forcey + w.tauy + a.Umassdti * (p.brlx * a.vold + 0.0);
     } else {
-        cc1 = o.strintx + a.forcex + taux + a.Umassdti * (p.brlx * uold + p.revp * a.uvel_init);
-        cc2 = o.strinty + a.forcey + tauy + a.Umassdti * (p.brlx * vold + p.revp * a.vvel_init);
+        cc1 = o.strintx + a.forcex + w.taux + a.Umassdti * (p.brlx * a.uold + p.revp * a.uvel_init);
+        cc2 = o.strinty + a.forcey + w.tauy + a.Umassdti * (p.brlx * a.vold + p.revp * a.vvel_init);
     }
-    o.u = (cca * cc1 + ccb * cc2) / ab2;
-    o.v = (cca * cc2 - ccb * cc1) / ab2;
+    o.u = (w.cca * cc1 + w.ccb * cc2) / w.ab2;
+    o.v = (w.cca * cc2 - w.ccb * cc1) / w.ab2;
     // seabed stress component for outputs
-    o.taubx = -o.u * Cb;
-    o.tauby = -o.v * Cb;
+    o.taubx = -o.u * w.Cb;
+    o.tauby = -o.v * w.Cb;
+}
+
+template <bool SIMPLE = false, bool TBU = true>
+__device__ __forceinline__ void stepu_cell(const EvpScalars &p, const StepuIn &a, StepuOut &o)
+{
+    StepuPre w;
+    stepu_pre_cell<SIMPLE, TBU, false>(p, a, w);
+    stepu_post_cell<SIMPLE, false>(p, a, w, o);
 }
 
 // ---------------------------------------------------------------------

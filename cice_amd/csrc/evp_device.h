@@ -86,6 +86,7 @@ struct EvpResident2 {
     // 16 x 16 tiles only (rim wave / interior waves, see evp_resident2.hip): which T-cell of the tile a
     // thread owns, the T-cells that read ring velocities first; how many waves hold such cells / ring entries
     const uint8_t *perm;       // [ntiles][256] cell position trow*16 + tcol of (permuted) thread index
+    const uint8_t *uperm;      // [ntiles][256] RIMU: U-cell position of (permuted) thread index, 255 none (rim_plan.h); perm and nact are that plan's then
     const uint8_t *late_waves; // [ntiles]
     const uint8_t *nact;       // [ntiles] chunks (64 entries of perm) that hold ice cells: the first nact
     const uint8_t *nlate;      // [ntiles] COOP: rim T-cells with ice = the first nlate entries of perm (<= 64); NULL: the variant is off
@@ -115,9 +116,10 @@ struct EvpResident2 {
 int evp_resident2_max_blocks_per_cu(bool strict, int cap, unsigned flags, int logw, bool remote, bool coop = false);
 bool evp_resident2_coop_built(bool strict, int cap, int logw, bool remote);   // the rim-cells-by-corners variant exists for this combination
 bool evp_resident2_lean_built(bool strict, int cap, int logw, bool remote);   // the lean variant (one rank, no fold, ...) exists
-// lean: the caller has checked what the lean variant fixes (evp_host_resident.cpp, resident2_lean)
+// lean: 0 the general kernel; 1 the caller has checked what the lean variant fixes (evp_host_resident.cpp, launch_resident2);
+// 2 the same on the rim-wave schedule (RIMU), R.perm / R.uperm / R.nact from rim_plan.h
 void evp_launch_resident2(const EvpArgs &A, const EvpResident2 &R, int max_ni, int max_nj, int logw,
-                          bool strict, int cap, bool lean, hipStream_t st);
+                          bool strict, int cap, int lean, hipStream_t st);
 
 // Several (2 .. 4) subcycles per pass over a device-private strip-major layout (evp_march.hip, evp_host_march.cpp)
 #ifndef EVP_MARCH_PAD          // (a build-time A/B: -DEVP_MARCH_PAD=3 makes three the most subcycles per pass, strips of 58)

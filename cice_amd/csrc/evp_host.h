@@ -69,6 +69,7 @@ enum Field {
 };
 
 #define EVP_RES2_COOP_DEFAULT 0      // rim T-cells by corners in the resident B-grid kernel: the product's choice where it is possible
+#define EVP_RES2_RIMU_DEFAULT 1      // lean resident B-grid kernel: edge U-cells in the rim wave, one barrier per subcycle (rim_plan.h), where the tables allow it
 
 // Owner of a set of device allocations by registration: whatever alloc / alloc_fine / upload hand out is released by free_all (or,
 // for a buffer that is replaced on its own, free_one).  A pointer INTO somebody else's allocation is never registered: free_one
@@ -286,6 +287,12 @@ struct State {
     std::vector<char> res2_always_h;
     int res2_coop = -1;            // rim T-cells by corners (evp_resident2.hip COOP): -1 undecided, 0 off, 1 on
     bool res2_coop_ok = false;     // ... possible for the current tables (every tile's rim list fits 64 quads)
+    // rim-wave schedule of the lean variant (evp_resident2.hip RIMU, rim_plan.h): its lane tables, whether every tile satisfies
+    // the rules (else the launch takes the other lean schedule), what the last launch took
+    uint8_t *res2_perm_rim = nullptr, *res2_uperm = nullptr, *res2_nact_rim = nullptr;
+    bool res2_rimu_ok = false;
+    int res2_rimu = 0;
+    std::vector<uint8_t> res2_pubimg_h;                   // per cell: its record is polled by another tile or it has a ghost image
     int *res2_cuload = nullptr;                           // per-CU record of a launch (EvpResident2::cuload)
     unsigned long long *res2_prof = nullptr;              // phase stamps (CICE_EVP_HIP_RES_PROF=1)
     std::vector<uint8_t> res2_cls_h;                      // per tile and cell position: 0 not computed, 1 reads no ring velocity, 2 does

@@ -1,6 +1,7 @@
 // Host side of the on-chip resident kernel (evp_resident2.hip): ring tables, residency checks,
 // launches, error word, and the choices made at the first upload.
 #include "evp_host.h"
+#include "rim_plan.h"
 
 namespace evp_host {
 
@@ -63,6 +64,7 @@ int resident2_setup(int logw)
     DevicePool &M = S.mem;       // the tables of the previous tile shape
     M.free_one(S.res2_ring); M.free_one(S.res2_cnt); M.free_one(S.res2_pub); M.free_one(S.res2_perm); M.free_one(S.res2_late);
     M.free_one(S.res2_nact); M.free_one(S.res2_nlate); M.free_one(S.res2_live); M.free_one(S.res2_celltile);
+    M.free_one(S.res2_perm_rim); M.free_one(S.res2_uperm); M.free_one(S.res2_nact_rim);
     S.res2_nlive = 0;
     S.res2_cls_h.clear();
     S.res2_order_stale = true;
@@ -209,6 +211,12 @@ int resident2_setup(int logw)
     if (permuted) {
         if (S.mem.alloc(S.res2_perm, (size_t)ntiles * 256) || S.mem.alloc(S.res2_late, (size_t)ntiles) ||
             S.mem.alloc(S.res2_nact, (size_t)ntiles) || S.mem.alloc(S.res2_nlate, (size_t)ntiles)) return -1;
+        if (S.mem.alloc(S.res2_perm_rim, (size_t)ntiles * 256) || S.mem.alloc(S.res2_uperm, (size_t)ntiles * 256) ||
+            S.mem.alloc(S.res2_nact_rim, (size_t)ntiles)) return -1;
+        // the U-cells that write a record every subcycle: polled by another tile, or the source of a ghost image
+        S.res2_pubimg_h = pub;
+        for (size_t k = 0; k < S.plan.local_dst.size(); ++k)
+            if (S.plan.local_src[k] >= 0 && !tfold_image(k)) S.res2_pubimg_h[(size_t)S.plan.local_src[k]] = 1;
         if (!S.res2_cuload) {
             if (S.mem.alloc(S.res2_cuload, 2048 * 8)) return -1;
             HIPC(hipMemset(S.res2_cuload, 0, 2048 * 8 * sizeof(int)));
@@ -290,6 +298,10 @@ int resident2_order()
     std::vector<uint8_t> perm(permuted ? (size_t)ntiles * 256 : 0), late(permuted ? (size_t)ntiles : 0),
                          nact(permuted ? (size_t)ntiles : 0), nlt(permuted ? (size_t)ntiles : 0);
     bool coop_ok = permuted;
+    // the rim-wave schedule's tables (rim_plan.h): one block per rank only -- where the lean variant runs
+    const bool rim = permuted && S.d.nblocks == 1;
+    std::vector<uint8_t> perm_rim(rim ? (size_t)ntiles * 256 : 0), uperm(rim ? (size_t)ntiles * 256 : 0), nact_rim(rim ? (size_t)ntiles : 0);
+    bool rimu_ok = rim;
     for (int t = 0; t < ntiles; ++t) {
         const int b = t / (gx * gy), bx = (t % (gx * gy)) % gx, by = (t % (gx * gy)) / gx;
         const int i0 = S.ilo[b] + bx * (W - 1), j0 = S.jlo[b] + by * (H - 1);
@@ -320,6 +332,24 @@ int resident2_order()
             // pass through the stress update costs the same for 4 active lanes as for 64)
             nlt[t] = (uint8_t)std::min(n, 64);
             if (nlate > 64) coop_ok = false;
+            if (rim) {
+                uint8_t icep[256], uown[256], upub[256];
+                for (int pos = 0; pos < 256; ++pos) {
+                    const int i = i0 + (pos & (W - 1)), j = j0 + pos / W;
+                    icep[pos] = ice(pos);
+                    uown[pos] = (pos & (W - 1)) < W - 1 && pos / W < H - 1 && i <= S.ihi[b] && j <= S.jhi[b];
+                    upub[pos] = uown[pos] && S.res2_pubimg_h[b * S.plane + (size_t)(j - 1) * nx + (i - 1)];
+                }
+                rim_plan::Tile rt;
+                rim_plan::tile(cl, icep, uown, upub, rt);
+                std::copy(rt.perm, rt.perm + 256, &perm_rim[(size_t)t * 256]);
+                std::copy(rt.uperm, rt.uperm + 256, &uperm[(size_t)t * 256]);
+                nact_rim[t] = (uint8_t)rt.nact;
+                if (!rt.ok || late[t] > 1) rimu_ok = false;
+                // (the launch order weighs a tile by the chunks it keeps busy under either lean schedule: gx1 with ice everywhere has ten
+                // tiles that take one chunk more on the rim-wave schedule, profiles/r14_resident_rim_u.txt)
+                waves = std::max(waves, rt.nact);
+            }
         } else {
             int wave_on[4] = {0, 0, 0, 0};
             for (int pos = 0; pos < 256; ++pos)
@@ -344,6 +374,12 @@ int resident2_order()
         HIPC(hipMemcpyAsync(S.res2_nact, nact.data(), nact.size(), hipMemcpyHostToDevice, S.stream));
         HIPC(hipMemcpyAsync(S.res2_nlate, nlt.data(), nlt.size(), hipMemcpyHostToDevice, S.stream));
     }
+    if (rim) {
+        HIPC(hipMemcpyAsync(S.res2_perm_rim, perm_rim.data(), perm_rim.size(), hipMemcpyHostToDevice, S.stream));
+        HIPC(hipMemcpyAsync(S.res2_uperm, uperm.data(), uperm.size(), hipMemcpyHostToDevice, S.stream));
+        HIPC(hipMemcpyAsync(S.res2_nact_rim, nact_rim.data(), nact_rim.size(), hipMemcpyHostToDevice, S.stream));
+    }
+    S.res2_rimu_ok = rimu_ok;
     S.res2_coop_ok = coop_ok;
     const bool off = env_test("CICE_EVP_HIP_RES_ORDER") && !std::atoi(env_test("CICE_EVP_HIP_RES_ORDER"));
     std::vector<int> order((size_t)ntiles, 0);
@@ -460,7 +496,14 @@ int launch_resident2(int ndte, int cur0, bool dry)
                       R.nblocks == 1 && !R.seam && !R.tfold && !R.img3 && !R.rimg && !R.rraw && !R.nlate &&
                       A.p.revp == 0.0 && (A.flags & EVP_F_WATER_IS_OCN) && (A.flags & EVP_F_TBU_ZERO) &&
                       !(env_test("CICE_EVP_HIP_RES_LEAN") && !std::atoi(env_test("CICE_EVP_HIP_RES_LEAN")));
-    evp_launch_resident2(A, R, S.max_ni, S.max_nj, S.res2_logw, S.prm.strict != 0, cap_mode(), lean, S.stream);
+    // ... on the rim-wave schedule where every tile's lane tables satisfy its rules (CICE_EVP_HIP_RES_RIMU=1/0, test build: A/B)
+    const int want_rimu = env_test("CICE_EVP_HIP_RES_RIMU") ? std::atoi(env_test("CICE_EVP_HIP_RES_RIMU")) : EVP_RES2_RIMU_DEFAULT;
+    // (not with the test hooks that undo the rim-wave split or keep tiles without U-cells)
+    const bool rimu = lean && want_rimu != 0 && S.res2_rimu_ok && !(dbg2 & (32 | 256 | 512));
+    R.uperm = nullptr;
+    if (rimu) { R.perm = S.res2_perm_rim; R.uperm = S.res2_uperm; R.nact = S.res2_nact_rim; }
+    S.res2_rimu = rimu ? 1 : 0;
+    evp_launch_resident2(A, R, S.max_ni, S.max_nj, S.res2_logw, S.prm.strict != 0, cap_mode(), rimu ? 2 : lean ? 1 : 0, S.stream);
     HIPC(hipGetLastError());
     return 0;
 }
@@ -495,7 +538,8 @@ int resident_check_error()
         HIPC(hipMemset(S.res_err, 0, sizeof ev));
         S.res_mode = 0;
         return fail(-7, "resident EVP kernel: a wait gave up (%s; tile %d, subcycle %d, cell %d, tag seen %#x, wanted %#x)%s",
-                    e == 1 ? "record of this GPU" : e == 2 ? "record of another rank" : e == 3 ? "fold-row partner" : "?",
+                    e == 1 ? "record of this GPU" : e == 2 ? "record of another rank" : e == 3 ? "fold-row partner"
+                           : e == 5 ? "interior waves of the tile" : "?",
                     ev[1], ev[2], ev[3], (unsigned)ev[4], (unsigned)ev[5],
                     e == 2 ? " -- CICE_EVP_HIP_HALO_TIMEOUT_MS bounds the wait for other ranks"
                            : " -- workgroups not co-resident?");

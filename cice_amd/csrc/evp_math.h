@@ -45,6 +45,12 @@ template <> struct Math<true> {
     }
     template <int MODE = -1, bool TBU = true>
     static __device__ __forceinline__ void stepu(const EvpScalars &p, const UI &a, UO &o) { evp_strict::stepu_cell<MODE == 3, TBU>(p, a, o); }
+    // the momentum step in two parts: what reads no stress partial, and the rest (evp_cell.inc)
+    using UP = evp_strict::StepuPre;
+    template <int MODE = -1, bool TBU = true>
+    static __device__ __forceinline__ void stepu_pre(const EvpScalars &p, const UI &a, UP &w) { evp_strict::stepu_pre_cell<MODE == 3, TBU>(p, a, w); }
+    template <int MODE = -1>
+    static __device__ __forceinline__ void stepu_post(const EvpScalars &p, const UI &a, const UP &w, UO &o) { evp_strict::stepu_post_cell<MODE == 3, true>(p, a, w, o); }
     static __device__ __forceinline__ void metrics(double hte, double hte_im, double htn, double htn_jm, double dmin, SI &a)
     {
         evp_strict::metrics_cell(hte, hte_im, htn, htn_jm, dmin, a);
@@ -81,6 +87,12 @@ template <> struct Math<false> {
     }
     template <int MODE = -1, bool TBU = true>
     static __device__ __forceinline__ void stepu(const EvpScalars &p, const UI &a, UO &o) { evp_fused::stepu_cell<MODE == 3, TBU>(p, a, o); }
+    // the momentum step in two parts: what reads no stress partial, and the rest (evp_cell.inc)
+    using UP = evp_fused::StepuPre;
+    template <int MODE = -1, bool TBU = true>
+    static __device__ __forceinline__ void stepu_pre(const EvpScalars &p, const UI &a, UP &w) { evp_fused::stepu_pre_cell<MODE == 3, TBU>(p, a, w); }
+    template <int MODE = -1>
+    static __device__ __forceinline__ void stepu_post(const EvpScalars &p, const UI &a, const UP &w, UO &o) { evp_fused::stepu_post_cell<MODE == 3, true>(p, a, w, o); }
     static __device__ __forceinline__ void metrics(double hte, double hte_im, double htn, double htn_jm, double dmin, SI &a)
     {
         evp_fused::metrics_cell(hte, hte_im, htn, htn_jm, dmin, a);

@@ -29,6 +29,42 @@
 // arithmetic instead of preceding all of it.  The lane -> cell map is arbitrary here because no
 // array access of the loop is a global one; the eight stress-divergence partials travel through LDS
 // by cell position.  Same arithmetic per cell => same bits.
+//
+// RIMU (the lean variant's schedule where the lane tables allow it: rim_plan.h).  Under the schedule above every wave meets at a
+// barrier B1 between the stress update and the momentum step, because the U-cells that read a rim T-cell's partials -- the edge
+// U-cells, which are also the ones that write records -- are scattered over all four waves; the interior waves then sit at B1
+// for 45 % of a subcycle and step inside the chain's window.  Here the rim wave (chunk 0) holds L_T (the rim T-cells, and in a
+// full tile the four depth-1 corner cells) AND L_U (every U-cell that reads a partial of L_T or writes a record); every other
+// U-cell stays with its T-cell's lane in an interior wave (chunks 1-3).  By the closure of L_U no U-cell outside L_U reads a
+// T-cell of L_T, and no T-cell of L_T reads the velocity of a U-cell outside L_U.  Per subcycle k:
+//   interior wave:  stress of its T-cells -> partials to the planes -> s_waitcnt lgkmcnt(0) -> slot[chunk - 1] = k + 1 ->
+//                   spin until all three slots >= k + 1 -> momentum step of its U-cells -> s_u / s_v -> barrier B2
+//   rim wave:       ring poll -> stress of L_T -> planes -> spin on the three slots -> second part of the momentum step of L_U
+//                   -> records -> s_u / s_v -> barrier B2 -> first part of the momentum step of subcycle k + 1
+//                   (stepu_pre_cell: reads the cell's own new velocity and per-call operands only)
+// Who writes and who reads what, between which two synchronisation points (B2(k): the barrier that ends subcycle k):
+//   s_u / s_v, ring cells       written by the rim wave after its poll of subcycle k, read by L_T only (rim wave, program order;
+//                               LDS operations of one wave complete in order).  Interior T-cells read no polled ring cell.
+//   s_u / s_v, cells of L_U     written by the rim wave AFTER its slot spin of subcycle k, i.e. after every interior wave has
+//                               finished the stress update of subcycle k (its last read of them before B2(k)); read by L_T in
+//                               subcycle k + 1 (same wave) and by interior T-cells after B2(k).
+//   s_u / s_v, other U-cells    written by their interior wave after ITS slot spin of subcycle k: every interior wave's stress
+//                               reads of subcycle k are complete, and the rim wave never reads them; read after B2(k).
+//   planes, interior T-cells    (all eight: the NE partials str[0] / str[4] of a T-cell travel too, its own U-cell may sit on
+//                               another lane) written before the wave's slot says k + 1, read by interior U-cells and by L_U
+//                               only after the reader has seen all three slots >= k + 1; written again only after B2(k), which
+//                               no reader passes before its reads.  A position without an ice T-cell is never written: the
+//                               planes are zeroed once, before the loop.
+//   planes, cells of L_T        written and read by the rim wave only, in program order.
+//   slots                       slot[q] = k + 1 is written once per subcycle by lane 0 of interior wave q after its planes are
+//                               complete, and read (volatile, workgroup scope) by every wave; it only grows, and subcycle k + 1's
+//                               value is written after B2(k), when nobody spins on k + 1 any more.  Zeroed before the loop.
+// One workgroup barrier per subcycle remains.  Every spin is bounded; a wave whose wait gives up sets s_bad and goes straight to
+// B2, after which every wave tests s_bad and the workgroup leaves together (err[0] == 5: the slot spin).  Two record buffers
+// still suffice: publishing and polling are as independent of the ice masks as before (every cell another tile mirrors is in L_U
+// and stores its record every subcycle, every ring entry with a producer is polled every subcycle), and a tile's records of
+// subcycle k + 1 are stored by the wave that polled all of its ring entries of subcycle k before, in program order -- a tile
+// cannot be more than one subcycle ahead of any tile that still has to read its records.
 // =====================================================================
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -137,18 +173,21 @@ constexpr int QP_X1 = 0xB1, QP_X2 = 0x4E, QP_X3 = 0x1B;      // quad_perm [1,0,3
 // the other cases is in the subcycle loop, which runs two subcycles per trip (one per record buffer), the record loads and stores
 // addressed as scalar buffer base + lane offset.  Same operations in the same order => same bits
 // (profiles/r07_resident_lean_*.txt, tools/resident_isa_mix.py).
-template <bool STRICT, int CAP, int LOGW, bool REMOTE, bool COOP = false, bool LEAN = false>
+// RIMU: the lean loop on the rim-wave schedule of the header (profiles/r14_resident_rim_u.txt); where a tile's lane tables cannot
+// satisfy rim_plan.h's rules the launch takes the lean loop as it was (per launch, evp_host_resident.cpp).
+template <bool STRICT, int CAP, int LOGW, bool REMOTE, bool COOP = false, bool LEAN = false, bool RIMU = false>
 __global__ __launch_bounds__(64 * RTY, REMOTE ? 2 : 3) void evp_resident2_tile(EvpArgs A, EvpResident2 R)
 {
     static_assert(!COOP || (STRICT && CAP == 3 && LOGW == 4), "COOP: 16 x 16 tiles, strict build, default scalars");
     static_assert(!LEAN || (!REMOTE && !COOP && LOGW == 4), "LEAN: one rank, 16 x 16 tiles, one thread per rim cell");
+    static_assert(!RIMU || LEAN, "RIMU: a schedule of the lean loop");
     using MM = Math<STRICT>;
     constexpr int W = 1 << LOGW;
     constexpr int H = 256 / W;
     constexpr int LW = W + 1;                 // LDS velocity tile: (H+1) x (W+1), origin (-1,-1)
     constexpr int NUV = ((H + 1) * LW + 7) & ~7;
     constexpr bool PERM = (LOGW == 4);        // rim wave / interior waves (see the header)
-    constexpr int NSTR = PERM ? 6 : 4;        // planes of stress-divergence partials that travel through LDS
+    constexpr int NSTR = RIMU ? 8 : PERM ? 6 : 4;   // planes of stress-divergence partials that travel through LDS
     constexpr int SW = PERM ? W + 1 : W;      // row stride of a plane (PERM: odd, a column of cells is not one bank)
     constexpr int SP = SW * H;                // plane size
     // LDS (dynamic): s_str[NSTR][SP] | s_tc[4][256] | s_u[NUV] | s_v[NUV] | s_uc[nu][256]
@@ -163,6 +202,7 @@ __global__ __launch_bounds__(64 * RTY, REMOTE ? 2 : 3) void evp_resident2_tile(E
     __shared__ int s_bad;
 
     __shared__ int s_chunk[4], s_simd[4], s_cu;
+    __shared__ int s_slot[4];                 // RIMU: [0..2] the subcycles whose stress the interior waves have finished
 
     const int tx = threadIdx.x, ty = threadIdx.y;
     const int t = ty * 64 + tx;
@@ -273,6 +313,13 @@ __global__ __launch_bounds__(64 * RTY, REMOTE ? 2 : 3) void evp_resident2_tile(E
     const int cb = bz * (int)A.plane;             // first cell of the block in every (nx, ny, nblocks) array
     const int c = cb + (j - 1) * nx + (i - 1);
     const int li = (trow + 1) * LW + (tcol + 1);   // this cell in the LDS velocity tile
+    // RIMU: the U-cell a thread holds need not sit at its T-cell's position (R.uperm, rim_plan.h; 255: none -- never an owned cell)
+    const int upos = RIMU ? (int)R.uperm[tile * 256 + tq] : pos;
+    const int ucol = upos & (W - 1), urow = upos >> LOGW;
+    const int ui = RIMU ? i0 + ucol : i, uj = RIMU ? j0 + urow : j;
+    const int cu = RIMU ? cb + (uj - 1) * nx + (ui - 1) : c;
+    const int uli = RIMU ? (urow + 1) * LW + (ucol + 1) : li;
+    const int usp = RIMU ? urow * SW + ucol : sp;
     const unsigned flags = A.flags;
     const bool water = !LEAN && !(flags & EVP_F_WATER_IS_OCN);     // (LEAN: launched only with both flags set)
     const bool tbu = !LEAN && !(flags & EVP_F_TBU_ZERO);
@@ -285,15 +332,17 @@ __global__ __launch_bounds__(64 * RTY, REMOTE ? 2 : 3) void evp_resident2_tile(E
     unsigned m = 0;
     if (inT) m = A.mask[c];
     const bool actT = inT && (m & 1u);
-    const bool isU = (tcol < W - 1) && (trow < H - 1) && (i <= r.y) && (j <= r.w) && (m & 2u);
+    const bool ownU = (ucol < W - 1) && (urow < H - 1) && (ui <= r.y) && (uj <= r.w);
+    unsigned mU = m;
+    if (RIMU) mU = ownU ? A.mask[cu] : 0u;
+    const bool isU = ownU && (mU & 2u);
     const bool own = (tcol < W - 1 || i == r.y + 1) && (trow < H - 1 || j == r.w + 1);
     // Every U-cell another tile's ring mirrors publishes a record every subcycle, ice or not, and
     // every ring entry that has a producer is polled every subcycle: a tile then cannot run more
     // than one subcycle ahead of ANY tile that still has to read its records (the two-buffer
     // record scheme depends on that; making either side depend on the ice mask would let a tile
     // next to open water run ahead of its reader and overwrite a record that was never read).
-    const bool ownU = (tcol < W - 1) && (trow < H - 1) && (i <= r.y) && (j <= r.w);
-    const bool pub = ownU && (R.pubmap[c] != 0);
+    const bool pub = ownU && (R.pubmap[cu] != 0);
     const int par0 = R.par0;                      // record buffer of subcycle index 0 in this launch
     // COOP: the first nlate entries of the tile's permuted cell list are its rim T-cells with ice (resident2_order); the
     // thread that holds such a cell leaves its stress update to the quad g = its list index, lanes 4g .. 4g+3 of the workgroup
@@ -368,17 +417,17 @@ __global__ __launch_bounds__(64 * RTY, REMOTE ? 2 : 3) void evp_resident2_tile(E
         s_tc[3 * 256 + t] = a.dyhx;
     }
     if (isU) {
-        s_uc[0 * 256 + t] = A.vrelfac[c];
-        s_uc[1 * 256 + t] = A.uocn[c];
-        s_uc[2 * 256 + t] = A.vocn[c];
-        s_uc[3 * 256 + t] = A.forcex[c];
-        s_uc[4 * 256 + t] = A.forcey[c];
-        s_uc[5 * 256 + t] = A.umassdti[c];
-        s_uc[6 * 256 + t] = A.fm[c];
-        s_uc[7 * 256 + t] = A.uarear[c];
+        s_uc[0 * 256 + t] = A.vrelfac[cu];
+        s_uc[1 * 256 + t] = A.uocn[cu];
+        s_uc[2 * 256 + t] = A.vocn[cu];
+        s_uc[3 * 256 + t] = A.forcex[cu];
+        s_uc[4 * 256 + t] = A.forcey[cu];
+        s_uc[5 * 256 + t] = A.umassdti[cu];
+        s_uc[6 * 256 + t] = A.fm[cu];
+        s_uc[7 * 256 + t] = A.uarear[cu];
         int row = 8;
-        if (water) { s_uc[row * 256 + t] = A.waterx[c]; s_uc[(row + 1) * 256 + t] = A.watery[c]; row += 2; }
-        if (tbu) s_uc[row * 256 + t] = A.TbU[c];
+        if (water) { s_uc[row * 256 + t] = A.waterx[cu]; s_uc[(row + 1) * 256 + t] = A.watery[cu]; row += 2; }
+        if (tbu) s_uc[row * 256 + t] = A.TbU[cu];
     }
     // the velocity tile incl. its ring starts from the input arrays (ghost cells are valid on entry)
     {
@@ -411,10 +460,10 @@ __global__ __launch_bounds__(64 * RTY, REMOTE ? 2 : 3) void evp_resident2_tile(E
         // per-cell table, at most three images
         if (ownU) { img0 = R.img3[3 * c]; img1 = R.img3[3 * c + 1]; img2 = R.img3[3 * c + 2]; }
     } else
-    if (ownU && (flags & EVP_F_PUSH) && (i == r.x || i == r.y || j == r.z || j == r.w)) {
-        const int slots[4] = {(i == r.x) ? (j - r.z) : -1, (i == r.y) ? A.push_nj + (j - r.z) : -1,
-                              (j == r.z) ? 2 * A.push_nj + (i - r.x) : -1,
-                              (j == r.w) ? 2 * A.push_nj + A.push_ni + (i - r.x) : -1};
+    if (ownU && (flags & EVP_F_PUSH) && (ui == r.x || ui == r.y || uj == r.z || uj == r.w)) {
+        const int slots[4] = {(ui == r.x) ? (uj - r.z) : -1, (ui == r.y) ? A.push_nj + (uj - r.z) : -1,
+                              (uj == r.z) ? 2 * A.push_nj + (ui - r.x) : -1,
+                              (uj == r.w) ? 2 * A.push_nj + A.push_ni + (ui - r.x) : -1};
 #pragma unroll
         for (int e = 0; e < 4; ++e) {
             if (slots[e] < 0) continue;
@@ -506,6 +555,11 @@ __global__ __launch_bounds__(64 * RTY, REMOTE ? 2 : 3) void evp_resident2_tile(E
         }
     };
     if (t == 0) s_bad = 0;
+    if (RIMU) {
+        // a plane entry is written by the thread of an ice T-cell only: the others stay zero for the whole call
+        for (int q = t; q < NSTR * SP; q += 256) s_str[q] = 0.0;
+        if (t < 4) s_slot[t] = 0;
+    }
     __syncthreads();
 
     // bound of a wait on a record of this GPU: spin count (workgroups not co-resident -> fail fast) on
@@ -521,13 +575,13 @@ __global__ __launch_bounds__(64 * RTY, REMOTE ? 2 : 3) void evp_resident2_tile(E
                ((spins & 255u) == 0 && __hip_atomic_load(R.err, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) != 0);
     };
     double u_own = 0.0, v_own = 0.0;
-    if (ownU) { u_own = s_u[li]; v_own = s_v[li]; }
+    if (ownU) { u_own = s_u[uli]; v_own = s_v[uli]; }
     // initial records (subcycle tag 0) so that the neighbours' first ring refresh finds them
     {
         const unsigned tag = R.tag_base;
         v4u *r0 = (v4u *)R.rec[par0 & 1];
         if (rpub) publish_remote(par0 & 1, u_own, v_own, tag);
-        if (pub) st_rec2(r0 + 2 * (size_t)c, pack_rec(u_own, tag), pack_rec(v_own, tag));
+        if (pub) st_rec2(r0 + 2 * (size_t)cu, pack_rec(u_own, tag), pack_rec(v_own, tag));
         if (ownU) {
             if (img0 >= 0) { const double sg = (img0 & 1) ? -1.0 : 1.0; st_rec2(r0 + 2 * (size_t)(img0 >> 1), pack_rec(sg * u_own, tag), pack_rec(sg * v_own, tag)); }
             if (img1 >= 0) { const double sg = (img1 & 1) ? -1.0 : 1.0; st_rec2(r0 + 2 * (size_t)(img1 >> 1), pack_rec(sg * u_own, tag), pack_rec(sg * v_own, tag)); }
@@ -558,7 +612,7 @@ __global__ __launch_bounds__(64 * RTY, REMOTE ? 2 : 3) void evp_resident2_tile(E
     // 4.90 us per subcycle (gpurun_out/r4i): twice the poll traffic costs more than the earlier sighting saves.
     // LEAN: record addresses are a scalar base (the buffer of the subcycle's parity) plus a 32-bit lane offset fixed for the call
     const unsigned ring_off = 32u * (unsigned)(ring_cp >= 0 ? ring_cp : 0);
-    const unsigned own_off = 32u * (unsigned)c;
+    const unsigned own_off = 32u * (unsigned)cu;
     const unsigned img_off0 = 32u * (unsigned)(img0 >> 1), img_off1 = 32u * (unsigned)(img1 >> 1), img_off2 = 32u * (unsigned)(img2 >> 1);
     const double img_sg0 = (img0 & 1) ? -1.0 : 1.0, img_sg1 = (img1 & 1) ? -1.0 : 1.0, img_sg2 = (img2 & 1) ? -1.0 : 1.0;
     // one subcycle: reads the records of buffer rd, writes those of buffer wr; false: a wait gave up, the workgroup leaves
@@ -801,6 +855,164 @@ __global__ __launch_bounds__(64 * RTY, REMOTE ? 2 : 3) void evp_resident2_tile(E
         EVP_STAMP(pacc4)
         return true;
     };
+    // RIMU: the same subcycle on the schedule argued in the header.  rimw: this wave took chunk 0 (ring poll, L_T, L_U)
+    const bool rimw = RIMU && __builtin_amdgcn_readfirstlane(tq >> 6) == 0;      // (wave-uniform, and known to be)
+    typename MM::UP upre;                         // rim wave: the part of the next momentum step that reads no stress partial
+    auto ucell_operands = [&](typename MM::UI &q) {
+        q.uold = u_own; q.vold = v_own;
+        q.vrelfac = s_uc[0 * 256 + t]; q.uocn = s_uc[1 * 256 + t]; q.vocn = s_uc[2 * 256 + t];
+        q.forcex = s_uc[3 * 256 + t]; q.forcey = s_uc[4 * 256 + t]; q.Umassdti = s_uc[5 * 256 + t];
+        q.fm = s_uc[6 * 256 + t]; q.uarear = s_uc[7 * 256 + t];
+        q.waterx = q.uocn; q.watery = q.vocn;     // (LEAN: water == ocean current, TbU == 0, revp == 0)
+        q.TbU = 0.0; q.uvel_init = 0.0; q.vvel_init = 0.0;
+    };
+    if constexpr (RIMU) if (rimw && isU) {
+        typename MM::UI q;
+        ucell_operands(q);
+        MM::template stepu_pre<CAP, false>(A.p, q, upre);
+    }
+    auto subcycle_rim = [&](const int k, const v4u *rd, v4u *wr) -> bool {
+        const unsigned want = R.tag_base + (unsigned)k;       // tag of the velocities subcycle k reads
+        const int done = k + 1;                               // what an interior wave's slot says once its stress of subcycle k is in the planes
+        if ((RES_DBG(R) & 8) && (tile & 3) == 1) {            // robustness test: every fourth tile lags by ~10 us per subcycle
+            const unsigned long long t0 = wall_clock64();
+            while (wall_clock64() - t0 < 1000ull) __builtin_amdgcn_s_sleep(8);
+        }
+        int bad = 0;
+        if (rimw) {
+            bool gave = false;
+            if (ring_cp >= 0 && !(RES_DBG(R) & 2)) {
+                v4u ra, rb;
+                unsigned spins = 0;
+                for (;;) {
+                    ld_rec2_s(rd, ring_off, ra, rb);
+                    if ((ra.x == want && ra.w == want && rb.x == want && rb.w == want) || (RES_DBG(R) & 1)) break;
+                    if (gave_up(++spins, t_wait0)) {
+                        give_up_note(1, k, ring_cp, ra.x, want);
+                        __hip_atomic_store(&s_bad, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+                        gave = true;
+                        break;
+                    }
+                    if (RES_DBG(R) & 4) __builtin_amdgcn_s_sleep(8); else __builtin_amdgcn_s_sleep(1);
+                }
+                s_u[ring_li] = unpack_rec(ra);
+                s_v[ring_li] = unpack_rec(rb);
+            }
+            // ring cells are written and read by this wave only: LDS operations of one wave complete in order
+            __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+            __builtin_amdgcn_wave_barrier();
+            __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+            bad = __builtin_amdgcn_ballot_w64(gave) != 0;      // (no LDS round trip on the chain)
+        }
+        // the rim wave looks at the slots once before its stress update -- the interior waves are usually done by the time the
+        // neighbours' records have arrived -- so that the look's LDS round trip travels with the stress update's own loads
+        int slots_seen = 0;
+        if (rimw && !bad) {
+            const int a0 = __hip_atomic_load(&s_slot[0], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+            const int a1 = __hip_atomic_load(&s_slot[1], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+            const int a2 = __hip_atomic_load(&s_slot[2], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+            slots_seen = __builtin_amdgcn_readfirstlane(min(a0, min(a1, a2))) >= done;
+            __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
+        }
+        EVP_STAMP(pacc0)
+        if (!bad) {      // (a wave whose wait gave up goes straight to the barrier)
+            if (actT) {
+                double str[8];
+                a.u_ij = s_u[li]; a.v_ij = s_v[li];
+                a.u_im = s_u[li - 1]; a.v_im = s_v[li - 1];
+                a.u_jm = s_u[li - LW]; a.v_jm = s_v[li - LW];
+                a.u_mm = s_u[li - LW - 1]; a.v_mm = s_v[li - LW - 1];
+                a.strength = s_tc[0 * 256 + t]; a.DminTarea = s_tc[1 * 256 + t];
+                a.dxhy = s_tc[2 * 256 + t]; a.dyhx = s_tc[3 * 256 + t];
+                MM::template stress<CAP>(A.p, a, s, str);
+                s_str[0 * SP + sp] = str[2];
+                s_str[1 * SP + sp] = str[5];
+                s_str[2 * SP + sp] = str[3];
+                s_str[3 * SP + sp] = str[7];
+                s_str[4 * SP + sp] = str[1];
+                s_str[5 * SP + sp] = str[6];
+                s_str[6 * SP + sp] = str[0];
+                s_str[7 * SP + sp] = str[4];
+            }
+            EVP_STAMP(pacc1)
+            // the planes of this wave's T-cells are complete (s_waitcnt lgkmcnt(0)) before its slot says so; the rim wave's
+            // are read by the rim wave only
+            __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
+            if (!rimw && (t & 63) == 0) __hip_atomic_store(&s_slot[(tq >> 6) - 1], done, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+            if (!slots_seen) {
+                unsigned spins = 0;
+                for (;;) {
+                    const int a0 = __hip_atomic_load(&s_slot[0], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+                    const int a1 = __hip_atomic_load(&s_slot[1], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+                    const int a2 = __hip_atomic_load(&s_slot[2], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+                    const int lo = __builtin_amdgcn_readfirstlane(min(a0, min(a1, a2)));
+                    if (lo >= done) break;
+                    if (++spins > R.spin_limit) {
+                        give_up_note(5, k, -1, (unsigned)lo, (unsigned)done);
+                        __hip_atomic_store(&s_bad, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+                    }
+                    // (another wave of the tile gave up: nobody steps, everybody meets at the barrier)
+                    if ((spins & 255u) == 0 || spins > R.spin_limit)
+                        bad = __builtin_amdgcn_readfirstlane(__hip_atomic_load(&s_bad, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP));
+                    if (bad) break;
+                    __builtin_amdgcn_s_sleep(1);
+                }
+            }
+            __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
+            EVP_STAMP(pacc2)
+        }
+        if (!bad) {
+            double fin0 = 0.0, fin1 = 0.0, fin2 = 0.0, fin3 = 0.0;
+            if (isU) {
+                typename MM::UI q;
+                typename MM::UO o;
+                ucell_operands(q);
+                q.sx0 = s_str[6 * SP + usp]; q.sx1 = s_str[4 * SP + usp + 1];
+                q.sx2 = s_str[0 * SP + usp + SW]; q.sx3 = s_str[2 * SP + usp + SW + 1];
+                q.sy0 = s_str[7 * SP + usp]; q.sy1 = s_str[1 * SP + usp + SW];
+                q.sy2 = s_str[5 * SP + usp + 1]; q.sy3 = s_str[3 * SP + usp + SW + 1];
+                if (!rimw) MM::template stepu_pre<CAP, false>(A.p, q, upre);
+                MM::template stepu_post<CAP>(A.p, q, upre, o);
+                u_own = o.u; v_own = o.v;
+                fin0 = o.strintx; fin1 = o.strinty; fin2 = o.taubx; fin3 = o.tauby;
+            }
+            if (ownU) {      // the records first: the neighbours wait for them (every cell with a record to write is in L_U: rim_plan.h)
+                const unsigned tag = want + 1u;
+                if (pub) st_rec2_s(wr, own_off, pack_rec(u_own, tag), pack_rec(v_own, tag));
+                if (img0 >= 0) st_rec2_s(wr, img_off0, pack_rec(img_sg0 * u_own, tag), pack_rec(img_sg0 * v_own, tag));
+                if (img1 >= 0) st_rec2_s(wr, img_off1, pack_rec(img_sg1 * u_own, tag), pack_rec(img_sg1 * v_own, tag));
+                if (img2 >= 0) st_rec2_s(wr, img_off2, pack_rec(img_sg2 * u_own, tag), pack_rec(img_sg2 * v_own, tag));
+            }
+            if (isU) {
+                s_u[uli] = u_own; s_v[uli] = v_own;       // read by the next stress phase, after the barrier below
+                if (k == R.ndte - 1 && !R.dry) {
+                    R.tab[24][cu] = fin0; R.tab[25][cu] = fin1;
+                    R.tab[26][cu] = fin2; R.tab[27][cu] = fin3;
+                }
+            }
+            EVP_STAMP(pacc3)
+        }
+        __syncthreads();      // the one barrier: the tile's new velocities are in LDS, every read of the planes is done
+        EVP_STAMP(pacc4)
+        if (s_bad) return false;   // uniform: every thread of the workgroup leaves together
+        // the rim wave's first part of the NEXT momentum step: after the barrier, where it runs while the neighbours' records are
+        // still on their way (before the barrier it sat on the chain and measured slower: profiles/r14_resident_rim_u.txt, section 4)
+        if (rimw && isU) {
+            typename MM::UI q;
+            ucell_operands(q);
+            MM::template stepu_pre<CAP, false>(A.p, q, upre);
+        }
+        return true;
+    };
+    if constexpr (RIMU) {
+        const v4u *const rec_a = (const v4u *)R.rec[par0 & 1];
+        v4u *const rec_b = (v4u *)R.rec[(par0 & 1) ^ 1];
+        for (int k = 0; k < R.ndte; k += 2) {
+            if (!subcycle_rim(k, rec_a, rec_b)) return;
+            if (k + 1 == R.ndte) break;
+            if (!subcycle_rim(k + 1, rec_b, (v4u *)rec_a)) return;
+        }
+    } else
     if (LEAN) {
         // two subcycles per trip, one per record buffer: the buffers' addresses are fixed in each
         const v4u *const rec_a = (const v4u *)R.rec[par0 & 1];
@@ -851,7 +1063,7 @@ __global__ __launch_bounds__(64 * RTY, REMOTE ? 2 : 3) void evp_resident2_tile(E
 #pragma unroll
             for (int b = 0; b < 2; ++b) {
                 double *uu = R.u[b], *vv = R.v[b];
-                uu[c] = u_own; vv[c] = v_own;
+                uu[cu] = u_own; vv[cu] = v_own;
                 if (img0 >= 0) { const double sg = (img0 & 1) ? -1.0 : 1.0; uu[img0 >> 1] = sg * u_own; vv[img0 >> 1] = sg * v_own; }
                 if (img1 >= 0) { const double sg = (img1 & 1) ? -1.0 : 1.0; uu[img1 >> 1] = sg * u_own; vv[img1 >> 1] = sg * v_own; }
                 if (img2 >= 0) { const double sg = (img2 & 1) ? -1.0 : 1.0; uu[img2 >> 1] = sg * u_own; vv[img2 >> 1] = sg * v_own; }
@@ -860,12 +1072,12 @@ __global__ __launch_bounds__(64 * RTY, REMOTE ? 2 : 3) void evp_resident2_tile(E
     }
 }
 
-size_t lds_bytes(unsigned flags, int logw, bool coop = false)
+size_t lds_bytes(unsigned flags, int logw, bool coop = false, bool rimu = false)
 {
     const int W = 1 << logw, H = 256 / W;
     const int nuv = ((H + 1) * (W + 1) + 7) & ~7;
     const int nu = 8 + ((flags & EVP_F_WATER_IS_OCN) ? 0 : 2) + ((flags & EVP_F_TBU_ZERO) ? 0 : 1);
-    const size_t nstr = logw == 4 ? 6 * (size_t)(W + 1) * H : 4 * (size_t)256;   // PERM planes: row stride W + 1
+    const size_t nstr = logw == 4 ? (rimu ? 8 : 6) * (size_t)(W + 1) * H : 4 * (size_t)256;   // PERM planes: row stride W + 1 (RIMU: eight of them)
     return sizeof(double) * (nstr + (size_t)256 * (4 + nu) + 2 * (size_t)nuv + (coop ? 12 * (size_t)64 : 0));
 }
 
@@ -940,14 +1152,19 @@ int evp_resident2_max_blocks_per_cu(bool strict, int cap, unsigned flags, int lo
         int nb = 0;
         const hipError_t e = strict ? hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, evp_resident2_tile<true, 3, 4, false, false, true>, 64 * RTY, lds)
                                     : hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, evp_resident2_tile<false, 3, 4, false, false, true>, 64 * RTY, lds);
-        return e == hipSuccess ? std::min(nb, occ<4, false>(strict, cap, lds)) : 0;
+        // (RIMU: two more planes, 46720 B of LDS per workgroup with the operands the lean launch has)
+        int nr = 0;
+        const size_t lds_r = lds_bytes(flags | EVP_F_WATER_IS_OCN | EVP_F_TBU_ZERO, 4, false, true);
+        const hipError_t er = strict ? hipOccupancyMaxActiveBlocksPerMultiprocessor(&nr, evp_resident2_tile<true, 3, 4, false, false, true, true>, 64 * RTY, lds_r)
+                                     : hipOccupancyMaxActiveBlocksPerMultiprocessor(&nr, evp_resident2_tile<false, 3, 4, false, false, true, true>, 64 * RTY, lds_r);
+        return e == hipSuccess && er == hipSuccess ? std::min(std::min(nb, nr), occ<4, false>(strict, cap, lds)) : 0;
     }
     if (remote) return logw == 4 ? occ<4, true>(strict, cap, lds) : logw == 5 ? occ<5, true>(strict, cap, lds) : occ<6, true>(strict, cap, lds);
     return logw == 4 ? occ<4, false>(strict, cap, lds) : logw == 5 ? occ<5, false>(strict, cap, lds) : occ<6, false>(strict, cap, lds);
 }
 
 void evp_launch_resident2(const EvpArgs &A0, const EvpResident2 &R, int max_ni, int max_nj, int logw,
-                          bool strict, int cap, bool lean, hipStream_t st)
+                          bool strict, int cap, int lean, hipStream_t st)
 {
     EvpArgs A = A0;
     evp_resident_geometry(max_ni, max_nj, logw, &A.gx, &A.gy);
@@ -960,6 +1177,13 @@ void evp_launch_resident2(const EvpArgs &A0, const EvpResident2 &R, int max_ni, 
         return;
     }
 #endif
+    if (lean == 2 && evp_resident2_lean_built(strict, cap, logw, remote)) {      // RIMU: R.perm / R.uperm / R.nact are rim_plan's
+        dim3 grid(R.nlaunch > 0 ? R.nlaunch : A.ntiles), block(64, RTY);
+        const size_t lds = lds_bytes(A.flags, 4, false, true);
+        if (strict) hipLaunchKernelGGL((evp_resident2_tile<true, 3, 4, false, false, true, true>), grid, block, lds, st, A, R);
+        else hipLaunchKernelGGL((evp_resident2_tile<false, 3, 4, false, false, true, true>), grid, block, lds, st, A, R);
+        return;
+    }
     if (lean && evp_resident2_lean_built(strict, cap, logw, remote)) {
         dim3 grid(R.nlaunch > 0 ? R.nlaunch : A.ntiles), block(64, RTY);
         if (strict) hipLaunchKernelGGL((evp_resident2_tile<true, 3, 4, false, false, true>), grid, block, lds_bytes(A.flags, 4), st, A, R);

@@ -128,6 +128,12 @@ int cice_evp_hip_plan_build(const cice_evp_hip_dims *dims);
  * its length, then its entries; the peer lists (peers, cg_peers) as their length, then every peer member by member; cg_fold[0 .. 3];
  * the error text as its length, then its characters.  Returns the number of values; out = NULL: only counts; -1 when n is too small. */
 int cice_evp_hip_plan_dump(int32_t *out, int32_t n);
+/* Host-only: lane tables of the resident B-grid kernel's rim-wave schedule (csrc/rim_plan.h) for one block of ni x nj cells
+   with one ghost cell all round; mask: (ni + 2) x (nj + 2) bytes, bit 0 ice T-cell, bit 1 ice U-cell.  Returns the tile count
+   (all out pointers NULL: only that).  Per tile perm[256], uperm[256] (255: none), info8 = {|L_T|, |L_U|, active chunks,
+   active chunks of the ice-first packing, ok, tiles per row, tiles per column, 0}, cls[256]. */
+int cice_evp_hip_rim_plan(int32_t ni, int32_t nj, int32_t cyclic_ew, int32_t cyclic_ns, const uint8_t *mask, int32_t ntiles_max,
+                          uint8_t *perm, uint8_t *uperm, int32_t *info8, uint8_t *cls);
 int cice_evp_hip_halo_plan(int32_t *counts4, int32_t *local_dst, int32_t *local_src,
                            int32_t *local_sign, int32_t *peer_rank, int32_t *peer_nsend,
                            int32_t *peer_nrecv, int32_t *send_src, int32_t *recv_dst);

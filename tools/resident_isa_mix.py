@@ -6,8 +6,10 @@ Compiles cice_amd/csrc/evp_resident2.hip for gfx950 with the build's flags to as
 subcycle loop (the backward branch that spans the most instructions) and counts what the loop holds, per subcycle: a loop
 that carries two subcycles per trip (the lean variant: one per record-buffer parity) is halved.
 
-  python tools/resident_isa_mix.py [--general] [--asm FILE.s]
+  python tools/resident_isa_mix.py [--general | --lean] [--asm FILE.s]
      --general   the general kernel <true, 3, 4, false, false> even where the lean one exists
+     --lean      the lean variant on its first schedule (two workgroup barriers per subcycle) even where the rim-wave
+                 schedule (RIMU) exists
      --asm       count an assembly file made earlier instead of compiling
 """
 from __future__ import annotations
@@ -26,7 +28,10 @@ SRC = ROOT / "cice_amd" / "csrc" / "evp_resident2.hip"
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 GENERAL = ("_ZN12_GLOBAL__N_118evp_resident2_tileILb1ELi3ELi4ELb0ELb0ELb0EEEv7EvpArgs12EvpResident2",
            "_ZN12_GLOBAL__N_118evp_resident2_tileILb1ELi3ELi4ELb0ELb0EEEv7EvpArgs12EvpResident2")   # (before the LEAN parameter)
-LEAN = "_ZN12_GLOBAL__N_118evp_resident2_tileILb1ELi3ELi4ELb0ELb0ELb1EEEv7EvpArgs12EvpResident2"
+GENERAL = ("_ZN12_GLOBAL__N_118evp_resident2_tileILb1ELi3ELi4ELb0ELb0ELb0ELb0EEEv7EvpArgs12EvpResident2",) + GENERAL
+LEAN = ("_ZN12_GLOBAL__N_118evp_resident2_tileILb1ELi3ELi4ELb0ELb0ELb1ELb0EEEv7EvpArgs12EvpResident2",
+        "_ZN12_GLOBAL__N_118evp_resident2_tileILb1ELi3ELi4ELb0ELb0ELb1EEEv7EvpArgs12EvpResident2")          # (before the RIMU parameter)
+RIMU = "_ZN12_GLOBAL__N_118evp_resident2_tileILb1ELi3ELi4ELb0ELb0ELb1ELb1EEEv7EvpArgs12EvpResident2"
 
 
 def compile_asm(out: Path) -> None:
@@ -104,6 +109,7 @@ def classify(mn: str) -> str:
 def main() -> int:
     ap = argparse.ArgumentParser()
     ap.add_argument("--general", action="store_true")
+    ap.add_argument("--lean", action="store_true")
     ap.add_argument("--asm", default=None)
     a = ap.parse_args()
     if a.asm:
@@ -114,10 +120,11 @@ def main() -> int:
             compile_asm(out)
             lines = out.read_text().splitlines()
     body, meta, per_trip, name = None, {}, 1, None
-    if not a.general:
-        body, meta = function_body(lines, LEAN)
-        if body is not None:
-            per_trip, name = 2, LEAN
+    for cand in ([] if a.general else list(LEAN) if a.lean else [RIMU, *LEAN]):
+        if body is None:
+            body, meta = function_body(lines, cand)
+            if body is not None:
+                per_trip, name = 2, cand
     for g in GENERAL:
         if body is None:
             body, meta = function_body(lines, g)

@@ -1,5 +1,7 @@
 """Where a subcycle of the on-chip resident kernel goes, per wave: shader-cycle stamps collected under
-CICE_EVP_HIP_RES_PROF=1 (16 x 16 tiles).  Usage: python tools/resident_phases.py [gx1|gx3|p2] [ndte]"""
+CICE_EVP_HIP_RES_PROF=1 (16 x 16 tiles).  Usage: python tools/resident_phases.py [gx1|gx3|p2] [ndte]
+(CICE_EVP_HIP_RES_RIMU=0: the lean loop's first schedule, two workgroup barriers per subcycle.  On the rim-wave schedule the third
+stamp is the wait for the interior waves' slots and the fifth the one barrier; for an interior wave the fourth is its momentum step)"""
 import os, sys, pathlib
 R = str(pathlib.Path(__file__).resolve().parents[1]); sys.path[:0] = [R, R + "/tests", R + "/oracle"]
 os.environ["CICE_EVP_HIP_RES_PROF"] = "1"
@@ -20,17 +22,18 @@ for _ in range(3): core.subcycle(ndte)
 core.sync()
 p = core.debug_prof().astype(np.float64)
 tt = core.timings()
+rimu = "edge U-cells in the rim wave" in core.describe_path()
 core.finalize()
 used = p[:, :, :5].sum(axis=(1, 2)) > 0
 p = p[used]
 ph = p[:, :, :5] / ndte                     # cycles per subcycle
-names = ["poll", "stress", "wait B1", "stepu+publish", "wait B2"]
+names = ["poll", "stress", "wait slots", "stepu+publish", "barrier"] if rimu else ["poll", "stress", "wait B1", "stepu+publish", "wait B2"]
 nact = p[:, 0, 7].astype(int)
 word5 = p[:, 0, 5].astype(np.int64)
 rank = (word5 & 255).astype(int)
 cu = ((word5 >> 8) & 0xffff).astype(int)
 simd = ((p[:, :, 5].astype(np.int64) >> 24) & 3).astype(int)        # [tile][chunk]: SIMD of the wave that took the chunk
-print("RESULT", wl, "tiles", len(p), "us/subcycle (event)", 1e3 * tt["loop_ms"] / ndte)
+print("RESULT", wl, "rim-wave schedule" if rimu else "two-barrier schedule", "tiles", len(p), "us/subcycle (event)", 1e3 * tt["loop_ms"] / ndte)
 def show(sel, what):
     if not sel.any(): return
     late, early = ph[sel][:, 0, :], ph[sel][:, 1:, :].reshape(-1, 5)
