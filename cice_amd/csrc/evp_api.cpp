@@ -1136,6 +1136,32 @@ int cice_evp_hip_fold_split_plan(int32_t which, int32_t *count, int32_t *cells)
     return P.fold_split ? 1 : 0;
 }
 
+// The range-proved square root and division of the lean resident loops (evp_range_math.h) beside the compiler's, on the current
+// device; needs no cice_evp_hip_init.  Host arrays of n elements.
+int cice_evp_hip_debug_range_math(int64_t n, const double *x, const double *num, const double *den, double *sqrt_lib, double *sqrt_core,
+                                  double *div_lib, double *div_core, uint8_t *verdict)
+{
+    if (n < 1 || n > ((int64_t)1 << 26) || !x || !num || !den || !sqrt_lib || !sqrt_core || !div_lib || !div_core || !verdict)
+        return fail(-1, "debug_range_math: bad argument");
+    const size_t nb = (size_t)n * sizeof(double);
+    double *d = nullptr;
+    unsigned char *dv = nullptr;
+    HIPC(hipMalloc((void **)&d, 7 * nb));
+    hipError_t e = hipMalloc((void **)&dv, (size_t)n);
+    if (e == hipSuccess) e = hipMemcpy(d, x, nb, hipMemcpyHostToDevice);
+    if (e == hipSuccess) e = hipMemcpy(d + n, num, nb, hipMemcpyHostToDevice);
+    if (e == hipSuccess) e = hipMemcpy(d + 2 * n, den, nb, hipMemcpyHostToDevice);
+    if (e == hipSuccess) e = evp_range_math_probe((long long)n, d, d + n, d + 2 * n, d + 3 * n, d + 4 * n, d + 5 * n, d + 6 * n, dv, nullptr);
+    if (e == hipSuccess) e = hipDeviceSynchronize();
+    double *outs[4] = {sqrt_lib, sqrt_core, div_lib, div_core};
+    for (int k = 0; k < 4 && e == hipSuccess; ++k) e = hipMemcpy(outs[k], d + (3 + k) * n, nb, hipMemcpyDeviceToHost);
+    if (e == hipSuccess) e = hipMemcpy(verdict, dv, (size_t)n, hipMemcpyDeviceToHost);
+    (void)hipFree(d);
+    if (dv) (void)hipFree(dv);
+    if (e != hipSuccess) return fail(-2, "debug_range_math: %s", hipGetErrorString(e));
+    return 0;
+}
+
 int cice_evp_hip_stress_plan(int32_t *count, int32_t *dst, int32_t *src)
 {
     const size_t n = copy_out(dst, S.plan.stress_dst);

@@ -43,13 +43,18 @@ __device__ __forceinline__ void metrics_cell(double hte, double hte_im, double h
 // sum with exactly +-0.0 those values produce is dropped.  x*1.0 == x and x + (+-0.0*finite) == x bit
 // for bit, so the strict build stays bit-identical to the general code (the fused build contracts
 // differently: covered by its tolerance, and the same in every kernel).
-template <int CAP, bool SIMPLE = false>
+// CORE: strength and fmax(Delta, DminArea) are inside evp_range_math.h's window in every active lane (CAP == 1 only): the
+// division's core without its range handling, the same bits.
+template <int CAP, bool SIMPLE = false, bool CORE = false>
 __device__ __forceinline__ void visc_replpress(const EvpScalars &p, double strength, double DminArea,
                                                double Delta, double &zetax2, double &etax2,
                                                double &rep_prs)
 {
+    static_assert(!CORE || CAP == 1, "the range-proved division is instantiated for capping == 1 only");
     double tmpcalc;
-    if (CAP == 1) {
+    if (CORE) {
+        tmpcalc = evp_range::div_core(strength, fmax(Delta, DminArea));
+    } else if (CAP == 1) {
         tmpcalc = strength / fmax(Delta, DminArea);
     } else if (CAP == 0) {
         tmpcalc = strength / (Delta + DminArea);
@@ -69,9 +74,11 @@ __device__ __forceinline__ void visc_replpress(const EvpScalars &p, double stren
 
 // Updates the 12 stress components s[0..11] = stressp_1..4, stressm_1..4,
 // stress12_1..4 in place and returns the eight stress-divergence partials.
-template <int CAP, bool SIMPLE = false>
+// POL (evp_range_math.h): LibMath -- the compiler's sqrt and division; RangeMath -- their cores where every active lane of the wave
+// has the four Delta^2 (and, classified once per call, strength and DminTarea) inside the window, the library forms otherwise.
+template <int CAP, bool SIMPLE = false, class POL = evp_range::LibMath>
 __device__ __forceinline__ void stress_cell(const EvpScalars &p, const StressIn &a, double (&s)[12],
-                                            double (&str)[8])
+                                            double (&str)[8], const POL &pol = POL())
 {
     // divergence  =  e_11 + e_22
     const double divune = a.cyp * a.u_ij - a.dyT * a.u_im + a.cxp * a.v_ij - a.dxT * a.v_jm;
@@ -89,17 +96,42 @@ __device__ __forceinline__ void stress_cell(const EvpScalars &p, const StressIn 
     const double shearsw = -a.cyp * a.v_mm + a.dyT * a.v_jm - a.cxp * a.u_mm + a.dxT * a.u_im;
     const double shearse = -a.cym * a.v_jm - a.dyT * a.v_mm - a.cxp * a.u_jm + a.dxT * a.u_ij;
     // Delta (in the denominator of zeta, eta)
+    double zetax2ne, etax2ne, rep_prsne, zetax2nw, etax2nw, rep_prsnw;
+    double zetax2sw, etax2sw, rep_prssw, zetax2se, etax2se, rep_prsse;
+    if constexpr (POL::ranged) {
+        using namespace evp_range;
+        const double Delta2ne = divune * divune + p.e_factor * (tensionne * tensionne + shearne * shearne);
+        const double Delta2nw = divunw * divunw + p.e_factor * (tensionnw * tensionnw + shearnw * shearnw);
+        const double Delta2sw = divusw * divusw + p.e_factor * (tensionsw * tensionsw + shearsw * shearsw);
+        const double Delta2se = divuse * divuse + p.e_factor * (tensionse * tensionse + shearse * shearse);
+        bool cores;
+        const unsigned far = umax(umax(off_pos(Delta2ne), off_pos(Delta2nw)), umax(off_pos(Delta2sw), off_pos(Delta2se)));
+        cores = pol.wave_inside(outside(far), true);
+        if (cores) {      // uniform; Delta = sqrt(Delta^2) lies in [2^-125, 2^125], so fmax(Delta, DminTarea) is inside as well
+            const double Deltane = sqrt_core(Delta2ne), Deltanw = sqrt_core(Delta2nw);
+            const double Deltasw = sqrt_core(Delta2sw), Deltase = sqrt_core(Delta2se);
+            visc_replpress<CAP, SIMPLE, true>(p, a.strength, a.DminTarea, Deltane, zetax2ne, etax2ne, rep_prsne);
+            visc_replpress<CAP, SIMPLE, true>(p, a.strength, a.DminTarea, Deltanw, zetax2nw, etax2nw, rep_prsnw);
+            visc_replpress<CAP, SIMPLE, true>(p, a.strength, a.DminTarea, Deltasw, zetax2sw, etax2sw, rep_prssw);
+            visc_replpress<CAP, SIMPLE, true>(p, a.strength, a.DminTarea, Deltase, zetax2se, etax2se, rep_prsse);
+        } else {
+            const double Deltane = sqrt(Delta2ne), Deltanw = sqrt(Delta2nw);
+            const double Deltasw = sqrt(Delta2sw), Deltase = sqrt(Delta2se);
+            visc_replpress<CAP, SIMPLE>(p, a.strength, a.DminTarea, Deltane, zetax2ne, etax2ne, rep_prsne);
+            visc_replpress<CAP, SIMPLE>(p, a.strength, a.DminTarea, Deltanw, zetax2nw, etax2nw, rep_prsnw);
+            visc_replpress<CAP, SIMPLE>(p, a.strength, a.DminTarea, Deltasw, zetax2sw, etax2sw, rep_prssw);
+            visc_replpress<CAP, SIMPLE>(p, a.strength, a.DminTarea, Deltase, zetax2se, etax2se, rep_prsse);
+        }
+    } else {
     const double Deltane = sqrt(divune * divune + p.e_factor * (tensionne * tensionne + shearne * shearne));
     const double Deltanw = sqrt(divunw * divunw + p.e_factor * (tensionnw * tensionnw + shearnw * shearnw));
     const double Deltasw = sqrt(divusw * divusw + p.e_factor * (tensionsw * tensionsw + shearsw * shearsw));
     const double Deltase = sqrt(divuse * divuse + p.e_factor * (tensionse * tensionse + shearse * shearse));
-
-    double zetax2ne, etax2ne, rep_prsne, zetax2nw, etax2nw, rep_prsnw;
-    double zetax2sw, etax2sw, rep_prssw, zetax2se, etax2se, rep_prsse;
     visc_replpress<CAP, SIMPLE>(p, a.strength, a.DminTarea, Deltane, zetax2ne, etax2ne, rep_prsne);
     visc_replpress<CAP, SIMPLE>(p, a.strength, a.DminTarea, Deltanw, zetax2nw, etax2nw, rep_prsnw);
     visc_replpress<CAP, SIMPLE>(p, a.strength, a.DminTarea, Deltasw, zetax2sw, etax2sw, rep_prssw);
     visc_replpress<CAP, SIMPLE>(p, a.strength, a.DminTarea, Deltase, zetax2se, etax2se, rep_prsse);
+    }
 
     // the stresses: (1) northeast, (2) northwest, (3) southwest, (4) southeast
     const double arlx1i = p.arlx1i, revp = p.revp, denom1 = p.denom1;
@@ -308,13 +340,22 @@ struct StepuPre {
 // TBU: false when the host has verified TbU == 0 on every ice U-cell (seabed stress off): Cb = 0/(...) == 0
 // WITH_B: the first part also forms bu, bv; without, the second part forms them inside cc1 / cc2, where the one-piece form had
 // them -- stepu_cell takes that order, so that the kernels that call it compile to the code they compiled to before the split
-template <bool SIMPLE = false, bool TBU = true, bool WITH_B = true>
-__device__ __forceinline__ void stepu_pre_cell(const EvpScalars &p, const StepuIn &a, StepuPre &w)
+// POL (evp_range_math.h), RangeMath: the square root's core where du^2 + dv^2 is inside the window in every active lane.  The two
+// divisions of the second part stay the compiler's: the test of their three operands costs what their range handling costs.
+template <bool SIMPLE = false, bool TBU = true, bool WITH_B = true, class POL = evp_range::LibMath>
+__device__ __forceinline__ void stepu_pre_cell(const EvpScalars &p, const StepuIn &a, StepuPre &w, const POL &pol = POL())
 {
     const double uold = a.uold, vold = a.vold;
     // (magnitude of relative ocean current)*rhow*drag*aice
     const double du = a.uocn - uold, dv = a.vocn - vold;
-    const double vrel = a.vrelfac * sqrt(du * du + dv * dv);
+    double vrel;
+    if constexpr (POL::ranged) {
+        const double speed2 = du * du + dv * dv;
+        if (pol.wave_inside(evp_range::outside(evp_range::off_pos(speed2)), false)) vrel = a.vrelfac * evp_range::sqrt_core(speed2);
+        else vrel = a.vrelfac * sqrt(speed2);
+    } else {
+    vrel = a.vrelfac * sqrt(du * du + dv * dv);
+    }
     // ice/ocean stress
     w.taux = vrel * a.waterx;
     w.tauy = vrel * a.watery;
@@ -343,7 +384,8 @@ __device__ __forceinline__ void stepu_pre_cell(const EvpScalars &p, const StepuI
 }
 
 // the part that reads the stress partials (a.sx0 .. a.sy3; a.uarear, a.forcex / forcey, a.Umassdti besides)
-template <bool SIMPLE = false, bool WITH_B = true>
+// POL::lazy_taub: o.taubx / o.tauby are left to the caller, which forms them from o.u, o.v and w.Cb where it stores them
+template <bool SIMPLE = false, bool WITH_B = true, class POL = evp_range::LibMath>
 __device__ __forceinline__ void stepu_post_cell(const EvpScalars &p, const StepuIn &a, const StepuPre &w, StepuOut &o)
 {
     // divergence of the internal stress tensor
@@ -364,15 +406,16 @@ __device__ __forceinline__ void stepu_post_cell(const EvpScalars &p, const Stepu
     o.u = (w.cca * cc1 + w.ccb * cc2) / w.ab2;
     o.v = (w.cca * cc2 - w.ccb * cc1) / w.ab2;
     // seabed stress component for outputs
+    if (POL::lazy_taub) return;
     o.taubx = -o.u * w.Cb;
     o.tauby = -o.v * w.Cb;
 }
 
-template <bool SIMPLE = false, bool TBU = true>
-__device__ __forceinline__ void stepu_cell(const EvpScalars &p, const StepuIn &a, StepuOut &o)
+template <bool SIMPLE = false, bool TBU = true, class POL = evp_range::LibMath>
+__device__ __forceinline__ void stepu_cell(const EvpScalars &p, const StepuIn &a, StepuOut &o, const POL &pol = POL())
 {
     StepuPre w;
-    stepu_pre_cell<SIMPLE, TBU, false>(p, a, w);
+    stepu_pre_cell<SIMPLE, TBU, false, POL>(p, a, w, pol);
     stepu_post_cell<SIMPLE, false>(p, a, w, o);
 }
 

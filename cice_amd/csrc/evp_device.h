@@ -92,7 +92,7 @@ struct EvpResident2 {
     const uint8_t *nlate;      // [ntiles] COOP: rim T-cells with ice = the first nlate entries of perm (<= 64); NULL: the variant is off
     int *cuload;               // [2048][8] per-CU record of the launch: lock, stamp, ice-holding waves per SIMD
     unsigned long long *prof;  // NULL, or [ntiles][4 chunks][8]: cycles per phase (tools)
-    int dbg;                   // timing experiments only (CICE_EVP_HIP_RES_DEBUG; WRONG results): 1 no tag check, 2 no ring loads, 4 longer sleep; 8 = every fourth tile lags 10 us per subcycle (results stay right); 16 = tile 1 never runs (every wait on it gives up); A/B switches, results stay right: 32 = 16 x 16 tiles without the rim-wave split, 64 = without the per-CU SIMD balancing
+    int dbg;                   // timing experiments only (CICE_EVP_HIP_RES_DEBUG; WRONG results): 1 no tag check, 2 no ring loads, 4 longer sleep; 8 = every fourth tile lags 10 us per subcycle (results stay right); 16 = tile 1 never runs (every wait on it gives up); A/B switches, results stay right: 32 = 16 x 16 tiles without the rim-wave split, 64 = without the per-CU SIMD balancing, 1024 = the lean loops' square roots and divisions always the compiler's (evp_range_math.h)
     int par0;                  // which of rec[0/1] holds the records of subcycle index 0 of THIS launch
                                // (flips so that a launch never starts in the buffer the previous one ended in)
     // neighbours on other GPUs (ring entries with z == -2 are produced there); rimg == NULL: none
@@ -113,6 +113,16 @@ struct EvpResident2 {
     void *const *peer_raw;     // [npeers] the peer's rec_raw buffer (parity 0) as mapped here
     const size_t *peer_raw_stride;
 };
+// the lean resident loops take the cores of the fp64 square root and division where a wave's operands are proved in range
+// (evp_range_math.h); 0: compiled out of the product (the test build carries both, CICE_EVP_HIP_RES_RANGE)
+#ifndef EVP_RES2_RANGE_DEFAULT
+#define EVP_RES2_RANGE_DEFAULT 1
+#endif
+#ifdef CICE_EVP_HIP_TESTING
+// test build: evp_range_math.h's cores beside the compiler's forms over n elements (device pointers; evp_resident2.hip)
+hipError_t evp_range_math_probe(long long n, const double *x, const double *num, const double *den, double *sqrt_lib, double *sqrt_core,
+                                double *div_lib, double *div_core, unsigned char *verdict, hipStream_t st);
+#endif
 int evp_resident2_max_blocks_per_cu(bool strict, int cap, unsigned flags, int logw, bool remote, bool coop = false);
 bool evp_resident2_coop_built(bool strict, int cap, int logw, bool remote);   // the rim-cells-by-corners variant exists for this combination
 bool evp_resident2_lean_built(bool strict, int cap, int logw, bool remote);   // the lean variant (one rank, no fold, ...) exists

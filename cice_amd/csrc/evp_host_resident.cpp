@@ -464,7 +464,10 @@ int launch_resident2(int ndte, int cur0, bool dry)
         R.prof = S.res2_prof;
     }
     const int dbg2 = env_test("CICE_EVP_HIP_RES_DEBUG") ? std::atoi(env_test("CICE_EVP_HIP_RES_DEBUG")) : 0;
-    R.dbg = dbg2;
+    // range-proved square roots and divisions in the lean loops (CICE_EVP_HIP_RES_RANGE=1/0, test build: A/B; the product's
+    // kernel is compiled with or without them, EVP_RES2_RANGE_DEFAULT, and tests nothing)
+    const int want_range = env_test("CICE_EVP_HIP_RES_RANGE") ? std::atoi(env_test("CICE_EVP_HIP_RES_RANGE")) : EVP_RES2_RANGE_DEFAULT;
+    R.dbg = dbg2 | (want_range ? 0 : 1024);
     R.seam = S.res2_seam;
     R.tfold = S.plan.tfold ? 1 : 0;
     R.img3 = S.res2_img3;

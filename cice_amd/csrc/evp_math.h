@@ -4,6 +4,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 #include "evp_device.h"
+#include "evp_range_math.h"
 
 namespace {
 
@@ -45,12 +46,24 @@ template <> struct Math<true> {
     }
     template <int MODE = -1, bool TBU = true>
     static __device__ __forceinline__ void stepu(const EvpScalars &p, const UI &a, UO &o) { evp_strict::stepu_cell<MODE == 3, TBU>(p, a, o); }
+    // the same under a policy of evp_range_math.h (the lean resident loops)
+    template <int MODE, class POL>
+    static __device__ __forceinline__ void stress(const EvpScalars &p, const SI &a, double (&s)[12], double (&str)[8], const POL &pol)
+    {
+        evp_strict::stress_cell<(MODE == 3 ? 1 : MODE), MODE == 3, POL>(p, a, s, str, pol);
+    }
+    template <int MODE, bool TBU, class POL>
+    static __device__ __forceinline__ void stepu(const EvpScalars &p, const UI &a, UO &o, const POL &pol) { evp_strict::stepu_cell<MODE == 3, TBU, POL>(p, a, o, pol); }
     // the momentum step in two parts: what reads no stress partial, and the rest (evp_cell.inc)
     using UP = evp_strict::StepuPre;
     template <int MODE = -1, bool TBU = true>
     static __device__ __forceinline__ void stepu_pre(const EvpScalars &p, const UI &a, UP &w) { evp_strict::stepu_pre_cell<MODE == 3, TBU>(p, a, w); }
     template <int MODE = -1>
     static __device__ __forceinline__ void stepu_post(const EvpScalars &p, const UI &a, const UP &w, UO &o) { evp_strict::stepu_post_cell<MODE == 3, true>(p, a, w, o); }
+    template <int MODE, bool TBU, class POL>
+    static __device__ __forceinline__ void stepu_pre(const EvpScalars &p, const UI &a, UP &w, const POL &pol) { evp_strict::stepu_pre_cell<MODE == 3, TBU, true, POL>(p, a, w, pol); }
+    template <int MODE, class POL>
+    static __device__ __forceinline__ void stepu_post(const EvpScalars &p, const UI &a, const UP &w, UO &o, const POL &) { evp_strict::stepu_post_cell<MODE == 3, true, POL>(p, a, w, o); }
     static __device__ __forceinline__ void metrics(double hte, double hte_im, double htn, double htn_jm, double dmin, SI &a)
     {
         evp_strict::metrics_cell(hte, hte_im, htn, htn_jm, dmin, a);
@@ -87,12 +100,24 @@ template <> struct Math<false> {
     }
     template <int MODE = -1, bool TBU = true>
     static __device__ __forceinline__ void stepu(const EvpScalars &p, const UI &a, UO &o) { evp_fused::stepu_cell<MODE == 3, TBU>(p, a, o); }
+    // the same under a policy of evp_range_math.h (the lean resident loops)
+    template <int MODE, class POL>
+    static __device__ __forceinline__ void stress(const EvpScalars &p, const SI &a, double (&s)[12], double (&str)[8], const POL &pol)
+    {
+        evp_fused::stress_cell<(MODE == 3 ? 1 : MODE), MODE == 3, POL>(p, a, s, str, pol);
+    }
+    template <int MODE, bool TBU, class POL>
+    static __device__ __forceinline__ void stepu(const EvpScalars &p, const UI &a, UO &o, const POL &pol) { evp_fused::stepu_cell<MODE == 3, TBU, POL>(p, a, o, pol); }
     // the momentum step in two parts: what reads no stress partial, and the rest (evp_cell.inc)
     using UP = evp_fused::StepuPre;
     template <int MODE = -1, bool TBU = true>
     static __device__ __forceinline__ void stepu_pre(const EvpScalars &p, const UI &a, UP &w) { evp_fused::stepu_pre_cell<MODE == 3, TBU>(p, a, w); }
     template <int MODE = -1>
     static __device__ __forceinline__ void stepu_post(const EvpScalars &p, const UI &a, const UP &w, UO &o) { evp_fused::stepu_post_cell<MODE == 3, true>(p, a, w, o); }
+    template <int MODE, bool TBU, class POL>
+    static __device__ __forceinline__ void stepu_pre(const EvpScalars &p, const UI &a, UP &w, const POL &pol) { evp_fused::stepu_pre_cell<MODE == 3, TBU, true, POL>(p, a, w, pol); }
+    template <int MODE, class POL>
+    static __device__ __forceinline__ void stepu_post(const EvpScalars &p, const UI &a, const UP &w, UO &o, const POL &) { evp_fused::stepu_post_cell<MODE == 3, true, POL>(p, a, w, o); }
     static __device__ __forceinline__ void metrics(double hte, double hte_im, double htn, double htn_jm, double dmin, SI &a)
     {
         evp_fused::metrics_cell(hte, hte_im, htn, htn_jm, dmin, a);

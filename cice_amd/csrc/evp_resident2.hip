@@ -69,6 +69,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include <algorithm>
+#include <type_traits>
 
 // Debug hooks (lagging tiles, a workgroup that never shows up, A/B switches) and the per-phase cycle stamps exist in the
 // TEST build's object of this file only (-DCICE_EVP_HIP_TESTING, linked into libcice_evp_hip_testing.so): the product
@@ -175,6 +176,11 @@ constexpr int QP_X1 = 0xB1, QP_X2 = 0x4E, QP_X3 = 0x1B;      // quad_perm [1,0,3
 // (profiles/r07_resident_lean_*.txt, tools/resident_isa_mix.py).
 // RIMU: the lean loop on the rim-wave schedule of the header (profiles/r14_resident_rim_u.txt); where a tile's lane tables cannot
 // satisfy rim_plan.h's rules the launch takes the lean loop as it was (per launch, evp_host_resident.cpp).
+// Range-proved arithmetic (the two lean loops; evp_range_math.h, profiles/r15_resident_range_math.txt): a wave whose active lanes
+// all have their operands inside a window of exponents takes the cores of the fp64 square root and division without the range
+// handling the compiler wraps them in, any other wave the compiler's forms -- per pass, a uniform branch, the same bits.  The
+// product compiles it in or out (EVP_RES2_RANGE_DEFAULT); the test build carries it with a switch (RES_DEBUG bit 1024: always the
+// compiler's forms; CICE_EVP_HIP_RES_RANGE=0 sets it).
 template <bool STRICT, int CAP, int LOGW, bool REMOTE, bool COOP = false, bool LEAN = false, bool RIMU = false>
 __global__ __launch_bounds__(64 * RTY, REMOTE ? 2 : 3) void evp_resident2_tile(EvpArgs A, EvpResident2 R)
 {
@@ -182,6 +188,14 @@ __global__ __launch_bounds__(64 * RTY, REMOTE ? 2 : 3) void evp_resident2_tile(E
     static_assert(!LEAN || (!REMOTE && !COOP && LOGW == 4), "LEAN: one rank, 16 x 16 tiles, one thread per rim cell");
     static_assert(!RIMU || LEAN, "RIMU: a schedule of the lean loop");
     using MM = Math<STRICT>;
+#ifdef CICE_EVP_HIP_TESTING
+    constexpr bool RANGE = LEAN;
+#else
+    constexpr bool RANGE = LEAN && EVP_RES2_RANGE_DEFAULT;
+#endif
+    // the policy of the lean loops' arithmetic; POLE: the same with taubx / tauby formed every subcycle (the first lean loop)
+    using POL = std::conditional_t<RANGE, std::conditional_t<RIMU, evp_range::RangeMathLazy, evp_range::RangeMath>, evp_range::LibMath>;
+    using POLE = std::conditional_t<RANGE, evp_range::RangeMath, evp_range::LibMath>;
     constexpr int W = 1 << LOGW;
     constexpr int H = 256 / W;
     constexpr int LW = W + 1;                 // LDS velocity tile: (H+1) x (W+1), origin (-1,-1)
@@ -399,6 +413,8 @@ __global__ __launch_bounds__(64 * RTY, REMOTE ? 2 : 3) void evp_resident2_tile(E
     // ---- state that stays on the CU for the whole call -------------------------------------
     typename MM::SI a;
     double s[12];
+    POL pol;
+    bool percall_out = false;
     if (actN) {
 #pragma unroll
         for (int k = 0; k < 12; ++k) s[k] = R.tab[R.cur0 * 12 + k][c];
@@ -415,7 +431,13 @@ __global__ __launch_bounds__(64 * RTY, REMOTE ? 2 : 3) void evp_resident2_tile(E
         s_tc[1 * 256 + t] = a.DminTarea;
         s_tc[2 * 256 + t] = a.dxhy;
         s_tc[3 * 256 + t] = a.dyhx;
+        if constexpr (POL::ranged) percall_out = POL::percall_outside(a.strength, a.DminTarea);
     }
+    if constexpr (POL::ranged) {
+        pol.cbad = __builtin_amdgcn_ballot_w64(percall_out);
+        pol.off = (RES_DBG(R) & 1024) != 0;
+    }
+    const POLE &pole = pol;
     if (isU) {
         s_uc[0 * 256 + t] = A.vrelfac[cu];
         s_uc[1 * 256 + t] = A.uocn[cu];
@@ -671,7 +693,7 @@ __global__ __launch_bounds__(64 * RTY, REMOTE ? 2 : 3) void evp_resident2_tile(E
             a.u_mm = s_u[li - LW - 1]; a.v_mm = s_v[li - LW - 1];
             a.strength = s_tc[0 * 256 + t]; a.DminTarea = s_tc[1 * 256 + t];
             a.dxhy = s_tc[2 * 256 + t]; a.dyhx = s_tc[3 * 256 + t];
-            MM::template stress<CAP>(A.p, a, s, str);
+            MM::template stress<CAP, POLE>(A.p, a, s, str, pole);
         }
         EVP_STAMP(pacc1)
         double sx1, sy2;
@@ -744,8 +766,8 @@ __global__ __launch_bounds__(64 * RTY, REMOTE ? 2 : 3) void evp_resident2_tile(E
             q.sx2 = s_str[0 * SP + sp + SW]; q.sx3 = s_str[2 * SP + sp + SW + 1];
             q.sy0 = str[4]; q.sy1 = s_str[1 * SP + sp + SW];
             q.sy2 = sy2; q.sy3 = s_str[3 * SP + sp + SW + 1];
-            if (tbu) MM::template stepu<CAP, true>(A.p, q, o);
-            else MM::template stepu<CAP, false>(A.p, q, o);
+            if (tbu) MM::template stepu<CAP, true, POLE>(A.p, q, o, pole);
+            else MM::template stepu<CAP, false, POLE>(A.p, q, o, pole);
             u_own = o.u; v_own = o.v;
             if (k == R.ndte - 1 && !R.dry) {
                 R.tab[24][c] = o.strintx; R.tab[25][c] = o.strinty;
@@ -869,7 +891,7 @@ __global__ __launch_bounds__(64 * RTY, REMOTE ? 2 : 3) void evp_resident2_tile(E
     if constexpr (RIMU) if (rimw && isU) {
         typename MM::UI q;
         ucell_operands(q);
-        MM::template stepu_pre<CAP, false>(A.p, q, upre);
+        MM::template stepu_pre<CAP, false, POL>(A.p, q, upre, pol);
     }
     auto subcycle_rim = [&](const int k, const v4u *rd, v4u *wr) -> bool {
         const unsigned want = R.tag_base + (unsigned)k;       // tag of the velocities subcycle k reads
@@ -924,7 +946,7 @@ __global__ __launch_bounds__(64 * RTY, REMOTE ? 2 : 3) void evp_resident2_tile(E
                 a.u_mm = s_u[li - LW - 1]; a.v_mm = s_v[li - LW - 1];
                 a.strength = s_tc[0 * 256 + t]; a.DminTarea = s_tc[1 * 256 + t];
                 a.dxhy = s_tc[2 * 256 + t]; a.dyhx = s_tc[3 * 256 + t];
-                MM::template stress<CAP>(A.p, a, s, str);
+                MM::template stress<CAP, POL>(A.p, a, s, str, pol);
                 s_str[0 * SP + sp] = str[2];
                 s_str[1 * SP + sp] = str[5];
                 s_str[2 * SP + sp] = str[3];
@@ -963,6 +985,37 @@ __global__ __launch_bounds__(64 * RTY, REMOTE ? 2 : 3) void evp_resident2_tile(E
         }
         if (!bad) {
             double fin0 = 0.0, fin1 = 0.0, fin2 = 0.0, fin3 = 0.0;
+            if constexpr (POL::lazy_taub) {
+                // the same with the four outputs of the last subcycle formed where they are stored: strintx / strinty stay in
+                // o (read under isU only, like the momentum step that sets them), taubx / tauby = -u * Cb, -v * Cb from the
+                // operands stepu_post_cell forms them from
+                typename MM::UO o;
+                if (isU) {
+                    typename MM::UI q;
+                    ucell_operands(q);
+                    q.sx0 = s_str[6 * SP + usp]; q.sx1 = s_str[4 * SP + usp + 1];
+                    q.sx2 = s_str[0 * SP + usp + SW]; q.sx3 = s_str[2 * SP + usp + SW + 1];
+                    q.sy0 = s_str[7 * SP + usp]; q.sy1 = s_str[1 * SP + usp + SW];
+                    q.sy2 = s_str[5 * SP + usp + 1]; q.sy3 = s_str[3 * SP + usp + SW + 1];
+                    if (!rimw) MM::template stepu_pre<CAP, false, POL>(A.p, q, upre, pol);
+                    MM::template stepu_post<CAP, POL>(A.p, q, upre, o, pol);
+                    u_own = o.u; v_own = o.v;
+                }
+                if (ownU) {      // the records first: the neighbours wait for them (every cell with a record to write is in L_U: rim_plan.h)
+                    const unsigned tag = want + 1u;
+                    if (pub) st_rec2_s(wr, own_off, pack_rec(u_own, tag), pack_rec(v_own, tag));
+                    if (img0 >= 0) st_rec2_s(wr, img_off0, pack_rec(img_sg0 * u_own, tag), pack_rec(img_sg0 * v_own, tag));
+                    if (img1 >= 0) st_rec2_s(wr, img_off1, pack_rec(img_sg1 * u_own, tag), pack_rec(img_sg1 * v_own, tag));
+                    if (img2 >= 0) st_rec2_s(wr, img_off2, pack_rec(img_sg2 * u_own, tag), pack_rec(img_sg2 * v_own, tag));
+                }
+                if (isU) {
+                    s_u[uli] = u_own; s_v[uli] = v_own;       // read by the next stress phase, after the barrier below
+                    if (k == R.ndte - 1 && !R.dry) {
+                        R.tab[24][cu] = o.strintx; R.tab[25][cu] = o.strinty;
+                        R.tab[26][cu] = -u_own * upre.Cb; R.tab[27][cu] = -v_own * upre.Cb;
+                    }
+                }
+            } else {
             if (isU) {
                 typename MM::UI q;
                 typename MM::UO o;
@@ -971,8 +1024,8 @@ __global__ __launch_bounds__(64 * RTY, REMOTE ? 2 : 3) void evp_resident2_tile(E
                 q.sx2 = s_str[0 * SP + usp + SW]; q.sx3 = s_str[2 * SP + usp + SW + 1];
                 q.sy0 = s_str[7 * SP + usp]; q.sy1 = s_str[1 * SP + usp + SW];
                 q.sy2 = s_str[5 * SP + usp + 1]; q.sy3 = s_str[3 * SP + usp + SW + 1];
-                if (!rimw) MM::template stepu_pre<CAP, false>(A.p, q, upre);
-                MM::template stepu_post<CAP>(A.p, q, upre, o);
+                if (!rimw) MM::template stepu_pre<CAP, false, POL>(A.p, q, upre, pol);
+                MM::template stepu_post<CAP, POL>(A.p, q, upre, o, pol);
                 u_own = o.u; v_own = o.v;
                 fin0 = o.strintx; fin1 = o.strinty; fin2 = o.taubx; fin3 = o.tauby;
             }
@@ -990,6 +1043,7 @@ __global__ __launch_bounds__(64 * RTY, REMOTE ? 2 : 3) void evp_resident2_tile(E
                     R.tab[26][cu] = fin2; R.tab[27][cu] = fin3;
                 }
             }
+            }
             EVP_STAMP(pacc3)
         }
         __syncthreads();      // the one barrier: the tile's new velocities are in LDS, every read of the planes is done
@@ -1000,7 +1054,7 @@ __global__ __launch_bounds__(64 * RTY, REMOTE ? 2 : 3) void evp_resident2_tile(E
         if (rimw && isU) {
             typename MM::UI q;
             ucell_operands(q);
-            MM::template stepu_pre<CAP, false>(A.p, q, upre);
+            MM::template stepu_pre<CAP, false, POL>(A.p, q, upre, pol);
         }
         return true;
     };
@@ -1031,7 +1085,9 @@ __global__ __launch_bounds__(64 * RTY, REMOTE ? 2 : 3) void evp_resident2_tile(E
         unsigned long long *o = R.prof + ((size_t)tile * 4 + (tq >> 6)) * 8;
         o[0] = pacc0; o[1] = pacc1; o[2] = pacc2; o[3] = pacc3; o[4] = pacc4;
         o[5] = (unsigned long long)cu_rank | ((unsigned long long)(PERM && R.cuload ? s_cu : 0) << 8) | ((unsigned long long)(s_simd[t >> 6] & 3) << 24);
-        o[6] = (unsigned long long)(t >> 6); o[7] = (unsigned long long)R.nact[tile];
+        unsigned long long nlib = 0;      // passes of this wave that took the compiler's sqrt / division (evp_range_math.h)
+        if constexpr (POL::ranged) nlib = pol.nlib;
+        o[6] = (unsigned long long)(t >> 6) | (nlib << 8); o[7] = (unsigned long long)R.nact[tile];
     }
     // ghost cells that mirror another rank's cells: fetch the final velocities (the caller
     // relies on current ghosts, ice_dyn_evp.F90:920-934)
@@ -1114,6 +1170,35 @@ void launch(const EvpArgs &A, const EvpResident2 &R, bool strict, int cap, hipSt
 }
 
 }  // namespace
+
+#ifdef CICE_EVP_HIP_TESTING
+// Test build: the cores of evp_range_math.h beside the compiler's sqrt and division, element by element, with the verdicts of the
+// window tests the kernels use (cice_evp_hip_debug_range_math, tests/test_gpu_range_math.py).  Device pointers, n elements each.
+namespace {
+__global__ __launch_bounds__(256) void range_math_probe(long long n, const double *x, const double *num, const double *den, double *sqrt_lib,
+                                                        double *sqrt_core, double *div_lib, double *div_core, unsigned char *verdict)
+{
+    const long long e = (long long)blockIdx.x * 256 + threadIdx.x;
+    if (e >= n) return;
+    const double xx = x[e], nn = num[e], dd = den[e];
+    sqrt_lib[e] = sqrt(xx);
+    sqrt_core[e] = evp_range::sqrt_core(xx);
+    div_lib[e] = nn / dd;
+    div_core[e] = evp_range::div_core(nn, dd);
+    const bool x_in = !evp_range::outside(evp_range::off_pos(xx));
+    const bool q_in = !evp_range::outside(evp_range::umax(evp_range::off_abs(nn), evp_range::off_abs(dd)));
+    verdict[e] = (unsigned char)((x_in ? 1 : 0) | (q_in ? 2 : 0));
+}
+}  // namespace
+hipError_t evp_range_math_probe(long long n, const double *x, const double *num, const double *den, double *sqrt_lib, double *sqrt_core,
+                                double *div_lib, double *div_core, unsigned char *verdict, hipStream_t st)
+{
+    if (n <= 0) return hipSuccess;
+    hipLaunchKernelGGL(range_math_probe, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, n, x, num, den, sqrt_lib, sqrt_core, div_lib,
+                       div_core, verdict);
+    return hipGetLastError();
+}
+#endif
 
 void evp_resident_geometry(int max_ni, int max_nj, int logw, int *gx, int *gy)
 {

@@ -58,7 +58,7 @@ TEST_EXPORTS = [
     "cice_evp_hip_debug_device_allocs", "cice_evp_hip_debug_cuload", "cice_evp_hip_debug_prof", "cice_evp_hip_debug_cgrid_prof", "cice_evp_hip_debug_cgres_prof", "cice_evp_hip_plan_build", "cice_evp_hip_halo_plan", "cice_evp_hip_seam_plan",
     "cice_evp_hip_peer_plan", "cice_evp_hip_peer_signs", "cice_evp_hip_center_plan", "cice_evp_hip_stress_plan",
     "cice_evp_hip_fold_split_plan", "cice_evp_hip_plan_flags", "cice_evp_hip_fold_images_plan", "cice_evp_hip_cgrid_fold_xplan",
-    "cice_evp_hip_cgrid_fold_xpeers", "cice_evp_hip_plan_dump", "cice_evp_hip_rim_plan",
+    "cice_evp_hip_cgrid_fold_xpeers", "cice_evp_hip_plan_dump", "cice_evp_hip_rim_plan", "cice_evp_hip_debug_range_math",
 ]
 # environment switches only the test build reads (cice_amd/csrc/evp_host.h: env_test): experiments, fault injection, routing
 # of on-device copies through the remote transports.  An EvpHip made while one of them is set uses the test build.
@@ -70,7 +70,7 @@ TEST_ENV = [
     "CICE_EVP_HIP_HALO_RIDE", "CICE_EVP_HIP_GATHER", "CICE_EVP_HIP_SIMPLE", "CICE_EVP_HIP_SELF_EXCHANGE", "CICE_EVP_HIP_FLAGS", "CICE_EVP_HIP_LEAN",
     "CICE_EVP_HIP_PREFETCH", "CICE_EVP_HIP_FAULT_REPLAY", "CICE_EVP_HIP_MARCH_BANDSEG", "CICE_EVP_HIP_CGRID_PROF",
     # A/B switches of kernels and transports (forced tile shapes, schedules the default never picks, the ring exchange's other forms)
-    "CICE_EVP_HIP_NO_OVERLAP", "CICE_EVP_HIP_TYB", "CICE_EVP_HIP_NOGRAPH", "CICE_EVP_HIP_GRAPH_RCCL", "CICE_EVP_HIP_RES_LOGW", "CICE_EVP_HIP_RES_COOP", "CICE_EVP_HIP_RES_LEAN", "CICE_EVP_HIP_RES_RIMU",
+    "CICE_EVP_HIP_NO_OVERLAP", "CICE_EVP_HIP_TYB", "CICE_EVP_HIP_NOGRAPH", "CICE_EVP_HIP_GRAPH_RCCL", "CICE_EVP_HIP_RES_LOGW", "CICE_EVP_HIP_RES_COOP", "CICE_EVP_HIP_RES_LEAN", "CICE_EVP_HIP_RES_RIMU", "CICE_EVP_HIP_RES_RANGE",
     "CICE_EVP_HIP_MARCH_EXT", "CICE_EVP_HIP_MARCH_DIRECT", "CICE_EVP_HIP_CGRID_FUSED", "CICE_EVP_HIP_CGRID_GEO",
     "CICE_EVP_HIP_CGRID_RES_SLEEP", "CICE_EVP_HIP_CGRID_RES_CULL", "CICE_EVP_HIP_CGRID_RES_DEBUG",
     "CICE_EVP_HIP_CGRID_STRIP", "CICE_EVP_HIP_CGRID_STRIP_SEG", "CICE_EVP_HIP_CGRID_STRIP_EDGE", "CICE_EVP_HIP_CGRID_STRIP_RIDE", "CICE_EVP_HIP_CGRID_STRIP_LEN", "CICE_EVP_HIP_CGRID_STRIP_ITEMS", "CICE_EVP_HIP_CGRID_STRIP_LAST",
@@ -952,3 +952,21 @@ def rim_plan(ni: int, nj: int, mask: np.ndarray, cyclic_ew: bool = False, cyclic
         _check(lib, rc if rc < 0 else -1, "(rim_plan)")
     return dict(perm=perm, uperm=uperm, cls=cls, n_lt=info[:, 0], n_lu=info[:, 1], nact=info[:, 2], nact_packed=info[:, 3],
                 ok=info[:, 4].astype(bool), gx=int(info[0, 5]), gy=int(info[0, 6]))
+
+
+def range_math(x: np.ndarray, num: np.ndarray, den: np.ndarray) -> dict:
+    """GPU, test build: sqrt(x) and num / den by the compiler's forms and by the range-proved cores of the lean resident loops
+    (cice_amd/csrc/evp_range_math.h), with each element's in-window verdicts (see the testing header)."""
+    lib = load_library(testing=True)
+    x, num, den = (np.ascontiguousarray(a, dtype=np.float64) for a in (x, num, den))
+    assert x.ndim == 1 and x.shape == num.shape == den.shape
+    n = x.size
+    out = {k: np.empty(n, dtype=np.float64) for k in ("sqrt_lib", "sqrt_core", "div_lib", "div_core")}
+    verdict = np.zeros(n, dtype=np.uint8)
+    dp = lambda a: a.ctypes.data_as(_f64p)
+    _check(lib, lib.cice_evp_hip_debug_range_math(C.c_int64(n), dp(x), dp(num), dp(den), dp(out["sqrt_lib"]), dp(out["sqrt_core"]),
+                                                  dp(out["div_lib"]), dp(out["div_core"]), verdict.ctypes.data_as(C.POINTER(C.c_uint8))),
+           "(debug_range_math)")
+    out["x_inside"] = (verdict & 1) != 0
+    out["q_inside"] = (verdict & 2) != 0
+    return out

@@ -112,6 +112,14 @@ int cice_evp_hip_debug_cuload(int32_t *out, int32_t n);
  * per tile and chunk of 64 cells 8 x uint64 = shader cycles in {ring poll, stress, barrier wait, momentum
  * step + publish, barrier wait}, arrival rank of the workgroup on its CU, hardware wave, active chunks.    */
 int cice_evp_hip_debug_prof(uint64_t *out, int32_t ntiles_max);
+/* (word 6 of a chunk's stamps = hardware wave | passes that took the compiler's sqrt / division << 8: a wave of the lean loops makes
+ * one stress pass and one or two momentum-step passes per subcycle, each on the range-proved cores or not -- csrc/evp_range_math.h) */
+/* The range-proved fp64 square root and division of the lean resident loops (csrc/evp_range_math.h: sqrt_core, div_core) beside the
+ * compiler's sqrt and /, element by element on the current device (no cice_evp_hip_init needed): n host values each of x, num, den
+ * in; sqrt(x) and num / den by both out; verdict[e] bit 0: x[e] is inside the window the kernels test, bit 1: num[e] and den[e]
+ * both are.  Where a bit is set the two forms must agree to the bit.                                                             */
+int cice_evp_hip_debug_range_math(int64_t n, const double *x, const double *num, const double *den, double *sqrt_lib, double *sqrt_core,
+                                  double *div_lib, double *div_core, uint8_t *verdict);
 /* C grid, one-launch kernel: 8 stamps per window of the last launch (CICE_EVP_HIP_CGRID_PROF=1 when the geometry was set):
  * shader-clock cycles at 0 start, 1 / 2 before / after the first workgroup barrier, 3 / 4 the second, 5 level C's arithmetic
  * done, 6 end; 7 = XCC id << 32 | HW_ID.  Returns the number of windows.  tools/cgrid_phases.py */

@@ -6,11 +6,14 @@ Compiles cice_amd/csrc/evp_resident2.hip for gfx950 with the build's flags to as
 subcycle loop (the backward branch that spans the most instructions) and counts what the loop holds, per subcycle: a loop
 that carries two subcycles per trip (the lean variant: one per record-buffer parity) is halved.
 
-  python tools/resident_isa_mix.py [--general | --lean] [--asm FILE.s]
+  python tools/resident_isa_mix.py [--general | --lean] [--asm FILE.s] [--blocks]
      --general   the general kernel <true, 3, 4, false, false> even where the lean one exists
      --lean      the lean variant on its first schedule (two workgroup barriers per subcycle) even where the rim-wave
                  schedule (RIMU) exists
      --asm       count an assembly file made earlier instead of compiling
+     --blocks    also list the loop's basic blocks that hold a square root or a division: size, seeds (v_rsq_f64, v_rcp_f64) and
+                 range handling (v_ldexp_f64, v_div_scale_f64, v_div_fixup_f64) -- a block with seeds and no range handling is a
+                 range-proved core (csrc/evp_range_math.h), a block of range handling behind the loop's other blocks its library path
 """
 from __future__ import annotations
 
@@ -111,6 +114,7 @@ def main() -> int:
     ap.add_argument("--general", action="store_true")
     ap.add_argument("--lean", action="store_true")
     ap.add_argument("--asm", default=None)
+    ap.add_argument("--blocks", action="store_true")
     a = ap.parse_args()
     if a.asm:
         lines = Path(a.asm).read_text().splitlines()
@@ -150,6 +154,27 @@ def main() -> int:
     print("most frequent non-fp64 mnemonics (per subcycle):")
     for m, k in sorted(((m, k) for m, k in sub.items() if classify(m) != "fp64"), key=lambda x: -x[1])[:16]:
         print(f"  {m:28s} {k / per_trip:7.1f}")
+    if a.blocks:
+        print("blocks of the loop that hold a square root or a division (label: instructions; seeds; range handling):")
+        n, label, cur, rows = 0, None, [], []
+        for kind, t in ins:
+            if kind == "label":
+                if cur:
+                    rows.append((label, cur))
+                label, cur = t, []
+            else:
+                if lo <= n < hi:
+                    cur.append(t.split()[0])
+                n += 1
+        if cur:
+            rows.append((label, cur))
+        lib = 0
+        for label, b in rows:
+            c = Counter(m[:-4] if m.endswith("_e32") or m.endswith("_e64") else m for m in b)
+            seeds, handling = c["v_rsq_f64"] + c["v_rcp_f64"], c["v_ldexp_f64"] + c["v_div_scale_f64"] + c["v_div_fixup_f64"]
+            if seeds + handling:
+                print(f"  {label:12s} {len(b):4d}   rsq {c['v_rsq_f64']} rcp {c['v_rcp_f64']}   ldexp {c['v_ldexp_f64']} div_scale {c['v_div_scale_f64']} "
+                      f"div_fixup {c['v_div_fixup_f64']}")
     return 0
 
 

@@ -1,7 +1,9 @@
 """Where a subcycle of the on-chip resident kernel goes, per wave: shader-cycle stamps collected under
 CICE_EVP_HIP_RES_PROF=1 (16 x 16 tiles).  Usage: python tools/resident_phases.py [gx1|gx3|p2] [ndte]
 (CICE_EVP_HIP_RES_RIMU=0: the lean loop's first schedule, two workgroup barriers per subcycle.  On the rim-wave schedule the third
-stamp is the wait for the interior waves' slots and the fifth the one barrier; for an interior wave the fourth is its momentum step)"""
+stamp is the wait for the interior waves' slots and the fifth the one barrier; for an interior wave the fourth is its momentum step.
+CICE_EVP_HIP_RES_RANGE=0: the lean loops' square roots and divisions always the compiler's; the last line of the first block says how
+many wave passes of the last call took them -- csrc/evp_range_math.h)"""
 import os, sys, pathlib
 R = str(pathlib.Path(__file__).resolve().parents[1]); sys.path[:0] = [R, R + "/tests", R + "/oracle"]
 os.environ["CICE_EVP_HIP_RES_PROF"] = "1"
@@ -20,7 +22,8 @@ core = evp.EvpHip(d, evp.make_params(scal, strict=True), geo["HTE"], geo["HTN"],
 core.upload(fields, tm, um)
 for _ in range(3): core.subcycle(ndte)
 core.sync()
-p = core.debug_prof().astype(np.float64)
+raw = core.debug_prof()
+p = raw.astype(np.float64)
 tt = core.timings()
 rimu = "edge U-cells in the rim wave" in core.describe_path()
 core.finalize()
@@ -41,6 +44,9 @@ def show(sel, what):
     print("     rim wave      " + "  ".join(f"{n} {v:6.0f}" for n, v in zip(names, late.mean(axis=0))))
     print("     other waves   " + "  ".join(f"{n} {v:6.0f}" for n, v in zip(names, early.mean(axis=0))))
 show(nact == 4, "full tiles")
+nlib = (raw[used][:, :, 6] >> 8).astype(np.int64)       # passes on the compiler's sqrt / division per wave (lean loops; else 0)
+print(f"  passes on the library path: {int(nlib.sum())} in {int(nact.sum())} ice-holding waves x {ndte} subcycles "
+      f"(a wave makes one stress pass and one or two momentum-step passes per subcycle); waves with any: {int((nlib > 0).sum())}")
 for r in range(3):
     show((nact == 4) & (rank == r), f"full tiles, arrival rank {r} on their CU")
 show((nact > 0) & (nact < 4), "partial tiles")
