@@ -383,7 +383,7 @@ int build_cg_frame(const cice_evp_hip_dims &d, const HaloPlan &P, const std::vec
 }
 
 int build_cg_march_fold(const cice_evp_hip_dims &d, const HaloPlan &P, int ex, int ey, long slots, int seg_min, int seg, int want_len,
-                        const CgGeoCheck *geo, CgMarchFoldPlan &F, std::string &why)
+                        const CgGeoCheck *geo, CgMarchFoldPlan &F, std::string &why, bool allow_ranks)
 {
     F = CgMarchFoldPlan();
     why.clear();
@@ -392,8 +392,17 @@ int build_cg_march_fold(const cice_evp_hip_dims &d, const HaloPlan &P, int ex, i
         why = "no tripole fold (the one-launch schedule marches such a grid)";
         return 0;
     }
-    if (!P.peers.empty() || !P.cg_peers.empty() || P.cg_split || P.fold_rows != 1) {
+    const bool ranks = !P.peers.empty() || !P.cg_peers.empty();
+    if (ranks && !allow_ranks) {
         why = "several ranks, or the fold rows not on this rank";
+        return 0;
+    }
+    if (!ranks && (P.cg_split || P.fold_rows != 1)) {
+        why = "several ranks, or the fold rows not on this rank";
+        return 0;
+    }
+    if (P.fold_rows == 2 && !P.cg_split) {
+        why = "the fold rows shared with other ranks without the C grid's fold exchange";
         return 0;
     }
     if (d.nx_block < 3 || d.ny_block < 3 || d.nx_global % 2) {
@@ -422,13 +431,33 @@ int build_cg_march_fold(const cice_evp_hip_dims &d, const HaloPlan &P, int ex, i
     auto at_fold = [&](int loc, int jg) { return jg > NY || (jg == NY && (tf || loc == 1 || loc == 3)); };
     // ---- the fold step's cells: destinations and sources of every location ----
     std::vector<uint8_t> foldcell(ncell, 0);
+    // (the lists the host runs: the C grid's own where the fold rows have several owners -- operands >= ncell are staging slots the
+    // exchange fills --, build_fold_list's where they are all here, none on a rank without them)
     FoldList L[4];
     for (int loc = 0; loc < 4; ++loc) {
-        build_fold_list(d, loc, L[loc]);
+        if (P.cg_split) L[loc] = P.cg_fold[loc];
+        else if (P.fold_rows == 1) build_fold_list(d, loc, L[loc]);
         for (size_t k = 0; k < L[loc].dst.size(); ++k)
-            for (int32_t c : {L[loc].dst[k], L[loc].a[k], L[loc].b[k]})
+            for (int32_t c : {L[loc].dst[k], L[loc].a[k], L[loc].b[k]}) {
                 if (c >= 0 && (size_t)c < ncell) foldcell[(size_t)c] = 1;
+                else if (c >= 0 && (size_t)c >= ncell + (size_t)P.cg_tail) return X.bad("a fold-list operand behind the staging slots", 0, 0, 0);
+            }
     }
+    // ---- the FRAME: what leaves the rank in an in-loop exchange -- ghost cells of the peers and, in the C grid's lists, the raw fold
+    // sources for their staging slots -- and what has a ghost image here.  The marched kernel has no pushes and runs beside the
+    // exchanges: none of these may be a zone cell (the fold sources come off a rectangle's top with the fold step's own cells) ----
+    std::vector<uint8_t> frame(ncell, 0);
+    for (const std::vector<HaloPeer> *pp : {&P.peers, &P.cg_peers})
+        for (const HaloPeer &p : *pp)
+            for (int32_t c : p.send_src)
+                if (c >= 0 && (size_t)c < ncell && !frame[(size_t)c]) {
+                    frame[(size_t)c] = 1;
+                    foldcell[(size_t)c] = 1;
+                    F.sent.push_back(c);
+                }
+    std::sort(F.sent.begin(), F.sent.end());
+    for (int32_t c : P.local_src)
+        if (c >= 0 && (size_t)c < ncell) frame[(size_t)c] = 1;
     // ---- the rectangles, cut from the top until the fold rule holds ----
     // (ghost cells the fold step fills -- the row beyond the fold, on a T-fold the top physical row too -- are no images: their sources
     // are fold cells, which come off the rectangle's top below instead of costing a block its rectangle.  A rectangle narrower than a
@@ -502,6 +531,17 @@ int build_cg_march_fold(const cice_evp_hip_dims &d, const HaloPlan &P, int ex, i
                 if (!(f & EVP_CGS_REST)) return X.bad("a cell of the fold step is not a REST cell", b, i, j);
                 if (!(f & level_of_loc[loc]) || !(f & EVP_CGS_AVG) || !(f & EVP_CGS_S)) return X.bad("a cell of the fold step is not evaluated at its level", b, i, j);
             }
+    // (every sent cell runs the level that produces the field it is sent for: a REST cell runs them all; so does a cell with an image)
+    constexpr int every_level = EVP_CGS_REST | EVP_CGS_S | EVP_CGS_T | EVP_CGS_U | EVP_CGS_AVG;
+    for (size_t c = 0; c < ncell; ++c) {
+        if (!frame[c]) continue;
+        int b, i, j;
+        X.cell_of(c, b, i, j);
+        if (!X.interior(b, i, j)) return X.bad("a sent cell or the source of a ghost image is no interior cell", b, i, j);
+        if ((F.cells[c] & every_level) != every_level)
+            return X.bad("a cell another rank receives, or one with a ghost image, is not a REST cell evaluated at every level", b, i, j);
+        ++F.frame_cells;
+    }
     for (int b = 0; b < d.nblocks; ++b)
         for (int j = 1; j <= nyb; ++j)
             for (int i = 1; i <= nxb; ++i) {

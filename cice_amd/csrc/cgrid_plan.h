@@ -82,9 +82,9 @@ void plan_strip_zones(const cice_evp_hip_dims &d, const HaloPlan &P, int ex, int
 
 // ---- the marched kernel beside list-driven kernels: a rank's interior cells split in two ----
 // The ZONE -- the cells cg_strip's items own -- and the REST, every other interior cell, which list-driven variants of the un-fused or
-// fused kernels advance (evp_cgrid.hip).  Two schedules split a rank this way: several ranks (build_cg_frame; the rest is the FRAME
-// around each block's rectangle) and a tripole / tripoleT grid on one rank (build_cg_march_fold; the rest is the band under the fold and
-// the block edges).  A rest cell reads intermediates of its neighbours, so each level also runs on the zone cells the next level reads
+// fused kernels advance (evp_cgrid.hip).  Three schedules split a rank this way: several ranks (build_cg_frame; the rest is the FRAME
+// around each block's rectangle), a tripole / tripoleT grid on one rank (build_cg_march_fold; the rest is the band under the fold and
+// the block edges) and such a grid on several ranks (build_cg_march_fold again; the rest holds band and frame).  A rest cell reads intermediates of its neighbours, so each level also runs on the zone cells the next level reads
 // ("dilation"; a zone cell evaluated for a rest cell's sake stores to scratch arrays only).  Each plan is a table of reads -- level, the
 // level that produces what it reads, offsets, in cgrid_plan.cpp -- which one helper walks to mark the cells of every level and walks
 // again to check them.  Level T (stressC_T) also runs on the reference's extra T row and column (ghost cells i = ihi + 1, j = jhi + 1,
@@ -112,8 +112,8 @@ struct CgSplitPlan {
 using CgFramePlan = CgSplitPlan;
 int build_cg_frame(const cice_evp_hip_dims &d, const HaloPlan &P, const std::vector<int32_t> &items, CgFramePlan &F, std::string &why);
 
-// ---- a tripole / tripoleT grid on one rank (evp_host_cgrid.cpp: "marched zone + fold band"): the five un-fused phase kernels, cg_band_*,
-// with the fold steps of the five-phase schedule ----
+// ---- a tripole / tripoleT grid on one rank (evp_host_cgrid.cpp: "marched zone + fold band") or on several ("... + frame"): the five
+// un-fused phase kernels, cg_band_*, with the fold steps -- and across ranks the exchanges -- of the five-phase schedule ----
 // The zone: strip_zones' rectangles, cut from the top in the blocks at the fold until the fold rule holds for every item.  The fold rule
 // (what cg_strip forms, by field location and row, counted from its loop; jb = an item's last owned row):
 //   * nothing is FORMED at a point on the fold or beyond it.  The kernel forms, up to row jb + 1, the face -> corner and face <-> face
@@ -162,19 +162,26 @@ struct CgMarchFoldPlan : CgSplitPlan {
     std::vector<StripZone> zones;
     int band_rows = 0;                     // rows from the zone's top row (exclusive) to NY, on the blocks at the fold (the most)
     int seg = 0, lengths = 0;              // rows per segment; 1: the items own lanes >= 3 (the kernel forms six of the eight lengths)
+    std::vector<int32_t> sent;             // several ranks: the interior cells another rank receives in an in-loop exchange, ascending
+    long frame_cells = 0;                  // REST cells that are sent or have a ghost image on this rank (the FRAME)
 };
 // geo (may be null: everything holds): what the caller's static arrays allow for the rectangle z -- 0 an identity fails on a cell the
 // kernel would derive it for (a window row comes off the top and the question is asked again), 1 the 15 derived arrays hold, 3 the six
 // formed lengths hold as well.  The items own lanes >= 3 (lengths = 1) when every rectangle answers 3 and want_len != 0.
-// Declines (0) without a fold, on several ranks or with split fold rows, and when no rectangle is left under the band.  Its own
-// invariants: every fold-list source and destination that is an interior cell is a REST cell, evaluated at its level; no item forms a
-// value on the fold.
+// Declines (0) without a fold and when no rectangle is left under the band.  Its own invariants: every fold-list source and destination
+// that is an interior cell is a REST cell, evaluated at its level (an operand >= the rank's cells is a staging slot and needs none); no
+// item forms a value on the fold.
+// Several ranks ("marched zone + fold band + frame"; allow_ranks = false declines them, the one-rank question): the same plan on any
+// rank layout the five phases take.  The fold lists are the host's -- HaloPlan::cg_fold where the fold rows have several owners,
+// build_fold_list's where they are all here, none on a rank without them (zone + frame, band_rows = 0) -- and the REST also holds the
+// FRAME: every cell a peer receives (HaloPlan::peers and cg_peers send lists, the raw fold sources for other ranks' staging slots
+// included) and every cell with a ghost image here.  One more invariant: each of those is a REST cell evaluated at every level.
 struct CgGeoCheck {
     virtual int operator()(const StripZone &z) const = 0;
     virtual ~CgGeoCheck() {}
 };
 int build_cg_march_fold(const cice_evp_hip_dims &d, const HaloPlan &P, int ex, int ey, long slots, int seg_min, int seg, int want_len,
-                        const CgGeoCheck *geo, CgMarchFoldPlan &F, std::string &why);
+                        const CgGeoCheck *geo, CgMarchFoldPlan &F, std::string &why, bool allow_ranks = true);
 
 // The hand-off graph of the resident windows (tiles / tab as build_window_table(..., 16, 16, ., extra = 1) or
 // build_fold_window_table made them): window w READS window p when it polls a cell p owns.  A window cannot start subcycle j + 1

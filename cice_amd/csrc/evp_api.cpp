@@ -217,16 +217,18 @@ int cice_evp_hip_cgrid_frame_plan(const cice_evp_hip_dims *dims, int32_t ex, int
     return 0;
 }
 int cice_evp_hip_cgrid_march_fold_plan(const cice_evp_hip_dims *dims, int32_t ex, int32_t ey, int32_t slots, int32_t seg_min, int32_t seg, int32_t len,
-                                       int64_t *info11, uint8_t *cells, int32_t *wg, int32_t wg_cap, int32_t *items6, int32_t items_cap)
+                                       int64_t *info11, uint8_t *cells, int32_t *wg, int32_t wg_cap, int32_t *items6, int32_t items_cap,
+                                       int32_t ranks, int64_t *ranks3, int32_t *sent, int32_t sent_cap)
 {
     if (!dims || !info11) return fail(-1, "bad argument");
     HaloPlan P;
     if (!build_halo_plan(*dims, P)) return fail(-3, "halo plan: %s", P.error.c_str());
     CgMarchFoldPlan F;
     std::string why;
-    const int rc = build_cg_march_fold(*dims, P, ex, ey, slots, seg_min, seg, len, nullptr, F, why);
+    const int rc = build_cg_march_fold(*dims, P, ex, ey, slots, seg_min, seg, len, nullptr, F, why, ranks != 0);
     if (rc < 0) return fail(-5, "%s", why.c_str());
     for (int k = 0; k < 11; ++k) info11[k] = 0;
+    if (ranks3) { ranks3[0] = (int64_t)F.sent.size(); ranks3[1] = F.frame_cells; ranks3[2] = P.cg_split ? P.cg_tail : 0; }
     if (rc == 0) {                                            // declined: the reason is the last error's text
         g_err = why;
         return 1;
@@ -244,6 +246,10 @@ int cice_evp_hip_cgrid_march_fold_plan(const cice_evp_hip_dims *dims, int32_t ex
     if (items6) {
         if ((size_t)items_cap * 6 < F.items.size()) return fail(-1, "room for %d items", items_cap);
         std::copy(F.items.begin(), F.items.end(), items6);
+    }
+    if (sent) {
+        if ((size_t)sent_cap < F.sent.size()) return fail(-1, "room for %d sent cells", sent_cap);
+        std::copy(F.sent.begin(), F.sent.end(), sent);
     }
     return 0;
 }

@@ -32,13 +32,14 @@ struct Ran {
     int one = 0;                 // subcycles run as one launch each (cg_one)
     int march = 0;               // ... as the marched kernel beside the fused chain on the frame (several ranks)
     int mfold = 0;               // ... as the marched kernel beside the five phases on the fold band (tripole grids, one rank)
+    int mfold_ranks = 0;         // ... the same with the frame in the rest and the five phases' exchanges (tripole grids, several ranks)
 };
 // Everything a captured graph bakes in that can change between calls: pointers (in_alt) and kernel / template choices
 struct GraphKey {
     int ndte, avg_strength;
     unsigned in_alt;
-    bool first, fused, fast, one, geo, march, mfold, mfold_serial, mfold_sync;
-    auto tie() const { return std::tie(ndte, avg_strength, in_alt, first, fused, fast, one, geo, march, mfold, mfold_serial, mfold_sync); }
+    bool first, fused, fast, one, geo, march, mfold, mfold_serial, mfold_sync, mfold_ranks;
+    auto tie() const { return std::tie(ndte, avg_strength, in_alt, first, fused, fast, one, geo, march, mfold, mfold_serial, mfold_sync, mfold_ranks); }
     bool operator<(const GraphKey &o) const { return tie() < o.tie(); }
 };
 // The cells the marched kernel does not own, as the kernels beside it want them: per-cell bits, per level the workgroups to launch,
@@ -85,18 +86,20 @@ struct CGridState {
     CellLists fr;
     // tripole / tripoleT on one rank: the marched kernel on the rectangles under the fold band beside list-driven variants of the five
     // phase kernels on every other interior cell (enqueue_march_fold: "marched zone + fold band"; cgrid_plan.cpp: build_cg_march_fold).
+    // On several ranks the same with the frame in the rest and the five phases' exchanges at their points ("... + frame").
     // The items live in `one` (items, nitems, strip_*)
     struct MarchFold {
         CellLists rest;                      // cells: the EVP_CGS_* bits; five phases; scr: shearU, etax2T, stresspT, stressmT, stress12U; ncells: REST cells
         uint8_t *gmask = nullptr;            // the land masks as bits on the rows the marched kernel derives its geometry on
         int band_rows = 0;
+        long frame_cells = 0;                // several ranks: REST cells another rank receives or that have a ghost image here
         bool by_size = false;                // cg_strip's size rule holds for the zone
         bool synced = false;                 // the second allocations of the five ping-pong arrays agree with the current ones on every cell no
                                              // subcycle writes (false after an upload and after any call another schedule ran)
         std::string why;                     // why there is no plan on this rank
     } mf;
     // the marched kernel's stream beside S.stream, forked from and joined to it in every subcycle.  One per geometry: zone + frame
-    // needs several ranks and no fold, zone + fold band a fold and one rank
+    // needs several ranks and no fold, zone + fold band (+ frame) a fold
     struct Side {
         hipStream_t st = nullptr;
         hipEvent_t fork = nullptr, join = nullptr;
@@ -153,6 +156,7 @@ struct CGridState {
     int t_one = 0;               // subcycles of the last call that ran as one launch each (cg_one)
     int t_march = 0;             // ... as the marched kernel beside the fused chain on the frame (several ranks)
     int t_mfold = 0;             // ... as the marched kernel beside the five phases on the fold band (tripole grids, one rank)
+    int t_mfold_ranks = 0;       // ... as "marched zone + fold band + frame" (tripole grids, several ranks)
     double *tarear = nullptr, *post[5] = {};   // deformationsC_T: 1/tarea (static), divu shear vort rdg_conv rdg_shear
     // preparation phase on the device (cice_evp_hip_cgrid_prep)
     struct Prep {
@@ -192,6 +196,7 @@ static bool fused_switch() { return env_on(env_test("CICE_EVP_HIP_CGRID_FUSED"),
 static bool geo_switch() { return env_on(env_test("CICE_EVP_HIP_CGRID_GEO"), true); }
 static bool march_ranks_switch() { return env_on(env_test("CICE_EVP_HIP_CGRID_MARCH_RANKS"), true); }
 static int march_fold_switch() { return env_int(env_test("CICE_EVP_HIP_CGRID_MARCH_FOLD"), ENV_UNSET); }
+static int march_fold_ranks_switch() { return env_int(env_test("CICE_EVP_HIP_CGRID_MARCH_FOLD_RANKS"), ENV_UNSET); }
 static bool march_fold_serial() { return env_on(env_test("CICE_EVP_HIP_CGRID_MARCH_FOLD_SERIAL"), false); }
 static bool strip_last_on() { return env_on(env_test("CICE_EVP_HIP_CGRID_STRIP_LAST"), true); }
 static bool strip_ride_on() { return env_on(env_test("CICE_EVP_HIP_CGRID_STRIP_RIDE"), true); }
@@ -341,6 +346,8 @@ static int enqueue_phases(const EvpCgrid &A, int ndte, bool first)
     return 0;
 }
 
+// length of an exchanged array: the rank's cells and, where the fold rows have several owners, the staging slots of the fold exchange
+static size_t field_len() { return S.n + (fold_exchange() ? (size_t)S.plan.cg_tail : 0); }
 // The current and the other allocation of PP_FIELDS as a schedule sees them while it enqueues: swap() per subcycle, `swapped` for Ran
 struct PingPong {
     double *cur[5], *alt[5];
@@ -372,10 +379,11 @@ struct PingPong {
     }
     // bring the second allocations into line: both then agree on the cells no later subcycle writes (no ice; ghost cells nothing
     // is copied into)
+    // (with the fold exchange both allocations carry the staging slots behind the cells: copied along)
     int sync(unsigned which) const
     {
         for (int q = 0; q < 5; ++q)
-            if (which >> q & 1u) HIPC(hipMemcpyAsync(alt[q], cur[q], S.n * sizeof(double), hipMemcpyDeviceToDevice, S.stream));
+            if (which >> q & 1u) HIPC(hipMemcpyAsync(alt[q], cur[q], field_len() * sizeof(double), hipMemcpyDeviceToDevice, S.stream));
         return 0;
     }
 };
@@ -499,10 +507,24 @@ static int march_fold_wanted()         // 0 off, 1 forced on, 2 by the size rule
     if (forced != ENV_UNSET) return forced ? 1 : 0;
     return MARCH_FOLD_DEFAULT ? 2 : 0;
 }
+// Several ranks ("marched zone + fold band + frame"): the same split with the frame in the REST and the five phases' exchanges at
+// their points, so a rank without a zone keeps the five full phases and the ranks need not agree on anything.  Each rank applies the
+// size rule to its own zone.  CICE_EVP_HIP_CGRID_MARCH_FOLD_RANKS=0 / 1 (test build) switches it off / on wherever a zone forms;
+// ..._MARCH_FOLD=1 alone forces the one-rank schedule only (across ranks it leaves the size rule in charge), ..._MARCH_FOLD=0 and
+// CICE_EVP_HIP_CGRID_ONE=0 switch both off.
+static constexpr bool MARCH_FOLD_RANKS_DEFAULT = true;      // measured (two-process rehearsals): profiles/r10_cgrid_march_tripole_ranks.txt
+static int march_fold_ranks_wanted()   // 0 off, 1 forced on, 2 by the size rule
+{
+    if (!one_switch() || march_fold_switch() == 0) return 0;
+    const int forced = march_fold_ranks_switch();
+    if (forced != ENV_UNSET) return forced ? 1 : 0;
+    return MARCH_FOLD_RANKS_DEFAULT ? 2 : 0;
+}
+static int march_fold_wanted_here() { return remote() ? march_fold_ranks_wanted() : march_fold_wanted(); }
 static bool march_fold()
 {
-    if (!CG.mf.rest.cells || CG.one.nitems <= 0 || !CG.tripole || remote() || CG.avg_strength) return false;
-    const int want = march_fold_wanted();
+    if (!CG.mf.rest.cells || CG.one.nitems <= 0 || !CG.tripole || CG.avg_strength) return false;
+    const int want = march_fold_wanted_here();
     return want == 1 || (want == 2 && CG.mf.by_size);
 }
 static int enqueue_phases(const EvpCgrid &A, int ndte, bool first);
@@ -556,12 +578,20 @@ static int enqueue_march_fold(EvpCgrid A, int ndte, bool first, bool sync, Ran &
             evp_launch_cgrid_strip(A, Z.T, Z.Z, nullptr, fast, last, CG.side.st);
             HIPC(hipEventRecord(CG.side.join, CG.side.st));
         }
+        // several ranks: the exchanges of enqueue_phases at its points, in its order and pairing -- a peer on the five full phases
+        // matches them --, each ahead of the fold step that follows it there, on this subcycle's allocations (A is aimed at them).
+        // They read REST cells only (the plan's invariant) and write ghost cells and staging slots: the marched kernel runs beside them
+        XCHG(A.f[CF_SHEARU], A.f[CF_SHEARU]);
         fold({{A.f[CF_SHEARU], 1, false}});
         evp_launch_cgrid_band(A, B, 1, S.stream);
+        XCHG(A.f[CF_ETA], A.f[CF_ZETA]);
+        XCHG(A.f[CF_SP], A.f[CF_SM]);
         fold({{A.f[CF_ZETA], 0, false}, {A.f[CF_ETA], 0, false}, {A.f[CF_SP], 0, false}, {A.f[CF_SM], 0, false}});
         evp_launch_cgrid_band(A, B, 2, S.stream);
+        XCHG(A.f[CF_S12U], A.f[CF_S12U]);
         fold({{A.f[CF_S12U], 1, false}});
         evp_launch_cgrid_band(A, B, 3, S.stream);
+        XCHG(A.f[CF_UE], A.f[CF_VN]);
         fold({{A.f[CF_UE], 2, true}, {A.f[CF_VN], 3, true}});
         // the averages read the new velocities of both sets: the two meet again before them.  In the call's last subcycle over the
         // whole domain: the caller gets uvelN, vvelE, uvel, vvel of every cell
@@ -569,9 +599,11 @@ static int enqueue_march_fold(EvpCgrid A, int ndte, bool first, bool sync, Ran &
         // (and before a last subcycle that runs as the five full phases, which read them on every cell)
         if (last || (k == ndte - 2 && !strip_last)) evp_launch_cgrid_phase(A, 4, 1, S.stream);
         else evp_launch_cgrid_band(A, B, 4, S.stream);
+        XCHG(A.f[CF_UN], A.f[CF_VE]);
+        XCHG(A.f[CF_UU], A.f[CF_VU]);
         fold({{A.f[CF_UN], 3, true}, {A.f[CF_VE], 2, true}, {A.f[CF_UU], 1, true}, {A.f[CF_VU], 1, true}});
         P.swap(PP_ALL);
-        ++ran.mfold;
+        ++(remote() ? ran.mfold_ranks : ran.mfold);
     }
     ran.swapped = P.swapped;
     return 0;
@@ -738,7 +770,7 @@ static int zeros(double *&p, size_t n) { return CG.mem.alloc(p, n, true); }     
 static int need_alt()
 {
     for (int q = 0; q < 4; ++q)
-        if (!CG.alt[q] && zeros(CG.alt[q], S.n)) return -1;
+        if (!CG.alt[q] && zeros(CG.alt[q], field_len())) return -1;
     return 0;
 }
 static int upload_items(const std::vector<int32_t> &items, int ex, int ey, int lengths, int seg, long cells)
@@ -896,20 +928,17 @@ static int build_one_tables(const double *const *static23)
     return 0;
 }
 
-// ---- tripole / tripoleT on one rank: what the marched kernel needs under the fold band, and the lists of the five phase kernels
-// that advance every other interior cell (cgrid_plan.cpp: build_cg_march_fold plans and checks; enqueue_march_fold runs it).  Built
-// only where the schedule can be used; a rank where no rectangle survives keeps today's schedule, with the reason in CG.mf.why.
+// ---- tripole / tripoleT, one rank or several: what the marched kernel needs under the fold band, and the lists of the five phase
+// kernels that advance every other interior cell -- across ranks the frame too (cgrid_plan.cpp: build_cg_march_fold plans and
+// checks; enqueue_march_fold runs it).  Built only where the schedule can be used; a rank where no rectangle survives keeps the five
+// full phases, with the reason in CG.mf.why.
 static_assert(STRIP_AHEAD == EVP_CGSTRIP_AHEAD, "cgrid_plan.h and evp_device.h must agree on how far the marched kernel's loop runs ahead");
 static int build_march_fold_tables(const double *const *static23)
 {
     const HaloPlan &P = S.plan;
     CGridState::MarchFold &Q = CG.mf;
-    const int want = march_fold_wanted();
+    const int want = march_fold_wanted_here();
     if (!want) return 0;
-    if (!P.peers.empty() || !P.cg_peers.empty() || P.cg_split || P.fold_rows != 1) {
-        Q.why = "several ranks, or the fold rows not on this rank";
-        return 0;
-    }
     if (!strip_offsets_fit()) {
         Q.why = "the marched kernel's 32-bit offsets do not span the tables";
         return 0;
@@ -955,6 +984,7 @@ static int build_march_fold_tables(const double *const *static23)
     if (CG.mem.upload(Q.gmask, gm) || upload_cell_lists(Q.rest, FP.cells, FP.wg, 5, 5, FP.rest_cells)) return -1;
     if (upload_items(FP.items, EX, EY, FP.lengths, FP.seg, FP.zone_cells)) return -1;
     Q.band_rows = FP.band_rows;
+    Q.frame_cells = FP.frame_cells;
     return 0;
 }
 
@@ -1237,10 +1267,19 @@ int finish_upload(int32_t visc_method);
 
 std::string cgrid_schedule()
 {
-    char buf[200];
+    char buf[400];
     if (CG.geo && CG.uploaded && march_ranks()) {
         std::snprintf(buf, sizeof buf, "C grid: zone marched + frame (%ld cells in %d items beside %ld frame cells, fused chain and its exchanges)",
                       CG.one.strip_cells, CG.one.nitems, CG.fr.ncells);
+        return buf;
+    }
+    if (CG.geo && CG.uploaded && march_fold() && remote()) {
+        char fx[120] = "";
+        if (fold_exchange())
+            std::snprintf(fx, sizeof fx, " + fold exchange, fold rows on %d ranks (%d staging slots here)", S.plan.cg_fold_ranks, S.plan.cg_tail);
+        std::snprintf(buf, sizeof buf, "C grid: marched zone + fold band + frame, %d rows (%ld cells in %d items beside %ld rest cells, %ld of them frame "
+                      "cells, five phases with their exchanges and fold steps)%s", CG.mf.band_rows, CG.one.strip_cells, CG.one.nitems, CG.mf.rest.ncells,
+                      CG.mf.frame_cells, fx);
         return buf;
     }
     if (CG.geo && CG.uploaded && march_fold()) {
@@ -1248,9 +1287,9 @@ std::string cgrid_schedule()
                       "five phases and their fold steps)", CG.mf.band_rows, CG.one.strip_cells, CG.one.nitems, CG.mf.rest.ncells);
         return buf;
     }
-    if (CG.geo && CG.tripole && march_fold_wanted() == 1) {
+    if (CG.geo && CG.tripole && march_fold_wanted() == 1 && !(remote() && march_fold())) {
         // asked for and not in use: say why
-        const char *w = remote() ? "several ranks" : !CG.mf.rest.cells ? CG.mf.why.c_str() : (CG.uploaded && CG.avg_strength) ? "visc_method = avg_strength" : "";
+        const char *w = (remote() && march_fold_ranks_wanted() != 1) ? "several ranks" : !CG.mf.rest.cells ? CG.mf.why.c_str() : (CG.uploaded && CG.avg_strength) ? "visc_method = avg_strength" : "";
         if (*w) {
             std::snprintf(buf, sizeof buf, "C grid: five phases + fold steps (marched zone + fold band not in use: %s)", w);
             return buf;
@@ -1291,7 +1330,7 @@ int cice_evp_hip_cgrid_set_geometry(const double *const *static23)
         CG.g[k] = CG.gslab + (size_t)k * S.n;
         if (h2d(CG.g[k], static23[k])) return -1;
     }
-    if (zeros(CG.strengthU, S.n) || zeros(CG.alt[4], S.n) || zeros(CG.fac[0], S.n) || zeros(CG.fac[1], S.n)) return -1;
+    if (zeros(CG.strengthU, S.n) || zeros(CG.alt[4], nf) || zeros(CG.fac[0], S.n) || zeros(CG.fac[1], S.n)) return -1;
     if (remote() && zeros(CG.umaskd, nf)) return -1;
     if (CG.mem.alloc(CG.d_flags, 1) || CG.mem.alloc(CG.mask, S.n) || CG.mem.alloc(CG.mask4, 4 * S.n)) return -1;
     // ghost images: for every interior cell the ghost cells of this rank that mirror it (what ice_HaloUpdate copies)
@@ -1473,6 +1512,7 @@ int cice_evp_hip_cgrid_subcycle(int32_t ndte)
         key.first = CG.first; key.fused = fused; key.fast = CG.fast;
         key.one = fused && one_launch(); key.geo = geo_derived(); key.march = fused && march_ranks();
         key.mfold = mfold; key.mfold_serial = mfold && march_fold_serial(); key.mfold_sync = mf_sync;
+        key.mfold_ranks = mfold && remote();
         auto it = CG.graphs.find(key);
         if (it == CG.graphs.end()) {
             hipGraph_t gr = nullptr;
@@ -1500,6 +1540,7 @@ int cice_evp_hip_cgrid_subcycle(int32_t ndte)
     CG.t_one = ran.one;
     CG.t_march = ran.march;
     CG.t_mfold = ran.mfold;
+    CG.t_mfold_ranks = ran.mfold_ranks;
     CG.res.last_nsub = nres;
     CG.first = false;
     CG.t_nsub = ndte;
@@ -1925,6 +1966,11 @@ int cice_evp_hip_cgrid_timings(double *out, int32_t n)
         out[20] = (double)CG.t_mfold;                 // subcycles of the last call that ran as "marched zone + fold band" (tripole grids, one rank)
         out[21] = (double)CG.mf.band_rows;            // ... rows from the zone's top row to the fold (0: no such plan here)
         out[22] = (double)CG.mf.rest.ncells;               // ... and the cells the five list-driven phase kernels advance
+    }
+    if (n >= 26) {
+        out[23] = (double)CG.t_mfold_ranks;           // subcycles of the last call that ran as "marched zone + fold band + frame" (tripole grids, several ranks)
+        out[24] = (double)CG.mf.frame_cells;          // ... the frame cells among the rest cells (sent to another rank, or with a ghost image here)
+        out[25] = (CG.t_mfold_ranks > 0 && fold_exchange()) ? 1.0 : 0.0;   // ... 1: with the fold exchange (the fold rows on several ranks)
     }
     return 0;
 }

@@ -74,7 +74,7 @@ TEST_ENV = [
     "CICE_EVP_HIP_MARCH_EXT", "CICE_EVP_HIP_MARCH_DIRECT", "CICE_EVP_HIP_CGRID_FUSED", "CICE_EVP_HIP_CGRID_GEO",
     "CICE_EVP_HIP_CGRID_RES_SLEEP", "CICE_EVP_HIP_CGRID_RES_CULL", "CICE_EVP_HIP_CGRID_RES_DEBUG",
     "CICE_EVP_HIP_CGRID_STRIP", "CICE_EVP_HIP_CGRID_STRIP_SEG", "CICE_EVP_HIP_CGRID_STRIP_EDGE", "CICE_EVP_HIP_CGRID_STRIP_RIDE", "CICE_EVP_HIP_CGRID_STRIP_LEN", "CICE_EVP_HIP_CGRID_STRIP_ITEMS", "CICE_EVP_HIP_CGRID_STRIP_LAST",
-    "CICE_EVP_HIP_CGRID_MARCH_RESERVE", "CICE_EVP_HIP_CGRID_MARCH_RANKS", "CICE_EVP_HIP_CGRID_MARCH_FOLD", "CICE_EVP_HIP_CGRID_MARCH_FOLD_SERIAL",
+    "CICE_EVP_HIP_CGRID_MARCH_RESERVE", "CICE_EVP_HIP_CGRID_MARCH_RANKS", "CICE_EVP_HIP_CGRID_MARCH_FOLD", "CICE_EVP_HIP_CGRID_MARCH_FOLD_SERIAL", "CICE_EVP_HIP_CGRID_MARCH_FOLD_RANKS",
 ]
 # C-grid subcycle (cice_evp_hip_cgrid_*): order of the pointer tables, see include/cice_evp_hip.h
 CGRID_FIELDS = ["uvelE", "vvelE", "uvelN", "vvelN", "uvel", "vvel", "stresspT", "stressmT", "stress12T", "stress12U",
@@ -330,15 +330,19 @@ def cgrid_frame_plan(dims: "Dims", ex=32, ey=8, lo0=3, slots=2048, seg_min=8, se
                 wg=[wg[:n[0]], wg[n[0]:n[0] + n[1]], wg[n[0] + n[1]:n[0] + n[1] + n[2]]])
 
 
-def cgrid_march_fold_plan(dims: "Dims", ex=32, ey=8, slots=2048, seg_min=0, seg=0, lengths=1):
+def cgrid_march_fold_plan(dims: "Dims", ex=32, ey=8, slots=2048, seg_min=0, seg=0, lengths=1, ranks=False):
     """Host only: how one rank shares a tripole / tripoleT grid between the marched C-grid kernel (zone) and the list-driven phase
     kernels (the band under the fold and the block edges; see the testing header).  Where the schedule does not apply: a dict with
-    `declined` = the reason and nothing else."""
+    `declined` = the reason and nothing else.  ranks=True: the plan of the rank `dims` describes on any rank layout (the rest then
+    holds the frame too); the dict also has `sent` (offsets of the cells other ranks receive), `frame_cells`, `staging_slots`."""
     lib = load_library(testing=True)
     info = np.zeros(11, dtype=np.int64)
+    r3 = np.zeros(3, dtype=np.int64)
     ip = info.ctypes.data_as(C.POINTER(C.c_int64))
+    rp = r3.ctypes.data_as(C.POINTER(C.c_int64))
     a = (C.byref(dims), C.c_int32(ex), C.c_int32(ey), C.c_int32(slots), C.c_int32(seg_min), C.c_int32(seg), C.c_int32(lengths), ip)
-    rc = lib.cice_evp_hip_cgrid_march_fold_plan(*a, None, None, C.c_int32(0), None, C.c_int32(0))
+    rk = C.c_int32(1 if ranks else 0)
+    rc = lib.cice_evp_hip_cgrid_march_fold_plan(*a, None, None, C.c_int32(0), None, C.c_int32(0), rk, rp, None, C.c_int32(0))
     if rc == 1:
         buf = C.create_string_buffer(1024)
         lib.cice_evp_hip_last_error(buf, 1024)
@@ -348,12 +352,16 @@ def cgrid_march_fold_plan(dims: "Dims", ex=32, ey=8, slots=2048, seg_min=0, seg=
     n = [int(v) for v in info[2:7]]
     wg = np.zeros(max(sum(n), 1), dtype=np.int32)
     items = np.zeros((max(int(info[7]), 1), 6), dtype=np.int32)
+    sent = np.zeros(max(int(r3[0]), 1), dtype=np.int32)
     _check(lib, lib.cice_evp_hip_cgrid_march_fold_plan(*a, cells.ctypes.data_as(C.POINTER(C.c_uint8)), _ip(wg), C.c_int32(len(wg)), _ip(items),
-                                                       C.c_int32(len(items))), "(cgrid_march_fold_plan)")
+                                                       C.c_int32(len(items)), rk, rp, _ip(sent), C.c_int32(len(sent))), "(cgrid_march_fold_plan)")
     cut = np.cumsum([0] + n)
-    return dict(zone_cells=int(info[0]), rest_cells=int(info[1]), cells=cells, items=items[:int(info[7])],
+    plan = dict(zone_cells=int(info[0]), rest_cells=int(info[1]), cells=cells, items=items[:int(info[7])],
                 wg=[wg[cut[k]:cut[k + 1]] for k in range(5)], fold_band_rows=int(info[8]), segment_rows=int(info[9]),
                 lengths=bool(info[10]))
+    if ranks:
+        plan.update(sent=sent[:int(r3[0])], frame_cells=int(r3[1]), staging_slots=int(r3[2]))
+    return plan
 
 
 def stream_probe(ncells: int) -> float:
@@ -621,8 +629,8 @@ class EvpHip:
         _check(self.lib, self.lib.cice_evp_hip_cgrid_sync(), "(dyn_evp_hip_cgrid_sync)")
 
     def cgrid_timings(self):
-        out = np.zeros(23)
-        _check(self.lib, self.lib.cice_evp_hip_cgrid_timings(_dp(out), C.c_int32(23)), "(dyn_evp_hip_cgrid_timings)")
+        out = np.zeros(26)
+        _check(self.lib, self.lib.cice_evp_hip_cgrid_timings(_dp(out), C.c_int32(26)), "(dyn_evp_hip_cgrid_timings)")
         return dict(loop_ms=float(out[0]), nsub=int(out[1]), prep_ms=float(out[2]), one_launch_subcycles=int(out[3]),
                     geometry_derived=bool(out[4]), resident_subcycles=int(out[5]), resident_probe_ms=float(out[6]),
                     resident_fallbacks=int(out[7]), resident_windows_with_ice=int(out[8]), resident_windows=int(out[9]),
@@ -630,7 +638,8 @@ class EvpHip:
                     marched_segment_rows=int(out[13]), marched_lengths_derived=bool(out[14]), fold_exchange=bool(out[15]),
                     fold_ranks=int(out[16]), fold_staging_slots=int(out[17]),
                     marched_ranks_subcycles=int(out[18]), frame_cells=int(out[19]),
-                    marched_fold_subcycles=int(out[20]), fold_band_rows=int(out[21]), fold_rest_cells=int(out[22]))
+                    marched_fold_subcycles=int(out[20]), fold_band_rows=int(out[21]), fold_rest_cells=int(out[22]),
+                    marched_fold_ranks_subcycles=int(out[23]), fold_frame_cells=int(out[24]), marched_fold_exchange=bool(out[25]))
 
     def debug_cgres_prof(self):
         self._need_testing("debug_cgres_prof")
@@ -727,8 +736,8 @@ class EvpHip:
                     hip_device=int(v[4]), device_bus_id=buf.value.decode(errors="replace"))
 
     def describe_path(self) -> str:
-        buf = C.create_string_buffer(600)
-        _check(self.lib, self.lib.cice_evp_hip_describe_path(buf, C.c_int32(600)), "(describe_path)")
+        buf = C.create_string_buffer(1000)
+        _check(self.lib, self.lib.cice_evp_hip_describe_path(buf, C.c_int32(1000)), "(describe_path)")
         return buf.value.decode(errors="replace")
 
     def march_info(self) -> dict:

@@ -361,7 +361,15 @@ int cice_evp_hip_cgrid_dyn_finish(double *strocnxN, double *strocnyN, double *st
  * [18], [19] (n >= 20) several ranks, no fold, visc_method = avg_zeta: subcycles of the last call that ran as "zone marched + frame" --
  * cg_strip on the interior of the blocks (the items of [10]) on a second stream beside the three fused kernels' frame variants and
  * their five exchanges on every other interior cell --, and those frame cells on this rank (0: no such plan here; a rank without
- * rectangles for the marched kernel runs the fused schedule, and so does every rank under CICE_EVP_HIP_CGRID_ONE=0)  */
+ * rectangles for the marched kernel runs the fused schedule, and so does every rank under CICE_EVP_HIP_CGRID_ONE=0),
+ * [20] .. [22] (n >= 23) tripole / tripoleT grids on ONE rank, visc_method = avg_zeta: subcycles of the last call that ran as "marched
+ * zone + fold band" -- cg_strip on the rectangles under the fold band beside list-driven variants of the five phase kernels and
+ * their fold steps on every other interior cell --, the rows from the zone's top row to the fold, and those other cells,
+ * [23] .. [25] (n >= 26) such a grid on SEVERAL ranks: subcycles of the last call that ran as "marched zone + fold band + frame" --
+ * the same split with the five phases' exchanges at their points, the cells other ranks receive and the cells with ghost images in
+ * the rest --, the frame cells among the rest cells of [22], and 1 if the fold exchange of [15] ran inside it (the fold rows cut in
+ * x).  [20] stays 0 on several ranks and [23] on one.  Each rank decides for itself (a rank without rectangles keeps the five full
+ * phases: every schedule issues the same exchanges at the same points); CICE_EVP_HIP_CGRID_ONE=0 forces the five phases  */
 int cice_evp_hip_cgrid_timings(double *out, int32_t n);
 
 /* ---- multi-GPU: RCCL point-to-point halo over xGMI ---------------------------- */

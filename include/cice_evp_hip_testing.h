@@ -76,9 +76,14 @@ int cice_evp_hip_cgrid_frame_plan(const cice_evp_hip_dims *dims, int32_t ex, int
  * interior cell of global row NY.  wg: the workgroups of 64 x 4 cells of phases 0 .. 4, numbered as for cice_evp_hip_cgrid_frame_plan.
  * info11 = {zone cells, rest cells, workgroups of phases 0 .. 4, items, fold band rows, rows per segment, len}.  Arrays may be NULL.
  * Returns 0, or 1 when the schedule does not apply -- no fold, several ranks, a grid too short for a zone under the band -- with the
- * reason as the last error's text.                                                                                                   */
+ * reason as the last error's text.
+ * ranks: 0 the one-rank question ("marched zone + fold band": several ranks decline); 1 the plan of the rank `dims` describes on any
+ * rank layout ("marched zone + fold band + frame"): the rest then also holds every cell another rank receives in an in-loop exchange
+ * and every cell with a ghost image; a rank without the fold rows plans zone + frame (0 fold band rows).  ranks3 = {sent cells, frame
+ * cells -- sent or with a ghost image --, staging slots behind the arrays}; sent: the sent cells' offsets, ascending.  May be NULL.  */
 int cice_evp_hip_cgrid_march_fold_plan(const cice_evp_hip_dims *dims, int32_t ex, int32_t ey, int32_t slots, int32_t seg_min, int32_t seg, int32_t len,
-                                       int64_t *info11, uint8_t *cells, int32_t *wg, int32_t wg_cap, int32_t *items6, int32_t items_cap);
+                                       int64_t *info11, uint8_t *cells, int32_t *wg, int32_t wg_cap, int32_t *items6, int32_t items_cap,
+                                       int32_t ranks, int64_t *ranks3, int32_t *sent, int32_t sent_cap);
 /* Test hook: route the exchanges and the rank agreements of the marching path through HOST buffers and the caller's
  * callbacks instead of RCCL (which refuses two ranks on one device), so that its several-rank form can be run as
  * processes sharing one GPU (tools/mailbox_2proc.py --march: torch.distributed gloo underneath).  xchg: per peer q

@@ -52,6 +52,11 @@ def main():
                     help="with --cgrid: every rank on which the marched kernel has rectangles must have run every subcycle of its last "
                          "call but the first after an upload as 'zone marched + frame' (cgrid_timings: marched_ranks_subcycles), "
                          "and some rank must have rectangles")
+    ap.add_argument("--expect-marched-fold", action="store_true",
+                    help="with --cgrid on a tripole grid: every rank on which the marched kernel has rectangles must have run every "
+                         "subcycle of its last call but the first after an upload as 'marched zone + fold band + frame' (cgrid_timings: "
+                         "marched_fold_ranks_subcycles) with frame cells in its rest and say so in describe_path(), and some rank must "
+                         "have rectangles")
     ap.add_argument("--forcing", default="",
                     help="with --prep: a forcing layout 'calc_strair,grid_ocn,grid_atm', e.g. 0,C,B "
                          "(cice_evp_hip_set_forcing_layout): the ocean fields and strax / stray at those points")
@@ -205,6 +210,8 @@ def main():
             out["_halomask"] = hm
             if a.expect_marched and exchange:
                 out["_marched"] = (core.cgrid_timings(), want_marched, core.describe_path().rpartition("; ")[2])
+            if a.expect_marched_fold and exchange:
+                out["_marched_fold"] = (core.cgrid_timings(), want_marched, core.describe_path())
             if a.fold_ghosts:
                 cgt = core.cgrid_timings()
                 out["_schedule"] = (bool(cgt["fold_exchange"]), int(cgt["fold_ranks"]), core.describe_path().rpartition("; ")[2])
@@ -275,12 +282,21 @@ def main():
             zoned = 1 if cgt["marched_items"] > 0 else 0
             if zoned and not (cgt["marched_ranks_subcycles"] == want_marched and cgt["frame_cells"] > 0 and "zone marched + frame" in sched):
                 bad.append(("the marched kernel did not run beside the frame", cgt["marched_ranks_subcycles"], want_marched, cgt["marched_items"], sched))
+        if a.expect_marched_fold:
+            cgt, want_marched, path = got["_marched_fold"]
+            zoned = 1 if cgt["marched_items"] > 0 else 0
+            if zoned and not (cgt["marched_fold_ranks_subcycles"] == want_marched and cgt["fold_frame_cells"] > 0 and
+                              "marched zone + fold band + frame" in path):
+                bad.append(("the marched kernel did not run beside the fold band and the frame", cgt["marched_fold_ranks_subcycles"], want_marched,
+                            cgt["marched_items"], path))
         res = [None] * world
         dist.all_gather_object(res, (rank, bad, t_us, tim["halo_send_cells"]) + ((got["_schedule"],) if a.fold_ghosts else ()) +
-                               (((zoned, got["_marched"][0]["marched_cells"], got["_marched"][0]["frame_cells"]),) if a.expect_marched else ()))
+                               (((zoned, got["_marched"][0]["marched_cells"], got["_marched"][0]["frame_cells"]),) if a.expect_marched else ()) +
+                               (((zoned, got["_marched_fold"][0]["marched_cells"], got["_marched_fold"][0]["fold_frame_cells"],
+                                  got["_marched_fold"][0]["marched_fold_exchange"]),) if a.expect_marched_fold else ()))
         if rank == 0:
             ok = all(not r[1] for r in res)
-            if a.expect_marched:
+            if a.expect_marched or a.expect_marched_fold:
                 ok = ok and any(r[-1][0] for r in res)
             print("MAILBOX_2PROC", "OK" if ok else "FAIL", "cgrid", a.workload, f"world={world}", res, flush=True)
             if not ok:
