@@ -335,6 +335,8 @@ struct StepuOut {
 struct StepuPre {
     double taux, tauy, Cb, cca, ccb, ab2;
     double bu, bv;               // brlx*uold + revp*uvel_init, brlx*vold + revp*vvel_init (WITH_B)
+    double r;                    // POL::split_div: recip_core(ab2) ...
+    bool ab2_inside;             // ... and whether ab2 is inside the window in every active lane (wave-uniform)
 };
 
 // TBU: false when the host has verified TbU == 0 on every ice U-cell (seabed stress off): Cb = 0/(...) == 0
@@ -342,6 +344,8 @@ struct StepuPre {
 // them -- stepu_cell takes that order, so that the kernels that call it compile to the code they compiled to before the split
 // POL (evp_range_math.h), RangeMath: the square root's core where du^2 + dv^2 is inside the window in every active lane.  The two
 // divisions of the second part stay the compiler's: the test of their three operands costs what their range handling costs.
+// POL::split_div (RangeMathLazySplit; measured, not the default: profiles/r16_resident_rim_first.txt): the first part also forms
+// recip_core(ab2) and the verdict on ab2, the second part tests the two numerators and takes two quot_core.
 template <bool SIMPLE = false, bool TBU = true, bool WITH_B = true, class POL = evp_range::LibMath>
 __device__ __forceinline__ void stepu_pre_cell(const EvpScalars &p, const StepuIn &a, StepuPre &w, const POL &pol = POL())
 {
@@ -373,6 +377,13 @@ __device__ __forceinline__ void stepu_pre_cell(const EvpScalars &p, const StepuI
     }
     w.cca = cca; w.ccb = ccb;
     w.ab2 = cca * cca + ccb * ccb;
+    if constexpr (POL::split_div) {
+        // the denominator's share of the second part's two divisions, here where it is off the hand-off chain (evp_range_math.h)
+        if (!pol.nosplit) {
+            w.ab2_inside = pol.verdict(evp_range::outside(evp_range::off_pos(w.ab2)));
+            w.r = evp_range::recip_core(w.ab2);
+        }
+    }
     if (!WITH_B) return;
     if (SIMPLE) {      // revp*uvel_init == +0.0 (the kernels pass uvel_init = 0 when revp == 0); the add stays: -0 + 0 = +0
         w.bu = p.brlx * uold + 0.0;
@@ -386,7 +397,7 @@ __device__ __forceinline__ void stepu_pre_cell(const EvpScalars &p, const StepuI
 // the part that reads the stress partials (a.sx0 .. a.sy3; a.uarear, a.forcex / forcey, a.Umassdti besides)
 // POL::lazy_taub: o.taubx / o.tauby are left to the caller, which forms them from o.u, o.v and w.Cb where it stores them
 template <bool SIMPLE = false, bool WITH_B = true, class POL = evp_range::LibMath>
-__device__ __forceinline__ void stepu_post_cell(const EvpScalars &p, const StepuIn &a, const StepuPre &w, StepuOut &o)
+__device__ __forceinline__ void stepu_post_cell(const EvpScalars &p, const StepuIn &a, const StepuPre &w, StepuOut &o, const POL &pol = POL())
 {
     // divergence of the internal stress tensor
     o.strintx = a.uarear * (a.sx0 + a.sx1 + a.sx2 + a.sx3);
@@ -403,8 +414,22 @@ __device__ __forceinline__ void stepu_post_cell(const EvpScalars &p, const Stepu
         cc1 = o.strintx + a.forcex + w.taux + a.Umassdti * (p.brlx * a.uold + p.revp * a.uvel_init);
         cc2 = o.strinty + a.forcey + w.tauy + a.Umassdti * (p.brlx * a.vold + p.revp * a.vvel_init);
     }
+    if constexpr (POL::split_div) {
+        // a wave whose active lanes all have ab2 (the first part's verdict) and both numerators inside the window: the quotients'
+        // three operations each on the reciprocal the first part formed; any other wave the compiler's divisions
+        const double nu = w.cca * cc1 + w.ccb * cc2, nv = w.cca * cc2 - w.ccb * cc1;
+        if (!pol.nosplit &&
+            pol.wave_inside(evp_range::outside(evp_range::umax(evp_range::off_abs(nu), evp_range::off_abs(nv))), false, w.ab2_inside)) {
+            o.u = evp_range::quot_core(nu, w.ab2, w.r);
+            o.v = evp_range::quot_core(nv, w.ab2, w.r);
+        } else {
+            o.u = nu / w.ab2;
+            o.v = nv / w.ab2;
+        }
+    } else {
     o.u = (w.cca * cc1 + w.ccb * cc2) / w.ab2;
     o.v = (w.cca * cc2 - w.ccb * cc1) / w.ab2;
+    }
     // seabed stress component for outputs
     if (POL::lazy_taub) return;
     o.taubx = -o.u * w.Cb;

@@ -92,7 +92,7 @@ struct EvpResident2 {
     const uint8_t *nlate;      // [ntiles] COOP: rim T-cells with ice = the first nlate entries of perm (<= 64); NULL: the variant is off
     int *cuload;               // [2048][8] per-CU record of the launch: lock, stamp, ice-holding waves per SIMD
     unsigned long long *prof;  // NULL, or [ntiles][4 chunks][8]: cycles per phase (tools)
-    int dbg;                   // timing experiments only (CICE_EVP_HIP_RES_DEBUG; WRONG results): 1 no tag check, 2 no ring loads, 4 longer sleep; 8 = every fourth tile lags 10 us per subcycle (results stay right); 16 = tile 1 never runs (every wait on it gives up); A/B switches, results stay right: 32 = 16 x 16 tiles without the rim-wave split, 64 = without the per-CU SIMD balancing, 1024 = the lean loops' square roots and divisions always the compiler's (evp_range_math.h)
+    int dbg;                   // timing experiments only (CICE_EVP_HIP_RES_DEBUG; WRONG results): 1 no tag check, 2 no ring loads, 4 longer sleep; 8 = every fourth tile lags 10 us per subcycle (results stay right); 16 = tile 1 never runs (every wait on it gives up); A/B switches, results stay right: 32 = 16 x 16 tiles without the rim-wave split, 64 = without the per-CU SIMD balancing, 1024 = the lean loops' square roots and divisions always the compiler's (evp_range_math.h), 2048 | 4096 = the rim-wave schedule's priority form (0..3) << 11, 8192 = its full tiles skip the per-CU lock, 16384 = its U-cells' divisions on the cores with the reciprocal formed early (all three set by the host from their switches, never from RES_DEBUG's value alone)
     int par0;                  // which of rec[0/1] holds the records of subcycle index 0 of THIS launch
                                // (flips so that a launch never starts in the buffer the previous one ended in)
     // neighbours on other GPUs (ring entries with z == -2 are produced there); rimg == NULL: none
@@ -117,6 +117,23 @@ struct EvpResident2 {
 // (evp_range_math.h); 0: compiled out of the product (the test build carries both, CICE_EVP_HIP_RES_RANGE)
 #ifndef EVP_RES2_RANGE_DEFAULT
 #define EVP_RES2_RANGE_DEFAULT 1
+#endif
+// the rim-wave schedule's issue priorities (evp_resident2.hip, subcycle_rim): 0 none, 1 the rim wave first while it is on the
+// hand-off chain, 2 and the interior waves' stress update above their momentum step, 3 and all their arithmetic above their
+// spins (the test build carries all four, CICE_EVP_HIP_RES_PRIO).  Measured on gx1, profiles/r16_resident_rim_first.txt: each of
+// 1, 2, 3 takes 5-7 % off the step, 2 and 3 a little more than 1 and not apart from each other
+#ifndef EVP_RES2_PRIO_DEFAULT
+#define EVP_RES2_PRIO_DEFAULT 2
+#endif
+// the rim-wave schedule's full tiles take the identity chunk map without the per-CU lock (the test build carries both,
+// CICE_EVP_HIP_RES_NOLOCK).  Measured: 4 us less per launch, which five bench runs do not tell from their own spread -- off
+#ifndef EVP_RES2_NOLOCK_DEFAULT
+#define EVP_RES2_NOLOCK_DEFAULT 0
+#endif
+// the rim-wave schedule's two divisions per U-cell on the cores, the reciprocal formed in the first part of the momentum step
+// (evp_range_math.h: recip_core / quot_core; the test build carries both, CICE_EVP_HIP_RES_SPLITDIV)
+#ifndef EVP_RES2_SPLITDIV_DEFAULT
+#define EVP_RES2_SPLITDIV_DEFAULT 0
 #endif
 #ifdef CICE_EVP_HIP_TESTING
 // test build: evp_range_math.h's cores beside the compiler's forms over n elements (device pointers; evp_resident2.hip)

@@ -467,7 +467,14 @@ int launch_resident2(int ndte, int cur0, bool dry)
     // range-proved square roots and divisions in the lean loops (CICE_EVP_HIP_RES_RANGE=1/0, test build: A/B; the product's
     // kernel is compiled with or without them, EVP_RES2_RANGE_DEFAULT, and tests nothing)
     const int want_range = env_test("CICE_EVP_HIP_RES_RANGE") ? std::atoi(env_test("CICE_EVP_HIP_RES_RANGE")) : EVP_RES2_RANGE_DEFAULT;
-    R.dbg = dbg2 | (want_range ? 0 : 1024);
+    // the rim-wave schedule's issue priorities and its full tiles' way round the per-CU lock, likewise (CICE_EVP_HIP_RES_PRIO=0..3,
+    // CICE_EVP_HIP_RES_NOLOCK=1/0, test build: A/B; the product compiles EVP_RES2_PRIO_DEFAULT / EVP_RES2_NOLOCK_DEFAULT in)
+    const int want_prio = std::min(3, std::max(0, env_int(env_test("CICE_EVP_HIP_RES_PRIO"), EVP_RES2_PRIO_DEFAULT)));
+    const bool want_nolock = env_on(env_test("CICE_EVP_HIP_RES_NOLOCK"), EVP_RES2_NOLOCK_DEFAULT != 0);
+    // ... and its U-cells' divisions on the cores with the reciprocal formed early (CICE_EVP_HIP_RES_SPLITDIV=1/0; EVP_RES2_SPLITDIV_DEFAULT)
+    const bool want_split = env_on(env_test("CICE_EVP_HIP_RES_SPLITDIV"), EVP_RES2_SPLITDIV_DEFAULT != 0);
+    R.dbg = (dbg2 & ~(2048 | 4096 | 8192 | 16384)) | (want_range ? 0 : 1024) | (want_prio << 11) | (want_nolock ? 8192 : 0) |
+            (want_split ? 16384 : 0);
     R.seam = S.res2_seam;
     R.tfold = S.plan.tfold ? 1 : 0;
     R.img3 = S.res2_img3;

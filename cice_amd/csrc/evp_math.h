@@ -63,7 +63,7 @@ template <> struct Math<true> {
     template <int MODE, bool TBU, class POL>
     static __device__ __forceinline__ void stepu_pre(const EvpScalars &p, const UI &a, UP &w, const POL &pol) { evp_strict::stepu_pre_cell<MODE == 3, TBU, true, POL>(p, a, w, pol); }
     template <int MODE, class POL>
-    static __device__ __forceinline__ void stepu_post(const EvpScalars &p, const UI &a, const UP &w, UO &o, const POL &) { evp_strict::stepu_post_cell<MODE == 3, true, POL>(p, a, w, o); }
+    static __device__ __forceinline__ void stepu_post(const EvpScalars &p, const UI &a, const UP &w, UO &o, const POL &pol) { evp_strict::stepu_post_cell<MODE == 3, true, POL>(p, a, w, o, pol); }
     static __device__ __forceinline__ void metrics(double hte, double hte_im, double htn, double htn_jm, double dmin, SI &a)
     {
         evp_strict::metrics_cell(hte, hte_im, htn, htn_jm, dmin, a);
@@ -117,7 +117,7 @@ template <> struct Math<false> {
     template <int MODE, bool TBU, class POL>
     static __device__ __forceinline__ void stepu_pre(const EvpScalars &p, const UI &a, UP &w, const POL &pol) { evp_fused::stepu_pre_cell<MODE == 3, TBU, true, POL>(p, a, w, pol); }
     template <int MODE, class POL>
-    static __device__ __forceinline__ void stepu_post(const EvpScalars &p, const UI &a, const UP &w, UO &o, const POL &) { evp_fused::stepu_post_cell<MODE == 3, true, POL>(p, a, w, o); }
+    static __device__ __forceinline__ void stepu_post(const EvpScalars &p, const UI &a, const UP &w, UO &o, const POL &pol) { evp_fused::stepu_post_cell<MODE == 3, true, POL>(p, a, w, o, pol); }
     static __device__ __forceinline__ void metrics(double hte, double hte_im, double htn, double htn_jm, double dmin, SI &a)
     {
         evp_fused::metrics_cell(hte, hte_im, htn, htn_jm, dmin, a);

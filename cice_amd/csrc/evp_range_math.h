@@ -21,6 +21,12 @@
 //                             exponents differ by more than about 1020; the core's quotient has that sign already: q = n * r with
 //                             r of d's sign, and the last fma cannot cancel it (|e * r| <= 2^-51 |q|).  A numerator of -0 would
 //                             come out +0 from the core: zeros are outside W for that reason too.
+//                             The sequence is rcp, four fmas on d alone, then mul and two fmas with n: r = recip_core(d) depends on
+//                             d only and may be formed EARLIER than the quotient needs it (the rim wave's momentum step: ab2 is
+//                             known after the barrier, the numerators only once the stress partials are) and shared by two
+//                             quotients of one d; quot_core(n, d, r) then performs the same three operations on the same values,
+//                             so the argument above covers div_core == quot_core(n, d, recip_core(d)) unchanged.  The verdict on
+//                             d travels with r (same lanes active in both places).
 // A caller takes the core only where EVERY active lane of the wave has all its operands in W (one ballot, a uniform branch) and
 // today's code otherwise, so no bit can change; tests/test_gpu_range_math.py sweeps both against the compiler's forms.
 #pragma once
@@ -57,8 +63,8 @@ __device__ __forceinline__ double sqrt_core(double x)
     return g;
 }
 
-// n / d for n, d in W
-__device__ __forceinline__ double div_core(double n, double d)
+// n / d for n, d in W, in two pieces: the first five operations read the denominator only ...
+__device__ __forceinline__ double recip_core(double d)
 {
 #pragma clang fp contract(off)
     double r = __builtin_amdgcn_rcp(d);
@@ -66,17 +72,25 @@ __device__ __forceinline__ double div_core(double n, double d)
     r = __builtin_fma(r, e, r);
     e = __builtin_fma(-d, r, 1.0);
     r = __builtin_fma(r, e, r);
+    return r;
+}
+// ... and the last three take r = recip_core(d) from wherever it was formed
+__device__ __forceinline__ double quot_core(double n, double d, double r)
+{
+#pragma clang fp contract(off)
     double q = n * r;
-    e = __builtin_fma(-d, q, n);
+    const double e = __builtin_fma(-d, q, n);
     q = __builtin_fma(e, r, q);
     return q;
 }
+__device__ __forceinline__ double div_core(double n, double d) { return quot_core(n, d, recip_core(d)); }
 
 // ---- policies of evp_cell.inc -------------------------------------------------------------------------------------------------
 // LibMath: the compiler's sqrt and division everywhere (every kernel but the lean resident loops: their code is what it was).
 struct LibMath {
     static constexpr bool ranged = false;
     static constexpr bool lazy_taub = false;
+    static constexpr bool split_div = false;
 };
 // RangeMath: per pass, each lane tests its operands against W, the verdicts are combined over the wave's active lanes, and the wave
 // takes the cores only when all are inside.  cbad: the lanes whose per-call operands of the stress update (strength, DminTarea)
@@ -85,18 +99,23 @@ struct LibMath {
 struct RangeMath {
     static constexpr bool ranged = true;
     static constexpr bool lazy_taub = false;
+    static constexpr bool split_div = false;
     unsigned long long cbad = 0;
     bool off = false;
+    bool nosplit = false;      // split_div policies, the test build's A/B switch: the U-cell's divisions the compiler's, as they were
     mutable unsigned nlib = 0;
-    // wave-uniform: every active lane's operands are inside the window
-    __device__ __forceinline__ bool wave_inside(bool lane_outside, bool with_cbad) const
+    // wave-uniform: every active lane's operands are inside the window (carried: a wave-uniform verdict formed earlier, on the
+    // same active lanes, joins it)
+    __device__ __forceinline__ bool wave_inside(bool lane_outside, bool with_cbad, bool carried = true) const
     {
         if (off) { ++nlib; return false; }
         unsigned long long bad = __builtin_amdgcn_ballot_w64(lane_outside);
         if (with_cbad) bad |= cbad;
-        if (__builtin_expect(bad != 0, 0)) { ++nlib; return false; }
+        if (__builtin_expect(bad != 0 || !carried, 0)) { ++nlib; return false; }
         return true;
     }
+    // the verdict alone, for a later wave_inside to carry (counts nothing: the pass that uses it does)
+    __device__ __forceinline__ bool verdict(bool lane_outside) const { return __builtin_amdgcn_ballot_w64(lane_outside) == 0; }
     static __device__ __forceinline__ bool percall_outside(double strength, double DminTarea)
     {
         return outside(off_abs(strength)) || outside(off_pos(DminTarea));
@@ -105,6 +124,11 @@ struct RangeMath {
 // ... and taubx / tauby left to the caller, which forms them where it stores them (the rim-wave schedule)
 struct RangeMathLazy : RangeMath {
     static constexpr bool lazy_taub = true;
+};
+// ... and the U-cell's two divisions by ab2 on the cores, the reciprocal formed in the first part of the momentum step
+// (stepu_pre_cell: recip_core, the verdict on ab2 carried as a wave-uniform flag) and the quotients in the second (quot_core x 2)
+struct RangeMathLazySplit : RangeMathLazy {
+    static constexpr bool split_div = true;
 };
 
 }  // namespace evp_range

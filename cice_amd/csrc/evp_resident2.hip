@@ -194,7 +194,16 @@ __global__ __launch_bounds__(64 * RTY, REMOTE ? 2 : 3) void evp_resident2_tile(E
     constexpr bool RANGE = LEAN && EVP_RES2_RANGE_DEFAULT;
 #endif
     // the policy of the lean loops' arithmetic; POLE: the same with taubx / tauby formed every subcycle (the first lean loop)
-    using POL = std::conditional_t<RANGE, std::conditional_t<RIMU, evp_range::RangeMathLazy, evp_range::RangeMath>, evp_range::LibMath>;
+    // SPLIT (the rim-wave schedule): the U-cell's two divisions on the cores, their reciprocal formed in the first part of the
+    // momentum step, which the rim wave runs off the hand-off chain (EVP_RES2_SPLITDIV_DEFAULT; the test build carries it with a
+    // switch, RES_DEBUG bit 16384, CICE_EVP_HIP_RES_SPLITDIV)
+#ifdef CICE_EVP_HIP_TESTING
+    constexpr bool SPLIT = true;
+#else
+    constexpr bool SPLIT = EVP_RES2_SPLITDIV_DEFAULT != 0;
+#endif
+    using POLR = std::conditional_t<SPLIT, evp_range::RangeMathLazySplit, evp_range::RangeMathLazy>;
+    using POL = std::conditional_t<RANGE, std::conditional_t<RIMU, POLR, evp_range::RangeMath>, evp_range::LibMath>;
     using POLE = std::conditional_t<RANGE, evp_range::RangeMath, evp_range::LibMath>;
     constexpr int W = 1 << LOGW;
     constexpr int H = 256 / W;
@@ -247,7 +256,19 @@ __global__ __launch_bounds__(64 * RTY, REMOTE ? 2 : 3) void evp_resident2_tile(E
     // a small per-CU record under a lock, once per launch).  Speed only: any chunk -> wave map is correct.
     int tq = t;
     int cu_rank = 0;                          // how many workgroups had reached this CU before this one
-    if (PERM && R.cuload && !(RES_DBG(R) & 64)) {
+    // RIMU, full tiles (all four chunks hold ice): such a tile adds one wave to every SIMD's count, so it changes no later
+    // comparison and its own map is arbitrary -- it takes the identity map and leaves the per-CU record alone (no CAS, no loads,
+    // no stores; the partial tiles' choices are what they were).  The product compiles it in or out (EVP_RES2_NOLOCK_DEFAULT);
+    // the test build carries a switch (RES_DEBUG bit 8192, CICE_EVP_HIP_RES_NOLOCK) and keeps the lock for every tile while the
+    // stamps are on: the arrival rank feeds them.  profiles/r16_resident_rim_first.txt
+#ifdef CICE_EVP_HIP_TESTING
+    const bool skip_lock = RIMU && (RES_DBG(R) & 8192) && !RES_PROF(R);
+#else
+    constexpr bool skip_lock = RIMU && EVP_RES2_NOLOCK_DEFAULT;
+#endif
+    bool balance = PERM && R.cuload && !(RES_DBG(R) & 64);
+    if (skip_lock && balance && R.nact[tile] == 4) balance = false;      // (uniform over the workgroup)
+    if (balance) {
         const int wave = t >> 6;
         if ((t & 63) == 0) {
             unsigned hw, xcc;
@@ -300,9 +321,11 @@ __global__ __launch_bounds__(64 * RTY, REMOTE ? 2 : 3) void evp_resident2_tile(E
         __syncthreads();
         tq = s_chunk[wave] * 64 + (t & 63);
         cu_rank = s_simd[0] >> 8;
-        // (tried, no measurable effect on gx1: one s_setprio level per workgroup on all SIMDs of its CU, in
-        // either order; s_setprio 3 for the rim wave between its poll and the barrier; rim waves of the
-        // workgroups of a CU on different SIMDs; s_sleep 0/3/8 in the poll loop -- all within +-2 %)
+        // (tried in round 4 on the two-barrier schedule, no measurable effect on gx1: one s_setprio level per workgroup on
+        // all SIMDs of its CU, in either order; s_setprio 3 for the rim wave between its poll and the barrier; rim waves of
+        // the workgroups of a CU on different SIMDs; s_sleep 0/3/8 in the poll loop -- all within +-2 %.  There the interior
+        // waves sat at B1 while the rim wave worked.  On the rim-wave schedule they step inside its window and priorities do
+        // pay: subcycle_rim below)
     }
     // which T-cell of the tile this thread owns: row-major (lane = column) unless permuted
     const int pos = PERM ? (int)R.perm[tile * 256 + tq] : t;      // == trow*W + tcol
@@ -436,6 +459,9 @@ __global__ __launch_bounds__(64 * RTY, REMOTE ? 2 : 3) void evp_resident2_tile(E
     if constexpr (POL::ranged) {
         pol.cbad = __builtin_amdgcn_ballot_w64(percall_out);
         pol.off = (RES_DBG(R) & 1024) != 0;
+#ifdef CICE_EVP_HIP_TESTING
+        pol.nosplit = !(RES_DBG(R) & 16384);
+#endif
     }
     const POLE &pole = pol;
     if (isU) {
@@ -624,8 +650,9 @@ __global__ __launch_bounds__(64 * RTY, REMOTE ? 2 : 3) void evp_resident2_tile(E
         acc += now_ - pc0;                                              \
         pc0 = now_;                                                     \
     }
-    // Tried in round 4, measured on gx1 (tools/resident_phases.py), none moved the subcycle by more than
-    // 2 %: s_setprio 3 for the rim wave / 0 for interior stress / 2 for every wave's momentum step; the ring records of the
+    // Tried in round 4 on the two-barrier schedule (subcycle below), measured on gx1 (tools/resident_phases.py; DESIGN.md section
+    // 4), none moved the subcycle by more than 2 %: s_setprio 3 for the rim wave / 0 for interior stress / 2 for every wave's
+    // momentum step (on the rim-wave schedule priorities take 5-7 % off the step: subcycle_rim); the ring records of the
     // next subcycle requested before the momentum step (the hand-off is on a dependency CYCLE between neighbours, not on one
     // tile's critical path: nothing is there earlier); fine-grained / uncached memory for the record buffers; no s_sleep.
     // Two polls in flight per lane (a second poll a few hundred cycles behind the first, each re-issued once looked at; one
@@ -893,6 +920,22 @@ __global__ __launch_bounds__(64 * RTY, REMOTE ? 2 : 3) void evp_resident2_tile(E
         ucell_operands(q);
         MM::template stepu_pre<CAP, false, POL>(A.p, q, upre, pol);
     }
+    // Issue priorities (s_setprio) on this schedule, where the interior waves' momentum step runs inside the rim wave's window
+    // and other tiles' waves issue between the rim wave's instructions (profiles/r16_resident_rim_first.txt).  Forms:
+    //   1  the rim wave at level 3 from the moment every lane's poll has matched until its records are stored, 0 otherwise;
+    //   2  as 1, and the interior waves at level 1 during their stress update;
+    //   3  as 1, and the interior waves at level 1 throughout their arithmetic.
+    // Every spin (ring poll, slot spin), the barrier and the rim wave's first part after the barrier run at level 0: a spinning
+    // wave never outranks a wave that has work.  No bit depends on it.  The product compiles one form in (EVP_RES2_PRIO_DEFAULT,
+    // 0: none); the test build carries a switch (RES_DEBUG bits 2048 | 4096: the form; CICE_EVP_HIP_RES_PRIO).
+#ifdef CICE_EVP_HIP_TESTING
+    const int prio_form = RIMU ? (RES_DBG(R) >> 11) & 3 : 0;
+#else
+    constexpr int prio_form = RIMU ? EVP_RES2_PRIO_DEFAULT : 0;
+#endif
+    const bool prio_rim = prio_form != 0 && rimw;                 // (wave-uniform, like rimw)
+    const bool prio_in_stress = prio_form >= 2 && !rimw;
+    const bool prio_in_step = prio_form == 3 && !rimw;
     auto subcycle_rim = [&](const int k, const v4u *rd, v4u *wr) -> bool {
         const unsigned want = R.tag_base + (unsigned)k;       // tag of the velocities subcycle k reads
         const int done = k + 1;                               // what an interior wave's slot says once its stress of subcycle k is in the planes
@@ -925,6 +968,7 @@ __global__ __launch_bounds__(64 * RTY, REMOTE ? 2 : 3) void evp_resident2_tile(E
             __builtin_amdgcn_wave_barrier();
             __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
             bad = __builtin_amdgcn_ballot_w64(gave) != 0;      // (no LDS round trip on the chain)
+            if (prio_rim && !bad) __builtin_amdgcn_s_setprio(3);      // on the chain from here
         }
         // the rim wave looks at the slots once before its stress update -- the interior waves are usually done by the time the
         // neighbours' records have arrived -- so that the look's LDS round trip travels with the stress update's own loads
@@ -938,6 +982,7 @@ __global__ __launch_bounds__(64 * RTY, REMOTE ? 2 : 3) void evp_resident2_tile(E
         }
         EVP_STAMP(pacc0)
         if (!bad) {      // (a wave whose wait gave up goes straight to the barrier)
+            if (prio_in_stress) __builtin_amdgcn_s_setprio(1);
             if (actT) {
                 double str[8];
                 a.u_ij = s_u[li]; a.v_ij = s_v[li];
@@ -961,7 +1006,9 @@ __global__ __launch_bounds__(64 * RTY, REMOTE ? 2 : 3) void evp_resident2_tile(E
             // are read by the rim wave only
             __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
             if (!rimw && (t & 63) == 0) __hip_atomic_store(&s_slot[(tq >> 6) - 1], done, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+            if (prio_in_stress) __builtin_amdgcn_s_setprio(0);
             if (!slots_seen) {
+                if (prio_rim) __builtin_amdgcn_s_setprio(0);
                 unsigned spins = 0;
                 for (;;) {
                     const int a0 = __hip_atomic_load(&s_slot[0], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
@@ -979,7 +1026,9 @@ __global__ __launch_bounds__(64 * RTY, REMOTE ? 2 : 3) void evp_resident2_tile(E
                     if (bad) break;
                     __builtin_amdgcn_s_sleep(1);
                 }
+                if (prio_rim && !bad) __builtin_amdgcn_s_setprio(3);
             }
+            if (prio_in_step && !bad) __builtin_amdgcn_s_setprio(1);
             __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
             EVP_STAMP(pacc2)
         }
@@ -1008,6 +1057,7 @@ __global__ __launch_bounds__(64 * RTY, REMOTE ? 2 : 3) void evp_resident2_tile(E
                     if (img1 >= 0) st_rec2_s(wr, img_off1, pack_rec(img_sg1 * u_own, tag), pack_rec(img_sg1 * v_own, tag));
                     if (img2 >= 0) st_rec2_s(wr, img_off2, pack_rec(img_sg2 * u_own, tag), pack_rec(img_sg2 * v_own, tag));
                 }
+                if (prio_rim || prio_in_step) __builtin_amdgcn_s_setprio(0);      // off the chain
                 if (isU) {
                     s_u[uli] = u_own; s_v[uli] = v_own;       // read by the next stress phase, after the barrier below
                     if (k == R.ndte - 1 && !R.dry) {
@@ -1036,6 +1086,7 @@ __global__ __launch_bounds__(64 * RTY, REMOTE ? 2 : 3) void evp_resident2_tile(E
                 if (img1 >= 0) st_rec2_s(wr, img_off1, pack_rec(img_sg1 * u_own, tag), pack_rec(img_sg1 * v_own, tag));
                 if (img2 >= 0) st_rec2_s(wr, img_off2, pack_rec(img_sg2 * u_own, tag), pack_rec(img_sg2 * v_own, tag));
             }
+            if (prio_rim || prio_in_step) __builtin_amdgcn_s_setprio(0);      // off the chain
             if (isU) {
                 s_u[uli] = u_own; s_v[uli] = v_own;       // read by the next stress phase, after the barrier below
                 if (k == R.ndte - 1 && !R.dry) {

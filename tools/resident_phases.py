@@ -3,7 +3,10 @@ CICE_EVP_HIP_RES_PROF=1 (16 x 16 tiles).  Usage: python tools/resident_phases.py
 (CICE_EVP_HIP_RES_RIMU=0: the lean loop's first schedule, two workgroup barriers per subcycle.  On the rim-wave schedule the third
 stamp is the wait for the interior waves' slots and the fifth the one barrier; for an interior wave the fourth is its momentum step.
 CICE_EVP_HIP_RES_RANGE=0: the lean loops' square roots and divisions always the compiler's; the last line of the first block says how
-many wave passes of the last call took them -- csrc/evp_range_math.h)"""
+many wave passes of the last call took them -- csrc/evp_range_math.h.  CICE_EVP_HIP_RES_PRIO=0..3, CICE_EVP_HIP_RES_SPLITDIV=0/1: the
+rim-wave schedule's issue priorities and split division; with the stamps on every tile takes the per-CU lock, whatever
+CICE_EVP_HIP_RES_NOLOCK says.  Beside the per-class tables: the same by the number of tiles on the CU, and the ten tiles with the
+shortest poll -- the pace-setters -- each with what sits on its rim wave's SIMD)"""
 import os, sys, pathlib
 R = str(pathlib.Path(__file__).resolve().parents[1]); sys.path[:0] = [R, R + "/tests", R + "/oracle"]
 os.environ["CICE_EVP_HIP_RES_PROF"] = "1"
@@ -62,11 +65,17 @@ for n in sorted(set(per_cu)):
     print(f"  CUs holding {n} tiles: {len(set(cu[sel]))} CUs, {int(sel.sum())} tiles; rim-wave cycles/subcycle mean {tot[sel].mean():.0f} max {tot[sel].max():.0f}; "
           f"poll mean {ph[sel][:, 0, 0].mean():.0f} min {ph[sel][:, 0, 0].min():.0f}; active waves per CU mean {np.mean([nact[cu == c].sum() for c in set(cu[sel])]):.1f} "
           f"max {max(nact[cu == c].sum() for c in set(cu[sel]))}")
-order = np.argsort(ph[:, 0, 0])[:8]
-print("  tiles with the shortest poll (the ones everybody waits for):")
+for n in (2, 3):                            # the phase table by how many tiles share the CU
+    show((nact == 4) & (per_cu == n), f"full tiles on CUs holding {n} tiles")
+order = np.argsort(ph[:, 0, 0])[:10]
+print("  tiles with the shortest poll (the ones everybody waits for); 'beside it': the ice-holding chunks on its rim wave's SIMD, tile#chunk:")
 for t in order:
     c = cu[t]
-    print(f"    tile cu {c:4d} rank {rank[t]} nact {nact[t]} tiles on CU {ncu[c]} (nact {list(nact[cu == c])}): " + "  ".join(f"{n} {v:6.0f}" for n, v in zip(names, ph[t, 0, :])))
+    idx = np.nonzero(cu == c)[0]
+    beside = [f"{'own' if o == t else 'T%d' % list(idx).index(o)}#{ch}" for o in idx for ch in range(int(nact[o]))
+              if simd[o, ch] == simd[t, 0] and not (o == t and ch == 0)]
+    print(f"    tile cu {c:4d} rank {rank[t]} nact {nact[t]} tiles on CU {ncu[c]} (nact {[int(x) for x in nact[idx]]}) rim wave on SIMD {simd[t, 0]}, beside it {beside or 'nothing'}: "
+          + "  ".join(f"{n} {v:6.0f}" for n, v in zip(names, ph[t, 0, :])))
 
 # do rim waves (chunk 0) of the tiles of one CU share a SIMD, and does it matter?
 share = np.zeros(len(p), bool)
