@@ -269,7 +269,7 @@ int cice_evp_hip_stream_probe(int64_t ncells, double *bytes_per_second)
 // right on one node, and on several when the launcher places ranks block-wise.
 static int pick_device(int rank, int ndev)
 {
-    if (env("CICE_EVP_HIP_DEVICE")) return std::atoi(env("CICE_EVP_HIP_DEVICE"));
+    if (env("CICE_EVP_HIP_DEVICE")) return env_int(env("CICE_EVP_HIP_DEVICE"), 0);
     for (const char *name : {"LOCAL_RANK", "OMPI_COMM_WORLD_LOCAL_RANK", "MV2_COMM_WORLD_LOCAL_RANK", "MPI_LOCALRANKID", "SLURM_LOCALID"})
         if (const char *v = std::getenv(name))
             if (*v >= '0' && *v <= '9') return std::atoi(v) % ndev;
@@ -326,7 +326,7 @@ int cice_evp_hip_init(const cice_evp_hip_dims *dims, const cice_evp_hip_params *
     S.d = host_dims();
 
     if (!build_halo_plan(*dims, S.plan)) return fail(-3, "halo plan: %s", S.plan.error.c_str());
-    if (env_test("CICE_EVP_HIP_SELF_EXCHANGE") && std::atoi(env_test("CICE_EVP_HIP_SELF_EXCHANGE")) && dims->nranks == 1) {
+    if (env_on(env_test("CICE_EVP_HIP_SELF_EXCHANGE"), false) && dims->nranks == 1) {
         // test hook: route the on-device ghost copies through pack -> ncclSend/ncclRecv (to
         // self) -> unpack, so that the remote-halo code path runs on a single GPU
         HaloPeer self;
@@ -382,7 +382,7 @@ int cice_evp_hip_init(const cice_evp_hip_dims *dims, const cice_evp_hip_params *
     HIPC(hipStreamCreateWithFlags(&S.stream_comm, hipStreamNonBlocking));
     HIPC(hipEventCreateWithFlags(&S.ev_pack, hipEventDisableTiming));
     HIPC(hipEventCreateWithFlags(&S.ev_halo, hipEventDisableTiming));
-    S.overlap = !(env_test("CICE_EVP_HIP_NO_OVERLAP") && std::atoi(env_test("CICE_EVP_HIP_NO_OVERLAP")));
+    S.overlap = !env_on(env_test("CICE_EVP_HIP_NO_OVERLAP"), false);
     HIPC(hipEventCreate(&S.ev0));
     HIPC(hipEventCreate(&S.ev1));
     HIPC(hipEventCreate(&S.ev2));
@@ -400,11 +400,10 @@ int cice_evp_hip_init(const cice_evp_hip_dims *dims, const cice_evp_hip_params *
         S.max_nj = std::max(S.max_nj, S.jhi[b] - S.jlo[b] + 1);
     }
     S.tyb = 4;
-    if (env_test("CICE_EVP_HIP_TYB")) {
-        const int t = std::atoi(env_test("CICE_EVP_HIP_TYB"));   // tile height [+100: XCD-contiguous order]
+    if (const int t = env_int(env_test("CICE_EVP_HIP_TYB"), ENV_UNSET); t != ENV_UNSET) {   // tile height [+100: XCD-contiguous order]
         S.tyb = (t % 100 >= 2 && t % 100 <= 9) ? t : 5 + 100 * (t / 100);
     }
-    S.use_graph = !(env_test("CICE_EVP_HIP_NOGRAPH") && std::atoi(env_test("CICE_EVP_HIP_NOGRAPH")));
+    S.use_graph = !env_on(env_test("CICE_EVP_HIP_NOGRAPH"), false);
 
     for (auto &p : S.stat)
         if (S.mem.alloc(p, S.n, true)) return -1;
@@ -581,7 +580,7 @@ int cice_evp_hip_subcycle(int32_t ndte)
         return 0;
     }
     // RCCL p2p inside a captured graph: opt-in (CICE_EVP_HIP_GRAPH_RCCL=1) until measured on a multi-GPU node
-    const bool graph_rccl = env_test("CICE_EVP_HIP_GRAPH_RCCL") && std::atoi(env_test("CICE_EVP_HIP_GRAPH_RCCL"));
+    const bool graph_rccl = env_on(env_test("CICE_EVP_HIP_GRAPH_RCCL"), false);
     const bool graph_ok = S.use_graph && (S.plan.peers.empty() || graph_rccl || S.direct.on);
     if (graph_ok) {
         const auto key = std::make_tuple((int)ndte, S.cur, S.flags & S.flags_allowed);
@@ -850,7 +849,7 @@ int cice_evp_hip_run(double *stressp_1, double *stressp_2, double *stressp_3, do
         for (double *p : {strintxU, strintyU, taubxU, taubyU})
             if (p) D.items.push_back({p, nullptr});
         S.lean_diag = D.items.size() == 4 && batch_mapped(D, false) &&
-                      !(env_test("CICE_EVP_HIP_LEAN") && !std::atoi(env_test("CICE_EVP_HIP_LEAN")));
+                      env_on(env_test("CICE_EVP_HIP_LEAN"), true);
     }
     struct LeanOff { ~LeanOff() { S.lean_diag = false; } } lean_off;      // only for the duration of this call
     if (int rc = upload_impl(f, iceTmask, iceUmask, keep_sig)) return rc;
@@ -1034,6 +1033,26 @@ int cice_evp_hip_rim_plan(int32_t ni, int32_t nj, int32_t cyclic_ew, int32_t cyc
         }
     }
     return nt;
+}
+
+// Host-only: res2_choose (evp_device.h) over n cases that share cap, logw and hooks; bits as in include/cice_evp_hip_testing.h
+int cice_evp_hip_debug_res2_choose(int64_t n, const uint32_t *facts, int32_t cap, int32_t logw, int32_t hooks, uint32_t *chosen)
+{
+    if (n < 0 || !facts || !chosen) return fail(-1, "res2_choose: bad argument");
+    for (int64_t e = 0; e < n; ++e) {
+        auto bit = [&](int k) { return (facts[e] >> k & 1u) != 0; };
+        const unsigned fl = (bit(9) ? EVP_F_WATER_IS_OCN : 0u) | (bit(10) ? EVP_F_TBU_ZERO : 0u);
+        const Res2Facts f{bit(0), cap, logw, bit(1), bit(2) ? 1 : 2, bit(3), bit(4), bit(5), bit(6), bit(7), bit(8), fl, bit(11), bit(12), bit(13), bit(14), bit(15), bit(16), bit(17), hooks};
+        const Res2Choice c = res2_choose(f);
+        chosen[e] = (unsigned)c.v.strict | c.v.remote << 1 | c.v.coop << 2 | c.v.lean << 3 | c.v.rimu << 4 | c.rim_tables << 5 | (unsigned)c.v.logw << 8 | (unsigned)(c.v.cap + 1) << 16;
+    }
+    return 0;
+}
+
+// Host-only: 1 where the table of evp_resident2.hip has the instantiation
+int cice_evp_hip_debug_res2_built(int32_t strict, int32_t cap, int32_t logw, int32_t remote, int32_t coop, int32_t lean, int32_t rimu)
+{
+    return evp_resident2_kernel({strict != 0, cap, logw, remote != 0, coop != 0, lean != 0, rimu != 0}) != nullptr;
 }
 
 // Host-only: build the halo plan for `dims` without touching a device (tests).

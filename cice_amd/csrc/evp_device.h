@@ -92,7 +92,7 @@ struct EvpResident2 {
     const uint8_t *nlate;      // [ntiles] COOP: rim T-cells with ice = the first nlate entries of perm (<= 64); NULL: the variant is off
     int *cuload;               // [2048][8] per-CU record of the launch: lock, stamp, ice-holding waves per SIMD
     unsigned long long *prof;  // NULL, or [ntiles][4 chunks][8]: cycles per phase (tools)
-    int dbg;                   // timing experiments only (CICE_EVP_HIP_RES_DEBUG; WRONG results): 1 no tag check, 2 no ring loads, 4 longer sleep; 8 = every fourth tile lags 10 us per subcycle (results stay right); 16 = tile 1 never runs (every wait on it gives up); A/B switches, results stay right: 32 = 16 x 16 tiles without the rim-wave split, 64 = without the per-CU SIMD balancing, 1024 = the lean loops' square roots and divisions always the compiler's (evp_range_math.h), 2048 | 4096 = the rim-wave schedule's priority form (0..3) << 11, 8192 = its full tiles skip the per-CU lock, 16384 = its U-cells' divisions on the cores with the reciprocal formed early (all three set by the host from their switches, never from RES_DEBUG's value alone)
+    int dbg;                   // test hooks and A/B switches: EVP_RES2_HOOK_* below
     int par0;                  // which of rec[0/1] holds the records of subcycle index 0 of THIS launch
                                // (flips so that a launch never starts in the buffer the previous one ended in)
     // neighbours on other GPUs (ring entries with z == -2 are produced there); rimg == NULL: none
@@ -140,13 +140,50 @@ struct EvpResident2 {
 hipError_t evp_range_math_probe(long long n, const double *x, const double *num, const double *den, double *sqrt_lib, double *sqrt_core,
                                 double *div_lib, double *div_core, unsigned char *verdict, hipStream_t st);
 #endif
-int evp_resident2_max_blocks_per_cu(bool strict, int cap, unsigned flags, int logw, bool remote, bool coop = false);
-bool evp_resident2_coop_built(bool strict, int cap, int logw, bool remote);   // the rim-cells-by-corners variant exists for this combination
-bool evp_resident2_lean_built(bool strict, int cap, int logw, bool remote);   // the lean variant (one rank, no fold, ...) exists
-// lean: 0 the general kernel; 1 the caller has checked what the lean variant fixes (evp_host_resident.cpp, launch_resident2);
-// 2 the same on the rim-wave schedule (RIMU), R.perm / R.uperm / R.nact from rim_plan.h
-void evp_launch_resident2(const EvpArgs &A, const EvpResident2 &R, int max_ni, int max_nj, int logw,
-                          bool strict, int cap, int lean, hipStream_t st);
+// EvpResident2::dbg, bit by bit.  CICE_EVP_HIP_RES_DEBUG (test build) sets the hooks by these numbers; the last four A/B switches
+// are set by the host from switches of their own (evp_host_resident.cpp), never from RES_DEBUG's value alone.
+enum : int {
+    // timing experiments only: WRONG results
+    EVP_RES2_HOOK_NO_TAG_CHECK = 1,      // a polled record is taken whatever its tag
+    EVP_RES2_HOOK_NO_RING_LOADS = 2,     // the ring is not polled at all
+    EVP_RES2_HOOK_LONG_SLEEP = 4,        // longer sleep between two looks at a record
+    // robustness tests: results stay right
+    EVP_RES2_HOOK_LAG = 8,               // every fourth tile lags 10 us per subcycle
+    EVP_RES2_HOOK_ABSENT_TILE = 16,      // tile 1 never runs in a real launch (every wait on it gives up)
+    EVP_RES2_HOOK_LAG_NO_UCELL = 256,    // the tiles without U-cells lag likewise (where they run: the next hook)
+    EVP_RES2_HOOK_KEEP_NO_UCELL = 512,   // the tiles without U-cells run as they used to
+    // A/B switches: results stay right
+    EVP_RES2_HOOK_NO_RIM_SPLIT = 32,     // 16 x 16 tiles without the rim-wave split
+    EVP_RES2_HOOK_NO_BALANCE = 64,       // ... without the per-CU SIMD balancing
+    EVP_RES2_HOOK_NO_RANGE = 1024,       // the lean loops' square roots and divisions always the compiler's (evp_range_math.h)
+    EVP_RES2_HOOK_PRIO_SHIFT = 11,       // the rim-wave schedule's priority form (0..3) << 11 ...
+    EVP_RES2_HOOK_PRIO_MASK = 3 << 11,   // ... = bits 2048 | 4096
+    EVP_RES2_HOOK_NOLOCK = 8192,         // the rim-wave schedule's full tiles skip the per-CU lock
+    EVP_RES2_HOOK_SPLITDIV = 16384,      // its U-cells' divisions on the cores with the reciprocal formed early
+    EVP_RES2_HOOK_HOST_OWNED = EVP_RES2_HOOK_NO_RANGE | EVP_RES2_HOOK_PRIO_MASK | EVP_RES2_HOOK_NOLOCK | EVP_RES2_HOOK_SPLITDIV,
+    EVP_RES2_HOOK_BARS_RIMU = EVP_RES2_HOOK_NO_RIM_SPLIT | EVP_RES2_HOOK_LAG_NO_UCELL | EVP_RES2_HOOK_KEEP_NO_UCELL,
+};      // (BARS_RIMU: no rim-wave schedule with the hooks that undo the rim-wave split or keep tiles without U-cells)
+// One instantiation of evp_resident2_tile, by its template arguments (evp_resident2.hip: REMOTE, COOP, LEAN, RIMU).  That file
+// holds the one table of those that are built; res2_choose (res2_variant.cpp) names the one a launch runs.  COOP measured slower
+// wherever two or three tiles share a CU (HISTORY.md, round 5): test build only, an A/B switch (CICE_EVP_HIP_RES_COOP=1, tools/coop_ab.py)
+struct Res2Variant { bool strict; int cap; int logw; bool remote, coop, lean, rimu; };
+const void *evp_resident2_kernel(const Res2Variant &v);       // the kernel's host address; null: not built
+// workgroups of one CU; a general variant is admitted against the smallest of the general, lean and rim-wave kernels it may launch
+int evp_resident2_max_blocks_per_cu(const Res2Variant &v, unsigned flags);
+hipError_t evp_launch_resident2(const EvpArgs &A, const EvpResident2 &R, int max_ni, int max_nj, const Res2Variant &v, hipStream_t st);
+// Which variant a launch runs: host only, no HIP call, no global -- the caller states the facts (evp_host_resident.cpp: launch_resident2)
+struct Res2Facts {
+    bool strict; int cap, logw;      // arithmetic variant (cap_mode) and tile shape
+    bool remote; int nblocks;        // neighbours on other GPUs read this rank's records; CICE blocks of this rank
+    bool seam, tfold, img3, rimg, rraw;     // the launch carries that table (EvpResident2)
+    bool revp_zero; unsigned flags;  // EVP_F_*
+    bool coop_ok, coop_built, coop_fits;    // every tile's rim list fits its 64 quads; the table has the variant; the chip takes all its tiles
+    bool rimu_ok;                    // every tile's lane tables satisfy the rim-wave schedule's rules (rim_plan.h)
+    bool want_coop, want_lean, want_rimu;   // the switches RES_COOP, RES_LEAN, RES_RIMU
+    int hooks;                       // RES_DEBUG's value (EVP_RES2_HOOK_*)
+};
+struct Res2Choice { Res2Variant v; bool rim_tables; };     // rim_tables: perm / uperm / nact are rim_plan's, not resident2_order's
+Res2Choice res2_choose(const Res2Facts &f);
 
 // Several (2 .. 4) subcycles per pass over a device-private strip-major layout (evp_march.hip, evp_host_march.cpp)
 #ifndef EVP_MARCH_PAD          // (a build-time A/B: -DEVP_MARCH_PAD=3 makes three the most subcycles per pass, strips of 58)

@@ -376,6 +376,7 @@ inline const char *env(const char *k) { return std::getenv(k); }
 // a switch's value as env() / env_test() hand it over (null: not set -> dflt): on unless 0 / as a number
 inline bool env_on(const char *value, bool dflt) { return value ? std::atoi(value) != 0 : dflt; }
 inline int env_int(const char *value, int dflt) { return value ? std::atoi(value) : dflt; }
+inline double env_double(const char *value, double dflt) { return value ? std::atof(value) : dflt; }
 constexpr int ENV_UNSET = INT_MIN;      // env_int's dflt where "not set" is a third answer
 
 // mailbox layout: EVP_DIRECT_MAXPEER flag lines, then seq, err, then the inbox
@@ -452,6 +453,9 @@ bool use_riding_exchange();
 int get_tile_split(int variant, State::TileSplit **out);
 int enqueue_loop(int ndte, int cur0);
 // evp_host_resident.cpp
+int bgrid_resident_switch();      // its switches that other files ask as well: CICE_EVP_HIP_RESIDENT (-1: not set),
+int res_logw_switch();            // a forced tile shape (test build; 0: none),
+double halo_timeout_ms();         // the bound of a wait on another rank
 bool tripole_seam();
 bool resident_possible(bool with_peers = false);
 int resident2_setup(int logw);

@@ -76,7 +76,7 @@ static void *mapped_view(const void *host, size_t bytes)
 
 static int run_batch(CopyBatch &B, bool to_device)
 {
-    const bool off = env_test("CICE_EVP_HIP_GATHER") && !std::atoi(env_test("CICE_EVP_HIP_GATHER"));
+    const bool off = !env_on(env_test("CICE_EVP_HIP_GATHER"), true);
     EvpCopyTab T{};
     T.len = S.n;
     T.vec2 = 1;
@@ -107,7 +107,7 @@ static int run_batch(CopyBatch &B, bool to_device)
 // every host array of the batch lies in a range the caller page-locked and mapped (and the gather path is on)
 bool batch_mapped(const CopyBatch &B, bool to_device)
 {
-    if (env_test("CICE_EVP_HIP_GATHER") && !std::atoi(env_test("CICE_EVP_HIP_GATHER"))) return false;
+    if (!env_on(env_test("CICE_EVP_HIP_GATHER"), true)) return false;
     for (auto &it : B.items)
         if (!mapped_view(to_device ? (const void *)it.second : (const void *)it.first, S.n * sizeof(double))) return false;
     return true;
@@ -195,7 +195,7 @@ int upload_lists()
     if (up(P.late_sign, S.h_late_sign)) return -1;
     S.n_fin = (int)P.fin_dst.size();
     // the list is only run on layouts that split the seam row (halo_uv: general form) or when forced for tests
-    const bool fin_used = P.tail > 0 || (env_test("CICE_EVP_HIP_SEAM_FIN") && std::atoi(env_test("CICE_EVP_HIP_SEAM_FIN")));
+    const bool fin_used = P.tail > 0 || env_on(env_test("CICE_EVP_HIP_SEAM_FIN"), false);
     if (fin_used && S.n_fin > evp_halo_seam_fin_capacity()) return fail(-3, "tripole seam: %d cells to finalise on one rank (limit %d)", S.n_fin, evp_halo_seam_fin_capacity());
     if (up(P.fin_dst, S.h_fin_dst) || up(P.fin_a, S.h_fin_a) || up(P.fin_b, S.h_fin_b)) return -1;
     if (up(P.fin_coef, S.h_fin_coef)) return -1;
@@ -315,7 +315,7 @@ void fill_args(EvpArgs &A, int cur, int last)
 // exactly 1.0 / sums with exactly 0.0 the kernels then leave out, bit-neutral (CICE_EVP_HIP_SIMPLE=0: off)
 int cap_mode()
 {
-    const bool simple_ok = !(env_test("CICE_EVP_HIP_SIMPLE") && !std::atoi(env_test("CICE_EVP_HIP_SIMPLE")));
+    const bool simple_ok = env_on(env_test("CICE_EVP_HIP_SIMPLE"), true);
     if (simple_ok && S.prm.capping == 1.0 && S.prm.revp == 0.0 && S.prm.Ktens == 0.0 && S.prm.cosw == 1.0 &&
         S.prm.sinw == 0.0)
         return 3;

@@ -46,8 +46,7 @@ int direct_export(HaloBlob &B)
     // resident kernel across GPUs: its record buffers must be writable by the neighbours, so they
     // live in the mailbox allocation (one IPC handle)
     bool want_res = resident_possible(true) && !S.plan.peers.empty() &&
-                    !(env("CICE_EVP_HIP_RESIDENT") && std::atoi(env("CICE_EVP_HIP_RESIDENT")) == 0) &&
-                    !(env_test("CICE_EVP_HIP_RES_REMOTE") && std::atoi(env_test("CICE_EVP_HIP_RES_REMOTE")) == 0);
+                    bgrid_resident_switch() != 0 && env_on(env_test("CICE_EVP_HIP_RES_REMOTE"), true);
     size_t rec_off = 0;
     const size_t rec_stride = S.n * 32;            // one 32-byte record pair per cell of every block
     const size_t raw_stride = (S.n + (size_t)S.plan.tail) * 32;   // raw seam records: the cells + the staging slots of remote partners
@@ -80,7 +79,7 @@ int direct_export(HaloBlob &B)
             S.res2_rec_raw[0] = (char *)X.mailbox + X.raw_off;
             S.res2_rec_raw[1] = (char *)X.mailbox + X.raw_off + raw_stride;
         }
-        const int forced_w = env_test("CICE_EVP_HIP_RES_LOGW") ? std::atoi(env_test("CICE_EVP_HIP_RES_LOGW")) : 0;
+        const int forced_w = res_logw_switch();
         for (int logw : {4, 5, 6}) {
             if (forced_w && logw != forced_w) continue;
             if (resident2_setup(logw)) continue;

@@ -577,8 +577,7 @@ static int march_direct_setup()
         D.err = (int *)(mine + err_off);
         D.inbox = (const double *)(mine + inbox_off);
         D.inbox_pstride = par_doubles;
-        const double tmo_ms = env("CICE_EVP_HIP_HALO_TIMEOUT_MS") ? std::atof(env("CICE_EVP_HIP_HALO_TIMEOUT_MS")) : 30000.0;
-        D.timeout_ticks = (unsigned long long)(tmo_ms * 1.0e5);
+        D.timeout_ticks = (unsigned long long)(halo_timeout_ms() * 1.0e5);
         B.dx = D;
     }
     // everybody or nobody

@@ -5,6 +5,22 @@
 
 namespace evp_host {
 
+// ---- switches: each is read here and nowhere else.  env_test(): the test build only (evp_host.h) ----
+int bgrid_resident_switch() { return env_int(env("CICE_EVP_HIP_RESIDENT"), -1); }     // 0 / 1 forces the verdict
+double halo_timeout_ms() { return env_double(env("CICE_EVP_HIP_HALO_TIMEOUT_MS"), 30000.0); }   // bound of a wait on another rank
+int res_logw_switch() { return env_int(env_test("CICE_EVP_HIP_RES_LOGW"), 0); }       // 4 / 5 / 6: that tile shape only
+static bool coop_switch() { return env_on(env_test("CICE_EVP_HIP_RES_COOP"), EVP_RES2_COOP_DEFAULT != 0); }
+static bool prof_switch() { return env_on(env_test("CICE_EVP_HIP_RES_PROF"), false); }
+static int debug_hooks() { return env_int(env_test("CICE_EVP_HIP_RES_DEBUG"), 0); }   // EVP_RES2_HOOK_* (evp_device.h)
+static bool lean_switch() { return env_on(env_test("CICE_EVP_HIP_RES_LEAN"), true); }      // =0: never the lean variant
+static bool rimu_switch() { return env_on(env_test("CICE_EVP_HIP_RES_RIMU"), EVP_RES2_RIMU_DEFAULT != 0); }    // A/B: the rim-wave schedule
+static bool order_switch() { return env_on(env_test("CICE_EVP_HIP_RES_ORDER"), true); }    // =0: tiles in their natural order
+// A/B switches of the lean loops (evp_device.h: EVP_RES2_*_DEFAULT, which the product compiles in; EVP_RES2_HOOK_*)
+static bool range_switch() { return env_on(env_test("CICE_EVP_HIP_RES_RANGE"), EVP_RES2_RANGE_DEFAULT != 0); }
+static int prio_switch() { return std::min(3, std::max(0, env_int(env_test("CICE_EVP_HIP_RES_PRIO"), EVP_RES2_PRIO_DEFAULT))); }
+static bool nolock_switch() { return env_on(env_test("CICE_EVP_HIP_RES_NOLOCK"), EVP_RES2_NOLOCK_DEFAULT != 0); }
+static bool splitdiv_switch() { return env_on(env_test("CICE_EVP_HIP_RES_SPLITDIV"), EVP_RES2_SPLITDIV_DEFAULT != 0); }
+
 // ---- on-chip resident subcycle -------------------------------------------------------
 // (a rank of a fold row split in x may hold neither a pole point nor a pair with both halves: its seam cells are the plan's
 // general list then -- 3 x 1 and 4 x 1 cuts of tx1 showed it: two of the ranks ran without any fold handling)
@@ -255,7 +271,7 @@ bool resident2_fits(bool remote)
     if (cap < 0) {
         hipDeviceProp_t prop;
         if (hipGetDeviceProperties(&prop, S.device) != hipSuccess) return false;
-        const int per_cu = std::min(evp_resident2_max_blocks_per_cu(S.prm.strict != 0, cap_mode(), fl, S.res2_logw, remote), 8);
+        const int per_cu = std::min(evp_resident2_max_blocks_per_cu({S.prm.strict != 0, cap_mode(), S.res2_logw, remote, false, false, false}, fl), 8);
         cap = (long)per_cu * prop.multiProcessorCount;
         known.push_back(Key{S.device, S.res2_logw, S.prm.strict != 0, cap_mode(), fl, remote, cap});
     }
@@ -284,7 +300,7 @@ bool resident2_fits_now()
 //    CU with the most ice-holding waves paces the grid.  Workgroup w lands on CU w mod #CUs (observed
 //    breadth-first placement, tools/wg_placement.hip; used for speed only): longest-processing-time
 //    assignment of tiles to CUs with the slots each CU gets, heaviest tile of a CU first.
-//    CICE_EVP_HIP_RES_ORDER=0 keeps the natural order.
+//    order_switch() off keeps the natural order.
 int resident2_order()
 {
     if (S.res2_order && !S.res2_order_stale && S.res2_order_for == S.res2_logw) return 0;
@@ -361,8 +377,8 @@ int resident2_order()
         // records; never a tile without U-cells (it leaves at once anyway)
         const bool no_ucell = i0 > S.ihi[b] || j0 > S.jhi[b];
         live[t] = !no_ucell && (n > 0 || S.res2_always_h[t] || !S.plan.peers.empty()) ? 1 : 0;
-        // (test build, RES_DEBUG bit 512: the tiles without U-cells run as they used to -- the hazard they were, evp_resident2.hip)
-        if (no_ucell && env_test("CICE_EVP_HIP_RES_DEBUG") && (std::atoi(env_test("CICE_EVP_HIP_RES_DEBUG")) & 512)) live[t] = 1;
+        // (test hook: the tiles without U-cells run as they used to -- the hazard they were, evp_resident2.hip)
+        if (no_ucell && (debug_hooks() & EVP_RES2_HOOK_KEEP_NO_UCELL)) live[t] = 1;
     }
     std::vector<int> run;
     for (int t = 0; t < ntiles; ++t)
@@ -381,10 +397,9 @@ int resident2_order()
     }
     S.res2_rimu_ok = rimu_ok;
     S.res2_coop_ok = coop_ok;
-    const bool off = env_test("CICE_EVP_HIP_RES_ORDER") && !std::atoi(env_test("CICE_EVP_HIP_RES_ORDER"));
     std::vector<int> order((size_t)ntiles, 0);
     for (int w = 0; w < nrun; ++w) order[w] = run[w];
-    if (!off) {
+    if (order_switch()) {
         hipDeviceProp_t prop;
         int ncu = 256;
         if (hipGetDeviceProperties(&prop, S.device) == hipSuccess && prop.multiProcessorCount > 0) ncu = prop.multiProcessorCount;
@@ -417,6 +432,7 @@ int resident2_order()
     return 0;
 }
 
+// Three steps: the operands, the variant (res2_choose) with the tables it binds, the launch
 int launch_resident2(int ndte, int cur0, bool dry)
 {
     if (ndte >= 4096) return fail(-6, "resident2: ndte must be < 4096");
@@ -425,95 +441,63 @@ int launch_resident2(int ndte, int cur0, bool dry)
     EvpArgs A;
     fill_args(A, cur0, 1);
     EvpResident2 R;
-    R.ndte = ndte;
-    R.cur0 = dry ? 0 : cur0;
-    R.dry = dry ? 1 : 0;
+    R.ndte = ndte; R.cur0 = dry ? 0 : cur0; R.dry = dry ? 1 : 0;
     S.res2_epoch = (S.res2_epoch + 1u) & 0xFFFFFu;
     if (S.res2_epoch == 0) S.res2_epoch = 1;
     R.tag_base = S.res2_epoch << 12;
     R.par0 = S.res2_par;
     S.res2_par = (S.res2_par + ndte + 1) & 1;     // never start in the buffer the previous launch ended in
-    R.nblocks = S.d.nblocks;
-    R.order = S.res2_order;
-    R.nlaunch = S.res2_nlive;
+    R.nblocks = S.d.nblocks; R.order = S.res2_order; R.nlaunch = S.res2_nlive; R.celltile = S.res2_celltile;
     R.live = S.plan.peers.empty() ? S.res2_live : nullptr;
-    R.celltile = S.res2_celltile;
-    R.perm = S.res2_perm;
-    R.late_waves = S.res2_late;
-    R.nact = S.res2_nact;
-    // rim T-cells by corners (COOP): where the variant is built, every tile's rim list fits its 64 quads and the chip still
-    // takes all tiles at once with the variant's larger LDS share (the same rule as resident2_fits)
-    {
-        const int want = env_test("CICE_EVP_HIP_RES_COOP") ? std::atoi(env_test("CICE_EVP_HIP_RES_COOP")) : EVP_RES2_COOP_DEFAULT;
-        bool can = want != 0 && S.res2_coop_ok && S.res2_logw == 4 && !S.res_remote &&
-                   evp_resident2_coop_built(S.prm.strict != 0, cap_mode(), S.res2_logw, false);
-        if (can) {
-            hipDeviceProp_t prop;
-            const int per_cu = std::min(evp_resident2_max_blocks_per_cu(S.prm.strict != 0, cap_mode(), A.flags, 4, false, true), 8);
-            can = hipGetDeviceProperties(&prop, S.device) == hipSuccess &&
-                  (long)std::max(S.res2_nlive, 1) * 10 <= (long)per_cu * prop.multiProcessorCount * 9;
-        }
-        S.res2_coop = can ? 1 : 0;
-        R.nlate = can ? S.res2_nlate : nullptr;
-    }
-    R.cuload = S.res2_cuload;
+    R.late_waves = S.res2_late; R.cuload = S.res2_cuload;
     R.prof = nullptr;
-    if (S.res2_logw == 4 && env_test("CICE_EVP_HIP_RES_PROF") && std::atoi(env_test("CICE_EVP_HIP_RES_PROF"))) {
+    if (S.res2_logw == 4 && prof_switch()) {
         if (!S.res2_prof && S.mem.alloc(S.res2_prof, (size_t)S.res2_ntiles * 32)) return -1;
         HIPC(hipMemsetAsync(S.res2_prof, 0, (size_t)S.res2_ntiles * 32 * sizeof(unsigned long long), S.stream));
         R.prof = S.res2_prof;
     }
-    const int dbg2 = env_test("CICE_EVP_HIP_RES_DEBUG") ? std::atoi(env_test("CICE_EVP_HIP_RES_DEBUG")) : 0;
-    // range-proved square roots and divisions in the lean loops (CICE_EVP_HIP_RES_RANGE=1/0, test build: A/B; the product's
-    // kernel is compiled with or without them, EVP_RES2_RANGE_DEFAULT, and tests nothing)
-    const int want_range = env_test("CICE_EVP_HIP_RES_RANGE") ? std::atoi(env_test("CICE_EVP_HIP_RES_RANGE")) : EVP_RES2_RANGE_DEFAULT;
-    // the rim-wave schedule's issue priorities and its full tiles' way round the per-CU lock, likewise (CICE_EVP_HIP_RES_PRIO=0..3,
-    // CICE_EVP_HIP_RES_NOLOCK=1/0, test build: A/B; the product compiles EVP_RES2_PRIO_DEFAULT / EVP_RES2_NOLOCK_DEFAULT in)
-    const int want_prio = std::min(3, std::max(0, env_int(env_test("CICE_EVP_HIP_RES_PRIO"), EVP_RES2_PRIO_DEFAULT)));
-    const bool want_nolock = env_on(env_test("CICE_EVP_HIP_RES_NOLOCK"), EVP_RES2_NOLOCK_DEFAULT != 0);
-    // ... and its U-cells' divisions on the cores with the reciprocal formed early (CICE_EVP_HIP_RES_SPLITDIV=1/0; EVP_RES2_SPLITDIV_DEFAULT)
-    const bool want_split = env_on(env_test("CICE_EVP_HIP_RES_SPLITDIV"), EVP_RES2_SPLITDIV_DEFAULT != 0);
-    R.dbg = (dbg2 & ~(2048 | 4096 | 8192 | 16384)) | (want_range ? 0 : 1024) | (want_prio << 11) | (want_nolock ? 8192 : 0) |
-            (want_split ? 16384 : 0);
-    R.seam = S.res2_seam;
-    R.tfold = S.plan.tfold ? 1 : 0;
-    R.img3 = S.res2_img3;
-    R.rec_raw[0] = S.res2_rec_raw[0];
-    R.rec_raw[1] = S.res2_rec_raw[1];
-    R.rimg = S.res_remote ? S.res2_rimg : nullptr;
-    R.peer_rec = S.res2_peer_rec;
-    R.peer_rstride = S.res2_peer_rstride;
-    R.rraw = S.res_remote ? S.res2_rraw : nullptr;
-    R.peer_raw = S.res2_peer_raw;
-    R.peer_raw_stride = S.res2_peer_raw_stride;
-    const double tmo_ms = env("CICE_EVP_HIP_HALO_TIMEOUT_MS") ? std::atof(env("CICE_EVP_HIP_HALO_TIMEOUT_MS")) : 30000.0;
-    R.timeout_ticks = (unsigned long long)((S.res_timeout_ms > 0 ? S.res_timeout_ms : tmo_ms) * 1.0e5);
+    // the test hooks by their numbers; the A/B switches of the lean loops from switches of their own
+    R.dbg = (debug_hooks() & ~EVP_RES2_HOOK_HOST_OWNED) | (range_switch() ? 0 : EVP_RES2_HOOK_NO_RANGE) |
+            (prio_switch() << EVP_RES2_HOOK_PRIO_SHIFT) | (nolock_switch() ? EVP_RES2_HOOK_NOLOCK : 0) |
+            (splitdiv_switch() ? EVP_RES2_HOOK_SPLITDIV : 0);
+    R.seam = S.res2_seam; R.tfold = S.plan.tfold ? 1 : 0; R.img3 = S.res2_img3;
+    R.rec_raw[0] = S.res2_rec_raw[0]; R.rec_raw[1] = S.res2_rec_raw[1];
+    R.rimg = S.res_remote ? S.res2_rimg : nullptr; R.peer_rec = S.res2_peer_rec; R.peer_rstride = S.res2_peer_rstride;
+    R.rraw = S.res_remote ? S.res2_rraw : nullptr; R.peer_raw = S.res2_peer_raw; R.peer_raw_stride = S.res2_peer_raw_stride;
+    R.timeout_ticks = (unsigned long long)((S.res_timeout_ms > 0 ? S.res_timeout_ms : halo_timeout_ms()) * 1.0e5);
     R.spin_limit = 4000000u;
     R.err = S.res_err;
-    R.pubmap = S.res2_pub;
-    R.ring = S.res2_ring;
-    R.ring_cnt = S.res2_cnt;
-    R.rec[0] = S.res2_rec[0];
-    R.rec[1] = S.res2_rec[1];
+    R.pubmap = S.res2_pub; R.ring = S.res2_ring; R.ring_cnt = S.res2_cnt;
+    R.rec[0] = S.res2_rec[0]; R.rec[1] = S.res2_rec[1];
     if (dry) {   // inputs come from the current state, nothing is written back
         R.u[0] = S.u[cur0]; R.v[0] = S.v[cur0]; R.u[1] = S.u[cur0]; R.v[1] = S.v[cur0];
     } else {
         R.u[0] = S.u[0]; R.v[0] = S.v[0]; R.u[1] = S.u[1]; R.v[1] = S.v[1];
     }
     R.tab = S.res_tab + (dry ? 28 * (1 + cur0) : 0);
-    // the lean variant where nothing it leaves out can happen in this launch (CICE_EVP_HIP_RES_LEAN=0, test build: never)
-    const bool lean = evp_resident2_lean_built(S.prm.strict != 0, cap_mode(), S.res2_logw, R.rimg != nullptr) &&
-                      R.nblocks == 1 && !R.seam && !R.tfold && !R.img3 && !R.rimg && !R.rraw && !R.nlate &&
-                      A.p.revp == 0.0 && (A.flags & EVP_F_WATER_IS_OCN) && (A.flags & EVP_F_TBU_ZERO) &&
-                      !(env_test("CICE_EVP_HIP_RES_LEAN") && !std::atoi(env_test("CICE_EVP_HIP_RES_LEAN")));
-    // ... on the rim-wave schedule where every tile's lane tables satisfy its rules (CICE_EVP_HIP_RES_RIMU=1/0, test build: A/B)
-    const int want_rimu = env_test("CICE_EVP_HIP_RES_RIMU") ? std::atoi(env_test("CICE_EVP_HIP_RES_RIMU")) : EVP_RES2_RIMU_DEFAULT;
-    // (not with the test hooks that undo the rim-wave split or keep tiles without U-cells)
-    const bool rimu = lean && want_rimu != 0 && S.res2_rimu_ok && !(dbg2 & (32 | 256 | 512));
-    R.uperm = nullptr;
-    if (rimu) { R.perm = S.res2_perm_rim; R.uperm = S.res2_uperm; R.nact = S.res2_nact_rim; }
-    S.res2_rimu = rimu ? 1 : 0;
-    evp_launch_resident2(A, R, S.max_ni, S.max_nj, S.res2_logw, S.prm.strict != 0, cap_mode(), rimu ? 2 : lean ? 1 : 0, S.stream);
+    // ---- the variant: the facts, the chooser's answer
+    Res2Facts F{};
+    F.strict = S.prm.strict != 0; F.cap = cap_mode(); F.logw = S.res2_logw; F.remote = S.res_remote;
+    F.nblocks = R.nblocks; F.seam = R.seam != nullptr; F.tfold = R.tfold != 0; F.img3 = R.img3 != nullptr;
+    F.rimg = R.rimg != nullptr; F.rraw = R.rraw != nullptr; F.revp_zero = A.p.revp == 0.0; F.flags = A.flags;
+    F.coop_ok = S.res2_coop_ok; F.rimu_ok = S.res2_rimu_ok; F.coop_fits = true;      // (the device is asked below, where all else says COOP)
+    F.coop_built = evp_resident2_kernel({F.strict, F.cap, F.logw, F.rimg, true, false, false}) != nullptr;
+    F.want_coop = coop_switch(); F.want_lean = lean_switch(); F.want_rimu = rimu_switch(); F.hooks = debug_hooks();
+    Res2Choice c = res2_choose(F);
+    if (c.v.coop) {       // the chip still takes all tiles at once with the variant's larger LDS share (the same rule as resident2_fits)
+        hipDeviceProp_t prop;
+        const int per_cu = std::min(evp_resident2_max_blocks_per_cu(c.v, A.flags), 8);
+        F.coop_fits = hipGetDeviceProperties(&prop, S.device) == hipSuccess &&
+                      (long)std::max(S.res2_nlive, 1) * 10 <= (long)per_cu * prop.multiProcessorCount * 9;
+        c = res2_choose(F);
+    }
+    // ---- its tables, and the launch
+    R.perm = c.rim_tables ? S.res2_perm_rim : S.res2_perm;
+    R.uperm = c.rim_tables ? S.res2_uperm : nullptr;
+    R.nact = c.rim_tables ? S.res2_nact_rim : S.res2_nact;
+    R.nlate = c.v.coop ? S.res2_nlate : nullptr;
+    S.res2_coop = c.v.coop ? 1 : 0; S.res2_rimu = c.v.rimu ? 1 : 0;
+    HIPC(evp_launch_resident2(A, R, S.max_ni, S.max_nj, c.v, S.stream));
     HIPC(hipGetLastError());
     return 0;
 }
@@ -596,14 +580,13 @@ int tune_after_upload()
     // (same work, nothing written back) runs clean and faster than the streaming kernel
     if (S.res_mode < 0) {
         S.res_mode = 0;
-        int want = -1;
-        if (env("CICE_EVP_HIP_RESIDENT")) want = std::atoi(env("CICE_EVP_HIP_RESIDENT"));
+        const int want = bgrid_resident_switch();
         if (want != 0 && S.res_remote && S.direct.on) {
             // neighbours on other GPUs: tile shape fixed at export, no timing probes (every launch
             // of this kernel is collective across ranks)
             S.res_mode = 1;
         } else if (want != 0 && resident_possible()) {
-            const int forced_w = env_test("CICE_EVP_HIP_RES_LOGW") ? std::atoi(env_test("CICE_EVP_HIP_RES_LOGW")) : 0;
+            const int forced_w = res_logw_switch();
             float best = 1e30f;
             int best_w = 0;
             bool any_fit = false;

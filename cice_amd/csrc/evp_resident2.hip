@@ -170,7 +170,7 @@ constexpr int QP_X1 = 0xB1, QP_X2 = 0x4E, QP_X3 = 0x1B;      // quad_perm [1,0,3
 // operands and signs selected per lane, the operations and their order those of stress_cell: a - b*c == a + (-b)*c, x + y == y + x
 // bit for bit), fetches the other three corners' stresses with quad-permute moves, and forms the two stress-divergence partials
 // that carry its corner's coefficients.  The cell's stresses live three per lane in those quads for the whole call.
-// LEAN (one rank and block, no fold, TbU == 0, water == ocean current, revp == 0; evp_resident2_lean_built): none of the code for
+// LEAN (one rank and block, no fold, TbU == 0, water == ocean current, revp == 0; res2_choose, res2_variant.cpp): none of the code for
 // the other cases is in the subcycle loop, which runs two subcycles per trip (one per record buffer), the record loads and stores
 // addressed as scalar buffer base + lane offset.  Same operations in the same order => same bits
 // (profiles/r07_resident_lean_*.txt, tools/resident_isa_mix.py).
@@ -179,7 +179,7 @@ constexpr int QP_X1 = 0xB1, QP_X2 = 0x4E, QP_X3 = 0x1B;      // quad_perm [1,0,3
 // Range-proved arithmetic (the two lean loops; evp_range_math.h, profiles/r15_resident_range_math.txt): a wave whose active lanes
 // all have their operands inside a window of exponents takes the cores of the fp64 square root and division without the range
 // handling the compiler wraps them in, any other wave the compiler's forms -- per pass, a uniform branch, the same bits.  The
-// product compiles it in or out (EVP_RES2_RANGE_DEFAULT); the test build carries it with a switch (RES_DEBUG bit 1024: always the
+// product compiles it in or out (EVP_RES2_RANGE_DEFAULT); the test build carries it with a switch (EVP_RES2_HOOK_NO_RANGE: always the
 // compiler's forms; CICE_EVP_HIP_RES_RANGE=0 sets it).
 template <bool STRICT, int CAP, int LOGW, bool REMOTE, bool COOP = false, bool LEAN = false, bool RIMU = false>
 __global__ __launch_bounds__(64 * RTY, REMOTE ? 2 : 3) void evp_resident2_tile(EvpArgs A, EvpResident2 R)
@@ -196,7 +196,7 @@ __global__ __launch_bounds__(64 * RTY, REMOTE ? 2 : 3) void evp_resident2_tile(E
     // the policy of the lean loops' arithmetic; POLE: the same with taubx / tauby formed every subcycle (the first lean loop)
     // SPLIT (the rim-wave schedule): the U-cell's two divisions on the cores, their reciprocal formed in the first part of the
     // momentum step, which the rim wave runs off the hand-off chain (EVP_RES2_SPLITDIV_DEFAULT; the test build carries it with a
-    // switch, RES_DEBUG bit 16384, CICE_EVP_HIP_RES_SPLITDIV)
+    // switch, EVP_RES2_HOOK_SPLITDIV, CICE_EVP_HIP_RES_SPLITDIV)
 #ifdef CICE_EVP_HIP_TESTING
     constexpr bool SPLIT = true;
 #else
@@ -244,9 +244,9 @@ __global__ __launch_bounds__(64 * RTY, REMOTE ? 2 : 3) void evp_resident2_tile(E
         // on a single rank the call then fell back to the streaming kernel, across ranks it failed).
         const int pb = A.gx * A.gy;
         const int4 rb = A.blk[tile / pb];
-        // (test build, RES_DEBUG bit 512: keep them, bit 256: and let them lag -- to show the hazard, tests/test_gpu_parity.py)
+        // (test build, EVP_RES2_HOOK_KEEP_NO_UCELL: keep them, EVP_RES2_HOOK_LAG_NO_UCELL: and let them lag -- to show the hazard, tests/test_gpu_parity.py)
         no_ucell = rb.x + ((tile % pb) % A.gx) * (W - 1) > rb.y || rb.z + ((tile % pb) / A.gx) * (H - 1) > rb.w;
-        if (no_ucell && !(RES_DBG(R) & 512)) return;
+        if (no_ucell && !(RES_DBG(R) & EVP_RES2_HOOK_KEEP_NO_UCELL)) return;
     }
     // PERM: which quarter ("chunk") of the tile's permuted cell list this wave takes.  The host packs
     // the ice cells of a tile into its first chunks (a coastal tile then costs one or two waves, not
@@ -259,14 +259,14 @@ __global__ __launch_bounds__(64 * RTY, REMOTE ? 2 : 3) void evp_resident2_tile(E
     // RIMU, full tiles (all four chunks hold ice): such a tile adds one wave to every SIMD's count, so it changes no later
     // comparison and its own map is arbitrary -- it takes the identity map and leaves the per-CU record alone (no CAS, no loads,
     // no stores; the partial tiles' choices are what they were).  The product compiles it in or out (EVP_RES2_NOLOCK_DEFAULT);
-    // the test build carries a switch (RES_DEBUG bit 8192, CICE_EVP_HIP_RES_NOLOCK) and keeps the lock for every tile while the
+    // the test build carries a switch (EVP_RES2_HOOK_NOLOCK, CICE_EVP_HIP_RES_NOLOCK) and keeps the lock for every tile while the
     // stamps are on: the arrival rank feeds them.  profiles/r16_resident_rim_first.txt
 #ifdef CICE_EVP_HIP_TESTING
-    const bool skip_lock = RIMU && (RES_DBG(R) & 8192) && !RES_PROF(R);
+    const bool skip_lock = RIMU && (RES_DBG(R) & EVP_RES2_HOOK_NOLOCK) && !RES_PROF(R);
 #else
     constexpr bool skip_lock = RIMU && EVP_RES2_NOLOCK_DEFAULT;
 #endif
-    bool balance = PERM && R.cuload && !(RES_DBG(R) & 64);
+    bool balance = PERM && R.cuload && !(RES_DBG(R) & EVP_RES2_HOOK_NO_BALANCE);
     if (skip_lock && balance && R.nact[tile] == 4) balance = false;      // (uniform over the workgroup)
     if (balance) {
         const int wave = t >> 6;
@@ -336,8 +336,8 @@ __global__ __launch_bounds__(64 * RTY, REMOTE ? 2 : 3) void evp_resident2_tile(E
     // with exactly one such wave (every 16 x 16 tile: rim <= 60 cells, ring <= 64 entries) the others
     // never wait for it before their stress update ("split")
     const int late_waves = PERM ? (int)R.late_waves[tile] : 4;
-    const bool split = PERM && late_waves <= 1 && !(RES_DBG(R) & 32);
-    if ((RES_DBG(R) & 16) && tile == 1 && !R.dry) return;   // test hook: one workgroup "never becomes resident" (after the probes)
+    const bool split = PERM && late_waves <= 1 && !(RES_DBG(R) & EVP_RES2_HOOK_NO_RIM_SPLIT);
+    if ((RES_DBG(R) & EVP_RES2_HOOK_ABSENT_TILE) && tile == 1 && !R.dry) return;   // test hook: one workgroup "never becomes resident" (after the probes)
     const int per_blk = A.gx * A.gy;
     const int bz = tile / per_blk;                // CICE block of this rank
     const int bx = (tile % per_blk) % A.gx;
@@ -458,9 +458,9 @@ __global__ __launch_bounds__(64 * RTY, REMOTE ? 2 : 3) void evp_resident2_tile(E
     }
     if constexpr (POL::ranged) {
         pol.cbad = __builtin_amdgcn_ballot_w64(percall_out);
-        pol.off = (RES_DBG(R) & 1024) != 0;
+        pol.off = (RES_DBG(R) & EVP_RES2_HOOK_NO_RANGE) != 0;
 #ifdef CICE_EVP_HIP_TESTING
-        pol.nosplit = !(RES_DBG(R) & 16384);
+        pol.nosplit = !(RES_DBG(R) & EVP_RES2_HOOK_SPLITDIV);
 #endif
     }
     const POLE &pole = pol;
@@ -668,7 +668,7 @@ __global__ __launch_bounds__(64 * RTY, REMOTE ? 2 : 3) void evp_resident2_tile(E
     auto subcycle = [&](const int k, const v4u *rd, v4u *wr) -> bool {
         const unsigned want = R.tag_base + (unsigned)k;       // tag of the velocities subcycle k reads
 
-        if (((RES_DBG(R) & 8) && (tile & 3) == 1) || ((RES_DBG(R) & 256) && no_ucell)) {      // robustness test: every fourth tile lags by ~10 us per subcycle
+        if (((RES_DBG(R) & EVP_RES2_HOOK_LAG) && (tile & 3) == 1) || ((RES_DBG(R) & EVP_RES2_HOOK_LAG_NO_UCELL) && no_ucell)) {      // robustness test: every fourth tile lags by ~10 us per subcycle
             const unsigned long long t0 = wall_clock64();
             while (wall_clock64() - t0 < 1000ull) __builtin_amdgcn_s_sleep(8);
         }
@@ -679,14 +679,14 @@ __global__ __launch_bounds__(64 * RTY, REMOTE ? 2 : 3) void evp_resident2_tile(E
             if (!poll_remote(rd + 2 * (size_t)ring_cp, want, ra, rb)) s_bad = 1;
             s_u[ring_li] = unpack_rec(ra);
             s_v[ring_li] = unpack_rec(rb);
-        } else if (ring_cp >= 0 && !(RES_DBG(R) & 2)) {
+        } else if (ring_cp >= 0 && !(RES_DBG(R) & EVP_RES2_HOOK_NO_RING_LOADS)) {
             v4u ra, rb;
             unsigned spins = 0;
             if (REMOTE) t_wait0 = wall_clock64();
             for (;;) {
                 if (LEAN) ld_rec2_s(rd, ring_off, ra, rb);
                 else ld_rec2(rd + 2 * (size_t)ring_cp, ra, rb);
-                if ((ra.x == want && ra.w == want && rb.x == want && rb.w == want) || (RES_DBG(R) & 1)) break;
+                if ((ra.x == want && ra.w == want && rb.x == want && rb.w == want) || (RES_DBG(R) & EVP_RES2_HOOK_NO_TAG_CHECK)) break;
                 // a local neighbour may itself be waiting for another rank: with remote neighbours
                 // every wait is bounded by wall-clock time, not by a spin count
                 if (gave_up(++spins, t_wait0)) {
@@ -694,7 +694,7 @@ __global__ __launch_bounds__(64 * RTY, REMOTE ? 2 : 3) void evp_resident2_tile(E
                     s_bad = 1;
                     break;
                 }
-                if (RES_DBG(R) & 4) __builtin_amdgcn_s_sleep(8); else __builtin_amdgcn_s_sleep(1);
+                if (RES_DBG(R) & EVP_RES2_HOOK_LONG_SLEEP) __builtin_amdgcn_s_sleep(8); else __builtin_amdgcn_s_sleep(1);
             }
             s_u[ring_li] = unpack_rec(ra);
             s_v[ring_li] = unpack_rec(rb);
@@ -927,9 +927,9 @@ __global__ __launch_bounds__(64 * RTY, REMOTE ? 2 : 3) void evp_resident2_tile(E
     //   3  as 1, and the interior waves at level 1 throughout their arithmetic.
     // Every spin (ring poll, slot spin), the barrier and the rim wave's first part after the barrier run at level 0: a spinning
     // wave never outranks a wave that has work.  No bit depends on it.  The product compiles one form in (EVP_RES2_PRIO_DEFAULT,
-    // 0: none); the test build carries a switch (RES_DEBUG bits 2048 | 4096: the form; CICE_EVP_HIP_RES_PRIO).
+    // 0: none); the test build carries a switch (EVP_RES2_HOOK_PRIO_MASK: the form; CICE_EVP_HIP_RES_PRIO).
 #ifdef CICE_EVP_HIP_TESTING
-    const int prio_form = RIMU ? (RES_DBG(R) >> 11) & 3 : 0;
+    const int prio_form = RIMU ? (RES_DBG(R) & EVP_RES2_HOOK_PRIO_MASK) >> EVP_RES2_HOOK_PRIO_SHIFT : 0;
 #else
     constexpr int prio_form = RIMU ? EVP_RES2_PRIO_DEFAULT : 0;
 #endif
@@ -939,26 +939,26 @@ __global__ __launch_bounds__(64 * RTY, REMOTE ? 2 : 3) void evp_resident2_tile(E
     auto subcycle_rim = [&](const int k, const v4u *rd, v4u *wr) -> bool {
         const unsigned want = R.tag_base + (unsigned)k;       // tag of the velocities subcycle k reads
         const int done = k + 1;                               // what an interior wave's slot says once its stress of subcycle k is in the planes
-        if ((RES_DBG(R) & 8) && (tile & 3) == 1) {            // robustness test: every fourth tile lags by ~10 us per subcycle
+        if ((RES_DBG(R) & EVP_RES2_HOOK_LAG) && (tile & 3) == 1) {            // robustness test: every fourth tile lags by ~10 us per subcycle
             const unsigned long long t0 = wall_clock64();
             while (wall_clock64() - t0 < 1000ull) __builtin_amdgcn_s_sleep(8);
         }
         int bad = 0;
         if (rimw) {
             bool gave = false;
-            if (ring_cp >= 0 && !(RES_DBG(R) & 2)) {
+            if (ring_cp >= 0 && !(RES_DBG(R) & EVP_RES2_HOOK_NO_RING_LOADS)) {
                 v4u ra, rb;
                 unsigned spins = 0;
                 for (;;) {
                     ld_rec2_s(rd, ring_off, ra, rb);
-                    if ((ra.x == want && ra.w == want && rb.x == want && rb.w == want) || (RES_DBG(R) & 1)) break;
+                    if ((ra.x == want && ra.w == want && rb.x == want && rb.w == want) || (RES_DBG(R) & EVP_RES2_HOOK_NO_TAG_CHECK)) break;
                     if (gave_up(++spins, t_wait0)) {
                         give_up_note(1, k, ring_cp, ra.x, want);
                         __hip_atomic_store(&s_bad, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
                         gave = true;
                         break;
                     }
-                    if (RES_DBG(R) & 4) __builtin_amdgcn_s_sleep(8); else __builtin_amdgcn_s_sleep(1);
+                    if (RES_DBG(R) & EVP_RES2_HOOK_LONG_SLEEP) __builtin_amdgcn_s_sleep(8); else __builtin_amdgcn_s_sleep(1);
                 }
                 s_u[ring_li] = unpack_rec(ra);
                 s_v[ring_li] = unpack_rec(rb);
@@ -1179,45 +1179,23 @@ __global__ __launch_bounds__(64 * RTY, REMOTE ? 2 : 3) void evp_resident2_tile(E
     }
 }
 
-size_t lds_bytes(unsigned flags, int logw, bool coop = false, bool rimu = false)
+size_t lds_bytes(const Res2Variant &v, unsigned flags)
 {
-    const int W = 1 << logw, H = 256 / W;
+    const int W = 1 << v.logw, H = 256 / W;
     const int nuv = ((H + 1) * (W + 1) + 7) & ~7;
     const int nu = 8 + ((flags & EVP_F_WATER_IS_OCN) ? 0 : 2) + ((flags & EVP_F_TBU_ZERO) ? 0 : 1);
-    const size_t nstr = logw == 4 ? (rimu ? 8 : 6) * (size_t)(W + 1) * H : 4 * (size_t)256;   // PERM planes: row stride W + 1 (RIMU: eight of them)
-    return sizeof(double) * (nstr + (size_t)256 * (4 + nu) + 2 * (size_t)nuv + (coop ? 12 * (size_t)64 : 0));
+    const size_t nstr = v.logw == 4 ? (v.rimu ? 8 : 6) * (size_t)(W + 1) * H : 4 * (size_t)256;   // PERM planes: row stride W + 1 (RIMU: eight of them)
+    return sizeof(double) * (nstr + (size_t)256 * (4 + nu) + 2 * (size_t)nuv + (v.coop ? 12 * (size_t)64 : 0));
 }
 
+// ---- the table of instantiations (this template and evp_resident2_kernel below): the launch, the occupancy query and "is it
+// built" all ask it.  General: {strict} x {cap 3, 1, 0, -1} x {logw 4, 5, 6} x {remote}
+#define EVP_TILE(...) ((const void *)evp_resident2_tile<__VA_ARGS__>)
 template <int LOGW, bool REMOTE>
-int occ(bool strict, int cap, size_t lds)
+const void *general_tile(bool strict, int cap)
 {
-    int nb = 0;
-#define EVP_OCC(S, C) hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, evp_resident2_tile<S, C, LOGW, REMOTE>, 64 * RTY, lds)
-    hipError_t e;
-    if (strict) e = cap == 3 ? EVP_OCC(true, 3) : cap == 1 ? EVP_OCC(true, 1) : cap == 0 ? EVP_OCC(true, 0) : EVP_OCC(true, -1);
-    else e = cap == 3 ? EVP_OCC(false, 3) : cap == 1 ? EVP_OCC(false, 1) : cap == 0 ? EVP_OCC(false, 0) : EVP_OCC(false, -1);
-#undef EVP_OCC
-    return e == hipSuccess ? nb : 0;
-}
-
-template <int LOGW, bool REMOTE>
-void launch(const EvpArgs &A, const EvpResident2 &R, bool strict, int cap, hipStream_t st)
-{
-    dim3 grid(R.nlaunch > 0 ? R.nlaunch : A.ntiles), block(64, RTY);
-    const size_t lds = lds_bytes(A.flags, LOGW);
-#define EVP_LAUNCH(S, C) hipLaunchKernelGGL((evp_resident2_tile<S, C, LOGW, REMOTE>), grid, block, lds, st, A, R)
-    if (strict) {
-        if (cap == 3) EVP_LAUNCH(true, 3);
-        else if (cap == 1) EVP_LAUNCH(true, 1);
-        else if (cap == 0) EVP_LAUNCH(true, 0);
-        else EVP_LAUNCH(true, -1);
-    } else {
-        if (cap == 3) EVP_LAUNCH(false, 3);
-        else if (cap == 1) EVP_LAUNCH(false, 1);
-        else if (cap == 0) EVP_LAUNCH(false, 0);
-        else EVP_LAUNCH(false, -1);
-    }
-#undef EVP_LAUNCH
+    if (strict) return cap == 3 ? EVP_TILE(true, 3, LOGW, REMOTE) : cap == 1 ? EVP_TILE(true, 1, LOGW, REMOTE) : cap == 0 ? EVP_TILE(true, 0, LOGW, REMOTE) : cap == -1 ? EVP_TILE(true, -1, LOGW, REMOTE) : nullptr;
+    return cap == 3 ? EVP_TILE(false, 3, LOGW, REMOTE) : cap == 1 ? EVP_TILE(false, 1, LOGW, REMOTE) : cap == 0 ? EVP_TILE(false, 0, LOGW, REMOTE) : cap == -1 ? EVP_TILE(false, -1, LOGW, REMOTE) : nullptr;
 }
 
 }  // namespace
@@ -1258,81 +1236,47 @@ void evp_resident_geometry(int max_ni, int max_nj, int logw, int *gx, int *gy)
     *gy = (max_nj + H - 2) / (H - 1);
 }
 
-// LEAN (one rank, one block, no fold, TbU == 0, water == ocean current, revp == 0, default scalars, 16 x 16 tiles): what the
-// general kernel decides per launch is fixed at compile time -- the loop carries no seam, T-fold, remote or revp code, one
-// stepu -- and the record addresses are a scalar base per subcycle parity plus a lane offset fixed for the call
-bool evp_resident2_lean_built(bool, int cap, int logw, bool remote) { return cap == 3 && logw == 4 && !remote; }
-
-// (measured slower than one thread per rim cell wherever two or three tiles share a CU -- HISTORY.md, round 5 -- so the variant is
-// compiled into the test build only, as an A/B switch: CICE_EVP_HIP_RES_COOP=1, tools/coop_ab.py)
-#ifdef CICE_EVP_HIP_TESTING
-bool evp_resident2_coop_built(bool strict, int cap, int logw, bool remote) { return strict && cap == 3 && logw == 4 && !remote; }
-#else
-bool evp_resident2_coop_built(bool, int, int, bool) { return false; }
-#endif
-
-int evp_resident2_max_blocks_per_cu(bool strict, int cap, unsigned flags, int logw, bool remote, bool coop)
+// Coop (test build): strict, cap 3, logw 4, not remote; lean and lean + rimu: cap 3, logw 4, not remote.  (The kernels are named in
+// the order the file has always instantiated them: the compiler lays the code object out in it, and that layout is what was measured.)
+const void *evp_resident2_kernel(const Res2Variant &v)
 {
-    if (coop) {
+    if (v.coop || v.lean || v.rimu) {
+        if (v.cap != 3 || v.logw != 4 || v.remote) return nullptr;
 #ifdef CICE_EVP_HIP_TESTING
-        if (!evp_resident2_coop_built(strict, cap, logw, remote)) return 0;
-        int nb = 0;
-        return hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, evp_resident2_tile<true, 3, 4, false, true>, 64 * RTY, lds_bytes(flags, 4, true)) == hipSuccess ? nb : 0;
-#else
-        return 0;
+        if (v.coop) return v.strict && !v.lean && !v.rimu ? EVP_TILE(true, 3, 4, false, true) : nullptr;
 #endif
+        if (v.coop || !v.lean) return nullptr;
+        if (!v.rimu) return v.strict ? EVP_TILE(true, 3, 4, false, false, true) : EVP_TILE(false, 3, 4, false, false, true);
+        return v.strict ? EVP_TILE(true, 3, 4, false, false, true, true) : EVP_TILE(false, 3, 4, false, false, true, true);
     }
-    const size_t lds = lds_bytes(flags, logw);
-    if (evp_resident2_lean_built(strict, cap, logw, remote)) {
-        // admitted against the smaller of the two: the launch picks the lean variant only while the data allow it
+    if (v.logw == 4 && !v.remote) return general_tile<4, false>(v.strict, v.cap);
+    if (v.remote) return v.logw == 4 ? general_tile<4, true>(v.strict, v.cap) : v.logw == 5 ? general_tile<5, true>(v.strict, v.cap) : v.logw == 6 ? general_tile<6, true>(v.strict, v.cap) : nullptr;
+    return v.logw == 5 ? general_tile<5, false>(v.strict, v.cap) : v.logw == 6 ? general_tile<6, false>(v.strict, v.cap) : nullptr;
+}
+#undef EVP_TILE
+
+int evp_resident2_max_blocks_per_cu(const Res2Variant &v, unsigned flags)
+{
+    auto occ = [](const Res2Variant &w, unsigned fl) {
+        const void *k = evp_resident2_kernel(w);
         int nb = 0;
-        const hipError_t e = strict ? hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, evp_resident2_tile<true, 3, 4, false, false, true>, 64 * RTY, lds)
-                                    : hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, evp_resident2_tile<false, 3, 4, false, false, true>, 64 * RTY, lds);
-        // (RIMU: two more planes, 46720 B of LDS per workgroup with the operands the lean launch has)
-        int nr = 0;
-        const size_t lds_r = lds_bytes(flags | EVP_F_WATER_IS_OCN | EVP_F_TBU_ZERO, 4, false, true);
-        const hipError_t er = strict ? hipOccupancyMaxActiveBlocksPerMultiprocessor(&nr, evp_resident2_tile<true, 3, 4, false, false, true, true>, 64 * RTY, lds_r)
-                                     : hipOccupancyMaxActiveBlocksPerMultiprocessor(&nr, evp_resident2_tile<false, 3, 4, false, false, true, true>, 64 * RTY, lds_r);
-        return e == hipSuccess && er == hipSuccess ? std::min(std::min(nb, nr), occ<4, false>(strict, cap, lds)) : 0;
-    }
-    if (remote) return logw == 4 ? occ<4, true>(strict, cap, lds) : logw == 5 ? occ<5, true>(strict, cap, lds) : occ<6, true>(strict, cap, lds);
-    return logw == 4 ? occ<4, false>(strict, cap, lds) : logw == 5 ? occ<5, false>(strict, cap, lds) : occ<6, false>(strict, cap, lds);
+        return k && hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, k, 64 * RTY, lds_bytes(w, fl)) == hipSuccess ? nb : 0;
+    };
+    Res2Variant lean = v, rimu = v;
+    lean.lean = rimu.lean = rimu.rimu = true;
+    if (v.coop || v.lean || !evp_resident2_kernel(lean)) return occ(v, flags);
+    // admitted against the smallest of the three: the launch picks the lean variants only while the data allow it (RIMU: two more
+    // planes, 46720 B of LDS per workgroup with the operands the lean launch has)
+    return std::min(std::min(occ(lean, flags), occ(rimu, flags | EVP_F_WATER_IS_OCN | EVP_F_TBU_ZERO)), occ(v, flags));
 }
 
-void evp_launch_resident2(const EvpArgs &A0, const EvpResident2 &R, int max_ni, int max_nj, int logw,
-                          bool strict, int cap, int lean, hipStream_t st)
+hipError_t evp_launch_resident2(const EvpArgs &A0, const EvpResident2 &R, int max_ni, int max_nj, const Res2Variant &v, hipStream_t st)
 {
+    const void *kernel = evp_resident2_kernel(v);
+    if (!kernel) return hipErrorInvalidDeviceFunction;
     EvpArgs A = A0;
-    evp_resident_geometry(max_ni, max_nj, logw, &A.gx, &A.gy);
+    evp_resident_geometry(max_ni, max_nj, v.logw, &A.gx, &A.gy);
     A.ntiles = A.gx * A.gy * (R.nblocks > 0 ? R.nblocks : 1);
-    const bool remote = R.rimg != nullptr;
-#ifdef CICE_EVP_HIP_TESTING
-    if (R.nlate && evp_resident2_coop_built(strict, cap, logw, remote)) {
-        dim3 grid(R.nlaunch > 0 ? R.nlaunch : A.ntiles), block(64, RTY);
-        hipLaunchKernelGGL((evp_resident2_tile<true, 3, 4, false, true>), grid, block, lds_bytes(A.flags, 4, true), st, A, R);
-        return;
-    }
-#endif
-    if (lean == 2 && evp_resident2_lean_built(strict, cap, logw, remote)) {      // RIMU: R.perm / R.uperm / R.nact are rim_plan's
-        dim3 grid(R.nlaunch > 0 ? R.nlaunch : A.ntiles), block(64, RTY);
-        const size_t lds = lds_bytes(A.flags, 4, false, true);
-        if (strict) hipLaunchKernelGGL((evp_resident2_tile<true, 3, 4, false, false, true, true>), grid, block, lds, st, A, R);
-        else hipLaunchKernelGGL((evp_resident2_tile<false, 3, 4, false, false, true, true>), grid, block, lds, st, A, R);
-        return;
-    }
-    if (lean && evp_resident2_lean_built(strict, cap, logw, remote)) {
-        dim3 grid(R.nlaunch > 0 ? R.nlaunch : A.ntiles), block(64, RTY);
-        if (strict) hipLaunchKernelGGL((evp_resident2_tile<true, 3, 4, false, false, true>), grid, block, lds_bytes(A.flags, 4), st, A, R);
-        else hipLaunchKernelGGL((evp_resident2_tile<false, 3, 4, false, false, true>), grid, block, lds_bytes(A.flags, 4), st, A, R);
-        return;
-    }
-    if (remote) {
-        if (logw == 4) launch<4, true>(A, R, strict, cap, st);
-        else if (logw == 5) launch<5, true>(A, R, strict, cap, st);
-        else launch<6, true>(A, R, strict, cap, st);
-    } else {
-        if (logw == 4) launch<4, false>(A, R, strict, cap, st);
-        else if (logw == 5) launch<5, false>(A, R, strict, cap, st);
-        else launch<6, false>(A, R, strict, cap, st);
-    }
+    void *args[2] = {&A, const_cast<EvpResident2 *>(&R)};
+    return hipLaunchKernel(kernel, dim3(R.nlaunch > 0 ? R.nlaunch : A.ntiles), dim3(64, RTY), args, lds_bytes(v, A.flags), st);
 }

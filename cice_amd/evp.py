@@ -59,6 +59,7 @@ TEST_EXPORTS = [
     "cice_evp_hip_peer_plan", "cice_evp_hip_peer_signs", "cice_evp_hip_center_plan", "cice_evp_hip_stress_plan",
     "cice_evp_hip_fold_split_plan", "cice_evp_hip_plan_flags", "cice_evp_hip_fold_images_plan", "cice_evp_hip_cgrid_fold_xplan",
     "cice_evp_hip_cgrid_fold_xpeers", "cice_evp_hip_plan_dump", "cice_evp_hip_rim_plan", "cice_evp_hip_debug_range_math",
+    "cice_evp_hip_debug_res2_choose", "cice_evp_hip_debug_res2_built",
 ]
 # environment switches only the test build reads (cice_amd/csrc/evp_host.h: env_test): experiments, fault injection, routing
 # of on-device copies through the remote transports.  An EvpHip made while one of them is set uses the test build.

@@ -147,6 +147,15 @@ int cice_evp_hip_plan_dump(int32_t *out, int32_t n);
    active chunks of the ice-first packing, ok, tiles per row, tiles per column, 0}, cls[256]. */
 int cice_evp_hip_rim_plan(int32_t ni, int32_t nj, int32_t cyclic_ew, int32_t cyclic_ns, const uint8_t *mask, int32_t ntiles_max,
                           uint8_t *perm, uint8_t *uperm, int32_t *info8, uint8_t *cls);
+/* Host-only: which instantiation of the resident B-grid kernel a launch runs (csrc/res2_variant.cpp: res2_choose), for n cases that
+   share cap (3, 1, 0, -1), logw (4, 5, 6) and hooks (the value of CICE_EVP_HIP_RES_DEBUG: csrc/evp_device.h, EVP_RES2_HOOK_*).
+   facts[e] bit 0 strict, 1 neighbours on other GPUs, 2 one block per rank, 3 - 7 the launch carries the seam / T-fold / img3 / rimg /
+   rraw table, 8 revp == 0, 9 / 10 the flags WATER_IS_OCN / TBU_ZERO, 11 - 13 COOP is possible for the tables / built / fits the chip,
+   14 the rim-wave tables are valid, 15 - 17 the switches RES_COOP / RES_LEAN / RES_RIMU.  chosen[e] bit 0 strict, 1 remote, 2 coop,
+   3 lean, 4 rimu, 5 the launch binds rim_plan's tables; logw << 8; (cap + 1) << 16.                                              */
+int cice_evp_hip_debug_res2_choose(int64_t n, const uint32_t *facts, int32_t cap, int32_t logw, int32_t hooks, uint32_t *chosen);
+/* Host-only: 1 where this build holds that instantiation of the kernel (the table of csrc/evp_resident2.hip), else 0. */
+int cice_evp_hip_debug_res2_built(int32_t strict, int32_t cap, int32_t logw, int32_t remote, int32_t coop, int32_t lean, int32_t rimu);
 int cice_evp_hip_halo_plan(int32_t *counts4, int32_t *local_dst, int32_t *local_src,
                            int32_t *local_sign, int32_t *peer_rank, int32_t *peer_nsend,
                            int32_t *peer_nrecv, int32_t *send_src, int32_t *recv_dst);
