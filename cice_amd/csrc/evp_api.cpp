@@ -926,7 +926,7 @@ int cice_evp_hip_get_timings(double *out, int32_t n)
                          res ? 1.0 / std::max(S.t_nsub, 1) : S.march.last_call ? (double)S.march.call_passes / std::max(S.march.call_subcycles, 1) :
                          1.0 + ((S.n_local > 0 && !(S.push_ok && (S.flags & S.flags_allowed & EVP_F_PUSH))) ? 1.0 : 0.0) +
                              (S.plan.peers.empty() ? 0.0 : (S.direct.on ? (use_riding_exchange() ? 0.0 : 1.0) : 2.0)) + ((S.n_seam + S.n_pole + S.n_late) > 0 ? 1.0 : 0.0),
-                         (double)(res ? 2000 + S.res2_logw : (S.march.last_call ? 3000 + S.march.seglen : S.tyb)), marks_ms, S.t_stream_probe_ms, S.t_res_probe_ms,
+                         (double)(res ? 2000 + S.res2_logw : (S.march.last_call ? 3000 + S.march.L.seglen : S.tyb)), marks_ms, S.t_stream_probe_ms, S.t_res_probe_ms,
                           S.plan.peers.empty() ? 0.0 : (S.direct.on ? 2.0 : 1.0), S.prep.t_ms, (double)S.res_fallbacks,
                           (double)(S.msk.on ? S.msk.n_send : S.n_send), (double)(S.msk.on ? S.msk.n_recv : S.n_recv),
                           (double)(res ? (S.res2_nlive > 0 ? S.res2_nlive : S.res2_ntiles) : 0), (double)(S.res_mode == 1 ? S.res2_ntiles : 0)};
@@ -1211,9 +1211,9 @@ int cice_evp_hip_seam_fin_plan(int32_t *counts2, int32_t *dst, int32_t *a, int32
 int cice_evp_hip_march_info(int32_t *out, int32_t n)
 {
     const State::March &M = S.march;
-    const int32_t v[12] = {M.mode, (int32_t)std::min<long>(M.passes, 0x7fffffffL), M.declined, M.nstrips, M.nseg, M.seglen,
-                           M.last_call ? 1 : 0, M.direct, M.kpass, (int32_t)std::min<long>(M.subcycles, 0x7fffffffL),
-                           M.mode == 1 ? M.fold_h : 0, M.last_call ? M.call_band_subcycles : 0};
+    const int32_t v[12] = {M.mode, (int32_t)std::min<long>(M.passes, 0x7fffffffL), M.declined, M.L.nblk ? M.L.plan.me.nstrips : 0, M.L.nseg, M.L.seglen,
+                           M.last_call ? 1 : 0, M.direct, M.L.kpass, (int32_t)std::min<long>(M.subcycles, 0x7fffffffL),
+                           M.mode == 1 ? M.L.fold.H : 0, M.last_call ? M.call_band_subcycles : 0};
     for (int k = 0; out && k < n && k < 12; ++k) out[k] = v[k];
     return 0;
 }
@@ -1227,7 +1227,7 @@ int cice_evp_hip_describe_path(char *buf, int32_t n)
     const char *kernel = S.res_mode == 1 ? (S.res_remote ? "on-chip resident (tagged records, neighbours on other ranks)"
                                                        : S.res2_rimu ? "on-chip resident (tagged records; edge U-cells in the rim wave)"
                                                                      : "on-chip resident (tagged records)")
-                         : (M.last_call ? (M.kpass == 4 ? "four subcycles per pass (marching)" : M.kpass == 3 ? "three subcycles per pass (marching)" : "two subcycles per pass (marching)")
+                         : (M.last_call ? (M.L.kpass == 4 ? "four subcycles per pass (marching)" : M.L.kpass == 3 ? "three subcycles per pass (marching)" : "two subcycles per pass (marching)")
                                       : "one subcycle per launch (streaming)");
     const char *transport = S.plan.peers.empty() ? "none (one rank)" : (S.direct.on ? "mailbox over HIP IPC" : (S.have_comm ? "RCCL send/recv" : "not set up"));
     const char *ring = (M.mode == 1 && !S.plan.peers.empty())
@@ -1235,8 +1235,8 @@ int cice_evp_hip_describe_path(char *buf, int32_t n)
                                             : (M.direct == 2 ? " (ring between ranks: RCCL send/recv, direct stores on trial)" : " (ring between ranks: RCCL send/recv)"))
                            : "";
     char band[96] = "";
-    if (M.mode == 1 && M.fold_h > 0)
-        std::snprintf(band, sizeof band, " (tripole: rows 1 .. %d marched, fold band of %d rows one subcycle per launch)", M.fold_zone, M.fold_h);
+    if (M.mode == 1 && M.L.fold.H > 0)
+        std::snprintf(band, sizeof band, " (tripole: rows 1 .. %d marched, fold band of %d rows one subcycle per launch)", M.L.fold.zone, M.L.fold.H);
     std::snprintf(buf, (size_t)n, "rank %d of %d: kernel = %s; halo transport = %s%s%s; marching path: %s%s%s%s%s; blocks %d, cells per exchange %d",
                   (int)S.d.rank, (int)std::max(1, (int)S.d.nranks), kernel, transport,
                   (!S.plan.peers.empty() && !S.direct.on && !S.direct.why.empty()) ? " (mailbox off: " : "",

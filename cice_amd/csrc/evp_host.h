@@ -38,6 +38,7 @@
 #include "evp_device.h"
 #include "halo_plan.h"
 #include "cgrid_plan.h"
+#include "march_plan.h"
 
 namespace evp_host {
 
@@ -330,17 +331,10 @@ struct State {
     // several subcycles per pass over a device-private rectangle layout (evp_march.hip, evp_host_march.cpp)
     struct March {
         int mode = -1;                 // -1 undecided, 0 off, 1 on
-        EvpMarchGeo G{};
-        std::vector<int> blkid_h;
-        std::vector<int2> org_h;
-        int nstrips = 0, nseg = 0, seglen = 0, nitems = 0;
-        int kpass = EVP_MARCH_KMAX;    // subcycles a full pass advances the state by
-        int ring_valid = EVP_MARCH_PAD;// cells beyond the rank's own that are current after an exchange of the ring (ext + P):
-                                       // that many subcycles can follow before the next exchange
+        MarchLayout L;                 // what follows from the dims alone (march_plan.h): rim, passes, tables, segments, lists
+        EvpMarchGeo G{};               // ... as the gather / scatter / check kernels take it
         long subcycles = 0;            // subcycles advanced by passes since init
         int call_passes = 0, call_subcycles = 0;   // ... of the last call (launches per subcycle for the timing read-out)
-        size_t nblk = 0;               // (row, strip) blocks per buffer
-        std::vector<unsigned> dup_h;   // [nstrips][64] duplicate positions (EvpMarch::dup)
         bool stat_done = false, stat_ok = false;
         unsigned checked_seq = ~0u;    // upload_seq whose ghost-cell consistency has been verified
         long passes = 0;               // passes run since init
@@ -350,10 +344,7 @@ struct State {
         int direct = -1;               // the ring between ranks as stores into HIP-IPC-mapped inboxes: -1 not tried, 0 off, 1 on, 2 being verified
         std::string direct_why;        // ... and why it is off
         int direct_asked = -1;         // value of CICE_EVP_HIP_MARCH_DIRECT the decision was taken on (a change re-opens it)
-        // tripole grid on one rank (march_plan.h: MarchFold): the top fold_h rows and the ghost row beyond the fold stay in the block
-        // layout, advanced one subcycle at a time beside the passes; 0 = no band
-        int fold_h = 0, fold_zone = 0, fold_row0 = 0;
-        int call_band_subcycles = 0;   // subcycles the band advanced in the last call
+        int call_band_subcycles = 0;   // subcycles the fold band of a tripole grid (L.fold) advanced in the last call
     } march;
     unsigned upload_seq = 0;                       // bumped whenever the caller hands new state / inputs to the device
     int fault_calls = 0;                           // test hook counter (fault_hook, evp_api.cpp)

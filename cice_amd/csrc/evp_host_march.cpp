@@ -12,9 +12,10 @@
 // every block computes for itself, ice_dyn_shared.F90:740-749) are images of it.  The byte mask stays row-major.
 //
 // A call of cice_evp_hip_subcycle(ndte) through this path:
-//   [ndte = 4q + 1: one subcycle with the one-subcycle kernel]  gather -> consistency check (first call after an upload)
-//   -> q passes of four subcycles and one of the remaining two or three (ping-pong between two sets of u, v, 12
-//   stresses) -> scatter.
+//   [ndte = Kq + 1: one subcycle with the one-subcycle kernel]  gather -> consistency check (first call after an upload)
+//   -> q passes of K = 2 .. 4 subcycles and one of the remaining 2 .. K - 1 (ping-pong between two sets of u, v, 12
+//   stresses) -> scatter.  What is decided from the dims alone -- the rectangle, the rim, K, the segments, the lists and the
+//   order of passes and exchanges -- comes from march_plan.cpp (build_march_layout, march_schedule); this file is the plumbing.
 // Not eligible (the one-subcycle kernels keep running): cyclic north-south boundary, a tripole grid on several ranks, blocks
 // that do not tile a rectangle per rank (eliminated land blocks), metric terms (dxhy, dyhx) handed over as arrays that are not
 // what the kernel derives from HTE / HTN on the rows it evaluates, a rank too thin next to a closed boundary for its redundant
@@ -32,9 +33,11 @@
 // scatter of the zone's rows into the ping-pong buffer the band's last subcycle wrote.
 // =====================================================================
 #include "evp_host.h"
-#include "march_plan.h"
 
-static_assert(MARCH_PLAN_PAD == EVP_MARCH_PAD, "march_plan.h and evp_device.h must agree on the width of the overlap");
+static_assert(MARCH_PLAN_PAD == EVP_MARCH_PAD && MARCH_PLAN_OWN == EVP_MARCH_OWN && MARCH_PLAN_S_NF == EVP_MARCH_S_NF &&
+                  MARCH_PLAN_NODUP == EVP_MARCH_NODUP && MARCH_PLAN_MAXPEER == EVP_MARCH_DIRECT_MAXPEER,
+              "march_plan.h and evp_device.h must agree on the strip-major layout");
+static_assert(sizeof(MarchOrg) == sizeof(int2) && sizeof(MarchItem) == sizeof(int4), "the layout's tables are uploaded as they are");
 
 namespace evp_host {
 
@@ -56,7 +59,6 @@ struct MarchBuf {
     // the early launch of an exchange pass: work items that cover every cell other ranks receive from this one
     int4 *band_items = nullptr, *rest_items = nullptr;      // ... and every other (strip, row) of the rectangle
     std::map<int, std::pair<int *, int>> fold_tiles;        // fold band: tile list of the one-subcycle kernel, by tile variant
-    int nband = 0, nrest = 0;
     hipEvent_t ev_in = nullptr, ev_main = nullptr, ev_done = nullptr;
     // the same ring as stores into the peers' HIP-IPC-mapped inboxes (march_direct_setup)
     void *dx_area = nullptr;     // fine-grained: flag lines | count | err | inbox [2][n_recv * NF]
@@ -65,8 +67,7 @@ struct MarchBuf {
     unsigned dx_seq = 0;
     EvpRingCuts cut_send{}, cut_recv{};      // where each neighbour's block begins in the send / receive list
 };
-MarchPlan PL;
-MarchFold FD;                    // the fold band of a tripole grid (H == 0: none)
+MarchLayout &L = S.march.L;      // the one layout: march_geometry builds it, march_free resets it with the rest of S.march
 // slots of the constants block (evp_march.hip: C_*), of the optional block (O_*)
 enum { C_DXT = 0, C_DYT, C_STRENGTH, C_HTE, C_HTN, C_VRELFAC, C_UOCN, C_VOCN, C_FORCEX, C_FORCEY, C_UMASSDTI, C_FM, C_UAREAR };
 enum { O_WATERX = 0, O_WATERY, O_TBU, O_UINIT, O_VINIT };
@@ -91,8 +92,6 @@ void march_free()
     for (hipEvent_t e : {B.ev_in, B.ev_main, B.ev_done})
         if (e) (void)hipEventDestroy(e);
     B = MarchBuf();
-    PL = MarchPlan();
-    FD = MarchFold();
     S.march = State::March{};
 }
 
@@ -116,6 +115,13 @@ static void verbose(const char *fmt, ...)
 }
 // (test build) the ring between ranks as stores into HIP-IPC-mapped inboxes
 static bool march_direct_asked() { return env_on(env_test("CICE_EVP_HIP_MARCH_DIRECT"), false); }
+// (test build) what the layout may be asked for: own_max, wrap_inside, ext, kpass, seglen, bandseg; and the tile height in use
+static MarchAsk march_ask()
+{
+    return MarchAsk{env_int(env_test("CICE_EVP_HIP_MARCH_OWN"), EVP_MARCH_OWN), !env_on(env_test("CICE_EVP_HIP_MARCH_SELFX"), false),
+                    env_int(env_test("CICE_EVP_HIP_MARCH_EXT"), MARCH_ASK_UNSET), env_int(env_test("CICE_EVP_HIP_MARCH_K"), MARCH_ASK_UNSET),
+                    env_int(env_test("CICE_EVP_HIP_MARCH_SEG"), 0), env_int(env_test("CICE_EVP_HIP_MARCH_BANDSEG"), 0), S.tyb % 100};
+}
 
 // Are the metric terms the one-subcycle kernels read from arrays (cxp, cyp, cxm, cym, dxhy, dyhx, deltaminEVP * tarea) what the
 // marching kernel derives from HTE, HTN, dxT, dyT (evp_cell.inc: metrics) on every T-cell of the global rows below `nrows`?  On a
@@ -159,232 +165,66 @@ static bool metrics_hold(int nrows)
     return true;
 }
 
-// Can this rank's sub-domain be held as one rectangle?  Fills S.march.G (host fields) when it can.
+// Can this rank's sub-domain be held as one rectangle?  Builds the layout and fills S.march.G (host fields) when it can.
 static bool march_geometry(std::string &why)
 {
-    State::March &M = S.march;
     const cice_evp_hip_dims &d = S.d;
-    // tripole grid: the rectangle is the zone under the fold band, whose height follows from the rim
-    const bool tripole = d.ns_boundary_type == CICE_EVP_BND_TRIPOLE || d.ns_boundary_type == CICE_EVP_BND_TRIPOLET;
-    auto plan = [&](int e, int own_max, bool wrap_inside) -> bool {
-        FD = MarchFold();
-        if (tripole && !build_march_fold(d, e, S.tyb % 100, FD)) {
-            PL = MarchPlan();
-            PL.error = FD.error;
-            FD = MarchFold();
-            return false;
-        }
-        return build_march_plan(d, own_max, wrap_inside, e, PL, FD.H);
+    if (!build_march_layout(d, march_ask(), L)) { why = L.why; return false; }
+    // ... and what only this process knows; a layout refused here leaves no more behind than the pass size it had settled on
+    auto refuse = [&](const char *w) {
+        MarchLayout none;
+        none.kpass = L.kpass;
+        L = none;
+        why = w;
+        return false;
     };
-    // the rectangles of all ranks, this rank's strips and the exchange lists: the same verdict on every rank
-    const int own_max = env_int(env_test("CICE_EVP_HIP_MARCH_OWN"), EVP_MARCH_OWN);
-    const bool wrap_inside = !env_on(env_test("CICE_EVP_HIP_MARCH_SELFX"), false);
-    // cells a rank holds beyond its own on every side with a neighbour: the ring of ext + P cells is then exchanged every
-    // (ext + P)-th subcycle only (march_plan.h); 4 = after every second pass of four.  (Rounds 4-5, two subcycles per pass and a
-    // two-cell ring, 3600 x 2400 as 4x2 pieces, one-GPU rehearsal: 54.3 / 52.3 / 52.0 / 51.2 us per subcycle with ext 0 / 2 / 4 / 6
-    // against 47.0 without any exchange.)
-    const int ext_asked = env_int(env_test("CICE_EVP_HIP_MARCH_EXT"), ENV_UNSET);
-    int ext = ext_asked == ENV_UNSET ? -1 : std::max(0, ext_asked & ~1);
-    if (ext >= 0) {
-        if (!plan(ext, own_max, wrap_inside)) { why = PL.error; return false; }
-    } else {
-        // Default (round 6): the widest rim of 12 / 8 / 4 cells that costs no rank a strip more than a rim of 4 does and at most 2 %
-        // more rows -- the exchange then comes every 16th / 12th / 8th subcycle for the same bytes per subcycle.  (The 8 x 1 pieces of
-        // 3600 x 2400: 450 + 2 x 12 = 474 columns still fit the 9 strips that 458 need; measured on one GPU, ring exchanged with the
-        // rank itself, an exchange costs ~38 us: 4.8 us per subcycle at every 8th.)  Every rank reaches the same value from the global
-        // block table; a layout the plan refuses (a rank too thin next to a closed boundary) tries the next narrower rim.
-        bool ok = false;
-        std::string first_error;
-        for (int e : {12, 8, 4, 0}) {
-            if (!plan(e, own_max, wrap_inside)) {
-                if (first_error.empty()) first_error = PL.error;
-                continue;
-            }
-            bool fits = true;
-            const bool ew_cyc = d.ew_boundary_type == CICE_EVP_BND_CYCLIC;
-            for (const MarchRect &R : PL.all) {
-                if (!R.ok || e <= 4) continue;
-                const bool span = wrap_inside && ew_cyc && R.nxr == d.nx_global;      // wraps inside: no rim in x
-                const int w = (R.gx0 > 0 || ew_cyc) ? 1 : 0, ea = (R.gx0 + R.nxr < d.nx_global || ew_cyc) ? 1 : 0;
-                const int sn = R.gy0 > 0 ? 1 : 0, nn = R.gy0 + R.nyr < d.ny_global ? 1 : 0;
-                const int own_eff = std::min(own_max > 0 ? own_max : EVP_MARCH_OWN, EVP_MARCH_OWN);
-                const int w4 = R.nxr + (span ? 0 : 4 * (w + ea)), we = R.nxr + (span ? 0 : e * (w + ea));
-                if ((we + own_eff - 1) / own_eff > (w4 + own_eff - 1) / own_eff) fits = false;
-                if ((long)(R.nyr + e * (sn + nn)) * 100 > (long)(R.nyr + 4 * (sn + nn)) * 102) fits = false;
-            }
-            if (fits) { ext = e; ok = true; break; }
-        }
-        if (!ok) { why = first_error.empty() ? PL.error : first_error; return false; }
-    }
-    M.ring_valid = ext + EVP_MARCH_PAD;
-    // Subcycles per pass.  Round 6 measured what binds the kernel: a wave issues one instruction per 2.4 ns whatever it is, and a
-    // row costs ~640 instructions per level plus ~350 that do not depend on the number of levels (loads, stores, addressing, the
-    // register pipelines); a segment of sl rows marches sl + 2K - 1, the warm-up rows with part of the levels idle.  Measured on
-    // the 8 x 1 and 4 x 2 pieces of 3600 x 2400 (22- and 20-row segments, profiles/r06_ring_rank.txt): 58.0 / 50.0 / 49.1 and
-    // 54.9 / 46.8 / 46.0 us per subcycle with two / three / four subcycles per pass; 3600 x 2400 itself (160 rows) 362 / 315 / 293.
-    // Four from 12 rows per segment, three from 8, two below.  Every rank must run the same passes (the ring is exchanged between
-    // them), so the rule looks at the SHORTEST segment of any rank, which every rank works out from the global block table alone.
-    // The test build can ask for a value.
-    {
-        int slmin = 1 << 30;
-        for (const MarchRect &R : PL.all) {
-            if (!R.ok) continue;
-            const int grow = d.nranks > 1 ? 2 * ext : 0;
-            const int ns = (R.nxr + grow + EVP_MARCH_OWN - 1) / EVP_MARCH_OWN;
-            const int nseg = std::max(1, 1024 / ns);
-            slmin = std::min(slmin, std::max(6, (R.nyr + grow + nseg - 1) / nseg));
-        }
-        M.kpass = std::min(EVP_MARCH_KMAX, slmin >= 12 ? 4 : slmin >= 8 ? 3 : 2);
-    }
-    const int k_asked = env_int(env_test("CICE_EVP_HIP_MARCH_K"), ENV_UNSET);
-    if (k_asked != ENV_UNSET) M.kpass = std::min(EVP_MARCH_KMAX, std::max(2, k_asked));
-    if (PL.peers.size() > (size_t)EVP_MARCH_DIRECT_MAXPEER) { why = "more ring neighbours than the exchange lists hold"; return false; }
-    if (!PL.peers.empty() && !S.have_comm && !S.test_xchg) { why = "cells of other ranks needed but no RCCL communicator (cice_evp_hip_comm_init)"; return false; }
+    if (!L.plan.peers.empty() && !S.have_comm && !S.test_xchg) return refuse("cells of other ranks needed but no RCCL communicator (cice_evp_hip_comm_init)");
     // The kernel derives every metric term from HTE, HTN, dxT, dyT.  A closed grid: tarea == dxT * dyT was verified on every cell
     // at init (EVP_F_METRICS) and nothing else stands in the arrays.  A tripole grid: the arrays differ from that on the ghost row
     // beyond the fold (and, tripoleT, on the top physical row), so the test is the thing itself -- the terms hold on every row
     // the zone evaluates: its own, the redundant rim and the ring.
-    if (tripole) {
-        if (!metrics_hold(FD.to_rect[1])) { why = "the metric arrays are not what HTE, HTN, dxT, dyT give on the rows the marching kernel evaluates"; return false; }
-    } else if (!(S.flags & EVP_F_METRICS) || (S.flags & EVP_F_DXHY_ARRAY)) { why = "metric terms come from arrays"; return false; }
-    if (d.nblocks < 1) { why = "no blocks"; return false; }
-    // blocks must tile [gx0, gx0+nxr) x [gy0, gy0+nyr) with full blocks of bsx x bsy (the last column / row may be smaller)
-    int gx0 = 1 << 30, gy0 = 1 << 30, gx1 = 0, gy1 = 0;
-    for (int b = 0; b < d.nblocks; ++b) {
-        gx0 = std::min(gx0, S.iglob0[b]); gy0 = std::min(gy0, S.jglob0[b]);
-        gx1 = std::max(gx1, S.iglob0[b] + (S.ihi[b] - S.ilo[b])); gy1 = std::max(gy1, S.jglob0[b] + (S.jhi[b] - S.jlo[b]));
-    }
-    const int nxr = gx1 - gx0 + 1, nyr = gy1 - gy0 + 1;
-    int bsx = 0, bsy = 0;
-    for (int b = 0; b < d.nblocks; ++b) {
-        if (S.iglob0[b] == gx0) bsx = std::max(bsx, S.ihi[b] - S.ilo[b] + 1);
-        if (S.jglob0[b] == gy0) bsy = std::max(bsy, S.jhi[b] - S.jlo[b] + 1);
-    }
-    if (bsx <= 0 || bsy <= 0) { why = "no block at the origin of the rectangle"; return false; }
-    const int nbx = (nxr + bsx - 1) / bsx, nby = (nyr + bsy - 1) / bsy;
-    if ((long)nbx * nby != d.nblocks) { why = "blocks do not tile a rectangle"; return false; }
-    M.blkid_h.assign((size_t)nbx * nby, -1);
-    M.org_h.assign(d.nblocks, int2{0, 0});
-    for (int b = 0; b < d.nblocks; ++b) {
-        const int ox = S.iglob0[b] - gx0, oy = S.jglob0[b] - gy0;
-        if (ox % bsx || oy % bsy) { why = "block origins off the block grid"; return false; }
-        const int bi = ox / bsx, bj = oy / bsy;
-        const int wx = std::min(bsx, nxr - ox), wy = std::min(bsy, nyr - oy);
-        if (S.ihi[b] - S.ilo[b] + 1 != wx || S.jhi[b] - S.jlo[b] + 1 != wy) { why = "irregular block sizes"; return false; }
-        if (M.blkid_h[(size_t)bj * nbx + bi] >= 0) { why = "two blocks at one place"; return false; }
-        M.blkid_h[(size_t)bj * nbx + bi] = b;
-        M.org_h[b] = int2{ox, oy};
-    }
-    if (nxr != PL.owned.nxr || nyr - FD.H != PL.owned.nyr || gx0 - 1 != PL.owned.gx0 || gy0 - 1 != PL.owned.gy0) { why = "local blocks disagree with the global block table"; return false; }
-    for (auto &o : M.org_h) { o.x += PL.ext_w; o.y += PL.ext_s; }        // block origins in the rectangle the rank HOLDS
-    const bool wrapx = PL.wrapx;
-    EvpMarchGeo &G = M.G;
-    G.nxr = PL.me.nxr; G.nyr = PL.me.nyr;                                  // held: own cells + the redundant rim
-    G.ext_w = PL.ext_w; G.ext_s = PL.ext_s; G.nxo = nxr; G.nyo = nyr - FD.H;
-    G.nyblk = nyr;                   // (a fold band: the blocks go on above the zone, and the ring above it is read from them)
-    M.fold_h = FD.H; M.fold_zone = FD.zone; M.fold_row0 = FD.list_row0;
+    if (L.fold.H > 0) {
+        if (!metrics_hold(L.fold.to_rect[1])) return refuse("the metric arrays are not what HTE, HTN, dxT, dyT give on the rows the marching kernel evaluates");
+    } else if (!(S.flags & EVP_F_METRICS) || (S.flags & EVP_F_DXHY_ARRAY)) return refuse("metric terms come from arrays");
+    if (d.nblocks < 1) return refuse("no blocks");
+    EvpMarchGeo &G = S.march.G;
+    const MarchPlan &P = L.plan;
+    G.nxr = P.me.nxr; G.nyr = P.me.nyr; G.ldx = L.ldx; G.rows = L.rows; G.own = P.me.own; G.nstrips = P.me.nstrips;     // held: own cells + rim
     G.nxb = d.nx_block; G.nyb = d.ny_block; G.plane = (int)S.plane; G.nblocks = d.nblocks;
-    G.bsx = bsx; G.bsy = bsy; G.nbx = nbx; G.nby = nby;
+    G.bsx = L.bsx; G.bsy = L.bsy; G.nbx = L.nbx; G.nby = L.nby;
     G.ilo = d.nghost + 1;
-    G.wrapx = wrapx ? 1 : 0;
-    G.gx0 = PL.me.gx0; G.gy0 = PL.me.gy0; G.nxg = d.nx_global; G.nyg = d.ny_global;
+    G.wrapx = P.wrapx ? 1 : 0;
+    G.gx0 = P.me.gx0; G.gy0 = P.me.gy0; G.nxg = d.nx_global; G.nyg = d.ny_global;
     G.ew_cyclic = d.ew_boundary_type == CICE_EVP_BND_CYCLIC ? 1 : 0;
-    G.own = PL.me.own; G.nstrips = PL.me.nstrips;
-    M.dup_h.assign(PL.dup.size(), EVP_MARCH_NODUP);
-    for (size_t k = 0; k < PL.dup.size(); ++k)
-        if (PL.dup[k] >= 0) M.dup_h[k] = (unsigned)((((size_t)(PL.dup[k] >> 8)) * EVP_MARCH_S_NF * 64 + (PL.dup[k] & 255)) * 8);
-    M.nstrips = G.nstrips;
-    G.ldx = ((G.nstrips * G.own + 64 + 2 * EVP_MARCH_PAD + 7) / 8) * 8;
-    G.rows = G.nyr + 2 * EVP_MARCH_PAD + 3;      // y = -P .. nyr+P+2: halo, two rows the prefetch may touch, the dump row
-    M.nblk = (size_t)G.rows * G.nstrips;
-    if (M.nblk * EVP_MARCH_S_NF * 512 >= (1ull << 32)) { why = "state buffer beyond 32-bit byte offsets"; return false; }
-    // segments: one wave per SIMD (1024 of them), all resident at once -- measured at 3600 x 2400: 16 segments (960
-    // waves) 318 us per subcycle, 24 (1440: some SIMDs get two) 400, 34 (2040: two each) 378, 12 (720) 372
-    int seglen = env_int(env_test("CICE_EVP_HIP_MARCH_SEG"), 0);
-    if (seglen <= 0) {
-        // (medium domains, 0.45M .. 1M cells: shorter segments keep the count near 1000 -- 1080 x 720: 14-row segments 39 us
-        // per subcycle against 53 for the one-subcycle kernel; each segment recomputes ~3.5 rows of warm-up)
-        // (as many segments as fit 1024 waves: 3600 x 2400 has 60 strips -- 17 segments = 1020 waves = 255 workgroups, one per CU,
-        // 302.8 us per subcycle; 16 segments (960 waves, 16 CUs idle) 310.1; 18 (1080: some SIMDs get two) 472 -- round 5, same box)
-        const int want_seg = std::max(1, 1024 / M.nstrips);
-        seglen = std::max(6, (G.nyr + want_seg - 1) / want_seg);
-    }
-    M.seglen = std::min(seglen, G.nyr);
-    M.nseg = (G.nyr + M.seglen - 1) / M.seglen;
-    M.nitems = M.nseg * M.nstrips;
+    G.ext_w = P.ext_w; G.ext_s = P.ext_s; G.nxo = P.owned.nxr; G.nyo = P.owned.nyr;
+    G.nyblk = P.owned.nyr + L.fold.H;      // (a fold band: the blocks go on above the zone, and the ring above it is read from them)
     return true;
 }
 
+// The buffers by the layout's sizes, its tables and lists as they are.
 static int march_alloc()
 {
     State::March &M = S.march;
     auto A = [&](double *&p, int nf) -> int {
         if (p) return 0;
-        return B.mem.alloc(p, M.nblk * (size_t)nf * 64, true);
+        return B.mem.alloc(p, L.nblk * (size_t)nf * 64, true);
     };
     if (A(B.st[0], EVP_MARCH_S_NF) || A(B.st[1], EVP_MARCH_S_NF) || A(B.cst, EVP_MARCH_C_NF) || A(B.opt, EVP_MARCH_O_NF) ||
         A(B.diag, EVP_MARCH_D_NF)) return -1;
     if (!B.mask && B.mem.alloc(B.mask, (size_t)M.G.rows * M.G.ldx, true)) return -1;
     if (!B.bad && B.mem.alloc(B.bad, 1)) return -1;
-    if (!B.blkid && (B.mem.upload(B.blkid, M.blkid_h) || B.mem.upload(B.org, M.org_h) || B.mem.upload(B.dup, M.dup_h))) return -1;
-    if (PL.n_send + PL.n_recv > 0 && !B.sendbuf) {
-        std::vector<int> sp, r1, r2, sm, rm;
-        for (const MarchPeer &p : PL.peers) {
-            sp.insert(sp.end(), p.send_pos.begin(), p.send_pos.end());
-            r1.insert(r1.end(), p.recv_pos1.begin(), p.recv_pos1.end());
-            r2.insert(r2.end(), p.recv_pos2.begin(), p.recv_pos2.end());
-            for (size_t k = 0; k < p.send_pos.size(); ++k)
-                sm.push_back((int)((size_t)((p.send_pos[k] >> 6) / M.G.nstrips) * M.G.ldx + EVP_MARCH_PAD + p.send_col[k]));
-            for (size_t k = 0; k < p.recv_pos1.size(); ++k)
-                rm.push_back((int)((size_t)p.recv_row[k] * M.G.ldx + EVP_MARCH_PAD + p.recv_col[k]));
-        }
-        if (B.mem.upload(B.send_pos, sp) || B.mem.upload(B.recv_pos1, r1) || B.mem.upload(B.recv_pos2, r2) || B.mem.upload(B.send_midx, sm) ||
-            B.mem.upload(B.recv_midx, rm)) return -1;
-        B.cut_send.n = B.cut_recv.n = (int)PL.peers.size();
-        int cs = 0, cr = 0;
-        for (size_t q = 0; q < PL.peers.size(); ++q) {
-            B.cut_send.start[q] = cs; B.cut_recv.start[q] = cr;
-            cs += (int)PL.peers[q].send_pos.size(); cr += (int)PL.peers[q].recv_pos1.size();
-        }
-        B.cut_send.start[PL.peers.size()] = cs; B.cut_recv.start[PL.peers.size()] = cr;
-        if (B.mem.alloc(B.sendbuf, std::max<size_t>(PL.n_send, 1) * EVP_MARCH_S_NF) ||
-            B.mem.alloc(B.recvbuf, std::max<size_t>(PL.n_recv, 1) * EVP_MARCH_S_NF)) return -1;
-        // Work items of the EARLY launch of an exchange pass (march_run): per strip the rows that hold cells some other rank
-        // receives, cut into short segments -- from the send lists themselves, so every sent cell is covered whatever the
-        // layout.  Short segments (a third of the regular length, at least 6 rows) so that the launch, the pack and the
-        // transfer end before the pass they overlap with does; each costs 2K - 1 rows of warm-up like any segment.  The pass
-        // itself then runs over every OTHER (strip, row) of the rectangle (rest_items): the two launches of an exchange pass
-        // store into disjoint cells (round-4 advice: they used to overlap on the band, storing the same bits twice).
-        const int nstr = M.G.nstrips;
-        std::vector<std::vector<char>> rows((size_t)nstr, std::vector<char>((size_t)M.G.nyr, 0));
-        for (int pos : sp) {
-            const int blk = pos >> 6, strip = blk % nstr, y = blk / nstr - EVP_MARCH_PAD;
-            if (y >= 0 && y < M.G.nyr) rows[(size_t)strip][(size_t)y] = 1;
-        }
-        int bseg = env_int(env_test("CICE_EVP_HIP_MARCH_BANDSEG"), 0);
-        if (bseg <= 0) bseg = std::max(6, M.seglen / 3);
-        std::vector<int4> items;
-        for (int st = 0; st < nstr; ++st)
-            for (int y = 0; y < M.G.nyr;) {
-                if (!rows[(size_t)st][(size_t)y]) { ++y; continue; }
-                int y1 = y;
-                while (y1 < M.G.nyr && y1 - y < bseg && rows[(size_t)st][(size_t)y1]) ++y1;
-                items.push_back(make_int4(st, y, y1, 0));
-                y = y1;
-            }
-        B.nband = (int)items.size();
-        if (B.nband > 0 && B.mem.upload(B.band_items, items)) return -1;
-        std::vector<int4> rest;
-        for (int st = 0; st < nstr; ++st)
-            for (int y = 0; y < M.G.nyr;) {
-                if (rows[(size_t)st][(size_t)y]) { ++y; continue; }
-                int y1 = y;
-                while (y1 < M.G.nyr && y1 - y < M.seglen && !rows[(size_t)st][(size_t)y1]) ++y1;
-                rest.push_back(make_int4(st, y, y1, 0));
-                y = y1;
-            }
-        B.nrest = (int)rest.size();
-        if (B.nrest > 0 && B.mem.upload(B.rest_items, rest)) return -1;
+    if (!B.blkid && (B.mem.upload(B.blkid, L.blkid) || B.mem.upload(B.org, L.org) || B.mem.upload(B.dup, L.dup))) return -1;
+    if (L.plan.n_send + L.plan.n_recv > 0 && !B.sendbuf) {
+        if (B.mem.upload(B.send_pos, L.send_pos) || B.mem.upload(B.recv_pos1, L.recv_pos1) || B.mem.upload(B.recv_pos2, L.recv_pos2) ||
+            B.mem.upload(B.send_midx, L.send_midx) || B.mem.upload(B.recv_midx, L.recv_midx)) return -1;
+        B.cut_send.n = B.cut_recv.n = (int)L.plan.peers.size();
+        std::copy(std::begin(L.cut_send), std::end(L.cut_send), B.cut_send.start);
+        std::copy(std::begin(L.cut_recv), std::end(L.cut_recv), B.cut_recv.start);
+        if (B.mem.alloc(B.sendbuf, std::max<size_t>(L.plan.n_send, 1) * EVP_MARCH_S_NF) ||
+            B.mem.alloc(B.recvbuf, std::max<size_t>(L.plan.n_recv, 1) * EVP_MARCH_S_NF)) return -1;
+        // the two launches of an overlapped exchange pass (march_run)
+        if (!L.band_items.empty() && B.mem.upload(B.band_items, L.band_items)) return -1;
+        if (!L.rest_items.empty() && B.mem.upload(B.rest_items, L.rest_items)) return -1;
         for (hipEvent_t *e : {&B.ev_in, &B.ev_main, &B.ev_done})
             if (!*e) HIPC(hipEventCreateWithFlags(e, hipEventDisableTiming));
     }
@@ -394,7 +234,7 @@ static int march_alloc()
     return 0;
 }
 
-// One transfer between the ranks of PL.peers on stream `st`: to / from each, in the plan's order, nf doubles per cell of its send /
+// One transfer between the ranks of L.plan.peers on stream `st`: to / from each, in the plan's order, nf doubles per cell of its send /
 // receive list (per_cell) or nf doubles flat, out of `send` into `recv` (device buffers, the peers' shares one after the other).
 // ncclGroupStart{ncclSend, ncclRecv per neighbour}ncclGroupEnd, or (test hook) host buffers and the caller's callback.
 static int ring_transfer(const double *send, double *recv, int nf, hipStream_t st, bool per_cell = true)
@@ -404,7 +244,7 @@ static int ring_transfer(const double *send, double *recv, int nf, hipStream_t s
         std::vector<int32_t> ranks;
         std::vector<int64_t> ns, nr;
         size_t ts = 0, tr = 0;
-        for (const MarchPeer &p : PL.peers) {
+        for (const MarchPeer &p : L.plan.peers) {
             ranks.push_back(p.rank);
             ns.push_back((int64_t)count(p.send_pos.size()));
             nr.push_back((int64_t)count(p.recv_pos1.size()));
@@ -422,7 +262,7 @@ static int ring_transfer(const double *send, double *recv, int nf, hipStream_t s
     }
     size_t so = 0, ro = 0;
     NCCLC(ncclGroupStart());
-    for (const MarchPeer &p : PL.peers) {
+    for (const MarchPeer &p : L.plan.peers) {
         const size_t ns = count(p.send_pos.size()), nr = count(p.recv_pos1.size());
         if (ns) NCCLC(ncclSend(send + so, ns, ncclDouble, p.rank, S.comm, st));
         if (nr) NCCLC(ncclRecv(recv + ro, nr, ncclDouble, p.rank, S.comm, st));
@@ -436,7 +276,7 @@ static int ring_transfer(const double *send, double *recv, int nf, hipStream_t s
 // `st` (what is left is the unpack, incl. the duplicates).  Once per exchange pass for the state, once per call for the constants.
 static int march_send_recv(double *buf, int nf, hipStream_t st)
 {
-    evp_launch_march_pack(buf, nf, B.send_pos, PL.n_send, B.cut_send, B.sendbuf, st);
+    evp_launch_march_pack(buf, nf, B.send_pos, L.plan.n_send, B.cut_send, B.sendbuf, st);
     return ring_transfer(B.sendbuf, B.recvbuf, nf, st);
 }
 
@@ -456,7 +296,7 @@ static int agree(unsigned &v, ncclRedOp_t op, bool store, bool collective)
     return 0;
 }
 // ... the maximum over the ranks that have ring neighbours
-static int agree_max(unsigned &v, bool store = false) { return agree(v, ncclMax, store, !PL.peers.empty() && S.d.nranks > 1); }
+static int agree_max(unsigned &v, bool store = false) { return agree(v, ncclMax, store, !L.plan.peers.empty() && S.d.nranks > 1); }
 
 // ---- the ring without a communication library ------------------------------------------------------------------------
 // What a rank tells each of its ring neighbours: how to map its inbox and where that neighbour's entries land in it.
@@ -480,7 +320,7 @@ static int march_direct_setup()
 {
     State::March &M = S.march;
     M.direct = 0;
-    const int np = (int)PL.peers.size();
+    const int np = (int)L.plan.peers.size();
     // Opt-in (CICE_EVP_HIP_MARCH_DIRECT=1), and only if every rank asks: on one GPU (the ring exchanged with the rank itself,
     // 450 x 2400 and 900 x 1200 pieces) it is no faster than RCCL -- 54.7 against 52.6 and 52.7 against 52.1 us per subcycle: the
     // pack kernel's uncached 8-byte stores take as long (13.4 us) as RCCL's pack + copy kernel (6.4 + 8.3) -- and what it does over
@@ -499,7 +339,7 @@ static int march_direct_setup()
     if (!ok) M.direct_why = "more ring neighbours than the direct exchange holds";
     const size_t flag_bytes = (size_t)EVP_MARCH_DIRECT_MAXPEER * 64, count_off = flag_bytes, err_off = flag_bytes + 64;
     const size_t inbox_off = flag_bytes + 128;
-    const size_t par_doubles = ((size_t)std::max(PL.n_recv, 1) * EVP_MARCH_S_NF + 31) & ~(size_t)31;
+    const size_t par_doubles = ((size_t)std::max(L.plan.n_recv, 1) * EVP_MARCH_S_NF + 31) & ~(size_t)31;
     std::vector<double> out((size_t)np * MARCH_BLOB_DOUBLES, 0.0), in((size_t)np * MARCH_BLOB_DOUBLES, 0.0);
     if (ok) {
         const size_t bytes = inbox_off + 2 * par_doubles * sizeof(double);
@@ -521,15 +361,15 @@ static int march_direct_setup()
         MarchBlob b{};
         b.magic = ok ? MARCH_BLOB_MAGIC : 0u;
         b.nf = EVP_MARCH_S_NF;
-        b.from = S.d.rank; b.to = PL.peers[q].rank;
+        b.from = S.d.rank; b.to = L.plan.peers[q].rank;
         b.host_id = host_identity();
         b.pid = (int64_t)getpid();
         b.base = (uint64_t)(uintptr_t)B.dx_area;
         b.inbox_off = inbox_off; b.inbox_pstride = par_doubles * sizeof(double); b.flag_off = (size_t)q * 64;
-        b.off_cells = (int64_t)ro; b.count = (int64_t)PL.peers[q].recv_pos1.size();
+        b.off_cells = (int64_t)ro; b.count = (int64_t)L.plan.peers[q].recv_pos1.size();
         b.handle = handle;
         std::memcpy(&out[(size_t)q * MARCH_BLOB_DOUBLES], &b, sizeof b);
-        ro += PL.peers[q].recv_pos1.size();
+        ro += L.plan.peers[q].recv_pos1.size();
     }
     // the blobs travel like a ring of 32 doubles per neighbour
     {
@@ -545,7 +385,7 @@ static int march_direct_setup()
     for (int q = 0; q < np && ok; ++q) {
         MarchBlob b;
         std::memcpy(&b, &in[(size_t)q * MARCH_BLOB_DOUBLES], sizeof b);
-        const MarchPeer &p = PL.peers[q];
+        const MarchPeer &p = L.plan.peers[q];
         if (b.magic != MARCH_BLOB_MAGIC) { ok = false; M.direct_why = "rank " + std::to_string(p.rank) + " cannot take part"; break; }
         if (b.from != p.rank || b.to != S.d.rank || b.nf != EVP_MARCH_S_NF || b.count != (int64_t)p.send_pos.size()) {
             ok = false;
@@ -596,13 +436,13 @@ int march_direct_error()
     int e = 0;
     HIPC(hipMemcpy(&e, B.dx.err, sizeof e, hipMemcpyDeviceToHost));
     if (e) return fail(-8, "marching path: ring neighbour rank %d never signalled within the time-out (CICE_EVP_HIP_HALO_TIMEOUT_MS)",
-                       (e - 1 < (int)PL.peers.size()) ? PL.peers[e - 1].rank : -1);
+                       (e - 1 < (int)L.plan.peers.size()) ? L.plan.peers[e - 1].rank : -1);
     return 0;
 }
 
 static int march_exchange(double *buf, double *buf2, int nf)
 {
-    if (PL.peers.empty()) return 0;
+    if (L.plan.peers.empty()) return 0;
     State::March &M = S.march;
 #ifndef CICE_EVP_HIP_TESTING
     // Product build: the ring goes through RCCL send / recv; its direct-store form is a switch of the test build (until a
@@ -629,18 +469,18 @@ static int march_exchange(double *buf, double *buf2, int nf)
 #endif
     if (nf == EVP_MARCH_S_NF && M.direct == 1) {
         const unsigned seq = ++B.dx_seq;
-        evp_launch_march_pack_direct(buf, nf, B.send_pos, PL.n_send, B.cut_send, B.dx, seq, S.stream);
-        evp_launch_march_unpack_direct(buf, buf2, nf, B.recv_pos1, B.recv_pos2, PL.n_recv, B.cut_recv, B.dx, seq, nullptr, nullptr, S.stream);
+        evp_launch_march_pack_direct(buf, nf, B.send_pos, L.plan.n_send, B.cut_send, B.dx, seq, S.stream);
+        evp_launch_march_unpack_direct(buf, buf2, nf, B.recv_pos1, B.recv_pos2, L.plan.n_recv, B.cut_recv, B.dx, seq, nullptr, nullptr, S.stream);
         return 0;
     }
     if (int rc = march_send_recv(buf, nf, S.stream)) return rc;
-    evp_launch_march_unpack(buf, buf2, nf, B.recv_pos1, B.recv_pos2, PL.n_recv, B.cut_recv, B.recvbuf, S.stream);
+    evp_launch_march_unpack(buf, buf2, nf, B.recv_pos1, B.recv_pos2, L.plan.n_recv, B.cut_recv, B.recvbuf, S.stream);
     if (nf == EVP_MARCH_S_NF && M.direct == 2) {
         // once: the same ring through the inboxes as well, compared bit for bit with what the library delivered
         const unsigned seq = ++B.dx_seq;
         HIPC(hipMemsetAsync(B.bad, 0, sizeof(unsigned), S.stream));
-        evp_launch_march_pack_direct(buf, nf, B.send_pos, PL.n_send, B.cut_send, B.dx, seq, S.stream);
-        evp_launch_march_unpack_direct(buf, buf2, nf, B.recv_pos1, B.recv_pos2, PL.n_recv, B.cut_recv, B.dx, seq, B.recvbuf, B.bad, S.stream);
+        evp_launch_march_pack_direct(buf, nf, B.send_pos, L.plan.n_send, B.cut_send, B.dx, seq, S.stream);
+        evp_launch_march_unpack_direct(buf, buf2, nf, B.recv_pos1, B.recv_pos2, L.plan.n_recv, B.cut_recv, B.dx, seq, B.recvbuf, B.bad, S.stream);
         unsigned bad = 0;
         if (agree_max(bad)) return -1;
         int e = 0;
@@ -657,10 +497,10 @@ static int march_exchange(double *buf, double *buf2, int nf)
 
 static int march_exchange_mask()
 {
-    if (PL.peers.empty()) return 0;
-    evp_launch_march_pack_mask(B.mask, B.send_midx, PL.n_send, B.sendbuf, S.stream);
+    if (L.plan.peers.empty()) return 0;
+    evp_launch_march_pack_mask(B.mask, B.send_midx, L.plan.n_send, B.sendbuf, S.stream);
     if (int rc = ring_transfer(B.sendbuf, B.recvbuf, 1, S.stream)) return rc;
-    evp_launch_march_unpack_mask(B.mask, B.recv_midx, PL.n_recv, B.recvbuf, S.stream);
+    evp_launch_march_unpack_mask(B.mask, B.recv_midx, L.plan.n_recv, B.recvbuf, S.stream);
     return 0;
 }
 
@@ -687,7 +527,7 @@ static EvpMarchRows rows_window(int y0, int y1)
 {
     const State::March &M = S.march;
     int j0 = 1 << 28, j1 = -(1 << 28);
-    for (const int2 &o : M.org_h) {
+    for (const MarchOrg &o : L.org) {
         j0 = std::min(j0, std::max(y0, -(1 << 20)) - o.y + M.G.ilo);
         j1 = std::max(j1, std::min(y1, 1 << 20) - o.y + M.G.ilo);
     }
@@ -698,17 +538,17 @@ static EvpMarchRows rows_window(int y0, int y1)
 static EvpMarchRows check_window()
 {
     const State::March &M = S.march;
-    return M.fold_h > 0 ? rows_window(-(1 << 28), M.G.nyr + EVP_MARCH_PAD) : EvpMarchAllRows;
+    return L.fold.H > 0 ? rows_window(-(1 << 28), M.G.nyr + EVP_MARCH_PAD) : EvpMarchAllRows;
 }
 
-// The tile list of the fold band for the tile variant in use: every tile of every block that reaches row FD.list_row0 or above.
+// The tile list of the fold band for the tile variant in use: every tile of every block that reaches row L.fold.list_row0 or above.
 static int fold_tile_list(int variant, int *&list, int &count)
 {
     auto it = B.fold_tiles.find(variant);
     if (it == B.fold_tiles.end()) {
         int tyb, gx, gy;
         evp_tile_geometry(S.max_ni, S.max_nj, variant, &tyb, &gx, &gy);
-        MarchFold Fv = FD;
+        MarchFold Fv = L.fold;
         Fv.trow = tyb - 1;
         std::vector<int> t;
         for (int b = 0; b < S.d.nblocks; ++b) {
@@ -819,10 +659,10 @@ static void march_args(EvpMarch &A, int cur, int last)
     A.p = {q.arlx1i, q.denom1, q.brlx, q.revp, q.e_factor, q.epp2i, q.capping, q.Ktens, q.u0, q.cosw, q.sinw, q.rhow};
     A.deltaminEVP = q.deltaminEVP;
     A.nxr = M.G.nxr; A.nyr = M.G.nyr; A.ldx = M.G.ldx; A.own = M.G.own;
-    A.nstrips = M.nstrips; A.nseg = M.nseg; A.seglen = M.seglen; A.nitems = M.nitems;
+    A.nstrips = M.G.nstrips; A.nseg = L.nseg; A.seglen = L.seglen; A.nitems = L.nitems;
     A.wrapx = M.G.wrapx;
     A.last = last;
-    A.kpass = M.kpass;
+    A.kpass = L.kpass;
     A.order = env_int(env_test("CICE_EVP_HIP_MARCH_ORDER"), 1);
     A.flags = S.flags & S.flags_allowed;
     A.mask = B.mask;
@@ -852,27 +692,21 @@ int march_run(int ndte)
         return 0;
     };
     if (!M.stat_ok) return fallback("ghost values of the static grid fields are not images of one global field");
-    // ndte = q passes of kpass subcycles + one pass of the remaining 2 .. kpass-1; a single remaining subcycle goes first, through
-    // the one-subcycle kernel in the block layout
-    std::vector<int> sizes;
-    {
-        const int kp = M.kpass;
-        int q = left / kp, rem = left % kp;
-        if (rem == 1) {
-            if (int rc = enqueue_loop(1, cur)) return rc;
-            cur ^= 1;
-            --left;
-            rem = 0;
-            S.cur = cur;     // the device state HAS advanced: an error further down must not leave S.cur on the old copy
-        }
-        sizes.assign((size_t)q, kp);
-        if (rem) sizes.push_back(rem);
+    // the passes of this call (march_plan.h: march_schedule); a single left-over subcycle goes first, through the one-subcycle
+    // kernel in the block layout
+    std::vector<MarchStep> steps = march_schedule(ndte, L.kpass, L.ring_valid, !L.plan.peers.empty(), L.fold.H > 0);
+    if (!steps.empty() && steps[0].size == 1) {
+        if (int rc = enqueue_loop(1, cur)) return rc;
+        cur ^= 1;
+        --left;
+        S.cur = cur;     // the device state HAS advanced: an error further down must not leave S.cur on the old copy
+        steps.erase(steps.begin());
     }
     M.call_passes = 0; M.call_subcycles = 0; M.call_band_subcycles = 0;
     if (left == 0) { S.cur = cur; return 0; }
     // Fold band (tripole grid): its subcycles flip the block layout's ping-pong buffers, one flip each; bcur names the buffer
     // that holds the band's current state.  The zone's rows reach it at the ring exchanges and in the final scatter.
-    const bool fold = M.fold_h > 0;
+    const bool fold = L.fold.H > 0;
     int bcur = cur;
     const unsigned fl = S.flags & S.flags_allowed;
     // ---- gather the state and the per-call inputs ----
@@ -898,7 +732,7 @@ int march_run(int ndte)
         if (march_exchange_mask()) return -1;
         if (march_exchange(B.st[0], B.st[1], EVP_MARCH_S_NF)) return -1;
     }
-    if (M.checked_seq != S.upload_seq || !PL.peers.empty()) {
+    if (M.checked_seq != S.upload_seq || !L.plan.peers.empty()) {
         // first call on this uploaded state: are the caller's ghost values images of one global state?
         TabBuilder C;
         C.add_state(cur, B.st[0]);
@@ -918,9 +752,8 @@ int march_run(int ndte)
     // RCCL point-to-point on a second HIP stream over interior compute).  The two launches read the same input state and store
     // into disjoint cells (a cell's result does not depend on the segment it is computed in).  Only the unpack waits for the
     // pass: the pass still writes its (spent) redundant rim where the received cells go.
-    const int npass = (int)sizes.size();
+    const int npass = (int)steps.size();
     int rc = 0;
-    int valid = M.ring_valid;        // cells beyond the rank's own that hold the current state (the gather's exchange just filled them)
     // Opt-in, in the PRODUCT library too (CICE_EVP_HIP_MARCH_OVERLAP=1; every rank alike): where it can be measured -- one GPU, the
     // ring exchanged with the rank itself, profiles/r06_ring_rank.txt -- it still loses, 64.2 against 57.3 us per subcycle on the
     // 450 x 2400 piece and 61.2 against 56.9 on 900 x 1200, although the two launches no longer advance the band twice (rounds 4-5:
@@ -928,37 +761,32 @@ int march_run(int ndte)
     // no idle resource to hide a transfer under, and "early" means SHORT segments for the band -- 2K - 1 rows of warm-up on 7 stored.
     // On one GPU the transfer is a 7-us device copy; over xGMI it is 1.6 MB per neighbour every eighth subcycle, and only a node
     // can say whether hiding that is worth 6 us per subcycle.  bench.py --gpus N --extras ring_variants times both.
-    const bool overlap = !PL.peers.empty() && B.nband > 0 && M.direct != 1 && march_overlap_asked() && !march_direct_asked();
-    for (int k = 0; k < npass; ++k) {
-        // the ring of the new state travels after this pass when the next one needs more valid cells than are left, and after the
-        // last one (the way back to the block layout reads the ghost cells from it)
-        // (a pass advances the cells the rank holds -- its own + ext -- and only reads the P-cell ring around them: whatever is left of
-        // the ring afterwards is a state older)
-        valid = std::min(valid - sizes[(size_t)k], M.ring_valid - EVP_MARCH_PAD);
-        const bool exch = !PL.peers.empty() && (k == npass - 1 || valid < sizes[(size_t)k + 1]);
-        // (the fold band's ring: at the same points, but not after the last pass -- the final scatter moves the zone's rows then)
-        const bool fexch = fold && k < npass - 1 && valid < sizes[(size_t)k + 1];
-        if (exch || fexch) valid = M.ring_valid;
+    const bool overlap = !L.plan.peers.empty() && !L.band_items.empty() && M.direct != 1 && march_overlap_asked() && !march_direct_asked();
+    for (const MarchStep &step : steps) {
+        // step.exch: the ring of the new state travels after this pass -- the next one needs more valid cells than are left, or this
+        // is the last one (the way back to the block layout reads the ghost cells from it)
+        // step.fexch: the fold band's ring, at the same points but not after the last pass -- the final scatter moves the zone's rows then
+        const bool exch = step.exch;
         EvpMarch A;
-        march_args(A, rc, k == npass - 1);
-        A.kpass = sizes[(size_t)k];
+        march_args(A, rc, step.last);
+        A.kpass = step.size;
         if (exch && overlap) {
             HIPC(hipEventRecord(B.ev_in, S.stream));
             HIPC(hipStreamWaitEvent(S.stream_comm, B.ev_in, 0));
             EvpMarch E = A;
             E.items = B.band_items;
-            E.nitems = B.nband;                                  // (the last pass: the band's diagnostics are this launch's business)
+            E.nitems = (int)L.band_items.size();           // (the last pass: the band's diagnostics are this launch's business)
             evp_launch_march(E, S.prm.strict != 0, cap_mode(), S.stream_comm);
             if (int e = march_send_recv(B.st[rc ^ 1], EVP_MARCH_S_NF, S.stream_comm)) return e;
             A.items = B.rest_items;                              // the pass itself: everything else
-            A.nitems = B.nrest;
+            A.nitems = (int)L.rest_items.size();
         }
         if (A.nitems > 0) evp_launch_march(A, S.prm.strict != 0, cap_mode(), S.stream);
         rc ^= 1;
         if (exch && overlap) {
             HIPC(hipEventRecord(B.ev_main, S.stream));
             HIPC(hipStreamWaitEvent(S.stream_comm, B.ev_main, 0));
-            evp_launch_march_unpack(B.st[rc], nullptr, EVP_MARCH_S_NF, B.recv_pos1, B.recv_pos2, PL.n_recv, B.cut_recv, B.recvbuf, S.stream_comm);
+            evp_launch_march_unpack(B.st[rc], nullptr, EVP_MARCH_S_NF, B.recv_pos1, B.recv_pos2, L.plan.n_recv, B.cut_recv, B.recvbuf, S.stream_comm);
             HIPC(hipEventRecord(B.ev_done, S.stream_comm));
             HIPC(hipStreamWaitEvent(S.stream, B.ev_done, 0));
         } else if (exch) {
@@ -968,13 +796,13 @@ int march_run(int ndte)
             // the band catches up with the pass; then, when either side has used up its ring, the two trade rows: the zone's
             // ext + P rows under the band into the block layout (every image of a cell), the band's ext + P rows above the zone
             // into the rectangle (every lane that holds the column)
-            if (int e = fold_band_subcycles(sizes[(size_t)k], bcur, k == npass - 1)) return e;
-            M.call_band_subcycles += sizes[(size_t)k];
-            if (fexch) {
+            if (int e = fold_band_subcycles(step.size, bcur, step.last)) return e;
+            M.call_band_subcycles += step.size;
+            if (step.fexch) {
                 TabBuilder T;
                 T.add_state(bcur, B.st[rc]);
-                evp_launch_march_scatter(M.G, T.T, S.mask, 2, 12, rows_window(FD.to_block[0], FD.to_block[1]), S.stream);
-                evp_launch_march_gather(M.G, T.T, nullptr, nullptr, rows_window(FD.to_rect[0], FD.to_rect[1]), S.stream);
+                evp_launch_march_scatter(M.G, T.T, S.mask, 2, 12, rows_window(L.fold.to_block[0], L.fold.to_block[1]), S.stream);
+                evp_launch_march_gather(M.G, T.T, nullptr, nullptr, rows_window(L.fold.to_rect[0], L.fold.to_rect[1]), S.stream);
             }
         }
     }
@@ -989,7 +817,7 @@ int march_run(int ndte)
         T.add_state(bcur, B.st[rc]);
         T.add(S.in[F_STRINTX], B.diag, nullptr, EVP_MARCH_D_NF, 0); T.add(S.in[F_STRINTY], B.diag, nullptr, EVP_MARCH_D_NF, 1);
         T.add(S.in[F_TAUBX], B.diag, nullptr, EVP_MARCH_D_NF, 2); T.add(S.in[F_TAUBY], B.diag, nullptr, EVP_MARCH_D_NF, 3);
-        evp_launch_march_scatter(M.G, T.T, S.mask, 2, 12, fold ? rows_window(-(1 << 28), FD.zone) : EvpMarchAllRows, S.stream);
+        evp_launch_march_scatter(M.G, T.T, S.mask, 2, 12, fold ? rows_window(-(1 << 28), L.fold.zone) : EvpMarchAllRows, S.stream);
     }
     HIPC(hipGetLastError());
     S.cur = bcur;           // without a band the passes leave the block layout's ping-pong buffer where it was: the scatter wrote the
@@ -1035,6 +863,53 @@ extern "C" int cice_evp_hip_march_plan(const cice_evp_hip_dims *dims, int32_t ow
             if (recv_pos2) recv_pos2[ro + k] = p.recv_pos2[k];
         }
         so += p.send_pos.size(); ro += p.recv_pos1.size();
+    }
+    return 0;
+}
+
+// Host-only: the whole layout of dims->rank as the host would build it when asked `ask7` (march_plan.h: build_march_layout).
+extern "C" int cice_evp_hip_march_layout(const cice_evp_hip_dims *dims, const int32_t *ask7, int32_t *info34, int32_t *blkid, int32_t *org2,
+                                         uint32_t *dup, int32_t *ring5, int32_t *cuts2, int32_t *band4, int32_t *rest4)
+{
+    using namespace evp_host;
+    if (!dims || !ask7) return fail(-1, "null dims / ask");
+    MarchAsk a;
+    a.own_max = ask7[0]; a.wrap_inside = ask7[1] != 0; a.ext = ask7[2]; a.kpass = ask7[3]; a.seglen = ask7[4]; a.bandseg = ask7[5]; a.tyb = ask7[6];
+    MarchLayout Y;
+    if (!build_march_layout(*dims, a, Y)) return fail(-3, "march layout: %s", Y.why.c_str());
+    const int np = (int)Y.plan.peers.size(), ns = Y.plan.n_send, nr = Y.plan.n_recv;
+    if (info34) {
+        const MarchPlan &P = Y.plan;
+        const int32_t v[34] = {Y.ext, Y.ring_valid, Y.kpass, Y.bsx, Y.bsy, Y.nbx, Y.nby, P.me.nxr, P.me.nyr, Y.ldx, Y.rows, P.me.own, P.me.nstrips, P.wrapx,
+                               P.me.gx0, P.me.gy0, P.ext_w, P.ext_s, P.owned.nxr, P.owned.nyr, P.owned.nyr + Y.fold.H, (int32_t)Y.nblk, Y.seglen, Y.nseg, Y.nitems, np, ns, nr,
+                               (int32_t)Y.band_items.size(), (int32_t)Y.rest_items.size(), Y.fold.H, Y.fold.zone, (int32_t)Y.org.size(),
+                               (int32_t)Y.dup.size()};
+        std::copy(v, v + 34, info34);
+    }
+    if (blkid) std::copy(Y.blkid.begin(), Y.blkid.end(), blkid);
+    if (org2) std::memcpy(org2, Y.org.data(), Y.org.size() * sizeof(MarchOrg));
+    if (dup) std::copy(Y.dup.begin(), Y.dup.end(), dup);
+    if (ring5 && !Y.send_pos.empty()) {      // send_pos, send_midx [n_send] | recv_pos1, recv_pos2, recv_midx [n_recv]
+        int32_t *o = ring5;
+        for (const std::vector<int32_t> *l : {&Y.send_pos, &Y.send_midx, &Y.recv_pos1, &Y.recv_pos2, &Y.recv_midx}) o = std::copy(l->begin(), l->end(), o);
+    }
+    if (cuts2) {
+        std::copy(Y.cut_send, Y.cut_send + np + 1, cuts2);
+        std::copy(Y.cut_recv, Y.cut_recv + np + 1, cuts2 + np + 1);
+    }
+    if (band4) std::memcpy(band4, Y.band_items.data(), Y.band_items.size() * sizeof(MarchItem));
+    if (rest4) std::memcpy(rest4, Y.rest_items.data(), Y.rest_items.size() * sizeof(MarchItem));
+    return 0;
+}
+
+// Host-only: the passes of a call of ndte subcycles (march_plan.h: march_schedule); steps4 = per step {size, exch, fexch, last}.
+extern "C" int cice_evp_hip_march_schedule(int32_t ndte, int32_t kpass, int32_t ring_valid, int32_t has_peers, int32_t fold, int32_t *n, int32_t *steps4)
+{
+    const std::vector<MarchStep> st = march_schedule(ndte, kpass, ring_valid, has_peers != 0, fold != 0);
+    if (n) *n = (int32_t)st.size();
+    for (size_t k = 0; steps4 && k < st.size(); ++k) {
+        const int32_t v[4] = {st[k].size, st[k].exch, st[k].fexch, st[k].last};
+        std::copy(v, v + 4, steps4 + 4 * k);
     }
     return 0;
 }

@@ -250,3 +250,204 @@ bool build_march_plan(const cice_evp_hip_dims &d, int own_max, bool wrap_inside,
     }
     return true;
 }
+
+bool build_march_layout(const cice_evp_hip_dims &d, const MarchAsk &ask, MarchLayout &L)
+{
+    L = MarchLayout();
+    MarchPlan &P = L.plan;
+    MarchFold &F = L.fold;
+    auto refuse = [&](const std::string &why) { L.why = why; return false; };
+    // tripole grid: the rectangle is the zone under the fold band, whose height follows from the rim
+    const bool tripole = d.ns_boundary_type == CICE_EVP_BND_TRIPOLE || d.ns_boundary_type == CICE_EVP_BND_TRIPOLET;
+    // the rectangles of all ranks, this rank's strips and the exchange lists: the same verdict on every rank
+    auto plan = [&](int e) -> bool {
+        F = MarchFold();
+        if (tripole && !build_march_fold(d, e, ask.tyb, F)) {
+            P = MarchPlan();
+            P.error = F.error;
+            F = MarchFold();
+            return false;
+        }
+        return build_march_plan(d, ask.own_max, ask.wrap_inside, e, P, F.H);
+    };
+    // cells a rank holds beyond its own on every side with a neighbour: the ring of ext + P cells is then exchanged every
+    // (ext + P)-th subcycle only (march_plan.h); 4 = after every second pass of four.  (Rounds 4-5, two subcycles per pass and a
+    // two-cell ring, 3600 x 2400 as 4x2 pieces, one-GPU rehearsal: 54.3 / 52.3 / 52.0 / 51.2 us per subcycle with ext 0 / 2 / 4 / 6
+    // against 47.0 without any exchange.)
+    int ext = ask.ext == MARCH_ASK_UNSET ? -1 : std::max(0, ask.ext & ~1);
+    if (ext >= 0) {
+        if (!plan(ext)) return refuse(P.error);
+    } else {
+        // Default (round 6): the widest rim of 12 / 8 / 4 cells that costs no rank a strip more than a rim of 4 does and at most 2 %
+        // more rows -- the exchange then comes every 16th / 12th / 8th subcycle for the same bytes per subcycle.  (The 8 x 1 pieces of
+        // 3600 x 2400: 450 + 2 x 12 = 474 columns still fit the 9 strips that 458 need; measured on one GPU, ring exchanged with the
+        // rank itself, an exchange costs ~38 us: 4.8 us per subcycle at every 8th.)  Every rank reaches the same value from the global
+        // block table; a layout the plan refuses (a rank too thin next to a closed boundary) tries the next narrower rim.
+        bool ok = false;
+        std::string first_error;
+        for (int e : {12, 8, 4, 0}) {
+            if (!plan(e)) {
+                if (first_error.empty()) first_error = P.error;
+                continue;
+            }
+            bool fits = true;
+            const bool ew_cyc = d.ew_boundary_type == CICE_EVP_BND_CYCLIC;
+            for (const MarchRect &R : P.all) {
+                if (!R.ok || e <= 4) continue;
+                const bool span = ask.wrap_inside && ew_cyc && R.nxr == d.nx_global;      // wraps inside: no rim in x
+                const int w = (R.gx0 > 0 || ew_cyc) ? 1 : 0, ea = (R.gx0 + R.nxr < d.nx_global || ew_cyc) ? 1 : 0;
+                const int sn = R.gy0 > 0 ? 1 : 0, nn = R.gy0 + R.nyr < d.ny_global ? 1 : 0;
+                const int own_eff = std::min(ask.own_max > 0 ? ask.own_max : MARCH_PLAN_OWN, MARCH_PLAN_OWN);
+                const int w4 = R.nxr + (span ? 0 : 4 * (w + ea)), we = R.nxr + (span ? 0 : e * (w + ea));
+                if ((we + own_eff - 1) / own_eff > (w4 + own_eff - 1) / own_eff) fits = false;
+                if ((long)(R.nyr + e * (sn + nn)) * 100 > (long)(R.nyr + 4 * (sn + nn)) * 102) fits = false;
+            }
+            if (fits) { ext = e; ok = true; break; }
+        }
+        if (!ok) return refuse(first_error.empty() ? P.error : first_error);
+    }
+    L.ext = ext;
+    L.ring_valid = ext + PW;
+    // Subcycles per pass.  Round 6 measured what binds the kernel: a wave issues one instruction per 2.4 ns whatever it is, and a
+    // row costs ~640 instructions per level plus ~350 that do not depend on the number of levels (loads, stores, addressing, the
+    // register pipelines); a segment of sl rows marches sl + 2K - 1, the warm-up rows with part of the levels idle.  Measured on
+    // the 8 x 1 and 4 x 2 pieces of 3600 x 2400 (22- and 20-row segments, profiles/r06_ring_rank.txt): 58.0 / 50.0 / 49.1 and
+    // 54.9 / 46.8 / 46.0 us per subcycle with two / three / four subcycles per pass; 3600 x 2400 itself (160 rows) 362 / 315 / 293.
+    // Four from 12 rows per segment, three from 8, two below.  Every rank must run the same passes (the ring is exchanged between
+    // them), so the rule looks at the SHORTEST segment of any rank, which every rank works out from the global block table alone.
+    // The test build can ask for a value.
+    {
+        int slmin = 1 << 30;
+        for (const MarchRect &R : P.all) {
+            if (!R.ok) continue;
+            const int grow = d.nranks > 1 ? 2 * ext : 0;
+            const int ns = (R.nxr + grow + MARCH_PLAN_OWN - 1) / MARCH_PLAN_OWN;
+            const int nseg = std::max(1, 1024 / ns);
+            slmin = std::min(slmin, std::max(6, (R.nyr + grow + nseg - 1) / nseg));
+        }
+        L.kpass = std::min(PW, slmin >= 12 ? 4 : slmin >= 8 ? 3 : 2);
+    }
+    if (ask.kpass != MARCH_ASK_UNSET) L.kpass = std::min(PW, std::max(2, ask.kpass));
+    if (P.peers.size() > (size_t)MARCH_PLAN_MAXPEER) return refuse("more ring neighbours than the exchange lists hold");
+    // blocks must tile [gx0, gx0+nxr) x [gy0, gy0+nyr) with full blocks of bsx x bsy (the last column / row may be smaller)
+    auto bnx = [&](int b) { return d.ihi[b] - d.ilo[b] + 1; };
+    auto bny = [&](int b) { return d.jhi[b] - d.jlo[b] + 1; };
+    int gx0 = 1 << 30, gy0 = 1 << 30, gx1 = 0, gy1 = 0;
+    for (int b = 0; b < d.nblocks; ++b) {
+        gx0 = std::min(gx0, d.iglob0[b]); gy0 = std::min(gy0, d.jglob0[b]);
+        gx1 = std::max(gx1, d.iglob0[b] + bnx(b) - 1); gy1 = std::max(gy1, d.jglob0[b] + bny(b) - 1);
+    }
+    const int nxr = gx1 - gx0 + 1, nyr = gy1 - gy0 + 1;
+    int bsx = 0, bsy = 0;
+    for (int b = 0; b < d.nblocks; ++b) {
+        if (d.iglob0[b] == gx0) bsx = std::max(bsx, bnx(b));
+        if (d.jglob0[b] == gy0) bsy = std::max(bsy, bny(b));
+    }
+    if (bsx <= 0 || bsy <= 0) return refuse("no block at the origin of the rectangle");
+    const int nbx = (nxr + bsx - 1) / bsx, nby = (nyr + bsy - 1) / bsy;
+    if ((long)nbx * nby != d.nblocks) return refuse("blocks do not tile a rectangle");
+    L.blkid.assign((size_t)nbx * nby, -1);
+    L.org.assign(d.nblocks, MarchOrg{0, 0});
+    for (int b = 0; b < d.nblocks; ++b) {
+        const int ox = d.iglob0[b] - gx0, oy = d.jglob0[b] - gy0;
+        if (ox % bsx || oy % bsy) return refuse("block origins off the block grid");
+        const int bi = ox / bsx, bj = oy / bsy;
+        if (bnx(b) != std::min(bsx, nxr - ox) || bny(b) != std::min(bsy, nyr - oy)) return refuse("irregular block sizes");
+        if (L.blkid[(size_t)bj * nbx + bi] >= 0) return refuse("two blocks at one place");
+        L.blkid[(size_t)bj * nbx + bi] = b;
+        L.org[b] = MarchOrg{ox + P.ext_w, oy + P.ext_s};        // block origins in the rectangle the rank HOLDS
+    }
+    if (nxr != P.owned.nxr || nyr - F.H != P.owned.nyr || gx0 - 1 != P.owned.gx0 || gy0 - 1 != P.owned.gy0)
+        return refuse("local blocks disagree with the global block table");
+    L.bsx = bsx; L.bsy = bsy; L.nbx = nbx; L.nby = nby;
+    const MarchRect &me = P.me;       // held: own cells + the redundant rim
+    L.dup.assign(P.dup.size(), MARCH_PLAN_NODUP);
+    for (size_t k = 0; k < P.dup.size(); ++k)
+        if (P.dup[k] >= 0) L.dup[k] = (uint32_t)((((size_t)(P.dup[k] >> 8)) * MARCH_PLAN_S_NF * 64 + (P.dup[k] & 255)) * 8);
+    L.ldx = ((me.nstrips * me.own + 64 + 2 * PW + 7) / 8) * 8;
+    L.rows = me.nyr + 2 * PW + 3;      // y = -P .. nyr+P+2: halo, two rows the prefetch may touch, the dump row
+    L.nblk = (size_t)L.rows * me.nstrips;
+    if ((unsigned long long)L.nblk * MARCH_PLAN_S_NF * 512 >= (1ull << 32)) return refuse("state buffer beyond 32-bit byte offsets");
+    // segments: one wave per SIMD (1024 of them), all resident at once -- measured at 3600 x 2400: 16 segments (960
+    // waves) 318 us per subcycle, 24 (1440: some SIMDs get two) 400, 34 (2040: two each) 378, 12 (720) 372
+    int seglen = ask.seglen;
+    if (seglen <= 0) {
+        // (medium domains, 0.45M .. 1M cells: shorter segments keep the count near 1000 -- 1080 x 720: 14-row segments 39 us
+        // per subcycle against 53 for the one-subcycle kernel; each segment recomputes ~3.5 rows of warm-up)
+        // (as many segments as fit 1024 waves: 3600 x 2400 has 60 strips -- 17 segments = 1020 waves = 255 workgroups, one per CU,
+        // 302.8 us per subcycle; 16 segments (960 waves, 16 CUs idle) 310.1; 18 (1080: some SIMDs get two) 472 -- round 5, same box)
+        const int want_seg = std::max(1, 1024 / me.nstrips);
+        seglen = std::max(6, (me.nyr + want_seg - 1) / want_seg);
+    }
+    L.seglen = std::min(seglen, me.nyr);
+    L.nseg = (me.nyr + L.seglen - 1) / L.seglen;
+    L.nitems = L.nseg * me.nstrips;
+    if (P.n_send + P.n_recv == 0) return true;
+    // the ring: the peers' lists one after the other, and the same cells in the row-major byte mask
+    for (size_t q = 0; q < P.peers.size(); ++q) {
+        const MarchPeer &p = P.peers[q];
+        L.cut_send[q] = (int)L.send_pos.size(); L.cut_recv[q] = (int)L.recv_pos1.size();
+        L.send_pos.insert(L.send_pos.end(), p.send_pos.begin(), p.send_pos.end());
+        L.recv_pos1.insert(L.recv_pos1.end(), p.recv_pos1.begin(), p.recv_pos1.end());
+        L.recv_pos2.insert(L.recv_pos2.end(), p.recv_pos2.begin(), p.recv_pos2.end());
+        for (size_t k = 0; k < p.send_pos.size(); ++k)
+            L.send_midx.push_back((int32_t)((size_t)((p.send_pos[k] >> 6) / me.nstrips) * L.ldx + PW + p.send_col[k]));
+        for (size_t k = 0; k < p.recv_pos1.size(); ++k)
+            L.recv_midx.push_back((int32_t)((size_t)p.recv_row[k] * L.ldx + PW + p.recv_col[k]));
+    }
+    L.cut_send[P.peers.size()] = (int)L.send_pos.size(); L.cut_recv[P.peers.size()] = (int)L.recv_pos1.size();
+    // Work items of the EARLY launch of an exchange pass (evp_host_march.cpp: march_run): per strip the rows that hold cells some
+    // other rank receives, cut into short segments -- from the send lists themselves, so every sent cell is covered whatever the
+    // layout.  Short segments (a third of the regular length, at least 6 rows) so that the launch, the pack and the
+    // transfer end before the pass they overlap with does; each costs 2K - 1 rows of warm-up like any segment.  The pass
+    // itself then runs over every OTHER (strip, row) of the rectangle (rest_items): the two launches of an exchange pass
+    // store into disjoint cells (round-4 advice: they used to overlap on the band, storing the same bits twice).
+    const int nstr = me.nstrips;
+    std::vector<std::vector<char>> sent((size_t)nstr, std::vector<char>((size_t)me.nyr, 0));
+    for (int pos : L.send_pos) {
+        const int blk = pos >> 6, strip = blk % nstr, y = blk / nstr - PW;
+        if (y >= 0 && y < me.nyr) sent[(size_t)strip][(size_t)y] = 1;
+    }
+    // runs of rows of one strip that are all sent (1) or all not (0), no longer than `most`
+    auto runs = [&](char which, int most, std::vector<MarchItem> &items) {
+        for (int st = 0; st < nstr; ++st)
+            for (int y = 0; y < me.nyr;) {
+                if (sent[(size_t)st][(size_t)y] != which) { ++y; continue; }
+                int y1 = y;
+                while (y1 < me.nyr && y1 - y < most && sent[(size_t)st][(size_t)y1] == which) ++y1;
+                items.push_back(MarchItem{st, y, y1, 0});
+                y = y1;
+            }
+    };
+    runs(1, ask.bandseg > 0 ? ask.bandseg : std::max(6, L.seglen / 3), L.band_items);
+    runs(0, L.seglen, L.rest_items);
+    return true;
+}
+
+std::vector<MarchStep> march_schedule(int ndte, int kpass, int ring_valid, bool has_peers, bool fold)
+{
+    std::vector<MarchStep> steps;
+    if (ndte <= 0 || kpass < 2) return steps;
+    const int q = ndte / kpass;
+    int rem = ndte % kpass;
+    if (rem == 1) {
+        steps.push_back(MarchStep{1, false, false, false});
+        rem = 0;
+    }
+    const size_t first = steps.size();
+    steps.insert(steps.end(), (size_t)q, MarchStep{kpass, false, false, false});
+    if (rem) steps.push_back(MarchStep{rem, false, false, false});
+    // (a pass advances the cells the rank holds -- its own + ext -- and only reads the P-cell ring around them: whatever is left of
+    // the ring afterwards is a state older)
+    int valid = ring_valid;          // cells beyond the rank's own that hold the current state (the gather's exchange just filled them)
+    for (size_t k = first; k < steps.size(); ++k) {
+        MarchStep &s = steps[k];
+        s.last = k + 1 == steps.size();
+        valid = std::min(valid - s.size, ring_valid - PW);
+        const bool spent = !s.last && valid < steps[k + 1].size;
+        s.exch = has_peers && (s.last || spent);
+        s.fexch = fold && spent;
+        if (s.exch || s.fexch) valid = ring_valid;
+    }
+    return steps;
+}

@@ -87,3 +87,45 @@ struct MarchFold {
 bool build_march_fold(const cice_evp_hip_dims &d, int ext, int tyb, MarchFold &F);
 // tile rows [by0, by1) of a block with `gny` rows whose first row is global row gj0 (0-based) that belong to the band's list
 void march_fold_tile_rows(const MarchFold &F, int gj0, int gny, int &by0, int &by1);
+
+// ---- one layout: everything the host of the marching path decides from the dims and a few asked-for integers alone ----
+// (evp_host_march.cpp uploads it, allocates by it, and asserts that these agree with evp_device.h)
+constexpr int MARCH_PLAN_OWN = 64 - 2 * MARCH_PLAN_PAD, MARCH_PLAN_S_NF = 14, MARCH_PLAN_MAXPEER = 16;
+constexpr uint32_t MARCH_PLAN_NODUP = 0xffffffffu;
+constexpr int MARCH_ASK_UNSET = INT32_MIN;
+struct MarchAsk {                   // what the host may be asked for (the test build's switches)
+    int own_max = MARCH_PLAN_OWN;
+    bool wrap_inside = true;
+    int ext = MARCH_ASK_UNSET;      // redundant rim (rounded down to an even number >= 0); unset: the widest of 12 / 8 / 4 / 0 that fits
+    int kpass = MARCH_ASK_UNSET;    // subcycles per pass (2 .. P); unset: by the shortest segment of any rank
+    int seglen = 0, bandseg = 0;    // rows per segment / per work item of an early launch; 0: by the rules
+    int tyb = 5;                    // tile height of the one-subcycle kernel (the fold band's tiles)
+};
+struct MarchOrg { int32_t x, y; };                   // as the kernels read them: int2
+struct MarchItem { int32_t strip, y0, y1, pad; };    // ... int4 {strip, Y0, Y1, 0}
+struct MarchLayout {
+    MarchPlan plan;                 // the rectangle the rank holds (plan.me), its own cells (plan.owned), the peers
+    MarchFold fold;                 // the fold band of a tripole grid (H == 0: none)
+    int ext = 0, ring_valid = MARCH_PLAN_PAD;   // the rim; cells beyond the rank's own that are current after an exchange of the
+                                                // ring (ext + P): that many subcycles can follow before the next exchange
+    int kpass = MARCH_PLAN_PAD;     // subcycles a full pass advances the state by
+    int bsx = 0, bsy = 0, nbx = 0, nby = 0;     // the rank's blocks as a grid of bsx x bsy cells (the last column / row may be smaller)
+    std::vector<int32_t> blkid;     // [nby][nbx] local block index
+    std::vector<MarchOrg> org;      // [nblocks] the block's first interior cell in the rectangle the rank HOLDS
+    int ldx = 0, rows = 0;          // row stride of the byte mask, rows of every buffer
+    size_t nblk = 0;                // (row, strip) blocks per buffer
+    int seglen = 0, nseg = 0, nitems = 0;
+    std::vector<uint32_t> dup;      // [nstrips][64] byte offset, from the start of a state row, of the lane's duplicate (or NODUP)
+    // the ring: the peers' lists one after the other, the mask's indices of the same cells, where each peer's share begins
+    std::vector<int32_t> send_pos, recv_pos1, recv_pos2, send_midx, recv_midx;
+    int cut_send[MARCH_PLAN_MAXPEER + 1] = {}, cut_recv[MARCH_PLAN_MAXPEER + 1] = {};
+    std::vector<MarchItem> band_items, rest_items;   // (strip, rows) that hold a cell some rank receives | every other one
+    std::string why;                // why not (the same verdict, the same words on every rank); L keeps what had been decided by then
+};
+bool build_march_layout(const cice_evp_hip_dims &d, const MarchAsk &ask, MarchLayout &L);
+
+// ---- one schedule: a call of ndte subcycles as q passes of kpass and one of the remaining 2 .. kpass - 1; a single remaining
+// subcycle goes FIRST, through the one-subcycle kernel (size 1).  exch: the ring between ranks travels after the pass -- the next
+// one needs more valid cells than are left, or it is the last; fexch: zone and fold band trade rows, never after the last pass.
+struct MarchStep { int size; bool exch, fexch, last; };
+std::vector<MarchStep> march_schedule(int ndte, int kpass, int ring_valid, bool has_peers, bool fold);

@@ -54,7 +54,7 @@ EXPORTS = [
 # libcice_evp_hip_testing.so only (include/cice_evp_hip_testing.h): plan introspection of the CPU tests, read-outs of the tools,
 # the test transport
 TEST_EXPORTS = [
-    "cice_evp_hip_cgrid_fold_plan", "cice_evp_hip_cgrid_window_plan", "cice_evp_hip_cgrid_window_plan_ext", "cice_evp_hip_cgrid_window_deps", "cice_evp_hip_cgrid_strip_plan", "cice_evp_hip_cgrid_strip_zones", "cice_evp_hip_cgrid_frame_plan", "cice_evp_hip_cgrid_march_fold_plan", "cice_evp_hip_set_test_transport", "cice_evp_hip_march_plan", "cice_evp_hip_march_fold_plan",
+    "cice_evp_hip_cgrid_fold_plan", "cice_evp_hip_cgrid_window_plan", "cice_evp_hip_cgrid_window_plan_ext", "cice_evp_hip_cgrid_window_deps", "cice_evp_hip_cgrid_strip_plan", "cice_evp_hip_cgrid_strip_zones", "cice_evp_hip_cgrid_frame_plan", "cice_evp_hip_cgrid_march_fold_plan", "cice_evp_hip_set_test_transport", "cice_evp_hip_march_plan", "cice_evp_hip_march_fold_plan", "cice_evp_hip_march_layout", "cice_evp_hip_march_schedule",
     "cice_evp_hip_debug_device_allocs", "cice_evp_hip_debug_cuload", "cice_evp_hip_debug_prof", "cice_evp_hip_debug_cgrid_prof", "cice_evp_hip_debug_cgres_prof", "cice_evp_hip_plan_build", "cice_evp_hip_halo_plan", "cice_evp_hip_seam_plan",
     "cice_evp_hip_peer_plan", "cice_evp_hip_peer_signs", "cice_evp_hip_center_plan", "cice_evp_hip_stress_plan",
     "cice_evp_hip_fold_split_plan", "cice_evp_hip_plan_flags", "cice_evp_hip_fold_images_plan", "cice_evp_hip_cgrid_fold_xplan",
@@ -875,6 +875,50 @@ def march_fold_plan(dims: Dims, ext: int = 0, tyb: int = 5) -> dict:
     _check(lib, lib.cice_evp_hip_march_fold_plan(C.byref(dims), ext, tyb, _ip(v), _ip(tr)), "(march_fold_plan)")
     return dict(zone=int(v[0]), band_rows=int(v[1]), ext=int(v[2]), tile_rows_height=int(v[3]), list_row0=int(v[4]),
                 to_block=(int(v[5]), int(v[6])), to_rect=(int(v[7]), int(v[8])), rect_rows=int(v[9]), tile_rows=tr[:int(dims.nblocks)])
+
+
+MARCH_LAYOUT_INFO = ("ext", "ring_valid", "kpass", "bsx", "bsy", "nbx", "nby", "nxr", "nyr", "ldx", "rows", "own", "nstrips", "wrapx", "gx0", "gy0",
+                     "ext_w", "ext_s", "nxo", "nyo", "nyblk", "nblk", "seglen", "nseg", "nitems", "npeers", "n_send", "n_recv", "nband", "nrest",
+                     "fold_h", "fold_zone", "norg", "ndup")
+
+
+def march_layout(dims: Dims, own_max: int = 56, wrap_inside: bool = True, ext: int | None = None, kpass: int | None = None,
+                 seglen: int = 0, bandseg: int = 0, tyb: int = 5) -> dict:
+    """Host-only: what the marching path's host decides from the dims and what it is asked for (None: its own rules) -- rim, subcycles
+    per pass, block grid, sizes, segments, exchange lists, work items of an overlapped exchange pass (CPU tests; see the testing
+    header).  Raises EvpHipError with the library's own words where the layout refuses the domain."""
+    lib = load_library(testing=True)
+    unset = -2 ** 31
+    ask = np.array([own_max, int(wrap_inside), unset if ext is None else ext, unset if kpass is None else kpass, seglen, bandseg, tyb],
+                   dtype=np.int32)
+    info = np.zeros(len(MARCH_LAYOUT_INFO), dtype=np.int32)
+    _check(lib, lib.cice_evp_hip_march_layout(C.byref(dims), _ip(ask), _ip(info), *[None] * 7), "(march_layout)")
+    out = {k: int(v) for k, v in zip(MARCH_LAYOUT_INFO, info)}
+    ns, nr, npeer = out["n_send"], out["n_recv"], out["npeers"]
+    blkid = np.zeros((out["nby"], out["nbx"]), dtype=np.int32)
+    org = np.zeros((out["norg"], 2), dtype=np.int32)
+    dup = np.zeros((out["nstrips"], 64), dtype=np.uint32)
+    ring = np.zeros(max(2 * ns + 3 * nr, 1), dtype=np.int32)
+    cuts = np.zeros((2, npeer + 1), dtype=np.int32)
+    band = np.zeros((out["nband"], 4), dtype=np.int32)
+    rest = np.zeros((out["nrest"], 4), dtype=np.int32)
+    _check(lib, lib.cice_evp_hip_march_layout(C.byref(dims), _ip(ask), None, _ip(blkid), _ip(org), dup.ctypes.data_as(C.POINTER(C.c_uint32)),
+                                              _ip(ring), _ip(cuts), _ip(band), _ip(rest)), "(march_layout)")
+    out.update(blkid=blkid, org=org, dup=dup, send_pos=ring[:ns], send_midx=ring[ns:2 * ns], recv_pos1=ring[2 * ns:2 * ns + nr],
+               recv_pos2=ring[2 * ns + nr:2 * ns + 2 * nr], recv_midx=ring[2 * ns + 2 * nr:2 * ns + 3 * nr], cut_send=cuts[0], cut_recv=cuts[1],
+               band_items=band, rest_items=rest)
+    return out
+
+
+def march_schedule(ndte: int, kpass: int, ring_valid: int, has_peers: bool, fold: bool) -> list:
+    """Host-only: the steps of a call of ndte subcycles on the marching path as (size, exch, fexch, last) -- a step of size 1 is
+    the leading subcycle of the one-subcycle kernel; exch: the ring between ranks travels after the pass, fexch: zone and fold band
+    trade rows after it (CPU tests; march_plan.h: march_schedule, which the host iterates over)."""
+    lib = load_library(testing=True)
+    n = C.c_int32(0)
+    steps = np.zeros((max(ndte, 1), 4), dtype=np.int32)
+    _check(lib, lib.cice_evp_hip_march_schedule(ndte, kpass, ring_valid, int(has_peers), int(fold), C.byref(n), _ip(steps)), "(march_schedule)")
+    return [(int(s[0]), bool(s[1]), bool(s[2]), bool(s[3])) for s in steps[:n.value]]
 
 
 def halo_plan(dims: Dims) -> dict:

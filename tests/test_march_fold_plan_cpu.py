@@ -31,19 +31,18 @@ def fixture_dims(name):
 
 
 def simulate(plan, ny, kpass, nsub, to_block=None, to_rect=None):
-    """Both sides over nsub subcycles with the host's schedule (passes of kpass; the ring is exchanged when fewer valid rows
-    are left than the next pass advances -- evp_host_march.cpp: march_run).  Returns None, or what went wrong."""
+    """Both sides over nsub subcycles with the host's schedule: the very steps march_run iterates over (march_plan.cpp:
+    march_schedule -- passes of kpass; the ring is exchanged when fewer valid rows are left than the next pass advances).  Returns
+    None, or what went wrong."""
     zone, ext = plan["zone"], plan["ext"]
     to_block = to_block or plan["to_block"]
     to_rect = to_rect or plan["to_rect"]
     held = plan["rect_rows"]                       # rows the rectangle advances; it reads P more above them
     zvalid = set(range(0, held + P))               # the gather at the start of a call fills all of it
     bvalid = set(range(0, ny))                     # the block layout is complete then
-    ring = ext + P
-    valid = ring
-    left = nsub - (nsub % kpass == 1)              # (the host runs a single left-over subcycle first, over the whole domain)
-    while left >= 2:
-        k = min(kpass, left)
+    for k, _, fexch, _ in evp.march_schedule(nsub, kpass, ext + P, False, True):
+        if k == 1:                                 # (the host runs a single left-over subcycle first, over the whole domain)
+            continue
         # The zone's pass advances k subcycles at once: the levels in between live in the kernel (it evaluates them on the ring
         # rows too, as far as they are valid) and only rows below `held` are stored -- a stored row is current when the k rows
         # on either side of it were.  South of row 0 lies the closed boundary.
@@ -56,10 +55,7 @@ def simulate(plan, ny, kpass, nsub, to_block=None, to_rect=None):
                       if r - 1 in bvalid and r in bvalid and (r == ny - 1 or r + 1 in bvalid)}
             if not set(range(zone, ny)) <= bvalid:
                 return f"the band lost one of its own rows (valid from {min(bvalid)})"
-        left -= k
-        valid = min(valid - k, ring - P)
-        nxt = min(kpass, left)
-        if left >= 2 and valid < nxt:
+        if fexch:
             src_b, src_r = set(range(*to_block)), set(range(*to_rect))
             if not src_b <= zvalid:
                 return "the exchange copied a stale row of the rectangle into the block layout"
@@ -67,8 +63,49 @@ def simulate(plan, ny, kpass, nsub, to_block=None, to_rect=None):
                 return "the exchange copied a stale row of the block layout into the rectangle"
             bvalid |= src_b
             zvalid |= src_r
-            valid = ring
     return None
+
+
+def countdown(ndte, kpass, ring_valid, has_peers, fold):
+    """The schedule restated: a single left-over subcycle first, passes of kpass, the remaining 2 .. kpass - 1; every pass costs its
+    size in valid cells beyond the rank's own, and what is left of the P-cell ring after a pass is a state older; the ring travels
+    when the next pass needs more than there is (and, between ranks, after the last pass)."""
+    steps = [(1, False, False, False)] if ndte % kpass == 1 else []
+    sizes = np.array([kpass] * (ndte // kpass) + ([ndte % kpass] if ndte % kpass > 1 else []), dtype=int)
+    valid = ring_valid
+    for i, size in enumerate(sizes):
+        last = i == len(sizes) - 1
+        valid = min(valid - size, ring_valid - P)
+        spent = not last and valid < sizes[i + 1]
+        steps.append((int(size), has_peers and (last or spent), fold and spent, last))
+        if steps[-1][1] or steps[-1][2]:
+            valid = ring_valid
+    return steps
+
+
+@pytest.mark.parametrize("kpass", (2, 3, 4))
+def test_schedule_sizes_and_countdown(kpass):
+    for ndte in range(1, 41):
+        for ext in EXTS:
+            for has_peers in (False, True):
+                for fold in (False, True):
+                    st = evp.march_schedule(ndte, kpass, ext + P, has_peers, fold)
+                    what = (ndte, kpass, ext, has_peers, fold, st)
+                    assert sum(s[0] for s in st) == ndte, what
+                    assert all(s[0] >= 2 for s in st[1:]) and all(1 <= s[0] <= kpass for s in st), what
+                    assert st == countdown(ndte, kpass, ext + P, has_peers, fold), what
+                    if st[0][0] == 1:
+                        assert st[0][1:] == (False, False, False), what
+                    passes = [s for s in st if s[0] > 1]
+                    assert [s[3] for s in passes] == [False] * (len(passes) - 1) + [True] * bool(passes), what
+                    # no pass runs on fewer valid cells than it advances: between two exchanges at most ring_valid subcycles
+                    if has_peers or fold:
+                        run = 0
+                        for size, exch, fexch, last in passes:
+                            run += size
+                            assert run <= ext + P, what
+                            if exch or fexch:
+                                run = 0
 
 
 def check_plan(d, blocks, ny, ext, tyb, tfold=False):
