@@ -326,6 +326,7 @@ int cice_evp_hip_init(const cice_evp_hip_dims *dims, const cice_evp_hip_params *
     S.d = host_dims();
 
     if (!build_halo_plan(*dims, S.plan)) return fail(-3, "halo plan: %s", S.plan.error.c_str());
+    build_stress_tfold_xplan(*dims, S.plan, S.stress_x);
     if (env_on(env_test("CICE_EVP_HIP_SELF_EXCHANGE"), false) && dims->nranks == 1) {
         // test hook: route the on-device ghost copies through pack -> ncclSend/ncclRecv (to
         // self) -> unpack, so that the remote-halo code path runs on a single GPU
@@ -613,12 +614,17 @@ int cice_evp_hip_subcycle(int32_t ndte)
     return 0;
 }
 
-// 1 if cice_evp_hip_stress_halo can do its job on this rank layout (tripole: always; tripoleT: the top row on one rank and no
-// eliminated block in it; other boundaries: there is nothing to do, 1), else 0 -- for a host that wants to keep the stresses
+// tripoleT with a top-row partner on another rank: the symmetrisation goes through the fold exchange (S.stress_x; the same
+// answer on every rank, the exchange is a collective)
+static bool stress_tfold_exchange() { return S.plan.tfold && S.stress_x.ok() && S.stress_x.collective; }
+
+// 1 if cice_evp_hip_stress_halo can do its job on this rank layout (tripole: always; tripoleT: no eliminated block among the
+// cells the top row mirrors; other boundaries: there is nothing to do, 1), else 0 -- for a host that wants to keep the stresses
 // on the device between calls and must know whether evp()'s twelve ice_HaloUpdate_stress calls can be left to the library.
 int cice_evp_hip_stress_halo_available(void)
 {
     if (!S.ready) return 0;
+    if (stress_tfold_exchange()) return 1;
     return (S.plan.tfold && S.plan.stress_remote) ? 0 : 1;
 }
 
@@ -626,11 +632,16 @@ int cice_evp_hip_stress_halo_available(void)
 // on the host arrays after the subcycle loop (12 x ice_HaloUpdate_stress, ice_dyn_evp.F90:1321-1389).
 int cice_evp_hip_stress_halo(void)
 {
-    if (!S.ready || !S.uploaded) return fail(-1, "state not uploaded");
+    if (!S.ready) return fail(-1, "state not uploaded");
+    // (the layout's verdict first: it does not depend on what has been uploaded)
+    if (S.plan.tfold && S.plan.stress_remote && !stress_tfold_exchange())
+        return fail(-9, "tripoleT: on this layout the stress symmetrisation stays with the host (evp() applies it to its own "
+                        "arrays, ice_dyn_evp.F90:1321-1389): %s", S.stress_x.why.c_str());
+    if (!S.uploaded) return fail(-1, "state not uploaded");
     if (S.plan.tfold) {
-        if (S.plan.stress_remote)
-            return fail(-9, "tripoleT: with the top row split over ranks (or next to an eliminated block) the stress symmetrisation "
-                            "stays with the host (evp() applies it to its own arrays, ice_dyn_evp.F90:1321-1389)");
+        // the top row on several ranks: each pair (a1, a2) through the C grid's fold exchange, then the three lists with the
+        // partners' values in staging slots -- collective, as the u-fold form below
+        if (stress_tfold_exchange()) return stress_tfold_split();
         evp_launch_halo_stress_tfold(S.sig[S.cur], S.h_stress_dst, S.h_stress_src, S.n_stress, S.h_stress_own_dst, S.h_stress_own_src,
                                      S.n_stress_own, S.stream);
         // the north-west corner ghost cells: both arrays of a pair, each from the other's row NY-1 (which nothing above writes)
@@ -1060,6 +1071,26 @@ int cice_evp_hip_plan_build(const cice_evp_hip_dims *dims)
 {
     if (!dims) return fail(-1, "null dims");
     if (!build_halo_plan(*dims, S.plan)) return fail(-3, "halo plan: %s", S.plan.error.c_str());
+    build_stress_tfold_xplan(*dims, S.plan, S.stress_x);
+    return 0;
+}
+
+// tripoleT stress symmetrisation of the plan built last on any rank layout (fold_prep_plan.h), see the testing header
+int cice_evp_hip_stress_tfold_xplan(int32_t *info4, int32_t *dst, int32_t *src, int32_t *own_dst, int32_t *own_src,
+                                    int32_t *corner_dst, int32_t *corner_src)
+{
+    const StressTfoldXPlan &X = S.stress_x;
+    if (info4) {
+        info4[0] = (int32_t)X.dst.size(); info4[1] = (int32_t)X.own_dst.size(); info4[2] = (int32_t)X.corner_dst.size();
+        info4[3] = X.collective ? 1 : 0;
+    }
+    if (!X.ok()) {                                            // declined: the reason is the last error's text
+        g_err = X.why;
+        return 1;
+    }
+    copy_out(dst, X.dst); copy_out(src, X.src);
+    copy_out(own_dst, X.own_dst); copy_out(own_src, X.own_src);
+    copy_out(corner_dst, X.corner_dst); copy_out(corner_src, X.corner_src);
     return 0;
 }
 

@@ -590,6 +590,33 @@ struct EvpCgFold {
     int maxn;
 };
 void evp_launch_cgrid_fold(const EvpCgFold &F, hipStream_t st);
+// The fold step of location 0 (centre) for the T-grid fields of a preparation in one pass (evp_fold_prep.hip): the entries
+// above, up to 12 arrays, a gather launch into tmp (narrays x n) and a scatter launch -- every read before every write over
+// the WHOLE list.  An operand is a cell or a staging slot behind the cells (the arrays carry the fold exchange's tail).
+#define EVP_FOLD_BATCH_MAX 12
+struct EvpFoldBatch {
+    double *x[EVP_FOLD_BATCH_MAX];
+    double isign[EVP_FOLD_BATCH_MAX];     // -1 vector kind, +1 scalar
+    int narrays;
+    const int *dst, *a, *b;
+    const unsigned char *flip;
+    int n;
+    double *tmp;
+};
+void evp_launch_fold_center_batch(const EvpFoldBatch &F, hipStream_t st);
+// tripoleT stress symmetrisation on any rank layout (fold_prep_plan.h; evp_fold_prep.hip): the three lists for the twelve
+// stresses in one gather + one scatter.  An operand >= ncell is a staging slot: its raw value in tails[array][operand - ncell].
+struct EvpStressTfold {
+    double *sig[12];
+    const double *tails;       // 12 x ntail
+    int ncell, ntail;
+    const int *dst, *src, *odst, *osrc, *cdst, *csrc;
+    int n, no, nc;
+    double *tmp;               // 12 x (n + no + nc)
+};
+void evp_launch_stress_tfold_split(const EvpStressTfold &T, hipStream_t st);
+// a2[c] = a[c], b2[c] = b[c] on the listed cells: what an exchange sends, into scratch arrays that carry its tail
+void evp_launch_fold_stage2(const double *a, const double *b, double *a2, double *b2, const int *cells, int n, hipStream_t st);
 // m4: iceTmask | iceUmask | iceEmask | iceNmask, n 32-bit words each
 void evp_launch_cgrid_mask(const EvpCgrid &A, const int *m4, hipStream_t st);
 void evp_launch_cgrid_umask(const EvpCgrid &A, double *scratch, int back, hipStream_t st);

@@ -39,6 +39,7 @@
 #include "halo_plan.h"
 #include "cgrid_plan.h"
 #include "march_plan.h"
+#include "fold_prep_plan.h"
 
 namespace evp_host {
 
@@ -149,6 +150,7 @@ struct State {
     bool push_ok = false;
 
     HaloPlan plan;
+    StressTfoldXPlan stress_x;   // tripoleT stress symmetrisation on any rank layout (fold_prep_plan.h), built beside the plan
     int32_t *h_local_dst = nullptr, *h_local_src = nullptr;
     int8_t *h_local_sign = nullptr;
     int n_local = 0;
@@ -184,6 +186,19 @@ struct State {
         int n_cells = 0, n_dst[2] = {0, 0}, n_seam = 0;
         double *scr[2] = {nullptr, nullptr};
     } foldx;
+    // device side of what runs around the loop where the fold rows are split over ranks (evp_fold_prep.hip): the centre fold
+    // step of the preparation's T-grid fields from HaloPlan::cg_fold[0], and the lists of stress_x with their scratch
+    struct FoldPrep {
+        bool center_ready = false, stress_ready = false;
+        int32_t *dst = nullptr, *a = nullptr, *b = nullptr;
+        uint8_t *flip = nullptr;
+        int n = 0;
+        double *tmp = nullptr;                     // EVP_FOLD_BATCH_MAX x n
+        int32_t *s_dst = nullptr, *s_src = nullptr, *o_dst = nullptr, *o_src = nullptr, *c_dst = nullptr, *c_src = nullptr;
+        int ns = 0, no = 0, nc = 0;
+        double *s_tmp = nullptr, *tails = nullptr; // 12 x (ns + no + nc); 12 x cg_tail
+        double *scr[2] = {nullptr, nullptr};       // the pair an exchange of two stresses runs on (n + cg_tail)
+    } fprep;
     struct Prep {
         bool geo = false;
         uint8_t *tmask = nullptr, *umask = nullptr, *umask_old = nullptr, *tmphm = nullptr;
@@ -427,8 +442,17 @@ int check_tfields(const double *const *tfields11);
 // evp_host_loop.cpp
 void fill_direct(EvpDirect &D);
 int halo_remote_pair(double *a, double *bb, bool masked = false, bool has_tail = false);
-// the C grid's exchange of two arrays (with staging tail) through S.cgx: ghost cells and fold sources, one handshake
-int cgrid_fold_exchange(double *a, double *bb);
+// the C grid's exchange of two arrays (with staging tail) through S.cgx: ghost cells and fold sources, one handshake.  len: the
+// doubles either array holds, as the caller allocated it -- the staging slots lie BEHIND the cells, so an array shorter than
+// fold_exchange_len() is an error return, never a launch
+int cgrid_fold_exchange(double *a, double *bb, size_t len);
+inline size_t fold_exchange_len() { return S.n + (S.plan.cg_split ? (size_t)S.plan.cg_tail : 0); }
+// elements of a T-grid array of the preparation (either grid): its cells and the staging slots of whichever exchange carries it
+inline size_t prep_len() { return S.n + (size_t)std::max(S.plan.tail, S.plan.cg_split ? S.plan.cg_tail : 0); }
+// the centre fold step (HaloPlan::cg_fold[0]) of narr <= EVP_FOLD_BATCH_MAX arrays of len doubles after their fold exchange
+int fold_center_batch(double *const *arr, const bool *vec, int narr, size_t len);
+// tripoleT stress symmetrisation through the fold exchange (S.stress_x; collective)
+int stress_tfold_split();
 void fill_direct_cg(EvpDirect &D);      // ... its mailbox form
 // centre-kind fields across a tripole fold whose row is split over ranks (halo_plan.h): dstA[d] <- fa * (the exchange of the
 // shifted copy of srcA)[d] for d in the list, likewise B.  kind 0: the centre-field ghost cells of the preparation phase,

@@ -262,6 +262,8 @@ static bool remote() { return !S.plan.peers.empty() || !S.plan.cg_peers.empty();
 // the blocks next to the tripole fold have more than one owner: the C grid's exchange (ghost cells + fold sources into
 // staging slots n + t of every exchanged array) replaces the velocity lists at every exchange point
 static bool fold_exchange() { return CG.tripole && S.plan.cg_split; }
+// length of an exchanged array: the rank's cells and, where the fold rows have several owners, the staging slots of the fold exchange
+static size_t field_len() { return S.n + (fold_exchange() ? (size_t)S.plan.cg_tail : 0); }
 // ghost cells owned by other ranks, for two of the loop's arrays (no-op on one rank).  Every exchange inside the loop
 // goes through the masked halo when the host has handed one over (maskhalo_dyn: evp() builds it for the C grid as the
 // five-point dilation of iceTmask, ice_dyn_evp.F90:739-770, and passes halo_info_mask to every dyn_haloUpdate of the
@@ -269,7 +271,7 @@ static bool fold_exchange() { return CG.tripole && S.plan.cg_split; }
 #define XCHG(a, b)                                             \
     do {                                                       \
         if (fold_exchange()) {                                 \
-            if (int rc_ = cgrid_fold_exchange((a), (b))) return rc_; \
+            if (int rc_ = cgrid_fold_exchange((a), (b), field_len())) return rc_; \
         } else if (remote()) {                                 \
             if (int rc_ = halo_remote_pair((a), (b), true)) return rc_; \
         }                                                      \
@@ -346,8 +348,6 @@ static int enqueue_phases(const EvpCgrid &A, int ndte, bool first)
     return 0;
 }
 
-// length of an exchanged array: the rank's cells and, where the fold rows have several owners, the staging slots of the fold exchange
-static size_t field_len() { return S.n + (fold_exchange() ? (size_t)S.plan.cg_tail : 0); }
 // The current and the other allocation of PP_FIELDS as a schedule sees them while it enqueues: swap() per subcycle, `swapped` for Ran
 struct PingPong {
     double *cur[5], *alt[5];
@@ -1452,7 +1452,7 @@ int finish_upload(int32_t visc_method)
         fill(A);
         evp_launch_cgrid_umask(A, CG.umaskd, 0, S.stream);
         if (fold_exchange()) {
-            if (int rc = cgrid_fold_exchange(CG.umaskd, CG.umaskd)) return rc;
+            if (int rc = cgrid_fold_exchange(CG.umaskd, CG.umaskd, field_len())) return rc;
         } else if (int rc = halo_remote_pair(CG.umaskd, CG.umaskd)) {
             return rc;
         }
@@ -1667,7 +1667,10 @@ int cice_evp_hip_cgrid_set_prep_geometry(const int32_t *tmask, const int32_t *um
 {
     if (!S.ready || !CG.geo) return fail(-1, "C-grid EVP: geometry not set");
     if (!tmask || !umaskCD || !emask || !nmask || !fcor_blk || !fcorE_blk || !fcorN_blk) return fail(-1, "null argument");
-    if (S.plan.center_fold_remote || (S.plan.tfold && S.plan.center_tf_remote) || (CG.tripole && S.plan.cg_split))
+    // Where the blocks next to the fold have several owners the T-grid fields go through the fold exchange and the centre fold
+    // step of its lists (cice_evp_hip_cgrid_prep).  What stays refused is a fold neighbourhood with an eliminated block on a
+    // layout without that exchange: the rank-local lists cannot name its cells
+    if (!fold_exchange() && (S.plan.center_fold_remote || (S.plan.tfold && S.plan.center_tf_remote)))
         return fail(-9, "device preparation: T-grid ghost cells across the tripole fold live on other ranks here; keep "
                         "evp()'s host preparation (cice_evp_hip_cgrid_run) on this configuration");
     CGridState::Prep &Q = CG.prep;
@@ -1682,9 +1685,10 @@ int cice_evp_hip_cgrid_set_prep_geometry(const int32_t *tmask, const int32_t *um
     const double *fc[3] = {fcor_blk, fcorE_blk, fcorN_blk};
     for (int k = 0; k < 3; ++k)
         if ((!Q.fcor[k] && zeros(Q.fcor[k], S.n)) || h2d(Q.fcor[k], fc[k])) return -1;
+    // (with the staging slots of the fold exchange: the ten halo-updated ones travel through it)
     for (auto &p : Q.t)
-        if (!p && zeros(p, S.n)) return -1;
-    if ((!Q.tmass && zeros(Q.tmass, S.n)) || (!Q.maskd && zeros(Q.maskd, S.n))) return -1;
+        if (!p && zeros(p, field_len())) return -1;
+    if ((!Q.tmass && zeros(Q.tmass, field_len())) || (!Q.maskd && zeros(Q.maskd, field_len()))) return -1;
     const HaloPlan &P = S.plan;
     Q.n_center = (int)P.center_dst.size();
     if (Q.n_center && !Q.c_dst) {
@@ -1770,14 +1774,26 @@ int cice_evp_hip_cgrid_prep(const cice_evp_hip_prep_params *pp, const double *co
         for (int k = 0; k < nh; ++k) { H.a[H.narr] = arrs[k].first; H.is_vec[H.narr] = arrs[k].second; ++H.narr; }
         H.dst = Q.c_dst; H.src = Q.c_src; H.vsign = Q.c_vsign; H.n = Q.n_center;
         evp_launch_halo_center(H, S.stream);
-        if (CG.tfold) {
+        if (fold_exchange()) {
+            // the blocks next to the fold on several ranks: pair by pair through the fold exchange (ghost cells other ranks own
+            // up to the fold, raw fold sources into the staging slots), then the fold step of location 0 on all of them in one
+            // pass -- instead of the list's fold-crossing entries, the T-fold step below and the plain exchange.  Collective:
+            // ranks without fold rows take part with empty fold lists.
+            double *pairs[5][2] = {{Q.maskd, Q.tmass}, {Q.t[3], Q.t[4]}, {Q.t[5], Q.t[6]}, {Q.t[7], Q.t[8]}, {Q.t[9], Q.t[10]}};
+            for (int q = 0; q < nh / 2; ++q)
+                if (int rc = cgrid_fold_exchange(pairs[q][0], pairs[q][1], field_len())) return rc;
+            double *x[10];
+            bool vec[10];
+            for (int k = 0; k < nh; ++k) { x[k] = arrs[k].first; vec[k] = arrs[k].second; }
+            if (int rc = fold_center_batch(x, vec, nh, field_len())) return rc;
+        } else if (CG.tfold) {
             // tripoleT: the centre rule rewrites the top physical row (made symmetric, then mirrored) and fills the ghost row
             // from row NY-1: the fold step of location 0, after the plain ghost copies (whose sources it does not write)
             fold({{arrs[0].first, 0, arrs[0].second}, {arrs[1].first, 0, arrs[1].second}, {arrs[2].first, 0, arrs[2].second}, {arrs[3].first, 0, arrs[3].second}});
             fold({{arrs[4].first, 0, arrs[4].second}, {arrs[5].first, 0, arrs[5].second}, {arrs[6].first, 0, arrs[6].second}, {arrs[7].first, 0, arrs[7].second}});
             if (nh == 10) fold({{arrs[8].first, 0, arrs[8].second}, {arrs[9].first, 0, arrs[9].second}});
         }
-        if (S.plan.center_remote) {
+        if (S.plan.center_remote && !fold_exchange()) {
             double *pairs[5][2] = {{Q.maskd, Q.tmass}, {Q.t[3], Q.t[4]}, {Q.t[5], Q.t[6]}, {Q.t[7], Q.t[8]}, {Q.t[9], Q.t[10]}};
             for (int q = 0; q < nh / 2; ++q)
                 if (int rc = halo_remote_pair(pairs[q][0], pairs[q][1])) return rc;
@@ -1792,21 +1808,25 @@ int cice_evp_hip_cgrid_prep(const cice_evp_hip_prep_params *pp, const double *co
     // them -- the tail of a subcycle (phase 4), on every cell (nothing is masked yet)
     evp_launch_cgrid_phase(A, 9, CF_UE, S.stream);
     evp_launch_cgrid_phase(A, 9, CF_VN, S.stream);
-    if (remote())
-        if (int rc = halo_remote_pair(A.f[CF_UE], A.f[CF_VN])) return rc;
+    // (never masked: the halo mask is built from this call's iceTmask)
+    auto exchange = [&](double *a, double *b) -> int {
+        if (fold_exchange()) return cgrid_fold_exchange(a, b, field_len());
+        return remote() ? halo_remote_pair(a, b) : 0;
+    };
+    if (int rc = exchange(A.f[CF_UE], A.f[CF_VN])) return rc;
     fold({{A.f[CF_UE], 2, true}, {A.f[CF_VN], 3, true}});
     evp_launch_cgrid_phase(A, 6, 1, S.stream);
     evp_launch_cgrid_phase(A, 4, 1, S.stream);
-    if (remote()) {
-        if (int rc = halo_remote_pair(A.f[CF_UN], A.f[CF_VE])) return rc;
-        if (int rc = halo_remote_pair(A.f[CF_UU], A.f[CF_VU])) return rc;
-    }
+    if (int rc = exchange(A.f[CF_UN], A.f[CF_VE])) return rc;
+    if (int rc = exchange(A.f[CF_UU], A.f[CF_VU])) return rc;
     fold({{A.f[CF_UN], 3, true}, {A.f[CF_VE], 2, true}, {A.f[CF_UU], 1, true}, {A.f[CF_VU], 1, true}});
     HIPC(hipEventRecord(S.ev1, S.stream));
     Q.h4.resize(4 * S.n);
     HIPC(hipMemcpyAsync(Q.h4.data(), CG.mask4, 4 * S.n * sizeof(int32_t), hipMemcpyDeviceToHost, S.stream));
     HIPC(hipGetLastError());
     HIPC(hipStreamSynchronize(S.stream));
+    if (fold_exchange())                        // a fold exchange whose wait gave up: nothing goes back to the caller
+        if (int rc = direct_check_error()) return rc;
     int32_t *out[4] = {iceTmask, iceUmask, iceEmask, iceNmask};
     for (int k = 0; k < 4; ++k) std::memcpy(out[k], Q.h4.data() + (size_t)k * S.n, S.n * sizeof(int32_t));
     float ms = 0;

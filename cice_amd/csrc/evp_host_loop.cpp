@@ -96,9 +96,13 @@ void fill_direct_cg(EvpDirect &D)
     D.peer_flag = X.peer_flag;
 }
 
-int cgrid_fold_exchange(double *a, double *bb)
+int cgrid_fold_exchange(double *a, double *bb, size_t len)
 {
     const State::CgX &X = S.cgx;
+    // the staging slots lie BEHIND the cells of an array (offsets S.n .. S.n + cg_tail - 1): a shorter target would be
+    // written out of bounds
+    if (len < fold_exchange_len())
+        return fail(-3, "fold exchange of an array of %zu doubles: the rank's cells and staging slots take %zu", len, fold_exchange_len());
     if (S.plan.cg_peers.empty()) return 0;       // (its own channel: only the ranks that trade entries take part)
     if (S.direct.on) {
         EvpDirect D;
@@ -168,6 +172,74 @@ static int foldx_setup()
             if (S.mem.alloc(p, S.nuv, true)) return -1;
         F.ready = true;
     }
+    return 0;
+}
+
+// ---- around the loop, fold rows split over ranks (evp_fold_prep.hip) ----
+// After the fold exchange of its arrays (each len doubles: cells + staging slots): the fold step of location 0 on all of them
+// in one pass.  On a T-fold the destinations in row NY are sources of their partners: gather launch, then scatter launch.
+int fold_center_batch(double *const *arr, const bool *vec, int narr, size_t len)
+{
+    if (narr < 0 || narr > EVP_FOLD_BATCH_MAX) return fail(-1, "fold_center_batch: %d arrays (at most %d)", narr, EVP_FOLD_BATCH_MAX);
+    if (len < fold_exchange_len())
+        return fail(-3, "centre fold step on arrays of %zu doubles: the rank's cells and staging slots take %zu", len, fold_exchange_len());
+    State::FoldPrep &Q = S.fprep;
+    if (!Q.center_ready) {
+        const FoldList &L = S.plan.cg_fold[0];
+        const int32_t lim = (int32_t)fold_exchange_len();
+        for (size_t k = 0; k < L.dst.size(); ++k)
+            if (L.dst[k] < 0 || L.dst[k] >= (int32_t)S.n || L.a[k] >= lim || L.b[k] >= lim)
+                return fail(-3, "centre fold step: entry %zu names a cell outside the rank's arrays", k);
+        Q.n = (int)L.dst.size();
+        if (Q.n && (S.mem.upload(Q.dst, L.dst) || S.mem.upload(Q.a, L.a) || S.mem.upload(Q.b, L.b) || S.mem.upload(Q.flip, L.flip) ||
+                    S.mem.alloc(Q.tmp, (size_t)EVP_FOLD_BATCH_MAX * Q.n))) return -1;
+        Q.center_ready = true;
+    }
+    EvpFoldBatch F{};
+    for (int k = 0; k < narr; ++k) { F.x[k] = arr[k]; F.isign[k] = vec[k] ? -1.0 : 1.0; }
+    F.narrays = narr;
+    F.dst = Q.dst; F.a = Q.a; F.b = Q.b; F.flip = Q.flip; F.n = Q.n; F.tmp = Q.tmp;
+    evp_launch_fold_center_batch(F, S.stream);
+    return 0;
+}
+
+// tripoleT, the twelve ice_HaloUpdate_stress calls with the top row on several ranks (S.stress_x): the stresses carry no
+// staging tail, so each pair (a1, a2) = (_1, _3), (_2, _4) of a family is exchanged through two scratch arrays of the full
+// length -- the cells the exchange sends copied in, the raw values it brings kept per array -- then the three lists in one
+// gather + one scatter.  Every rank takes part in the six exchanges, with or without entries of its own.
+int stress_tfold_split()
+{
+    State::FoldPrep &Q = S.fprep;
+    const StressTfoldXPlan &X = S.stress_x;
+    const size_t len = fold_exchange_len(), tail = len - S.n;
+    if (!Q.stress_ready) {
+        auto up = [&](int32_t *&dp, const std::vector<int32_t> &v) -> int { return v.empty() ? 0 : S.mem.upload(dp, v); };
+        Q.ns = (int)X.dst.size(); Q.no = (int)X.own_dst.size(); Q.nc = (int)X.corner_dst.size();
+        if (up(Q.s_dst, X.dst) || up(Q.s_src, X.src) || up(Q.o_dst, X.own_dst) || up(Q.o_src, X.own_src) || up(Q.c_dst, X.corner_dst) ||
+            up(Q.c_src, X.corner_src)) return -1;
+        if (S.mem.alloc(Q.s_tmp, (size_t)12 * std::max(1, Q.ns + Q.no + Q.nc)) || S.mem.alloc(Q.tails, 12 * std::max<size_t>(1, tail), true)) return -1;
+        for (auto &p : Q.scr)
+            if (S.mem.alloc(p, len, true)) return -1;
+        Q.stress_ready = true;
+    }
+    double *const *sig = S.sig[S.cur];
+    for (int fam = 0; fam < 12; fam += 4)
+        for (int q = fam; q < fam + 2; ++q) {
+            evp_launch_fold_stage2(sig[q], sig[q ^ 2], Q.scr[0], Q.scr[1], S.cgx.send_src, S.cgx.n_send, S.stream);
+            if (int rc = cgrid_fold_exchange(Q.scr[0], Q.scr[1], len)) return rc;
+            if (tail) {
+                HIPC(hipMemcpyAsync(Q.tails + (size_t)q * tail, Q.scr[0] + S.n, tail * sizeof(double), hipMemcpyDeviceToDevice, S.stream));
+                HIPC(hipMemcpyAsync(Q.tails + (size_t)(q ^ 2) * tail, Q.scr[1] + S.n, tail * sizeof(double), hipMemcpyDeviceToDevice, S.stream));
+            }
+        }
+    EvpStressTfold T{};
+    for (int k = 0; k < 12; ++k) T.sig[k] = sig[k];
+    T.tails = Q.tails; T.ncell = (int)S.n; T.ntail = (int)tail;
+    T.dst = Q.s_dst; T.src = Q.s_src; T.odst = Q.o_dst; T.osrc = Q.o_src; T.cdst = Q.c_dst; T.csrc = Q.c_src;
+    T.n = Q.ns; T.no = Q.no; T.nc = Q.nc;
+    T.tmp = Q.s_tmp;
+    evp_launch_stress_tfold_split(T, S.stream);
+    HIPC(hipGetLastError());
     return 0;
 }
 

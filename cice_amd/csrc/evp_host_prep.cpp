@@ -52,14 +52,18 @@ int cice_evp_hip_set_prep_geometry(const int32_t *tmask, const int32_t *umask, c
     // fields) -- except across the tripole fold, where centre fields mirror other cells than corner fields do
     // (tripoleT: the centre rule rewrites the top physical row -- a fold step of its own after the plain ghost copies, one rank)
     // (ranks cut in y only are fine: what travels between them are plain ghost rows, the fold step stays on the top rank)
-    if (S.plan.tfold && S.plan.center_tf_remote)
+    // Where the rows next to the fold have several owners (cg_split) the T-grid fields go through the C grid's fold exchange
+    // and the centre fold step of its lists instead (cice_evp_hip_prep); what stays refused is an eliminated block in the
+    // fold's neighbourhood on a layout without that exchange
+    if (S.plan.tfold && S.plan.center_tf_remote && !S.plan.cg_split)
         return fail(-9, "device preparation on a tripoleT grid: the top row's mirror cells live on other ranks (or in an eliminated "
                         "block) here; keep evp()'s host preparation (cice_evp_hip_run)");
     auto B = [&](uint8_t *&p) -> int { return p ? 0 : S.mem.alloc(p, S.n); };
     if (B(Q.tmask) || B(Q.umask) || B(Q.umask_old) || B(Q.tmphm)) return -1;
     if (!Q.umask_old32 && S.mem.alloc(Q.umask_old32, S.n)) return -1;
-    // (with the staging tail of a split tripole seam row: these arrays go through the velocity exchange too)
-    auto D = [&](double *&p) -> int { return p ? 0 : S.mem.alloc(p, S.nuv, true); };
+    // (with the staging tail of a split tripole seam row: these arrays go through the velocity exchange too -- or, tripoleT,
+    // through the C grid's fold exchange with its own staging slots: the longer of the two tails)
+    auto D = [&](double *&p) -> int { return p ? 0 : S.mem.alloc(p, prep_len(), true); };
     if (D(Q.hm) || D(Q.tarea) || D(Q.uarea) || D(Q.fcor) || D(Q.tmass) || D(Q.umass) || D(Q.maskd) ||
         D(Q.ss_tltxU) || D(Q.ss_tltyU) || D(Q.strairxU) || D(Q.strairyU) || D(Q.strtltx) || D(Q.strtlty)) return -1;
     for (auto &q : Q.t)
@@ -200,7 +204,20 @@ int cice_evp_hip_prep(const cice_evp_hip_prep_params *pp, const double *const *t
         evp_launch_halo_center(H, S.stream);
     };
     halo();
-    if (S.plan.tfold && Q.n_tf) {
+    const bool fold_x = S.plan.tfold && S.plan.cg_split;
+    if (fold_x) {
+        // tripoleT, the rows next to the fold on several ranks: the C grid's exchange carries, pair by pair, the ghost cells of
+        // rows below NY that other ranks own and the raw fold sources into the staging slots behind the arrays; then its fold
+        // step of location 0 (rows NY and NY+1, ghost columns included) on all of them in one pass.  Collective: ranks without
+        // fold rows take part with empty fold lists.
+        double *pairs[5][2] = {{Q.maskd, Q.tmass}, {Q.t[3], Q.t[4]}, {Q.t[5], Q.t[6]}, {Q.t[7], Q.t[8]}, {Q.t[9], Q.t[10]}};
+        for (int q = 0; q < nh / 2; ++q)
+            if (int rc = cgrid_fold_exchange(pairs[q][0], pairs[q][1], prep_len())) return rc;
+        double *x[10];
+        bool vec[10];
+        for (int k = 0; k < nh; ++k) { x[k] = arrs[k].first; vec[k] = arrs[k].second; }
+        if (int rc = fold_center_batch(x, vec, nh, prep_len())) return rc;
+    } else if (S.plan.tfold && Q.n_tf) {
         // tripoleT: rows NY (on the fold: symmetrised, rewritten from its mirror) and NY+1 of the same ten fields, after the
         // plain ghost copies (whose sources are rows the fold step does not write); the two-pass fold launch of the C grid
         // (evp_cgrid.hip: cg_fold_reg / cg_fold_one), four fields at a time
@@ -218,7 +235,7 @@ int cice_evp_hip_prep(const cice_evp_hip_prep_params *pp, const double *const *t
             evp_launch_cgrid_fold(F, S.stream);
         }
     }
-    if (S.plan.center_remote) {
+    if (S.plan.center_remote && !fold_x) {
         // neighbours on other ranks (no tripole fold here: centre and corner fields mirror the same
         // cells, so the velocity exchange carries pairs of T-grid fields)
         double *pairs[5][2] = {{Q.maskd, Q.tmass}, {Q.t[3], Q.t[4]}, {Q.t[5], Q.t[6]}, {Q.t[7], Q.t[8]}, {Q.t[9], Q.t[10]}};
@@ -267,6 +284,8 @@ int cice_evp_hip_prep(const cice_evp_hip_prep_params *pp, const double *const *t
     HIPC(hipMemcpyAsync(S.hmask.data(), S.mask, S.n, hipMemcpyDeviceToHost, S.stream));
     HIPC(hipMemcpyAsync(&flagword, Q.flagword, sizeof(unsigned), hipMemcpyDeviceToHost, S.stream));
     HIPC(hipStreamSynchronize(S.stream));
+    if (fold_x)                                 // a fold exchange whose wait gave up: nothing goes back to the caller
+        if (int rc = direct_check_error()) return rc;
     float ms = 0;
     HIPC(hipEventElapsedTime(&ms, S.ev2, S.ev3));
     S.t_h2d_ms = ms;

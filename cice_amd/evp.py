@@ -58,7 +58,7 @@ TEST_EXPORTS = [
     "cice_evp_hip_debug_device_allocs", "cice_evp_hip_debug_cuload", "cice_evp_hip_debug_prof", "cice_evp_hip_debug_cgrid_prof", "cice_evp_hip_debug_cgres_prof", "cice_evp_hip_plan_build", "cice_evp_hip_halo_plan", "cice_evp_hip_seam_plan",
     "cice_evp_hip_peer_plan", "cice_evp_hip_peer_signs", "cice_evp_hip_center_plan", "cice_evp_hip_stress_plan",
     "cice_evp_hip_fold_split_plan", "cice_evp_hip_plan_flags", "cice_evp_hip_fold_images_plan", "cice_evp_hip_cgrid_fold_xplan",
-    "cice_evp_hip_cgrid_fold_xpeers", "cice_evp_hip_plan_dump", "cice_evp_hip_rim_plan", "cice_evp_hip_debug_range_math",
+    "cice_evp_hip_cgrid_fold_xpeers", "cice_evp_hip_stress_tfold_xplan", "cice_evp_hip_plan_dump", "cice_evp_hip_rim_plan", "cice_evp_hip_debug_range_math",
     "cice_evp_hip_debug_res2_choose", "cice_evp_hip_debug_res2_built",
 ]
 # environment switches only the test build reads (cice_amd/csrc/evp_host.h: env_test): experiments, fault injection, routing
@@ -261,6 +261,27 @@ def cgrid_fold_xplan(dims: "Dims") -> dict:
     return dict(split=bool(info[0]), tail=int(info[1]), fold=out, peer_rank=p5[:npeer, 0].copy(), peer_nsend=p5[:npeer, 1].copy(),
                 peer_nrecv=p5[:npeer, 2].copy(), peer_nghost_send=p5[:npeer, 3].copy(), peer_nghost_recv=p5[:npeer, 4].copy(),
                 send_src=ss[:ns], send_dst=sd[:ns], recv_dst=rd[:nr], recv_gid=rg[:nr])
+
+
+def stress_tfold_xplan(dims: "Dims") -> dict:
+    """Host only: the tripoleT stress symmetrisation of `dims.rank` on any rank layout (see the testing header): the three
+    lists, sources >= n_local being staging slots of the C-grid exchange (cgrid_fold_xplan).  ok=False: declined, `why`
+    says why (no lists)."""
+    lib = load_library(testing=True)
+    _check(lib, lib.cice_evp_hip_plan_build(C.byref(dims)), "(plan_build)")
+    info = np.zeros(4, dtype=np.int32)
+    rc = lib.cice_evp_hip_stress_tfold_xplan(_ip(info), None, None, None, None, None, None)
+    if rc == 1:
+        buf = C.create_string_buffer(1024)
+        lib.cice_evp_hip_last_error(buf, 1024)
+        return dict(ok=False, why=buf.value.decode(errors="replace"), collective=bool(info[3]))
+    _check(lib, rc, "(stress_tfold_xplan)")
+    names = ("dst", "src", "own_dst", "own_src", "corner_dst", "corner_src")
+    L = {k: np.zeros(max(int(info[i // 2]), 1), dtype=np.int32) for i, k in enumerate(names)}
+    _check(lib, lib.cice_evp_hip_stress_tfold_xplan(None, *[_ip(L[k]) for k in names]), "(stress_tfold_xplan)")
+    out = {k: L[k][:int(info[i // 2])] for i, k in enumerate(names)}
+    out.update(ok=True, why="", collective=bool(info[3]))
+    return out
 
 
 def cgrid_window_plan(dims: "Dims", ox: int, oy: int, extra: int = 0) -> dict:

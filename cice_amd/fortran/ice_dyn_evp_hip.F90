@@ -500,7 +500,7 @@ contains
     case ('open');    bnd_code = 1
     case ('cyclic');  bnd_code = 2
     case ('tripole'); bnd_code = 3
-    case ('tripoleT'); bnd_code = 4          ! T-fold: the loop on any rank layout; preparation / symmetrisation with the top row on one rank
+    case ('tripoleT'); bnd_code = 4          ! T-fold: loop, preparation and symmetrisation on any rank layout (not next to an eliminated block)
     case default
        bnd_code = -1
        call abort_ice('(dyn_evp_hip_init) ERROR: unsupported boundary type '//trim(bnd), &
@@ -513,8 +513,9 @@ contains
 ! loop -- preparation phase (ice_dyn_evp.F90:383-840), loop (:859-913) and, on a tripole grid, the
 ! stress symmetrisation (:1321-1389) -- on the device.  The caller supplies the ice strength
 ! through a callback that runs between the two device phases, because icepack_ice_strength
-! needs the iceTmask the preparation produces (:541-552).  Ranks whose T-grid halo needs another
-! rank keep evp()'s host preparation (the C side refuses them).
+! needs the iceTmask the preparation produces (:541-552).  T-grid ghost cells that other ranks own
+! travel through the library's transports, across a tripole fold cut in x too; what the C side
+! still refuses is a fold neighbourhood with an eliminated block that no exchange covers.
   subroutine dyn_evp_hip_evp_body(dt, compute_strength)
 
     use ice_blocks, only: nx_block, ny_block, block, get_block
@@ -553,8 +554,9 @@ contains
        call compute_strength()      ! (whatever the host does there among the tasks happens on this one too)
        return
     endif
-    ! (tripoleT: the library takes the preparation and the symmetrisation where the top row lies on one rank and says
-    ! so otherwise -- cice_evp_hip_set_prep_geometry / cice_evp_hip_stress_halo return an error that check() reports)
+    ! (tripoleT: the library takes the preparation and the symmetrisation on every rank layout but one with an eliminated
+    ! block among the cells the top row mirrors, and says so there -- cice_evp_hip_set_prep_geometry /
+    ! cice_evp_hip_stress_halo return an error that check() reports)
     nall = nx_block*ny_block*max_blocks
     if (.not. geometry_set) then
        ! logical(log_kind) is a 4-byte logical: the C side tests "non-zero"
@@ -1117,7 +1119,8 @@ contains
 ! dyn_evp_hip_keep_stresses_resident both come here).  Resident stresses on a tripole / tripoleT grid need the device to
 ! do what evp()'s twelve ice_HaloUpdate_stress calls do on the host arrays (ice_dyn_evp.F90:1321-1389), and every rank
 ! must reach the same verdict: tripole -- always possible; tripoleT -- only where cice_evp_hip_stress_halo_available()
-! says so on EVERY rank (MIN over the ranks: one rank with its top row split falls back, so all do, and
+! says so on EVERY rank (it does with the top row split over ranks; MIN over the ranks: one rank whose top row mirrors
+! an eliminated block falls back, so all do, and
 ! dyn_evp_hip_fetch_stresses / restart behaviour never depends on the rank).  explicit = the host asked for it after
 ! initialisation: a request that cannot be honoured aborts instead of silently leaving the device copy unsymmetrised.
   subroutine settle_stress_residency(want, explicit)

@@ -44,9 +44,11 @@ enum {
                                * _download), any rank layout (the streaming kernel; the images of the top row are interior
                                * cells, so the exchange always follows the launch); cice_evp_hip_stress_halo and the
                                * preparation phase (cice_evp_hip_prep: the centre rule of the T-fold rewrites the top physical
-                               * row, ice_boundary.F90:1563-1583) with the top row on one rank; the C grid (cice_evp_hip_cgrid_*:
-                               * five launches + fold steps from the T-fold lists of the four field locations, device
-                               * preparation included) with the rows NY-2 .. NY on one rank */
+                               * row, ice_boundary.F90:1563-1583) on any rank layout too -- where the rows next to the fold have
+                               * several owners, through the C grid's fold exchange; the C grid (cice_evp_hip_cgrid_*: five
+                               * launches + fold steps from the T-fold lists of the four field locations, device preparation
+                               * included) likewise.  Still refused (-9): preparation and symmetrisation next to an eliminated
+                               * land block that no exchange covers */
 };
 
 /* Block decomposition of this process (type(block), ice_blocks.F90:21-41;
@@ -183,13 +185,15 @@ int cice_evp_hip_sync(void);
  * PHYSICAL row of components 1 and 2 from the partner's mirrored cell, leave 3 and 4 with plain images in
  * the east-west ghost cells of that row, and touch one cell of the ghost row: the north-west corner ghost
  * cell of every top-row block (pinned on the reference's own output).
+ * Where the top row has several owners (either fold) the call is collective: the partners' values travel through the
+ * library's transport -- on tripoleT each pair of components through the C grid's fold exchange.
  * Call between cice_evp_hip_subcycle and cice_evp_hip_download; no-op on other grids.            */
 int cice_evp_hip_stress_halo(void);
-/* 1 if cice_evp_hip_stress_halo can do that on this rank layout (tripole: always; tripoleT: the top row on one rank and no
- * eliminated block in it), else 0: a host that keeps the stresses resident asks before it leaves the step to the library.
- * The answer is THIS rank's (a rank without top-row blocks says 1 whatever the others say); that is sound rank by rank because
- * the tripoleT symmetrisation on the device never crosses ranks -- a host whose restart / diagnostics code wants one answer
- * for the whole job reduces it itself (MIN).                                                                              */
+/* 1 if cice_evp_hip_stress_halo can do that on this rank layout (tripole: always; tripoleT: no eliminated block among the
+ * cells the top row mirrors), else 0: a host that keeps the stresses resident asks before it leaves the step to the library.
+ * With the tripoleT top row on several ranks the answer is 1 on every rank or on none.  Next to an eliminated block it is
+ * THIS rank's (0 where its own lists name a cell nobody holds, 1 elsewhere): a host reduces it over the ranks itself (MIN)
+ * and leaves the step to the library only where every rank said 1.                                                        */
 int cice_evp_hip_stress_halo_available(void);
 int cice_evp_hip_set_post_geometry(const double *dxU, const double *dyU, const double *tarear);
 int cice_evp_hip_deformations(double *divu, double *shear, double *vort, double *rdg_conv,
@@ -215,8 +219,10 @@ int cice_evp_hip_dyn_finish(double *strocnxU, double *strocnyU);
  * iceUmask: in = mask of the previous call (new ice starts at the ocean velocity), out = new mask;
  * strintxU/strintyU/strocnxU/strocnyU (may be NULL): zeroed off the ice on the host arrays.
  * On a split domain the T-grid halos use the same transport as the velocities (collective call);
- * on a tripole domain too, whatever the rank layout (a fold row split over ranks in x: through the
- * exchange of a shifted copy, cice_amd/csrc/halo_plan.h).
+ * on a tripole domain too, whatever the rank layout (a u-fold row split over ranks in x: through the
+ * exchange of a shifted copy, cice_amd/csrc/halo_plan.h; tripoleT with the rows next to the fold on several
+ * ranks: through the C grid's fold exchange and its centre fold step, cice_amd/csrc/evp_fold_prep.hip).
+ * Refused (-9): a tripoleT fold neighbourhood with an eliminated land block on a layout without that exchange.
  * Forcing layout (both grids; cice_evp_hip_set_forcing_layout, below): by default the ocean fields and the wind stress
  * are on the T grid (calc_strair = .true., grid_ocn = 'A').  Otherwise slots 5-8 hold uocn, vocn, ss_tltx, ss_tlty at the
  * grid_ocn points (halo-updated as cell-centre vectors, as the reference does whatever grid they live on), and with
@@ -312,7 +318,9 @@ int cice_evp_hip_cgrid_run(int32_t ndte, int32_t visc_method, double *const *fie
  *   cice_evp_hip_cgrid_prep_finish(strength, visc_method) -> cice_evp_hip_cgrid_subcycle -> cice_evp_hip_cgrid_download
  *   cice_evp_hip_cgrid_fetch(table, index, dst): table 0 = fields19, 1 = inputs23 as they are on the device (dyn_finish at
  *     E / N points reads aiX, fmX, uocnX, vocnX on the host).
- * A tripole fold row split over ranks in x is refused (centre-field mirror across the fold on another rank).          */
+ * Any rank layout the loop accepts: where the blocks next to a tripole fold have several owners the T-grid fields and the
+ * velocities travel through the fold exchange of the loop (collective; ranks without fold rows take part with empty fold
+ * lists).  Refused (-9): a fold neighbourhood with an eliminated land block on a layout without that exchange.         */
 int cice_evp_hip_cgrid_set_prep_geometry(const int32_t *tmask, const int32_t *umaskCD, const int32_t *emask,
                                          const int32_t *nmask, const double *fcor_blk, const double *fcorE_blk,
                                          const double *fcorN_blk);
@@ -451,7 +459,8 @@ int cice_evp_hip_stream_probe(int64_t ncells, double *bytes_per_second);
  * counts2 = {entries, staging slots}.  After the velocity exchange x[dst] = coef * 0.5*(x[a] - x[b]) (b >= 0) or
  * coef * x[a] (b = -1), a / b = local cells or staging slots n_local + t filled by the exchange with RAW seam values
  * of other ranks (they are the last entries of the peers' send / recv lists).  Returns 1 (not an error) when the
- * stress symmetrisation would need another rank (then cice_evp_hip_stress_halo refuses).  Lists may be NULL.   */
+ * stress symmetrisation would need another rank or an eliminated block's cells (tripoleT: cice_evp_hip_stress_halo then
+ * goes through the C grid's fold exchange, or refuses next to an eliminated block).  Lists may be NULL.          */
 int cice_evp_hip_seam_fin_plan(int32_t *counts2, int32_t *dst, int32_t *a, int32_t *b, int32_t *coef);
 /* (The plan introspection entry points of the CPU tests, the phase / placement read-outs of the tools and the test
  * transport are NOT part of this library: they are declared in cice_evp_hip_testing.h and exist only in the test build,

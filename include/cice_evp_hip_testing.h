@@ -223,6 +223,15 @@ int cice_evp_hip_cgrid_fold_xplan(int32_t loc, int32_t *info4, int32_t *count, i
  * cell or staging slot each sent entry fills at the peer; recv_gid: the global cell number (ig-1) + NX*(jg-1) each received
  * entry carries. */
 int cice_evp_hip_cgrid_fold_xpeers(int32_t *peer5, int32_t *send_src, int32_t *send_dst, int32_t *recv_dst, int32_t *recv_gid);
+/* tripoleT, the stress symmetrisation of the plan of cice_evp_hip_plan_build on ANY rank layout (cice_amd/csrc/fold_prep_plan.h):
+ * (dst, src) row NY of _1 / _2 from the partner array, (own_dst, own_src) east-west ghost cells of row NY of _3 / _4 from
+ * their own array, (corner_dst, corner_src) the north-west corner ghost cell of a top-row block from the partner's row NY-1.
+ * A source >= nx_block * ny_block * nblocks is a staging slot of the C-grid exchange above (the one the centre fold step's
+ * entries use for that cell).  info4 = {entries of the three lists, 1 if some rank needs a cell of another rank (the same
+ * on every rank: the exchange is then collective)}; lists may be NULL.  Returns 1 where it declines (not tripoleT, an
+ * eliminated block among the cells read, a cell the exchange does not carry): cice_evp_hip_last_error says why.          */
+int cice_evp_hip_stress_tfold_xplan(int32_t *info4, int32_t *dst, int32_t *src, int32_t *own_dst, int32_t *own_src,
+                                    int32_t *corner_dst, int32_t *corner_src);
 /* Read-outs of the forcing-layout tests (no entry of their own): cice_evp_hip_prep_fetch serves which = 21, 22 = ss_tltxU,
  * ss_tltyU; cice_evp_hip_cgrid_fetch serves table 2, index 0..3 = strairxE, strairyN, ss_tltxE, ss_tltyN as the last
  * cice_evp_hip_cgrid_prep under a forcing layout other than the default averaged them (every cell).                    */

@@ -64,6 +64,15 @@ def main():
                     help="with --forcing and calc_strair 0: strax / stray ghost cells as an exchange would fill them, or "
                          "(own) different on the split run -- the averages must read them as given: compared with the numpy "
                          "restatement on this rank's inputs, and the wind-dependent arrays are not compared with the one-rank run")
+    ap.add_argument("--stress-halo", action="store_true",
+                    help="B grid: after the loop call stress_halo() on tripole AND tripoleT grids (evp()'s 12 x ice_HaloUpdate_stress "
+                         "on the resident stresses; without it only the u-fold form runs)")
+    ap.add_argument("--same-blocks-ref", action="store_true",
+                    help="B grid: the reference run is ONE rank owning the same blocks as the split run, not one big block: every "
+                         "block array of the 12 stresses is then compared whole, ghost ring included, bit for bit")
+    ap.add_argument("--report-prep", action="store_true",
+                    help="with --prep: run the preparation three times on the same inputs and print every rank's device time of "
+                         "the quickest of the last two (the first call also builds its lists), ms")
     a = ap.parse_args()
     import torch
     import torch.distributed as dist
@@ -186,6 +195,12 @@ def main():
                     pm = {"T": static["hm"], "U": static["uvm"], "E": static["epm"], "N": static["npm"]}
                     wind_check = apply_forcing(core, dc, r, exchange, tb, area, pm)
                 newm = core.cgrid_prep(pp, tb, state, prevb)
+                if a.report_prep:
+                    ms = []
+                    for _ in range(2):
+                        newm = core.cgrid_prep(pp, tb, state, prevb)
+                        ms.append(core.cgrid_timings()["prep_ms"])
+                    print(f"PREP_MS cgrid {a.workload} {'split ' + a.shape if exchange else 'one rank'} rank {r}: {min(ms):.4f}", flush=True)
                 wind_bad = wind_check(core.cgrid_fetch, ("strairxE", "strairyN")) if wind_check else []
                 if exchange and a.maskhalo:
                     pass                  # (the mask above was built from the synthetic loop masks: not used together with --prep)
@@ -373,6 +388,12 @@ def main():
                     pm = {"T": static["hm"]}
                     wind_check = apply_forcing(core, dc, r, exchange, tf, area, pm)
                 tmk, umk, _ = core.prep(pp, tf, {k: sc(v) for k, v in pr["state"].items()})
+                if a.report_prep:
+                    ms = []
+                    for _ in range(2):
+                        tmk, umk, _ = core.prep(pp, tf, {k: sc(v) for k, v in pr["state"].items()})
+                        ms.append(core.timings()["prep_ms"])
+                    print(f"PREP_MS bgrid {a.workload} {'split ' + a.shape if exchange else 'one rank'} rank {r}: {min(ms):.4f}", flush=True)
                 core.set_strength(fields["strength"])
                 extra = {k: core.prep_fetch(k) for k in ("forcexU", "umassdti", "uvel_init", "aiU") + (
                     ("uocnU", "vocnU", "strairxU", "strairyU") if a.forcing else ())}
@@ -395,7 +416,7 @@ def main():
                 core.subcycle(7)          # an odd count: the record-buffer parity flips between launches
             for _ in range(a.soak):
                 core.subcycle(120)
-            if ns_bnd == "tripole" and not a.timing:
+            if (ns_bnd == "tripole" and not a.timing) or (a.stress_halo and ns_bnd in ("tripole", "tripoleT")):
                 core.stress_halo()          # evp()'s 12 x ice_HaloUpdate_stress on the resident stresses (any rank layout)
             out = core.download()
             out.update(extra)
@@ -406,20 +427,37 @@ def main():
 
     # The single-rank reference run assumes it has the GPU to itself (its resident kernel needs all its
     # tiles co-resident; a tx1-sized domain fills the chip): the processes take turns.
-    ref = None
-    for turn in range(world):
-        if turn == rank:
-            ref, _, _ = run(decomp.single_block(nx, ny, "cyclic", ns_bnd), 0, False)
-        dist.barrier()
     shape = tuple(int(v) for v in a.shape.split("x")) if a.shape else None
     dcN = decomp.per_rank_blocks(nx, ny, world, "cyclic", ns_bnd, proc_shape=shape)
     if a.blocks_per_rank:
         sx, sy = (int(v) for v in a.blocks_per_rank.split("x"))
         dcN = decomp.Decomp(nx, ny, -(-dcN.block_size_x // sx), -(-dcN.block_size_y // sy), "cyclic", ns_bnd, world,
                             dcN.proc_shape)
+    # (--same-blocks-ref: the split run's blocks, all on one rank -- same block grid, same block ids)
+    dc1 = (decomp.Decomp(nx, ny, dcN.block_size_x, dcN.block_size_y, "cyclic", ns_bnd, 1) if a.same_blocks_ref
+           else decomp.single_block(nx, ny, "cyclic", ns_bnd))
+    ref = None
+    for turn in range(world):
+        if turn == rank:
+            ref, _, _ = run(dc1, 0, False)
+        dist.barrier()
+    ref_global = {}
+
+    def refg(k):            # the reference run's field on the global grid (interior cells of its blocks)
+        if k not in ref_global:
+            ref_global[k] = dc1.gather({0: ref[k]})
+        return ref_global[k]
     got, tim, t_us = run(dcN, rank, True)
     assert tim["halo_transport"] == "mailbox", tim
     bad = list(got.get("_wind_bad", []))
+    if a.same_blocks_ref:
+        # the 12 stresses, every block array whole: what the loop and the symmetrisation leave in the ghost ring included
+        ref_local = {b.gid: b.local for b in dc1.blocks}
+        for k in evp.FIELDS[:12]:
+            for b in dcN.local_blocks(rank):
+                w, h = ref[k][ref_local[b.gid]], got[k][b.local]
+                if not np.array_equal(w.view(np.uint64), h.view(np.uint64)):
+                    bad.append((k + " whole block", b.gid, int((w.view(np.uint64) != h.view(np.uint64)).sum())))
     if a.march:
         mi = got["_march"]
         if not (mi["mode"] == 1 and mi["last_call"] and mi["declined"] == 0 and mi["passes"] > 0):
@@ -433,7 +471,7 @@ def main():
               "forcexU", "umassdti", "uvel_init", "aiU", "iceTmask", "uocnU", "vocnU", "strairxU", "strairyU"):
         if k not in got or k in wind_dep:
             continue
-        want = dcN.scatter(ref[k][0][1:-1, 1:-1], rank)
+        want = dcN.scatter(refg(k), rank)
         for b in dcN.local_blocks(rank):
             w = want[b.local][1:1 + b.gny, 1:1 + b.gnx]
             h = got[k][b.local][1:1 + b.gny, 1:1 + b.gnx]
@@ -443,7 +481,7 @@ def main():
             # the ghost row beyond the fold after the symmetrisation: the partner array's top row, mirrored (centre rule)
             fam, q = k.rsplit("_", 1)
             partner = f"{fam}_{((int(q) - 1) ^ 2) + 1}"
-            wantp = dcN.scatter(ref[partner][0][1:-1, 1:-1], rank, fold=("center", 1.0))
+            wantp = dcN.scatter(refg(partner), rank, fold=("center", 1.0))
             for b in dcN.local_blocks(rank):
                 if b.gj0 + b.gny - 1 != ny:
                     continue
