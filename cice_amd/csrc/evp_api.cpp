@@ -445,6 +445,45 @@ int cice_evp_hip_set_metrics(const double *cxp, const double *cyp, const double 
     for (int k = 0; k < 7; ++k)
         if (src[k] && h2d(S.stat[2 + k], src[k])) return -1;
     HIPC(hipStreamSynchronize(S.stream));
+    if (!(S.flags & EVP_F_METRICS)) return 0;      // the kernels read the arrays already
+    // The kernels derive the terms from HTE, HTN, dxT, dyT (evp_cell.inc: metrics_cell) and would never look at what was
+    // just uploaded: an array that is not that term, bit for bit, on a T-cell a kernel may evaluate (every block's
+    // ilo .. ihi+1 x jlo .. jhi+1) takes the shortcut away -- dxhy / dyhx alone keep the other five derived.
+    std::vector<double> hte(S.n), htn(S.n), dxT(S.n), dyT(S.n);
+    const size_t bytes = S.n * sizeof(double);
+    HIPC(hipMemcpy(hte.data(), S.hte, bytes, hipMemcpyDeviceToHost));
+    HIPC(hipMemcpy(htn.data(), S.htn, bytes, hipMemcpyDeviceToHost));
+    HIPC(hipMemcpy(dxT.data(), S.stat[0], bytes, hipMemcpyDeviceToHost));
+    HIPC(hipMemcpy(dyT.data(), S.stat[1], bytes, hipMemcpyDeviceToHost));
+    const int nx = S.d.nx_block;
+    const double p5 = 0.5, c1p5 = 1.5, dmin = S.prm.deltaminEVP;
+    bool differs[7] = {};
+    for (int k = 0; k < 7; ++k) {
+        if (!src[k]) continue;
+        for (int b = 0; b < S.d.nblocks && !differs[k]; ++b)
+            for (int j = S.jlo[b]; j <= S.jhi[b] + 1 && !differs[k]; ++j)
+                for (int i = S.ilo[b]; i <= S.ihi[b] + 1; ++i) {
+                    // (column ihi+1 / row jhi+1 of a block at a boundary that is not cyclic lies outside the domain: no ice there,
+                    // and the host model's halo update leaves another value there than the local difference)
+                    const int ig = S.iglob0[b] + (i - S.ilo[b]), jg = S.jglob0[b] + (j - S.jlo[b]);
+                    if ((ig > S.d.nx_global && S.d.ew_boundary_type != CICE_EVP_BND_CYCLIC) ||
+                        (jg > S.d.ny_global && S.d.ns_boundary_type != CICE_EVP_BND_CYCLIC)) continue;
+                    const size_t c = (size_t)b * S.plane + (size_t)(j - 1) * nx + (i - 1);
+                    double e;
+                    switch (k) {
+                    case 0: e = p5 * (hte[c] - hte[c - 1]); break;
+                    case 1: e = p5 * (htn[c] - htn[c - nx]); break;
+                    case 2: e = (c1p5 * htn[c] - p5 * htn[c - nx]); break;
+                    case 3: e = (c1p5 * hte[c] - p5 * hte[c - 1]); break;
+                    case 4: e = -(c1p5 * htn[c - nx] - p5 * htn[c]); break;
+                    case 5: e = -(c1p5 * hte[c - 1] - p5 * hte[c]); break;
+                    default: { const double tarea = dxT[c] * dyT[c]; e = dmin * tarea; }
+                    }
+                    if (std::memcmp(&e, &src[k][c], 8) != 0) { differs[k] = true; break; }
+                }
+    }
+    if (differs[2] || differs[3] || differs[4] || differs[5] || differs[6]) S.flags &= ~EVP_F_METRICS;
+    else if (differs[0] || differs[1]) S.flags |= EVP_F_DXHY_ARRAY;
     return 0;
 }
 
@@ -500,15 +539,21 @@ static int upload_impl(const double *const *f, const int32_t *iceTmask, const in
     bool water_is_ocn = true, tbu_zero = true;
     {
         const double *wx = f[F_WATERX], *wy = f[F_WATERY], *uo = f[F_UOCN], *vo = f[F_VOCN], *tb = f[F_TBU];
-        for (size_t k = 0; k < S.n; ++k) {
-            const bool um = iceUmask[k] != 0;
-            S.hmask[k] = (uint8_t)((iceTmask[k] != 0 ? 1 : 0) | (um ? 2 : 0));
-            if (um) {
-                // bit-for-bit identical operands (cosw=1, sinw=0: ice_dyn_shared.F90:69-70,819-820)
-                if (std::memcmp(&wx[k], &uo[k], 8) != 0 || std::memcmp(&wy[k], &vo[k], 8) != 0) water_is_ocn = false;
-                if (tb[k] != 0.0) tbu_zero = false;
-            }
-        }
+        const double plus0 = 0.0;
+        for (size_t k = 0; k < S.n; ++k) S.hmask[k] = (uint8_t)((iceTmask[k] != 0 ? 1 : 0) | (iceUmask[k] != 0 ? 2 : 0));
+        // (the U-cells a kernel advances: iceUmask on the physical cells of each block.  A caller may hold iceUmask on ghost cells
+        // too -- images of cells another block or rank advances, and judges)
+        const int nxb = S.d.nx_block;
+        for (int b = 0; b < S.d.nblocks; ++b)
+            for (int j = S.jlo[b]; j <= S.jhi[b]; ++j)
+                for (int i = S.ilo[b]; i <= S.ihi[b]; ++i) {
+                    const size_t k = (size_t)b * S.plane + (size_t)(j - 1) * nxb + (i - 1);
+                    if (!(S.hmask[k] & 2u)) continue;
+                    // bit-for-bit identical operands (cosw=1, sinw=0: ice_dyn_shared.F90:69-70,819-820)
+                    if (std::memcmp(&wx[k], &uo[k], 8) != 0 || std::memcmp(&wy[k], &vo[k], 8) != 0) water_is_ocn = false;
+                    // (bits: TbU = -0.0 gives Cb = -0.0 and taubx = -uvel*Cb the other sign of zero, :939, 964-965)
+                    if (std::memcmp(&tb[k], &plus0, 8) != 0) tbu_zero = false;
+                }
         CopyBatch B2;
         if (!(water_is_ocn && (S.flags_allowed & EVP_F_WATER_IS_OCN))) {
             B2.items.push_back({S.in[F_WATERX], wx});

@@ -308,6 +308,7 @@ struct State {
     uint8_t *res2_perm_rim = nullptr, *res2_uperm = nullptr, *res2_nact_rim = nullptr;
     bool res2_rimu_ok = false;
     int res2_rimu = 0;
+    int res2_lean = 0;             // the last launch took a lean variant (read-out: cice_evp_hip_debug_call_flags)
     std::vector<uint8_t> res2_pubimg_h;                   // per cell: its record is polled by another tile or it has a ghost image
     int *res2_cuload = nullptr;                           // per-CU record of a launch (EvpResident2::cuload)
     unsigned long long *res2_prof = nullptr;              // phase stamps (CICE_EVP_HIP_RES_PROF=1)

@@ -1421,6 +1421,7 @@ int cice_evp_hip_cgrid_upload(const double *const *state14, const double *const 
 }  // extern "C"
 
 namespace evp_host {
+static unsigned g_last_call_flags = ~0u;        // the flag word of the last finish_upload as cg_call_setup left it (test build's read-out)
 // what follows the arrival of the loop's inputs, however they arrived (cice_evp_hip_cgrid_upload: from the host;
 // cice_evp_hip_cgrid_prep: computed here)
 int finish_upload(int32_t visc_method)
@@ -1466,6 +1467,7 @@ int finish_upload(int32_t visc_method)
     HIPC(hipGetLastError());
     HIPC(hipStreamSynchronize(S.stream));       // the caller may change its arrays after this returns
     CG.fast = (h_flags & 255u) == 0 && fast_switch();
+    g_last_call_flags = h_flags;
     CG.res.pairs_state_ok = (h_flags & 256u) == 0;
     if (CG.res.tab) {
         CGridState::Res &Q = CG.res;
@@ -1954,6 +1956,17 @@ int cice_evp_hip_debug_cgrid_prof(uint64_t *out, int32_t ntiles_max)
     HIPC(hipStreamSynchronize(S.stream));
     HIPC(hipMemcpy(out, CG.one.prof, (size_t)CG.one.ntiles * 8 * sizeof(uint64_t), hipMemcpyDeviceToHost));
     return CG.one.ntiles;
+}
+
+// The shortcut verdicts of the call about to run, see the testing header: B-grid word, C-grid word, CG.fast
+int cice_evp_hip_debug_call_flags(uint32_t *out, int32_t n)
+{
+    if (!S.ready) return fail(-1, "not initialised");
+    const uint32_t v[4] = {S.flags & S.flags_allowed, CG.uploaded ? g_last_call_flags : 0u, (CG.uploaded && CG.fast) ? 1u : 0u,
+                           (S.res_ran && S.res2_lean) ? 1u : 0u};
+    int32_t k = 0;
+    for (; out && k < n && k < 4; ++k) out[k] = v[k];
+    return k;
 }
 #endif
 

@@ -692,6 +692,14 @@ int march_run(int ndte)
         return 0;
     };
     if (!M.stat_ok) return fallback("ghost values of the static grid fields are not images of one global field");
+    // Several ranks: the redundant rim holds other ranks' cells and the optional operands travel in an exchange of their own -- both
+    // only right where every rank formed the same verdicts on waterx / TbU, and those are per rank (evp_api.cpp: upload_impl).  Where
+    // they differ this call goes through the one-subcycle kernel, on every rank.
+    if (!L.plan.peers.empty() && S.d.nranks > 1) {
+        unsigned hi = S.flags & S.flags_allowed & (EVP_F_WATER_IS_OCN | EVP_F_TBU_ZERO), lo = hi;
+        if (agree(hi, ncclMax, true, true) || agree(lo, ncclMin, true, true)) return -1;
+        if (hi != lo) return fallback("the ranks' verdicts on waterx == uocn / TbU == 0 differ");
+    }
     // the passes of this call (march_plan.h: march_schedule); a single left-over subcycle goes first, through the one-subcycle
     // kernel in the block layout
     std::vector<MarchStep> steps = march_schedule(ndte, L.kpass, L.ring_valid, !L.plan.peers.empty(), L.fold.H > 0);

@@ -3,6 +3,15 @@
 
 using namespace evp_host;
 
+// TbU counts as absent only where it is +0.0, the value the kernels substitute: -0.0 gives Cb = -0.0 and taubx = -uvel*Cb the
+// other sign of zero (ice_dyn_shared.F90:939, 964-965)
+static inline bool plus_zero(double x)
+{
+    uint64_t b;
+    std::memcpy(&b, &x, 8);
+    return b == 0;
+}
+
 namespace evp_host {
 
 // the EvpForcing of a preparation kernel; area / pm: tarea uarea earea narea, hm uvm epm npm as this grid holds them.
@@ -158,7 +167,7 @@ int cice_evp_hip_prep(const cice_evp_hip_prep_params *pp, const double *const *t
     bool tbu_zero = true;
     if (fields32[F_TBU]) {
         B.items.push_back({S.in[F_TBU], fields32[F_TBU]});
-        for (size_t k = 0; k < S.n && tbu_zero; ++k) tbu_zero = fields32[F_TBU][k] == 0.0;
+        for (size_t k = 0; k < S.n && tbu_zero; ++k) tbu_zero = plus_zero(fields32[F_TBU][k]);
     } else {
         HIPC(hipMemsetAsync(S.in[F_TBU], 0, S.n * sizeof(double), S.stream));
     }
@@ -341,7 +350,13 @@ int cice_evp_hip_set_tbu(const double *TbU)
     if (!TbU) return fail(-1, "null argument");
     if (h2d(S.in[F_TBU], TbU)) return -1;
     bool zero = true;
-    for (size_t k = 0; k < S.n && zero; ++k) zero = !(S.hmask[k] & 2u) || TbU[k] == 0.0;
+    // (on the U-cells a kernel advances: the physical cells of each block, as the scan of cice_evp_hip_upload)
+    for (int b = 0; b < S.d.nblocks && zero; ++b)
+        for (int j = S.jlo[b]; j <= S.jhi[b] && zero; ++j)
+            for (int i = S.ilo[b]; i <= S.ihi[b] && zero; ++i) {
+                const size_t k = (size_t)b * S.plane + (size_t)(j - 1) * S.d.nx_block + (i - 1);
+                zero = !(S.hmask[k] & 2u) || plus_zero(TbU[k]);
+            }
     HIPC(hipStreamSynchronize(S.stream));      // the caller may reuse its array
     S.flags &= ~EVP_F_TBU_ZERO;
     if (zero) S.flags |= EVP_F_TBU_ZERO;

@@ -496,7 +496,7 @@ int launch_resident2(int ndte, int cur0, bool dry)
     R.uperm = c.rim_tables ? S.res2_uperm : nullptr;
     R.nact = c.rim_tables ? S.res2_nact_rim : S.res2_nact;
     R.nlate = c.v.coop ? S.res2_nlate : nullptr;
-    S.res2_coop = c.v.coop ? 1 : 0; S.res2_rimu = c.v.rimu ? 1 : 0;
+    S.res2_coop = c.v.coop ? 1 : 0; S.res2_rimu = c.v.rimu ? 1 : 0; S.res2_lean = c.v.lean ? 1 : 0;
     HIPC(evp_launch_resident2(A, R, S.max_ni, S.max_nj, c.v, S.stream));
     HIPC(hipGetLastError());
     return 0;

@@ -241,7 +241,7 @@ __global__ void seabed_lkd(EvpPrep P, const double *__restrict__ hwater, double 
         const double hu = fmax(fmax(fmax(vice[c], vice[c1]), vice[c2]), vice[c3]);
         const double hcu = au * hwu / k1;
         tb = docalc * k2 * fmax(0.0, (hu - hcu)) * exp(-alphab * (1.0 - au));
-        if (tb != 0.0) atomicOr(flagword, 2u);
+        if (__double_as_longlong(tb) != 0ll) atomicOr(flagword, 2u);      // (bits: -0.0 is not the +0.0 the kernels substitute)
     }
     TbU[c] = tb;
 }
@@ -318,7 +318,7 @@ __global__ void seabed_prob_U(EvpPrep P, const double *__restrict__ Tbt, double 
     double tb = 0.0;
     if (i >= r.x && i <= r.y && j >= r.z && j <= r.w && (P.mask[c] & 2u)) {
         tb = fmax(fmax(fmax(Tbt[c], Tbt[c + 1]), Tbt[c + P.nx]), Tbt[c + P.nx + 1]);
-        if (tb != 0.0) atomicOr(flagword, 2u);
+        if (__double_as_longlong(tb) != 0ll) atomicOr(flagword, 2u);
     }
     TbU[c] = tb;
 }

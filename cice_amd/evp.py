@@ -59,8 +59,11 @@ TEST_EXPORTS = [
     "cice_evp_hip_peer_plan", "cice_evp_hip_peer_signs", "cice_evp_hip_center_plan", "cice_evp_hip_stress_plan",
     "cice_evp_hip_fold_split_plan", "cice_evp_hip_plan_flags", "cice_evp_hip_fold_images_plan", "cice_evp_hip_cgrid_fold_xplan",
     "cice_evp_hip_cgrid_fold_xpeers", "cice_evp_hip_stress_tfold_xplan", "cice_evp_hip_plan_dump", "cice_evp_hip_rim_plan", "cice_evp_hip_debug_range_math",
-    "cice_evp_hip_debug_res2_choose", "cice_evp_hip_debug_res2_built",
+    "cice_evp_hip_debug_res2_choose", "cice_evp_hip_debug_res2_built", "cice_evp_hip_debug_call_flags",
 ]
+# the B grid's flag word (cice_amd/csrc/evp_device.h: EVP_F_*) and the C grid's (evp_cgrid.hip: cg_call_setup), as call_flags() reads them
+F_METRICS, F_WATER_IS_OCN, F_TBU_ZERO, F_DXHY_ARRAY = 1, 2, 4, 32
+CG_WATER_DIFFERS, CG_TB_NONZERO, CG_RHEOFACT = 1, 2, 4
 # environment switches only the test build reads (cice_amd/csrc/evp_host.h: env_test): experiments, fault injection, routing
 # of on-device copies through the remote transports.  An EvpHip made while one of them is set uses the test build.
 TEST_ENV = [
@@ -761,6 +764,18 @@ class EvpHip:
         buf = C.create_string_buffer(1000)
         _check(self.lib, self.lib.cice_evp_hip_describe_path(buf, C.c_int32(1000)), "(describe_path)")
         return buf.value.decode(errors="replace")
+
+    def call_flags(self) -> dict:
+        """Test build: the shortcut verdicts the next launch runs under -- bgrid: the effective EVP_F_* word after the last upload /
+        prep / set_metrics (F_*); cgrid: the raw word of the last C-grid upload (CG_*: a set bit takes the shortcut away) and
+        cgrid_fast: whether the default-configuration kernels were taken; resident_lean: whether the last B-grid call ran the on-chip
+        resident kernel in a lean variant."""
+        self._need_testing("call_flags")
+        v = np.zeros(4, dtype=np.uint32)
+        n = self.lib.cice_evp_hip_debug_call_flags(v.ctypes.data_as(C.POINTER(C.c_uint32)), C.c_int32(4))
+        if n != 4:
+            _check(self.lib, -1 if n >= 0 else n, "(debug_call_flags)")
+        return dict(bgrid=int(v[0]), cgrid=int(v[1]), cgrid_fast=bool(v[2]), resident_lean=bool(v[3]))
 
     def march_info(self) -> dict:
         """The marching path (evp_march.hip): did it run, how is the domain cut."""

@@ -111,7 +111,12 @@ int cice_evp_hip_init(const cice_evp_hip_dims *dims, const cice_evp_hip_params *
  * interior value (halo update with sign, ice_dyn_shared.F90:412-417) which the library
  * can only reproduce by local differencing when the grid is symmetric about the seam.
  * (The marching path derives the terms in its kernel: on a tripole grid it verifies once, on
- * the host, that the arrays are those terms on every row below the fold band it marches.) */
+ * the host, that the arrays are those terms on every row below the fold band it marches.)
+ * Where the kernels derive the terms themselves (tarea == dxT*dyT at init), every array given here is compared, on the host and bit
+ * for bit, with the term the kernels would derive, on the T-cells the kernels may evaluate it on (every block's ilo .. ihi+1 x
+ * jlo .. jhi+1 inside the domain).  An array that differs anywhere is
+ * honoured: from then on the kernels read the arrays (dxhy / dyhx alone: only those two; any other: all seven), and the marching
+ * path, which has no array form, declines with "metric terms come from arrays".  Arrays equal to the derived terms change nothing. */
 int cice_evp_hip_set_metrics(const double *cxp, const double *cyp, const double *cxm,
                              const double *cym, const double *dxhy, const double *dyhx,
                              const double *DminTarea);

@@ -213,6 +213,12 @@ int cice_evp_hip_fold_split_plan(int32_t which, int32_t *count, int32_t *cells);
  * hang on; [1] fold_rows (0 none here, 1 all here, 2 shared); [2] stress symmetrisation needs another rank;
  * [3] a cell-centre ghost needs another rank; [4] ... across the fold.  Returns the number written.           */
 int cice_evp_hip_plan_flags(int32_t *flags, int32_t n);
+/* The per-call shortcut verdicts as the kernels of the next launch see them, up to n words: [0] the B grid's effective flag word
+ * (flags & allowed, csrc/evp_device.h: EVP_F_*) after the last upload, prep or set_metrics; [1] the C grid's raw flag word of the
+ * last finish_upload (csrc/evp_cgrid.hip: cg_call_setup -- bit 0 water differs from ocean, 1 TbE / TbN nonzero, 2 rheofact other
+ * than 1); [2] 1 where the C grid then took its default-configuration kernels (CG.fast); [3] 1 where the last B-grid call ran the
+ * on-chip resident kernel in a lean variant.  Returns the number written.                                                        */
+int cice_evp_hip_debug_call_flags(uint32_t *out, int32_t n);
 /* The C grid on a tripole grid, from the plan of cice_evp_hip_plan_build (cice_amd/csrc/halo_plan.h: cg_*).  For field location
  * loc (0 centre, 1 NE corner, 2 E face, 3 N face) the fold step's entries as cice_evp_hip_cgrid_fold_plan gives them; an
  * operand >= nx_block * ny_block * nblocks is a staging slot (the raw value of another rank's cell).  info4 = {1 if the blocks next

@@ -733,12 +733,9 @@ def stir_momentum(inputs, masks, rng):
         inputs[f"rheofact{t}"] = inputs[f"rheofact{t}"] * (rng.random(shape) > 0.1)
 
 
-def marched_case(seed, nx, ny, bs, case, holes, land, general=False, ew="cyclic", ns="closed"):
-    """A synthetic workload in the default configuration (the reference's start-up identities hold for the geometry, waterx == uocn,
-    Tb == 0, rheofact == 1 on ice: what the marched kernel is for) with the branches stirred up: random land cells inside the ocean
-    (coastal corners: the boundary-condition ratios), random, mutually independent holes in the four ice masks.  ns = "cyclic": the
-    closed grid's lengths, with ocean (and ice) up to the top and bottom rows."""
-    from cice_amd import decomp, synth
+def marched_case_global(seed, nx, ny, case, holes, land, general=False, ns="closed"):
+    """marched_case before it is cut into blocks: (g, cg, state, inputs, masks) on the global grid."""
+    from cice_amd import synth
     rng = np.random.default_rng(seed)
     g0 = synth.make_grid(nx, ny, 2.0e4, ns="closed" if ns == "cyclic" else ns)
     if ns == "cyclic":
@@ -761,6 +758,16 @@ def marched_case(seed, nx, ny, bs, case, holes, land, general=False, ew="cyclic"
     for k in ("stresspT", "stressmT", "stress12T"):
         state[k] = state[k] * masks["iceTmask"]
     state["stress12U"] = state["stress12U"] * masks["iceUmask"]
+    return g, cg, state, inputs, masks
+
+
+def marched_case(seed, nx, ny, bs, case, holes, land, general=False, ew="cyclic", ns="closed"):
+    """A synthetic workload in the default configuration (the reference's start-up identities hold for the geometry, waterx == uocn,
+    Tb == 0, rheofact == 1 on ice: what the marched kernel is for) with the branches stirred up: random land cells inside the ocean
+    (coastal corners: the boundary-condition ratios), random, mutually independent holes in the four ice masks.  ns = "cyclic": the
+    closed grid's lengths, with ocean (and ice) up to the top and bottom rows."""
+    from cice_amd import decomp, synth
+    g, cg, state, inputs, masks = marched_case_global(seed, nx, ny, case, holes, land, general=general, ns=ns)
     dc = decomp.Decomp(nx, ny, bs[0], bs[1], ew, ns, 1)
     return (dc, g) + synth.cgrid_scatter(dc, 0, cg, state, inputs, masks)
 
@@ -1022,6 +1029,7 @@ def test_cgrid_default_configuration_shortcuts_are_bit_neutral(monkeypatch):
         core = cgrid_core(c)
         try:
             out = core.cgrid_run(120, state, inputs, masks)
+            assert core.call_flags()["cgrid_fast"] == (fast == "1"), core.call_flags()      # taken under 1, not under 0
         finally:
             core.finalize()
         oracle.halo_update(dom, out["strintxE"], "Eface", "vector")

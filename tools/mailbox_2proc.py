@@ -73,6 +73,10 @@ def main():
     ap.add_argument("--report-prep", action="store_true",
                     help="with --prep: run the preparation three times on the same inputs and print every rank's device time of "
                          "the quickest of the last two (the first call also builds its lists), ms")
+    ap.add_argument("--deviate", default="",
+                    help="RANK:KIND, KIND = TbU (B grid) or TbN (--cgrid): the default configuration (no seabed stress, water == ocean "
+                         "current) with that factor 0.7 on ONE ice cell of RANK next to the cut -- that rank must drop the shortcut, "
+                         "every other rank must keep it (the test build's read-out), and the result must still be the one-rank run's")
     a = ap.parse_args()
     import torch
     import torch.distributed as dist
@@ -97,6 +101,24 @@ def main():
     pr = synth.make_primary(g, "full", seed=9) if a.prep else None
     scal = synth.evp_scalars(120)
     own_wind = bool(a.forcing) and a.wind_ghosts == "own"
+
+    def deviate_cell(ice):
+        """--deviate: the global (row, column) of an ice cell of the named rank with a neighbour cell on another rank."""
+        who = int(a.deviate.split(":")[0])
+        shp = tuple(int(v) for v in a.shape.split("x")) if a.shape else None
+        dcx = decomp.per_rank_blocks(nx, ny, world, "cyclic", ns_bnd, proc_shape=shp)
+        owner = np.full((ny, nx), -1)
+        for b in dcx.blocks:
+            owner[b.gj0 - 1:b.gj0 - 1 + b.gny, b.gi0 - 1:b.gi0 - 1 + b.gnx] = b.owner
+        edge = (np.roll(owner, 1, axis=1) != who) | (np.roll(owner, -1, axis=1) != who)
+        edge[1:] |= owner[:-1] != who
+        edge[:-1] |= owner[1:] != who
+        jj, ii = np.nonzero((owner == who) & edge & (np.asarray(ice) != 0))
+        assert jj.size, "--deviate: no ice cell next to the cut"
+        return int(jj[jj.size // 2]), int(ii[jj.size // 2])
+    if a.deviate and not a.cgrid:
+        assert a.deviate.endswith(":TbU"), a.deviate
+        st["TbU"][deviate_cell(st["iceUmask"])] = 0.7
     if a.forcing:
         calc_s, ocn_s, atm_s = a.forcing.split(",")
         layout = (calc_s == "1", ocn_s, atm_s)
@@ -150,7 +172,10 @@ def main():
 
     def run_cgrid(dc, r, exchange):
         cg = synth.cgrid_geometry(g)
-        state, inputs, masks = synth.cgrid_state(g, cg, case=a.case, seed=7, warm=True, seabed=True)
+        state, inputs, masks = synth.cgrid_state(g, cg, case=a.case, seed=7, warm=True, seabed=not a.deviate)
+        if a.deviate:
+            assert a.deviate.endswith(":TbN"), a.deviate
+            inputs["TbN"][deviate_cell(masks["iceNmask"])] = 0.7
         tmg = np.asarray(masks["iceTmask"]) != 0          # global: the halo mask of the C-grid loop
         hmg = tmg | np.roll(tmg, 1, 1) | np.roll(tmg, -1, 1)
         hmg[1:] |= tmg[:-1]
@@ -158,7 +183,7 @@ def main():
         static, state, inputs, masks = synth.cgrid_scatter(dc, r, cg, state, inputs, masks)
         d, keep = evp.make_dims(dc, r)
         core = evp.EvpHip(d, evp.make_params(scal, strict=True), static["dyE"], static["dxN"], static["dxT"], static["dyT"],
-                          1.0 / static["uarea"], static["tarea"], keepalive=keep, testing=(True if a.forcing else None))
+                          1.0 / static["uarea"], static["tarea"], keepalive=keep, testing=(True if a.forcing or a.deviate else None))
         try:
             if exchange:
                 blobs = [None] * world
@@ -223,6 +248,8 @@ def main():
                 core.cgrid_subcycle(7)
             out = core.cgrid_download()
             out["_halomask"] = hm
+            if a.deviate:
+                out["_flags"] = core.call_flags()
             if a.expect_marched and exchange:
                 out["_marched"] = (core.cgrid_timings(), want_marched, core.describe_path().rpartition("; ")[2])
             if a.expect_marched_fold and exchange:
@@ -291,6 +318,11 @@ def main():
                             w3, h3 = w3[keep3], h3[keep3]
                         if not np.array_equal(w3.view(np.int64), h3.view(np.int64)):
                             bad.append((k + (" fold ghost row" if jr > ny else " row NY ghosts"), int((w3 != h3).sum())))
+        if a.deviate:       # this rank's verdict: the shortcut dropped on the named rank (and in the one-rank run), kept on the others
+            hit = rank == int(a.deviate.split(":")[0])
+            fl, fl1 = got["_flags"], ref["_flags"]
+            if (fl["cgrid"] & 7) != (evp.CG_TB_NONZERO if hit else 0) or fl["cgrid_fast"] == hit or fl1["cgrid_fast"]:
+                bad.append(("flag word of this rank / of the one-rank run", fl, fl1))
         zoned = 0
         if a.expect_marched:
             cgt, want_marched, sched = got["_marched"]
@@ -306,6 +338,7 @@ def main():
                             cgt["marched_items"], path))
         res = [None] * world
         dist.all_gather_object(res, (rank, bad, t_us, tim["halo_send_cells"]) + ((got["_schedule"],) if a.fold_ghosts else ()) +
+                               ((("fast", got["_flags"]["cgrid_fast"]),) if a.deviate else ()) +
                                (((zoned, got["_marched"][0]["marched_cells"], got["_marched"][0]["frame_cells"]),) if a.expect_marched else ()) +
                                (((zoned, got["_marched_fold"][0]["marched_cells"], got["_marched_fold"][0]["fold_frame_cells"],
                                   got["_marched_fold"][0]["marched_fold_exchange"]),) if a.expect_marched_fold else ()))
@@ -313,6 +346,8 @@ def main():
             ok = all(not r[1] for r in res)
             if a.expect_marched or a.expect_marched_fold:
                 ok = ok and any(r[-1][0] for r in res)
+            if a.deviate:       # the ranks differ
+                ok = ok and len({r[4][1] for r in res}) == 2
             print("MAILBOX_2PROC", "OK" if ok else "FAIL", "cgrid", a.workload, f"world={world}", res, flush=True)
             if not ok:
                 sys.exit(1)
@@ -329,7 +364,7 @@ def main():
         # (the test transport of --march exists in the test build only; everything else runs the product library unless the
         # environment holds one of the test build's switches)
         core = evp.EvpHip(d, evp.make_params(scal, strict=True), geo["HTE"], geo["HTN"], geo["dxT"],
-                          geo["dyT"], geo["uarear"], geo["tarea"], keepalive=keep, testing=(True if a.march or a.forcing else None))
+                          geo["dyT"], geo["uarear"], geo["tarea"], keepalive=keep, testing=(True if a.march or a.forcing or a.deviate else None))
         try:
             if exchange:
                 blobs = [None] * world
@@ -401,7 +436,7 @@ def main():
                 extra["iceTmask"] = tmk.astype(np.float64)
             else:
                 core.upload(fields, tm, um)
-                extra = {}
+                extra = {"_flags": core.call_flags()["bgrid"]} if a.deviate else {}
             core.subcycle(a.ndte)
             t = None
             if a.timing:      # the same launches in the reference run: back-to-back loops are compared too
@@ -458,16 +493,23 @@ def main():
                 w, h = ref[k][ref_local[b.gid]], got[k][b.local]
                 if not np.array_equal(w.view(np.uint64), h.view(np.uint64)):
                     bad.append((k + " whole block", b.gid, int((w.view(np.uint64) != h.view(np.uint64)).sum())))
+    if a.deviate:           # this rank's verdict: TBU_ZERO dropped on the named rank (and in the one-rank run), kept on the others
+        hit = rank == int(a.deviate.split(":")[0])
+        if bool(got["_flags"] & evp.F_TBU_ZERO) == hit or not got["_flags"] & evp.F_WATER_IS_OCN or ref["_flags"] & evp.F_TBU_ZERO:
+            bad.append(("flags of this rank / of the one-rank run", hex(got["_flags"]), hex(ref["_flags"])))
     if a.march:
         mi = got["_march"]
-        if not (mi["mode"] == 1 and mi["last_call"] and mi["declined"] == 0 and mi["passes"] > 0):
+        if a.deviate:       # the ranks' verdicts differ: every rank declines the call together and takes the one-subcycle kernel
+            if not (mi["mode"] == 1 and not mi["last_call"] and mi["declined"] == 1):
+                bad.append(("marching kernel: the call was not declined", mi))
+        elif not (mi["mode"] == 1 and mi["last_call"] and mi["declined"] == 0 and mi["passes"] > 0):
             bad.append(("marching kernel did not run", mi))
         want_ring = "direct stores (HIP IPC)" if os.environ.get("CICE_EVP_HIP_MARCH_DIRECT") == "1" and os.environ.get("CICE_EVP_HIP_MARCH_OVERLAP", "0") != "1" else None
         if want_ring and mi["ring"] != want_ring:
             bad.append(("ring of the marching path not exchanged through the inboxes", mi))
     wind_dep = {"uvel", "vvel", "stressp_1", "stressm_3", "stress12_4", "strintxU", "taubyU", "forcexU", "strairxU",
                 "strairyU"} if own_wind else set()      # (--wind-ghosts own: checked against the restatement instead)
-    for k in ("uvel", "vvel", "stressp_1", "stressm_3", "stress12_4", "strintxU", "taubyU",
+    for k in ("uvel", "vvel", "stressp_1", "stressm_3", "stress12_4", "strintxU", "taubyU", "taubxU",
               "forcexU", "umassdti", "uvel_init", "aiU", "iceTmask", "uocnU", "vocnU", "strairxU", "strairyU"):
         if k not in got or k in wind_dep:
             continue
@@ -499,9 +541,12 @@ def main():
             if not np.array_equal(w2, h2):
                 bad.append((k + " ghosts", float(np.abs(w2 - h2).max())))
     res = [None] * world
-    dist.all_gather_object(res, (rank, bad, t_us, tim["launches_per_subcycle"], tim["tile_variant"]))
+    dist.all_gather_object(res, (rank, bad, t_us, tim["launches_per_subcycle"], tim["tile_variant"]) +
+                           ((hex(got["_flags"]),) if a.deviate else ()))
     if rank == 0:
         ok = all(not r[1] for r in res)
+        if a.deviate:           # the ranks differ
+            ok = ok and len({r[5] for r in res}) == 2
         if a.expect_resident:
             ok = ok and all(r[4] >= 2000 for r in res)
         print("MAILBOX_2PROC", "OK" if ok else "FAIL", a.workload, f"world={world}", res, flush=True)
