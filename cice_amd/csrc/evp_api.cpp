@@ -1289,7 +1289,7 @@ int cice_evp_hip_march_info(int32_t *out, int32_t n)
     const State::March &M = S.march;
     const int32_t v[12] = {M.mode, (int32_t)std::min<long>(M.passes, 0x7fffffffL), M.declined, M.L.nblk ? M.L.plan.me.nstrips : 0, M.L.nseg, M.L.seglen,
                            M.last_call ? 1 : 0, M.direct, M.L.kpass, (int32_t)std::min<long>(M.subcycles, 0x7fffffffL),
-                           M.mode == 1 ? M.L.fold.H : 0, M.last_call ? M.call_band_subcycles : 0};
+                           M.mode == 1 ? M.L.band_rows : 0, M.last_call ? M.call_band_subcycles : 0};
     for (int k = 0; out && k < n && k < 12; ++k) out[k] = v[k];
     return 0;
 }
@@ -1310,8 +1310,14 @@ int cice_evp_hip_describe_path(char *buf, int32_t n)
                            ? (M.direct == 1 ? " (ring between ranks: stores into HIP-IPC-mapped inboxes)"
                                             : (M.direct == 2 ? " (ring between ranks: RCCL send/recv, direct stores on trial)" : " (ring between ranks: RCCL send/recv)"))
                            : "";
-    char band[96] = "";
-    if (M.mode == 1 && M.L.fold.H > 0)
+    char band[400] = "";
+    if (M.mode == 1 && M.L.fold.H > 0 && S.d.nranks > 1) {
+        const char *ovl = env("CICE_EVP_HIP_MARCH_OVERLAP");
+        std::snprintf(band, sizeof band, " (tripole: rows 1 .. %d marched, fold band of %d rows one subcycle per launch on %d of %d ranks, %s; its "
+                      "velocity halo in lockstep on every rank with the full lists%s)", M.L.fold.zone, M.L.fold.H, M.L.band_ranks, (int)S.d.nranks,
+                      M.L.band_rows > 0 ? "this one among them" : "none of it here",
+                      (ovl && env_on(ovl, false)) ? "; the overlapped ring is not taken beside a band: serial form" : "");
+    } else if (M.mode == 1 && M.L.fold.H > 0)
         std::snprintf(band, sizeof band, " (tripole: rows 1 .. %d marched, fold band of %d rows one subcycle per launch)", M.L.fold.zone, M.L.fold.H);
     std::snprintf(buf, (size_t)n, "rank %d of %d: kernel = %s; halo transport = %s%s%s; marching path: %s%s%s%s%s; blocks %d, cells per exchange %d",
                   (int)S.d.rank, (int)std::max(1, (int)S.d.nranks), kernel, transport,

@@ -16,7 +16,7 @@
 //   -> q passes of K = 2 .. 4 subcycles and one of the remaining 2 .. K - 1 (ping-pong between two sets of u, v, 12
 //   stresses) -> scatter.  What is decided from the dims alone -- the rectangle, the rim, K, the segments, the lists and the
 //   order of passes and exchanges -- comes from march_plan.cpp (build_march_layout, march_schedule); this file is the plumbing.
-// Not eligible (the one-subcycle kernels keep running): cyclic north-south boundary, a tripole grid on several ranks, blocks
+// Not eligible (the one-subcycle kernels keep running): cyclic north-south boundary, blocks
 // that do not tile a rectangle per rank (eliminated land blocks), metric terms (dxhy, dyhx) handed over as arrays that are not
 // what the kernel derives from HTE / HTN on the rows it evaluates, a rank too thin next to a closed boundary for its redundant
 // rim (march_plan.cpp), a caller whose ghost values are not images of one global state.  Several ranks: the ring of ext + P
@@ -31,6 +31,14 @@
 // windows): the zone's rows under the band into the block layout, the band's rows above the zone into the rectangle; in between
 // each side loses one row of validity per subcycle and never reads a lost row for a cell it owns.  The call ends with the
 // scatter of the zone's rows into the ping-pong buffer the band's last subcycle wrote.
+//
+// The same grid on SEVERAL ranks (march_plan.h: build_march_plan, ranks_fold): one zone and one band for the grid, the band on the
+// ranks whose blocks reach above the zone, each over its own columns.  A band subcycle is the tile kernel over the band's tiles and
+// halo_uv in its remote form, which EVERY rank runs in lockstep with the lists of the one-subcycle loop -- a rank without band rows
+// only exchanges, and flips its ping-pong buffer with the others.  At a trade: band rows into the rectangle (gather), then the rank
+// ring -- which also carries the corner cells above the zone, out of the rows just gathered on the rank that owns them -- then zone
+// rows into the block layout (scatter), whose ghost columns and east-fringe stresses at a rank's x-edges come from the ring cells the
+// exchange has just brought.  Runs when asked for (CICE_EVP_HIP_MARCH=1); the overlapped ring is not taken beside a band.
 // =====================================================================
 #include "evp_host.h"
 
@@ -197,7 +205,7 @@ static bool march_geometry(std::string &why)
     G.gx0 = P.me.gx0; G.gy0 = P.me.gy0; G.nxg = d.nx_global; G.nyg = d.ny_global;
     G.ew_cyclic = d.ew_boundary_type == CICE_EVP_BND_CYCLIC ? 1 : 0;
     G.ext_w = P.ext_w; G.ext_s = P.ext_s; G.nxo = P.owned.nxr; G.nyo = P.owned.nyr;
-    G.nyblk = P.owned.nyr + L.fold.H;      // (a fold band: the blocks go on above the zone, and the ring above it is read from them)
+    G.nyblk = P.owned.nyr + L.band_rows;   // (a fold band on this rank: the blocks go on above the zone, and the ring above it is read from them)
     return true;
 }
 
@@ -538,8 +546,10 @@ static EvpMarchRows rows_window(int y0, int y1)
 static EvpMarchRows check_window()
 {
     const State::March &M = S.march;
-    return L.fold.H > 0 ? rows_window(-(1 << 28), M.G.nyr + EVP_MARCH_PAD) : EvpMarchAllRows;
+    return L.band_rows > 0 ? rows_window(-(1 << 28), M.G.nyr + EVP_MARCH_PAD) : EvpMarchAllRows;
 }
+// global rows [g0, g1) (march_plan.h: MarchFold) as a window of the rectangle this rank holds
+static EvpMarchRows fold_window(int g0, int g1) { return rows_window(g0 - L.plan.me.gy0, g1 - L.plan.me.gy0); }
 
 // The tile list of the fold band for the tile variant in use: every tile of every block that reaches row L.fold.list_row0 or above.
 static int fold_tile_list(int variant, int *&list, int &count)
@@ -567,17 +577,23 @@ static int fold_tile_list(int variant, int *&list, int &count)
     return 0;
 }
 
-// n subcycles of the fold band in the block layout, as enqueue_loop runs them on a tripole grid but over the band's tiles only
+// n subcycles of the fold band in the block layout, as enqueue_loop runs them on a tripole grid but over the band's tiles only.
+// Several ranks: the velocity halo after each runs on EVERY rank, in lockstep, with the lists of the one-subcycle loop (its seam
+// staging where the fold row is cut) -- a rank without band rows launches no tiles and only exchanges: what lands in its ghost cells
+// is overwritten by the final scatter before anything reads it, and its ping-pong buffer flips with everybody else's.
 static int fold_band_subcycles(int n, int &bcur, bool ends_call)
 {
     const int variant = S.tyb % 100;         // (the list holds row-major tile ids)
     int *list = nullptr, count = 0;
-    if (int rc = fold_tile_list(variant, list, count)) return rc;
+    if (L.band_rows > 0)
+        if (int rc = fold_tile_list(variant, list, count)) return rc;
     for (int k = 0; k < n; ++k) {
-        EvpArgs A;
-        fill_args(A, bcur, ends_call && k == n - 1);       // strintx/y, taubx/y of the band: from its own last subcycle
-        A.tile_list = list; A.tile_count = count;
-        evp_launch_subcycle(A, S.max_ni, S.max_nj, S.d.nblocks, variant, S.prm.strict != 0, cap_mode(), S.stream);
+        if (count > 0) {
+            EvpArgs A;
+            fill_args(A, bcur, ends_call && k == n - 1);       // strintx/y, taubx/y of the band: from its own last subcycle
+            A.tile_list = list; A.tile_count = count;
+            evp_launch_subcycle(A, S.max_ni, S.max_nj, S.d.nblocks, variant, S.prm.strict != 0, cap_mode(), S.stream);
+        }
         if (int rc = halo_uv(bcur ^ 1, true)) return rc;
         bcur ^= 1;
     }
@@ -645,6 +661,12 @@ bool march_wanted()
     // worth it when the domain is far beyond what stays on the chip (the on-chip resident kernel is chosen before this
     // is asked): measured against the one-subcycle kernel 24 vs 26.5 us per subcycle at 389k cells, 39 vs 53 at 778k
     if (want < 0 && (long)S.d.nx_global * S.d.ny_global < 450000L * std::max(1, (int)S.d.nranks)) { M.why = "below 450k cells per rank"; return false; }
+    // A fold band shared by several ranks: every band subcycle is a launch set and a collective halo on every piece, and the form has
+    // not been timed against the one-subcycle kernels on these layouts -- so the size rule does not choose it yet.
+    if (want < 0 && L.fold.H > 0 && S.d.nranks > 1) {
+        M.why = "tripole grid on several ranks: marched zone + fold band runs when asked for (CICE_EVP_HIP_MARCH=1), not by the size rule";
+        return false;
+    }
     M.mode = 1;
     return true;
 }
@@ -714,7 +736,9 @@ int march_run(int ndte)
     if (left == 0) { S.cur = cur; return 0; }
     // Fold band (tripole grid): its subcycles flip the block layout's ping-pong buffers, one flip each; bcur names the buffer
     // that holds the band's current state.  The zone's rows reach it at the ring exchanges and in the final scatter.
-    const bool fold = L.fold.H > 0;
+    // Several ranks (shared): ONE band for the grid, held by the top row of ranks; every rank walks the same steps -- the band's
+    // per-subcycle halo is collective -- whether it holds band rows (band) or not.
+    const bool fold = L.fold.H > 0, band = L.band_rows > 0, shared = fold && S.d.nranks > 1;
     int bcur = cur;
     const unsigned fl = S.flags & S.flags_allowed;
     // ---- gather the state and the per-call inputs ----
@@ -769,7 +793,8 @@ int march_run(int ndte)
     // no idle resource to hide a transfer under, and "early" means SHORT segments for the band -- 2K - 1 rows of warm-up on 7 stored.
     // On one GPU the transfer is a 7-us device copy; over xGMI it is 1.6 MB per neighbour every eighth subcycle, and only a node
     // can say whether hiding that is worth 6 us per subcycle.  bench.py --gpus N --extras ring_variants times both.
-    const bool overlap = !L.plan.peers.empty() && !L.band_items.empty() && M.direct != 1 && march_overlap_asked() && !march_direct_asked();
+    // (beside a fold band on several ranks the serial form is taken: the band's rows must be in the rectangle before the ring travels)
+    const bool overlap = !L.plan.peers.empty() && !L.band_items.empty() && M.direct != 1 && march_overlap_asked() && !march_direct_asked() && !shared;
     for (const MarchStep &step : steps) {
         // step.exch: the ring of the new state travels after this pass -- the next one needs more valid cells than are left, or this
         // is the last one (the way back to the block layout reads the ghost cells from it)
@@ -797,10 +822,27 @@ int march_run(int ndte)
             evp_launch_march_unpack(B.st[rc], nullptr, EVP_MARCH_S_NF, B.recv_pos1, B.recv_pos2, L.plan.n_recv, B.cut_recv, B.recvbuf, S.stream_comm);
             HIPC(hipEventRecord(B.ev_done, S.stream_comm));
             HIPC(hipStreamWaitEvent(S.stream, B.ev_done, 0));
-        } else if (exch) {
+        } else if (exch && !shared) {
             if (march_exchange(B.st[rc], nullptr, EVP_MARCH_S_NF)) return -1;
         }
-        if (fold) {
+        if (shared) {
+            // The same steps with the rank ring BETWEEN the two halves of the trade.  The band catches up; on the ranks that hold band
+            // rows, the band's ext + P rows above the zone go into the rectangle; then the ring of the rectangle travels -- the corner
+            // cells above the zone from the rows that gather has just filled on the rank that owns them; only then do the zone's
+            // ext + P rows under the band go into the block layout.  Every image of a cell: at a rank's x-edges the ghost columns and
+            // the T-cells of the east fringe are its neighbour's zone cells, and the ring has just brought them.  (Before the ring they
+            // would come out of spent ring cells; a velocity halo afterwards would mend the velocities but not the fringe stresses,
+            // which every block carries for itself from one subcycle to the next.)
+            if (int e = fold_band_subcycles(step.size, bcur, step.last)) return e;
+            if (band) M.call_band_subcycles += step.size;
+            TabBuilder T;
+            T.add_state(bcur, B.st[rc]);
+            if (step.fexch && band)
+                evp_launch_march_gather(M.G, T.T, nullptr, nullptr, fold_window(L.fold.to_rect[0], L.fold.to_rect[1]), S.stream);
+            if (exch && march_exchange(B.st[rc], nullptr, EVP_MARCH_S_NF)) return -1;
+            if (step.fexch && band)
+                evp_launch_march_scatter(M.G, T.T, S.mask, 2, 12, fold_window(L.fold.to_block[0], L.fold.to_block[1]), S.stream);
+        } else if (fold) {
             // the band catches up with the pass; then, when either side has used up its ring, the two trade rows: the zone's
             // ext + P rows under the band into the block layout (every image of a cell), the band's ext + P rows above the zone
             // into the rectangle (every lane that holds the column)
@@ -825,7 +867,7 @@ int march_run(int ndte)
         T.add_state(bcur, B.st[rc]);
         T.add(S.in[F_STRINTX], B.diag, nullptr, EVP_MARCH_D_NF, 0); T.add(S.in[F_STRINTY], B.diag, nullptr, EVP_MARCH_D_NF, 1);
         T.add(S.in[F_TAUBX], B.diag, nullptr, EVP_MARCH_D_NF, 2); T.add(S.in[F_TAUBY], B.diag, nullptr, EVP_MARCH_D_NF, 3);
-        evp_launch_march_scatter(M.G, T.T, S.mask, 2, 12, fold ? rows_window(-(1 << 28), L.fold.zone) : EvpMarchAllRows, S.stream);
+        evp_launch_march_scatter(M.G, T.T, S.mask, 2, 12, band ? fold_window(-(1 << 27), L.fold.zone) : EvpMarchAllRows, S.stream);
     }
     HIPC(hipGetLastError());
     S.cur = bcur;           // without a band the passes leave the block layout's ping-pong buffer where it was: the scatter wrote the
@@ -876,8 +918,8 @@ extern "C" int cice_evp_hip_march_plan(const cice_evp_hip_dims *dims, int32_t ow
 }
 
 // Host-only: the whole layout of dims->rank as the host would build it when asked `ask7` (march_plan.h: build_march_layout).
-extern "C" int cice_evp_hip_march_layout(const cice_evp_hip_dims *dims, const int32_t *ask7, int32_t *info34, int32_t *blkid, int32_t *org2,
-                                         uint32_t *dup, int32_t *ring5, int32_t *cuts2, int32_t *band4, int32_t *rest4)
+extern "C" int cice_evp_hip_march_layout(const cice_evp_hip_dims *dims, const int32_t *ask7, int32_t *info37, int32_t *blkid, int32_t *org2,
+                                         uint32_t *dup, int32_t *ring5, int32_t *cuts3, int32_t *band4, int32_t *rest4)
 {
     using namespace evp_host;
     if (!dims || !ask7) return fail(-1, "null dims / ask");
@@ -886,13 +928,13 @@ extern "C" int cice_evp_hip_march_layout(const cice_evp_hip_dims *dims, const in
     MarchLayout Y;
     if (!build_march_layout(*dims, a, Y)) return fail(-3, "march layout: %s", Y.why.c_str());
     const int np = (int)Y.plan.peers.size(), ns = Y.plan.n_send, nr = Y.plan.n_recv;
-    if (info34) {
+    if (info37) {
         const MarchPlan &P = Y.plan;
-        const int32_t v[34] = {Y.ext, Y.ring_valid, Y.kpass, Y.bsx, Y.bsy, Y.nbx, Y.nby, P.me.nxr, P.me.nyr, Y.ldx, Y.rows, P.me.own, P.me.nstrips, P.wrapx,
-                               P.me.gx0, P.me.gy0, P.ext_w, P.ext_s, P.owned.nxr, P.owned.nyr, P.owned.nyr + Y.fold.H, (int32_t)Y.nblk, Y.seglen, Y.nseg, Y.nitems, np, ns, nr,
+        const int32_t v[37] = {Y.ext, Y.ring_valid, Y.kpass, Y.bsx, Y.bsy, Y.nbx, Y.nby, P.me.nxr, P.me.nyr, Y.ldx, Y.rows, P.me.own, P.me.nstrips, P.wrapx,
+                               P.me.gx0, P.me.gy0, P.ext_w, P.ext_s, P.owned.nxr, P.owned.nyr, P.owned.nyr + Y.band_rows, (int32_t)Y.nblk, Y.seglen, Y.nseg, Y.nitems, np, ns, nr,
                                (int32_t)Y.band_items.size(), (int32_t)Y.rest_items.size(), Y.fold.H, Y.fold.zone, (int32_t)Y.org.size(),
-                               (int32_t)Y.dup.size()};
-        std::copy(v, v + 34, info34);
+                               (int32_t)Y.dup.size(), Y.band_rows, Y.band_ranks, Y.fold.list_row0};
+        std::copy(v, v + 37, info37);
     }
     if (blkid) std::copy(Y.blkid.begin(), Y.blkid.end(), blkid);
     if (org2) std::memcpy(org2, Y.org.data(), Y.org.size() * sizeof(MarchOrg));
@@ -901,9 +943,10 @@ extern "C" int cice_evp_hip_march_layout(const cice_evp_hip_dims *dims, const in
         int32_t *o = ring5;
         for (const std::vector<int32_t> *l : {&Y.send_pos, &Y.send_midx, &Y.recv_pos1, &Y.recv_pos2, &Y.recv_midx}) o = std::copy(l->begin(), l->end(), o);
     }
-    if (cuts2) {
-        std::copy(Y.cut_send, Y.cut_send + np + 1, cuts2);
-        std::copy(Y.cut_recv, Y.cut_recv + np + 1, cuts2 + np + 1);
+    if (cuts3) {           // where each peer's share begins in the send / the receive list | the peers' ranks (and -1)
+        std::copy(Y.cut_send, Y.cut_send + np + 1, cuts3);
+        std::copy(Y.cut_recv, Y.cut_recv + np + 1, cuts3 + np + 1);
+        for (int q = 0; q <= np; ++q) cuts3[2 * (np + 1) + q] = q < np ? Y.plan.peers[q].rank : -1;
     }
     if (band4) std::memcpy(band4, Y.band_items.data(), Y.band_items.size() * sizeof(MarchItem));
     if (rest4) std::memcpy(rest4, Y.rest_items.data(), Y.rest_items.size() * sizeof(MarchItem));

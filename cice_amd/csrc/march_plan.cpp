@@ -42,12 +42,13 @@ bool dup_table(int nxr, int own, bool wrapx, std::vector<int32_t> &dup)
 
 }  // namespace
 
-bool build_march_fold(const cice_evp_hip_dims &d, int ext, int tyb, MarchFold &F)
+bool build_march_fold(const cice_evp_hip_dims &d, int ext, int tyb, MarchFold &F, bool several_ranks)
 {
     F = MarchFold();
     const int NY = d.ny_global;
     if (d.ns_boundary_type != CICE_EVP_BND_TRIPOLE && d.ns_boundary_type != CICE_EVP_BND_TRIPOLET) { F.error = "no tripole fold"; return false; }
-    if (d.nranks > 1) { F.error = "tripole grid on several ranks: the fold band of the marching path is built for one rank"; return false; }
+    if (d.nranks > 1 && !several_ranks) { F.error = "tripole grid on several ranks: the fold band of the marching path is built for one rank"; return false; }
+    if (d.nranks > 1 && (d.gj0 == nullptr || d.nblocks_tot <= 0)) { F.error = "global block table required when nranks > 1"; return false; }
     if (ext < 0 || (ext & 1)) { F.error = "ext must be even and >= 0"; return false; }
     if (tyb < 2 || tyb > 9) tyb = 5;
     F.ext = ext;
@@ -59,8 +60,11 @@ bool build_march_fold(const cice_evp_hip_dims &d, int ext, int tyb, MarchFold &F
     int row0 = NY - top - 2 * ring;                 // first row of the list with the smallest band, H = ext + P (+ 1)
     if (row0 < 0) { F.error = "grid too short for a marched zone under the fold band"; return false; }
     // down to a tile row of the block that holds it (the highest such row if blocks with different origins hold it)
+    // Several ranks: one band for the whole grid, and NO snap -- the tile height is tuned by timing on each rank for itself
+    // (evp_host_resident.cpp: tune_after_upload), so it is no input that every rank shares; each rank's tile list then starts with
+    // the tile row of its own kernel that holds list_row0, and the rows below it that those tiles also run are spent like the rest.
     int snapped = -1;
-    for (int b = 0; b < d.nblocks; ++b) {
+    for (int b = 0; b < d.nblocks && d.nranks <= 1; ++b) {
         const int gj0 = d.jglob0[b] - 1, gny = d.jhi[b] - d.jlo[b] + 1;
         if (row0 < gj0 || row0 >= gj0 + gny) continue;
         snapped = std::max(snapped, gj0 + ((row0 - gj0) / F.trow) * F.trow);
@@ -83,14 +87,14 @@ void march_fold_tile_rows(const MarchFold &F, int gj0, int gny, int &by0, int &b
     by1 = (gny - 1) / F.trow + 1;                                 // (its last tile row also owns the T-row jhi + 1)
 }
 
-bool build_march_plan(const cice_evp_hip_dims &d, int own_max, bool wrap_inside, int ext, MarchPlan &P, int fold_h)
+bool build_march_plan(const cice_evp_hip_dims &d, int own_max, bool wrap_inside, int ext, MarchPlan &P, int fold_h, const MarchFold *ranks_fold)
 {
     P = MarchPlan();
     const int me = d.rank;
     const int NX = d.nx_global, NY = d.ny_global;
     if (d.nghost != 1) { P.error = "nghost != 1"; return false; }
     const bool tripole = d.ns_boundary_type == CICE_EVP_BND_TRIPOLE || d.ns_boundary_type == CICE_EVP_BND_TRIPOLET;
-    if (tripole && d.nranks > 1) {
+    if (tripole && d.nranks > 1 && !ranks_fold) {
         P.error = "tripole grid on several ranks: the fold band of the marching path is built for one rank";
         return false;
     }
@@ -108,6 +112,36 @@ bool build_march_plan(const cice_evp_hip_dims &d, int own_max, bool wrap_inside,
         for (int b = 0; b < d.nblocks; ++b)
             blk.push_back({d.iglob0[b] - 1, d.jglob0[b] - 1, d.ihi[b] - d.ilo[b] + 1, d.jhi[b] - d.jlo[b] + 1, me});
     }
+    const int nranks = std::max(1, (int)d.nranks);
+    // Several ranks under ONE fold band (ranks_fold): the ranks whose blocks reach above the zone hold the band, each over its own
+    // columns (P.top); the band's tile list (rows list_row0 .. NY - 1) must lie inside that top row of ranks.
+    const bool shared = ranks_fold != nullptr && fold_h > 0 && nranks > 1;
+    const int zone = NY - fold_h, fring = ext + PW;
+    P.top.assign(nranks, 0);
+    if (shared) {
+        std::vector<int> uy0(nranks, 1 << 30), uy1(nranks, -1);
+        for (const Blk &b : blk) {
+            if (b.owner < 0) { P.error = "eliminated land blocks: the ranks' sub-domains are not rectangles"; return false; }
+            if (b.owner >= nranks) { P.error = "block owner out of range"; return false; }
+            uy0[b.owner] = std::min(uy0[b.owner], b.gj0); uy1[b.owner] = std::max(uy1[b.owner], b.gj0 + b.gny - 1);
+        }
+        for (int r = 0; r < nranks; ++r) {
+            if (uy1[r] < 0) continue;
+            P.top[r] = uy1[r] >= zone ? 1 : 0;
+            // (the rule of the closed boundary below, with the zone's top in the boundary's place: the rank under a top rank holds
+            // ext + P rows of it, and those must be rows of the zone.  list_row0 == zone - (ext + P), so this is also the test that
+            // the rows of the band's tile list, list_row0 .. NY - 1, lie inside the top row of ranks: one refusal, one reason)
+            if (P.top[r] && uy0[r] > 0 && uy0[r] > ranks_fold->list_row0) {
+                P.error = "a top rank's share of the marched zone is thinner than its redundant rim + ring: the fold band's list rows "
+                          "do not lie inside the top row of ranks";
+                return false;
+            }
+        }
+        for (char t : P.top) P.band_ranks += t;
+    } else if (fold_h > 0) {
+        P.top[std::min(std::max(me, 0), nranks - 1)] = 1;
+        P.band_ranks = 1;
+    }
     if (fold_h > 0) {
         // the zone of a folded grid: the blocks cut off at row NY - fold_h (what lies above belongs to the band)
         std::vector<Blk> cut;
@@ -119,7 +153,6 @@ bool build_march_plan(const cice_evp_hip_dims &d, int own_max, bool wrap_inside,
         blk.swap(cut);
     }
     // every rank's rectangle
-    const int nranks = std::max(1, (int)d.nranks);
     P.all.assign(nranks, MarchRect());
     std::vector<long> area(nranks, 0);
     std::vector<int> x0(nranks, 1 << 30), y0(nranks, 1 << 30), x1(nranks, -1), y1(nranks, -1);
@@ -190,10 +223,14 @@ bool build_march_plan(const cice_evp_hip_dims &d, int own_max, bool wrap_inside,
     if (!found) { P.error = "no strip width gives every column a single duplicate"; return false; }
     P.me.nstrips = (P.me.nxr + P.me.own - 1) / P.me.own;
 
+    // (under a shared fold band the table is seen uncut up to row zone + ring: the ext + P columns a top rank holds beyond its own go on
+    // above the zone, where they are rows of its x-neighbour's band -- which that rank has gathered into its rectangle, at these very
+    // positions, before the ring travels: the corner cells)
     auto owner_of = [&](int gx, int gy) -> int {
         for (int r = 0; r < nranks; ++r) {
             const MarchRect &R = P.all[r];
-            if (R.ok && gx >= R.gx0 && gx < R.gx0 + R.nxr && gy >= R.gy0 && gy < R.gy0 + R.nyr) return r;
+            if (!R.ok || gx < R.gx0 || gx >= R.gx0 + R.nxr || gy < R.gy0) continue;
+            if (gy < R.gy0 + R.nyr || (shared && P.top[r] && gy < zone + fring)) return r;
         }
         return -1;
     };
@@ -210,6 +247,8 @@ bool build_march_plan(const cice_evp_hip_dims &d, int own_max, bool wrap_inside,
                 int gx = E.gx0 + x;
                 const int gy = E.gy0 + y;
                 if (gy < 0 || gy >= NY) continue;                          // closed north / south
+                // above D's own columns lies D's own band: gathered from its block layout, never exchanged
+                if (shared && gy >= zone && x >= HD.w && x < E.nxr - HD.e) continue;
                 if (gx < 0 || gx >= NX) {
                     if (!ew_cyclic) continue;
                     if (HD.wrap) continue;                                 // D reads those columns through the wrap of its strips
@@ -262,13 +301,13 @@ bool build_march_layout(const cice_evp_hip_dims &d, const MarchAsk &ask, MarchLa
     // the rectangles of all ranks, this rank's strips and the exchange lists: the same verdict on every rank
     auto plan = [&](int e) -> bool {
         F = MarchFold();
-        if (tripole && !build_march_fold(d, e, ask.tyb, F)) {
+        if (tripole && !build_march_fold(d, e, ask.tyb, F, true)) {
             P = MarchPlan();
             P.error = F.error;
             F = MarchFold();
             return false;
         }
-        return build_march_plan(d, ask.own_max, ask.wrap_inside, e, P, F.H);
+        return build_march_plan(d, ask.own_max, ask.wrap_inside, e, P, F.H, &F);
     };
     // cells a rank holds beyond its own on every side with a neighbour: the ring of ext + P cells is then exchanged every
     // (ext + P)-th subcycle only (march_plan.h); 4 = after every second pass of four.  (Rounds 4-5, two subcycles per pass and a
@@ -357,7 +396,10 @@ bool build_march_layout(const cice_evp_hip_dims &d, const MarchAsk &ask, MarchLa
         L.blkid[(size_t)bj * nbx + bi] = b;
         L.org[b] = MarchOrg{ox + P.ext_w, oy + P.ext_s};        // block origins in the rectangle the rank HOLDS
     }
-    if (nxr != P.owned.nxr || nyr - F.H != P.owned.nyr || gx0 - 1 != P.owned.gx0 || gy0 - 1 != P.owned.gy0)
+    // (the fold band: this rank's rows of it, and the ranks that hold some -- on several ranks only those whose blocks reach above the zone)
+    L.band_rows = (F.H > 0 && !P.top.empty() && P.top[d.nranks > 1 ? d.rank : 0]) ? F.H : 0;
+    L.band_ranks = P.band_ranks;
+    if (nxr != P.owned.nxr || nyr - L.band_rows != P.owned.nyr || gx0 - 1 != P.owned.gx0 || gy0 - 1 != P.owned.gy0)
         return refuse("local blocks disagree with the global block table");
     L.bsx = bsx; L.bsy = bsy; L.nbx = nbx; L.nby = nby;
     const MarchRect &me = P.me;       // held: own cells + the redundant rim

@@ -42,12 +42,15 @@ struct MarchPeer {
     std::vector<int32_t> recv_col, recv_row;     // column x / storage row of the halo cell (byte mask)
 };
 
+struct MarchFold;
 struct MarchPlan {
     MarchRect me;                                // the rectangle this rank HOLDS: its own cells plus `ext` more on every side that
                                                  // has a neighbour (computed redundantly, so that the ring is exchanged less often)
     MarchRect owned;                             // the cells this rank owns (gx0, gy0, nxr, nyr)
     int ext_w = 0, ext_e = 0, ext_s = 0, ext_n = 0;
     std::vector<MarchRect> all;                  // every rank's OWN rectangle (index = rank; ok = false: rank holds nothing)
+    std::vector<char> top;                       // fold band: does the rank's share of the grid reach above the zone (it holds band rows)?
+    int band_ranks = 0;                          // ... how many do
     bool wrapx = false;                          // E-W cyclic wrap handled inside the rank (it spans the whole dimension)
     std::vector<int32_t> dup;                    // [nstrips][64]: (strip << 8) | lane of the duplicate of an owner lane's column, -1 none
     std::vector<MarchPeer> peers;                // ascending rank; may contain this rank itself (self-exchange across the seam)
@@ -63,7 +66,14 @@ struct MarchPlan {
 // fold_h > 0 (one rank, tripole / tripoleT): the plan is built for the ZONE of a folded grid -- global rows 0 .. NY - fold_h - 1, a
 // rectangle closed in the south with a neighbour in the north.  That neighbour is no rank: it is this process's own fold band
 // (MarchFold), so no peer list names it; the rows above the zone's own are filled by the ring exchange of evp_host_march.cpp.
-bool build_march_plan(const cice_evp_hip_dims &d, int own_max, bool wrap_inside, int ext, MarchPlan &P, int fold_h = 0);
+// ranks_fold (build_march_layout only; without it a tripole grid on several ranks is refused): the same zone under ONE band shared by
+// the top row of ranks.  Every rank's rectangle is its blocks cut off at row `zone`; a rank whose blocks reach that row has the band --
+// its own columns of it -- as its northern neighbour, a rank below has a rank there.  The ext + P columns a top rank holds beyond its
+// own continue above the zone (rows zone .. zone + ext + P - 1): those CORNER cells belong to the band of its x-neighbour and travel
+// with the rank ring, from the positions of the neighbour's rectangle its own band rows were gathered into.  Refused: band list rows
+// (list_row0 .. NY - 1) outside the top row of ranks, a top rank whose share of the zone is thinner than ext + P.
+bool build_march_plan(const cice_evp_hip_dims &d, int own_max, bool wrap_inside, int ext, MarchPlan &P, int fold_h = 0,
+                      const MarchFold *ranks_fold = nullptr);
 
 // A tripole grid on one rank: two sets of cells with a ring between them.
 //   zone  global rows 0 .. zone-1, advanced several subcycles per pass in the strip-major rectangle (which also holds `ext`
@@ -84,7 +94,10 @@ struct MarchFold {
 // tyb: tile height of the one-subcycle kernel (2 .. 9).  H is the smallest ext + P (tripoleT: one more, the zone's ring stays
 // below the top physical row), rounded up so that the band's list starts on a tile row of the block that holds it (the same
 // tiles run either way; the zone loses the rows).
-bool build_march_fold(const cice_evp_hip_dims &d, int ext, int tyb, MarchFold &F);
+// several_ranks (build_march_layout only): one zone and one band for the whole grid -- global rows, identical on every rank, from
+// the grid's size and ext alone: H = ext + P (+ 1), no snap, because each rank tunes its tile height for itself and tyb is therefore
+// not the same everywhere.  Without it several ranks are refused (the one-rank question).
+bool build_march_fold(const cice_evp_hip_dims &d, int ext, int tyb, MarchFold &F, bool several_ranks = false);
 // tile rows [by0, by1) of a block with `gny` rows whose first row is global row gj0 (0-based) that belong to the band's list
 void march_fold_tile_rows(const MarchFold &F, int gj0, int gny, int &by0, int &by1);
 
@@ -105,7 +118,8 @@ struct MarchOrg { int32_t x, y; };                   // as the kernels read them
 struct MarchItem { int32_t strip, y0, y1, pad; };    // ... int4 {strip, Y0, Y1, 0}
 struct MarchLayout {
     MarchPlan plan;                 // the rectangle the rank holds (plan.me), its own cells (plan.owned), the peers
-    MarchFold fold;                 // the fold band of a tripole grid (H == 0: none)
+    MarchFold fold;                 // the fold band of a tripole grid (H == 0: none); on several ranks the same on every rank
+    int band_rows = 0, band_ranks = 0;          // rows of the band THIS rank holds (fold.H or 0) | ranks that hold some
     int ext = 0, ring_valid = MARCH_PLAN_PAD;   // the rim; cells beyond the rank's own that are current after an exchange of the
                                                 // ring (ext + P): that many subcycles can follow before the next exchange
     int kpass = MARCH_PLAN_PAD;     // subcycles a full pass advances the state by

@@ -915,7 +915,7 @@ def march_fold_plan(dims: Dims, ext: int = 0, tyb: int = 5) -> dict:
 
 MARCH_LAYOUT_INFO = ("ext", "ring_valid", "kpass", "bsx", "bsy", "nbx", "nby", "nxr", "nyr", "ldx", "rows", "own", "nstrips", "wrapx", "gx0", "gy0",
                      "ext_w", "ext_s", "nxo", "nyo", "nyblk", "nblk", "seglen", "nseg", "nitems", "npeers", "n_send", "n_recv", "nband", "nrest",
-                     "fold_h", "fold_zone", "norg", "ndup")
+                     "fold_h", "fold_zone", "norg", "ndup", "band_rows", "band_ranks", "list_row0")
 
 
 def march_layout(dims: Dims, own_max: int = 56, wrap_inside: bool = True, ext: int | None = None, kpass: int | None = None,
@@ -935,13 +935,13 @@ def march_layout(dims: Dims, own_max: int = 56, wrap_inside: bool = True, ext: i
     org = np.zeros((out["norg"], 2), dtype=np.int32)
     dup = np.zeros((out["nstrips"], 64), dtype=np.uint32)
     ring = np.zeros(max(2 * ns + 3 * nr, 1), dtype=np.int32)
-    cuts = np.zeros((2, npeer + 1), dtype=np.int32)
+    cuts = np.zeros((3, npeer + 1), dtype=np.int32)
     band = np.zeros((out["nband"], 4), dtype=np.int32)
     rest = np.zeros((out["nrest"], 4), dtype=np.int32)
     _check(lib, lib.cice_evp_hip_march_layout(C.byref(dims), _ip(ask), None, _ip(blkid), _ip(org), dup.ctypes.data_as(C.POINTER(C.c_uint32)),
                                               _ip(ring), _ip(cuts), _ip(band), _ip(rest)), "(march_layout)")
     out.update(blkid=blkid, org=org, dup=dup, send_pos=ring[:ns], send_midx=ring[ns:2 * ns], recv_pos1=ring[2 * ns:2 * ns + nr],
-               recv_pos2=ring[2 * ns + nr:2 * ns + 2 * nr], recv_midx=ring[2 * ns + 2 * nr:2 * ns + 3 * nr], cut_send=cuts[0], cut_recv=cuts[1],
+               recv_pos2=ring[2 * ns + nr:2 * ns + 2 * nr], recv_midx=ring[2 * ns + 2 * nr:2 * ns + 3 * nr], cut_send=cuts[0], cut_recv=cuts[1], peer_rank=cuts[2, :npeer],
                band_items=band, rest_items=rest)
     return out
 

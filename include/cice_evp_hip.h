@@ -447,14 +447,19 @@ int cice_evp_hip_time_kernels(int32_t nrep, double *out3);
  * 1 stores into the neighbours' HIP-IPC-mapped inboxes (opt-in: CICE_EVP_HIP_MARCH_DIRECT=1 on every rank, inside one
  * node; in use once a trial exchange has delivered the same bits as RCCL on every rank), 2 on trial; [8] (n >= 10) subcycles
  * a full pass advances the state by (4), [9] subcycles advanced by passes since init; (n >= 12) [10] rows of the fold band
- * (0 = no band), [11] subcycles the band advanced in the last call.  Tripole / tripoleT grid on one rank: rows 1 .. NY - [10] are
- * marched, the top [10] rows and the ghost row beyond the fold advance one subcycle per launch beside the passes (tile kernel +
- * seam step), and the two trade a ring of rows on the device every few passes.  Not eligible: cyclic north-south boundary, a
- * tripole grid on several ranks, blocks that do not tile a rectangle per rank, metric arrays that are not what HTE, HTN, dxT, dyT
- * give on the rows the marching kernel evaluates.
- * CICE_EVP_HIP_MARCH=0/1 forces the path off / on (default: from 450k cells per rank).  Several ranks:
+ * THIS rank holds (0 = none), [11] subcycles the band advanced here in the last call.  Tripole / tripoleT grid on one rank: rows
+ * 1 .. NY - [10] are marched, the top [10] rows and the ghost row beyond the fold advance one subcycle per launch beside the passes
+ * (tile kernel + seam step), and the two trade a ring of rows on the device every few passes.  On several ranks the same with ONE
+ * band for the grid, held by the ranks whose blocks reach above the zone ([10], [11] are 0 on the others); the band's velocity halo
+ * runs on every rank in lockstep, the rank ring also carries the corner cells above the zone, and the form runs only when asked for
+ * (CICE_EVP_HIP_MARCH=1: not timed against the one-subcycle kernels yet).  Not eligible: cyclic north-south boundary, blocks that do
+ * not tile a rectangle per rank (eliminated land blocks), a rank closer to a closed boundary -- or a top rank's zone rows fewer --
+ * than rim + ring, metric arrays that are not what HTE, HTN, dxT, dyT give on the rows the marching kernel evaluates.
+ * CICE_EVP_HIP_MARCH=0/1 forces the path off / on (default: from 450k cells per rank, on closed grids and on tripole grids of one
+ * rank).  Several ranks:
  * CICE_EVP_HIP_MARCH_OVERLAP=1 (every rank alike) advances the cells other ranks wait for first, on a second stream, and
- * overlaps their RCCL send / recv with the rest of the pass (default: pack, send / recv, unpack after the pass).        */
+ * overlaps their RCCL send / recv with the rest of the pass (default: pack, send / recv, unpack after the pass; beside a fold band
+ * on several ranks the serial form is taken, and cice_evp_hip_describe_path says so).                                  */
 int cice_evp_hip_march_info(int32_t *out, int32_t n);
 /* One line of text on what the last cice_evp_hip_subcycle ran (kernel, halo transport, the marching path and why it is
  * off when it is), for logs.                                                                                       */

@@ -108,20 +108,24 @@ int cice_evp_hip_march_plan(const cice_evp_hip_dims *dims, int32_t own_max, int3
  * global, 0-based, windows half open.  out10 = {zone rows (the zone is rows 0 .. zone-1), band rows H, ext, U-rows per tile row,
  * lowest row the band's tile list covers, ring exchange rectangle -> block layout [lo, hi), block layout -> rectangle [lo, hi),
  * rows the zone's rectangle holds (zone + ext)}; tile_rows (may be NULL) = per local block the tile rows [by0, by1) of the band's
- * list.  Fails (-3) where there is no fold, on several ranks, and on a grid too short for a zone under the band.           */
+ * list.  Fails (-3) where there is no fold, on several ranks (the one-rank question: the several-rank form is planned by
+ * cice_evp_hip_march_layout only), and on a grid too short for a zone under the band.                                     */
 int cice_evp_hip_march_fold_plan(const cice_evp_hip_dims *dims, int32_t ext, int32_t tyb, int32_t *out10, int32_t *tile_rows);
 /* Host-only (CPU tests): everything the marching path's host decides from the dims and what it may be asked for alone
  * (cice_amd/csrc/march_plan.h: build_march_layout).  ask7 = {own_max, wrap_inside, ext, kpass, seglen, bandseg, tyb}: the test build's
  * switches CICE_EVP_HIP_MARCH_OWN / _SELFX (inverted) / _EXT / _K / _SEG / _BANDSEG and the tile height; ext, kpass = INT32_MIN: not
- * asked for (the rim and pass size rules decide), seglen, bandseg = 0 likewise.  info34 = {ext, ring_valid, kpass, bsx, bsy, nbx, nby, nxr,
+ * asked for (the rim and pass size rules decide), seglen, bandseg = 0 likewise.  info37 = {ext, ring_valid, kpass, bsx, bsy, nbx, nby, nxr,
  * nyr, ldx, rows, own, nstrips, wrapx, gx0, gy0, ext_w, ext_s, nxo, nyo, nyblk, nblk, seglen, nseg, nitems, peers, cells sent, cells
- * received, band items, rest items, fold band rows, zone rows, entries of org, entries of dup}.  Tables (any may be NULL; sizes from a
+ * received, band items, rest items, fold band rows, zone rows, entries of org, entries of dup, fold band rows THIS rank holds, ranks
+ * that hold some, lowest row the band's tile list covers}.  A tripole / tripoleT grid on several ranks: one zone and one band for the
+ * grid (the same fold band rows, zone rows and list row on every rank), the band on the ranks whose blocks reach above the zone; the
+ * exchange lists of such a rank also name the corner cells above the zone beside its own columns (march_plan.h).  Tables (any may be NULL; sizes from a
  * first call): blkid [nby][nbx]; org2 [nblocks]{x, y}; dup [nstrips][64] byte offsets; ring5 = send_pos, send_midx [cells sent] then
- * recv_pos1, recv_pos2, recv_midx [cells received]; cuts2 = where each peer's share begins in the send list, then in the receive list,
- * [peers + 1] each; band4 / rest4 = the work items {strip, y0, y1, 0} of an overlapped exchange pass.  Fails (-3) with the words the
+ * recv_pos1, recv_pos2, recv_midx [cells received]; cuts3 = where each peer's share begins in the send list, then in the receive list,
+ * then the peers' ranks (and -1), [peers + 1] each; band4 / rest4 = the work items {strip, y0, y1, 0} of an overlapped exchange pass.  Fails (-3) with the words the
  * library gives for "marching kernel off" where the layout refuses the domain.                                                   */
-int cice_evp_hip_march_layout(const cice_evp_hip_dims *dims, const int32_t *ask7, int32_t *info34, int32_t *blkid, int32_t *org2, uint32_t *dup,
-                              int32_t *ring5, int32_t *cuts2, int32_t *band4, int32_t *rest4);
+int cice_evp_hip_march_layout(const cice_evp_hip_dims *dims, const int32_t *ask7, int32_t *info37, int32_t *blkid, int32_t *org2, uint32_t *dup,
+                              int32_t *ring5, int32_t *cuts3, int32_t *band4, int32_t *rest4);
 /* Host-only (CPU tests): the steps of a call of ndte subcycles (march_plan.h: march_schedule): steps4 = per step {size, ring between ranks
  * travels after it, zone and fold band trade rows after it, last}; a step of size 1 is the leading subcycle of the one-subcycle kernel.
  * *n = number of steps (<= ndte); steps4 may be NULL.                                                                            */

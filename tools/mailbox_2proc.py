@@ -32,11 +32,23 @@ def main():
                     help="start from the primary model state: evp()'s preparation phase on the device on every "
                          "rank (T-grid halos across ranks through the same transport), then the loop")
     ap.add_argument("--maskhalo", action="store_true",
-                    help="with --cgrid: hand the loop the masked halo evp() builds when maskhalo_dyn (five-point dilation of "
+                    help="B grid or --cgrid: hand the loop the masked halo evp() builds when maskhalo_dyn (five-point dilation of "
                          "iceTmask, ice_dyn_evp.F90:739-770); ghost cells outside the mask stay stale, everything else must not change")
     ap.add_argument("--march", action="store_true",
                     help="force the marching kernel on every rank; its ring exchanges and rank agreements go "
                          "through the library's test transport (host buffers + gloo here: RCCL refuses two ranks per device)")
+    ap.add_argument("--ref-march-off", action="store_true",
+                    help="B grid: the one-rank reference run takes the one-subcycle kernels (CICE_EVP_HIP_MARCH=0 while it is set up and "
+                         "run), so that the two sides of the comparison share no marching code")
+    ap.add_argument("--all-fields", action="store_true",
+                    help="B grid: compare all 12 stresses and strintx / strinty / taubx / tauby, not the usual selection, and everything "
+                         "as bit patterns; on a tripoleT grid the velocities are handed over with the top row as the fold's image")
+    ap.add_argument("--fused", action="store_true", help="B grid: fused mode (strict = 0) on both sides")
+    ap.add_argument("--expect-fold-band", action="store_true",
+                    help="with --march on a tripole grid: every rank that holds rows of the fold band must have advanced them by every "
+                         "subcycle of the call but a leading single one, the others by none, and describe_path() must name the band")
+    ap.add_argument("--expect-march-off", default="",
+                    help="with --march: every rank must have stayed off the marching path and give these words as the reason")
     ap.add_argument("--case", default="full")
     ap.add_argument("--cgrid", action="store_true",
                     help="the C-grid subcycle (cice_evp_hip_cgrid_*): ghost cells other ranks own filled through the "
@@ -97,7 +109,15 @@ def main():
     ns_bnd = spec.get("ns", "closed")          # tx1: tripole north boundary (rank layouts with px = 1 only)
     # ("NXxNY:tripoleT": the T-fold -- the same grid as the u-fold's; only the halo rule differs, and the top row is an image)
     g = synth.derive_geometry(synth.make_grid(nx, ny, spec["dx0"], ns=("tripole" if ns_bnd == "tripoleT" else ns_bnd)))
-    st = synth.make_state(g, case="full", seed=7, warm=True)
+    st = synth.make_state(g, case=(a.case if a.march and not a.cgrid else "full"), seed=7, warm=True)
+    if a.all_fields and ns_bnd == "tripoleT" and not a.cgrid:
+        # Bit patterns, ghost cells included: hand over velocities as a halo update leaves them, as evp() does.  On the T-fold the top
+        # row is the image of the row below, a(i, NY) = -a(NX - i + 1, NY - 1), so a resting land cell shows as -0.0 up there.  The
+        # kernels refresh the images of the cells they compute; where a rank's blocks let each computing thread store its own images,
+        # the image of a land cell keeps the value it came with -- and a synthetic +0.0 would differ from the one-rank run's -0.0.
+        for k in ("uvel", "vvel"):
+            st[k] = np.array(st[k], dtype=np.float64, copy=True)
+            st[k][ny - 1, :] = -st[k][ny - 2, ::-1]
     pr = synth.make_primary(g, "full", seed=9) if a.prep else None
     scal = synth.evp_scalars(120)
     own_wind = bool(a.forcing) and a.wind_ghosts == "own"
@@ -363,13 +383,22 @@ def main():
         d, keep = evp.make_dims(dc, r)
         # (the test transport of --march exists in the test build only; everything else runs the product library unless the
         # environment holds one of the test build's switches)
-        core = evp.EvpHip(d, evp.make_params(scal, strict=True), geo["HTE"], geo["HTN"], geo["dxT"],
+        core = evp.EvpHip(d, evp.make_params(scal, strict=not a.fused), geo["HTE"], geo["HTN"], geo["dxT"],
                           geo["dyT"], geo["uarear"], geo["tarea"], keepalive=keep, testing=(True if a.march or a.forcing or a.deviate else None))
         try:
             if exchange:
                 blobs = [None] * world
                 dist.all_gather_object(blobs, core.halo_export())
                 core.halo_import(blobs)
+            hm = None
+            if exchange and a.maskhalo:
+                # ice_HaloMask as evp() builds it when maskhalo_dyn: the five-point dilation of iceTmask (ice_dyn_evp.F90:739-770)
+                tmg = np.asarray(st["iceTmask"]) != 0
+                hmg = tmg | np.roll(tmg, 1, 1) | np.roll(tmg, -1, 1)
+                hmg[1:] |= tmg[:-1]
+                hmg[:-1] |= tmg[1:]
+                hm = dc.scatter(hmg.astype(np.int32), r, fill=0)
+                core.halo_mask(hm)
             if exchange and a.march:
                 def xchg(ranks, ns, nr, send, recv):
                     ops, so, ro = [], 0, 0
@@ -456,6 +485,8 @@ def main():
             out = core.download()
             out.update(extra)
             out["_march"] = core.march_info()
+            out["_path"] = core.describe_path()
+            out["_halomask"] = hm
             return out, core.timings(), t
         finally:
             core.finalize()
@@ -474,7 +505,18 @@ def main():
     ref = None
     for turn in range(world):
         if turn == rank:
-            ref, _, _ = run(dc1, 0, False)
+            was = os.environ.get("CICE_EVP_HIP_MARCH")
+            if a.ref_march_off:
+                os.environ["CICE_EVP_HIP_MARCH"] = "0"
+            try:
+                ref, _, _ = run(dc1, 0, False)
+            finally:
+                if a.ref_march_off:
+                    os.environ.pop("CICE_EVP_HIP_MARCH")
+                    if was is not None:
+                        os.environ["CICE_EVP_HIP_MARCH"] = was
+            if a.ref_march_off and ref["_march"]["mode"] != 0:
+                raise SystemExit(f"--ref-march-off: the reference run took the marching path: {ref['_march']}")
         dist.barrier()
     ref_global = {}
 
@@ -499,26 +541,40 @@ def main():
             bad.append(("flags of this rank / of the one-rank run", hex(got["_flags"]), hex(ref["_flags"])))
     if a.march:
         mi = got["_march"]
-        if a.deviate:       # the ranks' verdicts differ: every rank declines the call together and takes the one-subcycle kernel
+        if a.expect_march_off:
+            if not (mi["mode"] == 0 and mi["passes"] == 0 and "marching path: off -- " in got["_path"] and a.expect_march_off in got["_path"]):
+                bad.append(("marching kernel: not off, or for another reason", mi, got["_path"]))
+        elif a.deviate:     # the ranks' verdicts differ: every rank declines the call together and takes the one-subcycle kernel
             if not (mi["mode"] == 1 and not mi["last_call"] and mi["declined"] == 1):
                 bad.append(("marching kernel: the call was not declined", mi))
         elif not (mi["mode"] == 1 and mi["last_call"] and mi["declined"] == 0 and mi["passes"] > 0):
             bad.append(("marching kernel did not run", mi))
+        if a.expect_fold_band:
+            holds = any(b.gj0 + b.gny - 1 == ny for b in dcN.local_blocks(rank))
+            led = 1 if a.ndte % mi["kpass"] == 1 else 0
+            if holds != (mi["band_rows"] > 0) or mi["band_subcycles"] != (a.ndte - led if holds else 0) or "fold band" not in got["_path"] \
+                    or f"of {world} ranks" not in got["_path"]:
+                bad.append(("fold band: rows, subcycles or wording", holds, mi, got["_path"]))
         want_ring = "direct stores (HIP IPC)" if os.environ.get("CICE_EVP_HIP_MARCH_DIRECT") == "1" and os.environ.get("CICE_EVP_HIP_MARCH_OVERLAP", "0") != "1" else None
         if want_ring and mi["ring"] != want_ring:
             bad.append(("ring of the marching path not exchanged through the inboxes", mi))
     wind_dep = {"uvel", "vvel", "stressp_1", "stressm_3", "stress12_4", "strintxU", "taubyU", "forcexU", "strairxU",
                 "strairyU"} if own_wind else set()      # (--wind-ghosts own: checked against the restatement instead)
+    same = (lambda p, q: np.array_equal(p.view(np.uint64), q.view(np.uint64))) if a.all_fields else np.array_equal      # (bit patterns)
+    more = tuple(k for k in tuple(evp.FIELDS[:12]) + ("strintxU", "strintyU", "taubxU", "taubyU")
+                 if k not in ("stressp_1", "stressm_3", "stress12_4", "strintxU", "taubyU", "taubxU")) if a.all_fields else ()
     for k in ("uvel", "vvel", "stressp_1", "stressm_3", "stress12_4", "strintxU", "taubyU", "taubxU",
-              "forcexU", "umassdti", "uvel_init", "aiU", "iceTmask", "uocnU", "vocnU", "strairxU", "strairyU"):
+              "forcexU", "umassdti", "uvel_init", "aiU", "iceTmask", "uocnU", "vocnU", "strairxU", "strairyU") + more:
         if k not in got or k in wind_dep:
             continue
         want = dcN.scatter(refg(k), rank)
         for b in dcN.local_blocks(rank):
             w = want[b.local][1:1 + b.gny, 1:1 + b.gnx]
             h = got[k][b.local][1:1 + b.gny, 1:1 + b.gnx]
-            if not np.array_equal(w, h):
-                bad.append((k, float(np.abs(w - h).max())))
+            if not same(np.ascontiguousarray(w), np.ascontiguousarray(h)):
+                jj, ii = np.nonzero(w != h)          # (where: global rows and columns, 1-based, of the cells that differ)
+                where = (int(jj.min()) + b.gj0, int(jj.max()) + b.gj0, int(ii.min()) + b.gi0, int(ii.max()) + b.gi0, int(jj.size)) if jj.size else ()
+                bad.append((k, float(np.abs(w - h).max())) + ((where,) if a.all_fields else ()))
         if k.startswith("stress") and ns_bnd == "tripole" and not a.timing:
             # the ghost row beyond the fold after the symmetrisation: the partner array's top row, mirrored (centre rule)
             fam, q = k.rsplit("_", 1)
@@ -538,8 +594,17 @@ def main():
                     if b.gj0 + b.gny - 1 == ny:           # (row gny + 1: a padded block has spare rows above it)
                         w2[b.local][b.gny + 1:, :] = 0.0
                         h2[b.local][b.gny + 1:, :] = 0.0
-            if not np.array_equal(w2, h2):
-                bad.append((k + " ghosts", float(np.abs(w2 - h2).max())))
+            if got.get("_halomask") is not None:     # ghost cells outside the mask are not refreshed (stale, as in the reference)
+                for b in dcN.local_blocks(rank):
+                    stale = got["_halomask"][b.local] == 0
+                    stale[1:1 + b.gny, 1:1 + b.gnx] = False
+                    w2[b.local][stale] = 0.0
+                    h2[b.local][stale] = 0.0
+            if not same(w2, h2):
+                # (where, under --all-fields: the first few as (local block, row, column, wanted, got) -- a sign of zero shows in the reprs)
+                nb, jj, ii = np.nonzero(w2.view(np.uint64) != h2.view(np.uint64)) if a.all_fields else ((), (), ())
+                first = [(int(q), int(j), int(i), repr(float(w2[q, j, i])), repr(float(h2[q, j, i]))) for q, j, i in list(zip(nb, jj, ii))[:4]]
+                bad.append((k + " ghosts", float(np.abs(w2 - h2).max())) + ((len(jj), first) if a.all_fields else ()))
     res = [None] * world
     dist.all_gather_object(res, (rank, bad, t_us, tim["launches_per_subcycle"], tim["tile_variant"]) +
                            ((hex(got["_flags"]),) if a.deviate else ()))
