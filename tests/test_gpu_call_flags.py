@@ -13,23 +13,24 @@ import call_flag_cases as cf
 import oracle
 from cice_amd import evp
 from common import assert_bitwise
+from evp_call_chain import PATH_ENV, PATHS as PATH_SWITCHES
 
 pytestmark = pytest.mark.gpu
 
 OCN, TBU, MET, DXHY = evp.F_WATER_IS_OCN, evp.F_TBU_ZERO, evp.F_METRICS, evp.F_DXHY_ARRAY
-# path -> (environment, 3 x 3 padded blocks or one block)
+# path -> (environment, 3 x 3 padded blocks or one block); the switches of a path are tests/evp_call_chain.py's, as is the list of
+# switches cleared before a row's own are set
 PATHS = {
-    "streaming": ({"CICE_EVP_HIP_RESIDENT": "0", "CICE_EVP_HIP_MARCH": "0"}, True),
-    "resident general": ({"CICE_EVP_HIP_RESIDENT": "1", "CICE_EVP_HIP_RES_LEAN": "0"}, True),
-    "resident lean-eligible": ({"CICE_EVP_HIP_RESIDENT": "1", "CICE_EVP_HIP_RES_LOGW": "4"}, False),
-    "marching k=4": ({"CICE_EVP_HIP_MARCH": "1", "CICE_EVP_HIP_RESIDENT": "0", "CICE_EVP_HIP_MARCH_K": "4"}, True),
-    "marching k=2": ({"CICE_EVP_HIP_MARCH": "1", "CICE_EVP_HIP_RESIDENT": "0", "CICE_EVP_HIP_MARCH_K": "2"}, False),
+    "streaming": (PATH_SWITCHES["streaming"], True),
+    "resident general": (PATH_SWITCHES["resident general"], True),
+    "resident lean-eligible": (PATH_SWITCHES["resident lean-eligible"], False),
+    "marching k=4": (PATH_SWITCHES["marching k=4"], True),
+    "marching k=2": (dict(PATH_SWITCHES["marching k=4"], CICE_EVP_HIP_MARCH_K="2"), False),
 }
 
 
 def make_core(monkeypatch, env, split, geo=None):
-    for k in ("CICE_EVP_HIP_RESIDENT", "CICE_EVP_HIP_MARCH", "CICE_EVP_HIP_RES_LEAN", "CICE_EVP_HIP_RES_LOGW", "CICE_EVP_HIP_MARCH_K",
-              "CICE_EVP_HIP_FLAGS"):
+    for k in PATH_ENV:
         monkeypatch.delenv(k, raising=False)
     for k, v in env.items():
         monkeypatch.setenv(k, v)

@@ -950,17 +950,38 @@ def test_prep_path_zeroes_diagnostics_where_the_ice_has_gone():
         core.finalize()
 
 
-@pytest.mark.parametrize("name", ["rect_cyc_2x2_full", "pop_cyc_3x2pad_caps", "pop_cyc_2x2_seabed", "trip_cyc_2x2_full"])
-def test_run_with_page_locked_arrays_and_resident_stresses(name):
+def entry_rows(names):
+    """(fixture, path) of the per-call entry tests: the library's own choice (the tests' first form) and every host of the loop
+    (tests/evp_call_chain.py: PATHS), on a tripole fixture the marched zone beside its fold band too."""
+    import evp_call_chain as cc
+    return [pytest.param(n, p, id=(n if p == "default" else None)) for n in names
+            for p in ["default"] + cc.LOOP_PATHS + (cc.FOLD_PATHS if n.startswith("trip") else [])]
+
+
+def check_post_from_resident_state(core, c, icall, what):
+    """deformations / dyn_finish on what the per-call entry left on the device (cice_evp_hip_run downloads; the state stays)."""
+    got = core.deformations()
+    z = np.zeros(core.shape)
+    got.update(core.dyn_finish(z, z))
+    assert_bitwise(got, {k: c.d[f"o{icall:02d}n{c.ndte:04d}_{k}"] for k in got}, f"{what}: deformations / dyn_finish from the resident state")
+
+
+@pytest.mark.parametrize("name,path", entry_rows(["rect_cyc_2x2_full", "pop_cyc_3x2pad_caps", "pop_cyc_2x2_seabed", "trip_cyc_2x2_full"]))
+def test_run_with_page_locked_arrays_and_resident_stresses(name, path, monkeypatch):
     """The per-call path CICE would use: the caller's arrays page-locked once (cice_evp_hip_pin_host -> mapped, so
     the 20 + 6 field transfers of a call are ONE gather and ONE scatter launch) and the 12 stresses resident on the
     device between calls (CICE_EVP_HIP_OPT_STRESS_RESIDENT): the second call is handed NaN in the stress arrays --
     they must be neither read nor written -- and still returns the reference's second call; the stresses fetched
-    afterwards are the reference's too (tripole: after the device-side symmetrisation)."""
+    afterwards are the reference's too (tripole: after the device-side symmetrisation).  On the path the library picks
+    ("default") and behind every host of the loop, each with the evidence that it ran; after call 2 the post-loop calls
+    run from the state the entry left on the device."""
+    import evp_call_chain as cc
+    cc.set_path(monkeypatch, path)
     c = GoldenCase(name)
     core = hip_from_case(c, strict=True)
     try:
         core.set_option(evp.OPT_STRESS_RESIDENT, 1)
+        core.set_post_geometry(c.d["dxU"], c.d["dyU"], c.d["tarear"])
         work = {k: np.zeros(core.shape) for k in evp.FIELDS}
         core.pin_host(*work.values())
         nonsig = [k for k in evp.OUTPUTS if k not in SIG]
@@ -972,40 +993,49 @@ def test_run_with_page_locked_arrays_and_resident_stresses(name):
                 for k in SIG:
                     work[k][...] = np.nan
             core.run_inplace(work, np.ascontiguousarray(tm, np.int32), np.ascontiguousarray(um, np.int32), c.ndte)
+            cc.assert_path_ran(core, path, c.ndte, cc.is_fold(c.ns), cc.fixture_lean(c, icall), f"{name} call {icall} on {path}")
             if c.ns == "tripole":
                 core.stress_halo()
             want = c.expected(icall, c.ndte)
-            assert_bitwise({k: work[k] for k in nonsig}, {k: want[k] for k in nonsig}, f"{name} call {icall}: pinned + resident")
+            assert_bitwise({k: work[k] for k in nonsig}, {k: want[k] for k in nonsig}, f"{name} call {icall} on {path}: pinned + resident")
             if icall == 2:
                 assert all(np.isnan(work[k]).all() for k in SIG), "resident stresses: the host arrays must stay untouched"
+        check_post_from_resident_state(core, c, 2, f"{name} on {path}")
         got = core.fetch_stresses()
-        assert_bitwise(got, {k: want[k] for k in SIG}, f"{name}: stresses fetched after call 2")
+        assert_bitwise(got, {k: want[k] for k in SIG}, f"{name} on {path}: stresses fetched after call 2")
         # back to copy-in / copy-out: same answer again from call-2 inputs
         core.set_option(evp.OPT_STRESS_RESIDENT, 0)
         dyn, tm, um = c.inputs(2)
         for k in evp.FIELDS:
             work[k][...] = dyn[k]
         core.run_inplace(work, np.ascontiguousarray(tm, np.int32), np.ascontiguousarray(um, np.int32), c.ndte)
+        cc.assert_path_ran(core, path, c.ndte, cc.is_fold(c.ns), cc.fixture_lean(c, 2), f"{name} on {path}, copy-in / copy-out")
         out = post_evp(c, {k: work[k] for k in evp.OUTPUTS})
-        assert_bitwise(out, want, f"{name}: pinned, copy-in/copy-out")
+        assert_bitwise(out, want, f"{name} on {path}: pinned, copy-in/copy-out")
     finally:
         core.finalize()
 
 
-@pytest.mark.parametrize("name", ["rect_cyc_2x2_full", "pop_cyc_3x2pad_caps", "trip_cyc_2x2_full"])
-def test_resident_stresses_survive_a_replayed_call(name, monkeypatch):
+@pytest.mark.parametrize("name,path", [r for r in entry_rows(["rect_cyc_2x2_full", "pop_cyc_3x2pad_caps", "trip_cyc_2x2_full"])
+                                       if r.values[1] == "default" or r.values[1].startswith("resident")])
+def test_resident_stresses_survive_a_replayed_call(name, path, monkeypatch):
     """A call of the on-chip resident kernel that gives up (GPU shared with something else) is repeated with the
     streaming kernel.  With the 12 stresses resident on the device the host has no copy of the pre-call stresses and
     the resident kernel has already overwritten the device copy: the library keeps a snapshot and replays from it.
     The failure is injected AFTER the resident kernel has completed call 2 (CICE_EVP_HIP_FAULT_REPLAY=2), i.e. with
     both ping-pong copies of the stresses overwritten -- the replayed call must still return the reference's call 2,
-    and sig_valid must not have been set by the failed attempt."""
-    monkeypatch.setenv("CICE_EVP_HIP_RESIDENT", "1")
+    and sig_valid must not have been set by the failed attempt.  "default" is the resident kernel asked for and nothing
+    else, the two resident rows add their variant switches (the other hosts have no resident call to fail)."""
+    import evp_call_chain as cc
+    cc.set_path(monkeypatch, path)
+    if path == "default":
+        monkeypatch.setenv("CICE_EVP_HIP_RESIDENT", "1")
     monkeypatch.setenv("CICE_EVP_HIP_FAULT_REPLAY", "2")
     c = GoldenCase(name)
     core = hip_from_case(c, strict=True)
     try:
         core.set_option(evp.OPT_STRESS_RESIDENT, 1)
+        core.set_post_geometry(c.d["dxU"], c.d["dyU"], c.d["tarear"])
         work = {k: np.zeros(core.shape) for k in evp.FIELDS}
         nonsig = [k for k in evp.OUTPUTS if k not in SIG]
         for icall in (1, 2):
@@ -1016,12 +1046,15 @@ def test_resident_stresses_survive_a_replayed_call(name, monkeypatch):
                 for k in SIG:
                     work[k][...] = np.nan
             core.run_inplace(work, np.ascontiguousarray(tm, np.int32), np.ascontiguousarray(um, np.int32), c.ndte)
+            if icall == 1:           # (the replayed call ends in the streaming kernel)
+                cc.assert_path_ran(core, path, c.ndte, cc.is_fold(c.ns), None, f"{name} call {icall} on {path}")
             if c.ns == "tripole":
                 core.stress_halo()
             want = c.expected(icall, c.ndte)
-            assert_bitwise({k: work[k] for k in nonsig}, {k: want[k] for k in nonsig}, f"{name} call {icall}")
+            assert_bitwise({k: work[k] for k in nonsig}, {k: want[k] for k in nonsig}, f"{name} call {icall} on {path}")
         assert core.timings()["resident_fallbacks"] == 1, "the injected failure must have been replayed"
-        assert_bitwise(core.fetch_stresses(), {k: want[k] for k in SIG}, f"{name}: stresses after the replayed call")
+        check_post_from_resident_state(core, c, 2, f"{name} on {path}")
+        assert_bitwise(core.fetch_stresses(), {k: want[k] for k in SIG}, f"{name} on {path}: stresses after the replayed call")
     finally:
         core.finalize()
 

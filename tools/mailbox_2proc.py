@@ -16,6 +16,7 @@ from pathlib import Path
 import numpy as np
 
 ROOT = Path(__file__).resolve().parents[1]
+POST_SENTINEL = (7.0, -3.0)         # --post: what dyn_finish is handed in strocnxU / strocnyU
 sys.path.insert(0, str(ROOT))
 sys.path.insert(0, str(ROOT / "tests"))      # (--forcing: the numpy restatement of the averages, tests/forcing_layout_ref.py)
 
@@ -89,6 +90,11 @@ def main():
                     help="RANK:KIND, KIND = TbU (B grid) or TbN (--cgrid): the default configuration (no seabed stress, water == ocean "
                          "current) with that factor 0.7 on ONE ice cell of RANK next to the cut -- that rank must drop the shortcut, "
                          "every other rank must keep it (the test build's read-out), and the result must still be the one-rank run's")
+    ap.add_argument("--post", action="store_true",
+                    help="B grid: after the loop (and after --stress-halo) every rank runs deformations and dyn_finish on its resident "
+                         "state, dyn_finish with a sentinel in both arrays; compared as bit patterns with the one-rank run on this "
+                         "rank's blocks -- the T-cells of the east / north fringe (ghost cells of the block) included, every cell "
+                         "neither kernel owns exactly 0 / the sentinel")
     a = ap.parse_args()
     import torch
     import torch.distributed as dist
@@ -484,6 +490,11 @@ def main():
                 core.stress_halo()          # evp()'s 12 x ice_HaloUpdate_stress on the resident stresses (any rank layout)
             out = core.download()
             out.update(extra)
+            if a.post:
+                core.set_post_geometry(*[dc.scatter(g[k], r, fill=(1.0 if k != "tarear" else 0.0)) for k in ("dxU", "dyU", "tarear")])
+                out.update({"post_" + k: v for k, v in core.deformations().items()})
+                out.update({"post_" + k: v for k, v in core.dyn_finish(np.full(core.shape, POST_SENTINEL[0]),
+                                                                       np.full(core.shape, POST_SENTINEL[1])).items()})
             out["_march"] = core.march_info()
             out["_path"] = core.describe_path()
             out["_halomask"] = hm
@@ -605,6 +616,40 @@ def main():
                 nb, jj, ii = np.nonzero(w2.view(np.uint64) != h2.view(np.uint64)) if a.all_fields else ((), (), ())
                 first = [(int(q), int(j), int(i), repr(float(w2[q, j, i])), repr(float(h2[q, j, i]))) for q, j, i in list(zip(nb, jj, ii))[:4]]
                 bad.append((k + " ghosts", float(np.abs(w2 - h2).max())) + ((len(jj), first) if a.all_fields else ()))
+    if a.post:
+        bits = lambda x: np.ascontiguousarray(x).view(np.uint64)
+        moved = 0
+        for k in ("divu", "shear", "vort", "rdg_conv", "rdg_shear", "strocnxU", "strocnyU"):
+            want = dcN.scatter(refg("post_" + k), rank)
+            h_all = got["post_" + k]
+            finish = k.startswith("strocn")
+            rest = POST_SENTINEL[0 if k == "strocnxU" else 1] if finish else 0.0
+            for b in dcN.local_blocks(rank):
+                # deformations: dyn_prep2's T list, ilo .. ihi + 1 x jlo .. jhi + 1 -- the fringe cells are ghost cells of this block and
+                # cells of the one-rank run's block (scatter() wraps the cyclic seam); dyn_finish: the block's own U-cells
+                n1 = 0 if finish else 1
+                w = want[b.local][1:1 + b.gny + n1, 1:1 + b.gnx + n1].copy()
+                h = h_all[b.local][1:1 + b.gny + n1, 1:1 + b.gnx + n1]
+                top = b.gj0 + b.gny - 1 == ny
+                if top and not finish and ns_bnd in ("tripole", "tripoleT"):
+                    # the row beyond the fold: the one-rank run's own ghost row (scatter() does not know the fold and leaves 0 there,
+                    # which is right beyond a closed boundary: no ice, nothing written)
+                    cols = (np.arange(b.gi0, b.gi0 + b.gnx + 1) - 1) % nx + 1
+                    w[b.gny, :] = ref["post_" + k][0][ny + 1, cols]
+                if not np.array_equal(bits(w), bits(h)):
+                    jj, ii = np.nonzero(bits(w) != bits(h))
+                    bad.append(("post " + k, b.gid, int(jj.size), (int(jj.min()) + b.gj0, int(jj.max()) + b.gj0, int(ii.min()) + b.gi0, int(ii.max()) + b.gi0),
+                                float(np.abs(w - h).max())))
+                other = np.ones(h_all[b.local].shape, dtype=bool)
+                other[1:1 + b.gny + n1, 1:1 + b.gnx + n1] = False
+                if not (h_all[b.local][other] == rest).all():
+                    bad.append(("post " + k + f": a cell the kernel does not own is not {rest}", b.gid, int((h_all[b.local][other] != rest).sum())))
+                if not finish:
+                    moved += int((h[:, b.gnx] != 0).sum()) + int((h[b.gny, :] != 0).sum())
+                elif (h == rest).all() or not (h == rest).any():
+                    bad.append(("post " + k + ": the sentinel survives everywhere or nowhere inside the block", b.gid))
+        if moved == 0:
+            bad.append(("post: nothing on the fringe cells of this rank's blocks",))
     res = [None] * world
     dist.all_gather_object(res, (rank, bad, t_us, tim["launches_per_subcycle"], tim["tile_variant"]) +
                            ((hex(got["_flags"]),) if a.deviate else ()))
