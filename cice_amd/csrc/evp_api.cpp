@@ -764,6 +764,8 @@ int cice_evp_hip_dyn_finish(double *strocnxU, double *strocnyU)
     evp_launch_dyn_finish(A, S.d.nblocks, S.prm.strict != 0, S.post_out[5], S.post_out[6], S.stream);
     if (d2h(strocnxU, S.post_out[5]) || d2h(strocnyU, S.post_out[6])) return -1;
     HIPC(hipStreamSynchronize(S.stream));
+    S.tail.strocn = true;              // the device copy stays: cice_evp_hip_strocn_t reads it
+    S.tail.strocn_seq = S.upload_seq;
     return 0;
 }
 

@@ -650,3 +650,26 @@ void evp_launch_cgrid_seabed_lkd(const EvpCgPrep &P, int nblocks, const uint8_t 
                                  double alphab, double threshold_hw, hipStream_t st);
 // seabed_stress_factor_prob, C-grid tail (ice_dyn_shared.F90:1656-1676): TbE / TbN = max of Tbt over the two T-cells of a face
 void evp_launch_cgrid_seabed_prob_faces(const EvpCgPrep &P, int nblocks, const uint8_t *mask, const double *Tbt, hipStream_t st);
+
+// After the loop, before transport (evp_tail.hip): the T-point ocean stress (general/ice_step_mod.F90:1012-1041), the C grid's
+// strintxU / strintyU diagnostics (ice_dyn_evp.F90:1436-1443) and principal_stress (ice_dyn_shared.F90:1691-1747).  One thread
+// per cell of the block arrays; the halo updates between the kernels are enqueued by the host.
+struct EvpTail {
+    const int4 *blk;              // per block: ilo, ihi, jlo, jhi (1-based)
+    int nx, ny, nblocks;
+    size_t plane;
+};
+void evp_launch_tail_divide(const EvpTail &G, const double *sx, const double *sy, const double *ai, double *wx, double *wy,
+                            hipStream_t st);
+void evp_launch_tail_u2t_flux(const EvpTail &G, const double *wx, const double *wy, const double *uarea, const double *tarea,
+                              double *ox, double *oy, hipStream_t st);
+// north = 1: out(i,j) from src(i,j), src(i,j+1) ('N': E2US); 0: from src(i,j), src(i+1,j) ('E': N2US)
+void evp_launch_tail_x2ys(const EvpTail &G, const double *src, const double *wght, const double *msk, double *out, int north,
+                          hipStream_t st);
+void evp_launch_tail_principal(size_t n, const double *sp, const double *sm, const double *s12, const double *strength,
+                               double puny, double *sig1, double *sig2, double *sigP, hipStream_t st);
+void evp_launch_tail_zero_cells(double *a, double *b, const int *cells, int n, hipStream_t st);
+// dyn_finish at the C grid's U points: mask bit `bit` = iceUmask; strocnx / strocny inout
+void evp_launch_tail_dyn_finish_u(const EvpTail &G, const uint8_t *mask, unsigned bit, double rhow, double cosw, double sinw,
+                                  const double *Cw, const double *ai, const double *uocn, const double *vocn, const double *fm,
+                                  const double *u, const double *v, double *strocnx, double *strocny, hipStream_t st);

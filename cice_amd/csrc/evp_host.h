@@ -9,6 +9,7 @@
 //   evp_host_mailbox.cpp   mailbox halo over HIP IPC, RCCL bootstrap, probes
 //   evp_host_prep.cpp      preparation phase of evp() (f-2)
 //   evp_host_cgrid.cpp     C-grid subcycle (f-4): state, ghost images, the loop
+//   evp_host_tail.cpp      after the loop: T-point ocean stress, principal stresses (B-grid state)
 //
 // HBM layout: structure-of-arrays; every field is one contiguous fp64 array
 // (nx_block, ny_block, nblocks), i fastest -- the memory image of the CICE
@@ -362,6 +363,15 @@ struct State {
         int direct_asked = -1;         // value of CICE_EVP_HIP_MARCH_DIRECT the decision was taken on (a change re-opens it)
         int call_band_subcycles = 0;   // subcycles the fold band of a tripole grid (L.fold) advanced in the last call
     } march;
+    // after the loop, before transport (evp_tail.hip, evp_host_tail.cpp): ice_grid's uarea / tarea as first handed over, the
+    // pair work1 / work2 of step_dyn_horiz (velocity-buffer length: the exchange's staging slots lie behind the cells), outputs
+    struct Tail {
+        double *uarea = nullptr, *tarea = nullptr;
+        double *work[2] = {nullptr, nullptr};
+        double *out[3] = {nullptr, nullptr, nullptr};
+        bool strocn = false;           // post_out[5], [6] hold the strocnxU / yU cice_evp_hip_dyn_finish made ...
+        unsigned strocn_seq = 0;       // ... for the state of this upload_seq
+    } tail;
     unsigned upload_seq = 0;                       // bumped whenever the caller hands new state / inputs to the device
     int fault_calls = 0;                           // test hook counter (fault_hook, evp_api.cpp)
     bool opt_sig_resident = false;
@@ -464,6 +474,10 @@ int fold_remote_pair(const double *srcA, const double *srcB, double *dstA, doubl
 int fold_seam_ghosts(double *a, double *b);
 void fill_direct(EvpDirect &D, bool masked);
 int halo_uv(int b, bool masked = false);
+// evp_host_tail.cpp: the kernels' view of the block arrays; the unmasked NE-corner vector halo update of a pair of arrays of
+// velocity-buffer length (S.nuv) through the per-subcycle path's lists and transports -- what halo_uv does for S.u / S.v
+void fill_tail(EvpTail &G);
+int halo_pair_unmasked(double *a, double *b);
 bool use_overlap();
 bool use_riding_exchange();
 int get_tile_split(int variant, State::TileSplit **out);

@@ -158,6 +158,12 @@ struct CGridState {
     int t_mfold = 0;             // ... as the marched kernel beside the five phases on the fold band (tripole grids, one rank)
     int t_mfold_ranks = 0;       // ... as "marched zone + fold band + frame" (tripole grids, several ranks)
     double *tarear = nullptr, *post[5] = {};   // deformationsC_T: 1/tarea (static), divu shear vort rdg_conv rdg_shear
+    // after the loop (evp_tail.hip): strintxU strintyU / strocn{x,y}T_iavg; U-point operands of dyn_finish (cdn_ocnU aiU uocnU vocnU
+    // fmU), its strocnxU / yU; work1 / work2 of step_dyn_horiz (exchanged: the length of CG.f)
+    struct Tail {
+        double *out[2] = {}, *uin[5] = {}, *strocn[2] = {}, *work[2] = {};
+        bool strocn_ok = false;                // strocn[] / uin[1] belong to the state the loop last ran on
+    } tail;
     // preparation phase on the device (cice_evp_hip_cgrid_prep)
     struct Prep {
         bool geo = false, pending = false;     // pending: prepared, cice_evp_hip_cgrid_prep_finish not yet called
@@ -1480,6 +1486,7 @@ int finish_upload(int32_t visc_method)
     CG.uploaded = true;
     CG.first = true;
     CG.mf.synced = false;
+    CG.tail.strocn_ok = false;
     return 0;
 }
 }  // namespace evp_host
@@ -1629,6 +1636,141 @@ int cice_evp_hip_cgrid_dyn_finish(double *strocnxN, double *strocnyN, double *st
     for (int k = 0; k < 4; ++k) D.items.push_back({host[k], CG.post[k]});
     if (d2h_batch(D)) return -1;
     HIPC(hipStreamSynchronize(S.stream));
+    return 0;
+}
+
+}  // extern "C"
+
+namespace evp_host {
+// ice_HaloUpdate(a, halo_info, loca, field_type_vector) and the same for b, on two arrays of field_len() doubles: every ghost
+// cell this rank fills itself (the images, unconditionally; 0 next to an eliminated land block), the exchange with the other
+// ranks over the UNMASKED lists -- the reference passes halo_info here, never halo_info_mask (ice_dyn_evp.F90:1437-1440,
+// general/ice_step_mod.F90:1036-1039) --, the fold step of each location.  Ghost cells outside a closed or open boundary keep
+// what they hold, as in ice_HaloUpdate (ice_boundary.F90:1178-1182: no fill there).  Collective wherever the loop's exchanges are.
+static int tail_halo_pair(double *a, int loca, double *b, int locb)
+{
+    EvpCgrid A;
+    fill(A);
+    A.f[CF_UE] = a;      // (the image kernel addresses a field of the table: the pair stands in for two of them)
+    A.f[CF_VN] = b;
+    evp_launch_cgrid_phase(A, 9, CF_UE, S.stream);
+    evp_launch_cgrid_phase(A, 9, CF_VN, S.stream);
+    evp_launch_tail_zero_cells(a, b, CG.zero_cells, CG.n_zero, S.stream);
+    if (fold_exchange()) {
+        if (int rc = cgrid_fold_exchange(a, b, field_len())) return rc;
+    } else if (remote()) {
+        if (int rc = halo_remote_pair(a, b, false)) return rc;
+    }
+    fold({{a, loca, true}, {b, locb, true}});
+    HIPC(hipGetLastError());
+    return 0;
+}
+
+// the loop's final state is there and no resident launch or fold exchange has given up on it
+static int tail_state_ok()
+{
+    if (!CG.uploaded) return fail(-1, "C-grid EVP: nothing uploaded");
+    if (CG.res.launched || (fold_exchange() && S.direct.on)) {
+        HIPC(hipStreamSynchronize(S.stream));
+        if (int rc = res_check_error()) return rc;
+        if (int rc = direct_check_error()) return rc;
+    }
+    return 0;
+}
+}  // namespace evp_host
+
+extern "C" {
+
+// The end of evp() for grid_ice = 'C' (ice_dyn_evp.F90:1436-1443) on the loop's resident final state:
+// (a) ice_HaloUpdate of strintxE (E face, vector) and strintyN (N face, vector) over the plain halo;
+// (b) strintxU = grid_average_X2YS('N', strintxE, earea, epm), strintyU = grid_average_X2YS('E', strintyN, narea, npm)
+//     (E2US / N2US, ice_grid.F90:3997-4004, 4290-4351): 0 everywhere, the quotient on the physical cells whose weights do not sum to 0.
+// The device copies of strintxE / strintyN are the updated ones afterwards.  flags: reserved, 0.
+int cice_evp_hip_cgrid_tail(double *strintxE, double *strintyN, double *strintxU, double *strintyU, int32_t flags)
+{
+    if (int rc = tail_state_ok()) return rc;
+    if (flags != 0) return fail(-1, "cice_evp_hip_cgrid_tail: flags %d (reserved: 0)", (int)flags);
+    for (auto &p : CG.tail.out)
+        if (!p && zeros(p, S.n)) return -1;
+    if (int rc = tail_halo_pair(CG.f[CF_STRX], 2, CG.f[CF_STRY], 3)) return rc;
+    EvpTail G;
+    fill_tail(G);
+    evp_launch_tail_x2ys(G, CG.f[CF_STRX], CG.g[CG_EAREA], CG.g[CG_EPM], CG.tail.out[0], 1, S.stream);
+    evp_launch_tail_x2ys(G, CG.f[CF_STRY], CG.g[CG_NAREA], CG.g[CG_NPM], CG.tail.out[1], 0, S.stream);
+    HIPC(hipGetLastError());
+    CopyBatch D;
+    if (strintxE) D.items.push_back({strintxE, CG.f[CF_STRX]});
+    if (strintyN) D.items.push_back({strintyN, CG.f[CF_STRY]});
+    if (strintxU) D.items.push_back({strintxU, CG.tail.out[0]});
+    if (strintyU) D.items.push_back({strintyU, CG.tail.out[1]});
+    if (d2h_batch(D)) return -1;
+    HIPC(hipStreamSynchronize(S.stream));
+    if (fold_exchange() && S.direct.on)
+        if (int rc = direct_check_error()) return rc;
+    return 0;
+}
+
+// dyn_finish at U points, which evp() runs for grid_ice = 'C' too (ice_dyn_evp.F90:1395-1406; ice_dyn_shared.F90:1291-1365), from
+// the loop's resident final uvel / vvel and iceUmask; the five U-point operands are the host's (the C-grid loop reads none of
+// them): cdn_ocnU aiU uocnU vocnU fmU.  strocnxU / strocnyU inout: written on the ice U-cells only.  The device keeps the
+// result and aiU for cice_evp_hip_cgrid_strocn_t.
+int cice_evp_hip_cgrid_dyn_finish_u(const double *cdn_ocnU, const double *aiU, const double *uocnU, const double *vocnU,
+                                    const double *fmU, double *strocnxU, double *strocnyU)
+{
+    if (int rc = tail_state_ok()) return rc;
+    const double *host[5] = {cdn_ocnU, aiU, uocnU, vocnU, fmU};
+    CGridState::Tail &T = CG.tail;
+    if (!strocnxU || !strocnyU) return fail(-1, "null argument");
+    CopyBatch U;
+    for (int k = 0; k < 5; ++k) {
+        if (!host[k]) return fail(-1, "null argument");
+        if (!T.uin[k] && zeros(T.uin[k], S.n)) return -1;
+        U.items.push_back({T.uin[k], host[k]});
+    }
+    for (auto &p : T.strocn)
+        if (!p && zeros(p, S.n)) return -1;
+    U.items.push_back({T.strocn[0], strocnxU});
+    U.items.push_back({T.strocn[1], strocnyU});
+    if (h2d_batch(U)) return -1;
+    EvpTail G;
+    fill_tail(G);
+    evp_launch_tail_dyn_finish_u(G, CG.mask, 2u, S.prm.rhow, S.prm.cosw, S.prm.sinw, T.uin[0], T.uin[1], T.uin[2], T.uin[3], T.uin[4],
+                                 CG.f[CF_UU], CG.f[CF_VU], T.strocn[0], T.strocn[1], S.stream);
+    HIPC(hipGetLastError());
+    CopyBatch D;
+    D.items.push_back({strocnxU, T.strocn[0]});
+    D.items.push_back({strocnyU, T.strocn[1]});
+    if (d2h_batch(D)) return -1;
+    HIPC(hipStreamSynchronize(S.stream));
+    T.strocn_ok = true;
+    return 0;
+}
+
+// strocn{x,y}T_iavg of step_dyn_horiz (general/ice_step_mod.F90:1012-1041) for grid_ice = 'C', as cice_evp_hip_strocn_t: from the
+// strocnxU / yU and aiU cice_evp_hip_cgrid_dyn_finish_u left on the device, uarea / tarea of cice_evp_hip_cgrid_set_geometry; the
+// NE-corner vector halo update through the loop's exchange of uvel / vvel and its fold step (unmasked).
+int cice_evp_hip_cgrid_strocn_t(double *strocnxT_iavg, double *strocnyT_iavg)
+{
+    if (int rc = tail_state_ok()) return rc;
+    CGridState::Tail &T = CG.tail;
+    if (!T.strocn_ok) return fail(-1, "cice_evp_hip_cgrid_strocn_t: call cice_evp_hip_cgrid_dyn_finish_u first (its strocnxU / strocnyU stay on the device)");
+    for (auto &p : T.work)
+        if (!p && zeros(p, field_len())) return -1;
+    for (auto &p : T.out)
+        if (!p && zeros(p, S.n)) return -1;
+    EvpTail G;
+    fill_tail(G);
+    evp_launch_tail_divide(G, T.strocn[0], T.strocn[1], T.uin[1], T.work[0], T.work[1], S.stream);
+    if (int rc = tail_halo_pair(T.work[0], 1, T.work[1], 1)) return rc;
+    evp_launch_tail_u2t_flux(G, T.work[0], T.work[1], CG.g[CG_UAREA], CG.g[CG_TAREA], T.out[0], T.out[1], S.stream);
+    HIPC(hipGetLastError());
+    CopyBatch D;
+    if (strocnxT_iavg) D.items.push_back({strocnxT_iavg, T.out[0]});
+    if (strocnyT_iavg) D.items.push_back({strocnyT_iavg, T.out[1]});
+    if (d2h_batch(D)) return -1;
+    HIPC(hipStreamSynchronize(S.stream));
+    if (fold_exchange() && S.direct.on)
+        if (int rc = direct_check_error()) return rc;
     return 0;
 }
 

@@ -49,7 +49,9 @@ EXPORTS = [
     "cice_evp_hip_set_forcing_layout",
     "cice_evp_hip_addr", "cice_evp_hip_set_option", "cice_evp_hip_fetch_stresses", "cice_evp_hip_invalidate_stresses",
     "cice_evp_hip_cgrid_set_geometry", "cice_evp_hip_cgrid_run", "cice_evp_hip_cgrid_upload", "cice_evp_hip_cgrid_subcycle",
-    "cice_evp_hip_cgrid_download", "cice_evp_hip_cgrid_sync", "cice_evp_hip_cgrid_deformations", "cice_evp_hip_cgrid_dyn_finish", "cice_evp_hip_cgrid_timings", "cice_evp_hip_stream_probe", 
+    "cice_evp_hip_cgrid_download", "cice_evp_hip_cgrid_sync", "cice_evp_hip_cgrid_deformations", "cice_evp_hip_cgrid_dyn_finish", "cice_evp_hip_cgrid_timings", "cice_evp_hip_stream_probe",
+    "cice_evp_hip_strocn_t", "cice_evp_hip_principal_stress", "cice_evp_hip_cgrid_tail", "cice_evp_hip_cgrid_dyn_finish_u",
+    "cice_evp_hip_cgrid_strocn_t",
 ]
 # libcice_evp_hip_testing.so only (include/cice_evp_hip_testing.h): plan introspection of the CPU tests, read-outs of the tools,
 # the test transport
@@ -623,6 +625,31 @@ class EvpHip:
         _check(self.lib, self.lib.cice_evp_hip_cgrid_dyn_finish(*[_dp(out[k]) for k in keys]), "(dyn_evp_hip_cgrid_dyn_finish)")
         return out
 
+    def cgrid_tail(self) -> dict:
+        """The end of evp() on the C grid from the resident state: strintxE / strintyN after their (unmasked) halo update,
+        and the diagnostics strintxU = E2US(strintxE), strintyU = N2US(strintyN)."""
+        keys = ["strintxE", "strintyN", "strintxU", "strintyU"]
+        out = {k: np.zeros(self.shape) for k in keys}
+        _check(self.lib, self.lib.cice_evp_hip_cgrid_tail(*[_dp(out[k]) for k in keys], C.c_int32(0)), "(dyn_evp_hip_cgrid_tail)")
+        return out
+
+    def cgrid_dyn_finish_u(self, uin: dict, prev: dict | None = None) -> dict:
+        """dyn_finish at U points from the resident uvel / vvel / iceUmask; uin: cdn_ocnU aiU uocnU vocnU fmU (the host's);
+        prev: strocnxU, strocnyU (inout; default zeros)."""
+        a = [self._c(uin[k]) for k in ("cdn_ocnU", "aiU", "uocnU", "vocnU", "fmU")]
+        keys = ["strocnxU", "strocnyU"]
+        out = {k: (np.array(self._c(prev[k]), copy=True) if prev and k in prev else np.zeros(self.shape)) for k in keys}
+        _check(self.lib, self.lib.cice_evp_hip_cgrid_dyn_finish_u(*[_dp(x) for x in a], *[_dp(out[k]) for k in keys]),
+               "(dyn_evp_hip_cgrid_dyn_finish_u)")
+        return out
+
+    def cgrid_strocn_t(self) -> dict:
+        """strocnxT_iavg / strocnyT_iavg of step_dyn_horiz from what cgrid_dyn_finish_u left on the device."""
+        keys = ["strocnxT_iavg", "strocnyT_iavg"]
+        out = {k: np.zeros(self.shape) for k in keys}
+        _check(self.lib, self.lib.cice_evp_hip_cgrid_strocn_t(*[_dp(out[k]) for k in keys]), "(dyn_evp_hip_cgrid_strocn_t)")
+        return out
+
     def cgrid_deformations(self, tarear, prev: dict | None = None) -> dict:
         """deformationsC_T on the resident final state of the C-grid loop; `prev`: the five inout arrays (zeros if absent)."""
         keys = ("divu", "shear", "vort", "rdg_conv", "rdg_shear")
@@ -815,6 +842,25 @@ class EvpHip:
         sy = np.array(self._c(strocnyU), copy=True)
         _check(self.lib, self.lib.cice_evp_hip_dyn_finish(_dp(sx), _dp(sy)), "(dyn_finish)")
         return dict(strocnxU=sx, strocnyU=sy)
+
+    # -- after the loop, before transport -------------------------------------------------
+    def strocn_t(self, uarea=None, tarea=None) -> dict:
+        """strocnxT_iavg / strocnyT_iavg of step_dyn_horiz from the strocnxU / yU dyn_finish left on the device and this
+        call's aiU; uarea, tarea (ice_grid): needed at the first call, None afterwards keeps them."""
+        a = [self._c(x) if x is not None else None for x in (uarea, tarea)]
+        keys = ["strocnxT_iavg", "strocnyT_iavg"]
+        out = {k: np.zeros(self.shape) for k in keys}
+        _check(self.lib, self.lib.cice_evp_hip_strocn_t(*[(_dp(x) if x is not None else None) for x in a], *[_dp(out[k]) for k in keys]),
+               "(dyn_evp_hip_strocn_t)")
+        return out
+
+    def principal_stress(self, puny: float) -> dict:
+        """sig1, sig2, sigP (principal_stress on corner 1) from the stresses and the strength on the device."""
+        keys = ["sig1", "sig2", "sigP"]
+        out = {k: np.zeros(self.shape) for k in keys}
+        _check(self.lib, self.lib.cice_evp_hip_principal_stress(C.c_double(puny), *[_dp(out[k]) for k in keys]),
+               "(dyn_evp_hip_principal_stress)")
+        return out
 
     def debug_cuload(self):
         self._need_testing("debug_cuload")

@@ -33,7 +33,8 @@ module ice_dyn_evp_hip
             dyn_evp_hip_fetch_stresses, dyn_evp_hip_invalidate_stresses, dyn_evp_hip_cgrid_run, &
             dyn_evp_hip_keep_stresses_resident, dyn_evp_hip_cgrid_deformations, dyn_evp_hip_cgrid_dyn_finish, &
             dyn_evp_hip_cgrid_evp_body, &
-            dyn_evp_hip_cgrid_fetch_forcing
+            dyn_evp_hip_cgrid_fetch_forcing, &
+            dyn_evp_hip_cgrid_tail, dyn_evp_hip_cgrid_dyn_finish_u, dyn_evp_hip_strocn_t, dyn_evp_hip_principal_stress
 
   ! mirror of cice_evp_hip_dims (include/cice_evp_hip.h)
   type, bind(C) :: cice_evp_hip_dims
@@ -238,6 +239,37 @@ module ice_dyn_evp_hip
        import :: c_int, c_double
        real(c_double), intent(inout) :: strocnxN(*), strocnyN(*), strocnxE(*), strocnyE(*)
      end function cice_evp_hip_cgrid_dyn_finish
+
+     ! after the loop, before transport (include/cice_evp_hip.h)
+     integer(c_int) function cice_evp_hip_cgrid_tail(strintxE, strintyN, strintxU, strintyU, flags) &
+          bind(C, name='cice_evp_hip_cgrid_tail')
+       import :: c_int, c_int32_t, c_double
+       real(c_double), intent(inout) :: strintxE(*), strintyN(*), strintxU(*), strintyU(*)
+       integer(c_int32_t), value :: flags
+     end function cice_evp_hip_cgrid_tail
+     integer(c_int) function cice_evp_hip_cgrid_dyn_finish_u(cdn_ocnU, aiU, uocnU, vocnU, fmU, strocnxU, strocnyU) &
+          bind(C, name='cice_evp_hip_cgrid_dyn_finish_u')
+       import :: c_int, c_double
+       real(c_double), intent(in) :: cdn_ocnU(*), aiU(*), uocnU(*), vocnU(*), fmU(*)
+       real(c_double), intent(inout) :: strocnxU(*), strocnyU(*)
+     end function cice_evp_hip_cgrid_dyn_finish_u
+     integer(c_int) function cice_evp_hip_cgrid_strocn_t(strocnxT_iavg, strocnyT_iavg) &
+          bind(C, name='cice_evp_hip_cgrid_strocn_t')
+       import :: c_int, c_double
+       real(c_double), intent(inout) :: strocnxT_iavg(*), strocnyT_iavg(*)
+     end function cice_evp_hip_cgrid_strocn_t
+     integer(c_int) function cice_evp_hip_strocn_t(uarea, tarea, strocnxT_iavg, strocnyT_iavg) &
+          bind(C, name='cice_evp_hip_strocn_t')
+       import :: c_int, c_double
+       real(c_double), intent(in) :: uarea(*), tarea(*)
+       real(c_double), intent(inout) :: strocnxT_iavg(*), strocnyT_iavg(*)
+     end function cice_evp_hip_strocn_t
+     integer(c_int) function cice_evp_hip_principal_stress(puny, sig1, sig2, sigP) &
+          bind(C, name='cice_evp_hip_principal_stress')
+       import :: c_int, c_double
+       real(c_double), value :: puny
+       real(c_double), intent(inout) :: sig1(*), sig2(*), sigP(*)
+     end function cice_evp_hip_principal_stress
 
      integer(c_int) function cice_evp_hip_describe_path(buf, n) bind(C, name='cice_evp_hip_describe_path')
        import :: c_int, c_int32_t, c_char
@@ -1113,6 +1145,63 @@ contains
     if (empty_rank) return
     call check(cice_evp_hip_cgrid_dyn_finish(strocnxN, strocnyN, strocnxE, strocnyE), subname, __FILE__, __LINE__)
   end subroutine dyn_evp_hip_cgrid_dyn_finish
+
+  ! The end of evp() for grid_ice = 'C' (ice_dyn_evp.F90:1436-1443) on the device: the halo updates of strintxE / strintyN over
+  ! the plain halo_info and the diagnostics strintxU = E2US(strintxE), strintyU = N2US(strintyN).  Collective.  A host that
+  ! calls this drops its own two ice_HaloUpdate calls and the two grid_average_X2Y calls after the loop.
+  ! (The three wrappers below and this one are compile-checked only: no harness of this repository runs them.)
+  subroutine dyn_evp_hip_cgrid_tail
+    use ice_flux, only: strintxE, strintyN, strintxU, strintyU
+    character(len=*), parameter :: subname = '(dyn_evp_hip_cgrid_tail)'
+    if (.not. initialised) call abort_ice(subname//' ERROR: dyn_evp_hip_init not called', file=__FILE__, line=__LINE__)
+    if (empty_rank) return
+    call check(cice_evp_hip_cgrid_tail(strintxE, strintyN, strintxU, strintyU, 0_c_int32_t), subname, __FILE__, __LINE__)
+  end subroutine dyn_evp_hip_cgrid_tail
+
+  ! dyn_finish at U points on the C grid (ice_dyn_evp.F90:1395-1406) from the device's final uvel / vvel; cdn_ocnU, uocnU, vocnU
+  ! are ice_dyn_evp's own arrays (handed in, as in dyn_evp_hip_cgrid_fetch_forcing).  The device keeps strocnxU / strocnyU and aiU
+  ! for dyn_evp_hip_strocn_t.
+  subroutine dyn_evp_hip_cgrid_dyn_finish_u(cdn_ocnU, uocnU, vocnU)
+    use ice_state, only: aiU
+    use ice_flux, only: fmU, strocnxU, strocnyU
+    real(kind=dbl_kind), dimension(:,:,:), intent(in), contiguous :: cdn_ocnU, uocnU, vocnU
+    character(len=*), parameter :: subname = '(dyn_evp_hip_cgrid_dyn_finish_u)'
+    if (.not. initialised) call abort_ice(subname//' ERROR: dyn_evp_hip_init not called', file=__FILE__, line=__LINE__)
+    if (empty_rank) return
+    call check(cice_evp_hip_cgrid_dyn_finish_u(cdn_ocnU, aiU, uocnU, vocnU, fmU, strocnxU, strocnyU), subname, __FILE__, __LINE__)
+  end subroutine dyn_evp_hip_cgrid_dyn_finish_u
+
+  ! The first thing step_dyn_horiz does after evp() (general/ice_step_mod.F90:1012-1041): strocn{x,y}T_iavg from the
+  ! strocn{x,y}U the device's dyn_finish of this call left there (B grid: cice_evp_hip_dyn_finish; cgrid = .true.:
+  ! dyn_evp_hip_cgrid_dyn_finish_u).  Collective (the halo update of work1 / work2 runs over the plain halo).  A host that calls
+  ! this drops the block of step_dyn_horiz between `call evp (dt)` and the transport.
+  subroutine dyn_evp_hip_strocn_t(cgrid)
+    use ice_grid, only: uarea, tarea
+    use ice_flux, only: strocnxT_iavg, strocnyT_iavg
+    logical(kind=log_kind), intent(in) :: cgrid
+    character(len=*), parameter :: subname = '(dyn_evp_hip_strocn_t)'
+    if (.not. initialised) call abort_ice(subname//' ERROR: dyn_evp_hip_init not called', file=__FILE__, line=__LINE__)
+    if (empty_rank) return
+    if (cgrid) then
+       call check(cice_evp_hip_cgrid_strocn_t(strocnxT_iavg, strocnyT_iavg), subname, __FILE__, __LINE__)
+    else
+       call check(cice_evp_hip_strocn_t(uarea, tarea, strocnxT_iavg, strocnyT_iavg), subname, __FILE__, __LINE__)
+    endif
+  end subroutine dyn_evp_hip_strocn_t
+
+  ! principal_stress on corner 1 (ice_history.F90:3802-3811) from the stresses and the strength on the device: with the
+  ! stresses resident (dyn_evp_hip_keep_stresses_resident) the history output needs no dyn_evp_hip_fetch_stresses for it.
+  ! Call it where the device still holds the call's final state: after dyn_evp_hip_run, before the next one.
+  subroutine dyn_evp_hip_principal_stress
+    use ice_flux, only: sig1, sig2, sigP
+    use icepack_intfc, only: icepack_query_parameters
+    real(kind=dbl_kind) :: puny
+    character(len=*), parameter :: subname = '(dyn_evp_hip_principal_stress)'
+    if (.not. initialised) call abort_ice(subname//' ERROR: dyn_evp_hip_init not called', file=__FILE__, line=__LINE__)
+    if (empty_rank) return
+    call icepack_query_parameters(puny_out=puny)
+    call check(cice_evp_hip_principal_stress(puny, sig1, sig2, sigP), subname, __FILE__, __LINE__)
+  end subroutine dyn_evp_hip_principal_stress
 
 !-----------------------------------------------------------------------
 ! The one place that decides whether the stresses stay on the device (dyn_evp_hip_init and

@@ -205,6 +205,31 @@ int cice_evp_hip_deformations(double *divu, double *shear, double *vort, double 
                               double *rdg_shear);
 int cice_evp_hip_dyn_finish(double *strocnxU, double *strocnyU);
 
+/* ---- after the loop, before transport: what the host otherwise does on full arrays between "last subcycle done" and
+ * "transport may start" (kernels: cice_amd/csrc/evp_tail.hip; compiled without FMA contraction in either build mode, as the
+ * preparation phase: bit-identical to the reference whichever build ran the loop) -------------------------------------------
+ * cice_evp_hip_strocn_t: the first thing step_dyn_horiz does after evp() returns (general/ice_step_mod.F90:1012-1041):
+ *   work = strocn{x,y}U / aiU where aiU /= 0 on ilo..ihi x jlo..jhi, else 0;
+ *   ice_HaloUpdate(work, halo_info, field_loc_NEcorner, field_type_vector): the loop's velocity halo -- its lists and transports,
+ *     tripole fold with the top-row averaging -- NEVER masked, whatever cice_evp_hip_halo_mask was given; collective wherever the
+ *     loop's exchange is.  Ghost cells next to an eliminated land block get the fill value 0; ghost cells outside a closed or
+ *     open boundary keep the 0 the work arrays start with (ice_HaloUpdate does not touch them, ice_boundary.F90:1178-1182);
+ *   strocn{x,y}T_iavg = grid_average_X2YF('SW', work, uarea, tarea) (ice_grid.F90:4640, 4665-4683): 0 everywhere, then on the
+ *     physical cells p25 * (w(i,j)*ua(i,j) + w(i-1,j)*ua(i-1,j) + w(i,j-1)*ua(i,j-1) + w(i-1,j-1)*ua(i-1,j-1)) / tarea(i,j).
+ * Operands: the strocnxU / strocnyU that cice_evp_hip_dyn_finish of THIS call left on the device and this call's aiU; calling
+ * it without that dyn_finish is an error.  dyn_finish's arrays are inout: off the ice U-cells the device copy holds what the
+ * caller passed in, which is the +0 dyn_prep2 stores on every physical cell without ice (ice_dyn_shared.F90:776-784) -- so the
+ * quotient is formed from the same numbers as on the host, on every cell.  uarea, tarea (ice_grid): taken at the first call,
+ * NULL afterwards keeps them.  Outputs: whole blocks; a pointer may be NULL.
+ * cice_evp_hip_principal_stress (ice_dyn_shared.F90:1691-1747; called by ice_history.F90:3802-3811 on corner 1): sig1, sig2,
+ * sigP from stressp_1, stressm_1, stress12_1 and the strength as they are on the device, on every cell of every block array
+ * (ghost cells included: the reference loops over 1..nx_block x 1..ny_block); where strength <= puny the three take spval_dbl
+ * = 1.0e30 (ice_constants.F90:27).  Call it between the loop and cice_evp_hip_download, on tripole grids after
+ * cice_evp_hip_stress_halo.  With CICE_EVP_HIP_OPT_STRESS_RESIDENT the history output then needs no cice_evp_hip_fetch_stresses:
+ * three arrays come back instead of twelve.                                                                               */
+int cice_evp_hip_strocn_t(const double *uarea, const double *tarea, double *strocnxT_iavg, double *strocnyT_iavg);
+int cice_evp_hip_principal_stress(double puny, double *sig1, double *sig2, double *sigP);
+
 /* ---- next tier: the preparation phase of evp() on the device ---------------
  * Everything evp() does between its entry and the subcycle loop on the B grid
  * (ice_dyn_evp.F90:383-840): dyn_prep1 (ice_dyn_shared.F90:496-576), the ice_HaloUpdate calls on
@@ -354,6 +379,28 @@ int cice_evp_hip_cgrid_deformations(const double *tarear, double *divu, double *
  * the device, from the loop's resident final face velocities and the per-call operands it already holds: strocnxN, strocnyN,
  * strocnxE, strocnyE (ice_flux arrays, inout: written on the cells of dyn_prep2's N / E lists only).                       */
 int cice_evp_hip_cgrid_dyn_finish(double *strocnxN, double *strocnyN, double *strocnxE, double *strocnyE);
+/* The end of evp() for grid_ice = 'C' (ice_dyn_evp.F90:1436-1443), after cice_evp_hip_cgrid_subcycle / _run, on the device state
+ * the loop left:
+ *  (a) ice_HaloUpdate of strintxE (E face, vector) and strintyN (N face, vector) over the plain halo_info: every ghost cell
+ *      ice_HaloUpdate writes is written -- images inside the rank unconditionally, cells of other ranks through the loop's exchange
+ *      with the UNMASKED lists (a halo mask handed over for the loop is not used), 0 next to an eliminated land block, the
+ *      tripole / tripoleT fold with sign -1 and the rule of each location.  Ghost cells outside a closed or open boundary keep
+ *      what the caller's arrays held at upload (ice_HaloUpdate leaves them alone, ice_boundary.F90:1178-1182; 0 in a model run);
+ *  (b) strintxU = grid_average_X2YS('N', strintxE, earea, epm), strintyU = grid_average_X2YS('E', strintyN, narea, npm)
+ *      (ice_grid.F90:3997-4004, 4290-4351): 0 everywhere, then the quotient on ilo..ihi x jlo..jhi where the weights do not sum to 0.
+ * Every rank layout the loop accepts; fold rows cut in x go through the fold exchange; collective wherever the loop's exchanges
+ * are.  The four arrays come back whole (a pointer may be NULL); the device copies of strintxE / strintyN are the updated ones, so
+ * cice_evp_hip_cgrid_download afterwards returns the same arrays.  flags: reserved, 0.
+ * cice_evp_hip_cgrid_dyn_finish_u: dyn_finish at U points, which evp() runs for grid_ice = 'C' too (ice_dyn_evp.F90:1395-1406), from
+ * the loop's final uvel / vvel and iceUmask; cdn_ocnU, aiU, uocnU, vocnU, fmU are the host's (the C-grid loop holds no U-point
+ * operand); strocnxU / strocnyU inout, written on the ice U-cells.  The device keeps the result and aiU.
+ * cice_evp_hip_cgrid_strocn_t: cice_evp_hip_strocn_t (above) for grid_ice = 'C', from what cice_evp_hip_cgrid_dyn_finish_u of this
+ * call left on the device, uarea / tarea of cice_evp_hip_cgrid_set_geometry, the halo update through the loop's exchange of
+ * uvel / vvel and the NE-corner fold step.                                                                                */
+int cice_evp_hip_cgrid_tail(double *strintxE, double *strintyN, double *strintxU, double *strintyU, int32_t flags);
+int cice_evp_hip_cgrid_dyn_finish_u(const double *cdn_ocnU, const double *aiU, const double *uocnU, const double *vocnU,
+                                    const double *fmU, double *strocnxU, double *strocnyU);
+int cice_evp_hip_cgrid_strocn_t(double *strocnxT_iavg, double *strocnyT_iavg);
 /* out[0] = ms of the last cgrid_subcycle (HIP events), out[1] = its ndte, [2] (n >= 3) = device ms of the last cgrid_prep,
  * [3] (n >= 4) = how many of those subcycles ran as one launch each (the default schedule on one rank without a fold),
  * [4] (n >= 5) = 1 if that kernel derives 15 of the 23 static arrays from the eight dx / dy arrays (allowed when

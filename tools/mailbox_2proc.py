@@ -21,6 +21,119 @@ sys.path.insert(0, str(ROOT))
 sys.path.insert(0, str(ROOT / "tests"))      # (--forcing: the numpy restatement of the averages, tests/forcing_layout_ref.py)
 
 
+TAIL_PUNY = 1.0e-11
+
+
+def tail_mode(a, dist, rank, world, nx, ny, ns_bnd, g, st, scal):
+    """--tail: every rank runs the loop, dyn_finish and the calls after the loop (B grid: principal_stress, strocn_t; --cgrid:
+    cgrid_tail, cgrid_dyn_finish_u, cgrid_strocn_t); every output array of every rank, whole blocks, is compared bit for bit with
+    the one-rank run of the same state cut into the same blocks."""
+    from cice_amd import decomp, evp, synth
+    shape = tuple(int(v) for v in a.shape.split("x")) if a.shape else None
+    dcN = decomp.per_rank_blocks(nx, ny, world, "cyclic", ns_bnd, proc_shape=shape)
+    if a.blocks_per_rank:
+        sx, sy = (int(v) for v in a.blocks_per_rank.split("x"))
+        dcN = decomp.Decomp(nx, ny, -(-dcN.block_size_x // sx), -(-dcN.block_size_y // sy), "cyclic", ns_bnd, world, dcN.proc_shape)
+    dc1 = decomp.Decomp(nx, ny, dcN.block_size_x, dcN.block_size_y, "cyclic", ns_bnd, 1)
+    fold = ns_bnd in ("tripole", "tripoleT")
+    rng = np.random.default_rng(41)
+    uin_g = dict(cdn_ocnU=np.full((ny, nx), 0.00536), aiU=np.where(rng.uniform(size=(ny, nx)) < 0.2, 0.0, rng.uniform(0.2, 1.0, (ny, nx))),
+                 uocnU=rng.uniform(-0.1, 0.1, (ny, nx)), vocnU=rng.uniform(-0.1, 0.1, (ny, nx)), fmU=rng.uniform(-20.0, 20.0, (ny, nx)))
+
+    def bootstrap(core, exchange):
+        if exchange:
+            blobs = [None] * world
+            dist.all_gather_object(blobs, core.halo_export())
+            core.halo_import(blobs)
+
+    def run_b(dc, r, exchange):
+        stt = dict(st)
+        if ns_bnd == "tripoleT":        # velocities as a halo update leaves them: the top row is the fold's image
+            for k in ("uvel", "vvel", "uvel_init", "vvel_init"):
+                stt[k] = np.array(stt[k], dtype=np.float64, copy=True)
+                stt[k][ny - 1, :] = -stt[k][ny - 2, ::-1]
+        geo = {k: dc.scatter(g[k], r, fill=(1.0 if k != "uarear" else 0.0)) for k in ("HTE", "HTN", "dxT", "dyT", "tarea", "uarear", "uarea")}
+        fields = {k: dc.scatter(stt[k], r) for k in evp.FIELDS}
+        tm, um = dc.scatter(stt["iceTmask"], r, fill=0), dc.scatter(stt["iceUmask"], r, fill=0)
+        d, keep = evp.make_dims(dc, r)
+        core = evp.EvpHip(d, evp.make_params(scal, strict=True), geo["HTE"], geo["HTN"], geo["dxT"], geo["dyT"], geo["uarear"], geo["tarea"],
+                          keepalive=keep)
+        try:
+            bootstrap(core, exchange)
+            if exchange and a.maskhalo:
+                tmg = np.asarray(stt["iceTmask"]) != 0
+                hmg = tmg | np.roll(tmg, 1, 1) | np.roll(tmg, -1, 1)
+                hmg[1:] |= tmg[:-1]
+                hmg[:-1] |= tmg[1:]
+                core.halo_mask(dc.scatter(hmg.astype(np.int32), r, fill=0))
+            core.upload(fields, tm, um)
+            core.subcycle(a.ndte)
+            if fold:
+                core.stress_halo()
+            out = core.principal_stress(TAIL_PUNY)
+            z = np.zeros(core.shape)
+            out.update(core.dyn_finish(z, z))
+            out.update(core.strocn_t(geo["uarea"], geo["tarea"]))
+            return out, core.timings()
+        finally:
+            core.finalize()
+
+    def run_c(dc, r, exchange):
+        cg = synth.cgrid_geometry(g)
+        state, inputs, masks = synth.cgrid_state(g, cg, case=a.case, seed=7, warm=True, seabed=True)
+        tmg = np.asarray(masks["iceTmask"]) != 0
+        static, state, inputs, masks = synth.cgrid_scatter(dc, r, cg, state, inputs, masks)
+        d, keep = evp.make_dims(dc, r)
+        core = evp.EvpHip(d, evp.make_params(scal, strict=True), static["dyE"], static["dxN"], static["dxT"], static["dyT"], 1.0 / static["uarea"],
+                          static["tarea"], keepalive=keep)
+        try:
+            bootstrap(core, exchange)
+            if exchange and a.maskhalo:
+                hmg = tmg | np.roll(tmg, 1, 1) | np.roll(tmg, -1, 1)
+                hmg[1:] |= tmg[:-1]
+                hmg[:-1] |= tmg[1:]
+                core.halo_mask(dc.scatter(hmg.astype(np.int32), r, fill=0))
+            core.cgrid_set_geometry(static)
+            core.cgrid_upload(state, inputs, masks, visc_method=a.visc)
+            core.cgrid_subcycle(a.ndte)
+            out = core.cgrid_tail()
+            out.update(core.cgrid_dyn_finish_u({k: dc.scatter(v, r) for k, v in uin_g.items()}))
+            out.update(core.cgrid_strocn_t())
+            dl = core.cgrid_download()
+            out["download strintxE"], out["download strintyN"] = dl["strintxE"], dl["strintyN"]
+            return out, core.timings()
+        finally:
+            core.finalize()
+
+    run = run_c if a.cgrid else run_b
+    ref = None
+    for turn in range(world):           # (the one-rank run has the GPU to itself: the processes take turns)
+        if turn == rank:
+            ref, _ = run(dc1, 0, False)
+        dist.barrier()
+    got, tim = run(dcN, rank, True)
+    assert tim["halo_transport"] == "mailbox", tim
+    ref_local = {b.gid: b.local for b in dc1.blocks}
+    bits = lambda x: np.ascontiguousarray(x).view(np.uint64)
+    bad = []
+    for k in sorted(got):
+        if not np.abs(ref[k]).max() > 0:
+            bad.append((k, "all zero in the one-rank run"))
+        for b in dcN.local_blocks(rank):
+            w, h = ref[k][ref_local[b.gid]], got[k][b.local]
+            if not np.array_equal(bits(w), bits(h)):
+                jj, ii = np.nonzero(bits(w) != bits(h))
+                bad.append((k, b.gid, int(jj.size), (int(jj.min()), int(jj.max()), int(ii.min()), int(ii.max())), float(np.nanmax(np.abs(w - h)))))
+    res = [None] * world
+    dist.all_gather_object(res, (rank, bad, sorted(got)))
+    if rank == 0:
+        ok = all(not r[1] for r in res)
+        print("MAILBOX_2PROC", "OK" if ok else "FAIL", "tail", "cgrid" if a.cgrid else "bgrid", a.workload, f"world={world}", res, flush=True)
+        if not ok:
+            sys.exit(1)
+    dist.destroy_process_group()
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--workload", default="gx3")
@@ -95,6 +208,11 @@ def main():
                          "state, dyn_finish with a sentinel in both arrays; compared as bit patterns with the one-rank run on this "
                          "rank's blocks -- the T-cells of the east / north fringe (ghost cells of the block) included, every cell "
                          "neither kernel owns exactly 0 / the sentinel")
+    ap.add_argument("--tail", action="store_true",
+                    help="both grids: after the loop every rank runs dyn_finish and the calls between the loop and transport (B grid: "
+                         "stress_halo on a fold, principal_stress, strocn_t; --cgrid: cgrid_tail, cgrid_dyn_finish_u, cgrid_strocn_t); "
+                         "every output array, whole blocks, is compared as bit patterns with the one-rank run of the same state cut "
+                         "into the same blocks (--same-blocks-ref is implied); --maskhalo hands the loop a masked halo the calls must not use")
     a = ap.parse_args()
     import torch
     import torch.distributed as dist
@@ -126,6 +244,8 @@ def main():
             st[k][ny - 1, :] = -st[k][ny - 2, ::-1]
     pr = synth.make_primary(g, "full", seed=9) if a.prep else None
     scal = synth.evp_scalars(120)
+    if a.tail:
+        return tail_mode(a, dist, rank, world, nx, ny, ns_bnd, g, st, scal)
     own_wind = bool(a.forcing) and a.wind_ghosts == "own"
 
     def deviate_cell(ice):
