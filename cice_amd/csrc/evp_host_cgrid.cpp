@@ -2147,6 +2147,7 @@ int cice_evp_hip_cgrid_timings(double *out, int32_t n)
         out[24] = (double)CG.mf.frame_cells;          // ... the frame cells among the rest cells (sent to another rank, or with a ghost image here)
         out[25] = (CG.t_mfold_ranks > 0 && fold_exchange()) ? 1.0 : 0.0;   // ... 1: with the fold exchange (the fold rows on several ranks)
     }
+    if (n >= 27) out[26] = (double)CG.in_alt;         // bit q: PP_FIELDS[q] is in its second allocation now (where the last call left it)
     return 0;
 }
 

@@ -681,8 +681,8 @@ class EvpHip:
         _check(self.lib, self.lib.cice_evp_hip_cgrid_sync(), "(dyn_evp_hip_cgrid_sync)")
 
     def cgrid_timings(self):
-        out = np.zeros(26)
-        _check(self.lib, self.lib.cice_evp_hip_cgrid_timings(_dp(out), C.c_int32(26)), "(dyn_evp_hip_cgrid_timings)")
+        out = np.zeros(27)
+        _check(self.lib, self.lib.cice_evp_hip_cgrid_timings(_dp(out), C.c_int32(27)), "(dyn_evp_hip_cgrid_timings)")
         return dict(loop_ms=float(out[0]), nsub=int(out[1]), prep_ms=float(out[2]), one_launch_subcycles=int(out[3]),
                     geometry_derived=bool(out[4]), resident_subcycles=int(out[5]), resident_probe_ms=float(out[6]),
                     resident_fallbacks=int(out[7]), resident_windows_with_ice=int(out[8]), resident_windows=int(out[9]),
@@ -691,7 +691,8 @@ class EvpHip:
                     fold_ranks=int(out[16]), fold_staging_slots=int(out[17]),
                     marched_ranks_subcycles=int(out[18]), frame_cells=int(out[19]),
                     marched_fold_subcycles=int(out[20]), fold_band_rows=int(out[21]), fold_rest_cells=int(out[22]),
-                    marched_fold_ranks_subcycles=int(out[23]), fold_frame_cells=int(out[24]), marched_fold_exchange=bool(out[25]))
+                    marched_fold_ranks_subcycles=int(out[23]), fold_frame_cells=int(out[24]), marched_fold_exchange=bool(out[25]),
+                    in_alt=int(out[26]))
 
     def debug_cgres_prof(self):
         self._need_testing("debug_cgres_prof")

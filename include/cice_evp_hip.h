@@ -429,7 +429,10 @@ int cice_evp_hip_cgrid_strocn_t(double *strocnxT_iavg, double *strocnyT_iavg);
  * the same split with the five phases' exchanges at their points, the cells other ranks receive and the cells with ghost images in
  * the rest --, the frame cells among the rest cells of [22], and 1 if the fold exchange of [15] ran inside it (the fold rows cut in
  * x).  [20] stays 0 on several ranks and [23] on one.  Each rank decides for itself (a rank without rectangles keeps the five full
- * phases: every schedule issues the same exchanges at the same points); CICE_EVP_HIP_CGRID_ONE=0 forces the five phases  */
+ * phases: every schedule issues the same exchanges at the same points); CICE_EVP_HIP_CGRID_ONE=0 forces the five phases.
+ * [26] (n >= 27): where the last call left the five arrays the loop keeps in two allocations (uvelE, vvelN, stresspT, stressmT,
+ * stress12U, in that order): bit q set = array q is in its second allocation now.  Every call after the loop -- download,
+ * deformations, dyn_finish, the tail, the next cgrid_prep without a state -- reads them there; a read-out for tests  */
 int cice_evp_hip_cgrid_timings(double *out, int32_t n);
 
 /* ---- multi-GPU: RCCL point-to-point halo over xGMI ---------------------------- */

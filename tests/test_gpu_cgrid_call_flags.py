@@ -11,20 +11,13 @@ import pytest
 import call_flag_cases as cf
 from cice_amd import evp
 from common import assert_bitwise
+from evp_cgrid_call_chain import CG_PATHS, CG_SWITCHES as SWITCHES
 
 pytestmark = pytest.mark.gpu
 
-SWITCHES = ("CICE_EVP_HIP_CGRID_RESIDENT", "CICE_EVP_HIP_CGRID_ONE", "CICE_EVP_HIP_CGRID_FUSED", "CICE_EVP_HIP_CGRID_STRIP",
-            "CICE_EVP_HIP_CGRID_ONE_SHAPE", "CICE_EVP_HIP_CGRID_FAST")
-# schedule -> (environment, 3 x 3 padded blocks or one block)
-PATHS = {
-    "cg_one": ({"CICE_EVP_HIP_CGRID_RESIDENT": "0", "CICE_EVP_HIP_CGRID_STRIP": "0"}, True),
-    "fused, three launches": ({"CICE_EVP_HIP_CGRID_RESIDENT": "0", "CICE_EVP_HIP_CGRID_ONE": "0"}, True),
-    "five phases": ({"CICE_EVP_HIP_CGRID_RESIDENT": "0", "CICE_EVP_HIP_CGRID_FUSED": "0"}, True),
-    "cg_strip": ({"CICE_EVP_HIP_CGRID_RESIDENT": "0", "CICE_EVP_HIP_CGRID_ONE_SHAPE": "2", "CICE_EVP_HIP_CGRID_STRIP": "1"}, False),
-    "cg_res": ({"CICE_EVP_HIP_CGRID_RESIDENT": "1"}, True),
-    "cg_res, one block": ({"CICE_EVP_HIP_CGRID_RESIDENT": "1"}, False),
-}
+# the schedules and their switches: the rows of the one table of C-grid schedules that this file runs (tests/evp_cgrid_call_chain.py:
+# CG_PATHS, as the B-grid file takes its rows from evp_call_chain.PATHS); schedule -> (environment, 3 x 3 padded blocks or one block)
+PATHS = {p: (r.env, r.flags_split) for p, r in CG_PATHS.items() if r.flags_split is not None}
 
 
 def make_core(monkeypatch, env, split):

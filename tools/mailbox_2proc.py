@@ -27,7 +27,9 @@ TAIL_PUNY = 1.0e-11
 def tail_mode(a, dist, rank, world, nx, ny, ns_bnd, g, st, scal):
     """--tail: every rank runs the loop, dyn_finish and the calls after the loop (B grid: principal_stress, strocn_t; --cgrid:
     cgrid_tail, cgrid_dyn_finish_u, cgrid_strocn_t); every output array of every rank, whole blocks, is compared bit for bit with
-    the one-rank run of the same state cut into the same blocks."""
+    the one-rank run of the same state cut into the same blocks.  --cgrid --post: cgrid_deformations and cgrid_dyn_finish (a sentinel in
+    every inout array) ahead of them, or alone; --cgrid --prep: the loop's inputs from cice_evp_hip_cgrid_prep on every rank;
+    --expect-marched / --expect-marched-fold: the evidence that the loop before these calls ran on that schedule."""
     from cice_amd import decomp, evp, synth
     shape = tuple(int(v) for v in a.shape.split("x")) if a.shape else None
     dcN = decomp.per_rank_blocks(nx, ny, world, "cyclic", ns_bnd, proc_shape=shape)
@@ -94,13 +96,33 @@ def tail_mode(a, dist, rank, world, nx, ny, ns_bnd, g, st, scal):
                 hmg[:-1] |= tmg[1:]
                 core.halo_mask(dc.scatter(hmg.astype(np.int32), r, fill=0))
             core.cgrid_set_geometry(static)
-            core.cgrid_upload(state, inputs, masks, visc_method=a.visc)
+            if a.prep:
+                t11, st7, prev = synth.cgrid_prep_inputs(g, cg, case=a.case, seed=17)
+                vec = ("uocn", "vocn", "ss_tltx", "ss_tlty", "strairxT", "strairyT")
+                tb = {k: dc.scatter(v, r, fold=("center", -1.0 if k in vec else 1.0)) for k, v in t11.items()}
+                loc = {"umaskCD": "NEcorner", "emask": "Eface", "nmask": "Nface", "fcor_blk": "NEcorner", "fcorE_blk": "Eface", "fcorN_blk": "Nface"}
+                static.update({k: dc.scatter(v, r, fill=0, fold=(loc.get(k, "center"), 1.0)) for k, v in st7.items()})
+                core.cgrid_set_prep_geometry(static)
+                core.cgrid_prep(evp.PrepParams(dt=3600.0, rhoi=917.0, rhos=330.0, gravit=9.80616, dyn_area_min=1e-11, dyn_mass_min=1e-10,
+                                               ssh_stress_coupled=0), tb, state, {k: dc.scatter(v, r, fill=0) for k, v in prev.items()})
+                core.cgrid_prep_finish(inputs["strength"], a.visc)
+            else:
+                core.cgrid_upload(state, inputs, masks, visc_method=a.visc)
             core.cgrid_subcycle(a.ndte)
-            out = core.cgrid_tail()
-            out.update(core.cgrid_dyn_finish_u({k: dc.scatter(v, r) for k, v in uin_g.items()}))
-            out.update(core.cgrid_strocn_t())
+            out = {"_schedule": (core.cgrid_timings(), core.describe_path())}
+            if a.post:          # every inout array with the sentinel: the cells no kernel owns keep it
+                sent = lambda keys: {k: np.full(core.shape, POST_SENTINEL[0] if "x" in k or k in ("divu", "vort") else POST_SENTINEL[1]) for k in keys}
+                tarear = np.where(static["tarea"] > 0, 1.0 / np.where(static["tarea"] > 0, static["tarea"], 1.0), 0.0)
+                out.update(core.cgrid_deformations(tarear, prev=sent(("divu", "shear", "vort", "rdg_conv", "rdg_shear"))))
+                out.update(core.cgrid_dyn_finish(prev=sent(("strocnxN", "strocnyN", "strocnxE", "strocnyE"))))
+            if a.tail:
+                out.update(core.cgrid_tail())
+                out.update(core.cgrid_dyn_finish_u({k: dc.scatter(v, r) for k, v in uin_g.items()}))
+                out.update(core.cgrid_strocn_t())
             dl = core.cgrid_download()
             out["download strintxE"], out["download strintyN"] = dl["strintxE"], dl["strintyN"]
+            for k in ("uvelE", "vvelN", "stresspT", "stressmT", "stress12U"):       # the five arrays the schedules keep in two allocations
+                out["download " + k] = dl[k]
             return out, core.timings()
         finally:
             core.finalize()
@@ -116,7 +138,7 @@ def tail_mode(a, dist, rank, world, nx, ny, ns_bnd, g, st, scal):
     ref_local = {b.gid: b.local for b in dc1.blocks}
     bits = lambda x: np.ascontiguousarray(x).view(np.uint64)
     bad = []
-    for k in sorted(got):
+    for k in sorted(q for q in got if not q.startswith("_")):
         if not np.abs(ref[k]).max() > 0:
             bad.append((k, "all zero in the one-rank run"))
         for b in dcN.local_blocks(rank):
@@ -124,11 +146,25 @@ def tail_mode(a, dist, rank, world, nx, ny, ns_bnd, g, st, scal):
             if not np.array_equal(bits(w), bits(h)):
                 jj, ii = np.nonzero(bits(w) != bits(h))
                 bad.append((k, b.gid, int(jj.size), (int(jj.min()), int(jj.max()), int(ii.min()), int(ii.max())), float(np.nanmax(np.abs(w - h)))))
+    zoned = 0
+    if a.cgrid and (a.expect_marched or a.expect_marched_fold):
+        # every rank with rectangles ran every subcycle of the call but the first after an upload on the schedule, and says so
+        cgt, path = got["_schedule"]
+        zoned = 1 if cgt["marched_items"] > 0 else 0
+        if a.expect_marched:
+            ran = cgt["marched_ranks_subcycles"] == a.ndte - 1 and cgt["frame_cells"] > 0 and "zone marched + frame" in path
+        else:
+            ran = cgt["marched_fold_ranks_subcycles"] == a.ndte - 1 and cgt["fold_frame_cells"] > 0 and "marched zone + fold band + frame" in path
+        if zoned and not ran:
+            bad.append(("the loop before the calls did not run on the schedule asked for", cgt, path))
     res = [None] * world
-    dist.all_gather_object(res, (rank, bad, sorted(got)))
+    dist.all_gather_object(res, (rank, bad, sorted(q for q in got if not q.startswith("_")), zoned,
+                                 got["_schedule"][1] if a.cgrid else "", got["_schedule"][0]["in_alt"] if a.cgrid else 0))
     if rank == 0:
         ok = all(not r[1] for r in res)
-        print("MAILBOX_2PROC", "OK" if ok else "FAIL", "tail", "cgrid" if a.cgrid else "bgrid", a.workload, f"world={world}", res, flush=True)
+        if a.expect_marched or a.expect_marched_fold:
+            ok = ok and any(r[3] for r in res)
+        print("MAILBOX_2PROC", "OK" if ok else "FAIL", "tail" if a.tail else "post", "cgrid" if a.cgrid else "bgrid", a.workload, f"world={world}", res, flush=True)
         if not ok:
             sys.exit(1)
     dist.destroy_process_group()
@@ -204,7 +240,10 @@ def main():
                          "current) with that factor 0.7 on ONE ice cell of RANK next to the cut -- that rank must drop the shortcut, "
                          "every other rank must keep it (the test build's read-out), and the result must still be the one-rank run's")
     ap.add_argument("--post", action="store_true",
-                    help="B grid: after the loop (and after --stress-halo) every rank runs deformations and dyn_finish on its resident "
+                    help="--cgrid: after the loop every rank runs cgrid_deformations and cgrid_dyn_finish on its resident state, a sentinel in "
+                         "every inout array; whole blocks are compared as bit patterns with the one-rank run cut into the same blocks (alone or "
+                         "ahead of --tail's calls; with --prep the loop's inputs come from cgrid_prep; --expect-marched / --expect-marched-fold "
+                         "ask for the schedule of the loop before them).  B grid: after the loop (and after --stress-halo) every rank runs deformations and dyn_finish on its resident "
                          "state, dyn_finish with a sentinel in both arrays; compared as bit patterns with the one-rank run on this "
                          "rank's blocks -- the T-cells of the east / north fringe (ghost cells of the block) included, every cell "
                          "neither kernel owns exactly 0 / the sentinel")
@@ -214,6 +253,8 @@ def main():
                          "every output array, whole blocks, is compared as bit patterns with the one-rank run of the same state cut "
                          "into the same blocks (--same-blocks-ref is implied); --maskhalo hands the loop a masked halo the calls must not use")
     a = ap.parse_args()
+    if (a.expect_marched or a.expect_marched_fold) and not a.cgrid:
+        ap.error("--expect-marched / --expect-marched-fold name C-grid schedules: give --cgrid")
     import torch
     import torch.distributed as dist
     from cice_amd import decomp, evp, synth
@@ -244,7 +285,7 @@ def main():
             st[k][ny - 1, :] = -st[k][ny - 2, ::-1]
     pr = synth.make_primary(g, "full", seed=9) if a.prep else None
     scal = synth.evp_scalars(120)
-    if a.tail:
+    if a.tail or (a.post and a.cgrid):
         return tail_mode(a, dist, rank, world, nx, ny, ns_bnd, g, st, scal)
     own_wind = bool(a.forcing) and a.wind_ghosts == "own"
 
