@@ -605,7 +605,7 @@ int cice_evp_hip_subcycle(int32_t ndte)
     HIPC(hipEventRecord(S.ev0, S.stream));
     // (the tiles that hold ice must all be on the chip at once: checked against THIS call's masks -- a call with more ice than that
     // goes through the kernels below, the next one is asked again)
-    S.res_ran = S.res_mode == 1 && resident2_fits_now();
+    S.res_ran = S.res_mode == 1 && !resident_declined_switch() && resident2_fits_now();
     if (S.res_ran) {
         if (int rc = launch_resident2(ndte, S.cur, false)) return rc;
         S.res_launched = true;
@@ -914,8 +914,8 @@ int cice_evp_hip_run(double *stressp_1, double *stressp_2, double *stressp_3, do
     // The resident kernel assumes the GPU to itself.  If that did not hold (another process or a long kernel on the
     // device: a wait gave up) the call is repeated with the streaming kernel, which is then kept.  Without resident
     // stresses nothing has been written back yet and the caller's inputs are intact.  With them (keep_sig) the only
-    // copy of the pre-call stresses is sig[cur], which the resident kernel overwrites at its end (both ping-pong
-    // copies): keep a device snapshot for the replay.
+    // copy of the pre-call stresses is sig[cur], which the resident kernel overwrites at its end when ndte is even (it
+    // stores into sig[cur ^ (ndte & 1)]; the general variants into both ping-pong copies): keep a device snapshot for the replay.
     const bool may_replay = S.res_mode == 1 && S.plan.peers.empty();
     const int cur0 = S.cur;
     if (may_replay && keep_sig) {
@@ -1054,6 +1054,18 @@ int cice_evp_hip_debug_cuload(int32_t *out, int32_t n)
     if (!out || n < 0 || n > 2048 * 8) return fail(-1, "bad argument");
     HIPC(hipStreamSynchronize(S.stream));
     HIPC(hipMemcpy(out, S.res2_cuload, (size_t)n * sizeof(int32_t), hipMemcpyDeviceToHost));
+    // the rim-wave schedule keeps a CU's record as one word behind these (evp_resident2.hip, EVP_RES2_LOCK_CAS): where that word
+    // is the last launch's, the record is read out of it, in the same layout
+    std::vector<unsigned long long> words(2048);
+    HIPC(hipMemcpy(words.data(), S.res2_cuload + 2048 * 8, words.size() * sizeof(unsigned long long), hipMemcpyDeviceToHost));
+    for (int cu = 0; cu < 2048 && 8 * cu + 8 <= n; ++cu) {
+        const unsigned long long w = words[(size_t)cu];
+        if ((unsigned)(w >> 40) != S.res2_epoch) continue;
+        int32_t *o = out + 8 * cu;
+        o[0] = 0; o[1] = (int32_t)(S.res2_epoch << 12);
+        for (int q = 0; q < 4; ++q) o[2 + q] = (int32_t)((w >> (8 * q)) & 255u);
+        o[6] = (int32_t)((w >> 32) & 255u); o[7] = 0;
+    }
     return 0;
 }
 
@@ -1064,6 +1076,17 @@ int cice_evp_hip_debug_prof(uint64_t *out, int32_t ntiles_max)
     if (!out || ntiles_max < S.res2_ntiles) return fail(-1, "bad argument: need room for %d tiles", S.res2_ntiles);
     HIPC(hipStreamSynchronize(S.stream));
     HIPC(hipMemcpy(out, S.res2_prof, (size_t)S.res2_ntiles * 32 * sizeof(uint64_t), hipMemcpyDeviceToHost));
+    return S.res2_ntiles > 0 ? 0 : -1;
+}
+
+// Launch stamps of the same launch: [tiles][4 waves][8] x u64 -- 100 MHz wall clock at workgroup start, after the per-CU lock, the
+// lane tables and masks, the state loads, the first ring poll, the loop's end, the write-back's end; [7] = chunk | active chunks << 8.
+int cice_evp_hip_debug_prof_launch(uint64_t *out, int32_t ntiles_max)
+{
+    if (!S.ready || !S.res2_prof) return fail(-1, "no profiled resident launch (CICE_EVP_HIP_RES_PROF=1, 16 x 16 tiles)");
+    if (!out || ntiles_max < S.res2_ntiles) return fail(-1, "bad argument: need room for %d tiles", S.res2_ntiles);
+    HIPC(hipStreamSynchronize(S.stream));
+    HIPC(hipMemcpy(out, S.res2_prof + (size_t)S.res2_ntiles * 32, (size_t)S.res2_ntiles * 32 * sizeof(uint64_t), hipMemcpyDeviceToHost));
     return S.res2_ntiles > 0 ? 0 : -1;
 }
 

@@ -71,7 +71,8 @@ struct EvpResident2 {
     const int4 *ring;          // [ntiles][EVP_RES2_RING]: x record cell, y LDS index, z producing U-cell (-1 none)
     const int *ring_cnt;       // [ntiles]
     void *rec[2];              // [2][ncell] x {u granule, v granule} (2 x 16 bytes), by subcycle parity
-    double *u[2], *v[2];       // plain arrays: input from [cur0], final state to both
+    double *u[2], *v[2];       // plain arrays: input from [cur0]; final state to both, the lean variants (EVP_RES2_WRITE_ONCE) to
+                               // [cur0 ^ (ndte & 1)] only -- the buffer the host names current afterwards
     // pointer table in device memory (keeps 28 pointers out of the kernel's SGPR budget):
     // [0..11] sig buffer 0, [12..23] sig buffer 1, [24..27] strintx strinty taubx tauby
     double *const *tab;
@@ -90,8 +91,10 @@ struct EvpResident2 {
     const uint8_t *late_waves; // [ntiles]
     const uint8_t *nact;       // [ntiles] chunks (64 entries of perm) that hold ice cells: the first nact
     const uint8_t *nlate;      // [ntiles] COOP: rim T-cells with ice = the first nlate entries of perm (<= 64); NULL: the variant is off
-    int *cuload;               // [2048][8] per-CU record of the launch: lock, stamp, ice-holding waves per SIMD
-    unsigned long long *prof;  // NULL, or [ntiles][4 chunks][8]: cycles per phase (tools)
+    int *cuload;               // [2048][8] per-CU record of the launch: lock, stamp, ice-holding waves per SIMD; behind them [2048] x 64 bits:
+                               // the same as one word, epoch << 40 | arrivals << 32 | waves on SIMD 3..0, 8 bits each (EVP_RES2_LOCK_CAS)
+    unsigned long long *prof;  // NULL, or [ntiles][4 chunks][8]: cycles per phase (tools); behind them [ntiles][4 waves][8]: the launch's
+                               // wall-clock stamps (100 MHz): start, after the lock, tables, state loads, first poll, loop end, write-back end
     int dbg;                   // test hooks and A/B switches: EVP_RES2_HOOK_* below
     int par0;                  // which of rec[0/1] holds the records of subcycle index 0 of THIS launch
                                // (flips so that a launch never starts in the buffer the previous one ended in)
@@ -126,9 +129,21 @@ struct EvpResident2 {
 #define EVP_RES2_PRIO_DEFAULT 2
 #endif
 // the rim-wave schedule's full tiles take the identity chunk map without the per-CU lock (the test build carries both,
-// CICE_EVP_HIP_RES_NOLOCK).  Measured: 4 us less per launch, which five bench runs do not tell from their own spread -- off
+// CICE_EVP_HIP_RES_NOLOCK).  Measured: 4 us less per launch (profiles/r16_resident_rim_first.txt, r24_resident_launch_cost.txt)
 #ifndef EVP_RES2_NOLOCK_DEFAULT
-#define EVP_RES2_NOLOCK_DEFAULT 0
+#define EVP_RES2_NOLOCK_DEFAULT 1
+#endif
+// the lean variants store the final stresses and velocities into ONE ping-pong buffer, the one that is current after the call
+// (cur0 ^ (ndte & 1)), as every streaming call leaves them: the other buffer differs on cells the loop writes only, and nobody
+// reads those before writing them (evp_resident2.hip, "write the state back"; the test build carries both, CICE_EVP_HIP_RES_WRITE_ONCE)
+#ifndef EVP_RES2_WRITE_ONCE_DEFAULT
+#define EVP_RES2_WRITE_ONCE_DEFAULT 1
+#endif
+// the rim-wave schedule's partial tiles keep the per-CU record in ONE 64-bit word {launch epoch, arrivals, ice-holding waves per
+// SIMD} and update it by a compare-and-swap loop -- a load and a swap where the lock takes a swap, two rounds of loads, the stores,
+// their acknowledgement and the unlock (the test build carries both, CICE_EVP_HIP_RES_LOCK_CAS).  The same choices from the same counts
+#ifndef EVP_RES2_LOCK_CAS_DEFAULT
+#define EVP_RES2_LOCK_CAS_DEFAULT 1
 #endif
 // the rim-wave schedule's two divisions per U-cell on the cores, the reciprocal formed in the first part of the momentum step
 // (evp_range_math.h: recip_core / quot_core; the test build carries both, CICE_EVP_HIP_RES_SPLITDIV)
@@ -140,7 +155,7 @@ struct EvpResident2 {
 hipError_t evp_range_math_probe(long long n, const double *x, const double *num, const double *den, double *sqrt_lib, double *sqrt_core,
                                 double *div_lib, double *div_core, unsigned char *verdict, hipStream_t st);
 #endif
-// EvpResident2::dbg, bit by bit.  CICE_EVP_HIP_RES_DEBUG (test build) sets the hooks by these numbers; the last four A/B switches
+// EvpResident2::dbg, bit by bit.  CICE_EVP_HIP_RES_DEBUG (test build) sets the hooks by these numbers; the last six A/B switches
 // are set by the host from switches of their own (evp_host_resident.cpp), never from RES_DEBUG's value alone.
 enum : int {
     // timing experiments only: WRONG results
@@ -160,7 +175,10 @@ enum : int {
     EVP_RES2_HOOK_PRIO_MASK = 3 << 11,   // ... = bits 2048 | 4096
     EVP_RES2_HOOK_NOLOCK = 8192,         // the rim-wave schedule's full tiles skip the per-CU lock
     EVP_RES2_HOOK_SPLITDIV = 16384,      // its U-cells' divisions on the cores with the reciprocal formed early
-    EVP_RES2_HOOK_HOST_OWNED = EVP_RES2_HOOK_NO_RANGE | EVP_RES2_HOOK_PRIO_MASK | EVP_RES2_HOOK_NOLOCK | EVP_RES2_HOOK_SPLITDIV,
+    EVP_RES2_HOOK_WRITE_ONCE = 32768,    // the lean variants store the final state into the buffer that is current afterwards only
+    EVP_RES2_HOOK_LOCK_CAS = 65536,      // the rim-wave schedule's per-CU record as one 64-bit word under a compare-and-swap loop
+    EVP_RES2_HOOK_HOST_OWNED = EVP_RES2_HOOK_NO_RANGE | EVP_RES2_HOOK_PRIO_MASK | EVP_RES2_HOOK_NOLOCK | EVP_RES2_HOOK_SPLITDIV |
+                               EVP_RES2_HOOK_WRITE_ONCE | EVP_RES2_HOOK_LOCK_CAS,
     EVP_RES2_HOOK_BARS_RIMU = EVP_RES2_HOOK_NO_RIM_SPLIT | EVP_RES2_HOOK_LAG_NO_UCELL | EVP_RES2_HOOK_KEEP_NO_UCELL,
 };      // (BARS_RIMU: no rim-wave schedule with the hooks that undo the rim-wave split or keep tiles without U-cells)
 // One instantiation of evp_resident2_tile, by its template arguments (evp_resident2.hip: REMOTE, COOP, LEAN, RIMU).  That file

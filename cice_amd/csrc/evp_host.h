@@ -495,6 +495,7 @@ int resident2_order();
 int resident_tables();
 int launch_resident2(int ndte, int cur0, bool dry);
 int resident_check_error();
+bool resident_declined_switch();  // test build, CICE_EVP_HIP_RES_DECLINE=1: this call does not take the resident kernel
 int tune_after_upload();
 // evp_host_march.cpp
 bool march_wanted();

@@ -20,6 +20,12 @@ static bool range_switch() { return env_on(env_test("CICE_EVP_HIP_RES_RANGE"), E
 static int prio_switch() { return std::min(3, std::max(0, env_int(env_test("CICE_EVP_HIP_RES_PRIO"), EVP_RES2_PRIO_DEFAULT))); }
 static bool nolock_switch() { return env_on(env_test("CICE_EVP_HIP_RES_NOLOCK"), EVP_RES2_NOLOCK_DEFAULT != 0); }
 static bool splitdiv_switch() { return env_on(env_test("CICE_EVP_HIP_RES_SPLITDIV"), EVP_RES2_SPLITDIV_DEFAULT != 0); }
+// what a launch pays beside its subcycles (profiles/r24_resident_launch_cost.txt): the final state into one ping-pong buffer, the
+// per-CU record of the partial tiles as one word under a compare-and-swap loop
+static bool write_once_switch() { return env_on(env_test("CICE_EVP_HIP_RES_WRITE_ONCE"), EVP_RES2_WRITE_ONCE_DEFAULT != 0); }
+static bool lock_cas_switch() { return env_on(env_test("CICE_EVP_HIP_RES_LOCK_CAS"), EVP_RES2_LOCK_CAS_DEFAULT != 0); }
+// test build: this call goes through the kernels the resident kernel stands in for (read at every cice_evp_hip_subcycle)
+bool resident_declined_switch() { return env_on(env_test("CICE_EVP_HIP_RES_DECLINE"), false); }
 
 // ---- on-chip resident subcycle -------------------------------------------------------
 // (a rank of a fold row split in x may hold neither a pole point nor a pair with both halves: its seam cells are the plan's
@@ -234,8 +240,9 @@ int resident2_setup(int logw)
         for (size_t k = 0; k < S.plan.local_dst.size(); ++k)
             if (S.plan.local_src[k] >= 0 && !tfold_image(k)) S.res2_pubimg_h[(size_t)S.plan.local_src[k]] = 1;
         if (!S.res2_cuload) {
-            if (S.mem.alloc(S.res2_cuload, 2048 * 8)) return -1;
-            HIPC(hipMemset(S.res2_cuload, 0, 2048 * 8 * sizeof(int)));
+            // [2048][8] records under the lock, behind them [2048] 64-bit words for the compare-and-swap form (evp_resident2.hip)
+            if (S.mem.alloc(S.res2_cuload, 2048 * 10)) return -1;
+            HIPC(hipMemset(S.res2_cuload, 0, 2048 * 10 * sizeof(int)));
         }
         S.res2_cls_h = cls;
         S.res2_cnt_h = cnt;
@@ -452,14 +459,16 @@ int launch_resident2(int ndte, int cur0, bool dry)
     R.late_waves = S.res2_late; R.cuload = S.res2_cuload;
     R.prof = nullptr;
     if (S.res2_logw == 4 && prof_switch()) {
-        if (!S.res2_prof && S.mem.alloc(S.res2_prof, (size_t)S.res2_ntiles * 32)) return -1;
-        HIPC(hipMemsetAsync(S.res2_prof, 0, (size_t)S.res2_ntiles * 32 * sizeof(unsigned long long), S.stream));
+        // [ntiles][4][8] phase stamps, behind them [ntiles][4][8] launch stamps
+        if (!S.res2_prof && S.mem.alloc(S.res2_prof, (size_t)S.res2_ntiles * 64)) return -1;
+        HIPC(hipMemsetAsync(S.res2_prof, 0, (size_t)S.res2_ntiles * 64 * sizeof(unsigned long long), S.stream));
         R.prof = S.res2_prof;
     }
     // the test hooks by their numbers; the A/B switches of the lean loops from switches of their own
     R.dbg = (debug_hooks() & ~EVP_RES2_HOOK_HOST_OWNED) | (range_switch() ? 0 : EVP_RES2_HOOK_NO_RANGE) |
             (prio_switch() << EVP_RES2_HOOK_PRIO_SHIFT) | (nolock_switch() ? EVP_RES2_HOOK_NOLOCK : 0) |
-            (splitdiv_switch() ? EVP_RES2_HOOK_SPLITDIV : 0);
+            (splitdiv_switch() ? EVP_RES2_HOOK_SPLITDIV : 0) | (write_once_switch() ? EVP_RES2_HOOK_WRITE_ONCE : 0) |
+            (lock_cas_switch() ? EVP_RES2_HOOK_LOCK_CAS : 0);
     R.seam = S.res2_seam; R.tfold = S.plan.tfold ? 1 : 0; R.img3 = S.res2_img3;
     R.rec_raw[0] = S.res2_rec_raw[0]; R.rec_raw[1] = S.res2_rec_raw[1];
     R.rimg = S.res_remote ? S.res2_rimg : nullptr; R.peer_rec = S.res2_peer_rec; R.peer_rstride = S.res2_peer_rstride;

@@ -248,6 +248,11 @@ __global__ __launch_bounds__(64 * RTY, REMOTE ? 2 : 3) void evp_resident2_tile(E
         no_ucell = rb.x + ((tile % pb) % A.gx) * (W - 1) > rb.y || rb.z + ((tile % pb) / A.gx) * (H - 1) > rb.w;
         if (no_ucell && !(RES_DBG(R) & EVP_RES2_HOOK_KEEP_NO_UCELL)) return;
     }
+    // what a launch pays beside its subcycles (test build, with the phase stamps; tools/resident_launch_stamps.py): wall-clock stamps
+    // of every wave -- workgroup start, after the lock, the lane tables and masks loaded, the state loads issued and landed, the first
+    // ring poll matched, the loop's end, the write-back's stores landed
+    unsigned long long lst0 = 0, lst1 = 0, lst2 = 0, lst3 = 0, lst4 = 0;
+    if (RES_PROF(R)) lst0 = wall_clock64();
     // PERM: which quarter ("chunk") of the tile's permuted cell list this wave takes.  The host packs
     // the ice cells of a tile into its first chunks (a coastal tile then costs one or two waves, not
     // four).  A SIMD issues for one wave at a time and all tiles advance in lock step, so the SIMD with
@@ -284,11 +289,52 @@ __global__ __launch_bounds__(64 * RTY, REMOTE ? 2 : 3) void evp_resident2_tile(E
             int chunk_of[4] = {0, 1, 2, 3};
             unsigned spins = 0;
             bool locked = false;
+            // RIMU: the record as ONE 64-bit word (behind the [2048][8] records: launch epoch << 40 | arrivals << 32 | the four SIMD
+            // counts, 8 bits each) under a compare-and-swap loop: a load and a swap, one swap more per workgroup of the CU that came
+            // in between -- where the lock below takes a swap, the stamp's load, the counts' loads, the stores, their
+            // acknowledgement and the unlock, and every later workgroup of the CU waits for all of it.  A word of another launch
+            // counts as zeros (epochs start at 1).  The same counts give the same chunk -> wave map.  The product compiles it in or
+            // out (EVP_RES2_LOCK_CAS_DEFAULT); the test build carries a switch (EVP_RES2_HOOK_LOCK_CAS, CICE_EVP_HIP_RES_LOCK_CAS).
+#ifdef CICE_EVP_HIP_TESTING
+            const bool lock_cas = RIMU && (RES_DBG(R) & EVP_RES2_HOOK_LOCK_CAS);
+#else
+            constexpr bool lock_cas = RIMU && EVP_RES2_LOCK_CAS_DEFAULT;
+#endif
+            if (lock_cas) {
+                unsigned long long *L64 = reinterpret_cast<unsigned long long *>(R.cuload + 2048 * 8) + s_cu;
+                const unsigned long long epoch = (unsigned long long)(R.tag_base >> 12);
+                unsigned long long seen = __hip_atomic_load(L64, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                while (spins++ < 200000u) {
+                    const bool fresh = (seen >> 40) != epoch;
+                    int ld[4];
+#pragma unroll
+                    for (int q = 0; q < 4; ++q) ld[q] = fresh ? 0 : (int)((seen >> (8 * q)) & 255u);
+                    const int rank = fresh ? 0 : (int)((seen >> 32) & 255u);
+                    bool used[4] = {false, false, false, false};
+                    for (int ck = 0; ck < 4; ++ck) {      // active chunks first, each to the free wave on the least loaded SIMD
+                        int best = -1;
+                        for (int w = 0; w < 4; ++w) {
+                            if (used[w]) continue;
+                            if (best < 0 || ld[s_simd[w] & 3] < ld[s_simd[best] & 3]) best = w;
+                        }
+                        used[best] = true;
+                        chunk_of[best] = ck;
+                        if (ck < nact) ld[s_simd[best] & 3] += 1;
+                    }
+                    const unsigned long long next = (epoch << 40) | ((unsigned long long)((rank + 1) & 255) << 32) |
+                                                    ((unsigned long long)(ld[3] & 255) << 24) | ((unsigned long long)(ld[2] & 255) << 16) |
+                                                    ((unsigned long long)(ld[1] & 255) << 8) | (unsigned long long)(ld[0] & 255);
+                    const unsigned long long was = atomicCAS(L64, seen, next);
+                    if (was == seen) { s_simd[0] |= rank << 8; locked = true; break; }
+                    seen = was;
+                }
+                if (!locked) { chunk_of[0] = 0; chunk_of[1] = 1; chunk_of[2] = 2; chunk_of[3] = 3; }      // (gave up: any map is correct)
+            } else
             while (spins++ < 200000u) {
                 if (atomicCAS(&L[0], 0, 1) == 0) { locked = true; break; }
                 __builtin_amdgcn_s_sleep(2);
             }
-            if (locked) {
+            if (locked && !lock_cas) {
                 int ld[4];
                 const int stamp = __hip_atomic_load(&L[1], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
                 const bool fresh = stamp != (int)R.tag_base;
@@ -327,6 +373,14 @@ __global__ __launch_bounds__(64 * RTY, REMOTE ? 2 : 3) void evp_resident2_tile(E
         // waves sat at B1 while the rim wave worked.  On the rim-wave schedule they step inside its window and priorities do
         // pay: subcycle_rim below)
     }
+    // (a launch stamp first waits for the wave's outstanding loads and stores: each span then holds what was issued inside it,
+    // and the stamped prologue is the sum of its levels, not their overlap)
+#define EVP_LSTAMP(x)                                                       \
+    if (RES_PROF(R)) {                                                      \
+        asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");         \
+        x = wall_clock64();                                                 \
+    }
+    EVP_LSTAMP(lst1)
     // which T-cell of the tile this thread owns: row-major (lane = column) unless permuted
     const int pos = PERM ? (int)R.perm[tile * 256 + tq] : t;      // == trow*W + tcol
     const int tcol = pos & (W - 1);
@@ -380,6 +434,7 @@ __global__ __launch_bounds__(64 * RTY, REMOTE ? 2 : 3) void evp_resident2_tile(E
     // record scheme depends on that; making either side depend on the ice mask would let a tile
     // next to open water run ahead of its reader and overwrite a record that was never read).
     const bool pub = ownU && (R.pubmap[cu] != 0);
+    EVP_LSTAMP(lst2)
     const int par0 = R.par0;                      // record buffer of subcycle index 0 in this launch
     // COOP: the first nlate entries of the tile's permuted cell list are its rim T-cells with ice (resident2_order); the
     // thread that holds such a cell leaves its stress update to the quad g = its list index, lanes 4g .. 4g+3 of the workgroup
@@ -608,6 +663,7 @@ __global__ __launch_bounds__(64 * RTY, REMOTE ? 2 : 3) void evp_resident2_tile(E
         for (int q = t; q < NSTR * SP; q += 256) s_str[q] = 0.0;
         if (t < 4) s_slot[t] = 0;
     }
+    EVP_LSTAMP(lst3)
     __syncthreads();
 
     // bound of a wait on a record of this GPU: spin count (workgroups not co-resident -> fail fast) on
@@ -709,6 +765,7 @@ __global__ __launch_bounds__(64 * RTY, REMOTE ? 2 : 3) void evp_resident2_tile(E
             __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
         }
         EVP_STAMP(pacc0)
+        if (prof && k == 0) lst4 = wall_clock64();
 
         double str[8];
 #pragma unroll
@@ -981,6 +1038,7 @@ __global__ __launch_bounds__(64 * RTY, REMOTE ? 2 : 3) void evp_resident2_tile(E
             __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
         }
         EVP_STAMP(pacc0)
+        if (prof && k == 0) lst4 = wall_clock64();      // (the rim wave: its first poll has matched; an interior wave: it starts)
         if (!bad) {      // (a wave whose wait gave up goes straight to the barrier)
             if (prio_in_stress) __builtin_amdgcn_s_setprio(1);
             if (actT) {
@@ -1132,6 +1190,8 @@ __global__ __launch_bounds__(64 * RTY, REMOTE ? 2 : 3) void evp_resident2_tile(E
             if (!subcycle(k, (const v4u *)R.rec[(k + par0) & 1], (v4u *)R.rec[((k + par0) & 1) ^ 1])) return;
     }
 #undef EVP_STAMP
+    unsigned long long lst5 = 0;
+    EVP_LSTAMP(lst5)
     if (prof && (t & 63) == 0) {
         unsigned long long *o = R.prof + ((size_t)tile * 4 + (tq >> 6)) * 8;
         o[0] = pacc0; o[1] = pacc1; o[2] = pacc2; o[3] = pacc3; o[4] = pacc4;
@@ -1153,6 +1213,35 @@ __global__ __launch_bounds__(64 * RTY, REMOTE ? 2 : 3) void evp_resident2_tile(E
     }
 
     // ---- write the state back --------------------------------------------------------------
+    // LEAN, one store per value: into the ping-pong buffer that is current after the call, cur0 ^ (ndte & 1) -- the one the host's
+    // S.cur names from here on.  That is how every call of the streaming kernel leaves the two buffers (its last subcycle writes
+    // the ice T-cells' stresses and the ice U-cells' velocities with their images into one of them, evp_kernels.hip): they differ
+    // on cells the loop writes and nowhere else.  Every reader -- the download, the stress halo, the tail, the preparation, the
+    // marching and streaming kernels, the next resident launch, the replay snapshot -- reads the current buffer, and every kernel
+    // that advances the state writes those very cells of the other buffer before anybody reads them; off the masks the buffers
+    // stay equal (the upload copies, evp_launch_zero_sig_off_mask zeroes both).  The product compiles it in or out
+    // (EVP_RES2_WRITE_ONCE_DEFAULT); the test build carries a switch (EVP_RES2_HOOK_WRITE_ONCE, CICE_EVP_HIP_RES_WRITE_ONCE).
+#ifdef CICE_EVP_HIP_TESTING
+    const bool write_once = LEAN && (RES_DBG(R) & EVP_RES2_HOOK_WRITE_ONCE);
+#else
+    constexpr bool write_once = LEAN && EVP_RES2_WRITE_ONCE_DEFAULT;
+#endif
+    if (write_once) {
+        if (!R.dry) {
+            const int fin = (R.cur0 ^ (R.ndte & 1)) & 1;
+            if (actN && own) {
+#pragma unroll
+                for (int k = 0; k < 12; ++k) R.tab[fin * 12 + k][c] = s[k];
+            }
+            if (isU) {
+                double *uu = R.u[fin], *vv = R.v[fin];
+                uu[cu] = u_own; vv[cu] = v_own;
+                if (img0 >= 0) { uu[img0 >> 1] = img_sg0 * u_own; vv[img0 >> 1] = img_sg0 * v_own; }
+                if (img1 >= 0) { uu[img1 >> 1] = img_sg1 * u_own; vv[img1 >> 1] = img_sg1 * v_own; }
+                if (img2 >= 0) { uu[img2 >> 1] = img_sg2 * u_own; vv[img2 >> 1] = img_sg2 * v_own; }
+            }
+        }
+    } else
     if (!R.dry) {
         if (actN && own) {
 #pragma unroll
@@ -1177,6 +1266,16 @@ __global__ __launch_bounds__(64 * RTY, REMOTE ? 2 : 3) void evp_resident2_tile(E
             }
         }
     }
+    if (RES_PROF(R)) {
+        unsigned long long lst6 = 0;
+        EVP_LSTAMP(lst6)
+        if ((t & 63) == 0) {      // per wave as it was dispatched, behind the [ntiles][4][8] phase stamps
+            unsigned long long *o = R.prof + ((size_t)A.ntiles * 4 + (size_t)tile * 4 + (t >> 6)) * 8;
+            o[0] = lst0; o[1] = lst1; o[2] = lst2; o[3] = lst3; o[4] = lst4; o[5] = lst5; o[6] = lst6;
+            o[7] = (unsigned long long)(tq >> 6) | ((unsigned long long)R.nact[tile] << 8);
+        }
+    }
+#undef EVP_LSTAMP
 }
 
 size_t lds_bytes(const Res2Variant &v, unsigned flags)

@@ -57,7 +57,7 @@ EXPORTS = [
 # the test transport
 TEST_EXPORTS = [
     "cice_evp_hip_cgrid_fold_plan", "cice_evp_hip_cgrid_window_plan", "cice_evp_hip_cgrid_window_plan_ext", "cice_evp_hip_cgrid_window_deps", "cice_evp_hip_cgrid_strip_plan", "cice_evp_hip_cgrid_strip_zones", "cice_evp_hip_cgrid_frame_plan", "cice_evp_hip_cgrid_march_fold_plan", "cice_evp_hip_set_test_transport", "cice_evp_hip_march_plan", "cice_evp_hip_march_fold_plan", "cice_evp_hip_march_layout", "cice_evp_hip_march_schedule",
-    "cice_evp_hip_debug_device_allocs", "cice_evp_hip_debug_cuload", "cice_evp_hip_debug_prof", "cice_evp_hip_debug_cgrid_prof", "cice_evp_hip_debug_cgres_prof", "cice_evp_hip_plan_build", "cice_evp_hip_halo_plan", "cice_evp_hip_seam_plan",
+    "cice_evp_hip_debug_device_allocs", "cice_evp_hip_debug_cuload", "cice_evp_hip_debug_prof", "cice_evp_hip_debug_prof_launch", "cice_evp_hip_debug_cgrid_prof", "cice_evp_hip_debug_cgres_prof", "cice_evp_hip_plan_build", "cice_evp_hip_halo_plan", "cice_evp_hip_seam_plan",
     "cice_evp_hip_peer_plan", "cice_evp_hip_peer_signs", "cice_evp_hip_center_plan", "cice_evp_hip_stress_plan",
     "cice_evp_hip_fold_split_plan", "cice_evp_hip_plan_flags", "cice_evp_hip_fold_images_plan", "cice_evp_hip_cgrid_fold_xplan",
     "cice_evp_hip_cgrid_fold_xpeers", "cice_evp_hip_stress_tfold_xplan", "cice_evp_hip_plan_dump", "cice_evp_hip_rim_plan", "cice_evp_hip_debug_range_math",
@@ -77,6 +77,7 @@ TEST_ENV = [
     "CICE_EVP_HIP_PREFETCH", "CICE_EVP_HIP_FAULT_REPLAY", "CICE_EVP_HIP_MARCH_BANDSEG", "CICE_EVP_HIP_CGRID_PROF",
     # A/B switches of kernels and transports (forced tile shapes, schedules the default never picks, the ring exchange's other forms)
     "CICE_EVP_HIP_NO_OVERLAP", "CICE_EVP_HIP_TYB", "CICE_EVP_HIP_NOGRAPH", "CICE_EVP_HIP_GRAPH_RCCL", "CICE_EVP_HIP_RES_LOGW", "CICE_EVP_HIP_RES_COOP", "CICE_EVP_HIP_RES_LEAN", "CICE_EVP_HIP_RES_RIMU", "CICE_EVP_HIP_RES_RANGE", "CICE_EVP_HIP_RES_PRIO", "CICE_EVP_HIP_RES_NOLOCK", "CICE_EVP_HIP_RES_SPLITDIV",
+    "CICE_EVP_HIP_RES_WRITE_ONCE", "CICE_EVP_HIP_RES_LOCK_CAS", "CICE_EVP_HIP_RES_DECLINE",
     "CICE_EVP_HIP_MARCH_EXT", "CICE_EVP_HIP_MARCH_DIRECT", "CICE_EVP_HIP_CGRID_FUSED", "CICE_EVP_HIP_CGRID_GEO",
     "CICE_EVP_HIP_CGRID_RES_SLEEP", "CICE_EVP_HIP_CGRID_RES_CULL", "CICE_EVP_HIP_CGRID_RES_DEBUG",
     "CICE_EVP_HIP_CGRID_STRIP", "CICE_EVP_HIP_CGRID_STRIP_SEG", "CICE_EVP_HIP_CGRID_STRIP_EDGE", "CICE_EVP_HIP_CGRID_STRIP_RIDE", "CICE_EVP_HIP_CGRID_STRIP_LEN", "CICE_EVP_HIP_CGRID_STRIP_ITEMS", "CICE_EVP_HIP_CGRID_STRIP_LAST",
@@ -873,6 +874,13 @@ class EvpHip:
         self._need_testing("debug_prof")
         a = np.zeros((ntiles_max, 4, 8), dtype=np.uint64)
         _check(self.lib, self.lib.cice_evp_hip_debug_prof(a.ctypes.data_as(C.POINTER(C.c_uint64)), C.c_int32(ntiles_max)), "(debug_prof)")
+        return a
+
+    def debug_prof_launch(self, ntiles_max: int = 4096):
+        """Wall-clock stamps (100 MHz) of the last profiled resident launch, per tile and hardware wave."""
+        self._need_testing("debug_prof_launch")
+        a = np.zeros((ntiles_max, 4, 8), dtype=np.uint64)
+        _check(self.lib, self.lib.cice_evp_hip_debug_prof_launch(a.ctypes.data_as(C.POINTER(C.c_uint64)), C.c_int32(ntiles_max)), "(debug_prof_launch)")
         return a
 
     def debug_cgrid_prof(self, ntiles_max: int = 1 << 16):

@@ -137,6 +137,10 @@ int cice_evp_hip_debug_cuload(int32_t *out, int32_t n);
  * per tile and chunk of 64 cells 8 x uint64 = shader cycles in {ring poll, stress, barrier wait, momentum
  * step + publish, barrier wait}, arrival rank of the workgroup on its CU, hardware wave, active chunks.    */
 int cice_evp_hip_debug_prof(uint64_t *out, int32_t ntiles_max);
+/* Launch stamps of the same launch (tools/resident_launch_stamps.py): per tile and hardware wave 8 x uint64 = the 100 MHz wall clock at
+ * workgroup start, after the per-CU lock, after the lane tables and masks, after the state loads, at the first ring poll's match,
+ * at the loop's end, at the write-back's end; chunk the wave took | active chunks of the tile << 8.                                */
+int cice_evp_hip_debug_prof_launch(uint64_t *out, int32_t ntiles_max);
 /* (word 6 of a chunk's stamps = hardware wave | passes that took the compiler's sqrt / division << 8: a wave of the lean loops makes
  * one stress pass and one or two momentum-step passes per subcycle, each on the range-proved cores or not -- csrc/evp_range_math.h) */
 /* The range-proved fp64 square root and division of the lean resident loops (csrc/evp_range_math.h: sqrt_core, div_core) beside the
