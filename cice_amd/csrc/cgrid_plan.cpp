@@ -388,24 +388,26 @@ int build_cg_march_fold(const cice_evp_hip_dims &d, const HaloPlan &P, int ex, i
     F = CgMarchFoldPlan();
     why.clear();
     const bool tf = d.ns_boundary_type == CICE_EVP_BND_TRIPOLET;
-    if (d.ns_boundary_type != CICE_EVP_BND_TRIPOLE && !tf) {
+    const bool folded = d.ns_boundary_type == CICE_EVP_BND_TRIPOLE || tf;
+    const bool ranks = !P.peers.empty() || !P.cg_peers.empty();
+    // (no fold, several ranks: the same plan with the frame as the whole REST -- no fold cells, no rows cut from the top)
+    if (!folded && !(ranks && allow_ranks)) {
         why = "no tripole fold (the one-launch schedule marches such a grid)";
         return 0;
     }
-    const bool ranks = !P.peers.empty() || !P.cg_peers.empty();
     if (ranks && !allow_ranks) {
         why = "several ranks, or the fold rows not on this rank";
         return 0;
     }
-    if (!ranks && (P.cg_split || P.fold_rows != 1)) {
+    if (folded && !ranks && (P.cg_split || P.fold_rows != 1)) {
         why = "several ranks, or the fold rows not on this rank";
         return 0;
     }
-    if (P.fold_rows == 2 && !P.cg_split) {
+    if (folded && P.fold_rows == 2 && !P.cg_split) {
         why = "the fold rows shared with other ranks without the C grid's fold exchange";
         return 0;
     }
-    if (d.nx_block < 3 || d.ny_block < 3 || d.nx_global % 2) {
+    if (d.nx_block < 3 || d.ny_block < 3 || (folded && d.nx_global % 2)) {
         why = "a block too small";
         return 0;
     }
@@ -423,18 +425,22 @@ int build_cg_march_fold(const cice_evp_hip_dims &d, const HaloPlan &P, int ex, i
     };
     static const CgSplitWords words = {"fold-band plan", "zone and rest do not add up to the interior", "a phase other than stressC_T on a ghost cell",
                                        "a REST cell without its own levels", "phase 1 loads outside the array", true};
-    CgSplit X(d, F, why, words, reads);
+    // (without a fold the same plan under its own name: a failure at set_geometry must not send its reader to a fold)
+    static const CgSplitWords words_no_fold = {"five-phase frame plan", "zone and rest do not add up to the interior", "a phase other than stressC_T on a ghost cell",
+                                               "a REST cell without its own levels", "phase 1 loads outside the array", true};
+    CgSplit X(d, F, why, folded ? words : words_no_fold, reads);
     const int nxb = d.nx_block, nyb = d.ny_block, NY = d.ny_global, sy = ey - 3;
     const size_t ncell = (size_t)nxb * nyb * d.nblocks;
     auto grow = [&](int b, int j) { return d.jglob0[b] + (j - d.jlo[b]); };          // global row of local row j
     // on the fold or beyond it, by field location (0 centre, 1 NE corner, 2 E face, 3 N face) and global row
-    auto at_fold = [&](int loc, int jg) { return jg > NY || (jg == NY && (tf || loc == 1 || loc == 3)); };
+    auto at_fold = [&](int loc, int jg) { return folded && (jg > NY || (jg == NY && (tf || loc == 1 || loc == 3))); };
     // ---- the fold step's cells: destinations and sources of every location ----
     std::vector<uint8_t> foldcell(ncell, 0);
     // (the lists the host runs: the C grid's own where the fold rows have several owners -- operands >= ncell are staging slots the
     // exchange fills --, build_fold_list's where they are all here, none on a rank without them)
     FoldList L[4];
     for (int loc = 0; loc < 4; ++loc) {
+        if (!folded) break;
         if (P.cg_split) L[loc] = P.cg_fold[loc];
         else if (P.fold_rows == 1) build_fold_list(d, loc, L[loc]);
         for (size_t k = 0; k < L[loc].dst.size(); ++k)
@@ -465,7 +471,7 @@ int build_cg_march_fold(const cice_evp_hip_dims &d, const HaloPlan &P, int ex, i
     // check below keeps its lanes inside the array)
     std::vector<int32_t> tiles;
     std::vector<StripZone> zones0, zones;
-    plan_strip_zones(d, P, ex, ey, ex - 3, NY - (tf ? 1 : 0), tiles, zones0);
+    plan_strip_zones(d, P, ex, ey, ex - 3, folded ? NY - (tf ? 1 : 0) : STRIP_EVERY_IMAGE, tiles, zones0);
     bool len_all = want_len != 0;
     for (StripZone z : zones0) {
         auto rule_holds = [&]() {
@@ -479,7 +485,7 @@ int build_cg_march_fold(const cice_evp_hip_dims &d, const HaloPlan &P, int ex, i
                 strip_items(one, ex, ey, lo0, 1, 1, z.j1 - z.j0 + sy, it);
                 for (size_t k = 0; k < it.size(); k += 6) {
                     const StripRange f = strip_footprint(&it[k], lo0 == 3);
-                    if (f.i0 < 1 || f.i1 > nxb || f.j0 < 1 || f.j1 > nyb || grow(z.b, f.j1) > NY + 1) return false;
+                    if (f.i0 < 1 || f.i1 > nxb || f.j0 < 1 || f.j1 > nyb || (folded && grow(z.b, f.j1) > NY + 1)) return false;
                 }
             }
             for (int j = z.j0; j <= jb; ++j)
@@ -497,7 +503,7 @@ int build_cg_march_fold(const cice_evp_hip_dims &d, const HaloPlan &P, int ex, i
         zones.push_back(z);
     }
     if (zones.empty()) {
-        why = "no rectangle for the marched kernel is left under the fold band";
+        why = folded ? "no rectangle for the marched kernel is left under the fold band" : "no rectangle for the marched kernel on this rank";
         return 0;
     }
     F.zones = zones;
@@ -506,7 +512,7 @@ int build_cg_march_fold(const cice_evp_hip_dims &d, const HaloPlan &P, int ex, i
     for (const StripZone &z : zones) zcells += (long)(z.i1 - z.i0 + ex - 3) * (z.j1 - z.j0 + sy);
     F.seg = strip_items(zones, ex, ey, F.lengths ? 3 : 2, slots, seg_min > 0 ? seg_min : (zcells >= 1000000 ? 16 : 8), seg, F.items);
     for (int b = 0; b < d.nblocks; ++b) {
-        if (grow(b, d.jhi[b]) != NY) continue;
+        if (!folded || grow(b, d.jhi[b]) != NY) continue;
         int top = d.jlo[b] - 1;
         for (const StripZone &z : zones)
             if (z.b == b) top = std::max(top, z.j1 + sy - 1);
@@ -515,7 +521,7 @@ int build_cg_march_fold(const cice_evp_hip_dims &d, const HaloPlan &P, int ex, i
     // ---- the two sets, the fold row, the phases ----
     if (X.own(F.items)) return -1;
     for (int b = 0; b < d.nblocks; ++b)
-        if (grow(b, d.jhi[b]) == NY)
+        if (folded && grow(b, d.jhi[b]) == NY)
             for (int i = d.ilo[b]; i <= d.ihi[b]; ++i) F.cells[X.off(b, i, d.jhi[b])] |= EVP_CGS_FOLDROW;
     if (X.dilate() || X.check_sum()) return -1;
     // ---- the invariants ----

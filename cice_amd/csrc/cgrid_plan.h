@@ -176,6 +176,14 @@ struct CgMarchFoldPlan : CgSplitPlan {
 // build_fold_list's where they are all here, none on a rank without them (zone + frame, band_rows = 0) -- and the REST also holds the
 // FRAME: every cell a peer receives (HaloPlan::peers and cg_peers send lists, the raw fold sources for other ranks' staging slots
 // included) and every cell with a ghost image here.  One more invariant: each of those is a REST cell evaluated at every level.
+// A grid WITHOUT a fold on several ranks (allow_ranks; evp_host_cgrid.cpp: "zone marched + frame" on the five phases, the schedule of
+// visc_method = avg_strength there): the same plan with no fold cells and no rows cut from the top -- the REST is the frame as
+// build_cg_frame defines it and what strip_zones leaves along the block edges; band_rows = 0.  On one rank, or with allow_ranks =
+// false, such a grid declines.
+// visc_method = avg_strength changes nothing in a plan: cg_strip<AVGS> loads the same rows (strip_footprint), and what it forms beyond
+// the avg_zeta instantiations -- both face averages on rows ja - 1 and jb + 1, deltaU on rows ja - 1 .. jb -- stays within
+// STRIP_LEVELS' last rows (LAST forms the same on row jb + 1) and one row below the first owned one, where shearU is formed anyway;
+// phase 2 of the list-driven kernels then reads deltaU of its own corner (phase 0 runs wherever phase 2 does) and no etax2T.
 struct CgGeoCheck {
     virtual int operator()(const StripZone &z) const = 0;
     virtual ~CgGeoCheck() {}

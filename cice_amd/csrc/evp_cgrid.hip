@@ -367,6 +367,8 @@ __global__ __launch_bounds__(TX *TY) void cg_frame_strain(EvpCgrid A, EvpCgFrame
 // kernel (EvpCgBand; cgrid_plan.h: build_cg_march_fold).  The same arithmetic; the five ping-pong arrays are read from the previous
 // subcycle's buffers and written to this subcycle's on REST cells only (EVP_CGS_REST; without ice: the previous value taken along); a zone
 // cell evaluated because a REST cell reads its shearU / etax2T / stresspT / stressmT / stress12U stores it to the scratch array only.
+// visc_method = avg_strength: phase 2 forms the corner's viscosity from strengthU and the corner's own deltaU, which phase 0 made in the
+// same subcycle -- in the array on a REST corner, in one more scratch array on a zone corner -- and reads no etax2T.
 template <bool BAND>
 __device__ __forceinline__ void strain_u_cell(const EvpCgrid &A, const EvpCgBand &B, const Cell &c)
 {
@@ -406,7 +408,9 @@ __device__ __forceinline__ void strain_u_cell(const EvpCgrid &A, const EvpCgBand
     const double vNij = vN[o] * npc + (npe - npc) * npe * rxNr * vN[e];
     const double sh = dxU * (uEijp1 - uEij) - uU * ddxE + dyU * (vNip1j - vNij) - vU * ddyN;
     if (BAND && !mine) {
+        // (visc_method = avg_strength: phase 2 at this corner takes its deltaU; the array itself is the marched kernel's here)
         B.sh[o] = sh;
+        if (A.avg_strength) B.dl[o] = sqrt(dv * dv + A.p.e_factor * (tn * tn + sh * sh));
         return;
     }
     A.f[CF_SHEARU][o] = sh;
@@ -527,10 +531,14 @@ __device__ __forceinline__ void stress_u_cell(const EvpCgrid &A, const EvpCgBand
     const bool mine = (fl & EVP_CGS_REST) != 0;
     const double *s12_in = BAND ? B.s12_in : A.f[CF_S12U];
     double etax2U;
-    if (!BAND && A.avg_strength) {               // (BAND: visc_method = avg_zeta only)
-        if (!(m & 2u)) return;
+    if (A.avg_strength) {
+        if (!(m & 2u)) {                         // (BAND, this subcycle's buffer: the previous value taken along)
+            if (BAND) (mine ? A.f[CF_S12U] : B.s12)[o] = s12_in[o];
+            return;
+        }
+        // (BAND: deltaU of a zone corner from the scratch copy phase 0 made, of a REST corner from the array)
         double z, r;
-        visc_replpress(A.p, A.strengthU[o], A.deltaminEVP * A.g[CG_UAREA][o], A.f[CF_DELTAU][o], z, etax2U, r);
+        visc_replpress(A.p, A.strengthU[o], A.deltaminEVP * A.g[CG_UAREA][o], ZArr<BAND>{A.f[CF_DELTAU], B.dl, B.cells}[o], z, etax2U, r);
     } else {
         etax2U = avg_t2u_g(A, PtrTab{A.g}, ZArr<BAND>{A.f[CF_ETA], B.eta, B.cells}, o);
         if (mine) A.f[CF_ETAU][o] = etax2U;             // every interior cell, as grid_average_X2YS does

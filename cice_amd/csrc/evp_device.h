@@ -544,6 +544,7 @@ struct EvpCgBand {
     int nwg[5];
     const double *uE_in, *vN_in, *sp_in, *sm_in, *s12_in;
     double *sh, *eta, *sp, *sm, *s12;   // shearU, etax2T and this subcycle's stresspT, stressmT, stress12U on the zone cells the REST reads
+    double *dl;                   // visc_method = avg_strength: deltaU on those zone cells (A.f[CF_DELTAU] there is the marched kernel's)
 };
 // phase: 0 strain_rates_U, 1 stressC_T, 2 etax2U + stressC_U, 3 divergence + momentum step, 4 the velocity averages (after the zone's launch)
 void evp_launch_cgrid_band(const EvpCgrid &A, const EvpCgBand &B, int phase, hipStream_t st);

@@ -31,6 +31,7 @@ struct Ran {
     unsigned swapped = 0;        // bit q: PP_FIELDS[q] ended in the allocation that was the other one when the call began
     int one = 0;                 // subcycles run as one launch each (cg_one)
     int march = 0;               // ... as the marched kernel beside the fused chain on the frame (several ranks)
+    int march_phases = 0;        // ... of those: with the five list-driven phase kernels on the frame instead (enqueue_march_fold without a fold)
     int mfold = 0;               // ... as the marched kernel beside the five phases on the fold band (tripole grids, one rank)
     int mfold_ranks = 0;         // ... the same with the frame in the rest and the five phases' exchanges (tripole grids, several ranks)
 };
@@ -48,7 +49,7 @@ struct CellLists {
     uint8_t *cells = nullptr;
     int *wg[5] = {};
     int nwg[5] = {};
-    double *scr[5] = {};
+    double *scr[6] = {};
     long ncells = 0;
 };
 
@@ -89,11 +90,16 @@ struct CGridState {
     // On several ranks the same with the frame in the rest and the five phases' exchanges at their points ("... + frame").
     // The items live in `one` (items, nitems, strip_*)
     struct MarchFold {
-        CellLists rest;                      // cells: the EVP_CGS_* bits; five phases; scr: shearU, etax2T, stresspT, stressmT, stress12U; ncells: REST cells
+        CellLists rest;                      // cells: the EVP_CGS_* bits; five phases; scr: shearU, etax2T, stresspT, stressmT, stress12U, deltaU; ncells: REST cells
         uint8_t *gmask = nullptr;            // the land masks as bits on the rows the marched kernel derives its geometry on
         int band_rows = 0;
         long frame_cells = 0;                // several ranks: REST cells another rank receives or that have a ghost image here
         bool by_size = false;                // cg_strip's size rule holds for the zone
+        // no fold, several ranks, visc_method = avg_strength ("zone marched + frame" on the five phases): this plan's own items --
+        // CG.one's belong to the fused chain's frame plan (CG.fr), whose rectangles may differ
+        int *items = nullptr;
+        int nitems = 0, strip_len = 0;
+        long strip_cells = 0;
         bool synced = false;                 // the second allocations of the five ping-pong arrays agree with the current ones on every cell no
                                              // subcycle writes (false after an upload and after any call another schedule ran)
         std::string why;                     // why there is no plan on this rank
@@ -155,6 +161,7 @@ struct CGridState {
     int t_nsub = 0;
     int t_one = 0;               // subcycles of the last call that ran as one launch each (cg_one)
     int t_march = 0;             // ... as the marched kernel beside the fused chain on the frame (several ranks)
+    int t_march_phases = 0;      // ... of those: with the five list-driven phase kernels on the frame (that plan's items and frame cells: CG.mf)
     int t_mfold = 0;             // ... as the marched kernel beside the five phases on the fold band (tripole grids, one rank)
     int t_mfold_ranks = 0;       // ... as "marched zone + fold band + frame" (tripole grids, several ranks)
     double *tarear = nullptr, *post[5] = {};   // deformationsC_T: 1/tarea (static), divu shear vort rdg_conv rdg_shear
@@ -203,6 +210,7 @@ static bool geo_switch() { return env_on(env_test("CICE_EVP_HIP_CGRID_GEO"), tru
 static bool march_ranks_switch() { return env_on(env_test("CICE_EVP_HIP_CGRID_MARCH_RANKS"), true); }
 static int march_fold_switch() { return env_int(env_test("CICE_EVP_HIP_CGRID_MARCH_FOLD"), ENV_UNSET); }
 static int march_fold_ranks_switch() { return env_int(env_test("CICE_EVP_HIP_CGRID_MARCH_FOLD_RANKS"), ENV_UNSET); }
+static bool march_avgs_switch() { return env_on(env_test("CICE_EVP_HIP_CGRID_MARCH_AVG_STRENGTH"), false); }   // =1: avg_strength on the marched split schedules
 static bool march_fold_serial() { return env_on(env_test("CICE_EVP_HIP_CGRID_MARCH_FOLD_SERIAL"), false); }
 static bool strip_last_on() { return env_on(env_test("CICE_EVP_HIP_CGRID_STRIP_LAST"), true); }
 static bool strip_ride_on() { return env_on(env_test("CICE_EVP_HIP_CGRID_STRIP_RIDE"), true); }
@@ -500,7 +508,8 @@ static bool march_ranks()
     return one_switch() && march_ranks_switch();
 }
 
-// Tripole / tripoleT on one rank, visc_method = avg_zeta, with rectangles for cg_strip under the fold band (set_geometry built the plan):
+// Tripole / tripoleT on one rank (visc_method = avg_strength: on request, march_fold()), with rectangles for cg_strip under the fold band
+// (set_geometry built the plan):
 // every subcycle but the first after an upload runs as "marched zone + fold band" (enqueue_march_fold).  The on-chip resident kernel
 // keeps precedence where it serves the call; CICE_EVP_HIP_CGRID_ONE=0 forces the five full-domain phases.  Whether the schedule is used
 // unforced: MARCH_FOLD_DEFAULT and cg_strip's size rule; CICE_EVP_HIP_CGRID_MARCH_FOLD=0 / 1 (test build) switches
@@ -529,9 +538,21 @@ static int march_fold_ranks_wanted()   // 0 off, 1 forced on, 2 by the size rule
 static int march_fold_wanted_here() { return remote() ? march_fold_ranks_wanted() : march_fold_wanted(); }
 static bool march_fold()
 {
-    if (!CG.mf.rest.cells || CG.one.nitems <= 0 || !CG.tripole || CG.avg_strength) return false;
+    if (!CG.mf.rest.cells || CG.one.nitems <= 0 || !CG.tripole) return false;
+    // (visc_method = avg_strength: on request until it has been timed -- CICE_EVP_HIP_CGRID_MARCH_AVG_STRENGTH=1)
+    // (... set when the geometry was, which allocates the scratch deltaU)
+    if (CG.avg_strength && !(march_avgs_switch() && CG.mf.rest.scr[5])) return false;
     const int want = march_fold_wanted_here();
     return want == 1 || (want == 2 && CG.mf.by_size);
+}
+// Several ranks, no fold, visc_method = avg_strength, on request (the same switch): "zone marched + frame" with the frame on the five
+// list-driven phase kernels -- the fused chain's frame kernels recompute neighbours and cannot serve avg_strength.  enqueue_march_fold
+// is that schedule (its fold steps are no-ops without a fold); set_geometry built the plan (build_march_frame_tables) under the
+// switches and the size rule that admit the fused chain's "zone marched + frame".
+static bool march_frame_phases()
+{
+    if (!CG.mf.rest.cells || CG.mf.nitems <= 0 || CG.tripole || !remote() || !CG.avg_strength || !geo_derived()) return false;
+    return march_avgs_switch() && one_switch() && march_ranks_switch();
 }
 static int enqueue_phases(const EvpCgrid &A, int ndte, bool first);
 // The marched kernel's arguments from CG.one: its items, and the buffers and tables as cg_one takes them (no window list)
@@ -541,6 +562,14 @@ static StripArgs strip_args(const PingPong &P, const uint8_t *gmask)
     const CGridState::One &O = CG.one;
     return {EvpCgOne{nullptr, nullptr, 0, 0, O.ex, O.ey, 0, P.cur[0], P.cur[1], P.cur[2], P.cur[3], CG.gslab, CG.inslab, S.n, nullptr, gmask},
             EvpCgStrip{O.items, O.nitems, ((O.nitems + 3) / 4 + 7) / 8, O.strip_len}};
+}
+// ... from the five-phase frame plan's own items (no fold, several ranks, avg_strength: CG.mf)
+static StripArgs strip_args_frame(const PingPong &P)
+{
+    StripArgs Z = strip_args(P, CG.gmask);
+    Z.T.ox = 32; Z.T.oy = 8;
+    Z.Z = EvpCgStrip{CG.mf.items, CG.mf.nitems, ((CG.mf.nitems + 3) / 4 + 7) / 8, CG.mf.strip_len};
+    return Z;
 }
 // sync: the second allocations have not been brought into line since the upload (another schedule ran the calls before this one)
 static int enqueue_march_fold(EvpCgrid A, int ndte, bool first, bool sync, Ran &ran)
@@ -570,9 +599,10 @@ static int enqueue_march_fold(EvpCgrid A, int ndte, bool first, bool sync, Ran &
         }
         // both sets read the previous subcycle's buffers and own disjoint cells of this subcycle's
         P.aim(A, PP_ALL);
-        const StripArgs Z = strip_args(P, Q.gmask);
+        // (no fold: the five-phase frame plan's own items, on the whole-domain view of the derived geometry)
+        const StripArgs Z = CG.tripole ? strip_args(P, Q.gmask) : strip_args_frame(P);
         EvpCgBand B{R.cells, {R.wg[0], R.wg[1], R.wg[2], R.wg[3], R.wg[4]}, {R.nwg[0], R.nwg[1], R.nwg[2], R.nwg[3], R.nwg[4]},
-                    P.cur[0], P.cur[1], P.cur[2], P.cur[3], P.cur[4], R.scr[0], R.scr[1], R.scr[2], R.scr[3], R.scr[4]};
+                    P.cur[0], P.cur[1], P.cur[2], P.cur[3], P.cur[4], R.scr[0], R.scr[1], R.scr[2], R.scr[3], R.scr[4], R.scr[5]};
         if (serial) {
             evp_launch_cgrid_strip(A, Z.T, Z.Z, nullptr, fast, last, S.stream);
             evp_launch_cgrid_band(A, B, 0, S.stream);
@@ -609,7 +639,8 @@ static int enqueue_march_fold(EvpCgrid A, int ndte, bool first, bool sync, Ran &
         XCHG(A.f[CF_UU], A.f[CF_VU]);
         fold({{A.f[CF_UN], 3, true}, {A.f[CF_VE], 2, true}, {A.f[CF_UU], 1, true}, {A.f[CF_VU], 1, true}});
         P.swap(PP_ALL);
-        ++(remote() ? ran.mfold_ranks : ran.mfold);
+        if (!CG.tripole) { ++ran.march; ++ran.march_phases; }
+        else ++(remote() ? ran.mfold_ranks : ran.mfold);
     }
     ran.swapped = P.swapped;
     return 0;
@@ -801,6 +832,7 @@ static int upload_cell_lists(CellLists &Q, const std::vector<uint8_t> &cells, co
     for (int k = 0; k < nscr; ++k)
         if (zeros(Q.scr[k], S.n)) return -1;
     if (need_alt()) return -1;
+    if (CG.side.st) return 0;           // (one second stream per geometry, whichever plans share it)
     HIPC(hipStreamCreateWithFlags(&CG.side.st, hipStreamNonBlocking));
     HIPC(hipEventCreateWithFlags(&CG.side.fork, hipEventDisableTiming));
     HIPC(hipEventCreateWithFlags(&CG.side.join, hipEventDisableTiming));
@@ -987,9 +1019,39 @@ static int build_march_fold_tables(const double *const *static23)
     std::string w;
     const std::vector<uint8_t> gm = derive_geometry_check(static23, w, true, &jmax);
     if (gm.empty()) return fail(-4, "C-grid EVP: fold-band plan: %s", w.c_str());
-    if (CG.mem.upload(Q.gmask, gm) || upload_cell_lists(Q.rest, FP.cells, FP.wg, 5, 5, FP.rest_cells)) return -1;
+    // (the sixth scratch array, deltaU, only where visc_method = avg_strength may run this schedule)
+    if (CG.mem.upload(Q.gmask, gm) || upload_cell_lists(Q.rest, FP.cells, FP.wg, 5, march_avgs_switch() ? 6 : 5, FP.rest_cells)) return -1;
     if (upload_items(FP.items, EX, EY, FP.lengths, FP.seg, FP.zone_cells)) return -1;
     Q.band_rows = FP.band_rows;
+    Q.frame_cells = FP.frame_cells;
+    return 0;
+}
+
+// ---- no fold, several ranks, visc_method = avg_strength on request: the same split with the frame as the whole REST
+// (build_cg_march_fold's plan of a grid without a fold: no fold cells, no rows cut from the top).  Built where the fused chain's
+// "zone marched + frame" has its plan (build_one_tables: the same switches and size rule) and the derived geometry holds on the
+// whole rank; the size rule is applied to this plan's own zone as well.
+static int build_march_frame_tables(const double *const *static23)
+{
+    CGridState::MarchFold &Q = CG.mf;
+    if (!march_avgs_switch() || !CG.fr.cells || !CG.gmask || !strip_offsets_fit()) return 0;
+    constexpr int EX = 32, EY = 8;
+    struct Geo : CgGeoCheck {       // (the 15 derived arrays hold everywhere: CG.gmask; the six formed lengths per rectangle)
+        const double *const *g;
+        int operator()(const StripZone &z) const override { return strip_lengths_hold(z, EX, EY, g) ? 3 : 1; }
+    } geo;
+    geo.g = static23;
+    const cice_evp_hip_dims d = host_dims();
+    const StripKnobs knobs = strip_knobs();
+    CgMarchFoldPlan FP;
+    const int rc = build_cg_march_fold(d, S.plan, EX, EY, knobs.slots, 0, knobs.seg_forced, knobs.want_len ? 1 : 0, &geo, FP, Q.why);
+    if (rc < 0) return fail(-4, "C-grid EVP: %s", Q.why.c_str());
+    if (rc == 0) return 0;
+    if (strip_switch() == ENV_UNSET && (2 * FP.zone_cells < interior_cells(d) || FP.zone_cells < STRIP_MIN_CELLS)) return 0;
+    if (upload_cell_lists(Q.rest, FP.cells, FP.wg, 5, 6, FP.rest_cells) || CG.mem.upload(Q.items, FP.items)) return -1;
+    Q.nitems = (int)(FP.items.size() / 6);
+    Q.strip_len = FP.lengths;
+    Q.strip_cells = FP.zone_cells;
     Q.frame_cells = FP.frame_cells;
     return 0;
 }
@@ -1279,23 +1341,32 @@ std::string cgrid_schedule()
                       CG.one.strip_cells, CG.one.nitems, CG.fr.ncells);
         return buf;
     }
+    if (CG.geo && CG.uploaded && march_frame_phases()) {
+        // (the text of march_ranks()' schedule up to the bracket: the same counters report it)
+        std::snprintf(buf, sizeof buf, "C grid: zone marched + frame (%ld cells in %d items beside %ld rest cells, %ld of them frame cells, five phases "
+                      "advance the frame with their exchanges, avg_strength)", CG.mf.strip_cells, CG.mf.nitems, CG.mf.rest.ncells, CG.mf.frame_cells);
+        return buf;
+    }
+    const char *avgs = CG.avg_strength ? ", avg_strength" : "";
     if (CG.geo && CG.uploaded && march_fold() && remote()) {
         char fx[120] = "";
         if (fold_exchange())
             std::snprintf(fx, sizeof fx, " + fold exchange, fold rows on %d ranks (%d staging slots here)", S.plan.cg_fold_ranks, S.plan.cg_tail);
         std::snprintf(buf, sizeof buf, "C grid: marched zone + fold band + frame, %d rows (%ld cells in %d items beside %ld rest cells, %ld of them frame "
-                      "cells, five phases with their exchanges and fold steps)%s", CG.mf.band_rows, CG.one.strip_cells, CG.one.nitems, CG.mf.rest.ncells,
-                      CG.mf.frame_cells, fx);
+                      "cells, five phases with their exchanges and fold steps%s)%s", CG.mf.band_rows, CG.one.strip_cells, CG.one.nitems, CG.mf.rest.ncells,
+                      CG.mf.frame_cells, avgs, fx);
         return buf;
     }
     if (CG.geo && CG.uploaded && march_fold()) {
         std::snprintf(buf, sizeof buf, "C grid: marched zone + fold band, %d rows (%ld cells in %d items beside %ld cells of the band and the block edges, "
-                      "five phases and their fold steps)", CG.mf.band_rows, CG.one.strip_cells, CG.one.nitems, CG.mf.rest.ncells);
+                      "five phases and their fold steps%s)", CG.mf.band_rows, CG.one.strip_cells, CG.one.nitems, CG.mf.rest.ncells, avgs);
         return buf;
     }
     if (CG.geo && CG.tripole && march_fold_wanted() == 1 && !(remote() && march_fold())) {
         // asked for and not in use: say why
-        const char *w = (remote() && march_fold_ranks_wanted() != 1) ? "several ranks" : !CG.mf.rest.cells ? CG.mf.why.c_str() : (CG.uploaded && CG.avg_strength) ? "visc_method = avg_strength" : "";
+        const char *w = (remote() && march_fold_ranks_wanted() != 1) ? "several ranks" : !CG.mf.rest.cells ? CG.mf.why.c_str() :
+                        !(CG.uploaded && CG.avg_strength) ? "" : !march_avgs_switch() ? "visc_method = avg_strength" :
+                        !CG.mf.rest.scr[5] ? "visc_method = avg_strength, and its switch was not set when the geometry was" : "";
         if (*w) {
             std::snprintf(buf, sizeof buf, "C grid: five phases + fold steps (marched zone + fold band not in use: %s)", w);
             return buf;
@@ -1382,6 +1453,8 @@ int cice_evp_hip_cgrid_set_geometry(const double *const *static23)
         const std::vector<uint8_t> gm = derive_geometry_check(static23, CG.geo_why);
         if (!gm.empty()) {
             if (CG.mem.upload(CG.gmask, gm)) return -1;
+            if (remote() && S.d.nx_block >= 3 && S.d.ny_block >= 3)
+                if (int rc = build_march_frame_tables(static23)) return rc;
         } else if (verbose()) {
             std::fprintf(stderr, "[cice_evp_hip] C grid: all 23 static arrays stay in use: %s\n", CG.geo_why.c_str());
         }
@@ -1504,7 +1577,7 @@ int cice_evp_hip_cgrid_subcycle(int32_t ndte)
     if (int rc = res_check_error()) return rc;
     if (int rc = res_decide(A)) return rc;       // (first call: the on-chip resident kernel's probe; refuses loudly when forced on a rank it cannot serve)
     const int nres = (fused || CG.tripole) ? res_subcycles(ndte, CG.first) : 0;
-    const bool mfold = nres == 0 && march_fold();
+    const bool mfold = nres == 0 && (march_fold() || march_frame_phases());
     const bool mf_sync = mfold && !CG.first && !CG.mf.synced;
     Ran ran;
     auto enqueue = [&]() -> int {
@@ -1548,6 +1621,7 @@ int cice_evp_hip_cgrid_subcycle(int32_t ndte)
     HIPC(hipGetLastError());
     CG.t_one = ran.one;
     CG.t_march = ran.march;
+    CG.t_march_phases = ran.march_phases;
     CG.t_mfold = ran.mfold;
     CG.t_mfold_ranks = ran.mfold_ranks;
     CG.res.last_nsub = nres;
@@ -2136,6 +2210,10 @@ int cice_evp_hip_cgrid_timings(double *out, int32_t n)
     if (n >= 20) {
         out[18] = (double)CG.t_march;                 // subcycles of the last call that ran as "zone marched + frame" (several ranks)
         out[19] = (double)CG.fr.ncells;               // ... and the frame cells of this rank (0: no such plan here)
+        if (CG.t_march_phases > 0) {      // (the five-phase frame plan ran: its frame cells, its own items)
+            out[19] = (double)CG.mf.frame_cells;
+            out[10] = (double)CG.mf.nitems; out[11] = (double)CG.mf.strip_cells; out[14] = (double)CG.mf.strip_len;
+        }
     }
     if (n >= 23) {
         out[20] = (double)CG.t_mfold;                 // subcycles of the last call that ran as "marched zone + fold band" (tripole grids, one rank)

@@ -82,6 +82,7 @@ TEST_ENV = [
     "CICE_EVP_HIP_CGRID_RES_SLEEP", "CICE_EVP_HIP_CGRID_RES_CULL", "CICE_EVP_HIP_CGRID_RES_DEBUG",
     "CICE_EVP_HIP_CGRID_STRIP", "CICE_EVP_HIP_CGRID_STRIP_SEG", "CICE_EVP_HIP_CGRID_STRIP_EDGE", "CICE_EVP_HIP_CGRID_STRIP_RIDE", "CICE_EVP_HIP_CGRID_STRIP_LEN", "CICE_EVP_HIP_CGRID_STRIP_ITEMS", "CICE_EVP_HIP_CGRID_STRIP_LAST",
     "CICE_EVP_HIP_CGRID_MARCH_RESERVE", "CICE_EVP_HIP_CGRID_MARCH_RANKS", "CICE_EVP_HIP_CGRID_MARCH_FOLD", "CICE_EVP_HIP_CGRID_MARCH_FOLD_SERIAL", "CICE_EVP_HIP_CGRID_MARCH_FOLD_RANKS",
+    "CICE_EVP_HIP_CGRID_MARCH_AVG_STRENGTH",
 ]
 # C-grid subcycle (cice_evp_hip_cgrid_*): order of the pointer tables, see include/cice_evp_hip.h
 CGRID_FIELDS = ["uvelE", "vvelE", "uvelN", "vvelN", "uvel", "vvel", "stresspT", "stressmT", "stress12T", "stress12U",
@@ -362,7 +363,9 @@ def cgrid_march_fold_plan(dims: "Dims", ex=32, ey=8, slots=2048, seg_min=0, seg=
     """Host only: how one rank shares a tripole / tripoleT grid between the marched C-grid kernel (zone) and the list-driven phase
     kernels (the band under the fold and the block edges; see the testing header).  Where the schedule does not apply: a dict with
     `declined` = the reason and nothing else.  ranks=True: the plan of the rank `dims` describes on any rank layout (the rest then
-    holds the frame too); the dict also has `sent` (offsets of the cells other ranks receive), `frame_cells`, `staging_slots`."""
+    holds the frame too); the dict also has `sent` (offsets of the cells other ranks receive), `frame_cells`, `staging_slots`.
+    ranks=True also plans a rank of a grid WITHOUT a fold that has neighbours on other ranks (zone + frame on the five phase
+    kernels, the several-ranks schedule of visc_method = avg_strength there); on one rank such a grid declines either way."""
     lib = load_library(testing=True)
     info = np.zeros(11, dtype=np.int64)
     r3 = np.zeros(3, dtype=np.int64)

@@ -418,11 +418,16 @@ int cice_evp_hip_cgrid_strocn_t(double *strocnxT_iavg, double *strocnyT_iavg);
  * (the reference's start-up means, verified bit for bit on the caller's arrays),
  * [15] .. [17] (n >= 18) tripole grids: 1 if the blocks next to the fold have more than one owner (fold exchange), on how many ranks,
  * staging slots of this rank,
- * [18], [19] (n >= 20) several ranks, no fold, visc_method = avg_zeta: subcycles of the last call that ran as "zone marched + frame" --
+ * [18], [19] (n >= 20) several ranks, no fold: subcycles of the last call that ran as "zone marched + frame" --
  * cg_strip on the interior of the blocks (the items of [10]) on a second stream beside the three fused kernels' frame variants and
  * their five exchanges on every other interior cell --, and those frame cells on this rank (0: no such plan here; a rank without
- * rectangles for the marched kernel runs the fused schedule, and so does every rank under CICE_EVP_HIP_CGRID_ONE=0),
- * [20] .. [22] (n >= 23) tripole / tripoleT grids on ONE rank, visc_method = avg_zeta: subcycles of the last call that ran as "marched
+ * rectangles for the marched kernel runs the fused schedule, and so does every rank under CICE_EVP_HIP_CGRID_ONE=0).  visc_method =
+ * avg_strength takes this schedule on request only (CICE_EVP_HIP_CGRID_MARCH_AVG_STRENGTH=1, as do [20] and [23]; without it: five
+ * phases, the counters read 0 -- and for now the TEST build alone reads that switch, libcice_evp_hip_testing.so: in this library
+ * avg_strength always runs the five phases on these grids): the frame then runs on list-driven variants of the five phase kernels with the five phases'
+ * exchanges, [19] counts the cells another rank receives or that have a ghost image here, and [10], [11], [14] describe that plan's
+ * own items,
+ * [20] .. [22] (n >= 23) tripole / tripoleT grids on ONE rank, either visc_method (avg_strength: on request, above): subcycles of the last call that ran as "marched
  * zone + fold band" -- cg_strip on the rectangles under the fold band beside list-driven variants of the five phase kernels and
  * their fold steps on every other interior cell --, the rows from the zone's top row to the fold, and those other cells,
  * [23] .. [25] (n >= 26) such a grid on SEVERAL ranks: subcycles of the last call that ran as "marched zone + fold band + frame" --

@@ -80,7 +80,10 @@ int cice_evp_hip_cgrid_frame_plan(const cice_evp_hip_dims *dims, int32_t ex, int
  * ranks: 0 the one-rank question ("marched zone + fold band": several ranks decline); 1 the plan of the rank `dims` describes on any
  * rank layout ("marched zone + fold band + frame"): the rest then also holds every cell another rank receives in an in-loop exchange
  * and every cell with a ghost image; a rank without the fold rows plans zone + frame (0 fold band rows).  ranks3 = {sent cells, frame
- * cells -- sent or with a ghost image --, staging slots behind the arrays}; sent: the sent cells' offsets, ascending.  May be NULL.  */
+ * cells -- sent or with a ghost image --, staging slots behind the arrays}; sent: the sent cells' offsets, ascending.  May be NULL.
+ * ranks = 1 on a rank of a grid WITHOUT a fold that has a neighbour on another rank: the plan of "zone marched + frame" with the five
+ * list-driven phase kernels on the frame (visc_method = avg_strength there): no fold cells, no rows cut from the top, 0 fold band rows.
+ * On one rank, or with ranks = 0, such a grid declines ("no tripole fold ...").  */
 int cice_evp_hip_cgrid_march_fold_plan(const cice_evp_hip_dims *dims, int32_t ex, int32_t ey, int32_t slots, int32_t seg_min, int32_t seg, int32_t len,
                                        int64_t *info11, uint8_t *cells, int32_t *wg, int32_t wg_cap, int32_t *items6, int32_t items_cap,
                                        int32_t ranks, int64_t *ranks3, int32_t *sent, int32_t sent_cap);
