@@ -34,7 +34,8 @@ module ice_dyn_evp_hip
             dyn_evp_hip_keep_stresses_resident, dyn_evp_hip_cgrid_deformations, dyn_evp_hip_cgrid_dyn_finish, &
             dyn_evp_hip_cgrid_evp_body, &
             dyn_evp_hip_cgrid_fetch_forcing, &
-            dyn_evp_hip_cgrid_tail, dyn_evp_hip_cgrid_dyn_finish_u, dyn_evp_hip_strocn_t, dyn_evp_hip_principal_stress
+            dyn_evp_hip_cgrid_tail, dyn_evp_hip_cgrid_dyn_finish_u, dyn_evp_hip_strocn_t, dyn_evp_hip_principal_stress, &
+            dyn_evp_hip_dyn_finish
 
   ! mirror of cice_evp_hip_dims (include/cice_evp_hip.h)
   type, bind(C) :: cice_evp_hip_dims
@@ -240,6 +241,12 @@ module ice_dyn_evp_hip
        real(c_double), intent(inout) :: strocnxN(*), strocnyN(*), strocnxE(*), strocnyE(*)
      end function cice_evp_hip_cgrid_dyn_finish
 
+     ! dyn_finish at U points on the B grid, from the state the loop left on the device (include/cice_evp_hip.h)
+     integer(c_int) function cice_evp_hip_dyn_finish(strocnxU, strocnyU) bind(C, name='cice_evp_hip_dyn_finish')
+       import :: c_int, c_double
+       real(c_double), intent(inout) :: strocnxU(*), strocnyU(*)
+     end function cice_evp_hip_dyn_finish
+
      ! after the loop, before transport (include/cice_evp_hip.h)
      integer(c_int) function cice_evp_hip_cgrid_tail(strintxE, strintyN, strintxU, strintyU, flags) &
           bind(C, name='cice_evp_hip_cgrid_tail')
@@ -342,6 +349,9 @@ module ice_dyn_evp_hip
   logical :: stress_resident_requested = .false.
   logical :: body_sig_on_device = .false.   ! Option A with resident stresses: the device copy is current (dyn_evp_hip_evp_body)
   logical :: on_tripole = .false.
+  ! tripole / tripoleT: the device copy of the stresses has had the symmetrisation of ice_dyn_evp.F90:1321-1389 (Option A always;
+  ! dyn_evp_hip_run only with resident stresses -- otherwise evp() applies it to the host arrays alone)
+  logical :: device_sig_symmetric = .false.
   logical :: cgrid_geometry_set = .false.
   logical :: cgrid_pinned = .false.
   logical :: cgrid_prep_geometry_set = .false.
@@ -672,8 +682,10 @@ contains
        call check(cice_evp_hip_set_tbu(TbU), subname, __FILE__, __LINE__)
     endif
     call check(cice_evp_hip_subcycle(int(ndte, c_int32_t)), subname, __FILE__, __LINE__)
-    if (trim(ns_boundary_type) == 'tripole' .or. trim(ns_boundary_type) == 'tripoleT') &
+    if (trim(ns_boundary_type) == 'tripole' .or. trim(ns_boundary_type) == 'tripoleT') then
        call check(cice_evp_hip_stress_halo(), subname, __FILE__, __LINE__)
+       device_sig_symmetric = .true.
+    endif
 
     out32 = c_null_ptr
     if (.not. stress_resident) out32(1:12) = s12
@@ -758,8 +770,11 @@ contains
          tmask_i, umask_i, int(ndte, c_int32_t)), subname, __FILE__, __LINE__)
     ! stresses resident on a tripole grid: evp()'s 12 x ice_HaloUpdate_stress after the loop (ice_dyn_evp.F90:1321-1389)
     ! act on the stale host arrays; the device copy gets the same symmetrisation here
-    if (stress_resident .and. on_tripole) &
+    device_sig_symmetric = .false.
+    if (stress_resident .and. on_tripole) then
        call check(cice_evp_hip_stress_halo(), subname, __FILE__, __LINE__)
+       device_sig_symmetric = .true.
+    endif
     call ice_timer_stop(timer_evp1dcore)
     call report_path_once()
 
@@ -1149,7 +1164,8 @@ contains
   ! The end of evp() for grid_ice = 'C' (ice_dyn_evp.F90:1436-1443) on the device: the halo updates of strintxE / strintyN over
   ! the plain halo_info and the diagnostics strintxU = E2US(strintxE), strintyU = N2US(strintyN).  Collective.  A host that
   ! calls this drops its own two ice_HaloUpdate calls and the two grid_average_X2Y calls after the loop.
-  ! (The three wrappers below and this one are compile-checked only: no harness of this repository runs them.)
+  ! (This wrapper and the four below run in oracle/ref/evp_ref_harness.F90 under `hiptail`, next to the reference's own
+  ! routines: tests/test_gpu_dropin_tail.py.)
   subroutine dyn_evp_hip_cgrid_tail
     use ice_flux, only: strintxE, strintyN, strintxU, strintyU
     character(len=*), parameter :: subname = '(dyn_evp_hip_cgrid_tail)'
@@ -1171,9 +1187,21 @@ contains
     call check(cice_evp_hip_cgrid_dyn_finish_u(cdn_ocnU, aiU, uocnU, vocnU, fmU, strocnxU, strocnyU), subname, __FILE__, __LINE__)
   end subroutine dyn_evp_hip_cgrid_dyn_finish_u
 
+  ! dyn_finish at U points on the B grid (ice_dyn_evp.F90:1395-1406) on the device, from the state the loop left there
+  ! (dyn_evp_hip_run or dyn_evp_hip_evp_body): ice_flux's strocnxU / strocnyU are written on the ice U-cells; every other cell
+  ! keeps what the arrays hold (the +0 of dyn_prep2 on the physical cells).  The device keeps the result for
+  ! dyn_evp_hip_strocn_t(.false.), which refuses to run without it.
+  subroutine dyn_evp_hip_dyn_finish
+    use ice_flux, only: strocnxU, strocnyU
+    character(len=*), parameter :: subname = '(dyn_evp_hip_dyn_finish)'
+    if (.not. initialised) call abort_ice(subname//' ERROR: dyn_evp_hip_init not called', file=__FILE__, line=__LINE__)
+    if (empty_rank) return
+    call check(cice_evp_hip_dyn_finish(strocnxU, strocnyU), subname, __FILE__, __LINE__)
+  end subroutine dyn_evp_hip_dyn_finish
+
   ! The first thing step_dyn_horiz does after evp() (general/ice_step_mod.F90:1012-1041): strocn{x,y}T_iavg from the
-  ! strocn{x,y}U the device's dyn_finish of this call left there (B grid: cice_evp_hip_dyn_finish; cgrid = .true.:
-  ! dyn_evp_hip_cgrid_dyn_finish_u).  Collective (the halo update of work1 / work2 runs over the plain halo).  A host that calls
+  ! strocn{x,y}U the device's dyn_finish of this call left there (cgrid = .false.: dyn_evp_hip_dyn_finish; cgrid = .true.:
+  ! dyn_evp_hip_cgrid_dyn_finish_u), which therefore comes first.  Collective (the halo update of work1 / work2 runs over the plain halo).  A host that calls
   ! this drops the block of step_dyn_horiz between `call evp (dt)` and the transport.
   subroutine dyn_evp_hip_strocn_t(cgrid)
     use ice_grid, only: uarea, tarea
@@ -1191,14 +1219,28 @@ contains
 
   ! principal_stress on corner 1 (ice_history.F90:3802-3811) from the stresses and the strength on the device: with the
   ! stresses resident (dyn_evp_hip_keep_stresses_resident) the history output needs no dyn_evp_hip_fetch_stresses for it.
-  ! Call it where the device still holds the call's final state: after dyn_evp_hip_run, before the next one.
+  ! Call it where the device still holds the call's final state: after evp() has returned (dyn_evp_hip_run or
+  ! dyn_evp_hip_evp_body inside it), before the next one.  On a tripole / tripoleT grid the values of the top row are those of
+  ! the SYMMETRISED stresses (ice_dyn_evp.F90:1321-1389), which is what the history output reads on the host.  After
+  ! dyn_evp_hip_run without resident stresses evp() has symmetrised the host arrays only: the device copy gets the same step
+  ! here first (cice_evp_hip_stress_halo: collective where the top row has several owners, so every task calls this routine).
+  ! Where the library leaves that step to the host (tripoleT next to an eliminated block) the call is refused.
   subroutine dyn_evp_hip_principal_stress
+    use ice_domain, only: ns_boundary_type
     use ice_flux, only: sig1, sig2, sigP
     use icepack_intfc, only: icepack_query_parameters
     real(kind=dbl_kind) :: puny
     character(len=*), parameter :: subname = '(dyn_evp_hip_principal_stress)'
     if (.not. initialised) call abort_ice(subname//' ERROR: dyn_evp_hip_init not called', file=__FILE__, line=__LINE__)
     if (empty_rank) return
+    if ((trim(ns_boundary_type) == 'tripole' .or. trim(ns_boundary_type) == 'tripoleT') .and. &
+        .not. device_sig_symmetric) then
+       if (.not. on_tripole) call abort_ice(subname//' ERROR: tripoleT: on this layout the stress symmetrisation stays '// &
+            'with the host, so the device copy is not the one the history output reads: call principal_stress on the '// &
+            'host arrays instead', file=__FILE__, line=__LINE__)
+       call check(cice_evp_hip_stress_halo(), subname, __FILE__, __LINE__)
+       device_sig_symmetric = .true.
+    endif
     call icepack_query_parameters(puny_out=puny)
     call check(cice_evp_hip_principal_stress(puny, sig1, sig2, sigP), subname, __FILE__, __LINE__)
   end subroutine dyn_evp_hip_principal_stress
@@ -1286,6 +1328,7 @@ contains
     wind_from_strax = .false.
     empty_rank = .false.
     pinned = .false.
+    device_sig_symmetric = .false.
   end subroutine dyn_evp_hip_finalize
 
 end module ice_dyn_evp_hip

@@ -224,8 +224,10 @@ int cice_evp_hip_dyn_finish(double *strocnxU, double *strocnyU);
  * cice_evp_hip_principal_stress (ice_dyn_shared.F90:1691-1747; called by ice_history.F90:3802-3811 on corner 1): sig1, sig2,
  * sigP from stressp_1, stressm_1, stress12_1 and the strength as they are on the device, on every cell of every block array
  * (ghost cells included: the reference loops over 1..nx_block x 1..ny_block); where strength <= puny the three take spval_dbl
- * = 1.0e30 (ice_constants.F90:27).  Call it between the loop and cice_evp_hip_download, on tripole grids after
- * cice_evp_hip_stress_halo.  With CICE_EVP_HIP_OPT_STRESS_RESIDENT the history output then needs no cice_evp_hip_fetch_stresses:
+ * = 1.0e30 (ice_constants.F90:27).  Call it between the loop and the next call's upload, on tripole / tripoleT grids after
+ * cice_evp_hip_stress_halo: the host's principal_stress reads the symmetrised stresses, and the step changes component 1 on the
+ * top physical row (tripoleT) or the ghost row north of it (tripole).  After cice_evp_hip_run without resident stresses nobody
+ * has applied it to the device copy -- the caller does (the Fortran wrapper dyn_evp_hip_principal_stress does so itself).  With CICE_EVP_HIP_OPT_STRESS_RESIDENT the history output then needs no cice_evp_hip_fetch_stresses:
  * three arrays come back instead of twelve.                                                                               */
 int cice_evp_hip_strocn_t(const double *uarea, const double *tarea, double *strocnxT_iavg, double *strocnyT_iavg);
 int cice_evp_hip_principal_stress(double puny, double *sig1, double *sig2, double *sigP);

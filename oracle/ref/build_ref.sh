@@ -84,7 +84,9 @@ build_variant () {
     $FC $fflags -cpp -c "$HERE/icepack_intfc_stub.F90" -o icepack_intfc.o
     for f in "${SRCS[@]}"; do
       b=$(basename "$f" .F90)
-      if [ ! -f "$b.o" ] || [ "$f" -nt "$b.o" ]; then
+      # (every module of the reference uses the Icepack stub's module file: a change of the stub recompiles them all)
+      # BUILD_REF_FORCE: objects of unknown origin lie in the cache (their time stamps say nothing): compile all of them
+      if [ -n "${BUILD_REF_FORCE:-}" ] || [ ! -f "$b.o" ] || [ "$f" -nt "$b.o" ] || [ "$HERE/icepack_intfc_stub.F90" -nt "$b.o" ]; then
         $FC $fflags -cpp -c "$f" -o "$b.o"
       fi
     done

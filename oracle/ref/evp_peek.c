@@ -10,6 +10,7 @@
 DESC(uocne) DESC(vocne) DESC(cdn_ocne) DESC(waterxe) DESC(forcexe) DESC(aie) DESC(rheofacte) DESC(emassdti)
 DESC(uocnn) DESC(vocnn) DESC(cdn_ocnn) DESC(wateryn) DESC(forceyn) DESC(ain) DESC(rheofactn) DESC(nmassdti)
 DESC(zetax2t) DESC(etax2t) DESC(etax2u) DESC(shearu) DESC(deltau)
+DESC(cdn_ocnu) DESC(uocnu) DESC(vocnu)      /* what a patched evp() hands dyn_evp_hip_cgrid_dyn_finish_u */
 #define BASE(n) (*(void **)_QMice_dyn_evpE##n)
 void *evp_peek_base(int which)
 {
@@ -22,6 +23,7 @@ void *evp_peek_base(int which)
     case 15: return BASE(rheofactn); case 16: return BASE(nmassdti);
     case 17: return BASE(zetax2t);  case 18: return BASE(etax2t);  case 19: return BASE(etax2u);
     case 20: return BASE(shearu);   case 21: return BASE(deltau);
+    case 22: return BASE(cdn_ocnu); case 23: return BASE(uocnu);   case 24: return BASE(vocnu);
     default: return NULL;
     }
 }

@@ -25,12 +25,12 @@ module evp_cgrid_capture
   use ice_domain_size, only: max_blocks, ncat
   use ice_blocks, only: nx_block, ny_block
   use ice_state, only: uvel, vvel, uvelE, vvelE, uvelN, vvelN, strength, divu, shear, vort, aice, vice, vsno, aice_init, &
-                       aice0, aicen, vicen
+                       aice0, aicen, vicen, aiU
   use ice_blocks, only: block, get_block
   use ice_domain, only: blocks_ice, halo_info
   use ice_boundary, only: ice_HaloUpdate
-  use ice_constants, only: field_loc_center, field_type_scalar, c0, c1
-  use ice_grid, only: tmask
+  use ice_constants, only: field_loc_center, field_type_scalar, field_loc_NEcorner, field_type_vector, c0, c1
+  use ice_grid, only: tmask, grid_ice, grid_average_X2Y
   use ice_arrays_column, only: Cdn_ocn
   use ice_flux
   use ice_calendar, only: dt_dyn
@@ -38,7 +38,8 @@ module evp_cgrid_capture
   use ice_dyn_evp, only: evp, ratiodxN, ratiodxNr, ratiodyE, ratiodyEr
 #ifdef HARNESS_HIP_BODY
   use ice_dyn_evp_hip, only: dyn_evp_hip_cgrid_run, dyn_evp_hip_cgrid_deformations, dyn_evp_hip_cgrid_evp_body, &
-       dyn_evp_hip_cgrid_dyn_finish
+       dyn_evp_hip_cgrid_dyn_finish, dyn_evp_hip_cgrid_tail, dyn_evp_hip_cgrid_dyn_finish_u, dyn_evp_hip_strocn_t, &
+       dyn_evp_hip_principal_stress, dyn_evp_hip_dyn_finish
 #endif
   use evp_dumpio
   implicit none
@@ -47,7 +48,115 @@ module evp_cgrid_capture
   real(dbl_kind), allocatable, dimension(:,:,:), private :: q_uE, q_vN, q_uN, q_vE, q_spT, q_smT, q_s12T, q_s12U, q_u, q_v, &
                                                             q_sxE, q_syN
   logical(log_kind), allocatable, dimension(:,:,:), private :: q_mU, q_mE, q_mN
+  ! hiptail: what the host does between "evp() has returned" and "transport may start", by the reference's own routines and
+  ! by the shim's post-loop wrappers.  Every output array of a wrapper is overwritten with tail_sentinel before the call.
+  logical :: hiptail = .false.
+  real(dbl_kind), parameter :: tail_sentinel = -7.e77_dbl_kind
+  real(dbl_kind), allocatable, dimension(:,:,:), private :: t_w1, t_w2
 contains
+
+  ! hiptail, reference side (every build): from the state the reference's evp() has just left --
+  !   strocn{x,y}T_iavg as step_dyn_horiz forms them (general/ice_step_mod.F90:1012-1041; ice_step_mod is not in the build):
+  !     the quotient strocn{x,y}U / aiU where aiU /= 0 on the physical cells of two zeroed work arrays, the reference's
+  !     ice_HaloUpdate at the NE corner, the reference's grid_average_X2Y('F', U -> T);
+  !   B grid: sig1 / sig2 / sigP by the reference's principal_stress on corner 1, block by block, as ice_history.F90:3802-3809;
+  !   C grid: strocn{x,y}U and the diagnostics strint{x,y}U, which evp() itself has written (ice_dyn_evp.F90:1395-1406, 1442-1443).
+  ! The inputs (aiU, the strength) are dumped with them: tests/test_ref_tail_cpu.py restates every step in numpy.
+  subroutine ref_tail(tg)
+    character(len=*), intent(in) :: tg
+    integer(int_kind) :: ib, i, j
+    type(block) :: tb
+    if (.not. allocated(t_w1)) allocate(t_w1(nx_block,ny_block,max_blocks), t_w2(nx_block,ny_block,max_blocks))
+    t_w1 = c0; t_w2 = c0
+    do ib = 1, nblocks
+       tb = get_block(blocks_ice(ib), ib)
+       do j = tb%jlo, tb%jhi
+       do i = tb%ilo, tb%ihi
+          if (aiU(i,j,ib) /= c0) then
+             t_w1(i,j,ib) = strocnxU(i,j,ib)/aiU(i,j,ib)
+             t_w2(i,j,ib) = strocnyU(i,j,ib)/aiU(i,j,ib)
+          endif
+       enddo
+       enddo
+    enddo
+    call ice_HaloUpdate(t_w1, halo_info, field_loc_NEcorner, field_type_vector)
+    call ice_HaloUpdate(t_w2, halo_info, field_loc_NEcorner, field_type_vector)
+    strocnxT_iavg = tail_sentinel; strocnyT_iavg = tail_sentinel
+    call grid_average_X2Y('F', t_w1, 'U', strocnxT_iavg, 'T')
+    call grid_average_X2Y('F', t_w2, 'U', strocnyT_iavg, 'T')
+    call dump_r8_3d(trim(tg)//'_aiU', aiU, nblocks)
+    call dump_r8_3d(trim(tg)//'_strocnxT_iavg', strocnxT_iavg, nblocks)
+    call dump_r8_3d(trim(tg)//'_strocnyT_iavg', strocnyT_iavg, nblocks)
+    if (trim(grid_ice) == 'C') then
+       call dump_r8_3d(trim(tg)//'_strocnxU', strocnxU, nblocks); call dump_r8_3d(trim(tg)//'_strocnyU', strocnyU, nblocks)
+       call dump_r8_3d(trim(tg)//'_strintxU', strintxU, nblocks); call dump_r8_3d(trim(tg)//'_strintyU', strintyU, nblocks)
+    else
+       sig1 = tail_sentinel; sig2 = tail_sentinel; sigP = tail_sentinel
+       do ib = 1, nblocks
+          call principal_stress(nx_block, ny_block, stressp_1(:,:,ib), stressm_1(:,:,ib), stress12_1(:,:,ib), &
+                                strength(:,:,ib), sig1(:,:,ib), sig2(:,:,ib), sigP(:,:,ib))
+       enddo
+       call dump_r8_3d(trim(tg)//'_strength', strength, nblocks)
+       call dump_r8_3d(trim(tg)//'_sig1', sig1, nblocks); call dump_r8_3d(trim(tg)//'_sig2', sig2, nblocks)
+       call dump_r8_3d(trim(tg)//'_sigP', sigP, nblocks)
+    endif
+  end subroutine ref_tail
+
+#ifdef HARNESS_HIP_BODY
+  ! dyn_finish writes the cells of dyn_prep2's U list and nothing else (its arrays are inout): the sentinel goes exactly there,
+  ! so that the array equals the reference's on EVERY cell only if each of them was written and no other cell touched
+  subroutine sentinel_on_ice_u()
+    integer(int_kind) :: ib, i, j
+    type(block) :: tb
+    do ib = 1, nblocks
+       tb = get_block(blocks_ice(ib), ib)
+       do j = tb%jlo, tb%jhi
+       do i = tb%ilo, tb%ihi
+          if (iceUmask(i,j,ib)) then
+             strocnxU(i,j,ib) = tail_sentinel; strocnyU(i,j,ib) = tail_sentinel
+          endif
+       enddo
+       enddo
+    enddo
+  end subroutine sentinel_on_ice_u
+
+  ! hiptail, device side, B grid: the three wrappers a host calls after evp() has returned, from the state this HIP run
+  ! (Option B behind dyn_evp1d_run, or Option A) left on the device
+  subroutine hip_bgrid_tail(tg)
+    character(len=*), intent(in) :: tg
+    sig1 = tail_sentinel; sig2 = tail_sentinel; sigP = tail_sentinel
+    call dyn_evp_hip_principal_stress
+    call dump_r8_3d(trim(tg)//'_sig1', sig1, nblocks); call dump_r8_3d(trim(tg)//'_sig2', sig2, nblocks)
+    call dump_r8_3d(trim(tg)//'_sigP', sigP, nblocks)
+    call sentinel_on_ice_u()
+    call dyn_evp_hip_dyn_finish
+    call dump_r8_3d(trim(tg)//'_tl_strocnxU', strocnxU, nblocks); call dump_r8_3d(trim(tg)//'_tl_strocnyU', strocnyU, nblocks)
+    strocnxT_iavg = tail_sentinel; strocnyT_iavg = tail_sentinel
+    call dyn_evp_hip_strocn_t(.false.)
+    call dump_r8_3d(trim(tg)//'_strocnxT_iavg', strocnxT_iavg, nblocks)
+    call dump_r8_3d(trim(tg)//'_strocnyT_iavg', strocnyT_iavg, nblocks)
+  end subroutine hip_bgrid_tail
+
+  ! hiptail, device side, C grid: the end of evp() and the start of step_dyn_horiz through the three wrappers.  strintxE /
+  ! strintyN are put back afterwards (the next run of this call starts from what the loop returned, as without hiptail).
+  subroutine hip_cgrid_tail(tg)
+    character(len=*), intent(in) :: tg
+    if (.not. allocated(t_w1)) allocate(t_w1(nx_block,ny_block,max_blocks), t_w2(nx_block,ny_block,max_blocks))
+    t_w1 = strintxE; t_w2 = strintyN
+    strintxE = tail_sentinel; strintyN = tail_sentinel; strintxU = tail_sentinel; strintyU = tail_sentinel
+    call dyn_evp_hip_cgrid_tail
+    call dump_r8_3d(trim(tg)//'_tl_strintxE', strintxE, nblocks); call dump_r8_3d(trim(tg)//'_tl_strintyN', strintyN, nblocks)
+    call dump_r8_3d(trim(tg)//'_strintxU', strintxU, nblocks);    call dump_r8_3d(trim(tg)//'_strintyU', strintyU, nblocks)
+    strintxE = t_w1; strintyN = t_w2
+    call sentinel_on_ice_u()
+    call dyn_evp_hip_cgrid_dyn_finish_u(pk3(22), pk3(23), pk3(24))      ! cdn_ocnU, uocnU, vocnU of ice_dyn_evp
+    call dump_r8_3d(trim(tg)//'_strocnxU', strocnxU, nblocks); call dump_r8_3d(trim(tg)//'_strocnyU', strocnyU, nblocks)
+    strocnxT_iavg = tail_sentinel; strocnyT_iavg = tail_sentinel
+    call dyn_evp_hip_strocn_t(.true.)
+    call dump_r8_3d(trim(tg)//'_strocnxT_iavg', strocnxT_iavg, nblocks)
+    call dump_r8_3d(trim(tg)//'_strocnyT_iavg', strocnyT_iavg, nblocks)
+  end subroutine hip_cgrid_tail
+#endif
 
   ! the ice cover between two calls: some cells lose their ice, some open-water cells gain some (dyn_prep2's
   ! "new ice starts at the ocean velocity" / "no ice: zero" branches, ice_dyn_shared.F90:747-764)
@@ -278,6 +387,7 @@ contains
           call dyn_evp_hip_cgrid_dyn_finish
           call dump_r8_3d(trim(tg)//'_strocnxN', strocnxN, nblocks); call dump_r8_3d(trim(tg)//'_strocnyN', strocnyN, nblocks)
           call dump_r8_3d(trim(tg)//'_strocnxE', strocnxE, nblocks); call dump_r8_3d(trim(tg)//'_strocnyE', strocnyE, nblocks)
+          if (hiptail) call hip_cgrid_tail(trim(tg))
           write(*,'(a,i3,a,i5,3es24.16)') 'Hcall', ic, ' nsub', ns, &
                maxval(abs(uvelE(:,:,1:nblocks))), maxval(abs(vvelN(:,:,1:nblocks))), maxval(abs(stresspT(:,:,1:nblocks)))
        enddo
@@ -307,6 +417,7 @@ contains
        ! dyn_finish at N and E points (ice_dyn_evp.F90:1408-1436)
        call dump_r8_3d(trim(tg)//'_strocnxN', strocnxN, nblocks); call dump_r8_3d(trim(tg)//'_strocnyN', strocnyN, nblocks)
        call dump_r8_3d(trim(tg)//'_strocnxE', strocnxE, nblocks); call dump_r8_3d(trim(tg)//'_strocnyE', strocnyE, nblocks)
+       if (hiptail) call ref_tail(trim(tg))
        write(*,'(a,i3,a,i5,3es24.16)') 'Ccall', ic, ' nsub', ns, &
             maxval(abs(uvelE(:,:,1:nblocks))), maxval(abs(vvelN(:,:,1:nblocks))), maxval(abs(stresspT(:,:,1:nblocks)))
     enddo
@@ -353,8 +464,11 @@ program evp_ref_harness
       dyn_evp_hip_keep_stresses_resident
 #endif
   use evp_dumpio
-  use evp_cgrid_capture, only: cgrid_call, evolve_ice, split_categories, dump_categories
-  use icepack_intfc, only: icepack_query_parameters
+  use evp_cgrid_capture, only: cgrid_call, evolve_ice, split_categories, dump_categories, hiptail, ref_tail
+#ifdef HARNESS_HIP_BODY
+  use evp_cgrid_capture, only: hip_bgrid_tail
+#endif
+  use icepack_intfc, only: icepack_query_parameters, stub_calc_strair
 #if defined (_OPENMP)
   use OMP_LIB
 #endif
@@ -398,12 +512,17 @@ program evp_ref_harness
   character(len=16)  :: h_visc_method = 'avg_zeta' ! C grid: 'avg_zeta' | 'avg_strength' (ice_dyn_evp.F90:992-996)
   integer(int_kind)  :: h_ncat      = 1           ! thickness categories; > 1: aice / vice split over them (split_categories)
   real(dbl_kind)     :: h_hw_span   = 40._dbl_kind ! with h_seabed: hwater = 8 + h_hw_span * y (> 42: deeper than 50 m in the north)
+  ! (hiptail, a variable of evp_cgrid_capture: after every evp() also what the host computes next -- the reference's own
+  !  routines after its runs, the shim's post-loop wrappers after the HIP runs of the drop-in build)
+  character(len=8)   :: h_grid_ocn  = 'A'         ! 'A' | 'B' | 'C': where uocn / vocn / ss_tltx / ss_tlty live (ice_init.F90:2036-2054)
+  character(len=8)   :: h_grid_atm  = 'A'         ! 'A' | 'B' | 'C': where strax / stray live (ice_init.F90:2016-2034)
+  logical            :: h_calc_strair = .true.    ! .false.: the wind stress is strax / stray, not strairxT / strairyT
 
   namelist /harness_nml/ grid_kind, kmt_kind, icecase, dumpfile, h_grid_file, h_kmt_file, &
      h_dxrect, h_dyrect, h_dt, h_ndte, ncalls, nsub_list, h_revised, h_arlx, h_brlx, &
      h_capping, h_Ktens, h_e_yield, h_e_plast, h_elasticDamp, h_coriolis, h_seabed, h_seabed_method, &
      dump_arrays, ntiming, hipmode, hipbody, hipresident, time_1d, h_grid_ice, h_visc_method, h_evolve, h_ssh, &
-     h_ncat, h_hw_span
+     h_ncat, h_hw_span, hiptail, h_grid_ocn, h_grid_atm, h_calc_strair
 
   ! ---- locals ----------------------------------------------------------
   integer(int_kind) :: i, j, iblk, icall, k, nsub, nl, ios, nthreads
@@ -439,9 +558,11 @@ program evp_ref_harness
   n_iso=0; n_aero=0; n_zaero=0; n_algae=0; n_doc=0; n_dic=0; n_don=0; n_fed=0; n_fep=0
   nfreq=1
 
-  grid_format='bin'; grid_ice=trim(h_grid_ice); grid_atm='A'; grid_ocn='A'
-  grid_atm_thrm='T'; grid_atm_dynu='T'; grid_atm_dynv='T'
-  grid_ocn_thrm='T'; grid_ocn_dynu='T'; grid_ocn_dynv='T'
+  grid_format='bin'; grid_ice=trim(h_grid_ice); grid_atm=trim(h_grid_atm); grid_ocn=trim(h_grid_ocn)
+  ! the points of the forcing, as ice_init derives them from grid_atm / grid_ocn (general/ice_init.F90:2016-2054)
+  grid_atm_thrm='T'; call forcing_points(h_grid_atm, grid_atm_dynu, grid_atm_dynv)
+  grid_ocn_thrm='T'; call forcing_points(h_grid_ocn, grid_ocn_dynu, grid_ocn_dynv)
+  stub_calc_strair = h_calc_strair
   dxrect=h_dxrect; dyrect=h_dyrect; scale_dxdy=.false.
   lonrefrect=-156.5_dbl_kind; latrefrect=71.35_dbl_kind
   bathymetry_format='default'; use_bathymetry=.false.
@@ -526,6 +647,12 @@ program evp_ref_harness
         endif
         strairxT(i,j,iblk) = aice(i,j,iblk)*0.1_dbl_kind*sin(twopi*x)*sin(p5*twopi*y)
         strairyT(i,j,iblk) = aice(i,j,iblk)*0.1_dbl_kind*sin(p5*twopi*x)*sin(twopi*y)
+        if (.not. h_calc_strair) then
+           ! the wind stress a coupler supplies at the grid_atm points: smooth, and not strairxT / strairyT (a wrapper that
+           ! hands over the wrong pair cannot pass).  evp() reads the arrays as they are, without a halo update (:467-468)
+           strax(i,j,iblk) = 0.08_dbl_kind*cos(twopi*x)*sin(p5*twopi*y + 0.3_dbl_kind) + 0.01_dbl_kind
+           stray(i,j,iblk) = -0.06_dbl_kind*sin(twopi*x + 0.7_dbl_kind)*cos(twopi*y) + 0.02_dbl_kind
+        endif
         if (h_seabed) hwater(i,j,iblk) = 8._dbl_kind + h_hw_span*y   ! shallow shelf in the south
      enddo
      enddo
@@ -719,6 +846,7 @@ program evp_ref_harness
            call dump_r8_3d(trim(tag)//'_shear', shear, nblocks)
            call dump_r8_3d(trim(tag)//'_strocnxU', strocnxU, nblocks)
 #ifdef HARNESS_HIP_BODY
+           if (hiptail) call hip_bgrid_tail(trim(tag))
            if (hipbody) then
               ! Option A: evp()'s preparation phase + loop (+ tripole stress symmetrisation) through
               ! dyn_evp_hip_evp_body, ice strength by callback -- from the same state
@@ -750,6 +878,7 @@ program evp_ref_harness
               call dump_r8_3d(trim(tag)//'_strintyU', strintyU, nblocks)
               call dump_r8_3d(trim(tag)//'_taubxU', taubxU, nblocks)
               call dump_r8_3d(trim(tag)//'_taubyU', taubyU, nblocks)
+              if (hiptail) call hip_bgrid_tail(trim(tag))
               if (hipresident) then
                  ! resident stresses, two evp() bodies in a row: the second one neither uploads nor downloads the 12 stresses
                  ! (they are where the first one left them); against the reference's evp() called twice from the same state
@@ -819,6 +948,7 @@ program evp_ref_harness
            call dump_r8_3d(trim(tag)//'_rdg_shear', rdg_shear, nblocks)
            call dump_r8_3d(trim(tag)//'_strocnxU', strocnxU, nblocks)
            call dump_r8_3d(trim(tag)//'_strocnyU', strocnyU, nblocks)
+           if (hiptail) call ref_tail(trim(tag))
         endif
         write(*,'(a,i3,a,i5,3es24.16)') 'call', icall, ' nsub', nsub, &
              maxval(abs(uvel(:,:,1:nblocks))), maxval(abs(vvel(:,:,1:nblocks))), &
@@ -853,6 +983,18 @@ program evp_ref_harness
   call end_run                 ! MPI_Finalize in the mpi* builds (comm/mpi/ice_exit.F90), nothing in the serial ones
 
 contains
+
+  subroutine forcing_points(g, dynu, dynv)
+    character(len=*), intent(in) :: g
+    character(len=*), intent(out) :: dynu, dynv
+    select case (trim(g))
+    case ('A'); dynu = 'T'; dynv = 'T'
+    case ('B'); dynu = 'U'; dynv = 'U'
+    case ('C'); dynu = 'E'; dynv = 'N'
+    case default
+       stop 'h_grid_ocn / h_grid_atm: A, B or C'
+    end select
+  end subroutine forcing_points
 
   ! what evp() does for the ice strength between its preparation phase and the loop
   ! (ice_dyn_evp.F90:541-552, 727-728): callback of dyn_evp_hip_evp_body

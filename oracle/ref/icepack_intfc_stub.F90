@@ -47,6 +47,10 @@
 
       integer, parameter, private :: dk = icepack_dbl_kind
 
+      ! what icepack_query_parameters answers for calc_strair_out: the harness sets it (h_calc_strair) before the first
+      ! evp() so that the reference's calc_strair = .false. branch (ice_dyn_evp.F90:467-468, 480-484) can be taken
+      logical :: stub_calc_strair = .true.
+
       contains
 
 !-----------------------------------------------------------------------
@@ -87,7 +91,7 @@
       if (present(zref_out))       zref_out = 10._dk
       if (present(iceruf_out))     iceruf_out = 0.0005_dk
       if (present(dragio_out))     dragio_out = 0.00536_dk
-      if (present(calc_strair_out)) calc_strair_out = .true.
+      if (present(calc_strair_out)) calc_strair_out = stub_calc_strair
       if (present(calc_dragio_out)) calc_dragio_out = .false.
       if (present(formdrag_out))   formdrag_out = .false.
       if (present(skl_bgc_out))    skl_bgc_out = .false.

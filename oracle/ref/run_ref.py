@@ -47,6 +47,16 @@ def have_ref(variant: str = "strict") -> bool:
     return p.exists() and os.access(p, os.X_OK)
 
 
+def harness_knows(variant: str, *switches: str) -> bool:
+    """True if the harness binary is there AND its namelist has every one of these items (their names are strings of the
+    binary).  oracle/_ref is not under version control: a binary built from an older harness source may lie there on a
+    machine that cannot rebuild it (no reference tree), and a test of a newer switch skips as it does without a binary."""
+    if not have_ref(variant):
+        return False
+    blob = harness_path(variant).read_bytes()
+    return all(s.lower().encode("ascii") in blob for s in switches)
+
+
 def read_dump(path) -> dict:
     """Parse the record stream written by evp_dumpio (see ice_dyn_evp1d_capture.F90):
     name(32 chars) | type code int32 (1=f64, 2=i32) | d1 d2 d3 int32 | payload (Fortran order)."""

@@ -47,10 +47,22 @@ CGRID_FIELDS = ["uvelE", "vvelE", "uvelN", "vvelN", "uvel", "vvel", "stresspT", 
 CGRID_DOWNSTREAM = ["divu", "shear", "vort", "rdg_conv", "rdg_shear", "strocnxN", "strocnyN", "strocnxE", "strocnyE"]
 
 
-def run_case(tmp_path, nx, ny, bx, by, ew, ns, nprocs, dist, body, kw, ndte=24, cgrid=False, maskhalo=False):
+# hiptail (tests/test_gpu_dropin_tail.py): (array the wrappers wrote, array the reference's own routines wrote)
+CGRID_TAIL = [("tl_strintxE", "strintxE"), ("tl_strintyN", "strintyN"), ("strintxU", "strintxU"), ("strintyU", "strintyU"),
+              ("strocnxU", "strocnxU"), ("strocnyU", "strocnyU"), ("strocnxT_iavg", "strocnxT_iavg"),
+              ("strocnyT_iavg", "strocnyT_iavg")]
+B_TAIL = [("sig1", "sig1"), ("sig2", "sig2"), ("sigP", "sigP"), ("tl_strocnxU", "strocnxU"), ("tl_strocnyU", "strocnyU"),
+          ("strocnxT_iavg", "strocnxT_iavg"), ("strocnyT_iavg", "strocnyT_iavg")]
+
+
+def run_case(tmp_path, nx, ny, bx, by, ew, ns, nprocs, dist, body, kw, ndte=24, cgrid=False, maskhalo=False, tail=False):
     FIELDS, DOWNSTREAM = (CGRID_FIELDS, CGRID_DOWNSTREAM) if cgrid else (B_FIELDS, B_DOWNSTREAM)
     if cgrid:
         kw = dict(kw, h_grid_ice="C")
+    if tail:
+        kw = dict(kw, hiptail=True)
+        if not (run_ref.harness_knows("hip_dropin_mpi", "hiptail") and (not run_ref.have_ref("strict") or run_ref.harness_knows("strict", "hiptail"))):
+            pytest.skip("oracle/_ref harnesses not built from this tree's harness source (needs the reference tree)")
     if not (run_ref.have_ref("hip_dropin_mpi") and run_ref.have_mpiexec()):
         pytest.skip("oracle/_ref/evp_hip_dropin_harness_mpi or mpiexec not available")
     files = None
@@ -95,12 +107,28 @@ def run_case(tmp_path, nx, ny, bx, by, ew, ns, nprocs, dist, body, kw, ndte=24, 
                         assert bits_equal(b, ref), f"Option A body, task {r} call {icall} nsub {nsub} {f}"
                         checked += 1
     assert checked == nprocs * 4 * (len(FIELDS) * (2 if body else 1) + len(DOWNSTREAM))
+    if tail:
+        # the post-loop wrappers, called by every task (they are collective), against the reference's own routines in the
+        # same task; every output array held -7e77 before its wrapper ran
+        tailed = 0
+        for r, d in enumerate(par):
+            for icall in (1, 2):
+                for nsub in (1, ndte):
+                    for letter in ("h", "b") if (body and not cgrid) else ("h",):
+                        for got, want in (CGRID_TAIL if cgrid else B_TAIL):
+                            a, b = d[f"{letter}{icall:02d}n{nsub:04d}_{got}"], d[f"o{icall:02d}n{nsub:04d}_{want}"]
+                            assert bits_equal(a, b), (f"task {r} call {icall} nsub {nsub} {letter}_{got}: {int((a != b).sum())} cells "
+                                                      f"differ, {int((a == -7.e77).sum())} hold the sentinel")
+                            tailed += 1
+        assert tailed == nprocs * 4 * (len(CGRID_TAIL) if cgrid else len(B_TAIL) * (2 if body else 1))
     # ... and the whole thing against the reference's serial build on the same domain
     if run_ref.have_ref("strict"):
         ser, _ = run_ref.run_harness(nx, ny, bx, by, variant="strict", workdir=tmp_path / "ser", **common)
-        for f in FIELDS:
+        for f in FIELDS + (["strocnxT_iavg", "strocnyT_iavg"] if tail else []):
             k = f"n{ndte:04d}_{f}"
             assert bits_equal(run_ref.global_field(par, "h02" + k), run_ref.global_field(ser, "o02" + k)), f
+    if tail:
+        assert np.nanmax(np.abs(run_ref.global_field(par, f"h02n{ndte:04d}_strocnxT_iavg"))) > 0.0
     if cgrid:
         assert np.nanmax(np.abs(run_ref.global_field(par, f"h02n{ndte:04d}_uvelE"))) > 1e-5
     assert np.nanmax(np.abs(run_ref.global_field(par, f"h02n{ndte:04d}_uvel"))) > 1e-5
@@ -210,6 +238,21 @@ def test_reference_mpi_driver_with_hip_cgrid_loop_bitwise(tmp_path, nx, ny, bx, 
     updates of a subcycle between the tasks' kernels), against the reference's evp() with grid_ice = 'C' whose halo
     goes through MPI -- every array the loop writes, every cell of every task, ghost cells included."""
     run_case(tmp_path, nx, ny, bx, by, ew, ns, nprocs, dist, False, kw, cgrid=True)
+
+
+@pytest.mark.parametrize("nx,ny,bx,by,ew,ns,nprocs,dist,body,cgrid,kw", [
+    # C grid, tripole, 2 x 2 blocks dealt round-robin: each task owns one column of blocks, so the fold row has two owners
+    (72, 40, 36, 20, "cyclic", "tripole", 2, "roundrobin", False, True, dict(grid_kind="tripolefile", icecase="full")),
+    # B grid, closed on all four sides, Option B and Option A
+    (64, 48, 32, 24, "closed", "closed", 2, "cartesian", True, False, dict(grid_kind="popfile", icecase="patchy")),
+], ids=["C_tripole_fold_row_two_owners", "B_closed"])
+def test_reference_mpi_driver_post_loop_wrappers(tmp_path, nx, ny, bx, by, ew, ns, nprocs, dist, body, cgrid, kw):
+    """The shim's post-loop wrappers (tests/test_gpu_dropin_tail.py) called by every task of the reference's MPI driver:
+    dyn_evp_hip_cgrid_tail and dyn_evp_hip_strocn_t are documented as collective -- their halo updates run between the
+    tasks' kernels, the C grid's across a fold row with two owners -- and this is the only place that shows it.  Every
+    task's arrays against the reference's own routines (halo through MPI) in the same task, and the assembled
+    strocn{x,y}T_iavg against the reference's serial build."""
+    run_case(tmp_path, nx, ny, bx, by, ew, ns, nprocs, dist, body, kw, ndte=5, cgrid=cgrid, tail=True)
 
 
 @pytest.mark.parametrize("nx,ny,bx,by,ew,ns,nprocs,dist,body,kw", CASES)
