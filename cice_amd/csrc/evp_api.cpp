@@ -3,6 +3,7 @@
 // per-call entry points, the post-loop kernels (f-1, f-3) and introspection.  The device
 // state and the helpers live in evp_host*.cpp (overview in evp_host.h).
 // =====================================================================
+#include "cgrid_schedule.h"
 #include "evp_host.h"
 #include "rim_plan.h"
 
@@ -1126,6 +1127,20 @@ int cice_evp_hip_debug_res2_choose(int64_t n, const uint32_t *facts, int32_t cap
         const Res2Facts f{bit(0), cap, logw, bit(1), bit(2) ? 1 : 2, bit(3), bit(4), bit(5), bit(6), bit(7), bit(8), fl, bit(11), bit(12), bit(13), bit(14), bit(15), bit(16), bit(17), hooks};
         const Res2Choice c = res2_choose(f);
         chosen[e] = (unsigned)c.v.strict | c.v.remote << 1 | c.v.coop << 2 | c.v.lean << 3 | c.v.rimu << 4 | c.rim_tables << 5 | (unsigned)c.v.logw << 8 | (unsigned)(c.v.cap + 1) << 16;
+    }
+    return 0;
+}
+
+// Host-only: cg_choose_schedule (cgrid_schedule.h) over n rows of facts, see the testing header
+int cice_evp_hip_debug_cgrid_choose(int64_t n, const int32_t *facts, int32_t *out)
+{
+    if (n < 0 || !facts || !out) return fail(-1, "cgrid_choose: bad argument");
+    static_assert(sizeof(int) == sizeof(int32_t), "a row of facts is the struct");
+    for (int64_t e = 0; e < n; ++e) {
+        CgSchedFacts f;
+        std::memcpy(&f, facts + e * CG_NFACTS, sizeof f);
+        const CgSchedule s = cg_choose_schedule(f);
+        std::memcpy(out + e * CG_NSCHED, &s, sizeof s);
     }
     return 0;
 }

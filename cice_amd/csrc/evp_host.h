@@ -8,7 +8,9 @@
 //   evp_host_resident.cpp  on-chip resident kernels: set-up, launch, checks, autotuning
 //   evp_host_mailbox.cpp   mailbox halo over HIP IPC, RCCL bootstrap, probes
 //   evp_host_prep.cpp      preparation phase of evp() (f-2)
-//   evp_host_cgrid.cpp     C-grid subcycle (f-4): state, ghost images, the loop
+//   evp_host_cgrid.cpp     C-grid subcycle (f-4): state, ghost images, tables, upload / download, preparation, after the loop
+//   evp_host_cgrid_loop.cpp  ... the loop: the schedule's facts, the enqueue_* functions, cice_evp_hip_cgrid_subcycle (evp_host_cgrid.h:
+//                          what the two share; cgrid_schedule.cpp: which schedule runs, a pure function of the facts)
 //   evp_host_tail.cpp      after the loop: T-point ocean stress, principal stresses (B-grid state)
 //
 // HBM layout: structure-of-arrays; every field is one contiguous fp64 array
@@ -508,6 +510,7 @@ int direct_check_error();
 // evp_host_cgrid.cpp
 void cgrid_free();
 size_t cgrid_allocs();
+// evp_host_cgrid_loop.cpp
 std::string cgrid_schedule();     // "" unless the C grid runs with the fold exchange (tripole fold rows on several ranks)
 
 }  // namespace evp_host

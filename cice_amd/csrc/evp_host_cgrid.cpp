@@ -1,7 +1,8 @@
 // =====================================================================
 // C-grid EVP subcycle behind the C ABI (include/cice_evp_hip.h, cice_evp_hip_cgrid_*): device state, ghost-image
-// table, the loop as a captured graph of one (cg_one: one rank, no fold), three (fused schedule) or five launches per
-// subcycle (evp_cgrid.hip).
+// table, the tables of every schedule, upload / download, the preparation, what follows the loop, the read-outs.  The loop
+// itself -- a captured graph of one (cg_one: one rank, no fold), three (fused schedule) or five launches per subcycle
+// (evp_cgrid.hip) -- is evp_host_cgrid_loop.cpp; the state both share: evp_host_cgrid.h.
 //
 // Replaces evp()'s loop for grid_ice = 'C' (ice_dyn_evp.F90:938-1099).  The caller has run the reference's own
 // preparation (dyn_prep1/2 at U, N and E points, seabed stress, the grid averages of the forcing) and hands over
@@ -17,177 +18,10 @@
 #include <cmath>
 #include <set>
 
-#include "evp_host.h"
+#include "evp_host_cgrid.h"
 
 namespace evp_host {
-
-// the five arrays a subcycle reads in one allocation and writes in the other (every schedule but the five phases), in this order
-static const int PP_FIELDS[5] = {CF_UE, CF_VN, CF_SP, CF_SM, CF_S12U};
-constexpr unsigned PP_FOUR = 15u, PP_S12 = 16u, PP_ALL = PP_FOUR | PP_S12;     // bit q: PP_FIELDS[q]
-
-// What a schedule did with a call's subcycles: the enqueue_* functions fill it in as they enqueue, the graph cache keeps it beside
-// the captured graph (a replay did what the capture did), cice_evp_hip_cgrid_subcycle applies it
-struct Ran {
-    unsigned swapped = 0;        // bit q: PP_FIELDS[q] ended in the allocation that was the other one when the call began
-    int one = 0;                 // subcycles run as one launch each (cg_one)
-    int march = 0;               // ... as the marched kernel beside the fused chain on the frame (several ranks)
-    int march_phases = 0;        // ... of those: with the five list-driven phase kernels on the frame instead (enqueue_march_fold without a fold)
-    int mfold = 0;               // ... as the marched kernel beside the five phases on the fold band (tripole grids, one rank)
-    int mfold_ranks = 0;         // ... the same with the frame in the rest and the five phases' exchanges (tripole grids, several ranks)
-};
-// Everything a captured graph bakes in that can change between calls: pointers (in_alt) and kernel / template choices
-struct GraphKey {
-    int ndte, avg_strength;
-    unsigned in_alt;
-    bool first, fused, fast, one, geo, march, mfold, mfold_serial, mfold_sync, mfold_ranks;
-    auto tie() const { return std::tie(ndte, avg_strength, in_alt, first, fused, fast, one, geo, march, mfold, mfold_serial, mfold_sync, mfold_ranks); }
-    bool operator<(const GraphKey &o) const { return tie() < o.tie(); }
-};
-// The cells the marched kernel does not own, as the kernels beside it want them: per-cell bits, per level the workgroups to launch,
-// scratch arrays for the intermediates of the zone cells those kernels read
-struct CellLists {
-    uint8_t *cells = nullptr;
-    int *wg[5] = {};
-    int nwg[5] = {};
-    double *scr[6] = {};
-    long ncells = 0;
-};
-
-struct CGridState {
-    DevicePool mem;              // owns every device allocation below
-    bool geo = false, uploaded = false;
-    double *f[CG_NF] = {}, *in[CG_NIN] = {}, *g[CG_NG] = {};
-    double *gslab = nullptr, *inslab = nullptr;   // g[k] = gslab + k * n, in[k] = inslab + k * n: one allocation per table (cg_one addresses them as base + k * stride)
-    double *strengthU = nullptr;
-    double *umaskd = nullptr;    // ranks > 1: iceU as a field, to learn the flags of ghost cells other ranks own
-    double *fac[2] = {nullptr, nullptr};   // leading factor of vrel at E / N (once per call)
-    unsigned *d_flags = nullptr;
-    bool fast = false;           // the shortcuts of cg_stress_u_step<true> hold on every ice cell of this call
-    // second allocations of PP_FIELDS (f[PP_FIELDS[q]] always holds the current one); [4] always, [0..3] where a schedule that
-    // ping-pongs them can run (need_alt)
-    double *alt[5] = {};
-    unsigned in_alt = 0;         // bit q: f[PP_FIELDS[q]] is the second allocation
-    // one launch per subcycle (evp_cgrid.hip: cg_one): window table
-    struct One {
-        int *tab = nullptr;
-        int4 *tiles = nullptr;
-        int ntiles = 0, per_xcd = 0, ox = 0, oy = 0;
-        unsigned long long *prof = nullptr;   // test build: phase stamps (CICE_EVP_HIP_CGRID_PROF=1)
-        // the interior of large blocks marched (evp_cgrid.hip: cg_strip): its items, and the windows cg_one keeps (the block edges)
-        int *items = nullptr;
-        int4 *tiles_e = nullptr;
-        int *tab_e = nullptr;
-        int nitems = 0, ntiles_e = 0, strip_seg = 0, ex = 0, ey = 0;   // (ex, ey: shape of the windows kept)
-        int strip_len = 0;       // 1: the marched kernel forms six of the eight lengths from dxN, dyE
-        long strip_cells = 0;    // cells the marched kernel owns
-    } one;
-    // several ranks: the marched kernel on the rectangles above beside the fused chain on every other interior cell (enqueue_fused:
-    // "zone marched + frame"; cgrid_plan.cpp: build_cg_frame).  cells: the EVP_CGS_* bits (REST = frame cell); three levels; scr:
-    // shearU, etax2T, stresspT, stressmT of the zone cells the frame reads; ncells: frame cells
-    CellLists fr;
-    // tripole / tripoleT on one rank: the marched kernel on the rectangles under the fold band beside list-driven variants of the five
-    // phase kernels on every other interior cell (enqueue_march_fold: "marched zone + fold band"; cgrid_plan.cpp: build_cg_march_fold).
-    // On several ranks the same with the frame in the rest and the five phases' exchanges at their points ("... + frame").
-    // The items live in `one` (items, nitems, strip_*)
-    struct MarchFold {
-        CellLists rest;                      // cells: the EVP_CGS_* bits; five phases; scr: shearU, etax2T, stresspT, stressmT, stress12U, deltaU; ncells: REST cells
-        uint8_t *gmask = nullptr;            // the land masks as bits on the rows the marched kernel derives its geometry on
-        int band_rows = 0;
-        long frame_cells = 0;                // several ranks: REST cells another rank receives or that have a ghost image here
-        bool by_size = false;                // cg_strip's size rule holds for the zone
-        // no fold, several ranks, visc_method = avg_strength ("zone marched + frame" on the five phases): this plan's own items --
-        // CG.one's belong to the fused chain's frame plan (CG.fr), whose rectangles may differ
-        int *items = nullptr;
-        int nitems = 0, strip_len = 0;
-        long strip_cells = 0;
-        bool synced = false;                 // the second allocations of the five ping-pong arrays agree with the current ones on every cell no
-                                             // subcycle writes (false after an upload and after any call another schedule ran)
-        std::string why;                     // why there is no plan on this rank
-    } mf;
-    // the marched kernel's stream beside S.stream, forked from and joined to it in every subcycle.  One per geometry: zone + frame
-    // needs several ranks and no fold, zone + fold band (+ frame) a fold
-    struct Side {
-        hipStream_t st = nullptr;
-        hipEvent_t fork = nullptr, join = nullptr;
-    } side;
-    // all subcycles of a call in one launch, state on the chip (evp_cgrid_res.hip: cg_res)
-    struct Res {
-        int *tab = nullptr;
-        int4 *tiles = nullptr, *tiles2 = nullptr;     // (tiles2: tripole grids, cgrid_plan.cpp build_fold_window_table)
-        int ntiles = 0;
-        uint8_t *pubmap = nullptr;
-        uint8_t *gmask = nullptr;    // tripole grids: the land masks as bits (elsewhere CG.gmask, which the one-launch kernels share)
-        char *rec = nullptr;         // EVP_CGRES_SLOTS x S.n records of 32 bytes
-        int *err = nullptr;
-        int *d_order = nullptr;      // the windows that hold ice in this call (cg_res_live at every upload), n_live of them
-        int *live_win = nullptr;     // [ntiles] 0 / 1
-        uint8_t *live_cell = nullptr;   // per cell: its window runs in this call
-        int n_live = 0;
-        std::vector<int> h_live;
-        unsigned epoch = 0;
-        int par = 0;
-        bool images_ok = false;      // every ghost cell's static arrays equal its source's bit for bit
-        int2 *pairs = nullptr;       // (array neighbour of a position's cell, the ghost cell outside the domain the table names for the
-        int npairs = 0;              // neighbouring position) where the two differ: must hold the same values (static: checked once)
-        bool pairs_state_ok = true;  // ... and the same state in this call (checked on the device at every upload)
-        std::string why;             // ... or why the kernel is not eligible on this rank
-        int mode = -1;               // -1 undecided (first eligible call probes), 0 off, 1 on
-        bool launched = false;       // a launch whose error word has not been looked at
-        long cap4[8] = {};           // windows that can be resident at once (occupancy x CUs), by kernel variant (avg_strength | revised << 1 | slow << 2)
-        double t_probe_ms = -1.0;    // probe: ms per subcycle
-        int last_nsub = 0;           // subcycles of the last call that ran inside it
-        int fallbacks = 0;           // cice_evp_hip_cgrid_run calls repeated without it after a wait gave up
-        unsigned long long *prof = nullptr;   // test build: phase stamps (CICE_EVP_HIP_CGRID_PROF=1)
-    } res;
-    uint8_t *mask = nullptr;
-    uint8_t *gmask = nullptr;    // the four land masks as bits (cg_one's derived view of the static table); null: an identity failed
-    std::string geo_why;         // ... and which one
-    int *img_slot = nullptr, *img_dst = nullptr;
-    // tripole fold: per field location the cells of the fold row / the ghost row beyond it and their sources
-    bool tripole = false;
-    bool tfold = false;                  // ... of the T-fold kind (tripoleT)
-    struct Fold { int *dst = nullptr, *a = nullptr, *b = nullptr; unsigned char *flip = nullptr; int n = 0; } fold[4];
-    double *fold_tmp = nullptr;
-    int fold_maxn = 0;
-    int *zero_cells = nullptr;   // ghost cells of eliminated (land) neighbour blocks
-    int n_zero = 0;
-    std::vector<int> h_img_slot, h_img_dst;
-    int32_t *mask4 = nullptr;    // the caller's four logical masks as uploaded (4 x n words)
-    int avg_strength = 0;
-    bool first = true;           // no subcycle has run since the upload
-    struct Captured { hipGraphExec_t exec; Ran ran; };
-    std::map<GraphKey, Captured> graphs;     // the loop of a call as a graph, with what it did
-    double t_loop_ms = 0;
-    int t_nsub = 0;
-    int t_one = 0;               // subcycles of the last call that ran as one launch each (cg_one)
-    int t_march = 0;             // ... as the marched kernel beside the fused chain on the frame (several ranks)
-    int t_march_phases = 0;      // ... of those: with the five list-driven phase kernels on the frame (that plan's items and frame cells: CG.mf)
-    int t_mfold = 0;             // ... as the marched kernel beside the five phases on the fold band (tripole grids, one rank)
-    int t_mfold_ranks = 0;       // ... as "marched zone + fold band + frame" (tripole grids, several ranks)
-    double *tarear = nullptr, *post[5] = {};   // deformationsC_T: 1/tarea (static), divu shear vort rdg_conv rdg_shear
-    // after the loop (evp_tail.hip): strintxU strintyU / strocn{x,y}T_iavg; U-point operands of dyn_finish (cdn_ocnU aiU uocnU vocnU
-    // fmU), its strocnxU / yU; work1 / work2 of step_dyn_horiz (exchanged: the length of CG.f)
-    struct Tail {
-        double *out[2] = {}, *uin[5] = {}, *strocn[2] = {}, *work[2] = {};
-        bool strocn_ok = false;                // strocn[] / uin[1] belong to the state the loop last ran on
-    } tail;
-    // preparation phase on the device (cice_evp_hip_cgrid_prep)
-    struct Prep {
-        bool geo = false, pending = false;     // pending: prepared, cice_evp_hip_cgrid_prep_finish not yet called
-        uint8_t *tmask = nullptr, *xmask[3] = {};
-        double *fcor[3] = {}, *t[11] = {}, *tmass = nullptr, *maskd = nullptr;
-        int *c_dst = nullptr, *c_src = nullptr;
-        signed char *c_vsign = nullptr;
-        int n_center = 0;
-        double *hwater = nullptr, *tbt = nullptr, *aicen = nullptr, *vicen = nullptr;
-        int ncat = 0;
-        std::vector<int32_t> h4;               // the four mask words as they come back
-        double *prod[4] = {};                  // test build, forcing layout on: strairxE strairyN ss_tltxE ss_tltyN (EvpForcing::prod)
-        cice_evp_hip_prep_params pp{};
-        double t_ms = 0;
-    } prep;
-};
-static CGridState CG;
+CGridState CG;
 
 size_t cgrid_allocs() { return CG.mem.owned.size(); }
 
@@ -201,31 +35,21 @@ void cgrid_free()
     CG = CGridState();
 }
 
-// ---- switches: each is read here and nowhere else.  env_test(): the test build only (evp_host.h) ----
-static bool one_switch() { return env_on(env("CICE_EVP_HIP_CGRID_ONE"), true); }     // =0: neither cg_one nor the marched kernel
+// ---- switches: each is read here and nowhere else (the loop's own: evp_host_cgrid_loop.cpp).  env_test(): the test build only (evp_host.h) ----
 static bool split_faces_on() { return env_on(env_test("CICE_EVP_HIP_CGRID_SPLIT"), S.n <= 600000); }
 static int xcd_switch() { return env_int(env_test("CICE_EVP_HIP_CGRID_XCD"), 1); }    // 0: plain 2-D launch, > 1: so many rows per band
-static bool fused_switch() { return env_on(env_test("CICE_EVP_HIP_CGRID_FUSED"), true); }
 static bool geo_switch() { return env_on(env_test("CICE_EVP_HIP_CGRID_GEO"), true); }
-static bool march_ranks_switch() { return env_on(env_test("CICE_EVP_HIP_CGRID_MARCH_RANKS"), true); }
-static int march_fold_switch() { return env_int(env_test("CICE_EVP_HIP_CGRID_MARCH_FOLD"), ENV_UNSET); }
-static int march_fold_ranks_switch() { return env_int(env_test("CICE_EVP_HIP_CGRID_MARCH_FOLD_RANKS"), ENV_UNSET); }
-static bool march_avgs_switch() { return env_on(env_test("CICE_EVP_HIP_CGRID_MARCH_AVG_STRENGTH"), false); }   // =1: avg_strength on the marched split schedules
-static bool march_fold_serial() { return env_on(env_test("CICE_EVP_HIP_CGRID_MARCH_FOLD_SERIAL"), false); }
-static bool strip_last_on() { return env_on(env_test("CICE_EVP_HIP_CGRID_STRIP_LAST"), true); }
-static bool strip_ride_on() { return env_on(env_test("CICE_EVP_HIP_CGRID_STRIP_RIDE"), true); }
-static bool one_xcd_on() { return env_on(env_test("CICE_EVP_HIP_CGRID_ONE_XCD"), true); }
+bool march_avgs_switch() { return env_on(env_test("CICE_EVP_HIP_CGRID_MARCH_AVG_STRENGTH"), false); }   // =1: avg_strength on the marched split schedules
 static int one_shape_switch(int dflt) { return std::min(2, std::max(0, env_int(env_test("CICE_EVP_HIP_CGRID_ONE_SHAPE"), dflt))); }
 static int one_strip_switch() { return std::max(1, env_int(env_test("CICE_EVP_HIP_CGRID_ONE_STRIP"), 1 << 20)); }
 static bool prof_on() { return env_on(env_test("CICE_EVP_HIP_CGRID_PROF"), false); }
 static int strip_switch() { return env_int(env_test("CICE_EVP_HIP_CGRID_STRIP"), ENV_UNSET); }
 static int strip_edge_switch() { return std::min(2, std::max(0, env_int(env_test("CICE_EVP_HIP_CGRID_STRIP_EDGE"), 0))); }
-static bool res_cull() { return env_on(env_test("CICE_EVP_HIP_CGRID_RES_CULL"), true); }
+bool res_cull() { return env_on(env_test("CICE_EVP_HIP_CGRID_RES_CULL"), true); }
 static bool res_sleep_on() { return env_on(env_test("CICE_EVP_HIP_CGRID_RES_SLEEP"), false); }
 static int res_debug() { return env_int(env_test("CICE_EVP_HIP_CGRID_RES_DEBUG"), 0); }
 static bool fast_switch() { return env_on(env_test("CICE_EVP_HIP_CGRID_FAST"), true); }
-static int resident_switch() { return env_int(env("CICE_EVP_HIP_CGRID_RESIDENT"), -1); }     // 0 / 1 forces the verdict
-static bool verbose() { return env("CICE_EVP_HIP_VERBOSE") != nullptr; }
+bool verbose() { return env("CICE_EVP_HIP_VERBOSE") != nullptr; }
 // The marched kernel's knobs (cg_strip; test build): work items that fill the chip once, a forced segment length in rows (0: the
 // planner's), whether the kernel may form six of the eight lengths itself, and -- several ranks -- slots left to the frame's workgroups
 constexpr long STRIP_SLOTS = 2048;           // about two waves per SIMD resident at once (256 CUs x 8)
@@ -238,8 +62,11 @@ static StripKnobs strip_knobs()
             env_on(env_test("CICE_EVP_HIP_CGRID_STRIP_LEN"), true), env_int(env_test("CICE_EVP_HIP_CGRID_MARCH_RESERVE"), ENV_UNSET)};
 }
 
-static bool geo_derived();
-static void fill(EvpCgrid &A)
+// cg_one with 15 of its 23 static arrays derived in the kernel from the other eight (evp_cgrid.hip: DSlab): allowed when
+// every identity holds bit for bit on the caller's arrays (derive_geometry_check, once per cice_evp_hip_cgrid_set_geometry).
+// CICE_EVP_HIP_CGRID_GEO=0 keeps all 23 arrays in use.
+bool geo_derived() { return CG.gmask && geo_switch(); }
+void fill(EvpCgrid &A)
 {
     const cice_evp_hip_params &q = S.prm;
     for (int k = 0; k < CG_NF; ++k) A.f[k] = CG.f[k];
@@ -272,37 +99,31 @@ static void fill(EvpCgrid &A)
     A.plane = S.plane;
 }
 
-static bool remote() { return !S.plan.peers.empty() || !S.plan.cg_peers.empty(); }
+bool remote() { return !S.plan.peers.empty() || !S.plan.cg_peers.empty(); }
 // the blocks next to the tripole fold have more than one owner: the C grid's exchange (ghost cells + fold sources into
 // staging slots n + t of every exchanged array) replaces the velocity lists at every exchange point
-static bool fold_exchange() { return CG.tripole && S.plan.cg_split; }
+bool fold_exchange() { return CG.tripole && S.plan.cg_split; }
 // length of an exchanged array: the rank's cells and, where the fold rows have several owners, the staging slots of the fold exchange
-static size_t field_len() { return S.n + (fold_exchange() ? (size_t)S.plan.cg_tail : 0); }
+size_t field_len() { return S.n + (fold_exchange() ? (size_t)S.plan.cg_tail : 0); }
 // ghost cells owned by other ranks, for two of the loop's arrays (no-op on one rank).  Every exchange inside the loop
 // goes through the masked halo when the host has handed one over (maskhalo_dyn: evp() builds it for the C grid as the
 // five-point dilation of iceTmask, ice_dyn_evp.F90:739-770, and passes halo_info_mask to every dyn_haloUpdate of the
-// loop, :965-1096); copies inside a rank -- the pushes of the kernels -- are never masked, as in ice_HaloMask.
-#define XCHG(a, b)                                             \
-    do {                                                       \
-        if (fold_exchange()) {                                 \
-            if (int rc_ = cgrid_fold_exchange((a), (b), field_len())) return rc_; \
-        } else if (remote()) {                                 \
-            if (int rc_ = halo_remote_pair((a), (b), true)) return rc_; \
-        }                                                      \
-    } while (0)
+// loop, :965-1096: masked = true); copies inside a rank -- the pushes of the kernels -- are never masked, as in ice_HaloMask.
+int exchange(double *a, double *b, bool masked)
+{
+    if (fold_exchange()) return cgrid_fold_exchange(a, b, field_len());
+    return remote() ? halo_remote_pair(a, b, masked) : 0;
+}
 
-// tripole: the fold step of up to four fields after the launch that produced them (what their ice_HaloUpdate does
-// at the fold: points ON it averaged with their partners, ghost row beyond it mirrored); loc 0 centre, 1 NE corner,
-// 2 E face, 3 N face; vec: vector kind (sign change across the fold)
-struct FoldField { double *x; int loc; bool vec; };
-static void fold(std::initializer_list<FoldField> fs)
+// the fold step of up to four fields (FoldField: evp_host_cgrid.h)
+void fold(const FoldField *fs, int n)
 {
     if (!CG.tripole) return;
     EvpCgFold F{};
-    for (const FoldField &f : fs) {
-        F.x[F.nfields] = f.x;
-        F.loc[F.nfields] = f.loc;
-        F.isign[F.nfields] = f.vec ? -1.0 : 1.0;
+    for (const FoldField *f = fs; f < fs + n; ++f) {
+        F.x[F.nfields] = f->x;
+        F.loc[F.nfields] = f->loc;
+        F.isign[F.nfields] = f->vec ? -1.0 : 1.0;
         ++F.nfields;
     }
     for (int l = 0; l < 4; ++l) F.L[l] = {CG.fold[l].dst, CG.fold[l].a, CG.fold[l].b, CG.fold[l].flip, CG.fold[l].n};
@@ -311,116 +132,7 @@ static void fold(std::initializer_list<FoldField> fs)
     evp_launch_cgrid_fold(F, S.stream);
 }
 
-static bool one_launch();
-static bool fused_schedule()
-{
-    if (CG.avg_strength && !one_launch()) return false;   // the three-launch kernels need deltaU at the neighbours: five phases
-    if (CG.tripole) return false;                // recomputing a neighbour across the fold would sum in mirrored order
-    return fused_switch();
-}
 
-// The kernels push a cell into its ghost images only where there is ice; the reference's ice_HaloUpdate copies every
-// cell.  The difference shows once per call: a cell WITHOUT ice whose ghost images hold something else than the cell
-// itself -- a corner that lost its ice since the last step (dyn_prep2 zeroes stress12U on ilo..ihi x jlo..jhi only,
-// iceUmask is never set on ghost cells: the ghost image keeps the old stress) -- is repaired by the reference's first
-// exchange of the field.  Cells without ice do not change during a call, so one unconditional copy in the first
-// subcycle, right after the launch that produces the field, leaves every ghost cell as the reference has it.
-static void first_exchange_copies_everything(const EvpCgrid &A, std::initializer_list<int> fields)
-{
-    for (int f : fields) evp_launch_cgrid_phase(A, 9, f, S.stream);
-}
-
-// five launches per subcycle, any visc_method
-static int enqueue_phases(const EvpCgrid &A, int ndte, bool first)
-{
-    for (int k = 0; k < ndte; ++k) {
-        evp_launch_cgrid_phase(A, 0, 1, S.stream);
-        // the first strain_rates_U still reads the caller's ghost values of uvelN / vvelE
-        if (first && k == 0) {
-            evp_launch_cgrid_phase(A, 6, 1, S.stream);
-            evp_launch_cgrid_zero_cells(A, CG.zero_cells, CG.n_zero, S.stream);
-        }
-        XCHG(A.f[CF_SHEARU], A.f[CF_SHEARU]);
-        fold({{A.f[CF_SHEARU], 1, false}});
-        evp_launch_cgrid_phase(A, 1, 1, S.stream);
-        if (first && k == 0) first_exchange_copies_everything(A, {CF_SP, CF_SM});
-        XCHG(A.f[CF_ETA], A.f[CF_ZETA]);
-        XCHG(A.f[CF_SP], A.f[CF_SM]);
-        fold({{A.f[CF_ZETA], 0, false}, {A.f[CF_ETA], 0, false}, {A.f[CF_SP], 0, false}, {A.f[CF_SM], 0, false}});
-        evp_launch_cgrid_phase(A, 2, 1, S.stream);
-        if (first && k == 0) first_exchange_copies_everything(A, {CF_S12U});
-        XCHG(A.f[CF_S12U], A.f[CF_S12U]);
-        fold({{A.f[CF_S12U], 1, false}});
-        evp_launch_cgrid_phase(A, 3, 1, S.stream);
-        XCHG(A.f[CF_UE], A.f[CF_VN]);
-        fold({{A.f[CF_UE], 2, true}, {A.f[CF_VN], 3, true}});
-        evp_launch_cgrid_phase(A, 4, 1, S.stream);
-        XCHG(A.f[CF_UN], A.f[CF_VE]);
-        XCHG(A.f[CF_UU], A.f[CF_VU]);
-        fold({{A.f[CF_UN], 3, true}, {A.f[CF_VE], 2, true}, {A.f[CF_UU], 1, true}, {A.f[CF_VU], 1, true}});
-    }
-    return 0;
-}
-
-// The current and the other allocation of PP_FIELDS as a schedule sees them while it enqueues: swap() per subcycle, `swapped` for Ran
-struct PingPong {
-    double *cur[5], *alt[5];
-    unsigned swapped = 0;
-    PingPong()
-    {
-        for (int q = 0; q < 5; ++q) {
-            cur[q] = CG.f[PP_FIELDS[q]];
-            alt[q] = CG.alt[q];
-        }
-    }
-    void swap(unsigned which)
-    {
-        for (int q = 0; q < 5; ++q)
-            if (which >> q & 1u) std::swap(cur[q], alt[q]);
-        swapped ^= which;
-    }
-    // a launch that works in place, and what the call leaves: the current allocations
-    void at_current(EvpCgrid &A) const
-    {
-        for (int q = 0; q < 5; ++q) A.f[PP_FIELDS[q]] = cur[q];
-    }
-    // this subcycle writes the other allocations and reads the current ones
-    void aim(EvpCgrid &A, unsigned which) const
-    {
-        for (int q = 0; q < 5; ++q)
-            if (which >> q & 1u) A.f[PP_FIELDS[q]] = alt[q];
-        if (which & PP_S12) A.s12_in = cur[4];
-    }
-    // bring the second allocations into line: both then agree on the cells no later subcycle writes (no ice; ghost cells nothing
-    // is copied into)
-    // (with the fold exchange both allocations carry the staging slots behind the cells: copied along)
-    int sync(unsigned which) const
-    {
-        for (int q = 0; q < 5; ++q)
-            if (which >> q & 1u) HIPC(hipMemcpyAsync(alt[q], cur[q], field_len() * sizeof(double), hipMemcpyDeviceToDevice, S.stream));
-        return 0;
-    }
-};
-// (the resident launch reads P.cur and leaves the final state in BOTH allocations: it swaps nothing)
-static int res_launch(const EvpCgrid &A, int nsub, bool dry, const PingPong &P);
-// tripole (u-fold) on one rank: the first subcycles as five launches + fold steps, the last nres inside ONE launch of the on-chip
-// resident kernel's FOLD variant, then the fold step of everything that launch leaves (ghost row beyond the fold; the points ON the fold
-// come out averaged already, and the step leaves an averaged pair as it is) and the velocity averages after the loop
-static int enqueue_phases_resident(const EvpCgrid &A, int ndte, bool first, int nres, Ran &ran);
-
-// one launch per subcycle (cg_one) for every subcycle but the first after an upload (which still reads the caller's
-// uvelN, vvelE, uvel, vvel): one rank, no fold.  Measured, us per subcycle, three launches -> one:
-// gx3 12.5 -> 9.5, 300x240 17.6 -> 12.8, gx1 22.4 -> 17.6, 720x270 28.3 -> 21.9, 720x540 44.1 -> 39.3 (window shapes:
-// build_one_tables), 1440x1080 196.6 -> 178.0, 3600x2400 1013 -> 902; avg_strength against its five launches:
-// gx1 30.1 -> 18.6, 1440x1080 235 -> 191, 3600x2400 1257 -> 968.  CICE_EVP_HIP_CGRID_ONE=0 switches it off
-// cg_one with 15 of its 23 static arrays derived in the kernel from the other eight (evp_cgrid.hip: DSlab): allowed when
-// every identity holds bit for bit on the caller's arrays (derive_geometry_check, once per cice_evp_hip_cgrid_set_geometry).
-// CICE_EVP_HIP_CGRID_GEO=0 keeps all 23 arrays in use.
-static bool geo_derived()
-{
-    if (!CG.gmask) return false;
-    return geo_switch();
-}
 // Checks, on every cell the kernels can read (the blocks' cells with their ghost ring; the ratios and nothing else need
 // a neighbour: interior cells), that the caller's derived arrays are what the reference's start-up computes from dx / dy
 // (the list: evp_cgrid.hip above DSlab).  Compared as BITS.  Returns the four masks as bits, or an empty vector + why.
@@ -496,282 +208,6 @@ static bool strip_lengths_hold(const StripZone &z, int EX, int EY, const double 
     return true;
 }
 
-static bool one_launch() { return CG.one.tab && !remote() && one_switch(); }
-// Several ranks, no fold, visc_method = avg_zeta, the derived view of the static table, and rectangles for the marched kernel on THIS
-// rank: cg_strip marches them on a second stream while the three fused kernels' frame variants advance every other interior cell on
-// S.stream, with today's exchanges at today's points -- so a rank without rectangles simply runs today's schedule and the ranks
-// need not agree on anything.  CICE_EVP_HIP_CGRID_ONE=0 forces today's schedule (CICE_EVP_HIP_CGRID_MARCH_RANKS=0, test build: this
-// schedule alone off, for A/B).  Faster than the fused schedule on both cuts measured: the default.
-static bool march_ranks()
-{
-    if (!CG.fr.cells || CG.one.nitems <= 0 || !remote() || CG.tripole || CG.avg_strength || !geo_derived()) return false;
-    return one_switch() && march_ranks_switch();
-}
-
-// Tripole / tripoleT on one rank (visc_method = avg_strength: on request, march_fold()), with rectangles for cg_strip under the fold band
-// (set_geometry built the plan):
-// every subcycle but the first after an upload runs as "marched zone + fold band" (enqueue_march_fold).  The on-chip resident kernel
-// keeps precedence where it serves the call; CICE_EVP_HIP_CGRID_ONE=0 forces the five full-domain phases.  Whether the schedule is used
-// unforced: MARCH_FOLD_DEFAULT and cg_strip's size rule; CICE_EVP_HIP_CGRID_MARCH_FOLD=0 / 1 (test build) switches
-// it off / on wherever a zone forms.
-static constexpr bool MARCH_FOLD_DEFAULT = true;       // measured: profiles/r09_cgrid_march_tripole.txt
-static int march_fold_wanted()         // 0 off, 1 forced on, 2 by the size rule
-{
-    if (!one_switch()) return 0;
-    const int forced = march_fold_switch();
-    if (forced != ENV_UNSET) return forced ? 1 : 0;
-    return MARCH_FOLD_DEFAULT ? 2 : 0;
-}
-// Several ranks ("marched zone + fold band + frame"): the same split with the frame in the REST and the five phases' exchanges at
-// their points, so a rank without a zone keeps the five full phases and the ranks need not agree on anything.  Each rank applies the
-// size rule to its own zone.  CICE_EVP_HIP_CGRID_MARCH_FOLD_RANKS=0 / 1 (test build) switches it off / on wherever a zone forms;
-// ..._MARCH_FOLD=1 alone forces the one-rank schedule only (across ranks it leaves the size rule in charge), ..._MARCH_FOLD=0 and
-// CICE_EVP_HIP_CGRID_ONE=0 switch both off.
-static constexpr bool MARCH_FOLD_RANKS_DEFAULT = true;      // measured (two-process rehearsals): profiles/r10_cgrid_march_tripole_ranks.txt
-static int march_fold_ranks_wanted()   // 0 off, 1 forced on, 2 by the size rule
-{
-    if (!one_switch() || march_fold_switch() == 0) return 0;
-    const int forced = march_fold_ranks_switch();
-    if (forced != ENV_UNSET) return forced ? 1 : 0;
-    return MARCH_FOLD_RANKS_DEFAULT ? 2 : 0;
-}
-static int march_fold_wanted_here() { return remote() ? march_fold_ranks_wanted() : march_fold_wanted(); }
-static bool march_fold()
-{
-    if (!CG.mf.rest.cells || CG.one.nitems <= 0 || !CG.tripole) return false;
-    // (visc_method = avg_strength: on request until it has been timed -- CICE_EVP_HIP_CGRID_MARCH_AVG_STRENGTH=1)
-    // (... set when the geometry was, which allocates the scratch deltaU)
-    if (CG.avg_strength && !(march_avgs_switch() && CG.mf.rest.scr[5])) return false;
-    const int want = march_fold_wanted_here();
-    return want == 1 || (want == 2 && CG.mf.by_size);
-}
-// Several ranks, no fold, visc_method = avg_strength, on request (the same switch): "zone marched + frame" with the frame on the five
-// list-driven phase kernels -- the fused chain's frame kernels recompute neighbours and cannot serve avg_strength.  enqueue_march_fold
-// is that schedule (its fold steps are no-ops without a fold); set_geometry built the plan (build_march_frame_tables) under the
-// switches and the size rule that admit the fused chain's "zone marched + frame".
-static bool march_frame_phases()
-{
-    if (!CG.mf.rest.cells || CG.mf.nitems <= 0 || CG.tripole || !remote() || !CG.avg_strength || !geo_derived()) return false;
-    return march_avgs_switch() && one_switch() && march_ranks_switch();
-}
-static int enqueue_phases(const EvpCgrid &A, int ndte, bool first);
-// The marched kernel's arguments from CG.one: its items, and the buffers and tables as cg_one takes them (no window list)
-struct StripArgs { EvpCgOne T; EvpCgStrip Z; };
-static StripArgs strip_args(const PingPong &P, const uint8_t *gmask)
-{
-    const CGridState::One &O = CG.one;
-    return {EvpCgOne{nullptr, nullptr, 0, 0, O.ex, O.ey, 0, P.cur[0], P.cur[1], P.cur[2], P.cur[3], CG.gslab, CG.inslab, S.n, nullptr, gmask},
-            EvpCgStrip{O.items, O.nitems, ((O.nitems + 3) / 4 + 7) / 8, O.strip_len}};
-}
-// ... from the five-phase frame plan's own items (no fold, several ranks, avg_strength: CG.mf)
-static StripArgs strip_args_frame(const PingPong &P)
-{
-    StripArgs Z = strip_args(P, CG.gmask);
-    Z.T.ox = 32; Z.T.oy = 8;
-    Z.Z = EvpCgStrip{CG.mf.items, CG.mf.nitems, ((CG.mf.nitems + 3) / 4 + 7) / 8, CG.mf.strip_len};
-    return Z;
-}
-// sync: the second allocations have not been brought into line since the upload (another schedule ran the calls before this one)
-static int enqueue_march_fold(EvpCgrid A, int ndte, bool first, bool sync, Ran &ran)
-{
-    const CGridState::MarchFold &Q = CG.mf;
-    const CellLists &R = Q.rest;
-    PingPong P;
-    // zone first, then the rest, on one stream (test build, A/B)
-    const bool serial = march_fold_serial(), strip_last = strip_last_on();
-    const int fast = CG.fast ? 1 : 0;
-    int k = 0;
-    if (first) {
-        // the first subcycle after an upload still reads the caller's uvelN, vvelE, uvel, vvel and repairs the ghost cells: the five
-        // full phases, in place
-        if (int rc = enqueue_phases(A, 1, true)) return rc;
-        k = 1;
-    }
-    if (first || sync)
-        if (int rc = P.sync(PP_ALL)) return rc;
-    for (; k < ndte; ++k) {
-        const int last = (k == ndte - 1);
-        if (last && !strip_last) {
-            // (A/B: the call's last subcycle without the marched kernel's LAST instantiation -- the five full phases, in place)
-            P.at_current(A);
-            if (int rc = enqueue_phases(A, 1, false)) return rc;
-            break;
-        }
-        // both sets read the previous subcycle's buffers and own disjoint cells of this subcycle's
-        P.aim(A, PP_ALL);
-        // (no fold: the five-phase frame plan's own items, on the whole-domain view of the derived geometry)
-        const StripArgs Z = CG.tripole ? strip_args(P, Q.gmask) : strip_args_frame(P);
-        EvpCgBand B{R.cells, {R.wg[0], R.wg[1], R.wg[2], R.wg[3], R.wg[4]}, {R.nwg[0], R.nwg[1], R.nwg[2], R.nwg[3], R.nwg[4]},
-                    P.cur[0], P.cur[1], P.cur[2], P.cur[3], P.cur[4], R.scr[0], R.scr[1], R.scr[2], R.scr[3], R.scr[4], R.scr[5]};
-        if (serial) {
-            evp_launch_cgrid_strip(A, Z.T, Z.Z, nullptr, fast, last, S.stream);
-            evp_launch_cgrid_band(A, B, 0, S.stream);
-        } else {
-            // (the rest's first launch goes ahead of the marched kernel, which fills the chip)
-            HIPC(hipEventRecord(CG.side.fork, S.stream));
-            evp_launch_cgrid_band(A, B, 0, S.stream);
-            HIPC(hipStreamWaitEvent(CG.side.st, CG.side.fork, 0));
-            evp_launch_cgrid_strip(A, Z.T, Z.Z, nullptr, fast, last, CG.side.st);
-            HIPC(hipEventRecord(CG.side.join, CG.side.st));
-        }
-        // several ranks: the exchanges of enqueue_phases at its points, in its order and pairing -- a peer on the five full phases
-        // matches them --, each ahead of the fold step that follows it there, on this subcycle's allocations (A is aimed at them).
-        // They read REST cells only (the plan's invariant) and write ghost cells and staging slots: the marched kernel runs beside them
-        XCHG(A.f[CF_SHEARU], A.f[CF_SHEARU]);
-        fold({{A.f[CF_SHEARU], 1, false}});
-        evp_launch_cgrid_band(A, B, 1, S.stream);
-        XCHG(A.f[CF_ETA], A.f[CF_ZETA]);
-        XCHG(A.f[CF_SP], A.f[CF_SM]);
-        fold({{A.f[CF_ZETA], 0, false}, {A.f[CF_ETA], 0, false}, {A.f[CF_SP], 0, false}, {A.f[CF_SM], 0, false}});
-        evp_launch_cgrid_band(A, B, 2, S.stream);
-        XCHG(A.f[CF_S12U], A.f[CF_S12U]);
-        fold({{A.f[CF_S12U], 1, false}});
-        evp_launch_cgrid_band(A, B, 3, S.stream);
-        XCHG(A.f[CF_UE], A.f[CF_VN]);
-        fold({{A.f[CF_UE], 2, true}, {A.f[CF_VN], 3, true}});
-        // the averages read the new velocities of both sets: the two meet again before them.  In the call's last subcycle over the
-        // whole domain: the caller gets uvelN, vvelE, uvel, vvel of every cell
-        if (!serial) HIPC(hipStreamWaitEvent(S.stream, CG.side.join, 0));
-        // (and before a last subcycle that runs as the five full phases, which read them on every cell)
-        if (last || (k == ndte - 2 && !strip_last)) evp_launch_cgrid_phase(A, 4, 1, S.stream);
-        else evp_launch_cgrid_band(A, B, 4, S.stream);
-        XCHG(A.f[CF_UN], A.f[CF_VE]);
-        XCHG(A.f[CF_UU], A.f[CF_VU]);
-        fold({{A.f[CF_UN], 3, true}, {A.f[CF_VE], 2, true}, {A.f[CF_UU], 1, true}, {A.f[CF_VU], 1, true}});
-        P.swap(PP_ALL);
-        if (!CG.tripole) { ++ran.march; ++ran.march_phases; }
-        else ++(remote() ? ran.mfold_ranks : ran.mfold);
-    }
-    ran.swapped = P.swapped;
-    return 0;
-}
-
-// three launches per subcycle + one after the loop (evp_cgrid.hip); stress12U ping-pongs, and with it -- one launch per subcycle, zone
-// marched + frame -- uvelE, vvelN, stresspT, stressmT
-// nres > 0: the last nres subcycles of the call run inside ONE launch of the on-chip resident kernel (evp_cgrid_res.hip)
-static int enqueue_fused(EvpCgrid A, int ndte, bool first, int nres, Ran &ran)
-{
-    const bool one = one_launch(), march = march_ranks();
-    const int fast = CG.fast ? 1 : 0;
-    PingPong P;
-    if (first) {
-        // the caller's ghost cells of stress12U are whatever dyn_prep left there (zero: iceUmask is never set on
-        // ghost cells, ice_dyn_evp.F90:683-690); the reference repairs them with the first halo update, the fused
-        // kernel recomputes neighbours from their previous value: make the previous values ghost-consistent first
-        evp_launch_cgrid_phase(A, 9, CF_S12U, S.stream);
-        XCHG(P.cur[4], P.cur[4]);
-        // (ghost cells of eliminated land blocks: zero in both buffers; no ice cell reads them before the first exchange)
-        evp_launch_cgrid_zero_cells(A, CG.zero_cells, CG.n_zero, S.stream);
-        if (int rc = P.sync(PP_S12)) return rc;
-    }
-    for (int k = 0; k < ndte - nres; ++k) {
-        const int last = (k == ndte - 1);
-        P.at_current(A);
-        if (one && !(first && k == 0)) {
-            EvpCgOne T{CG.one.tab, CG.one.tiles, CG.one.ntiles, CG.one.per_xcd, CG.one.ox, CG.one.oy, one_xcd_on() ? 0 : 1,
-                       P.cur[0], P.cur[1], P.cur[2], P.cur[3], CG.gslab, CG.inslab, S.n, CG.one.prof, geo_derived() ? CG.gmask : nullptr};
-            P.aim(A, PP_ALL);
-            if (CG.one.nitems > 0 && T.gmask && !(last && !strip_last_on())) {
-                // the interior of the blocks marched, the windows along their edges as before: both read the previous
-                // subcycle's buffers only and own disjoint cells
-                EvpCgOne E = T;
-                E.tab = CG.one.tab_e; E.tiles = CG.one.tiles_e; E.ntiles = CG.one.ntiles_e; E.per_xcd = (CG.one.ntiles_e + 7) / 8;
-                E.ox = CG.one.ex; E.oy = CG.one.ey;
-                E.prof = nullptr;
-                // (the edge windows on the second stream beside the marched kernel: measured no gain, 565 us against 552 -- a
-                // 1024-thread workgroup does not fit beside the marched kernel's waves on a CU anyway)
-                // windows of 32 x 8 ride in the marched kernel's launch; other shapes (A/B) get a launch of their own behind it
-                const bool ride = E.ox == 32 && E.oy == 8 && strip_ride_on();
-                evp_launch_cgrid_strip(A, T, strip_args(P, T.gmask).Z, ride ? &E : nullptr, fast, last, S.stream);
-                if (!ride && E.ntiles > 0) evp_launch_cgrid_one(A, E, fast, last, S.stream);
-            } else if (T.ntiles > 0) {
-                evp_launch_cgrid_one(A, T, fast, last, S.stream);
-            }
-            P.swap(PP_ALL);
-            ++ran.one;
-            continue;
-        }
-        if (march && !(first && k == 0)) {
-            // the rectangles marched on the second stream, every other interior cell by the frame variants of the three fused kernels
-            // here, with the exchanges of the fused schedule at their points: both read the previous subcycle's buffers, own disjoint
-            // cells of this subcycle's, and meet again before the buffers swap
-            const StripArgs Z = strip_args(P, CG.gmask);
-            const CellLists &Q = CG.fr;
-            EvpCgFrame Fr{Q.cells, {Q.wg[0], Q.wg[1], Q.wg[2]}, {Q.nwg[0], Q.nwg[1], Q.nwg[2]}, P.cur[0], P.cur[1], P.cur[2], P.cur[3],
-                          Q.scr[0], Q.scr[1], Q.scr[2], Q.scr[3]};
-            P.aim(A, PP_ALL);
-            // (the frame's first launch goes ahead of the marched kernel, which fills the chip: DESIGN.md section 7)
-            HIPC(hipEventRecord(CG.side.fork, S.stream));
-            evp_launch_cgrid_frame(A, Fr, 0, fast, last, S.stream);
-            HIPC(hipStreamWaitEvent(CG.side.st, CG.side.fork, 0));
-            evp_launch_cgrid_strip(A, Z.T, Z.Z, nullptr, fast, last, CG.side.st);
-            HIPC(hipEventRecord(CG.side.join, CG.side.st));
-            XCHG(A.f[CF_SHEARU], A.f[CF_SHEARU]);
-            evp_launch_cgrid_frame(A, Fr, 1, fast, last, S.stream);
-            XCHG(A.f[CF_ETA], A.f[CF_ZETA]);
-            XCHG(A.f[CF_SP], A.f[CF_SM]);
-            evp_launch_cgrid_frame(A, Fr, 2, fast, last, S.stream);
-            XCHG(A.f[CF_S12U], A.f[CF_S12U]);
-            XCHG(A.f[CF_UE], A.f[CF_VN]);
-            HIPC(hipStreamWaitEvent(S.stream, CG.side.join, 0));
-            P.swap(PP_ALL);
-            ++ran.march;
-            continue;
-        }
-        if (first && k == 0 && CG.avg_strength) {
-            // (only with cg_one for the rest: fused_schedule) the first subcycle as the five launches, stress12U in place
-            evp_launch_cgrid_phase(A, 0, 1, S.stream);
-            evp_launch_cgrid_phase(A, 6, 1, S.stream);
-            evp_launch_cgrid_phase(A, 1, 1, S.stream);
-            first_exchange_copies_everything(A, {CF_SP, CF_SM});
-            evp_launch_cgrid_phase(A, 2, 1, S.stream);
-            first_exchange_copies_everything(A, {CF_S12U});
-            evp_launch_cgrid_phase(A, 3, 1, S.stream);
-            if (int rc = P.sync(PP_ALL)) return rc;
-            continue;
-        }
-        if (first && k == 0) {
-            evp_launch_cgrid_phase(A, 0, 1, S.stream);
-            evp_launch_cgrid_phase(A, 6, 1, S.stream);
-        } else {
-            evp_launch_cgrid_phase(A, 7, last, S.stream);
-        }
-        XCHG(A.f[CF_SHEARU], A.f[CF_SHEARU]);
-        evp_launch_cgrid_phase(A, 10, last, S.stream);
-        if (first && k == 0) first_exchange_copies_everything(A, {CF_SP, CF_SM});   // (stress12U: above, before the loop)
-        XCHG(A.f[CF_ETA], A.f[CF_ZETA]);         // (zetax2T is stored in the last subcycle only; harmless before)
-        XCHG(A.f[CF_SP], A.f[CF_SM]);
-        P.aim(A, PP_S12);
-        evp_launch_cgrid_phase(A, CG.fast ? 11 : 8, last, S.stream);
-        XCHG(A.f[CF_S12U], A.f[CF_S12U]);
-        XCHG(A.f[CF_UE], A.f[CF_VN]);
-        P.swap(PP_S12);
-        if ((one || march) && first && k == 0)          // the four others ping-pong from the next subcycle on
-            if (int rc = P.sync(PP_FOUR)) return rc;
-    }
-    P.at_current(A);
-    ran.swapped = P.swapped;
-    if (nres > 0)
-        if (int rc = res_launch(A, nres, false, P)) return rc;
-    evp_launch_cgrid_phase(A, 4, 1, S.stream);
-    XCHG(A.f[CF_UN], A.f[CF_VE]);
-    XCHG(A.f[CF_UU], A.f[CF_VU]);
-    return 0;
-}
-
-static int enqueue_phases_resident(const EvpCgrid &A, int ndte, bool first, int nres, Ran &ran)
-{
-    if (ndte > nres)
-        if (int rc = enqueue_phases(A, ndte - nres, first)) return rc;
-    ran = Ran{};       // (the five phases run in place, the resident launch leaves its result in both allocations)
-    if (int rc = res_launch(A, nres, false, PingPong())) return rc;
-    fold({{A.f[CF_SHEARU], 1, false}, {A.f[CF_S12U], 1, false}});
-    fold({{A.f[CF_ZETA], 0, false}, {A.f[CF_ETA], 0, false}, {A.f[CF_SP], 0, false}, {A.f[CF_SM], 0, false}});
-    fold({{A.f[CF_UE], 2, true}, {A.f[CF_VN], 3, true}});
-    evp_launch_cgrid_phase(A, 4, 1, S.stream);
-    fold({{A.f[CF_UN], 3, true}, {A.f[CF_VE], 2, true}, {A.f[CF_UU], 1, true}, {A.f[CF_VU], 1, true}});
-    return 0;
-}
 
 // Fold lists (halo_plan.cpp: build_fold_list) on the device
 static int build_fold_lists()
@@ -810,15 +246,14 @@ static int need_alt()
         if (!CG.alt[q] && zeros(CG.alt[q], field_len())) return -1;
     return 0;
 }
-static int upload_items(const std::vector<int32_t> &items, int ex, int ey, int lengths, int seg, long cells)
+static int upload_items(MarchItems &M, const std::vector<int32_t> &items, int ex, int ey, int lengths, int seg, long cells)
 {
-    CGridState::One &O = CG.one;
-    O.nitems = (int)(items.size() / 6);
-    O.ex = ex; O.ey = ey;
-    O.strip_len = lengths;
-    O.strip_seg = seg;
-    O.strip_cells = cells;
-    return CG.mem.upload(O.items, items);
+    M.nitems = (int)(items.size() / 6);
+    M.ex = ex; M.ey = ey;
+    M.len = lengths;
+    M.seg = seg;
+    M.cells = cells;
+    return CG.mem.upload(M.items, items);
 }
 // the plan's per-cell bits and workgroup lists of nlev levels, nscr scratch arrays, the second buffers, the side stream
 static int upload_cell_lists(CellLists &Q, const std::vector<uint8_t> &cells, const std::vector<int32_t> *wg, int nlev, int nscr, long ncells)
@@ -958,7 +393,7 @@ static int build_one_tables(const double *const *static23)
                 tab_e.clear();
                 if (upload_cell_lists(CG.fr, FP.cells, FP.wg, 3, 4, FP.rest_cells)) return -1;
             }
-            if (upload_items(items, EX, EY, lengths ? 1 : 0, seg, zcells)) return -1;
+            if (upload_items(O.zone, items, EX, EY, lengths ? 1 : 0, seg, zcells)) return -1;
             O.ntiles_e = (int)(tiles_e.size() / 4);
             if (O.ntiles_e && (CG.mem.upload(O.tiles_e, tiles_e) || CG.mem.upload(O.tab_e, tab_e))) return -1;
         }
@@ -975,7 +410,7 @@ static int build_march_fold_tables(const double *const *static23)
 {
     const HaloPlan &P = S.plan;
     CGridState::MarchFold &Q = CG.mf;
-    const int want = march_fold_wanted_here();
+    const int want = cg_march_fold_wanted(sched_switches(), remote());    // (the rule the chooser applies: it reads the switches alone)
     if (!want) return 0;
     if (!strip_offsets_fit()) {
         Q.why = "the marched kernel's 32-bit offsets do not span the tables";
@@ -1021,7 +456,7 @@ static int build_march_fold_tables(const double *const *static23)
     if (gm.empty()) return fail(-4, "C-grid EVP: fold-band plan: %s", w.c_str());
     // (the sixth scratch array, deltaU, only where visc_method = avg_strength may run this schedule)
     if (CG.mem.upload(Q.gmask, gm) || upload_cell_lists(Q.rest, FP.cells, FP.wg, 5, march_avgs_switch() ? 6 : 5, FP.rest_cells)) return -1;
-    if (upload_items(FP.items, EX, EY, FP.lengths, FP.seg, FP.zone_cells)) return -1;
+    if (upload_items(CG.one.zone, FP.items, EX, EY, FP.lengths, FP.seg, FP.zone_cells)) return -1;
     Q.band_rows = FP.band_rows;
     Q.frame_cells = FP.frame_cells;
     return 0;
@@ -1048,10 +483,7 @@ static int build_march_frame_tables(const double *const *static23)
     if (rc < 0) return fail(-4, "C-grid EVP: %s", Q.why.c_str());
     if (rc == 0) return 0;
     if (strip_switch() == ENV_UNSET && (2 * FP.zone_cells < interior_cells(d) || FP.zone_cells < STRIP_MIN_CELLS)) return 0;
-    if (upload_cell_lists(Q.rest, FP.cells, FP.wg, 5, 6, FP.rest_cells) || CG.mem.upload(Q.items, FP.items)) return -1;
-    Q.nitems = (int)(FP.items.size() / 6);
-    Q.strip_len = FP.lengths;
-    Q.strip_cells = FP.zone_cells;
+    if (upload_cell_lists(Q.rest, FP.cells, FP.wg, 5, 6, FP.rest_cells) || upload_items(Q.zone, FP.items, EX, EY, FP.lengths, FP.seg, FP.zone_cells)) return -1;
     Q.frame_cells = FP.frame_cells;
     return 0;
 }
@@ -1201,31 +633,7 @@ static int build_res_tables(const double *const *static23)
     return 0;
 }
 
-// eligible in this call: one rank, no fold (either visc_method, classic or revised EVP), the default-configuration shortcuts hold on every ice cell, the static
-// identities hold (the kernel takes -1 for a boundary ratio away from a coast), every window co-resident
-// per_call (may be NULL): set when what stands in the way holds for THIS call only (the call's masks, operands, state)
-static bool res_eligible(std::string *why = nullptr, bool *per_call = nullptr)
-{
-    auto no = [&](const char *w) { if (why) *why = w; return false; };
-    const CGridState::Res &Q = CG.res;
-    if (per_call) *per_call = false;
-    if (CG.tripole) {
-        // a u-fold on one rank: the kernel's FOLD variant (the first subcycle of a call runs as the five phases)
-        if (CG.tfold || remote()) return no("a T-fold, or several ranks on a tripole grid");
-    } else if (!CG.one.tab || remote() || !fused_schedule() || !one_launch()) {
-        return no("several ranks, a block too small, or the one-launch schedule switched off");
-    }
-    if (!Q.tab) return no(Q.why.empty() ? "tables not built" : Q.why.c_str());
-    if (CG.tripole ? !Q.gmask : !geo_derived()) return no("a start-up identity of the static arrays does not hold");
-    if (per_call) *per_call = true;
-    if (!Q.pairs_state_ok) return no("ghost cells outside the domain that the kernel treats as one position hold different state");
-    if (Q.n_live < 1) return no("no window holds ice");
-    // (seabed stress, waterx / watery other than the ocean currents, rheofact != 1 on some ice cell: the kernel's SLOW variant, round 6)
-    if ((long)(res_cull() ? Q.n_live : Q.ntiles) > Q.cap4[(CG.avg_strength ? 1 : 0) | (S.prm.revp != 0.0 ? 2 : 0) | (CG.fast ? 0 : 4)]) return no("more windows with ice than can be resident at once");
-    return true;
-}
-
-static int res_launch(const EvpCgrid &A, int nsub, bool dry, const PingPong &P)
+int res_launch(const EvpCgrid &A, int nsub, bool dry, const PingPong &P)
 {
     CGridState::Res &Q = CG.res;
     EvpCgRes R{};
@@ -1262,7 +670,7 @@ static int res_launch(const EvpCgrid &A, int nsub, bool dry, const PingPong &P)
     return 0;
 }
 
-static int res_check_error()
+int res_check_error()
 {
     CGridState::Res &Q = CG.res;
     if (!Q.launched) return 0;
@@ -1278,105 +686,8 @@ static int res_check_error()
     return 0;
 }
 
-// First eligible call: a dry run (the same work on the uploaded state, nothing written back) proves that every window is
-// resident and gives the steady-state cost per subcycle.  CICE_EVP_HIP_CGRID_RESIDENT=0 / 1 forces the verdict.
-static int res_decide(const EvpCgrid &A)
-{
-    CGridState::Res &Q = CG.res;
-    if (Q.mode >= 0) return 0;
-    const int want = resident_switch();
-    std::string why;
-    bool per_call = false;
-    if (want == 0 || !res_eligible(&why, &per_call)) {
-        // forced on: only what can never change (tables, geometry, rank layout) is an error; a condition of this call's masks,
-        // operands or state is a fall-back for this call, as it is once the kernel has run (res_subcycles)
-        if (want == 1 && !per_call) return fail(-6, "resident C-grid kernel requested but not applicable: %s", why.c_str());
-        if (verbose() && want != 0) std::fprintf(stderr, "[cice_evp_hip] C grid: on-chip resident kernel not used: %s\n", why.c_str());
-        // (per-call conditions -- visc_method, the shortcuts -- may hold in a later call: stay undecided unless switched off)
-        if (want == 0) Q.mode = 0;
-        return 0;
-    }
-    if (want == 1) {       // forced on: no probe launches (profiles see real launches only); a window that is not resident shows at the next sync
-        Q.mode = 1;
-        return 0;
-    }
-    const PingPong P;
-    const int nshort = 8, nlong = 40;
-    float tl[2] = {0, 0}, ms = 0;
-    for (int rep = 0; rep < 3; ++rep) {
-        const int np = rep == 2 ? nlong : nshort;
-        HIPC(hipEventRecord(S.ev2, S.stream));
-        if (int rc = res_launch(A, np, true, P)) return rc;
-        HIPC(hipEventRecord(S.ev3, S.stream));
-        HIPC(hipStreamSynchronize(S.stream));
-        if (res_check_error()) {
-            if (want == 1) return -7;
-            g_err.clear();
-            Q.mode = 0;
-            if (verbose()) std::fprintf(stderr, "[cice_evp_hip] C grid: on-chip resident kernel failed its probe, not used\n");
-            return 0;
-        }
-        HIPC(hipEventElapsedTime(&ms, S.ev2, S.ev3));
-        if (rep >= 1) tl[rep - 1] = ms;
-    }
-    Q.t_probe_ms = (tl[1] - tl[0]) / (nlong - nshort);
-    Q.mode = 1;
-    return 0;
-}
-
-static int res_subcycles(int ndte, bool first)
-{
-    if (CG.res.mode != 1 || (!CG.tripole && !one_launch()) || !res_eligible()) return 0;
-    const int n = ndte - (first ? 1 : 0);
-    return (n >= 3 && n <= 4000) ? n : 0;
-}
-
 int finish_upload(int32_t visc_method);
 
-std::string cgrid_schedule()
-{
-    char buf[400];
-    if (CG.geo && CG.uploaded && march_ranks()) {
-        std::snprintf(buf, sizeof buf, "C grid: zone marched + frame (%ld cells in %d items beside %ld frame cells, fused chain and its exchanges)",
-                      CG.one.strip_cells, CG.one.nitems, CG.fr.ncells);
-        return buf;
-    }
-    if (CG.geo && CG.uploaded && march_frame_phases()) {
-        // (the text of march_ranks()' schedule up to the bracket: the same counters report it)
-        std::snprintf(buf, sizeof buf, "C grid: zone marched + frame (%ld cells in %d items beside %ld rest cells, %ld of them frame cells, five phases "
-                      "advance the frame with their exchanges, avg_strength)", CG.mf.strip_cells, CG.mf.nitems, CG.mf.rest.ncells, CG.mf.frame_cells);
-        return buf;
-    }
-    const char *avgs = CG.avg_strength ? ", avg_strength" : "";
-    if (CG.geo && CG.uploaded && march_fold() && remote()) {
-        char fx[120] = "";
-        if (fold_exchange())
-            std::snprintf(fx, sizeof fx, " + fold exchange, fold rows on %d ranks (%d staging slots here)", S.plan.cg_fold_ranks, S.plan.cg_tail);
-        std::snprintf(buf, sizeof buf, "C grid: marched zone + fold band + frame, %d rows (%ld cells in %d items beside %ld rest cells, %ld of them frame "
-                      "cells, five phases with their exchanges and fold steps%s)%s", CG.mf.band_rows, CG.one.strip_cells, CG.one.nitems, CG.mf.rest.ncells,
-                      CG.mf.frame_cells, avgs, fx);
-        return buf;
-    }
-    if (CG.geo && CG.uploaded && march_fold()) {
-        std::snprintf(buf, sizeof buf, "C grid: marched zone + fold band, %d rows (%ld cells in %d items beside %ld cells of the band and the block edges, "
-                      "five phases and their fold steps%s)", CG.mf.band_rows, CG.one.strip_cells, CG.one.nitems, CG.mf.rest.ncells, avgs);
-        return buf;
-    }
-    if (CG.geo && CG.tripole && march_fold_wanted() == 1 && !(remote() && march_fold())) {
-        // asked for and not in use: say why
-        const char *w = (remote() && march_fold_ranks_wanted() != 1) ? "several ranks" : !CG.mf.rest.cells ? CG.mf.why.c_str() :
-                        !(CG.uploaded && CG.avg_strength) ? "" : !march_avgs_switch() ? "visc_method = avg_strength" :
-                        !CG.mf.rest.scr[5] ? "visc_method = avg_strength, and its switch was not set when the geometry was" : "";
-        if (*w) {
-            std::snprintf(buf, sizeof buf, "C grid: five phases + fold steps (marched zone + fold band not in use: %s)", w);
-            return buf;
-        }
-    }
-    if (!CG.geo || !fold_exchange()) return "";
-    std::snprintf(buf, sizeof buf, "C grid: five phases + fold exchange, fold rows on %d ranks (%d staging slots here)", S.plan.cg_fold_ranks,
-                  S.plan.cg_tail);
-    return buf;
-}
 
 }  // namespace evp_host
 
@@ -1531,11 +842,7 @@ int finish_upload(int32_t visc_method)
         EvpCgrid A;
         fill(A);
         evp_launch_cgrid_umask(A, CG.umaskd, 0, S.stream);
-        if (fold_exchange()) {
-            if (int rc = cgrid_fold_exchange(CG.umaskd, CG.umaskd, field_len())) return rc;
-        } else if (int rc = halo_remote_pair(CG.umaskd, CG.umaskd)) {
-            return rc;
-        }
+        if (int rc = exchange(CG.umaskd, CG.umaskd, false)) return rc;
         evp_launch_cgrid_umask(A, CG.umaskd, 1, S.stream);
     }
     if (visc_method == 1) {
@@ -1565,70 +872,6 @@ int finish_upload(int32_t visc_method)
 }  // namespace evp_host
 
 extern "C" {
-
-int cice_evp_hip_cgrid_subcycle(int32_t ndte)
-{
-    if (!CG.uploaded) return fail(-1, "C-grid EVP: nothing uploaded");
-    if (ndte < 0) return fail(-1, "ndte < 0");
-    if (ndte == 0) return 0;
-    EvpCgrid A;
-    fill(A);
-    const bool fused = fused_schedule();
-    if (int rc = res_check_error()) return rc;
-    if (int rc = res_decide(A)) return rc;       // (first call: the on-chip resident kernel's probe; refuses loudly when forced on a rank it cannot serve)
-    const int nres = (fused || CG.tripole) ? res_subcycles(ndte, CG.first) : 0;
-    const bool mfold = nres == 0 && (march_fold() || march_frame_phases());
-    const bool mf_sync = mfold && !CG.first && !CG.mf.synced;
-    Ran ran;
-    auto enqueue = [&]() -> int {
-        if (fused) return enqueue_fused(A, ndte, CG.first, nres, ran);
-        if (nres > 0) return enqueue_phases_resident(A, ndte, CG.first, nres, ran);
-        if (mfold) return enqueue_march_fold(A, ndte, CG.first, mf_sync, ran);
-        return enqueue_phases(A, ndte, CG.first);      // (in place)
-    };
-    HIPC(hipEventRecord(S.ev0, S.stream));
-    // (the resident launch carries a fresh epoch in its arguments: enqueued eagerly, with the few launches around it)
-    if (nres == 0 && S.use_graph && (!remote() || S.direct.on)) {     // RCCL point-to-point is enqueued eagerly (as the B-grid loop does)
-        GraphKey key;
-        key.ndte = ndte; key.avg_strength = CG.avg_strength; key.in_alt = CG.in_alt;
-        key.first = CG.first; key.fused = fused; key.fast = CG.fast;
-        key.one = fused && one_launch(); key.geo = geo_derived(); key.march = fused && march_ranks();
-        key.mfold = mfold; key.mfold_serial = mfold && march_fold_serial(); key.mfold_sync = mf_sync;
-        key.mfold_ranks = mfold && remote();
-        auto it = CG.graphs.find(key);
-        if (it == CG.graphs.end()) {
-            hipGraph_t gr = nullptr;
-            hipGraphExec_t ex = nullptr;
-            HIPC(hipStreamBeginCapture(S.stream, hipStreamCaptureModeThreadLocal));
-            const int rc = enqueue();
-            HIPC(hipStreamEndCapture(S.stream, &gr));
-            if (rc) return rc;
-            HIPC(hipGraphInstantiate(&ex, gr, nullptr, nullptr, 0));
-            (void)hipGraphDestroy(gr);
-            it = CG.graphs.emplace(key, CGridState::Captured{ex, ran}).first;
-        }
-        HIPC(hipGraphLaunch(it->second.exec, S.stream));
-        ran = it->second.ran;
-    } else if (enqueue()) {
-        return -1;
-    }
-    CG.mf.synced = mfold;
-    // the current arrays are where the schedule left them
-    for (int q = 0; q < 5; ++q)
-        if (ran.swapped >> q & 1u) std::swap(CG.f[PP_FIELDS[q]], CG.alt[q]);
-    CG.in_alt ^= ran.swapped;
-    HIPC(hipEventRecord(S.ev1, S.stream));
-    HIPC(hipGetLastError());
-    CG.t_one = ran.one;
-    CG.t_march = ran.march;
-    CG.t_march_phases = ran.march_phases;
-    CG.t_mfold = ran.mfold;
-    CG.t_mfold_ranks = ran.mfold_ranks;
-    CG.res.last_nsub = nres;
-    CG.first = false;
-    CG.t_nsub = ndte;
-    return 0;
-}
 
 int cice_evp_hip_cgrid_download(double *const *fields19)
 {
@@ -1730,11 +973,7 @@ static int tail_halo_pair(double *a, int loca, double *b, int locb)
     evp_launch_cgrid_phase(A, 9, CF_UE, S.stream);
     evp_launch_cgrid_phase(A, 9, CF_VN, S.stream);
     evp_launch_tail_zero_cells(a, b, CG.zero_cells, CG.n_zero, S.stream);
-    if (fold_exchange()) {
-        if (int rc = cgrid_fold_exchange(a, b, field_len())) return rc;
-    } else if (remote()) {
-        if (int rc = halo_remote_pair(a, b, false)) return rc;
-    }
+    if (int rc = exchange(a, b, false)) return rc;
     fold({{a, loca, true}, {b, locb, true}});
     HIPC(hipGetLastError());
     return 0;
@@ -2027,16 +1266,12 @@ int cice_evp_hip_cgrid_prep(const cice_evp_hip_prep_params *pp, const double *co
     evp_launch_cgrid_phase(A, 9, CF_UE, S.stream);
     evp_launch_cgrid_phase(A, 9, CF_VN, S.stream);
     // (never masked: the halo mask is built from this call's iceTmask)
-    auto exchange = [&](double *a, double *b) -> int {
-        if (fold_exchange()) return cgrid_fold_exchange(a, b, field_len());
-        return remote() ? halo_remote_pair(a, b) : 0;
-    };
-    if (int rc = exchange(A.f[CF_UE], A.f[CF_VN])) return rc;
+    if (int rc = exchange(A.f[CF_UE], A.f[CF_VN], false)) return rc;
     fold({{A.f[CF_UE], 2, true}, {A.f[CF_VN], 3, true}});
     evp_launch_cgrid_phase(A, 6, 1, S.stream);
     evp_launch_cgrid_phase(A, 4, 1, S.stream);
-    if (int rc = exchange(A.f[CF_UN], A.f[CF_VE])) return rc;
-    if (int rc = exchange(A.f[CF_UU], A.f[CF_VU])) return rc;
+    if (int rc = exchange(A.f[CF_UN], A.f[CF_VE], false)) return rc;
+    if (int rc = exchange(A.f[CF_UU], A.f[CF_VU], false)) return rc;
     fold({{A.f[CF_UN], 3, true}, {A.f[CF_VE], 2, true}, {A.f[CF_UU], 1, true}, {A.f[CF_VU], 1, true}});
     HIPC(hipEventRecord(S.ev1, S.stream));
     Q.h4.resize(4 * S.n);
@@ -2189,41 +1424,44 @@ int cice_evp_hip_debug_call_flags(uint32_t *out, int32_t n)
 int cice_evp_hip_cgrid_timings(double *out, int32_t n)
 {
     if (!out || n < 2) return fail(-1, "need room for 2 values");
+    const int *ran = CG.last.count;              // the last call's subcycles by what ran them
+    const MarchItems &Z = CG.one.zone;
     out[0] = CG.t_loop_ms;
     out[1] = (double)CG.t_nsub;
     if (n >= 3) out[2] = CG.prep.t_ms;           // device time of the last cice_evp_hip_cgrid_prep (kernels, without the copies)
-    if (n >= 4) out[3] = (double)CG.t_one;       // subcycles of the last call run as one launch each
+    if (n >= 4) out[3] = (double)ran[CG_ONE];    // subcycles of the last call run as one launch each
     if (n >= 5) out[4] = geo_derived() ? 1.0 : 0.0;   // ... with 15 of the 23 static arrays derived in the kernel
     if (n >= 6) out[5] = (double)CG.res.last_nsub;    // subcycles of the last call inside ONE launch of the on-chip resident kernel
     if (n >= 7) out[6] = CG.res.t_probe_ms;           // ... and what its probe measured per subcycle, ms (-1: no probe ran)
     if (n >= 8) out[7] = (double)CG.res.fallbacks;    // cice_evp_hip_cgrid_run calls repeated without it after one of its waits gave up
     if (n >= 9) out[8] = (double)CG.res.n_live;       // windows of the resident kernel that hold ice in this call (only they run) ...
     if (n >= 10) out[9] = (double)CG.res.ntiles;      // ... of so many
-    if (n >= 11) out[10] = (double)CG.one.nitems;     // the one-launch schedule's marched kernel (cg_strip): work items (0: not in use) ...
-    if (n >= 12) out[11] = (double)CG.one.strip_cells;   // ... the cells it owns ...
+    if (n >= 11) out[10] = (double)Z.nitems;          // the one-launch schedule's marched kernel (cg_strip): work items (0: not in use) ...
+    if (n >= 12) out[11] = (double)Z.cells;           // ... the cells it owns ...
     if (n >= 13) out[12] = (double)CG.one.ntiles_e;   // ... and the windows cg_one keeps beside it
-    if (n >= 14) out[13] = (double)CG.one.strip_seg;  // ... rows per segment
-    if (n >= 15) out[14] = (double)CG.one.strip_len;  // ... 1: it forms six of the eight lengths from dxN, dyE
+    if (n >= 14) out[13] = (double)Z.seg;             // ... rows per segment
+    if (n >= 15) out[14] = (double)Z.len;             // ... 1: it forms six of the eight lengths from dxN, dyE
     if (n >= 16) out[15] = fold_exchange() ? 1.0 : 0.0;            // tripole: the blocks next to the fold on several ranks (fold exchange)
     if (n >= 17) out[16] = CG.tripole ? (double)S.plan.cg_fold_ranks : 0.0;   // ... on so many ranks
     if (n >= 18) out[17] = fold_exchange() ? (double)S.plan.cg_tail : 0.0;    // ... staging slots of this rank
     if (n >= 20) {
-        out[18] = (double)CG.t_march;                 // subcycles of the last call that ran as "zone marched + frame" (several ranks)
+        out[18] = (double)(ran[CG_ZONE_FRAME] + ran[CG_ZONE_FRAME_PHASES]);   // subcycles of the last call that ran as "zone marched + frame" (several ranks)
         out[19] = (double)CG.fr.ncells;               // ... and the frame cells of this rank (0: no such plan here)
-        if (CG.t_march_phases > 0) {      // (the five-phase frame plan ran: its frame cells, its own items)
+        if (ran[CG_ZONE_FRAME_PHASES] > 0) {          // (the five-phase frame plan ran: its frame cells, its own items)
+            const MarchItems &M = CG.mf.zone;
             out[19] = (double)CG.mf.frame_cells;
-            out[10] = (double)CG.mf.nitems; out[11] = (double)CG.mf.strip_cells; out[14] = (double)CG.mf.strip_len;
+            out[10] = (double)M.nitems; out[11] = (double)M.cells; out[14] = (double)M.len;
         }
     }
     if (n >= 23) {
-        out[20] = (double)CG.t_mfold;                 // subcycles of the last call that ran as "marched zone + fold band" (tripole grids, one rank)
+        out[20] = (double)ran[CG_MARCH_FOLD];         // subcycles of the last call that ran as "marched zone + fold band" (tripole grids, one rank)
         out[21] = (double)CG.mf.band_rows;            // ... rows from the zone's top row to the fold (0: no such plan here)
         out[22] = (double)CG.mf.rest.ncells;               // ... and the cells the five list-driven phase kernels advance
     }
     if (n >= 26) {
-        out[23] = (double)CG.t_mfold_ranks;           // subcycles of the last call that ran as "marched zone + fold band + frame" (tripole grids, several ranks)
+        out[23] = (double)ran[CG_MARCH_FOLD_RANKS];   // subcycles of the last call that ran as "marched zone + fold band + frame" (tripole grids, several ranks)
         out[24] = (double)CG.mf.frame_cells;          // ... the frame cells among the rest cells (sent to another rank, or with a ghost image here)
-        out[25] = (CG.t_mfold_ranks > 0 && fold_exchange()) ? 1.0 : 0.0;   // ... 1: with the fold exchange (the fold rows on several ranks)
+        out[25] = (ran[CG_MARCH_FOLD_RANKS] > 0 && fold_exchange()) ? 1.0 : 0.0;   // ... 1: with the fold exchange (the fold rows on several ranks)
     }
     if (n >= 27) out[26] = (double)CG.in_alt;         // bit q: PP_FIELDS[q] is in its second allocation now (where the last call left it)
     return 0;

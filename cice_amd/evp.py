@@ -61,7 +61,7 @@ TEST_EXPORTS = [
     "cice_evp_hip_peer_plan", "cice_evp_hip_peer_signs", "cice_evp_hip_center_plan", "cice_evp_hip_stress_plan",
     "cice_evp_hip_fold_split_plan", "cice_evp_hip_plan_flags", "cice_evp_hip_fold_images_plan", "cice_evp_hip_cgrid_fold_xplan",
     "cice_evp_hip_cgrid_fold_xpeers", "cice_evp_hip_stress_tfold_xplan", "cice_evp_hip_plan_dump", "cice_evp_hip_rim_plan", "cice_evp_hip_debug_range_math",
-    "cice_evp_hip_debug_res2_choose", "cice_evp_hip_debug_res2_built", "cice_evp_hip_debug_call_flags",
+    "cice_evp_hip_debug_res2_choose", "cice_evp_hip_debug_res2_built", "cice_evp_hip_debug_call_flags", "cice_evp_hip_debug_cgrid_choose",
 ]
 # the B grid's flag word (cice_amd/csrc/evp_device.h: EVP_F_*) and the C grid's (evp_cgrid.hip: cg_call_setup), as call_flags() reads them
 F_METRICS, F_WATER_IS_OCN, F_TBU_ZERO, F_DXHY_ARRAY = 1, 2, 4, 32

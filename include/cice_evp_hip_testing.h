@@ -181,6 +181,13 @@ int cice_evp_hip_rim_plan(int32_t ni, int32_t nj, int32_t cyclic_ew, int32_t cyc
    14 the rim-wave tables are valid, 15 - 17 the switches RES_COOP / RES_LEAN / RES_RIMU.  chosen[e] bit 0 strict, 1 remote, 2 coop,
    3 lean, 4 rimu, 5 the launch binds rim_plan's tables; logw << 8; (cap + 1) << 16.                                              */
 int cice_evp_hip_debug_res2_choose(int64_t n, const uint32_t *facts, int32_t cap, int32_t logw, int32_t hooks, uint32_t *chosen);
+/* Host-only: which schedule the C-grid subcycle loop runs (csrc/cgrid_schedule.cpp: cg_choose_schedule), for n rows of 26 facts each
+   in the order of CgSchedFacts (csrc/cgrid_schedule.h): one_tab remote tripole tfold geo frame_plan one_items rest_plan rest_items
+   by_size rest_scr5 | avg_strength fast | res_mode res_ok | the switches ONE FUSED MARCH_RANKS MARCH_FOLD MARCH_FOLD_RANKS
+   MARCH_AVG_STRENGTH MARCH_FOLD_SERIAL STRIP_LAST (the two tri-states: 0, 1 or INT32_MIN = not set) | ndte first synced.
+   out: n rows of 7, {kind, nres, fast, geo, serial, strip_last, sync}; kind 0 five phases, 1 three fused launches, 2 cg_one, 3 zone
+   marched + frame, 4 ... on the five phases, 5 marched zone + fold band, 6 ... + frame, 7 five phases + cg_res FOLD.            */
+int cice_evp_hip_debug_cgrid_choose(int64_t n, const int32_t *facts, int32_t *out);
 /* Host-only: 1 where this build holds that instantiation of the kernel (the table of csrc/evp_resident2.hip), else 0. */
 int cice_evp_hip_debug_res2_built(int32_t strict, int32_t cap, int32_t logw, int32_t remote, int32_t coop, int32_t lean, int32_t rimu);
 int cice_evp_hip_halo_plan(int32_t *counts4, int32_t *local_dst, int32_t *local_src,

@@ -3,7 +3,7 @@ import; the C-grid twin of tests/evp_call_chain.py): cgrid_set_prep_geometry -> 
 core, None afterwards) -> cgrid_set_tb or no seabed stress -> cgrid_prep_finish -> cgrid_subcycle -> cgrid_download ->
 cgrid_deformations -> cgrid_dyn_finish (N and E) -> cgrid_tail -> cgrid_dyn_finish_u -> cgrid_strocn_t -> cgrid_download again.
 Every schedule of the loop leaves uvelE, vvelN, stresspT, stressmT and stress12U in one of two allocations each
-(evp_host_cgrid.cpp: PingPong, Ran::swapped); every call after the loop, and the next cgrid_prep without a state, reads them where
+(evp_host_cgrid.h: PingPong, Ran::swapped); every call after the loop, and the next cgrid_prep without a state, reads them where
 CG.f[...] points at that moment.  run_fixture_call / run_synth_call / run_split_calls run the chain on a core whose schedule the caller forced (CG_PATHS, set_cg_path) and
 compares every stage with the reference's fixture arrays or with the oracle's chain (oracle_post, SynthCg.oracle_call), bit for bit on
 every cell, every message starting with the stage; assert_cg_path_ran is the evidence that the named schedule did the work and that
@@ -89,13 +89,13 @@ def strip_last(path):
 
 
 def resident_subcycles(n, first):
-    """cg_res takes every subcycle of a call but the first after an upload, from three on (evp_host_cgrid.cpp: res_subcycles)."""
+    """cg_res takes every subcycle of a call but the first after an upload, from three on (cgrid_schedule.cpp: res_subcycles)."""
     m = n - (1 if first else 0)
     return m if m >= 3 else 0
 
 
 def predicted_swaps(path, n, first):
-    """The bits of in_alt a call of n subcycles flips -- the host's rules restated (evp_host_cgrid.cpp: enqueue_fused,
+    """The bits of in_alt a call of n subcycles flips -- the host's rules restated (evp_host_cgrid_loop.cpp: enqueue_fused,
     enqueue_march_fold, enqueue_phases_resident), so that a read-out that disagrees is a finding and tests/test_cgrid_call_chain_cpu.py
     can show without a GPU that every ping-pong row's calls end in both allocations.  The first subcycle after an upload: the
     three-launch kernels (stress12U swaps alone), in place with avg_strength and beside a fold."""

@@ -73,7 +73,7 @@ def test_the_seabed_case_has_seabed_stress():
 
 
 def test_swap_rules_restated():
-    """The rules of evp_host_cgrid.cpp as the table has them: the five phases never swap; the three launches swap stress12U alone;
+    """The rules of evp_host_cgrid_loop.cpp as the table has them: the five phases never swap; the three launches swap stress12U alone;
     cg_one / cg_strip swap all five but in the first subcycle after an upload; beside a fold that one runs in place."""
     assert cc.predicted_swaps("five phases", 7, True) == 0 and cc.predicted_swaps("five phases + cg_res FOLD", 7, True) == 0
     assert cc.predicted_swaps("fused, three launches", 7, True) == cc.PP_S12 and cc.predicted_swaps("fused, three launches", 8, False) == 0

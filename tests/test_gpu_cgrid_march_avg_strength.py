@@ -1,5 +1,5 @@
 """GPU (-m gpu): visc_method = avg_strength on the marched split schedules of the C grid, which take it on request
-(CICE_EVP_HIP_CGRID_MARCH_AVG_STRENGTH=1; cice_amd/csrc/evp_host_cgrid.cpp: march_fold) -- here "marched zone + fold band" on tripole /
+(CICE_EVP_HIP_CGRID_MARCH_AVG_STRENGTH=1; cice_amd/csrc/cgrid_schedule.cpp: march_fold) -- here "marched zone + fold band" on tripole /
 tripoleT grids on one rank: cg_strip<AVGS> on the rectangles under the fold band, the list-driven phase kernels on every other interior
 cell, phase 2 forming the corner viscosity from strengthU and the corner's own deltaU (a zone corner's from the scratch copy phase 0
 made).  Built like tests/test_gpu_cgrid_march_tripole.py, whose helpers it uses: forced with CICE_EVP_HIP_CGRID_MARCH_FOLD=1, the

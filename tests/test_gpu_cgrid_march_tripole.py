@@ -1,5 +1,5 @@
 """GPU (-m gpu): the C-grid loop on tripole (u-fold) and tripoleT grids on one rank as "marched zone + fold band"
-(cice_amd/csrc/evp_host_cgrid.cpp: enqueue_march_fold) -- cg_strip on the rectangles under the fold band, list-driven variants of the
+(cice_amd/csrc/evp_host_cgrid_loop.cpp: enqueue_march_fold) -- cg_strip on the rectangles under the fold band, list-driven variants of the
 five phase kernels with the fold steps on every other interior cell.  Forced with CICE_EVP_HIP_CGRID_MARCH_FOLD=1 and the on-chip
 resident kernel off; every array of cgrid_run compared as bits, ghost cells included: with the CPU oracle (u-fold), with the reference
 itself through the prebuilt harness (tripoleT, and u-fold once more), with today's schedule (CICE_EVP_HIP_CGRID_ONE=0) and with the

@@ -1,5 +1,5 @@
 """GPU (-m gpu), run last: visc_method = avg_strength on the marched split schedules of the C grid over several ranks, which take it on
-request (CICE_EVP_HIP_CGRID_MARCH_AVG_STRENGTH=1; cice_amd/csrc/evp_host_cgrid.cpp):
+request (CICE_EVP_HIP_CGRID_MARCH_AVG_STRENGTH=1; cice_amd/csrc/evp_host_cgrid_loop.cpp):
 
   * tripole / tripoleT: "marched zone + fold band + frame" (enqueue_march_fold with the exchanges of the five phases), forced as
     tests/test_gpu_zz_cgrid_march_fold_ranks.py forces it;

@@ -1,5 +1,5 @@
 """GPU (-m gpu), run last: the C-grid subcycle on a tripole / tripoleT grid over several ranks as "marched zone + fold band + frame"
-(cice_amd/csrc/evp_host_cgrid.cpp: enqueue_march_fold; plan: cgrid_plan.cpp, build_cg_march_fold) -- cg_strip on the rectangles under
+(cice_amd/csrc/evp_host_cgrid_loop.cpp: enqueue_march_fold; plan: cgrid_plan.cpp, build_cg_march_fold) -- cg_strip on the rectangles under
 the fold band, the list-driven five phase kernels on every other interior cell, with the five phases' exchanges and fold steps at
 their points.  Several ranks = several processes on the one GPU of the test box (tools/mailbox_2proc.py --cgrid --fold-ghosts
 --expect-marched-fold): every rank's arrays, the ghost row beyond the fold and row NY's east-west ghost cells included, must equal the

@@ -1,5 +1,5 @@
 """GPU (-m gpu), run last: the C-grid subcycle on several ranks with the marched kernel (cg_strip) on the interior of every block
-and the frame variants of the three fused kernels on the block edges ("zone marched + frame": cice_amd/csrc/evp_host_cgrid.cpp,
+and the frame variants of the three fused kernels on the block edges ("zone marched + frame": cice_amd/csrc/evp_host_cgrid_loop.cpp,
 enqueue_fused; plan: halo_plan.cpp, build_cg_frame).  Several ranks = several processes on the one GPU of the test box
 (tools/mailbox_2proc.py --cgrid --expect-marched): every rank's arrays, ghost cells included, must equal the one-rank, one-block run
 of the same state bit for bit, and every rank with rectangles for the marched kernel must have run every subcycle of its last call
